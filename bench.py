@@ -10,7 +10,15 @@ projective config C2 the 8x8 DLT solve of every frame (k_solve_frames) is part o
 RGBA, meshes, destination points) are resident in HBM before the timed region; outputs stay in HBM.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--config C3|C4|C5|C2] [--sources both|shared|distinct]
-                    [--points both|resident|fresh]
+                    [--points both|resident|fresh] [--full] [--dump-outputs DIR]
+
+The plain command measures the headline alone: setup, warmup, the K timed steps of the shared-source, resident-points
+workload, and the result line (`roofline`, `checks`, `cpu_baseline` ... are null / empty).  `--full` adds everything
+described below -- both source layouts, fresh points, the other configs under "also", the output checks, the roofline
+figures and the CPU baseline -- as one invocation.  `--dump-outputs DIR` writes, after the timed steps, a fixed seeded
+sample of the frames the last timed step produced (RGBA as float32, plus the sampled pixel indices, the output windows
+and per-channel sums over every pixel of every frame, float64) as DIR/*.npy, at most ~48 MB; the inputs are the same
+from run to run, so two builds can be compared output for output.
 
 --gpus N > 1 without a torchrun environment re-executes itself under
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...
@@ -22,10 +30,10 @@ Two source layouts are measured:
             carries `hbm_compulsory_frac` (output written once + source read once).
   distinct  the video case (README.md:121-137): every frame has its own 33 MB source (F x 33 MB >> Infinity Cache), where
             the algorithmic bytes ARE HBM bytes: `roofline_distinct`.
-`--points fresh` (part of the default run) times the reference's own loop shape as well: a NEW destination point set goes up
+`--points fresh` (part of the --full run) times the reference's own loop shape as well: a NEW destination point set goes up
 inside every timed step (hg_piecewise_set_frames: host copy into page-locked staging + stream-ordered upload, no GPU wait),
 reported as `roofline_fresh` next to the resident-points line (`value`).
-After each timed region the bytes the timed kernels wrote are checked (untimed): frame 0 against the reference-generated
+With --full, after each timed region the bytes the timed kernels wrote are checked (untimed): frame 0 against the reference-generated
 golden SHA-256 (tests/golden/golden.json; a data fixture, not the oracle), the other frames against frame f mod 4, the
 distinct-source frames through XOR-linearity against the shared-source frames.  `verified` must be true; exit status 3
 otherwise.
@@ -34,7 +42,8 @@ Multi-GPU: frames shard across ranks (independent units, weak scaling: F frames 
 one-off broadcast of the shared source texture over RCCL (scatter + all_gather so each xGMI link carries 1/N of it),
 done before the timed region and reported as `broadcast_ms`.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) incl. `roofline`, `roofline_distinct` and `cpu_baseline`.
+Prints ONE JSON line on rank 0 with `metric`, `value`, `unit`, `ms_per_step` (wall milliseconds of one timed step), ...;
+with --full it also carries `roofline`, `roofline_distinct` and `cpu_baseline`.
 """
 import argparse
 import hashlib
@@ -53,7 +62,7 @@ HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.
 # reference-generated goldens whose k-th warp is frame k of the config's sequence on rank 0 (tests/golden/gen_golden.mjs)
 GOLDEN_CASE = {"C3": "C3_batch_4k", "C2": "C2_projective_1080p", "C5": "C5_batch_8k", "C4": "C4_orbit_4k"}
 HBM_ACHIEVABLE_GBS = 6300.0    # what a streaming kernel reaches on this part (same guide); prices `write_floor_ms`
-# what `python bench.py` measures besides the headline: the other BASELINE.json configs on one GPU (frames per GPU per step), and -- with
+# what `python bench.py --full` measures besides the headline: the other BASELINE.json configs on one GPU (frames per GPU per step), and -- with
 # --gpus N > 1 -- north_star's own sharded lines: C4 batch 512 and C5 batch 64, STRONG scaling, fan-out of the shared source priced in end_to_end
 DEFAULT_ALSO = "C4:64,C5:8,C2:64"
 DEFAULT_ALSO_STRONG = "C4:512:strong,C5:64:strong"
@@ -116,11 +125,12 @@ def launch_command(argv, n):
 
 def also_entries(args, world):
     """[(config, frames or batch, "weak" | "strong")] measured after the headline.  --also given: exactly that list ('none' / '' = nothing).
-    Not given: the plain command (no workload-selecting flag) takes DEFAULT_ALSO, plus DEFAULT_ALSO_STRONG when it runs on more than one GPU."""
+    Not given: --full with no workload-selecting flag takes DEFAULT_ALSO, plus DEFAULT_ALSO_STRONG when it runs on more than one GPU;
+    without --full, nothing."""
     also = args.also
     if also is None:
-        plain = (args.config == "C3" and args.frames == 64 and args.sources == "both" and args.points == "both" and args.scaling == "weak"
-                 and not args.batch and not args.no_verify)
+        plain = (args.full and args.config == "C3" and args.frames == 64 and args.sources in (None, "both") and args.points in (None, "both")
+                 and args.scaling == "weak" and not args.batch and not args.no_verify)
         also = (DEFAULT_ALSO + ("," + DEFAULT_ALSO_STRONG if world > 1 else "")) if plain else ""
     out = []
     for item in [a for a in also.split(",") if a and a != "none"]:
@@ -138,17 +148,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--frames", type=int, default=64, help="frames (destination point sets) per GPU per step")
     ap.add_argument("--config", default="C3", choices=["C3", "C4", "C5", "C2", "C5flat"])
-    ap.add_argument("--sources", default="both", choices=["both", "shared", "distinct"],
-                    help="shared: one source for all frames (BASELINE config, `value`); distinct: one source per frame; both (default)")
-    ap.add_argument("--points", default="both", choices=["both", "resident", "fresh"],
-                    help="resident: destination points uploaded once before the timed region (`value`); fresh: a new point set goes up "
-                         "inside EVERY timed step, like the reference's loop setDestinyPoints(dst_i); warp() (`roofline_fresh`); both (default)")
+    ap.add_argument("--sources", default=None, choices=["both", "shared", "distinct"],
+                    help="shared: one source for all frames (BASELINE config, `value`; the default); distinct: one source per frame; "
+                         "both (the default with --full)")
+    ap.add_argument("--points", default=None, choices=["both", "resident", "fresh"],
+                    help="resident: destination points uploaded once before the timed region (`value`; the default); fresh: a new point set "
+                         "goes up inside EVERY timed step, like the reference's loop setDestinyPoints(dst_i); warp() (`roofline_fresh`); "
+                         "both (the default with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: both source layouts and fresh points by default, the other configs under \"also\", "
+                         "the (untimed) output checks, the roofline figures and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed seeded sample of what the last timed step of the headline computed as DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="skip the (untimed) output checks")
+    ap.add_argument("--no-verify", action="store_true", help="skip the (untimed) output checks of --full")
     ap.add_argument("--cpu-frames", type=int, default=0, help="frames of the CPU-baseline sample (0 = auto, ~10-20 s)")
     ap.add_argument("--also", default=None, help="further measurements in the same invocation, reported under \"also\" with the fields of the headline line: "
                                                  "CONFIG:FRAMES (frames per GPU per step, weak) or CONFIG:BATCH:strong (a fixed batch over all GPUs, shared source, "
-                                                 "fan-out priced in end_to_end), comma-separated; 'none' = headline only.  Default (the plain command, no workload flag): "
+                                                 "fan-out priced in end_to_end), comma-separated; 'none' = headline only.  Default (--full, no workload flag): "
                                                  f"{DEFAULT_ALSO} and, with --gpus N > 1, {DEFAULT_ALSO_STRONG} (north_star's sharded configs)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak (default): --frames frames per GPU per step, per-GPU work fixed as N grows; strong: a FIXED batch of --batch frames "
@@ -197,7 +214,7 @@ def main():
     env = dict(torch=torch, dist=dist, world=world, rank=rank, local_rank=local_rank, dev=dev, n_devices=n_devices, hgdist=hgdist, hg=hg, wl=wl)
     line, ok = measure(args, args.config, args.frames, env, primary=True)
     # "also": the other configs of BASELINE.json in the SAME invocation (one lease yields every driver-timed line); each is a complete
-    # measurement (own context, own checks) with the fields of the headline.  The plain command takes the default list.
+    # measurement (own context, own checks) with the fields of the headline.  --full takes the default list.
     for name, fr, sc in also_entries(args, world):
         if sc == "strong":
             extra, ok_x = measure(args, name, fr, env, primary=False, scaling="strong", batch=fr, sources="shared", points="resident")
@@ -210,16 +227,49 @@ def main():
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
-    return 0 if (ok or args.no_verify) else 3
+    return 0 if ok else 3
+
+
+DUMP_SEED = 20240601           # fixed: the same pixels are sampled in every run with the same arguments
+DUMP_BYTES = 48 << 20          # budget of the sampled pixels (float32 RGBA + float64 index per pixel)
+
+
+def output_sample(torch, out_t, offs, n_out, geoms, dev):
+    """What the caller of the timed path receives -- F packed RGBA frames in HBM -- reduced to a fixed sample: per frame S pixels drawn
+    by a seeded generator (the same ones in every run with the same arguments), plus per-channel sums over every pixel of every frame."""
+    F = len(n_out)
+    S = max(1, min(16384, DUMP_BYTES // (F * 24)))
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.stack([np.sort(rng.integers(0, max(n, 1), S)) for n in n_out]).astype(np.int64)        # (F, S) pixel in the frame's window
+    pos = torch.as_tensor(np.asarray(offs[:F], np.int64), device=dev)[:, None] + torch.as_tensor(idx, device=dev) * 4
+    pos = (pos[:, :, None] + torch.arange(4, device=dev)).clamp_(0, out_t.numel() - 1)      # (an empty window samples nothing real: zeroed)
+    rgba = out_t[pos].float()
+    for f, n in enumerate(n_out):
+        if n == 0:
+            rgba[f] = 0.0
+    sums = torch.stack([out_t[offs[f]: offs[f] + n * 4].view(-1, 4).sum(0, dtype=torch.int64) for f, n in enumerate(n_out)])
+    return {"frames_rgba_sample": rgba.cpu().numpy().astype(np.float32),
+            "frames_pixel_index": idx.astype(np.float64),
+            "frames_window": np.asarray([g[:4] for g in geoms], np.float64),
+            "frames_channel_sum": sums.cpu().numpy().astype(np.float64)}
+
+
+def write_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def measure(args, config, F, env, primary=True, scaling=None, batch=None, sources=None, points=None):
     """One complete measurement of `config` with F frames per GPU per step (scaling "strong": a fixed batch over all GPUs): inputs -> HBM,
     timed regions, untimed checks, CPU baseline (headline only).  scaling / batch / sources / points default to the command line's.
-    Returns (the JSON line as a dict -- meaningful on rank 0 --, verified)."""
+    Without --full only the timed regions the layout flags ask for run: no checks, no CPU baseline, and no roofline figures unless a
+    second region (distinct sources, fresh points) was asked for.  Returns (the JSON line as a dict -- meaningful on rank 0 --, verified)."""
     scaling = scaling or args.scaling
-    sources = sources or args.sources
-    points = points or args.points
+    sources = sources or args.sources or ("both" if args.full else "shared")
+    points = points or args.points or ("both" if args.full else "resident")
+    figures = args.full or sources != "shared" or points != "resident"      # N_hit pass + roofline blocks
+    verify = args.full and not args.no_verify
     batch_arg = args.batch if batch is None else batch
     torch, dist, world, rank, local_rank, dev = env["torch"], env["dist"], env["world"], env["rank"], env["local_rank"], env["dev"]
     n_devices, hgdist, hg, wl = env["n_devices"], env["hgdist"], env["hg"], env["wl"]
@@ -349,17 +399,19 @@ def measure(args, config, F, env, primary=True, scaling=None, batch=None, source
         return t[offs[f]: offs[f] + n_out[f] * 4]
 
     # N_hit per frame (algorithmic read bytes): alpha==255 count when the same frames run on an all-255 source (untimed)
-    solid = torch.full((H, W, 4), 255, dtype=torch.uint8, device=dev)
-    ctx.set_image_device(solid.data_ptr(), W, H)
-    run(d_out)
-    ctx.sync()
-    hit_masks = [frame_view(out_t, f).view(-1, 4)[:, 3] == 255 for f in range(F)]
-    n_hit = [int(m.sum().item()) for m in hit_masks]
-    if not do_distinct or args.no_verify:
-        hit_masks = None
-    ctx.set_image_device(img_t.data_ptr(), W, H)
-    del solid
-    algo_bytes_per_launch = float(sum(4 * no + 4 * nh for no, nh in zip(n_out, n_hit)))
+    hit_masks, algo_bytes_per_launch = None, None
+    if figures:
+        solid = torch.full((H, W, 4), 255, dtype=torch.uint8, device=dev)
+        ctx.set_image_device(solid.data_ptr(), W, H)
+        run(d_out)
+        ctx.sync()
+        hit_masks = [frame_view(out_t, f).view(-1, 4)[:, 3] == 255 for f in range(F)]
+        n_hit = [int(m.sum().item()) for m in hit_masks]
+        if not do_distinct or not verify:
+            hit_masks = None
+        ctx.set_image_device(img_t.data_ptr(), W, H)
+        del solid
+        algo_bytes_per_launch = float(sum(4 * no + 4 * nh for no, nh in zip(n_out, n_hit)))
     compulsory_bytes_shared = float(sum(4 * no for no in n_out)) + 4.0 * W * H      # every output byte once + the shared source once
 
     def barrier():
@@ -439,19 +491,25 @@ def measure(args, config, F, env, primary=True, scaling=None, batch=None, source
         px_all = float(px.item())
     res = {}
     shared_copy = None
+    dump = None                                     # --dump-outputs: the headline region's last step, sampled right after it
+    want_dump = primary and rank == 0 and args.dump_outputs is not None
     if do_shared:
         elapsed, k_ms, k_launches = timed_region()
+        if want_dump:
+            dump = output_sample(torch, out_t, offs, n_out, geoms, dev)
         kernel_name = ({3: "k_pw_patch", 4: "k_pw_fused", 5: "k_pw_tile"}.get(ctx.last_piecewise_kernel(), "k_pw_rows") if piecewise else "k_geo_fast<projective>")
-        rf = roofline_block(k_ms, k_launches, "shared", elapsed)
-        comp = compulsory_bytes_shared / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-        rf["hbm_compulsory_frac"] = round(comp / HBM_PEAK_GBS, 4)
-        rf["note"] += ("; all frames share ONE source, whose reads are largely served by L2 / the 256 MiB Infinity Cache, so the ALGORITHMIC "
-                       "rate (SURVEY.md 8d: the source read is counted per frame) can exceed the HBM peak -- frac > 1 then says 'faster than a "
-                       "kernel that fetched every source pixel from HBM could be', not 'HBM at more than 100 %': hbm_compulsory_frac prices only "
-                       "what must cross HBM (every output byte once + the source once) and `traffic` is what did (PMC); "
-                       "roofline_distinct is the layout where algorithmic bytes are HBM bytes")
+        rf = None
+        if figures:
+            rf = roofline_block(k_ms, k_launches, "shared", elapsed)
+            comp = compulsory_bytes_shared / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+            rf["hbm_compulsory_frac"] = round(comp / HBM_PEAK_GBS, 4)
+            rf["note"] += ("; all frames share ONE source, whose reads are largely served by L2 / the 256 MiB Infinity Cache, so the ALGORITHMIC "
+                           "rate (SURVEY.md 8d: the source read is counted per frame) can exceed the HBM peak -- frac > 1 then says 'faster than a "
+                           "kernel that fetched every source pixel from HBM could be', not 'HBM at more than 100 %': hbm_compulsory_frac prices only "
+                           "what must cross HBM (every output byte once + the source once) and `traffic` is what did (PMC); "
+                           "roofline_distinct is the layout where algorithmic bytes are HBM bytes")
         res["shared"] = (elapsed, rf)
-        if not args.no_verify:                      # the bytes the timed kernels wrote (untimed checks)
+        if verify:                                  # the bytes the timed kernels wrote (untimed checks)
             want = {i: h for i, h in _golden_shas(config).items() if i in frame_ids}
             if want:
                 ok = all(hashlib.sha256(frame_view(out_t, frame_ids.index(i)).cpu().numpy().tobytes()).hexdigest() == h for i, h in want.items())
@@ -493,7 +551,7 @@ def measure(args, config, F, env, primary=True, scaling=None, batch=None, source
                  "layout_walks_in_region": ctx.layout_walks() - walks0, "frames_redone_in_region": ctx.redone_frames() - redone0,
                  "point_sets": f"ring of {len(fresh_sets)} sets (the config's sequence shifted by k frames), one hg_{'piecewise_set_frames' if piecewise else 'geometric_set_frames_points'} per step: "
                                f"{F} frames x {n_pts_txt} copied to page-locked staging and uploaded stream-ordered, no GPU wait"}
-        if not args.no_verify and shared_copy is not None:
+        if verify and shared_copy is not None:
             ok, n_cmp = True, 0
             for f in range(F):
                 fp = f + k_last if cfg["kind"] == "face" else ((f + k_last) % (4 if piecewise else 10))     # resident frame with the same point set
@@ -519,6 +577,8 @@ def measure(args, config, F, env, primary=True, scaling=None, batch=None, source
             srcs[f] ^= consts[f]
         ctx.set_images_device(srcs.data_ptr(), W, H, F, W * H * 4)
         elapsed_d, k_ms_d, k_launches_d = timed_region()
+        if want_dump and not do_shared:
+            dump = output_sample(torch, out_t, offs, n_out, geoms, dev)
         kernel_shared = kernel_name                 # (the layout policy may pick another kernel when every frame streams its own source)
         kernel_name = ({3: "k_pw_patch", 4: "k_pw_fused", 5: "k_pw_tile"}.get(ctx.last_piecewise_kernel(), "k_pw_rows") if piecewise else "k_geo_fast<projective>")
         rd = roofline_block(k_ms_d, k_launches_d, "distinct", elapsed_d)
@@ -527,7 +587,7 @@ def measure(args, config, F, env, primary=True, scaling=None, batch=None, source
         rd["ms_per_step"] = round(elapsed_d * 1e3 / args.steps, 4)
         rd["value_mpixels_per_s"] = round(px_all * args.steps / elapsed_d / 1e6, 1)
         res["distinct"] = (elapsed_d, rd)
-        if not args.no_verify and hit_masks is not None:
+        if verify and hit_masks is not None:
             # XOR-linearity of a pure gather: out(img ^ c) == out(img) ^ (c on pixels that read a source pixel, 0 elsewhere)
             base = shared_copy
             if base is None:                        # --sources distinct: produce the shared-source frames now (untimed)
@@ -568,7 +628,7 @@ def measure(args, config, F, env, primary=True, scaling=None, batch=None, source
 
     # ---------------------------------------------------------------- CPU baseline (rank 0, N=1 only): the oracle, 1 core, bounded sample
     cpu = None
-    if primary and rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if primary and args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         from hgtest import oracle as O             # checker / baseline only; never on the measured GPU path
         img = img_t.cpu().numpy()
@@ -651,11 +711,13 @@ def measure(args, config, F, env, primary=True, scaling=None, batch=None, source
                        "ms_per_step_by_rank": step_ms_by_rank,
                        "kernel_ms_over_ranks": {"min": round(region_stats[0]["kernel_ms_min"], 5), "max": round(region_stats[0]["kernel_ms_max"], 5),
                                                 "by_rank": [round(v, 5) for v in region_stats[0]["kernel_ms_by_rank"]]} if region_stats else None},
-            "verified": None if args.no_verify else verified, "checks": checks,
+            "verified": verified if verify else None, "checks": checks,
             "roofline": roofline, "roofline_fresh": fresh, "roofline_distinct": res["distinct"][1] if "distinct" in res and primary_src != "distinct" else None,
             "cpu_baseline": cpu}
     ctx.close()
-    return line, bool(verified or args.no_verify)
+    if dump is not None:
+        write_outputs(args.dump_outputs, dump)
+    return line, bool(verified or not verify)
 
 
 if __name__ == "__main__":

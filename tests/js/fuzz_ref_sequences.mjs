@@ -5,8 +5,11 @@
 // JavaScript oracle's loops from exactly the arguments the class passes).  After every op: same exception or same observable state
 // (transform, sizes, window, normalisation flags, both point sets in place, source bbox, null-ness of the two caches); after every
 // warp: same path, same RGBA bytes.  Stale-state quirks (SURVEY.md Appendix A-Q12) are therefore compared pixel for pixel.
-//   node tests/js/fuzz_ref_sequences.mjs [sequences = 300] [seed = 1] [--verbose]
+//   node tests/js/fuzz_ref_sequences.mjs [sequences = 300] [seed = 1] [--verbose] [--record FILE | --transcript FILE]
+// --record FILE also writes what the reference did (per op: its exception, a hash of its state, its warps) to FILE; --transcript FILE
+// replays such a recording in place of the live reference (tests/golden/ref_sequences.json: no reference checkout needed).
 // Prints one JSON line {sequences, ops, warps, stateCalls, failures: [...]}; exit 1 on any failure, 3 when the reference is absent.
+import fs from 'fs';
 import path from 'path';
 import crypto from 'crypto';
 import { fileURLToPath } from 'url';
@@ -16,12 +19,18 @@ import { triangulate } from '../../homography.js_amd/js/delaunay.mjs';
 import { rng, lcgImage, makeScript } from './seq_scripts.mjs';
 
 const HERE = path.dirname(fileURLToPath(import.meta.url));
-if (!referenceAvailable()) { console.log(JSON.stringify({ skipped: 'reference not present' })); process.exit(3); }
+const optArg = (flag) => { const i = process.argv.indexOf(flag); return i > 0 ? process.argv[i + 1] : null; };
+const recordTo = optArg('--record'), transcriptFile = optArg('--transcript');
+const transcript = transcriptFile ? JSON.parse(fs.readFileSync(transcriptFile, 'utf8')) : null;
+if (!transcript && !referenceAvailable()) { console.log(JSON.stringify({ skipped: 'reference not present' })); process.exit(3); }
 process.env.HGWARP_ADDON = path.join(HERE, 'mock_addon.cjs');
 const mock = createRequire(import.meta.url)(process.env.HGWARP_ADDON);
 
-const nSeq = Number(process.argv[2] || 300), seed0 = Number(process.argv[3] || 1), verbose = process.argv.includes('--verbose');
+const positional = process.argv.slice(2).filter((a, i, all) => !a.startsWith('--') && !['--record', '--transcript'].includes(all[i - 1]));
+const nSeq = transcript ? transcript.sequences : Number(positional[0] || 300), seed0 = transcript ? transcript.seed : Number(positional[1] || 1);
+const verbose = process.argv.includes('--verbose');
 const sha = (t) => crypto.createHash('sha256').update(Buffer.from(t.buffer, t.byteOffset, t.byteLength)).digest('hex').slice(0, 16);
+const shaText = (s) => crypto.createHash('sha256').update(s).digest('hex').slice(0, 16);
 
 // ---------------------------------------------------------------- running a script on one side
 const PATHS = { _geometricWarp: 1, _piecewiseAffineWarp: 1, _inverseGeometricWarp: 1, _inversePiecewiseAffineWarp: 1 };
@@ -72,7 +81,8 @@ function makeRunner(Cls, side) {
 const errRepr = (e) => (typeof e === 'string' ? 'S:' + e : (e && e.constructor ? e.constructor.name : String(e)));
 
 (async () => {
-    const ref = await loadReference();
+    const ref = transcript ? null : await loadReference();
+    const recorded = [];                                     // --record: per sequence, per op {e: exception, s: state hash, r: warps}
     const { Homography: Mine } = await import('../../homography.js_amd/js/Homography.mjs');
     globalThis.__TRI__ = (p) => triangulate(p);
     Mine.triangulate = (p) => triangulate(p);
@@ -98,11 +108,21 @@ const errRepr = (e) => (typeof e === 'string' ? 'S:' + e : (e && e.constructor ?
         const { images: specs, script } = s < 0 ? FIXED[s + FIXED.length]
                                                 : makeScript(rng(seed0 * 7919 + s), { triangles: (src) => Array.from(triangulate(Float32Array.from(src.flat()))) });
         const mk = () => { const o = {}; for (const [k, v] of Object.entries(specs)) o[k] = lcgImage(v.w, v.h, v.seed); return o; };
-        const A = makeRunner(ref.Homography, 'ref'), B = makeRunner(Mine, 'mine'), ia = mk(), ib = mk();
+        const A = transcript ? null : makeRunner(ref.Homography, 'ref'), B = makeRunner(Mine, 'mine'), ia = transcript ? null : mk(), ib = mk();
+        const tape = transcript ? transcript.ops[s + FIXED.length] : [];
+        if (recordTo) recorded.push(tape);
         for (let i = 0; i < script.length; i++) {
             ops++;
-            let ra = null, rb = null, ea = null, eb = null;
-            try { ra = A.run(script[i], ia); } catch (e) { ea = errRepr(e); }
+            let ra = null, rb = null, ea = null, eb = null, t = null;
+            if (transcript) {
+                t = tape[i];
+                if (!t) { failures.push(`seq ${s} (seed ${seed0}) op ${i}: the recording ends here, the class went on`); break; }
+                ea = t.e; ra = t.r;
+            } else {
+                try { ra = A.run(script[i], ia); } catch (e) { ea = errRepr(e); }
+                t = { e: ea, r: ra };
+                if (recordTo) tape.push(t);
+            }
             mock.calls.length = 0;
             try { rb = B.run(script[i], ib); } catch (e) { eb = errRepr(e); }
             stateCalls += mock.calls.filter((c) => c.endsWith('State')).length;
@@ -113,19 +133,22 @@ const errRepr = (e) => (typeof e === 'string' ? 'S:' + e : (e && e.constructor ?
                 if (ea !== eb) { failures.push(`${where}: reference ${ea === null ? 'returned' : 'threw ' + ea}, class ${eb === null ? 'returned' : 'threw ' + eb}`); break; }
                 if (ea !== null && !ea.startsWith('S:')) break;      // an Error out of the middle of a method: both instances are now in an unspecified state
             }
-            const sa = JSON.stringify(A.state()), sb = JSON.stringify(B.state());
-            if (sa !== sb) { failures.push(`${where}: state differs\n   ref  ${sa}\n   mine ${sb}`); break; }
+            const sa = transcript ? null : JSON.stringify(A.state()), sb = JSON.stringify(B.state());
+            if (recordTo) t.s = shaText(sa);
+            if (transcript ? t.s !== shaText(sb) : sa !== sb) { failures.push(`${where}: state differs\n   ref  ${transcript ? 'hash ' + t.s : sa}\n   mine ${sb}`); break; }
             if (ra && rb) {
                 warps += ra.length;
                 const ja = JSON.stringify(ra), jb = JSON.stringify(rb.map((x, k) => ({ path: x.path === undefined ? ra[k].path : x.path, w: x.w, h: x.h, sha: x.sha })));
                 if (ja !== jb) { failures.push(`${where}: warp differs (${mock.calls.join(',')})\n   ref  ${ja}\n   mine ${jb}`); break; }
             }
         }
-        A.close(); B.close();
+        if (A) A.close();
+        B.close();
         if (verbose && s % 50 === 0) console.error(`  ${s} sequences, ${failures.length} failures`);
         if (failures.length >= 12) break;
     }
-    ref.cleanup();
+    if (ref) ref.cleanup();
+    if (recordTo) fs.writeFileSync(recordTo, JSON.stringify({ seed: seed0, sequences: nSeq, fixed: FIXED.length, ops: recorded }) + '\n');
     console.log(JSON.stringify({ sequences: nSeq, ops, warps, stateCalls, throwsSeen, failures }, null, failures.length ? 1 : 0));
     process.exit(failures.length ? 1 : 0);
 })().catch((e) => { console.error(e); process.exit(2); });

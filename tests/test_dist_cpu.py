@@ -234,8 +234,8 @@ def test_bench_self_launch_command():
 
 
 def test_bench_default_also_entries():
-    """What the driver's one command records: `python bench.py [--gpus N --steps K --warmup W]` measures the headline AND the other
-    BASELINE.json configs; with N > 1 also north_star's fixed-batch (strong) lines.  Any workload-selecting flag means "exactly this"."""
+    """`python bench.py --full [--gpus N --steps K --warmup W]` measures the headline AND the other BASELINE.json configs; with N > 1 also
+    north_star's fixed-batch (strong) lines.  Any workload-selecting flag means "exactly this"; the plain command measures the headline alone."""
     import argparse
     import importlib.util
     spec = importlib.util.spec_from_file_location("hg_bench", os.path.join(ROOT, "bench.py"))
@@ -243,11 +243,14 @@ def test_bench_default_also_entries():
     spec.loader.exec_module(B)
 
     def ns(**kw):
-        base = dict(config="C3", frames=64, sources="both", points="both", scaling="weak", batch=0, no_verify=False, also=None)
+        base = dict(config="C3", frames=64, sources="both", points="both", scaling="weak", batch=0, no_verify=False, also=None, full=True)
         base.update(kw)
         return argparse.Namespace(**base)
     assert B.also_entries(ns(), 1) == [("C4", 64, "weak"), ("C5", 8, "weak"), ("C2", 64, "weak")]
     assert B.also_entries(ns(), 8) == [("C4", 64, "weak"), ("C5", 8, "weak"), ("C2", 64, "weak"), ("C4", 512, "strong"), ("C5", 64, "strong")]
+    assert B.also_entries(ns(sources=None, points=None), 1) == [("C4", 64, "weak"), ("C5", 8, "weak"), ("C2", 64, "weak")]
+    assert B.also_entries(ns(full=False, sources=None, points=None), 8) == [] and B.also_entries(ns(full=False), 1) == []
+    assert B.also_entries(ns(full=False, also="C2:4"), 1) == [("C2", 4, "weak")]
     for flag in (dict(config="C4"), dict(frames=8), dict(sources="shared"), dict(points="resident"), dict(scaling="strong"), dict(batch=64), dict(no_verify=True)):
         assert B.also_entries(ns(**flag), 8) == [], flag
     assert B.also_entries(ns(also="none"), 8) == [] and B.also_entries(ns(also=""), 1) == []

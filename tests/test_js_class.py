@@ -42,12 +42,13 @@ def test_state_machine_replay_matches_reference():
 
 
 @needs_js
-@pytest.mark.skipif(not os.path.exists("/root/reference/Homography.js"), reason="the live reference exists only in the build container")
 def test_random_call_sequences_against_the_live_reference():
-    """Differential fuzz: random call sequences on the reference's own Homography.js and on the class (over the mock addon), op by op."""
-    rc, res = _node("fuzz_ref_sequences.mjs", "250", "11", timeout=900)
+    """Differential fuzz: random call sequences on the class (over the mock addon), op by op against what the reference's own
+    Homography.js did on the same 250 sequences (seed 11) -- its exception, state and warps per op, recorded from the reference with
+    `node tests/js/fuzz_ref_sequences.mjs 250 11 --record tests/golden/ref_sequences.json`."""
+    rc, res = _node("fuzz_ref_sequences.mjs", "--transcript", os.path.join(ROOT, "tests", "golden", "ref_sequences.json"), timeout=900)
     assert res["failures"] == [] and rc == 0
-    assert res["warps"] >= 800 and res["stateCalls"] >= 50
+    assert res["sequences"] == 250 and res["warps"] >= 800 and res["stateCalls"] >= 50
 
 
 @needs_js

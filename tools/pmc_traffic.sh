@@ -5,7 +5,7 @@
 export TMPDIR=/tmp
 tag=$1; shift
 out=$PWD/gpurun_out/pmc_$tag; mkdir -p $out
-B="python bench.py --no-cpu-baseline --no-verify --steps 20 --warmup 2 $*"
+B="python bench.py --full --no-cpu-baseline --no-verify --steps 20 --warmup 2 $*"
 timeout 300 rocprofv3 --pmc FETCH_SIZE -d $out/f -o p -- $B > $out/f.log 2>&1
 timeout 300 rocprofv3 --pmc WRITE_SIZE -d $out/w -o p -- $B > $out/w.log 2>&1
 python - <<PY
