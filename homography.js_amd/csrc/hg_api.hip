@@ -256,6 +256,21 @@ extern "C" int hg_set_option(hg_ctx *c, const char *key, int value)
 
 extern "C" int hg_xcc_count(const hg_ctx *c) { return c ? 1 << c->xcc_log2 : 0; }
 
+extern "C" int hg_set_sampling(hg_ctx *c, int mode)
+{
+    if (!c) return fail(nullptr, HG_ERR_INVALID, "ctx is NULL");
+    if (mode != HG_SAMPLE_NEAREST && mode != HG_SAMPLE_BILINEAR) return fail(c, HG_ERR_INVALID, "hg_set_sampling: unknown mode " + std::to_string(mode));
+    c->sampling = mode;                                       // (queued runs keep the mode they were queued with: nothing to settle)
+    return HG_OK;
+}
+
+extern "C" int hg_get_sampling(const hg_ctx *c, int *mode)
+{
+    if (!c || !mode) return fail(nullptr, HG_ERR_INVALID, "hg_get_sampling: NULL argument");
+    *mode = c->sampling;
+    return HG_OK;
+}
+
 extern "C" int hg_set_timing(hg_ctx *c, int enabled)
 {
     HG_TRY(bind(c));

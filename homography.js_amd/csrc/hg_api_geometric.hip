@@ -142,7 +142,7 @@ extern "C" int hg_warp_inverse_geometric_frames_device(hg_ctx *c, void *d_out)
                c->n_imgs, (uint64_t)c->img_stride, static_cast<uint8_t *>(d_out),
                (c->geo_from_points && c->geo_kind == HG_PROJECTIVE) ? c->d_geo_plain : nullptr, c->opt_geo_nw,
                c->xcc_log2, c->opt_xcc_rotate >= 0 ? c->opt_xcc_rotate != 0 : c->n_imgs > 1,   // (XCD bands; rotating with the frame when every frame reads its own source)
-               c->stream);
+               c->sampling, c->stream);
     HG_TRY(time_end(c));
     HIP_TRY(c, hipGetLastError());
     return HG_OK;

@@ -381,7 +381,9 @@ static int run_setup(hg_ctx *c, bool for_tap = false)
     const size_t F = c->pw_frames.size();
     int mw = 0;
     for (const FrameDesc &d : c->pw_frames) mw = std::max(mw, d.obj_w);
-    c->pw_fast = pw_fast_ok(mesh_of(c), mw);
+    // bilinear sampling has no row / patch / tile kernels: the general path (k_tri_setup + k_pw_fused<bilinear>) -- not for the parity tap,
+    // whose map and matrices do not depend on the mode
+    c->pw_fast = pw_fast_ok(mesh_of(c), mw) && (for_tap || c->sampling != HG_SAMPLE_BILINEAR);
     if (c->pw_fast) {
         // entry format of the span lists (hg_kernels.h): 8 bytes for dense rows and whenever k_pw_patch will read them
         bool global_records = false;
@@ -509,7 +511,7 @@ static void run_warp(hg_ctx *c, uint8_t *d_out, int16_t *map_out)
     else if (c->pw_fast) {
         c->pw_last_variant = launch_pw_rows(mesh_of(c), frames_of(c), rows_of(c), d_out, map_out, c->status_next, c->stream); c->rows_clean = true;
     }
-    else          { launch_pw_fused(mesh_of(c), frames_of(c), d_out, map_out, c->stream); c->pw_last_variant = 600000; }
+    else          { launch_pw_fused(mesh_of(c), frames_of(c), d_out, map_out, c->sampling, c->stream); c->pw_last_variant = 600000; }
 }
 
 static int check_pw_state(hg_ctx *c)
@@ -530,7 +532,7 @@ static int run_frame_via_map(hg_ctx *c, int f, uint8_t *d_out)
     PwMesh mesh = mesh_of(c);
     mesh.img = frame_img(mesh, f); mesh.n_imgs = 1;          // this frame's own source
     launch_map_build(mesh, frames_of(c), f, fd, c->d_map32, c->stream);
-    launch_pw_from_map(mesh, frames_of(c), f, fd, c->d_map32, d_out, c->stream);
+    launch_pw_from_map(mesh, frames_of(c), f, fd, c->d_map32, d_out, c->sampling, c->stream);
     HIP_TRY(c, hipGetLastError());
     return HG_OK;
 }
@@ -538,8 +540,8 @@ static int run_frame_via_map(hg_ctx *c, int f, uint8_t *d_out)
 // Deferred redo: frame f of the staged set `stage` (the set a queued run warped; newer sets may have been uploaded since)
 // through the materialised map, into `d_out` at the frame's own offset.  Self-contained: the frame's window and points go from
 // the staging buffer to a one-frame scratch, k_tri_setup solves it there, then rasteriser + pixel loop.  Mesh and source
-// image are those of the context (changing either settles queued runs first).
-static int redo_frame_staged(hg_ctx *c, int stage, int f, uint8_t *d_out)
+// image are those of the context (changing either settles queued runs first); `sampling` is the mode the run was queued with.
+static int redo_frame_staged(hg_ctx *c, int stage, int f, uint8_t *d_out, int sampling)
 {
     const hg_ctx::Stage &st = c->stage[stage];
     if (stage < 0 || !st.h || f >= st.n || st.n_pts != c->n_pts) return fail(c, HG_ERR_STATE, "deferred redo: the staged frame set is gone");
@@ -568,7 +570,7 @@ static int redo_frame_staged(hg_ctx *c, int stage, int f, uint8_t *d_out)
     fr.inv = c->d_redo_inv; fr.status = c->d_redo_status; fr.n_frames = 1; fr.max_obj_h = fd.obj_h;
     launch_tri_setup(mesh, fr, c->stream);
     launch_map_build(mesh, fr, 0, fd, c->d_map32, c->stream);
-    launch_pw_from_map(mesh, fr, 0, fd, c->d_map32, d_out, c->stream);
+    launch_pw_from_map(mesh, fr, 0, fd, c->d_map32, d_out, sampling, c->stream);
     HIP_TRY(c, hipGetLastError());
     return HG_OK;
 }
@@ -624,11 +626,12 @@ extern "C" int hg_warp_inverse_piecewise_frames_device(hg_ctx *c, void *d_out)
     HG_TRY(time_end(c));
     HIP_TRY(c, hipGetLastError());
     const uint8_t path = (uint8_t)((c->pw_used_patch ? 1 : 0) | (c->pw_self ? 2 : 0) | (c->pw_self && c->pw_tile && c->pw_last_kernel == 5 ? 4 : 0));
-    if (c->pw_fast) c->pw_pending_out.push_back({static_cast<uint8_t *>(d_out), c->status_slot, c->stage_cur, extent, layout, path});
+    const uint8_t mode = (uint8_t)c->sampling;
+    if (c->pw_fast) c->pw_pending_out.push_back({static_cast<uint8_t *>(d_out), c->status_slot, c->stage_cur, extent, layout, path, mode});
     else {                                                   // general path: one status set, checked right away
         HIP_TRY(c, hipMemcpyAsync(c->h_status, c->status_ptr, sizeof(int32_t) * c->pw_frames.size(), hipMemcpyDeviceToHost, c->stream));
         c->status_base = nullptr;
-        c->pw_pending_out.push_back({static_cast<uint8_t *>(d_out), 0, c->stage_cur, extent, layout, 0});
+        c->pw_pending_out.push_back({static_cast<uint8_t *>(d_out), 0, c->stage_cur, extent, layout, 0, mode});
         HG_TRY(hg_sync(c));
     }
     return HG_OK;
@@ -712,7 +715,7 @@ extern "C" int hg_sync(hg_ctx *c)
         if (redo)
             HG_TRY(replay_queued(c, pending, [&](size_t) { return (int)F; },
                                  [&](size_t i, int f) { return c->h_status[(size_t)pending[i].slot * F + f] != FRAME_OK; },
-                                 [&](size_t i, int f) { return redo_frame_staged(c, pending[i].stage, f, pending[i].out); }));
+                                 [&](size_t i, int f) { return redo_frame_staged(c, pending[i].stage, f, pending[i].out, pending[i].sampling); }));
         if (redo) {
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             // A run that exceeded a LIMIT of its kernel teaches the layout policy, by the path THAT run took; a frame that was merely

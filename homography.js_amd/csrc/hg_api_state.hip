@@ -121,7 +121,7 @@ extern "C" int hg_warp_inverse_piecewise_state(hg_ctx *c, const float *fwd_mats,
     fr.two_round = nullptr;                                  // (a set-up of its own, outside the frame set's step numbering)
     fr.inv = c->d_st_mats;
     FrameDesc fd; fd.x_off = geom.x_off; fd.y_off = geom.y_off; fd.obj_w = geom.obj_w; fd.obj_h = geom.obj_h; fd.out_off = 0; fd.map_off = 0;
-    launch_pw_from_map(mesh, fr, 0, fd, c->d_map32, c->d_out_tmp, c->stream);       // :1042-1056
+    launch_pw_from_map(mesh, fr, 0, fd, c->d_map32, c->d_out_tmp, c->sampling, c->stream);       // :1042-1056 (or its bilinear form)
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(out_host, c->d_out_tmp, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));

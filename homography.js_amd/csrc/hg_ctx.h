@@ -86,6 +86,7 @@ struct hg_ctx {
     int32_t pw_last_flag = 0;                                  // status word of the last frame a fused run flagged (bits 4..: which limit, see k_pw_patch<SELF>)
     long pw_redone = 0;                                        // frames redone through the materialised map (hg_redone_frames())
     int opt_min_row_groups = 1152, opt_patch = -1, opt_phase = -1, opt_geo_nw = 8;   // hg_set_option()
+    int sampling = HG_SAMPLE_NEAREST;                          // hg_set_sampling: pixel body of the inverse warps called from now on (queued work keeps its own)
     int xcc_log2 = 3;                                          // log2(XCCs of the device): hipDeviceAttributeNumberOfXccs at hg_create, option "xcc"
     int opt_hi_bounds = 1;                                     // 0: fp64 bounds compares instead of the high-dword form (hg_dev.h)
     // fused runs whose per-frame status words have not been checked yet: up to kStatusRing - 1 calls are queued back to back
@@ -94,7 +95,8 @@ struct hg_ctx {
     // its frames' (offset, size) list -- a later call into the SAME layout supersedes its deferred redos frame by frame, any other
     // overlapping writer settles it first (settle_output_conflicts)
     // path: which layout the run took (bit 0 k_pw_patch, bit 1 self-span prologue, bit 2 k_pw_tile): what hg_sync disables when the run exceeded a limit
-    struct Pending { uint8_t *out; int slot; int stage; size_t extent; uint64_t layout; uint8_t path; };
+    // sampling: the mode the run was queued with (its deferred redos use it, whatever the context's mode is by then)
+    struct Pending { uint8_t *out; int slot; int stage; size_t extent; uint64_t layout; uint8_t path; uint8_t sampling; };
     std::vector<Pending> pw_pending_out;
     // Frame sets arrive through a ring of page-locked staging buffers (FrameDesc[F], then the F x n_pts x 2 destination
     // points): hg_piecewise_set_frames copies the caller's arrays there and queues stream-ordered uploads -- it neither waits

@@ -127,6 +127,82 @@ __device__ __forceinline__ uint32_t pw_pixel(int tid_raw, int x, double y, MatCa
     return 0u;
 }
 
+// ------------------------------------------------------------------------------------------------ bilinear sampling (HG_SAMPLE_BILINEAR)
+// Not the reference's: an opt-in mode of the inverse warps (include/hgwarp.h).  Straight RGBA, each channel in f32, contraction off:
+//   v = (p00*(1-fx) + p01*fx)*(1-fy) + (p10*(1-fx) + p11*fx)*fy,   out = min(255, floor(v + 0.5f))
+// where fx, fy are the fractions of the f64 source coordinate (where both are 0 the result is p00, the nearest pixel, byte for byte).
+__device__ __forceinline__ uint32_t blend4(uint32_t p00, uint32_t p01, uint32_t p10, uint32_t p11, float fx, float fy)
+{
+    const float gx = 1.0f - fx, gy = 1.0f - fy;
+    uint32_t o = 0u;
+#pragma unroll
+    for (int ch = 0; ch < 4; ch++) {
+        const int s = 8 * ch;
+        const float a = (float)((p00 >> s) & 255u), b = (float)((p01 >> s) & 255u);
+        const float c = (float)((p10 >> s) & 255u), d = (float)((p11 >> s) & 255u);
+        const float v = (a * gx + b * fx) * gy + (c * gx + d * fx) * fy;
+        o |= (uint32_t)fminf(255.0f, floorf(v + 0.5f)) << s;
+    }
+    return o;
+}
+
+// The four taps of a covered source coordinate (sx, sy): x0 = floor(sx), fx = (float)(sx - x0) (exact difference: |sx| < 2^52),
+// tap columns clamp(x0, 0, W-1) and clamp(x0+1, 0, W-1), rows alike.  The pixel indices are always inside the W x H image.
+struct BilTaps { int i00, i01, i10, i11; float fx, fy; };
+__device__ __forceinline__ BilTaps bil_taps(double sx, double sy, int W, int H)
+{
+    const double x0 = floor(sx), y0 = floor(sy);
+    BilTaps t;
+    t.fx = (float)(sx - x0); t.fy = (float)(sy - y0);
+    const int ix = (int)x0, iy = (int)y0;
+    const int cx0 = min(max(ix, 0), W - 1), cx1 = min(max(ix + 1, 0), W - 1);
+    const int r0 = min(max(iy, 0), H - 1) * W, r1 = min(max(iy + 1, 0), H - 1) * W;
+    t.i00 = r0 + cx0; t.i01 = r0 + cx1; t.i10 = r1 + cx0; t.i11 = r1 + cx1;
+    return t;
+}
+
+// (int32 pixel indices: the callers of bil_taps admit sources below 2^31 bytes.  This general form indexes in 64 bits.)
+__device__ __forceinline__ uint32_t bilinear_fetch(const uint32_t *__restrict__ img32, int W, int H, double sx, double sy)
+{
+    const double x0 = floor(sx), y0 = floor(sy);
+    const float fx = (float)(sx - x0), fy = (float)(sy - y0);
+    const int ix = (int)x0, iy = (int)y0;
+    const int64_t cx0 = min(max(ix, 0), W - 1), cx1 = min(max(ix + 1, 0), W - 1);
+    const int64_t r0 = (int64_t)min(max(iy, 0), H - 1) * W, r1 = (int64_t)min(max(iy + 1, 0), H - 1) * W;
+    return blend4(img32[r0 + cx0], img32[r0 + cx1], img32[r1 + cx0], img32[r1 + cx1], fx, fy);
+}
+
+// pw_pixel in bilinear mode: same triangle lookup, matrix, source coordinate and coverage test :1047; the taps index the source as the
+// reference's own lookup does (no minSrc subtraction), clamped to the image.
+__device__ __forceinline__ uint32_t pw_pixel_bilinear(int tid_raw, int x, double y, MatCache &mc, const float *__restrict__ invm,
+                                                      const uint32_t *__restrict__ img32, int W, int H,
+                                                      double bx0, double bx1, double by0, double by1)
+{
+    const int t16 = (int)(int16_t)tid_raw;
+    if (t16 < 0) return 0u;
+    if (t16 != mc.id) {
+        const float4 lo = *reinterpret_cast<const float4 *>(invm + (size_t)t16 * kInvStride);
+        const float2 hi = *reinterpret_cast<const float2 *>(invm + (size_t)t16 * kInvStride + 4);
+        mc.m[0] = lo.x; mc.m[1] = lo.y; mc.m[2] = lo.z; mc.m[3] = lo.w; mc.m[4] = hi.x; mc.m[5] = hi.y;
+        mc.id = t16;
+    }
+    const double xd = (double)x;
+    const double sx = (mc.m[0] * xd) + (mc.m[2] * y) + mc.m[4];
+    const double sy = (mc.m[1] * xd) + (mc.m[3] * y) + mc.m[5];
+    if (sx >= bx0 && sx < bx1 && sy >= by0 && sy < by1) return bilinear_fetch(img32, W, H, sx, sy);
+    return 0u;
+}
+
+// the pixel body of k_pw_fused / k_pw_from_map for sampling mode S (HG_SAMPLE_*)
+template <int S>
+__device__ __forceinline__ uint32_t pw_pixel_mode(int tid_raw, int x, double y, MatCache &mc, const float *__restrict__ invm,
+                                                  const uint32_t *__restrict__ img32, int64_t n_src_px, int W, int H,
+                                                  double bx0, double bx1, double by0, double by1)
+{
+    if (S == 1) return pw_pixel_bilinear(tid_raw, x, y, mc, invm, img32, W, H, bx0, bx1, by0, by1);
+    return pw_pixel(tid_raw, x, y, mc, invm, img32, n_src_px, W, H, bx0, bx1, by0, by1);
+}
+
 __device__ __forceinline__ uint32_t dlo(double v) { return (uint32_t)__double2loint(v); }
 // a wave-uniform double moved to scalar registers (v_cmp_f64 takes it as its scalar operand): frees two VGPRs each
 __device__ __forceinline__ double sgpr_f64(double v)

@@ -9,7 +9,8 @@ namespace hg {
 
 // ------------------------------------------------------------------------------------------------ k_geo
 // _inverseGeometricWarp pixel loop :997-1011.  Block = 64 x 4 threads = 4 rows x 256 pixels; blockIdx.z = frame.
-template <int KIND>
+// S: sampling mode (0 nearest, the reference's Math.round; 1 bilinear over the four clamped taps, hg_dev.h: same coordinate, same coverage).
+template <int KIND, int S>
 __global__ __launch_bounds__(256) void k_geo(const FrameDesc *__restrict__ frames, const double *__restrict__ mats,
                                              const uint8_t *__restrict__ img0, int W, int H, int n_imgs, uint64_t img_stride, uint8_t *__restrict__ out)
 {
@@ -36,8 +37,10 @@ __global__ __launch_bounds__(256) void k_geo(const FrameDesc *__restrict__ frame
         double sx, sy;
         if (KIND == 0) apply_affine(m, x, y, sx, sy); else apply_projective(m, x, y, sx, sy);     // :999
         px[k] = 0u;
-        if (sx >= 0 && sx < bw && sy >= 0 && sy < bh)                                            // :1001
-            px[k] = fetch_src(img32, n_src_px, W, round_inbounds(sx), round_inbounds(sy));       // :1005-1007
+        if (sx >= 0 && sx < bw && sy >= 0 && sy < bh) {                                          // :1001
+            if (S == 1) px[k] = bilinear_fetch(img32, W, H, sx, sy);
+            else        px[k] = fetch_src(img32, n_src_px, W, round_inbounds(sx), round_inbounds(sy));       // :1005-1007
+        }
     }
     store_quad(orow, cq, OW, vec_ok, px);
 }
@@ -98,7 +101,10 @@ __global__ void k_selftest_division(uint64_t seed, uint64_t n_per_thread, unsign
 //     choice from the flag the device-side solve wrote (k_solve_frames);
 //   * Math.round + bounds :1001 via two round-toward-minus-infinity adds per coordinate (round_x8), source through a
 //     range-checked buffer load (0 outside the array), stores through a per-row buffer descriptor (no tail guards).
-template <int KIND, int NW>
+// S = 1 (bilinear, instantiated with NW = 8 only): the same coordinates; the bounds test :1001 as fp64 compares on them, then the
+// four clamped taps of every pixel (bil_taps, hg_dev.h) gathered through the same stride-4 descriptor -- all 4 x 4 x NW of them in flight
+// before the first blend -- and one blend4 per pixel in front of its store.  Uncovered pixels gather index -1 (0) with zero fractions.
+template <int KIND, int NW, int S>
 __global__ __launch_bounds__(256) void k_geo_fast(const FrameDesc *__restrict__ frames, const double *__restrict__ mats,
                                                   const uint8_t *__restrict__ img0, int W, int H, int n_imgs, uint64_t img_stride, uint8_t *__restrict__ out,
                                                   const int32_t *__restrict__ plain, int xcc_log2, int groups_per_xcd, int chunks, int rotate)
@@ -129,6 +135,7 @@ __global__ __launch_bounds__(256) void k_geo_fast(const FrameDesc *__restrict__ 
     const __amdgpu_buffer_rsrc_t src = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(img), 4, W * H, 0x00020000);       // (records of 4 bytes: gathers by pixel index)
     const __amdgpu_buffer_rsrc_t dst = __builtin_amdgcn_make_buffer_rsrc(out + fd.out_off + (int64_t)r * OW * 4, 0, OW * 4, 0x00020000);
     const double y = (double)(r + fd.y_off);
+    const double bw = (double)W, bh = (double)H;           // (bilinear: :1001 as fp64 compares)
     // :1001 on the high dwords of h = RTN(s + 0.5) (hg_dev.h; the launcher admits only W, H < 2^20 here)
     const HiBounds hb = make_hi_bounds(0.5, (double)W + 0.5, 0.5, (double)H + 0.5);
     // row constants, once per wave: fl(m2*y), fl(m3*y) (affine) / fl(m1*y), fl(m4*y), fl(m7*y) (projective)   :1383-1384 / :1402-1403
@@ -136,7 +143,9 @@ __global__ __launch_bounds__(256) void k_geo_fast(const FrameDesc *__restrict__ 
     // KIND 4: matrices solved on the device (k_solve_frames), which also proved (or not) the plain range per frame
     const bool use_plain = KIND == 4 && __builtin_amdgcn_readfirstlane(plain[fz]) != 0;
     // NW windows per wave, gathers of all of them issued before the first store (see k_pw_rows: loads and stores share vmcnt)
-    uint32_t px[NW][4];
+    constexpr int NT = S == 1 ? 4 : 1;                     // gathers per pixel
+    uint32_t px[NW][4 * NT];
+    float frac[S == 1 ? NW : 1][S == 1 ? 8 : 1];           // bilinear: fx, fy of the window's 4 pixels
     // (the plain / IEEE choice of KIND 4 is wave-uniform: taken once around the whole gather loop, not once per pixel -- the per-pixel
     // form kept every pixel's dependent chain behind a scalar branch)
     auto gather = [&](auto plain_tag) {
@@ -163,12 +172,26 @@ __global__ __launch_bounds__(256) void k_geo_fast(const FrameDesc *__restrict__ 
                     else { h[2 * k] = nx / den; h[2 * k + 1] = ny / den; }
                 }
             }
-            round_x8(h, rd);
+            if constexpr (S == 1) {
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const bool inb = hi_inb(hb, h[2 * k], h[2 * k + 1]);                                     // :1001 (NaN fails)
-                const int idx = __mul24((int)dlo(rd[2 * k + 1]), W) + (int)dlo(rd[2 * k]);                            // :1005, in pixels
-                px[p][k] = hg_struct_load_u32(src, inb ? idx : -1, 0, 0, 0);
+                for (int k = 0; k < 4; k++) {
+                    const double sx = h[2 * k], sy = h[2 * k + 1];
+                    const bool inb = sx >= 0 && sx < bw && sy >= 0 && sy < bh;                                 // :1001 (NaN fails)
+                    const BilTaps t = bil_taps(inb ? sx : 0.0, inb ? sy : 0.0, W, H);
+                    frac[p][2 * k] = inb ? t.fx : 0.0f; frac[p][2 * k + 1] = inb ? t.fy : 0.0f;
+                    px[p][4 * k + 0] = hg_struct_load_u32(src, inb ? t.i00 : -1, 0, 0, 0);
+                    px[p][4 * k + 1] = hg_struct_load_u32(src, inb ? t.i01 : -1, 0, 0, 0);
+                    px[p][4 * k + 2] = hg_struct_load_u32(src, inb ? t.i10 : -1, 0, 0, 0);
+                    px[p][4 * k + 3] = hg_struct_load_u32(src, inb ? t.i11 : -1, 0, 0, 0);
+                }
+            } else {
+                round_x8(h, rd);
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const bool inb = hi_inb(hb, h[2 * k], h[2 * k + 1]);                                     // :1001 (NaN fails)
+                    const int idx = __mul24((int)dlo(rd[2 * k + 1]), W) + (int)dlo(rd[2 * k]);                            // :1005, in pixels
+                    px[p][k] = hg_struct_load_u32(src, inb ? idx : -1, 0, 0, 0);
+                }
             }
         }
     };
@@ -178,24 +201,34 @@ __global__ __launch_bounds__(256) void k_geo_fast(const FrameDesc *__restrict__ 
         const int c0 = cb + p * 256;
         if (c0 >= OW) break;
 #pragma unroll
-        for (int k = 0; k < 4; k++) __builtin_amdgcn_raw_buffer_store_b32(px[p][k], dst, (c0 + lane + k * 64) * 4, 0, kStoreNT);
+        for (int k = 0; k < 4; k++) {
+            uint32_t v;
+            if constexpr (S == 1) v = blend4(px[p][4 * k], px[p][4 * k + 1], px[p][4 * k + 2], px[p][4 * k + 3], frac[p][2 * k], frac[p][2 * k + 1]);
+            else v = px[p][k];
+            __builtin_amdgcn_raw_buffer_store_b32(v, dst, (c0 + lane + k * 64) * 4, 0, kStoreNT);
+        }
     }
 }
 
 void launch_geo(int kind, bool f32_exact, const FrameDesc *frames, const double *mats, int n_frames, int max_w, int max_h,
-                const uint8_t *img, int W, int H, int n_imgs, uint64_t img_stride, uint8_t *out, const int32_t *plain, int nw, int xcc_log2, bool rotate_bands, hipStream_t stream)
+                const uint8_t *img, int W, int H, int n_imgs, uint64_t img_stride, uint8_t *out, const int32_t *plain, int nw, int xcc_log2, bool rotate_bands,
+                int sampling, hipStream_t stream)
 {
     const int rotate = rotate_bands ? 1 : 0;
     if (n_frames <= 0 || max_w <= 0 || max_h <= 0) return;
     const bool fast = ((int64_t)H + 2) * W * 4 < ((int64_t)1 << 31) && hi_bounds_ok(0, W, 0, H) && max_w < (1 << 28);
+    const bool bil = sampling == 1;
     if (fast) {
-        const int NW = nw == 1 ? 1 : (nw == 2 ? 2 : (nw >= 8 ? 8 : 4));        // windows per wave (measured on C2, 1 -> 2 -> 4: 0.198 -> 0.177 -> 0.171 ms; round 3, 4 -> 8: 0.162 -> 0.153, one source per frame 0.219 -> 0.199)
+        // windows per wave (measured on C2, 1 -> 2 -> 4: 0.198 -> 0.177 -> 0.171 ms; round 3, 4 -> 8: 0.162 -> 0.153, one source per frame 0.219 -> 0.199);
+        // bilinear: 8 (its only instantiation)
+        const int NW = bil ? 8 : (nw == 1 ? 1 : (nw == 2 ? 2 : (nw >= 8 ? 8 : 4)));
         const int nx = 1 << xcc_log2, chunks = (max_w + 256 * NW - 1) / (256 * NW), gpx = ((max_h + 3) / 4 + nx - 1) / nx;
         dim3 grid((unsigned)chunks * (unsigned)gpx * (unsigned)nx * (unsigned)n_frames);
-#define HG_GEO(K) do { if (NW == 1) hipLaunchKernelGGL((k_geo_fast<K, 1>), grid, dim3(64, 4), 0, stream, frames, mats, img, W, H, n_imgs, img_stride, out, plain, xcc_log2, gpx, chunks, rotate); \
-                       else if (NW == 4) hipLaunchKernelGGL((k_geo_fast<K, 4>), grid, dim3(64, 4), 0, stream, frames, mats, img, W, H, n_imgs, img_stride, out, plain, xcc_log2, gpx, chunks, rotate); \
-                       else if (NW == 8) hipLaunchKernelGGL((k_geo_fast<K, 8>), grid, dim3(64, 4), 0, stream, frames, mats, img, W, H, n_imgs, img_stride, out, plain, xcc_log2, gpx, chunks, rotate); \
-                       else hipLaunchKernelGGL((k_geo_fast<K, 2>), grid, dim3(64, 4), 0, stream, frames, mats, img, W, H, n_imgs, img_stride, out, plain, xcc_log2, gpx, chunks, rotate); } while (0)
+#define HG_GEO(K) do { if (bil) hipLaunchKernelGGL((k_geo_fast<K, 8, 1>), grid, dim3(64, 4), 0, stream, frames, mats, img, W, H, n_imgs, img_stride, out, plain, xcc_log2, gpx, chunks, rotate); \
+                       else if (NW == 1) hipLaunchKernelGGL((k_geo_fast<K, 1, 0>), grid, dim3(64, 4), 0, stream, frames, mats, img, W, H, n_imgs, img_stride, out, plain, xcc_log2, gpx, chunks, rotate); \
+                       else if (NW == 4) hipLaunchKernelGGL((k_geo_fast<K, 4, 0>), grid, dim3(64, 4), 0, stream, frames, mats, img, W, H, n_imgs, img_stride, out, plain, xcc_log2, gpx, chunks, rotate); \
+                       else if (NW == 8) hipLaunchKernelGGL((k_geo_fast<K, 8, 0>), grid, dim3(64, 4), 0, stream, frames, mats, img, W, H, n_imgs, img_stride, out, plain, xcc_log2, gpx, chunks, rotate); \
+                       else hipLaunchKernelGGL((k_geo_fast<K, 2, 0>), grid, dim3(64, 4), 0, stream, frames, mats, img, W, H, n_imgs, img_stride, out, plain, xcc_log2, gpx, chunks, rotate); } while (0)
         if (kind == 1 && plain) HG_GEO(4);
         else if (kind == 1 && f32_exact) HG_GEO(3);
         else if (kind == 1) HG_GEO(1);
@@ -205,8 +238,10 @@ void launch_geo(int kind, bool f32_exact, const FrameDesc *frames, const double 
         return;
     }
     dim3 grid((max_w + 255) / 256, (max_h + 3) / 4, n_frames);
-    if (kind == 0) hipLaunchKernelGGL(k_geo<0>, grid, dim3(64, 4), 0, stream, frames, mats, img, W, H, n_imgs, img_stride, out);
-    else           hipLaunchKernelGGL(k_geo<1>, grid, dim3(64, 4), 0, stream, frames, mats, img, W, H, n_imgs, img_stride, out);
+#define HG_GEO_G(K, S) hipLaunchKernelGGL((k_geo<K, S>), grid, dim3(64, 4), 0, stream, frames, mats, img, W, H, n_imgs, img_stride, out)
+    if (kind == 0) { if (bil) HG_GEO_G(0, 1); else HG_GEO_G(0, 0); }
+    else           { if (bil) HG_GEO_G(1, 1); else HG_GEO_G(1, 0); }
+#undef HG_GEO_G
 }
 
 // ------------------------------------------------------------------------------------------------ k_solve_frames

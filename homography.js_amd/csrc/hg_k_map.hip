@@ -51,7 +51,8 @@ __global__ void k_map_max_i16(const int32_t *__restrict__ m32, size_t n, int32_t
     if ((threadIdx.x & 63) == 0 && best >= 0) atomicMax(out, best);
 }
 
-// Pixel loop :1042-1056 reading the materialised map.  Block = 64 x 4 threads = 4 rows x 256 pixels.
+// Pixel loop :1042-1056 reading the materialised map.  Block = 64 x 4 threads = 4 rows x 256 pixels.  S: sampling mode (pw_pixel_mode).
+template <int S>
 __global__ __launch_bounds__(256) void k_pw_from_map(PwMesh mesh, const float *__restrict__ invm, FrameDesc fd,
                                                      const int32_t *__restrict__ map32, uint8_t *__restrict__ out)
 {
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(256) void k_pw_from_map(PwMesh mesh, const float *_
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const int tid = (cq + k < W) ? map32[row0 + cq + k] : -1;
-        px[k] = pw_pixel(tid, cq + k + fd.x_off, y, mc, invm, img32, n_src_px, mesh.W, mesh.H, bx0, bx1, by0, by1);
+        px[k] = pw_pixel_mode<S>(tid, cq + k + fd.x_off, y, mc, invm, img32, n_src_px, mesh.W, mesh.H, bx0, bx1, by0, by1);
     }
     store_quad(orow, cq, W, vec_ok, px);
 }
@@ -94,12 +95,13 @@ void launch_map_build(const PwMesh &mesh, const PwFrames &fr, int f, const Frame
 }
 
 void launch_pw_from_map(const PwMesh &mesh, const PwFrames &fr, int f, const FrameDesc &fd, const int32_t *map32,
-                        uint8_t *out, hipStream_t stream)
+                        uint8_t *out, int sampling, hipStream_t stream)
 {
     if (fd.obj_w <= 0 || fd.obj_h <= 0) return;
     dim3 grid((fd.obj_w + 255) / 256, (fd.obj_h + 3) / 4);
-    hipLaunchKernelGGL(k_pw_from_map, grid, dim3(64, 4), 0, stream, mesh,
-                       (const float *)(fr.inv + (size_t)f * mesh.n_tris * kInvStride), fd, map32, out);
+    const float *invm = fr.inv + (size_t)f * mesh.n_tris * kInvStride;
+    if (sampling == 1) hipLaunchKernelGGL(k_pw_from_map<1>, grid, dim3(64, 4), 0, stream, mesh, invm, fd, map32, out);
+    else               hipLaunchKernelGGL(k_pw_from_map<0>, grid, dim3(64, 4), 0, stream, mesh, invm, fd, map32, out);
 }
 
 void launch_map_max_i16(const int32_t *map32, size_t n, int32_t *out, hipStream_t stream)

@@ -164,6 +164,9 @@ __global__ __launch_bounds__(256) void k_tri_setup(PwMesh mesh, PwFrames fr)
 //   phase 2: each wave walks 256-pixel windows of the row; the spans overlapping a window are found with one ballot
 //            per 64 spans, and each lane keeps max(id) over the spans covering its 4 pixels ("last writer wins" of
 //            the sequential fill loop :852-858 == largest id); then the pixel loop body :1044-1053.
+// S: sampling mode (0 nearest, the reference's body; 1 bilinear, pw_pixel_bilinear -- the only piecewise kernel of that mode besides
+// k_pw_from_map, which redoes the frames this one flags).
+template <int S>
 __global__ __launch_bounds__(256) void k_pw_fused(PwMesh mesh, PwFrames fr, uint8_t *__restrict__ out, int16_t *__restrict__ map_out)
 {
     const int f = blockIdx.y;
@@ -247,7 +250,7 @@ __global__ __launch_bounds__(256) void k_pw_fused(PwMesh mesh, PwFrames fr, uint
             MatCache mc; mc.id = -1;
 #pragma unroll
             for (int k = 0; k < 4; k++)
-                px[k] = pw_pixel(tid[k], cq + k + fd.x_off, y, mc, invm, img32, n_src_px, mesh.W, mesh.H, bx0, bx1, by0, by1);
+                px[k] = pw_pixel_mode<S>(tid[k], cq + k + fd.x_off, y, mc, invm, img32, n_src_px, mesh.W, mesh.H, bx0, bx1, by0, by1);
             store_quad(orow, cq, W, vec_ok, px);
             if (map_out) {
 #pragma unroll
@@ -955,11 +958,12 @@ void launch_tri_setup(const PwMesh &mesh, const PwFrames &fr, hipStream_t stream
     else             hipLaunchKernelGGL(k_tri_setup<false>, grid, dim3(256), 0, stream, mesh, fr);
 }
 
-void launch_pw_fused(const PwMesh &mesh, const PwFrames &fr, uint8_t *out, int16_t *map_out, hipStream_t stream)
+void launch_pw_fused(const PwMesh &mesh, const PwFrames &fr, uint8_t *out, int16_t *map_out, int sampling, hipStream_t stream)
 {
     if (fr.n_frames <= 0 || fr.max_obj_h <= 0) return;
     dim3 grid(fr.max_obj_h, fr.n_frames);
-    hipLaunchKernelGGL(k_pw_fused, grid, dim3(256), 0, stream, mesh, fr, out, map_out);
+    if (sampling == 1) hipLaunchKernelGGL(k_pw_fused<1>, grid, dim3(256), 0, stream, mesh, fr, out, map_out);
+    else               hipLaunchKernelGGL(k_pw_fused<0>, grid, dim3(256), 0, stream, mesh, fr, out, map_out);
 }
 
 bool pw_fast_ok(const PwMesh &mesh, int max_obj_w)

@@ -118,7 +118,8 @@ void launch_upload(const UploadSegs &sg, hipStream_t stream);              // sm
 // k_pw_fused: _inversePiecewiseAffineWarp :1029-1058 for all frames, one workgroup per output row, without a
 // materialised triangle map.  map_out (optional, int16 per output pixel) receives the per-pixel triangle id the
 // lookup resolved == the reference's _trianglesCorrespondencesMatrix.
-void launch_pw_fused(const PwMesh &mesh, const PwFrames &fr, uint8_t *out, int16_t *map_out, hipStream_t stream);
+// sampling: HG_SAMPLE_NEAREST (0, the reference's pixel body) or HG_SAMPLE_BILINEAR (1), here and in launch_pw_from_map / launch_geo.
+void launch_pw_fused(const PwMesh &mesh, const PwFrames &fr, uint8_t *out, int16_t *map_out, int sampling, hipStream_t stream);
 
 // Fast path (see hg_k_piecewise.hip): eligibility, span-list build (includes the per-triangle solves), row warp.
 bool pw_fast_ok(const PwMesh &mesh, int max_obj_w);
@@ -140,7 +141,7 @@ int launch_pw_tile(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl, u
 // the pixel loop :1042-1056 reading the map.
 void launch_map_build(const PwMesh &mesh, const PwFrames &fr, int f, const FrameDesc &fd, int32_t *map32, hipStream_t stream);
 void launch_pw_from_map(const PwMesh &mesh, const PwFrames &fr, int f, const FrameDesc &fd, const int32_t *map32,
-                        uint8_t *out, hipStream_t stream);
+                        uint8_t *out, int sampling, hipStream_t stream);
 void launch_map_to_i16(const int32_t *map32, int16_t *map16, size_t n, hipStream_t stream);
 void launch_map_max_i16(const int32_t *map32, size_t n, int32_t *out, hipStream_t stream);      // *out = largest (int16) value of the first n cells, -1 if none
 void launch_fill_i32(int32_t *p, size_t n, int32_t v, hipStream_t stream);      // grid-stride fill (map / winner-buffer initialisation)
@@ -149,7 +150,8 @@ void launch_fill_i32(int32_t *p, size_t n, int32_t v, hipStream_t stream);      
 // f32_exact: every affine matrix entry is a float value and |x| < 2^28 (lets the kernel use an exact-product fma).
 // n_imgs / img_stride: frame f reads the source at img + (f % n_imgs) * img_stride.
 void launch_geo(int kind, bool f32_exact, const FrameDesc *frames, const double *mats, int n_frames, int max_w, int max_h,
-                const uint8_t *img, int W, int H, int n_imgs, uint64_t img_stride, uint8_t *out, const int32_t *plain, int nw, int xcc_log2, bool rotate_bands, hipStream_t stream);
+                const uint8_t *img, int W, int H, int n_imgs, uint64_t img_stride, uint8_t *out, const int32_t *plain, int nw, int xcc_log2, bool rotate_bands,
+                int sampling, hipStream_t stream);
 // Per-frame matrix solves on the device (one lane per frame): kind 1 = projective 8x8 DLT in numeric.js' LU order, 4 points
 // per set; kind 0 = affine closed form, 3 points per set.  mats = F x 8 doubles; plain[f] = 1 where the projective frame's
 // window stays in the plain division range (launch_geo then takes the per-frame flag instead of a host proof).

@@ -68,6 +68,14 @@ extern "C" const char *hg_multi_last_error(const hg_multi *m) { return m ? m->er
 extern "C" int hg_multi_device_count(const hg_multi *m) { return m ? (int)m->devs.size() : 0; }
 extern "C" hg_ctx *hg_multi_ctx(hg_multi *m, int i) { return (m && i >= 0 && i < (int)m->devs.size()) ? m->devs[i].ctx : nullptr; }
 
+extern "C" int hg_multi_set_sampling(hg_multi *m, int mode)
+{
+    if (!m) return mfail(nullptr, HG_ERR_INVALID, "hg_multi_set_sampling: multi is NULL");
+    if (mode != HG_SAMPLE_NEAREST && mode != HG_SAMPLE_BILINEAR) return mfail(m, HG_ERR_INVALID, "hg_multi_set_sampling: unknown mode " + std::to_string(mode));
+    for (hg_multi::Dev &d : m->devs) MHG(m, d.ctx, hg_set_sampling(d.ctx, mode));
+    return HG_OK;
+}
+
 extern "C" void hg_multi_destroy(hg_multi *m)
 {
     if (!m) return;

@@ -758,6 +758,18 @@ static napi_value fn_redone_frames(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* setSampling(handle, mode): HG_SAMPLE_NEAREST (0) / HG_SAMPLE_BILINEAR (1) for the inverse warps called from now on */
+static napi_value fn_set_sampling(napi_env env, napi_callback_info info)
+{
+    napi_value a[2];
+    if (!get_args(env, info, 2, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    int mode;
+    if (!get_i32(env, a[1], &mode)) return NULL;
+    HG_CALL(h->ctx, "hg_set_sampling", hg_set_sampling(h->ctx, mode));
+    return NULL;
+}
+
 static napi_value fn_get_matrices(napi_env env, napi_callback_info info)
 {
     napi_value a[2];
@@ -1100,6 +1112,18 @@ static napi_value fn_multi_destroy(napi_env env, napi_callback_info info)
     return NULL;
 }
 
+static napi_value fn_multi_set_sampling(napi_env env, napi_callback_info info)
+{
+    napi_value a[2];
+    if (!get_args(env, info, 2, a)) return NULL;
+    mhandle_t *h = get_mhandle(env, a[0]); if (!h) return NULL;
+    int mode;
+    if (!get_i32(env, a[1], &mode)) return NULL;
+    int rc = hg_multi_set_sampling(h->m, mode);
+    if (rc != HG_OK) return throw_multi(env, h->m, "hg_multi_set_sampling", rc);
+    return NULL;
+}
+
 static napi_value fn_multi_set_image(napi_env env, napi_callback_info info)
 {
     napi_value a[4];
@@ -1264,7 +1288,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "releaseBatch", fn_release_batch }, { "pinnedBuffer", fn_pinned_buffer },
         { "solveAffineTriangles", fn_solve_affine_triangles }, { "warpInversePiecewiseState", fn_warp_inverse_piecewise_state },
         { "warpForwardPiecewiseState", fn_warp_forward_piecewise_state },
-        { "release", fn_release }, { "setPinnedLimit", fn_set_pinned_limit }, { "poolStats", fn_pool_stats }, { "redoneFrames", fn_redone_frames }, { "_poolTestFrames", fn_pool_test_frames }, { "poolPressure", fn_pool_pressure }, { "poolCollected", fn_pool_collected },
+        { "release", fn_release }, { "setPinnedLimit", fn_set_pinned_limit }, { "poolStats", fn_pool_stats }, { "redoneFrames", fn_redone_frames }, { "setSampling", fn_set_sampling }, { "multiSetSampling", fn_multi_set_sampling }, { "_poolTestFrames", fn_pool_test_frames }, { "poolPressure", fn_pool_pressure }, { "poolCollected", fn_pool_collected },
         { "multiCreate", fn_multi_create }, { "multiDestroy", fn_multi_destroy }, { "multiSetImage", fn_multi_set_image },
         { "multiSetMesh", fn_multi_set_mesh }, { "multiWarpBatch", fn_multi_warp_batch }, { "multiWarpGeometricBatch", fn_multi_warp_geometric_batch },
     };

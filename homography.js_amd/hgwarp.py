@@ -18,6 +18,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HGWARP_LIB") or os.path.join(HERE, "lib", "libhgwarp.so")
 
 HG_AFFINE, HG_PROJECTIVE = 0, 1
+# sampling modes of the inverse warps (hg_set_sampling): nearest is the reference's pixel copy, bilinear is opt-in
+SAMPLE_NEAREST, SAMPLE_BILINEAR = 0, 1
 
 # every symbol include/hgwarp.h declares (tests check that the built library exports all of them)
 EXPORTS = [
@@ -39,6 +41,7 @@ EXPORTS = [
     "hg_solve_affine_triangles", "hg_warp_inverse_piecewise_state", "hg_warp_forward_piecewise_state",
     "hg_upload_on_copy_stream", "hg_fence_copies", "hg_download_behind_warps", "hg_fence_downloads",
     "hg_set_timing", "hg_last_kernel_ms", "hg_kernel_ms_stats", "hg_last_piecewise_kernel", "hg_last_piecewise_variant", "hg_last_piecewise_self", "hg_last_piecewise_flag", "hg_last_forward_kernel", "hg_forward_tiles_admissible", "hg_redone_frames", "hg_layout_walks", "hg_set_option", "hg_xcc_count", "hg_selftest_division", "hg_projective_plain_range", "hg_affine_one_fma_form",
+    "hg_set_sampling", "hg_get_sampling", "hg_multi_set_sampling",
 ]
 
 
@@ -108,7 +111,8 @@ def lib():
         "hg_warp_inverse_piecewise_batch_device": (i, [vp, f32p, C.POINTER(Geom), C.POINTER(sz), i, vp]),
         "hg_get_tri_map": (i, [vp, C.POINTER(C.c_int16), sz]), "hg_get_tri_map_fused": (i, [vp, C.POINTER(C.c_int16), sz]),
         "hg_get_matrices": (i, [vp, f32p, f32p]), "hg_warp_inverse_piecewise_via_map": (i, [vp, u8p]),
-        "hg_last_piecewise_kernel": (i, [vp]), "hg_last_piecewise_variant": (i, [vp]), "hg_last_piecewise_self": (i, [vp]), "hg_last_piecewise_flag": (i, [vp]), "hg_last_forward_kernel": (i, [vp]), "hg_set_option": (i, [vp, C.c_char_p, i]), "hg_redone_frames": (C.c_long, [vp]), "hg_layout_walks": (C.c_long, [vp]), "hg_xcc_count": (i, [vp]),
+        "hg_last_piecewise_kernel": (i, [vp]), "hg_last_piecewise_variant": (i, [vp]), "hg_last_piecewise_self": (i, [vp]), "hg_last_piecewise_flag": (i, [vp]), "hg_last_forward_kernel": (i, [vp]), "hg_set_option": (i, [vp, C.c_char_p, i]),
+        "hg_set_sampling": (i, [vp, i]), "hg_get_sampling": (i, [vp, C.POINTER(i)]), "hg_multi_set_sampling": (i, [vp, i]), "hg_redone_frames": (C.c_long, [vp]), "hg_layout_walks": (C.c_long, [vp]), "hg_xcc_count": (i, [vp]),
         "hg_selftest_division": (i, [vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
         "hg_projective_plain_range": (i, [f64p, Geom]), "hg_affine_one_fma_form": (i, [f32p, Geom]), "hg_forward_tiles_admissible": (i, [i, f64p, i, i, Geom]),
         "hg_set_timing": (i, [vp, i]), "hg_last_kernel_ms": (i, [vp, f32p]),
@@ -366,6 +370,16 @@ class Context:
     def set_option(self, key, value):
         """Layout knobs of the piecewise fast path ("min_row_groups", "patch"); results never depend on them."""
         self._c(lib().hg_set_option(self._h, key.encode(), int(value)))
+
+    def set_sampling(self, mode):
+        """SAMPLE_NEAREST (default, the reference's pixel copy) or SAMPLE_BILINEAR for the inverse warps called from now on."""
+        self._c(lib().hg_set_sampling(self._h, int(mode)))
+
+    @property
+    def sampling(self):
+        m = C.c_int(-1)
+        self._c(lib().hg_get_sampling(self._h, C.byref(m)))
+        return m.value
 
     def selftest_division(self, samples, seed=1):
         """Mismatches between the shared-reciprocal division of the projective kernel and IEEE division (must be 0)."""
@@ -639,6 +653,10 @@ class Multi:
         for k in range(self.device_count()):
             ctx = lib().hg_multi_ctx(self._h, k)
             _check(lib().hg_set_option(C.c_void_p(ctx), key.encode(), int(value)), C.c_void_p(ctx))
+
+    def set_sampling(self, mode):
+        """Context.set_sampling on every per-device context."""
+        self._c(lib().hg_multi_set_sampling(self._h, int(mode)))
 
     def set_image(self, rgba):
         a = np.ascontiguousarray(rgba, dtype=np.uint8)

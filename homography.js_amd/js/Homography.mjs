@@ -62,6 +62,7 @@ function makeRoomFor(native, bytes, n) {
 }
 
 const TRANSFORMS = ['auto', 'piecewiseaffine', 'affine', 'projective'];
+const SAMPLING = ['nearest', 'bilinear'];       // index = HG_SAMPLE_NEAREST / HG_SAMPLE_BILINEAR
 const CSS_DECIMALS = 5;                 // :31
 const NORMALIZED_MAX = 8.0;             // :36  anything above is taken as pixel coordinates
 const AFFINE = 0, PROJECTIVE = 1;
@@ -141,6 +142,21 @@ class Homography {
         this._uploadedImage = null;
         this._ctxHandle = null;                                 // GPU context, created at the first warp
         this._multiHandle = null; this._multiKey = null; this._multiImage = null;   // hg_multi over a device list (warpBatch({devices}))
+        // Opt-in (not in the reference): {sampling: 'bilinear'} blends the four source pixels around each inverse-mapped coordinate
+        // (include/hgwarp.h, hg_set_sampling) instead of copying the nearest one.  Every warp then takes the inverse loop -- the
+        // forward (scatter) loops copy pixels by definition.  Default 'nearest': the reference's pixels, and no extra addon call.
+        this._sampling = 'nearest';
+        if (options.sampling !== undefined) this.sampling = options.sampling;
+    }
+
+    /** 'nearest' (default, the reference's pixel copy) or 'bilinear' (opt-in); applies to the warps called from now on. */
+    get sampling() { return this._sampling; }
+    set sampling(mode) {
+        if (!SAMPLING.includes(mode)) throw (`hgwarp: sampling must be 'nearest' or 'bilinear', but ${mode} was given`);
+        if (mode === this._sampling) return;
+        this._sampling = mode;
+        if (this._ctxHandle) this._native.setSampling(this._ctxHandle, SAMPLING.indexOf(mode));
+        if (this._multiHandle) this._native.multiSetSampling(this._multiHandle, SAMPLING.indexOf(mode));
     }
 
     /** Which map the shared field would hold: null | 'forward' | 'inverse'. */
@@ -148,7 +164,10 @@ class Homography {
 
     /** GPU context of this instance (one hg_ctx per Homography).  Throws a string without a usable gfx950 device. */
     get _ctx() {
-        if (this._ctxHandle === null) this._ctxHandle = this._native.create(this._device);
+        if (this._ctxHandle === null) {
+            this._ctxHandle = this._native.create(this._device);
+            if (this._sampling !== 'nearest') this._native.setSampling(this._ctxHandle, SAMPLING.indexOf(this._sampling));
+        }
         return this._ctxHandle;
     }
 
@@ -239,6 +258,7 @@ class Homography {
             throw ("warp() must receive an image if it was not setted before through `setImage(img)` or  `setSourcePoints(points, img)`");
         }
         if (asHTMLPromise) throw ("hgwarp: asHTMLPromise needs a browser DOM; use the returned ImageData-shaped object");
+        if (this._sampling === 'bilinear') applyAlwaysInverse = true;                                  // (the forward loops have nothing to blend)
         let out;
         switch (this.transform) {
             case 'piecewiseaffine':
@@ -293,7 +313,7 @@ class Homography {
             if (this._image === null && !options.images) throw ("warp() must receive an image if it was not setted before through `setImage(img)` or  `setSourcePoints(points, img)`");   // the loop's first warp() (:411-413)
             all.set(asF32(this._dstPoints), f * n);
             const [xo, yo, ow, oh] = this._window();
-            forward[f] = !(options.inverse === true || ow > this._width || oh > this._height || ow * 1.2 < this._width || oh * 1.2 < this._height);   // :421-422
+            forward[f] = !(options.inverse === true || this._sampling === 'bilinear' || ow > this._width || oh > this._height || ow * 1.2 < this._width || oh * 1.2 < this._height);   // :421-422
             blank[f] = !(ow * oh >= 1);                                                                 // :440: a 1 x 1 blank frame
             // the shared map field, carried from frame to frame as the loop would: an inverse frame leaves its own map there (:847-857),
             // a forward frame reads what it finds
@@ -384,7 +404,7 @@ class Homography {
             this.setDestinyPoints(dstPointSets[f], options.pointsAreNormalized === undefined ? null : options.pointsAreNormalized);
             if (this._image === null && !options.images) throw ("warp() must receive an image if it was not setted before through `setImage(img)` or  `setSourcePoints(points, img)`");   // the loop's first warp() (:411-413)
             const [xo, yo, ow, oh] = this._window();
-            forward[f] = this.transform === 'affine' && options.inverse !== true && ow === this._width && oh === this._height;      // :426-427, :431
+            forward[f] = this.transform === 'affine' && options.inverse !== true && this._sampling !== 'bilinear' && ow === this._width && oh === this._height;      // :426-427, :431
             if (forward[f]) mats.set(Array.from(this._transformMatrix), f * 8);                          // _geometricWarp uses _transformMatrix as it stands (:915)
             else {
                 this._alignRanges();                                                                     // :993
@@ -444,6 +464,7 @@ class Homography {
             if (this._multiHandle) this._native.multiDestroy(this._multiHandle);
             this._multiHandle = this._native.multiCreate(ids);
             this._multiKey = key; this._multiImage = null;
+            if (this._sampling !== 'nearest') this._native.multiSetSampling(this._multiHandle, SAMPLING.indexOf(this._sampling));
         }
         return this._multiHandle;
     }

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define HG_VERSION 100          /* 0.1.0 */
+#define HG_VERSION 100          /* 0.1.0 (sampling modes are detected by the presence of hg_set_sampling) */
 
 enum {
     HG_OK = 0,
@@ -47,6 +47,9 @@ enum {
 };
 
 enum { HG_AFFINE = 0, HG_PROJECTIVE = 1 };
+
+/* Sampling modes of the inverse warps (hg_set_sampling).  Not part of the reference, which always copies the nearest pixel. */
+enum { HG_SAMPLE_NEAREST = 0, HG_SAMPLE_BILINEAR = 1 };
 
 typedef struct hg_ctx hg_ctx;
 
@@ -75,6 +78,25 @@ const char *hg_last_error(const hg_ctx *ctx);
  * same holds for queued hg_warp_forward_piecewise_batch_device calls (tile lists over capacity, triangles the tiles cannot bound).
  * A frame is final once hg_sync (or any synchronous call) has returned. */
 int hg_sync(hg_ctx *ctx);
+/* Sampling mode of the ctx (HG_ERR_INVALID for any other value; the default is HG_SAMPLE_NEAREST).
+ *   HG_SAMPLE_NEAREST   the reference's Math.round(srcX) pixel copy (:1005-1007, :1048-1052), bit-identical to it.
+ *   HG_SAMPLE_BILINEAR  opt-in, not the reference's.  The source coordinate (sx, sy) is computed exactly as in nearest mode (f64,
+ *                       JS operation order) and the coverage test is unchanged (:1001; :1045-1047 with the minSrc bounds for
+ *                       piecewise): a pixel is written iff nearest mode writes it, uncovered pixels stay all-zero.  Taps:
+ *                       x0 = floor(sx), y0 = floor(sy), fx = (float)(sx - x0), fy = (float)(sy - y0); columns clamp(x0, 0, W-1) and
+ *                       clamp(x0+1, 0, W-1), rows alike (piecewise indexes the source as the reference does: no minSrc subtraction).
+ *                       No read leaves the image: nearest mode's wrap of the flat index does not exist here.  Blend: straight
+ *                       (not premultiplied) RGBA, each channel in f32,
+ *                           v = (p00*(1-fx) + p01*fx)*(1-fy) + (p10*(1-fx) + p11*fx)*fy,   out = (uint8)min(255, floor(v + 0.5f)),
+ *                       so that where fx == fy == 0 the result equals the nearest one byte for byte.
+ * The mode governs the INVERSE warps: single-frame, frame-set, batch and `_device` forms, per-frame sources (hg_set_images_device),
+ * hg_warp_inverse_piecewise_via_map, hg_warp_inverse_piecewise_state and the hg_multi_* batches.  The forward (scatter) entry points
+ * copy source pixels by definition and ignore it; so do the taps (hg_get_tri_map*, hg_get_matrices).  The mode in effect when a warp
+ * entry point is called governs that warp, whichever mode its frame set was staged under; work already queued keeps the mode it was
+ * queued with, including the frames hg_sync redoes through the map.  Bilinear piecewise warps run on the general kernel
+ * (hg_last_piecewise_kernel() == 4) and are settled within the call.  Not an hg_set_option knob: it changes results. */
+int hg_set_sampling(hg_ctx *ctx, int mode);
+int hg_get_sampling(const hg_ctx *ctx, int *mode);
 /* Device scratch/output helpers so that bindings without a device allocator (Node) can keep frames resident. */
 int hg_device_alloc(hg_ctx *ctx, size_t bytes, void **dptr);
 int hg_device_free(hg_ctx *ctx, void *dptr);
@@ -282,6 +304,8 @@ void hg_multi_destroy(hg_multi *multi);
 const char *hg_multi_last_error(const hg_multi *multi);
 int hg_multi_device_count(const hg_multi *multi);
 hg_ctx *hg_multi_ctx(hg_multi *multi, int index);                       /* the per-device context (options, taps) */
+/* hg_set_sampling on every per-device context (HG_ERR_INVALID for an unknown mode, no context changed). */
+int hg_multi_set_sampling(hg_multi *multi, int mode);
 /* Peer access is checked and enabled pair by pair at hg_multi_create.  hg_multi_peer_note: "" when every pair of distinct devices
  * has it, else a text listing the pairs without ("no peer access: 2->3, 3->2"); hg_multi_peer_access: 1 / 0 for one ordered pair of
  * indices into the device list (-1: bad index).  A pair without access only re-routes ITS copies of the source fan-out. */
