@@ -220,6 +220,7 @@ extern "C" int hg_copy_to_device(hg_ctx *c, void *dst, const void *src, size_t b
 
 extern "C" int hg_last_piecewise_kernel(hg_ctx *c) { return c ? c->pw_last_kernel : 0; }
 extern "C" int hg_last_piecewise_variant(hg_ctx *c) { return c ? c->pw_last_variant : 0; }
+extern "C" int hg_last_geometric_kernel(hg_ctx *c) { return c ? c->geo_last_kernel : -1; }
 extern "C" int hg_last_forward_kernel(hg_ctx *c) { return c ? c->fwd_last_kernel : 0; }
 
 extern "C" int hg_last_piecewise_self(hg_ctx *c) { return c && c->pw_self ? 1 : 0; }

@@ -210,12 +210,12 @@ __global__ __launch_bounds__(256) void k_geo_fast(const FrameDesc *__restrict__ 
     }
 }
 
-void launch_geo(int kind, bool f32_exact, const FrameDesc *frames, const double *mats, int n_frames, int max_w, int max_h,
-                const uint8_t *img, int W, int H, int n_imgs, uint64_t img_stride, uint8_t *out, const int32_t *plain, int nw, int xcc_log2, bool rotate_bands,
-                int sampling, hipStream_t stream)
+int launch_geo(int kind, bool f32_exact, const FrameDesc *frames, const double *mats, int n_frames, int max_w, int max_h,
+               const uint8_t *img, int W, int H, int n_imgs, uint64_t img_stride, uint8_t *out, const int32_t *plain, int nw, int xcc_log2, bool rotate_bands,
+               int sampling, hipStream_t stream)
 {
     const int rotate = rotate_bands ? 1 : 0;
-    if (n_frames <= 0 || max_w <= 0 || max_h <= 0) return;
+    if (n_frames <= 0 || max_w <= 0 || max_h <= 0) return -1;
     const bool fast = ((int64_t)H + 2) * W * 4 < ((int64_t)1 << 31) && hi_bounds_ok(0, W, 0, H) && max_w < (1 << 28);
     const bool bil = sampling == 1;
     if (fast) {
@@ -229,19 +229,21 @@ void launch_geo(int kind, bool f32_exact, const FrameDesc *frames, const double 
                        else if (NW == 4) hipLaunchKernelGGL((k_geo_fast<K, 4, 0>), grid, dim3(64, 4), 0, stream, frames, mats, img, W, H, n_imgs, img_stride, out, plain, xcc_log2, gpx, chunks, rotate); \
                        else if (NW == 8) hipLaunchKernelGGL((k_geo_fast<K, 8, 0>), grid, dim3(64, 4), 0, stream, frames, mats, img, W, H, n_imgs, img_stride, out, plain, xcc_log2, gpx, chunks, rotate); \
                        else hipLaunchKernelGGL((k_geo_fast<K, 2, 0>), grid, dim3(64, 4), 0, stream, frames, mats, img, W, H, n_imgs, img_stride, out, plain, xcc_log2, gpx, chunks, rotate); } while (0)
-        if (kind == 1 && plain) HG_GEO(4);
-        else if (kind == 1 && f32_exact) HG_GEO(3);
-        else if (kind == 1) HG_GEO(1);
-        else if (f32_exact) HG_GEO(0);
-        else                HG_GEO(2);
+        const int K = kind == 1 ? (plain ? 4 : (f32_exact ? 3 : 1)) : (f32_exact ? 0 : 2);
+        if (K == 4) HG_GEO(4);
+        else if (K == 3) HG_GEO(3);
+        else if (K == 1) HG_GEO(1);
+        else if (K == 0) HG_GEO(0);
+        else             HG_GEO(2);
 #undef HG_GEO
-        return;
+        return 100 * K + 10 * (bil ? 8 : NW) + (bil ? 1 : 0);
     }
     dim3 grid((max_w + 255) / 256, (max_h + 3) / 4, n_frames);
 #define HG_GEO_G(K, S) hipLaunchKernelGGL((k_geo<K, S>), grid, dim3(64, 4), 0, stream, frames, mats, img, W, H, n_imgs, img_stride, out)
     if (kind == 0) { if (bil) HG_GEO_G(0, 1); else HG_GEO_G(0, 0); }
     else           { if (bil) HG_GEO_G(1, 1); else HG_GEO_G(1, 0); }
 #undef HG_GEO_G
+    return 1000 + 10 * (kind == 0 ? 0 : 1) + (bil ? 1 : 0);
 }
 
 // ------------------------------------------------------------------------------------------------ k_solve_frames

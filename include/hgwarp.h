@@ -351,6 +351,12 @@ int hg_last_piecewise_kernel(hg_ctx *ctx);
  * (512-slot rows) * 10000 + windows / blocks per phase * 1000 + (8-byte row entries) * 100 + (bounds on the high dwords) * 10 + self-span
  * form; kind 1 k_pw_rows, 3 k_pw_rows_s80, 4 k_pw_patch, 5 k_pw_tile, 6 k_pw_fused, 8 k_pw_patch with records in global memory. */
 int hg_last_piecewise_variant(hg_ctx *ctx);
+/* Which kernel ran the last inverse geometric warp of this ctx (tests / profiling): -1 = none yet; 100 * KIND + 10 * NW + S for
+ * k_geo_fast<KIND, NW, S> (KIND 0 affine with f32-valued entries, 2 affine with arbitrary doubles, 1 projective with IEEE divisions,
+ * 3 projective in the proven plain division range, 4 projective per frame from the device-side solve; NW windows per wave; S the
+ * sampling mode); 1000 + 10 * kind + S for the generic k_geo<kind, S> (kind HG_AFFINE / HG_PROJECTIVE), which takes sources of 2^20
+ * pixels or more in width or height, sources of 2 GiB or more, and windows of 2^28 pixels or more in width. */
+int hg_last_geometric_kernel(hg_ctx *ctx);
 /* 1 if that run's row workgroups evaluated their own spans (k_tri_setup + k_pw_rows<SELF>: no row lists, no slot atomics, option
  * "self_spans"), 0 if they read the per-output-row span lists of k_tri_spans. */
 int hg_last_piecewise_self(hg_ctx *ctx);

@@ -8,8 +8,9 @@ F32 = np.float32
 
 
 def sample(img, sx, sy, covered):
-    """RGBA8 of every position of sx / sy (f64 arrays of one shape); positions where `covered` is False stay all-zero."""
-    img = np.ascontiguousarray(img, np.uint8)
+    """RGBA8 of every position of sx / sy (f64 arrays of one shape); positions where `covered` is False stay all-zero.  Only the four
+    taps of the covered positions are converted to f32 (a source of 2 GiB or more is never copied)."""
+    img = np.asarray(img, np.uint8)
     H, W = img.shape[:2]
     out = np.zeros(sx.shape + (4,), np.uint8)
     x, y = sx[covered], sy[covered]
@@ -18,9 +19,10 @@ def sample(img, sx, sy, covered):
     xi, yi = x0.astype(np.int64), y0.astype(np.int64)
     c0, c1 = np.clip(xi, 0, W - 1), np.clip(xi + 1, 0, W - 1)
     r0, r1 = np.clip(yi, 0, H - 1), np.clip(yi + 1, 0, H - 1)
-    p = img.astype(F32)
+    p00, p01 = img[r0, c0].astype(F32), img[r0, c1].astype(F32)
+    p10, p11 = img[r1, c0].astype(F32), img[r1, c1].astype(F32)
     gx, gy = F32(1) - fx, F32(1) - fy
-    v = (p[r0, c0] * gx + p[r0, c1] * fx) * gy + (p[r1, c0] * gx + p[r1, c1] * fx) * fy
+    v = (p00 * gx + p01 * fx) * gy + (p10 * gx + p11 * fx) * fy
     out[covered] = np.minimum(F32(255), np.floor(v + F32(0.5))).astype(np.uint8)
     return out
 

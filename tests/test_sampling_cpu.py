@@ -2,10 +2,12 @@
 hand-computed cases, and the JavaScript class's {sampling} option over a mock addon that records the addon calls."""
 import ctypes as C
 import json
+import math
 import os
 import shutil
 import subprocess
 import sys
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -108,3 +110,129 @@ def test_js_class_sampling_option_over_the_mock_addon():
     res = json.loads(line[-1])
     assert res["failures"] == [] and p.returncode == 0
     assert res["checks"] >= 30
+
+
+# ------------------------------------------------------------------------------------------------ two references for the model
+# The vectorised model (tests/hgtest/bilinear.py) and the kernels came in one change.  Here the model is held against a scalar
+# form written from the header's text (include/hgwarp.h, hg_set_sampling), one np.float32 operation per step, and against exact
+# rational interpolation.
+
+def _scalar_sample(img, sx, sy):
+    """One position, straight from the header: x0 = floor(sx), fx = (float)(sx - x0), clamped taps, the f32 blend in its written
+    order, min(255, floor(v + 0.5f))."""
+    H, W = img.shape[:2]
+    x0, y0 = float(math.floor(sx)), float(math.floor(sy))
+    fx, fy = np.float32(sx - x0), np.float32(sy - y0)                    # (the f64 difference is exact)
+    ix, iy = int(x0), int(y0)
+    c0, c1 = min(max(ix, 0), W - 1), min(max(ix + 1, 0), W - 1)
+    r0, r1 = min(max(iy, 0), H - 1), min(max(iy + 1, 0), H - 1)
+    one, half = np.float32(1.0), np.float32(0.5)
+    gx = one - fx
+    gy = one - fy
+    out = []
+    for ch in range(4):
+        a, b = np.float32(img[r0, c0, ch]), np.float32(img[r0, c1, ch])
+        c, d = np.float32(img[r1, c0, ch]), np.float32(img[r1, c1, ch])
+        top = a * gx
+        top = top + b * fx
+        top = top * gy
+        bot = c * gx
+        bot = bot + d * fx
+        bot = bot * fy
+        v = top + bot
+        out.append(int(min(np.float32(255.0), np.floor(v + half))))
+    return out
+
+
+def _exact(img, sx, sy):
+    """Exact rational bilinear value of every channel at (sx, sy) (the exact fractions of the f64 coordinate, clamped taps)."""
+    H, W = img.shape[:2]
+    X, Y = Fraction(sx), Fraction(sy)
+    x0, y0 = math.floor(X), math.floor(Y)
+    fx, fy = X - x0, Y - y0
+    c0, c1 = min(max(x0, 0), W - 1), min(max(x0 + 1, 0), W - 1)
+    r0, r1 = min(max(y0, 0), H - 1), min(max(y0 + 1, 0), H - 1)
+    return [(int(img[r0, c0, ch]) * (1 - fx) + int(img[r0, c1, ch]) * fx) * (1 - fy) +
+            (int(img[r1, c0, ch]) * (1 - fx) + int(img[r1, c1, ch]) * fx) * fy for ch in range(4)]
+
+
+def _edge_coords(W, H, rng):
+    """Hand-picked coordinates: integers, n + 0.5 ties, fractions that round to 1.0f, the clamped right / bottom column and row,
+    negative coordinates (a piecewise mesh with a negative source minimum), all combined with each other."""
+    def axis(n):
+        v = [0.0, float(n - 1), n - 0.5, n - 1e-9, n - 2.0 ** -40, -0.25, -1.0, -2.5, -7.75]
+        for k in sorted(set([0, n // 2, max(n - 2, 0), n - 1])):
+            v += [float(k), k + 0.5, k + 1 - 2.0 ** -30, k + 1 - 2.0 ** -25, k + 2.0 ** -30, k + 0.25, k + 0.75]
+        v += list(n - 1 + rng.random(8))                   # [n-1, n): the upper tap clamps
+        return np.array(v)
+    xs, ys = axis(W), axis(H)
+    return np.repeat(xs, ys.size), np.tile(ys, xs.size)
+
+
+def _random_coords(W, H, n, rng):
+    xs = rng.uniform(-3.0, W, n)
+    ys = rng.uniform(-3.0, H, n)
+    q = rng.random(n) < 0.3                                # a third on coarse grids: exact ties of the blend (v = k + 0.5)
+    xs[q] = np.round(xs[q] * 4) / 4
+    ys[q] = np.round(ys[q] * 2) / 2
+    return xs, ys
+
+
+_SOURCES = [(1, 1), (1, 9), (9, 1), (2, 2), (7, 5), (64, 3), (3, 64), (250, 130)]
+
+
+def test_model_equals_the_scalar_form_of_the_header():
+    rng = np.random.default_rng(2026)
+    n_random = 0
+    for k, (W, H) in enumerate(_SOURCES):
+        img = rng.integers(0, 256, (H, W, 4), dtype=np.uint8)
+        if k % 2:                                          # saturated and near-saturated channels: the min(255, .) clamp
+            img[..., 1] = 255
+            img[..., 2] = rng.integers(250, 256, (H, W), dtype=np.uint8)
+        ex, ey = _edge_coords(W, H, rng)
+        rx, ry = _random_coords(W, H, 12500, rng)
+        n_random += rx.size
+        sx, sy = np.concatenate([ex, rx]), np.concatenate([ey, ry])
+        got = B.sample(img, sx, sy, np.ones(sx.shape, bool))
+        for i in range(sx.size):
+            want = _scalar_sample(img, float(sx[i]), float(sy[i]))
+            assert list(got[i]) == want, ((W, H), float(sx[i]), float(sy[i]), list(got[i]), want)
+    assert n_random >= 100000
+
+
+def test_model_against_exact_rational_interpolation():
+    """Within 1 everywhere; equal wherever the exact value is at least 2^-8 away from a .5 boundary (round half up)."""
+    rng = np.random.default_rng(77)
+    margin = Fraction(1, 256)
+    checked = 0
+    for k, (W, H) in enumerate(_SOURCES):
+        img = rng.integers(0, 256, (H, W, 4), dtype=np.uint8)
+        ex, ey = _edge_coords(W, H, rng)
+        rx, ry = _random_coords(W, H, 2500, rng)
+        sx, sy = np.concatenate([ex, rx]), np.concatenate([ey, ry])
+        got = B.sample(img, sx, sy, np.ones(sx.shape, bool))
+        for i in range(sx.size):
+            for ch, v in enumerate(_exact(img, float(sx[i]), float(sy[i]))):
+                r = math.floor(v + Fraction(1, 2))
+                g = int(got[i, ch])
+                assert abs(g - r) <= 1, ((W, H), float(sx[i]), float(sy[i]), ch, g, v)
+                if abs(v - math.floor(v) - Fraction(1, 2)) >= margin:
+                    assert g == r, ((W, H), float(sx[i]), float(sy[i]), ch, g, float(v))
+                checked += 1
+    assert checked >= 80000
+
+
+def test_model_rounds_half_up_and_fraction_to_one_takes_the_right_tap():
+    img = np.zeros((2, 3, 4), np.uint8)
+    img[0, :, 0] = [0, 1, 2]
+    img[1, :, 0] = [4, 6, 200]
+    one = np.ones(1, bool)
+    # an exact tie v = 0.5: round half up gives 1 (round half even would give 0)
+    assert B.sample(img, np.array([0.5]), np.array([0.0]), one)[0, 0] == 1
+    assert B.sample(img, np.array([1.5]), np.array([0.0]), one)[0, 0] == 2           # v = 1.5 -> 2 under both
+    assert B.sample(img, np.array([0.25]), np.array([0.5]), one)[0, 0] == 2          # v = 0 * .375 + 1 * .125 + 4 * .375 + 6 * .125 = 2.375
+    assert B.sample(img, np.array([0.75]), np.array([0.5]), one)[0, 0] == 3          # v = 0 * .125 + 1 * .375 + 4 * .125 + 6 * .375 = 3.125
+    # fx = (float)(1 - 2^-30) == 1.0f: the blend is all right tap, though x0 stays 0
+    assert B.sample(img, np.array([1 - 2.0 ** -30]), np.array([1.0]), one)[0, 0] == 6
+    # the right tap of the last column clamps to that column
+    assert B.sample(img, np.array([2.5]), np.array([1.0]), one)[0, 0] == 200
