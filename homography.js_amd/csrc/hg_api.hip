@@ -223,7 +223,7 @@ extern "C" int hg_last_piecewise_variant(hg_ctx *c) { return c ? c->pw_last_vari
 extern "C" int hg_last_geometric_kernel(hg_ctx *c) { return c ? c->geo_last_kernel : -1; }
 extern "C" int hg_last_forward_kernel(hg_ctx *c) { return c ? c->fwd_last_kernel : 0; }
 
-extern "C" int hg_last_piecewise_self(hg_ctx *c) { return c && c->pw_self ? 1 : 0; }
+extern "C" int hg_last_piecewise_self(hg_ctx *c) { return c && c->pw_plan.self ? 1 : 0; }
 extern "C" int hg_last_piecewise_flag(hg_ctx *c) { return c ? c->pw_last_flag : 0; }
 extern "C" long hg_redone_frames(hg_ctx *c) { return c ? c->pw_redone : 0; }
 extern "C" long hg_layout_walks(hg_ctx *c) { return c ? c->pw_layout_walks : 0; }
@@ -240,8 +240,8 @@ extern "C" int hg_set_option(hg_ctx *c, const char *key, int value)
     else if (!std::strcmp(key, "xcc_rotate")) c->opt_xcc_rotate = value;
     else if (!std::strcmp(key, "sub_bands")) c->opt_sub_bands = std::min(value, 64);
     else if (!std::strcmp(key, "compact")) c->opt_compact = value < 0 ? -1 : (value ? 1 : 0);
-    else if (!std::strcmp(key, "tile")) { c->opt_tile = value < 0 ? -1 : (value ? 1 : 0); c->pw_tile_disabled = false; }
-    else if (!std::strcmp(key, "self_spans")) { c->opt_self = value < 0 ? -1 : (value ? 1 : 0); c->pw_self_disabled = false; }
+    else if (!std::strcmp(key, "tile")) { c->opt_tile = value < 0 ? -1 : (value ? 1 : 0); c->pw_learned.tile_disabled = false; }
+    else if (!std::strcmp(key, "self_spans")) { c->opt_self = value < 0 ? -1 : (value ? 1 : 0); c->pw_learned.self_disabled = false; }
     else if (!std::strcmp(key, "tri_group")) c->opt_tri_group = value < 0 ? -1 : (value >= 64 ? 64 : (value ? 16 : 0));
     else if (!std::strcmp(key, "safe_spans")) c->opt_safe_spans = value < 0 ? -1 : (value ? 1 : 0);
     else if (!std::strcmp(key, "upload_kernel")) c->opt_upload_kernel = value < 0 ? -1 : (value ? 1 : 0);

@@ -209,10 +209,7 @@ extern "C" int hg_warp_forward_piecewise_batch_device(hg_ctx *c, const float *ds
         c->fwd_rowext_ok = false;
     }
     // (B) forward matrices of every frame (:785-804) in one launch, then scatter + gather frame after frame
-    c->pw_quick_layout = true;                               // (the inverse kernels' layout estimate is not needed here: no host walk over the triangles)
-    const int rc_frames = hg_piecewise_set_frames(c, dst_points, geoms, offs, n);
-    c->pw_quick_layout = false;
-    HG_TRY(rc_frames);
+    HG_TRY(piecewise_set_frames(c, dst_points, geoms, offs, n, true));     // (the inverse kernels' layout estimate is not needed here: no host walk over the triangles)
     c->status_ptr = c->d_status;                             // (k_tri_setup only ORs flags into these words and nothing on the forward path reads them: not cleared)
     { PwFrames fr_ = frames_of(c); fr_.band_ent = nullptr; fr_.two_round = nullptr; launch_tri_setup(mesh_of(c), fr_, c->stream); }   // (no candidate bands: the forward kernels have their own tile lists)
     c->pw_setup_done = false;

@@ -20,6 +20,47 @@ constexpr size_t kStatusRing = 64;      // fused piecewise runs that may be queu
 // ------------------------------------------------------------------------------------------------ errors
 extern thread_local std::string g_err;   // (hg_api.hip) message of the last failure on this thread, for calls without a context
 
+// ------------------------------------------------------------------------------------------------ piecewise layout policy (hg_api_piecewise.hip)
+// What the host knows about the uploaded frame set: its extents and the layout estimates of hg_piecewise_set_frames (reused for the
+// next set of the same shape: LayoutKey).  Estimates only pick kernel layouts; the kernels check the real counts.
+struct PwShape {
+    int n = 0;                          // frames
+    int max_w = 0, max_h = 0;           // largest obj_w; largest obj_h of the frames with obj_w > 0
+    int64_t groups = 0;                 // 4-row groups of the frame set
+    bool self_geom = true;              // every window suits the self-span prologue's int32 arithmetic (>= 16 columns, < 2^24 rows near the origin)
+    int min_row_groups = 1152;          // option "min_row_groups" when the set was staged (what "small set" and the k_pw_patch fit are measured by)
+    bool quick = false;                 // estimate guessed from the triangle count, no walk over the triangles
+    int cover = 0;                      // estimated longest per-row span list (max_row_cover)
+    double tri_rows = 0.0;              // mean rows per triangle
+    int group_tris = 0;                 // most triangles with spans in one 4-row group
+    double shear = 0.0;                 // mean |d(source row) / d(output x)|
+    int tri_rows_max = 0;               // tallest triangle, in rows (0: unknown)
+    double fill = 1.0;                  // heaviest XCD row band / mean band (span counts per row), 1 = even rows
+    double spans_per_window = 0.0;      // longest row's span count per 256-pixel window
+};
+
+// What runs of this mesh taught the policy: a kernel that exceeded its limits once is not taken again until a new mesh (or the option
+// that forces it) is set.  Written by hg_set_option, hg_piecewise_set_mesh and learn_from_overflows only.
+struct PwLearned {
+    bool patch_disabled = false;        // k_pw_patch (row lists or self-spans) -> k_pw_rows
+    bool tile_disabled = false;         // k_pw_tile -> k_pw_patch<SELF>
+    bool self_disabled = false;         // self-span prologues -> row lists
+};
+
+enum class PwKernel { Rows, Patch, PatchGlobal, Tile, Fused };
+
+// plan_piecewise's answer for one inverse piecewise step: the kernel, what run_setup lays out for it, and the launch scalars of PwFrames.
+struct PwPlan {
+    PwKernel kernel = PwKernel::Fused;  // Fused: the general path (k_tri_setup -> k_pw_fused); any other: k_tri_spans or k_tri_setup in front
+    bool self = false;                  // the warp kernel evaluates the spans of its own rows (k_tri_setup in front, no row lists)
+    bool bands = false;                 // ... scanning candidate bands of 64 output rows (n_bands of up to band_cap triangles)
+    int n_bands = 0, band_cap = 0;
+    bool compact = false;               // row lists of 8-byte entries (else 32-byte)
+    int row_cap = 64;                   // row-list entries per row the lists were sized for
+    int row_group = kRowGroup, tri_threads = 128;
+    int tri_group = 0, phase = 2, xcc_rotate = 0, sub_bands = 0, sgpr_cap = 1, lds_pad_kb = 0, no_hi_bounds = 0, safe_spans = 0, safe_spans_patch = 1;
+};
+
 struct hg_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -63,26 +104,17 @@ struct hg_ctx {
     // fast path: per-output-row span lists
     int32_t *d_rowcnt = nullptr; size_t rowcnt_cap = 0;
     uint8_t *d_rowent = nullptr; size_t rowent_cap = 0;        // bytes
-    int pw_cover = 0;                                          // estimated longest per-row span list of the uploaded frames
-    bool pw_compact = false;                                   // span lists use 8-byte entries (dense rows / k_pw_patch), else 32-byte
     int row_cap = 64;                                          // entries per row; grows (sticky) after an overflow
-    bool pw_fast = false;                                      // uploaded frames are eligible for k_tri_spans/k_pw_rows
     bool rows_clean = false;                                   // span counters + the next status set were zeroed by the last k_pw_rows
     int status_slot = 0;                                       // which of the kStatusRing status-word sets the current step uses
     int32_t *status_base = nullptr, *status_next = nullptr;
-    int pw_row_group = kRowGroup;                              // output rows per k_pw_rows workgroup (4, or 1 for dense meshes)
-    int pw_tri_threads = 128;                                  // k_tri_spans workgroup size
-    bool pw_patch = false;                                     // dense mesh that fits k_pw_patch (4-row groups, 2-D gather patches)
-    bool pw_patch_fits = false;                                // ... the frame set is within k_pw_patch's limits (it may be preferred later: one source per frame)
-    double pw_fill = 1.0;                                      // heaviest XCD row band / mean band (span counts per row), 1 = even rows
+    PwShape pw_shape;                                          // the uploaded frame set (hg_piecewise_set_frames)
+    PwLearned pw_learned;                                      // per-mesh fallbacks (learn_from_overflows)
+    PwPlan pw_plan;                                            // the plan of the last set-up (run_setup); frames_of / rows_of hand it to the kernels
     int opt_sub_bands = -1;                                    // option "sub_bands": sub-bands per XCD of the warp kernels on a shared source with fixed bands (0 / 1 off, -1 by the source's size)
     int opt_xcc_rotate = -1;                                   // -1 by estimate, 0 / 1
     int opt_compact = -1;                                      // span-list entry format: 1 = 8-byte entries, 0 = 32-byte entries with the matrix, -1 by estimate
-    double pw_shear = 0.0;                                     // mean |d(source row) / d(output x)| of the uploaded frames (layout heuristic)
-    bool pw_patch_dense = false;                               // ... only in its global-record variant (up to 511 spans per row)
-    bool pw_patch_disabled = false;                            // a group exceeded k_pw_patch's limits once: stay with k_pw_rows for this mesh
-    bool pw_used_patch = false;                                // the last fused run went through k_pw_patch
-    int pw_last_kernel = 0;                                    // hg_last_piecewise_kernel()
+    int pw_last_kernel = 0;                                    // hg_last_piecewise_kernel(): code of the plan the last warp carried out
     int geo_last_kernel = -1;                                  // hg_last_geometric_kernel(): launch_geo's code of the last geometric warp
     int32_t pw_last_flag = 0;                                  // status word of the last frame a fused run flagged (bits 4..: which limit, see k_pw_patch<SELF>)
     long pw_redone = 0;                                        // frames redone through the materialised map (hg_redone_frames())
@@ -95,9 +127,9 @@ struct hg_ctx {
     // stage: which staged frame set (points + windows) the run warped; extent / layout: the bytes it writes from `out` on and a hash of
     // its frames' (offset, size) list -- a later call into the SAME layout supersedes its deferred redos frame by frame, any other
     // overlapping writer settles it first (settle_output_conflicts)
-    // path: which layout the run took (bit 0 k_pw_patch, bit 1 self-span prologue, bit 2 k_pw_tile): what hg_sync disables when the run exceeded a limit
+    // kernel / self: what the run's plan carried out (what hg_sync disables when the run exceeded a limit: learn_from_overflows)
     // sampling: the mode the run was queued with (its deferred redos use it, whatever the context's mode is by then)
-    struct Pending { uint8_t *out; int slot; int stage; size_t extent; uint64_t layout; uint8_t path; uint8_t sampling; };
+    struct Pending { uint8_t *out; int slot; int stage; size_t extent; uint64_t layout; PwKernel kernel; bool self; uint8_t sampling; };
     std::vector<Pending> pw_pending_out;
     // Frame sets arrive through a ring of page-locked staging buffers (FrameDesc[F], then the F x n_pts x 2 destination
     // points): hg_piecewise_set_frames copies the caller's arrays there and queues stream-ordered uploads -- it neither waits
@@ -124,20 +156,11 @@ struct hg_ctx {
     // layout of the row counters / status ring as of their last memset (a frame set with the same layout reuses them as they are)
     size_t rows_F = 0; int rows_stride = 0, rows_cap = 0;
     // self-span path (k_tri_setup -> k_pw_rows<SELF>, hg_kernels.h): the row workgroups evaluate their own spans, no row lists
-    int pw_tri_rows_max = 0;                                   // tallest triangle of the uploaded frames, in rows (host estimate)
-    int64_t pw_groups = 0;                                     // 4-row groups of the frame set (layout estimate)
-    bool pw_small_set = false;                                 // fewer 4-row groups than "min_row_groups": one row per workgroup, short-latency prologues
-    bool pw_self = false;                                      // the current step uses the self-span path
-    bool pw_self_disabled = false;                             // a run on it flagged a frame (more candidates / spans than its LDS blocks hold): row lists for this mesh
-    bool pw_self_patch = false;                                // ... through k_pw_patch (dense / sheared meshes, one source per frame)
-    bool pw_tile = false;                                      // ... through k_pw_tile (8-row x <= 2048-column tiles whose gathers follow the source rows)
-    bool pw_tile_disabled = false;                             // a tile exceeded its limits once: k_pw_patch for this mesh
     int pw_last_variant = 0;                                   // variant code of the last piecewise warp kernel launched (launch_pw_rows; hg_last_piecewise_variant)
     int opt_tile = -1;                                         // option "tile": 1 whenever k_pw_patch<SELF> would run, 0 never, -1 by policy
-    bool pw_bands = false;                                     // ... with candidate bands (meshes too large for every workgroup to scan)
-    int4 *d_bands = nullptr; size_t bands_cap = 0;             // F x n_bands x band_cap entries (hg_kernels.h)
-    int band_cap = 0, n_bands = 0;
-    int opt_self = -1;                                         // option "self_spans": 1 whenever eligible, 0 never, -1 by policy (run_setup)
+    int4 *d_bands = nullptr; size_t bands_cap = 0;             // F x n_bands x band_cap entries of the candidate bands (hg_kernels.h)
+    int band_cap = 0;                                          // entries per band; grows (sticky)
+    int opt_self = -1;                                         // option "self_spans": 1 whenever eligible, 0 never, -1 by policy (plan_piecewise)
     int rows_parity = 0;                                       // which of the two counter sets the current step counts into (ping-pong, hg_kernels.h)
     int opt_tri_group = -1;                                    // k_tri_spans_grouped: 16 / 64 triangles per workgroup, 0 never, -1 by mesh size
     int opt_upload_kernel = -1;                                // frame-set blocks up to 1 MB go up by k_upload (default) instead of hipMemcpyAsync (0)
@@ -145,7 +168,6 @@ struct hg_ctx {
     // layout estimates of the last frame set, reused for the next set of the same shape (the kernels check the real counts)
     struct LayoutKey { int n = -1, n_tris = -1, max_w = -1, max_h = -1; uint64_t mesh_gen = 0; bool quick = false; } layout_key;
     uint64_t mesh_gen = 0; int layout_age = 0;
-    double pw_tri_rows = 0.0; int pw_group_tris = 0;
     long pw_layout_walks = 0;                                  // host walks over the triangles (hg_layout_walks(): tests / bench)
 
     // geometric frame sets arrive like the piecewise ones: copied into page-locked staging, uploaded stream-ordered, no GPU wait
@@ -176,8 +198,6 @@ struct hg_ctx {
     int32_t *d_ftile_cnt = nullptr; size_t ftile_cnt_cap = 0;  // F x tiles counters (zero between calls)
     int32_t *d_fwd_status = nullptr; size_t fwd_status_cap = 0, fwd_status_stride = 0;   // kFwdStatusRing sets of `stride` status words of tile-binned forward piecewise batches (zero between calls)
     int32_t *d_ftile_ent = nullptr; size_t ftile_ent_cap = 0;  // F x tiles x fwd_pw_cap entries
-    double pw_spans_per_window = 0.0;                          // longest row's span count per 256-pixel window (layout heuristic)
-    bool pw_quick_layout = false;                              // set around the forward paths' hg_piecewise_set_frames calls
     int fwd_pw_cap = 64;                                       // entries per tile (doubles after an overflow, up to kFwdPwCapMax)
     bool fwd_pw_tiles_disabled = false;                        // overflowed at the largest capacity once: stay with the scatter path for this mesh
     // queued tile-binned forward piecewise batches: status set `slot` of the forward status ring, frame set in staging slot `stage`
@@ -260,6 +280,9 @@ void output_layout(const std::vector<FrameDesc> &frames, size_t *extent, uint64_
 // the new call has the same base and layout (then hg_sync skips the older run's redo frame by frame: `superseded`).  layout = 0:
 // a writer that keeps no pending record (geometric warps, the scatter paths) -- any overlap settles.
 int settle_output_conflicts(hg_ctx *c, const void *out, size_t extent, uint64_t layout);                     // hg_api.hip
+// hg_piecewise_set_frames with quick_layout: no host walk over the triangles for the layout estimate (the forward paths, which only
+// need the per-triangle solves)
+int piecewise_set_frames(hg_ctx *c, const float *dst, const hg_geom *geoms, const size_t *offs, int n, bool quick_layout);   // hg_api_piecewise.hip
 PwMesh mesh_of(const hg_ctx *c);                             // hg_api_piecewise.hip: kernel argument blocks of the current mesh / frame set
 PwFrames frames_of(const hg_ctx *c);
 int redo_forward_frame_staged(hg_ctx *c, int stage, int f, int max_src_x, int max_src_y, uint8_t *d_out);    // hg_api_piecewise.hip, beside its inverse twin

@@ -1695,6 +1695,76 @@ def test_queued_runs_settle_in_call_order():
         c.close()
 
 
+# What the DEFAULT layout policy picks (no option set), one frame set per instantiation the census reaches (tools/census.py --per-set,
+# DESIGN.md §5.2): label -> (hg_last_piecewise_variant, hg_last_piecewise_kernel, hg_last_piecewise_self)
+DEFAULT_POLICY = {
+    "C4 F=1": (104010, 2, 0),
+    "C3 F=1 shared": (302010, 2, 0),
+    "C3 F=8 shared": (104011, 1, 1),
+    "C3 F=8 distinct": (504011, 5, 1),
+    "G24 F=8 shared": (408011, 3, 1),
+    "G24 F=1": (102110, 2, 0),
+    "G40 F=1": (408010, 3, 0),
+    "README 23040 triangles -> 200^2": (111110, 2, 0),
+    "golden quirk_minsrc_neg#0": (101000, 2, 0),
+    "golden quirk_int16_wrap#0": (600000, 4, 0),
+}
+
+
+@pytest.mark.parametrize("label", list(DEFAULT_POLICY))
+def test_default_layout_policy(label):
+    """The kernel, instantiation and span path the policy picks with no option set, as the census's frame sets warp them (one set on a
+    fresh context, then hg_sync), and no frame redone.  Every other kernel test forces its kernel through an option."""
+    c = HG.Context(0)
+    d_src = d_out = None
+    try:
+        if label.startswith("golden"):
+            name, k = label.split()[1].split("#")
+            case = next(cs for cs in GOLD["cases"] if cs["name"] == name)
+            w = case["warps"][int(k)]
+            assert w["path"] == "_inversePiecewiseAffineWarp"
+            c.set_image(G.case_images(case)[G.warp_image_key(case, int(k))])
+            c.piecewise_set_mesh(G.f32_from_bits(w["srcPoints"]), G.warp_triangles(case, w), w["minSrcX"], w["minSrcY"])
+            c.piecewise_prepare(G.f32_from_bits(w["dstPoints"]), (w["xOff"], w["yOff"], w["objW"], w["objH"]))
+            c.warp_inverse_piecewise()
+        elif label.startswith("README"):
+            sp, tris = WL.grid_points(400, 400, 96, 120), WL.grid_triangles(96, 120)
+            dp = (WL.sin_dst(sp, 4.0, 8).reshape(-1, 2) * np.float32(0.5)).astype(np.float32).ravel()
+            c.set_image(WL.lcg_image(400, 400, 1))
+            c.piecewise_set_mesh(sp, tris, *WL.src_min(sp))
+            c.piecewise_prepare(dp, WL.piecewise_geom(dp))
+            c.warp_inverse_piecewise()
+        else:
+            config, nf = label.split()[:2]
+            F = int(nf[2:])
+            cfg = WL.CONFIGS[config]
+            W, H = cfg["W"], cfg["H"]
+            if cfg["kind"] == "face":
+                sp = WL.face_mesh(W, H, cfg["landmarks"]); tris = HG.triangulate(sp); seq = WL.face_frames(sp, W, cfg["total_frames"]); frames = [seq[f] for f in range(F)]
+            else:
+                sp, tris = WL.grid_points(W, H, cfg["nx"], cfg["ny"]), WL.grid_triangles(cfg["nx"], cfg["ny"])
+                frames = [WL.sin_grid_dst(W, H, cfg["nx"], cfg["ny"], cfg["A"], 8 + f % 4) for f in range(F)]
+            geoms = [WL.piecewise_geom(d) for d in frames]
+            offs, total = HG.pack_offsets(geoms)
+            n_img = min(F, 8) if label.endswith("distinct") else 1
+            img, stride = WL.lcg_image(W, H, 1), W * H * 4
+            d_src, d_out = c.alloc(stride * n_img), c.alloc(total)
+            for k in range(n_img):
+                c.to_device(d_src, img, k * stride)
+            if n_img == 1: c.set_image_device(d_src, W, H)
+            else: c.set_images_device(d_src, W, H, n_img, stride)
+            c.piecewise_set_mesh(sp, tris, *WL.src_min(sp))
+            c.piecewise_set_frames(np.concatenate(frames), geoms, offs)
+            c.warp_inverse_piecewise_frames_device(d_out)
+            c.sync()
+        got = (c.last_piecewise_variant(), c.last_piecewise_kernel(), c.last_piecewise_self())
+        assert got == DEFAULT_POLICY[label] and c.redone_frames() == 0, (label, got, c.redone_frames())
+    finally:
+        for d in (d_src, d_out):
+            if d is not None: c.free(d)
+        c.close()
+
+
 def test_dense_sheared_mesh_takes_the_patch_kernel():
     """A mesh with ~150 spans per row and shear ~1 (C5's regime at a size the oracle does in a blink): the host picks the 2-D gather
     kernels -- since round 6 k_pw_tile (8-row tiles, source-row-following runs) where the mesh is steeply sheared or packs more than two

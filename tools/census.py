@@ -5,7 +5,8 @@
   * every inverse piecewise warp of the 144 golden cases,
 the variant code of the kernel instantiation that ran (hg_last_piecewise_variant) and whether a frame was redone.  Prints one line per
 (variant, count, examples); instantiations and option keys that never show up here and lost wherever they were tried are what gets deleted.
-    python tools/census.py [--quick]        (GPU box; through gpurun)"""
+--per-set also prints one JSON line per frame set (label, variant, kernel, self, redone): two builds of the policy compare line by line.
+    python tools/census.py [--quick] [--per-set]        (GPU box)"""
 import collections, importlib.util, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -34,11 +35,14 @@ def describe(code):
 def main():
     import numpy as np, torch
     hg, wl = load("hgwarp", "hgwarp.py"), load("hg_workloads", "workloads.py")
-    quick = "--quick" in sys.argv
+    quick, per_set = "--quick" in sys.argv, "--per-set" in sys.argv
     dev = torch.device("cuda", 0)
     seen = collections.OrderedDict()
 
-    def note(code, what, redone):
+    def note(ctx, what):
+        code, redone = ctx.last_piecewise_variant(), ctx.redone_frames()
+        if per_set:
+            print(json.dumps({"set": what, "variant": code, "kernel": ctx.last_piecewise_kernel(), "self": ctx.last_piecewise_self(), "redone": redone}), flush=True)
         e = seen.setdefault(code, {"n": 0, "ex": [], "redone": 0})
         e["n"] += 1; e["redone"] += redone
         if len(e["ex"]) < 6: e["ex"].append(what)
@@ -69,7 +73,7 @@ def main():
                     ctx.piecewise_set_frames(np.concatenate(frames), geoms, offs)
                     ctx.warp_inverse_piecewise_frames_device(out.data_ptr())
                     ctx.sync()
-                    note(ctx.last_piecewise_variant(), f"{config} F={F} {sources}", ctx.redone_frames())
+                    note(ctx, f"{config} F={F} {sources}")
             del out
     # ---- the reference README's grid (test/benchmark.js:50-190): 400 x 400 source, 1 x 1 / 10 x 20 / 96 x 120 cells, outputs 200^2 / 400^2 / 800^2
     W = H = 400
@@ -85,7 +89,7 @@ def main():
                 ctx.piecewise_set_mesh(sp, tris, msx, msy)
                 ctx.piecewise_prepare(dp, geom)
                 ctx.warp_inverse_piecewise()
-                note(ctx.last_piecewise_variant(), f"README {tris.size // 3} triangles -> {size}^2", ctx.redone_frames())
+                note(ctx, f"README {tris.size // 3} triangles -> {size}^2")
     # ---- golden cases (single frames through hg_piecewise_prepare, as the class's warp() issues them)
     from hgtest import golden as G
     gold = G.load()
@@ -100,7 +104,7 @@ def main():
                 ctx.piecewise_set_mesh(sp, G.warp_triangles(case, w), w["minSrcX"], w["minSrcY"])
                 ctx.piecewise_prepare(dp, (w["xOff"], w["yOff"], w["objW"], w["objH"]))
                 ctx.warp_inverse_piecewise()
-                note(ctx.last_piecewise_variant(), f"golden {case['name']}#{k}", ctx.redone_frames())
+                note(ctx, f"golden {case['name']}#{k}")
     print(f"{'variant':>8}  {'sets':>5} {'redone':>6}  what / examples")
     for code, e in sorted(seen.items(), key=lambda kv: -kv[1]["n"]):
         print(f"{code:>8}  {e['n']:>5} {e['redone']:>6}  {describe(code)}   e.g. {'; '.join(e['ex'])}")
