@@ -37,14 +37,15 @@ extern "C" int hg_piecewise_set_mesh(hg_ctx *c, const float *src, int n_pts, con
     c->mesh_gen++;
     c->fwd_pw_tiles_disabled = false; c->fwd_pw_cap = 64;     // (learned on the previous mesh)
     c->pw_learned = PwLearned{};
-    c->pw_frames.clear(); c->pw_setup_done = false;
+    c->pw_frames.clear(); c->pw_setup_done = false; c->pw_moving = false;
     return HG_OK;
 }
 
 // Largest number of triangles whose fillTriangle row range (:1113-1120) covers one output row, over the uploaded frames:
 // an estimate of the longest per-row span list, used ONLY to pick k_pw_rows' layout (4 rows per workgroup with 64 LDS
 // slots each, or 1 row with all 256); the kernel checks the real counts and is exact either way.
-static int max_row_cover(const hg_ctx *c, const float *dst, double *mean_tri_rows, int *max_group_tris, double *mean_shear, int *max_tri_rows, double *fill)
+// src: the frames' own source points (F x n_pts x 2; the shear estimate reads frame f's), nullptr: the mesh's for every frame.
+static int max_row_cover(const hg_ctx *c, const float *dst, const float *src, double *mean_tri_rows, int *max_group_tris, double *mean_shear, int *max_tri_rows, double *fill)
 {
     double tallest = 0.0, band_worst = 1.0;
     const int nb = 1 << c->xcc_log2;
@@ -56,7 +57,7 @@ static int max_row_cover(const hg_ctx *c, const float *dst, double *mean_tri_row
     for (size_t f = 0; f < c->pw_frames.size(); f++) {
         const FrameDesc &fd = c->pw_frames[f];
         if (fd.obj_w <= 0 || fd.obj_h <= 0) continue;
-        const float *dp = dst + f * (size_t)c->n_pts * 2;
+        const float *dp = dst + f * (size_t)c->n_pts * 2, *sp = src ? src + f * (size_t)c->n_pts * 2 : c->h_src.data();
         diff.assign((size_t)fd.obj_h + 2, 0);
         starts.assign((size_t)fd.obj_h + 2, 0);
         tdiff.assign((size_t)fd.obj_h + 2, 0);
@@ -70,7 +71,7 @@ static int max_row_cover(const hg_ctx *c, const float *dst, double *mean_tri_row
                 const double y = dp[2 * (size_t)v + 1];
                 if (!(y == y)) { ok = false; break; }
                 lo = std::min(lo, y); hi = std::max(hi, y);
-                sx[k] = c->h_src[2 * (size_t)v]; sy[k] = c->h_src[2 * (size_t)v + 1]; dx[k] = dp[2 * (size_t)v]; dy[k] = y;
+                sx[k] = sp[2 * (size_t)v]; sy[k] = sp[2 * (size_t)v + 1]; dx[k] = dp[2 * (size_t)v]; dy[k] = y;
             }
             if (!ok) continue;
             if (t % shear_stride == 0) {   // |d(source row) / d(output x)| of the triangle's inverse map (a sample is enough): how many source lines 64 consecutive output
@@ -119,20 +120,42 @@ static int max_row_cover(const hg_ctx *c, const float *dst, double *mean_tri_row
     return worst;
 }
 
-static int pw_set_frames_impl(hg_ctx *c, const float *dst, const hg_geom *geoms, const size_t *offs, int n, bool quick_layout);
+// own_src: the frames bring their own source side src / min_src (hg_piecewise_set_frames_src); otherwise the mesh's
+static int pw_set_frames_impl(hg_ctx *c, bool own_src, const float *src, const int32_t *min_src, const float *dst, const hg_geom *geoms, const size_t *offs, int n, bool quick_layout);
 
 // Transactional wrapper: if validation, an allocation or an upload fails part-way, the context is left WITHOUT a frame set
 // (the next warp returns HG_ERR_STATE) rather than with n new host-side frames over device buffers sized for the old set.
-int piecewise_set_frames(hg_ctx *c, const float *dst, const hg_geom *geoms, const size_t *offs, int n, bool quick_layout)
+static int set_frames_transaction(hg_ctx *c, bool own_src, const float *src, const int32_t *min_src, const float *dst, const hg_geom *geoms, const size_t *offs, int n, bool quick_layout)
 {
-    const int rc = pw_set_frames_impl(c, dst, geoms, offs, n, quick_layout);
+    const int rc = pw_set_frames_impl(c, own_src, src, min_src, dst, geoms, offs, n, quick_layout);
     if (rc != HG_OK && c) {
         const std::string why = c->err;
         (void)hg_sync(c);                                   // queued runs of the old set are settled against the old set
-        c->pw_frames.clear(); c->pw_setup_done = false; c->rows_clean = false;
+        c->pw_frames.clear(); c->pw_setup_done = false; c->rows_clean = false; c->pw_moving = false;
         c->err = why; g_err = why;
     }
     return rc;
+}
+
+int piecewise_set_frames(hg_ctx *c, const float *dst, const hg_geom *geoms, const size_t *offs, int n, bool quick_layout)
+{
+    return set_frames_transaction(c, false, nullptr, nullptr, dst, geoms, offs, n, quick_layout);
+}
+
+// "as a fresh instance would" (:758): the rounded bounding-box minimum of one frame's source points, by the rule of hg_minmax_xy.  A minimum
+// that is no int32 (no finite point at all: +Infinity) is held at the int32 limit -- no coordinate passes :1047 against either.
+extern "C" int hg_piecewise_frame_min_src(const float *src, int n_pts, int32_t out[2])
+{
+    if (!src || n_pts <= 0 || !out) return fail(nullptr, HG_ERR_INVALID, "hg_piecewise_frame_min_src: bad arguments");
+    double mm[4];
+    HG_TRY(hg_minmax_xy(src, 2 * n_pts, mm));
+    for (int k = 0; k < 2; k++) out[k] = mm[k] >= 2147483647.0 ? INT32_MAX : (mm[k] <= -2147483647.0 ? -INT32_MAX : (int32_t)mm[k]);
+    return HG_OK;
+}
+
+extern "C" int hg_piecewise_set_frames_src(hg_ctx *c, const float *src, const int32_t *min_src, const float *dst, const hg_geom *geoms, const size_t *offs, int n)
+{
+    return set_frames_transaction(c, true, src, min_src, dst, geoms, offs, n, false);
 }
 
 extern "C" int hg_piecewise_set_frames(hg_ctx *c, const float *dst, const hg_geom *geoms, const size_t *offs, int n)
@@ -140,11 +163,13 @@ extern "C" int hg_piecewise_set_frames(hg_ctx *c, const float *dst, const hg_geo
     return piecewise_set_frames(c, dst, geoms, offs, n, false);
 }
 
-static int pw_set_frames_impl(hg_ctx *c, const float *dst, const hg_geom *geoms, const size_t *offs, int n, bool quick_layout)
+static int pw_set_frames_impl(hg_ctx *c, bool own_src, const float *src, const int32_t *min_src, const float *dst, const hg_geom *geoms, const size_t *offs, int n, bool quick_layout)
 {
     HG_TRY(bind(c));
     if (!c->have_mesh) return fail(c, HG_ERR_STATE, "no mesh: call hg_piecewise_set_mesh first");
-    if (!dst || !geoms || n <= 0) return fail(c, HG_ERR_INVALID, "hg_piecewise_set_frames: bad arguments");
+    if (!dst || !geoms || n <= 0 || (own_src && !src)) return fail(c, HG_ERR_INVALID, own_src ? "hg_piecewise_set_frames_src: bad arguments" : "hg_piecewise_set_frames: bad arguments");
+    if (src && !coords_ok(src, (size_t)n * c->n_pts * 2))
+        return fail(c, HG_ERR_INVALID, "hg_piecewise_set_frames_src: a source coordinate is infinite or beyond 2^24 in magnitude");
     if (!coords_ok(dst, (size_t)n * c->n_pts * 2))
         return fail(c, HG_ERR_INVALID, "hg_piecewise_set_frames: a destiny coordinate is infinite or beyond 2^24 in magnitude "
                                        "(the reference's fillTriangle row loop would run for that many rows, forever for Infinity)");
@@ -157,7 +182,10 @@ static int pw_set_frames_impl(hg_ctx *c, const float *dst, const hg_geom *geoms,
     for (const hg_ctx::FwdPending &pd : c->fwd_pending) if (pd.stage == slot) { HG_TRY(hg_sync(c)); break; }   // (their redo reads the staged set too)
     std::vector<FrameDesc> fresh;
     HG_TRY(fill_frames(c, fresh, geoms, offs, n));
-    HG_TRY(ensure(c, c->d_set, c->set_cap, sizeof(FrameDesc) * F + sizeof(float) * 2 * c->n_pts * F));
+    // the set's block: frame records, destiny points and -- a set with its own source side -- source points and source minima
+    const size_t fd_bytes = sizeof(FrameDesc) * F, pt_bytes = sizeof(float) * 2 * c->n_pts * F, ms_bytes = src ? sizeof(int2) * F : 0;
+    const size_t set_bytes = fd_bytes + pt_bytes + (src ? pt_bytes + ms_bytes : 0);
+    HG_TRY(ensure(c, c->d_set, c->set_cap, set_bytes));
     HG_TRY(ensure(c, c->d_trir, c->trir_cap, F * T));
     HG_TRY(ensure(c, c->d_trix, c->trix_cap, F * T));
     HG_TRY(ensure(c, c->d_segs, c->segs_cap, F * T * 3));
@@ -180,25 +208,42 @@ static int pw_set_frames_impl(hg_ctx *c, const float *dst, const hg_geom *geoms,
         c->h_status = static_cast<int32_t *>(q); c->h_status_cap = F * kStatusRing;
     }
     hg_ctx::Stage &st = c->stage[slot];
-    const size_t fd_bytes = sizeof(FrameDesc) * F, pt_bytes = sizeof(float) * 2 * c->n_pts * F;
     // An older upload out of this slot may still be queued (no queued run refers to the slot -- checked above -- but its DMA reads
     // it): wait for THAT copy, not for the stream.  64 sets back it has long run in any loop that also launches kernels.
     if (!st.done) HIP_TRY(c, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
     if (st.used) HIP_TRY(c, hipEventSynchronize(st.done));
-    if (fd_bytes + pt_bytes > st.cap) {
+    if (set_bytes > st.cap) {
         if (st.h) { HIP_TRY(c, hipHostFree(st.h)); st.h = nullptr; st.cap = 0; }
         void *q = nullptr;
-        const size_t want = fd_bytes + pt_bytes + (fd_bytes + pt_bytes) / 4;
+        const size_t want = set_bytes + set_bytes / 4;
         hipError_t e = hipHostMalloc(&q, want, hipHostMallocDefault);
         if (e != hipSuccess) return fail(c, HG_ERR_NOMEM, std::string("hipHostMalloc (frame-set staging): ") + hipGetErrorString(e));
         st.h = static_cast<uint8_t *>(q); st.cap = want;
     }
     std::memcpy(st.h, fresh.data(), fd_bytes);
     std::memcpy(st.h + fd_bytes, dst, pt_bytes);
-    st.n = n; st.n_pts = c->n_pts;
-    static_assert(sizeof(FrameDesc) % 8 == 0, "the destiny points follow the frame records in the same block");
+    // Device layout of the staged block: FrameDesc[F] | destiny points F x n_pts x 2 f32 | (own source side only:) source points F x n_pts x 2 f32 |
+    // source minima F x {minSrcX, minSrcY} int32.  Every part is a multiple of 8 bytes.
+    int ms_lo_x = 0, ms_hi_x = 0, ms_lo_y = 0, ms_hi_y = 0;
+    if (src) {
+        std::memcpy(st.h + fd_bytes + pt_bytes, src, pt_bytes);
+        int32_t *ms = reinterpret_cast<int32_t *>(st.h + fd_bytes + 2 * pt_bytes);
+        for (size_t f = 0; f < F; f++) {
+            if (min_src) { ms[2 * f] = min_src[2 * f]; ms[2 * f + 1] = min_src[2 * f + 1]; }
+            else HG_TRY(hg_piecewise_frame_min_src(src + f * (size_t)c->n_pts * 2, c->n_pts, ms + 2 * f));
+            if (f == 0) { ms_lo_x = ms_hi_x = ms[0]; ms_lo_y = ms_hi_y = ms[1]; }
+            ms_lo_x = std::min(ms_lo_x, ms[2 * f]); ms_hi_x = std::max(ms_hi_x, ms[2 * f]);
+            ms_lo_y = std::min(ms_lo_y, ms[2 * f + 1]); ms_hi_y = std::max(ms_hi_y, ms[2 * f + 1]);
+        }
+    }
+    st.n = n; st.n_pts = c->n_pts; st.moving = src != nullptr;
+    static_assert(sizeof(FrameDesc) % 8 == 0 && sizeof(int2) == 8, "the parts of the block keep 8-byte alignment");
     c->d_pw_frames = reinterpret_cast<FrameDesc *>(c->d_set); c->d_dst = reinterpret_cast<float *>(c->d_set + fd_bytes);
-    HG_TRY(upload_staged(c, c->d_set, st.h, fd_bytes + pt_bytes));      // (one copy: the staged block has the device layout)
+    c->pw_moving = src != nullptr;
+    c->d_srcf = src ? reinterpret_cast<float *>(c->d_set + fd_bytes + pt_bytes) : nullptr;
+    c->d_min_src = src ? reinterpret_cast<int2 *>(c->d_set + fd_bytes + 2 * pt_bytes) : nullptr;
+    c->ms_lo_x = ms_lo_x; c->ms_hi_x = ms_hi_x; c->ms_lo_y = ms_lo_y; c->ms_hi_y = ms_hi_y;
+    HG_TRY(upload_staged(c, c->d_set, st.h, set_bytes));     // (one copy: the staged block has the device layout)
     HIP_TRY(c, hipEventRecord(st.done, c->stream));
     st.used = true;
     c->pw_frames.swap(fresh);
@@ -238,7 +283,7 @@ static int pw_set_frames_impl(hg_ctx *c, const float *dst, const hg_geom *geoms,
         s.tri_rows = 64.0;
         s.tri_rows_max = 0;                                 // (unknown: no table path without the walk)
     } else {
-        s.cover = max_row_cover(c, dst, &s.tri_rows, &s.group_tris, &s.shear, &s.tri_rows_max, &s.fill);
+        s.cover = max_row_cover(c, dst, src, &s.tri_rows, &s.group_tris, &s.shear, &s.tri_rows_max, &s.fill);
         c->pw_layout_walks++;
     }
     if (!same_shape) { c->layout_key = key; c->layout_age = 0; }
@@ -275,6 +320,8 @@ PwFrames frames_of(const hg_ctx *c)
     const PwPlan &p = c->pw_plan;
     PwFrames f;
     f.host_flag = c->h_flag;                                 // (always armed: whether hg_sync may skip the status ring must not depend on an option that can change while runs are queued)
+    f.src_pts = c->pw_moving ? c->d_srcf : nullptr; f.min_src = c->pw_moving ? c->d_min_src : nullptr;
+    f.min_src_lo_x = c->ms_lo_x; f.min_src_hi_x = c->ms_hi_x; f.min_src_lo_y = c->ms_lo_y; f.min_src_hi_y = c->ms_hi_y;
     f.frames = c->d_pw_frames; f.dst_pts = c->d_dst; f.trir = c->d_trir; f.trix = c->d_trix; f.segs = c->d_segs; f.fwd = c->d_fwd; f.inv = c->d_inv;
     f.status = c->status_ptr ? c->status_ptr : c->d_status; f.n_frames = (int)c->pw_frames.size();
     f.two_round = c->d_two_round; f.gen = c->pw_gen;
@@ -324,7 +371,8 @@ static PwPlan plan_piecewise(const hg_ctx &c, bool for_tap)
 
     // bilinear sampling has no row / patch / tile kernels: the general path (k_tri_setup + k_pw_fused<bilinear>) -- not for the parity tap,
     // whose map and matrices do not depend on the mode.  So do meshes and sources beyond the fast kernels' ranges (pw_fast_ok).
-    const bool fast = pw_fast_ok(mesh_of(&c), s.max_w) && (for_tap || c.sampling != HG_SAMPLE_BILINEAR);
+    // (a set with per-frame source minima: every frame must be inside those ranges -- tested at the extremes of the set)
+    const bool fast = pw_fast_ok(mesh_of(&c), frames_of(&c), s.max_w) && (for_tap || c.sampling != HG_SAMPLE_BILINEAR);
     if (fast) {
         const int cover = s.cover, max_w = s.max_w;
         // Row lists through k_pw_patch: dense rows that still fit the patch kernel's LDS budget, sheared enough for 2-D gather patches to
@@ -607,6 +655,16 @@ static int load_redo_frame(hg_ctx *c, int stage, int f, const char *what, FrameD
     HIP_TRY(c, hipMemcpyAsync(c->d_redo_frame, st.h + sizeof(FrameDesc) * (size_t)f, sizeof(FrameDesc), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_redo_dst, pts, sizeof(float) * 2 * c->n_pts, hipMemcpyHostToDevice, c->stream));
     *fr = frames_of(c);
+    fr->src_pts = nullptr; fr->min_src = nullptr;            // the source side of the STAGED set (the context's current set may be another kind)
+    if (st.moving) {
+        const size_t pt_all = sizeof(float) * 2 * (size_t)c->n_pts * (size_t)st.n;
+        const uint8_t *src0 = st.h + sizeof(FrameDesc) * (size_t)st.n + pt_all;
+        HG_TRY(ensure(c, c->d_redo_src, c->redo_src_cap, (size_t)c->n_pts * 2));
+        HG_TRY(ensure(c, c->d_redo_min, c->redo_min_cap, (size_t)1));
+        HIP_TRY(c, hipMemcpyAsync(c->d_redo_src, src0 + sizeof(float) * 2 * (size_t)c->n_pts * (size_t)f, sizeof(float) * 2 * c->n_pts, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_redo_min, src0 + pt_all + sizeof(int2) * (size_t)f, sizeof(int2), hipMemcpyHostToDevice, c->stream));
+        fr->src_pts = c->d_redo_src; fr->min_src = c->d_redo_min;
+    }
     fr->two_round = nullptr;                                 // (a set-up of its own, outside the frame set's step numbering)
     fr->frames = c->d_redo_frame; fr->dst_pts = c->d_redo_dst; fr->trir = c->d_redo_trir; fr->trix = c->d_redo_trix; fr->band_ent = nullptr; fr->host_flag = nullptr; fr->segs = c->d_redo_segs; fr->fwd = c->d_redo_fwd;
     fr->inv = c->d_redo_inv; fr->status = c->d_redo_status; fr->n_frames = 1; fr->max_obj_h = fd->obj_h;
@@ -809,6 +867,13 @@ extern "C" int hg_sync(hg_ctx *c)
 extern "C" int hg_warp_inverse_piecewise_batch_device(hg_ctx *c, const float *dst, const hg_geom *geoms, const size_t *offs, int n, void *d_out)
 {
     HG_TRY(hg_piecewise_set_frames(c, dst, geoms, offs, n));
+    return hg_warp_inverse_piecewise_frames_device(c, d_out);
+}
+
+extern "C" int hg_warp_inverse_piecewise_src_batch_device(hg_ctx *c, const float *src, const int32_t *min_src, const float *dst, const hg_geom *geoms,
+                                                          const size_t *offs, int n, void *d_out)
+{
+    HG_TRY(hg_piecewise_set_frames_src(c, src, min_src, dst, geoms, offs, n));
     return hg_warp_inverse_piecewise_frames_device(c, d_out);
 }
 

@@ -90,6 +90,11 @@ struct hg_ctx {
     uint8_t *d_set = nullptr; size_t set_cap = 0;             // the frame set in ONE block: F frame records, then F x n_pts x 2 destiny floats (one upload)
     FrameDesc *d_pw_frames = nullptr;                         // = d_set
     float *d_dst = nullptr;                                   // = d_set + F * sizeof(FrameDesc)
+    // a frame set with a source side of its own (hg_piecewise_set_frames_src): F x n_pts x 2 source floats and F {minSrcX, minSrcY} pairs behind the
+    // destiny points, in the same block; the extremes of the minima over the set (what "fast path" and the bounds form are decided by)
+    bool pw_moving = false;
+    float *d_srcf = nullptr; int2 *d_min_src = nullptr;
+    int ms_lo_x = 0, ms_hi_x = 0, ms_lo_y = 0, ms_hi_y = 0;
     TriRange *d_trir = nullptr; size_t trir_cap = 0;
     int2 *d_trix = nullptr; size_t trix_cap = 0;
     Seg *d_segs = nullptr; size_t segs_cap = 0;
@@ -132,17 +137,19 @@ struct hg_ctx {
     struct Pending { uint8_t *out; int slot; int stage; size_t extent; uint64_t layout; PwKernel kernel; bool self; uint8_t sampling; };
     std::vector<Pending> pw_pending_out;
     // Frame sets arrive through a ring of page-locked staging buffers (FrameDesc[F], then the F x n_pts x 2 destination
-    // points): hg_piecewise_set_frames copies the caller's arrays there and queues stream-ordered uploads -- it neither waits
+    // points; `moving` sets: then the F x n_pts x 2 source points and the F source minima): hg_piecewise_set_frames copies the caller's arrays there and queues stream-ordered uploads -- it neither waits
     // for the GPU nor keeps caller memory.  A staged set stays intact until every run that used it has been settled, so frames a
     // fused run flagged can still be redone (through the materialised map) after newer sets were uploaded.
     // `done` is recorded behind the slot's upload: the slot's bytes are not rewritten before the DMA that reads them has run
     // (paths that keep no pending record -- the forward scatter path -- could otherwise lap the ring with uploads still queued)
-    struct Stage { uint8_t *h = nullptr; size_t cap = 0; int n = 0, n_pts = 0; hipEvent_t done = nullptr; bool used = false; };
+    struct Stage { uint8_t *h = nullptr; size_t cap = 0; int n = 0, n_pts = 0; hipEvent_t done = nullptr; bool used = false; bool moving = false; };
     Stage stage[kStatusRing];
     int stage_cur = -1;
     // scratch of the deferred redo (one frame): its FrameDesc, points, solves
     FrameDesc *d_redo_frame = nullptr; size_t redo_frame_cap = 0;
     float *d_redo_dst = nullptr; size_t redo_dst_cap = 0;
+    float *d_redo_src = nullptr; size_t redo_src_cap = 0;      // (frames of a set with its own source side)
+    int2 *d_redo_min = nullptr; size_t redo_min_cap = 0;
     TriRange *d_redo_trir = nullptr; size_t redo_trir_cap = 0;
     int2 *d_redo_trix = nullptr; size_t redo_trix_cap = 0;
     Seg *d_redo_segs = nullptr; size_t redo_segs_cap = 0;

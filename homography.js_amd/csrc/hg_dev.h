@@ -56,6 +56,12 @@ __host__ __device__ __forceinline__ bool hi_bounds_ok(int64_t ax, int64_t bx, in
 {
     return ax >= 0 && ay >= 0 && bx < (1 << 20) && by < (1 << 20) && ax <= bx && ay <= by;
 }
+// the launchers' choice of the bounds form for a frame set: the high-dword form only where EVERY frame's source window allows it
+inline bool set_hi_bounds_ok(const PwMesh &mesh, const PwFrames &fr)
+{
+    if (!fr.min_src) return hi_bounds_ok(mesh.min_src_x, (int64_t)mesh.W + mesh.min_src_x, mesh.min_src_y, (int64_t)mesh.H + mesh.min_src_y);
+    return hi_bounds_ok(fr.min_src_lo_x, (int64_t)mesh.W + fr.min_src_hi_x, fr.min_src_lo_y, (int64_t)mesh.H + fr.min_src_hi_y);
+}
 __device__ __forceinline__ HiBounds make_hi_bounds(double lox, double hix, double loy, double hiy)       // wave-uniform: kept in SGPRs
 {
     HiBounds b;

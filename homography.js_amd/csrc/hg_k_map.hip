@@ -53,7 +53,7 @@ __global__ void k_map_max_i16(const int32_t *__restrict__ m32, size_t n, int32_t
 
 // Pixel loop :1042-1056 reading the materialised map.  Block = 64 x 4 threads = 4 rows x 256 pixels.  S: sampling mode (pw_pixel_mode).
 template <int S>
-__global__ __launch_bounds__(256) void k_pw_from_map(PwMesh mesh, const float *__restrict__ invm, FrameDesc fd,
+__global__ __launch_bounds__(256) void k_pw_from_map(PwMesh mesh, const float *__restrict__ invm, const int2 *__restrict__ min_src, FrameDesc fd,
                                                      const int32_t *__restrict__ map32, uint8_t *__restrict__ out)
 {
     const int r = blockIdx.y * 4 + threadIdx.y;
@@ -66,8 +66,10 @@ __global__ __launch_bounds__(256) void k_pw_from_map(PwMesh mesh, const float *_
     uint32_t *__restrict__ orow = reinterpret_cast<uint32_t *>(out + fd.out_off) + row0;
     const bool vec_ok = ((W & 3) == 0) && ((fd.out_off & 15) == 0);
     const double y = (double)(r + fd.y_off);
-    const double bx0 = (double)mesh.min_src_x, bx1 = (double)mesh.W + (double)mesh.min_src_x;
-    const double by0 = (double)mesh.min_src_y, by1 = (double)mesh.H + (double)mesh.min_src_y;
+    // min_src: the frame's own source minima (a frame set with a source side of its own), nullptr: the mesh's; one scalar fetch
+    const int2 ms = min_src ? make_int2(__builtin_amdgcn_readfirstlane(min_src->x), __builtin_amdgcn_readfirstlane(min_src->y)) : make_int2(mesh.min_src_x, mesh.min_src_y);
+    const double bx0 = (double)ms.x, bx1 = (double)mesh.W + (double)ms.x;
+    const double by0 = (double)ms.y, by1 = (double)mesh.H + (double)ms.y;
     uint32_t px[4];
     MatCache mc; mc.id = -1;
 #pragma unroll
@@ -100,8 +102,9 @@ void launch_pw_from_map(const PwMesh &mesh, const PwFrames &fr, int f, const Fra
     if (fd.obj_w <= 0 || fd.obj_h <= 0) return;
     dim3 grid((fd.obj_w + 255) / 256, (fd.obj_h + 3) / 4);
     const float *invm = fr.inv + (size_t)f * mesh.n_tris * kInvStride;
-    if (sampling == 1) hipLaunchKernelGGL(k_pw_from_map<1>, grid, dim3(64, 4), 0, stream, mesh, invm, fd, map32, out);
-    else               hipLaunchKernelGGL(k_pw_from_map<0>, grid, dim3(64, 4), 0, stream, mesh, invm, fd, map32, out);
+    const int2 *ms = fr.min_src ? fr.min_src + f : nullptr;
+    if (sampling == 1) hipLaunchKernelGGL(k_pw_from_map<1>, grid, dim3(64, 4), 0, stream, mesh, invm, ms, fd, map32, out);
+    else               hipLaunchKernelGGL(k_pw_from_map<0>, grid, dim3(64, 4), 0, stream, mesh, invm, ms, fd, map32, out);
 }
 
 void launch_map_max_i16(const int32_t *map32, size_t n, int32_t *out, hipStream_t stream)

@@ -46,6 +46,7 @@ __global__ __launch_bounds__(256) void k_pw_patch(PwMesh mesh, PwFrames fr, RowL
     if (!frame_group(fr, xcd, bi, groups_per_xcd, f, gi)) return;           // (bands, rotating bands or dealt sub-bands: hg_dev.h)
     const int r0 = gi * kPatchRows;
     const FrameDesc fd = fr.frames[f];
+    const int2 ms = frame_min_src(mesh, fr, f);              // the source minima of :1047: the mesh's, or this frame's own (scalars, by the decoded frame index)
     if (bid == 0 && status_next) for (int i = threadIdx.x; i < fr.n_frames; i += 256) status_next[i] = 0;   // (see k_pw_rows)
     // the OTHER counter set, every row of the frame's block: clean for the next step's k_tri_spans (ping-pong, see k_pw_rows)
     if ((int)threadIdx.x < kPatchRows && r0 + (int)threadIdx.x < rl.row_stride) rl.cnt_clear[(size_t)f * rl.row_stride + r0 + threadIdx.x] = 0;
@@ -65,8 +66,8 @@ __global__ __launch_bounds__(256) void k_pw_patch(PwMesh mesh, PwFrames fr, RowL
     const int nbins = (W + 63) >> 6;
     const int nrows = min(kPatchRows, fd.obj_h - r0);
     // (the source window, also for the prologue's span flags)
-    const double bx_lo0 = (double)mesh.min_src_x + 0.5, bx_hi0 = (double)mesh.W + (double)mesh.min_src_x + 0.5;
-    const double by_lo0 = (double)mesh.min_src_y + 0.5, by_hi0 = (double)mesh.H + (double)mesh.min_src_y + 0.5;
+    const double bx_lo0 = (double)ms.x + 0.5, bx_hi0 = (double)mesh.W + (double)ms.x + 0.5;
+    const double by_lo0 = (double)ms.y + 0.5, by_hi0 = (double)mesh.H + (double)ms.y + 0.5;
     const HiBounds hb0 = make_hi_bounds(bx_lo0, bx_hi0, by_lo0, by_hi0);
     const bool flag_spans = SELF && fr.safe_spans_patch != 0;       // (uniform; host option)
     const float *__restrict__ ginv0 = fr.inv + (size_t)f * mesh.n_tris * kInvStride;     // this frame's inverse matrices (tap array)
@@ -287,8 +288,8 @@ __global__ __launch_bounds__(256) void k_pw_patch(PwMesh mesh, PwFrames fr, RowL
     // output: the group's rows as one raw buffer; lanes of rows past the frame end and pixels past the row end get an
     // offset the hardware range check drops
     const __amdgpu_buffer_rsrc_t dst = __builtin_amdgcn_make_buffer_rsrc(out + fd.out_off + (int64_t)r0 * W * 4, 0, nrows * W * 4, 0x00020000);
-    const double bx_lo = (double)mesh.min_src_x + 0.5, bx_hi = (double)mesh.W + (double)mesh.min_src_x + 0.5;
-    const double by_lo = (double)mesh.min_src_y + 0.5, by_hi = (double)mesh.H + (double)mesh.min_src_y + 0.5;
+    const double bx_lo = (double)ms.x + 0.5, bx_hi = (double)mesh.W + (double)ms.x + 0.5;
+    const double by_lo = (double)ms.y + 0.5, by_hi = (double)mesh.H + (double)ms.y + 0.5;
     const HiBounds hb = make_hi_bounds(bx_lo, bx_hi, by_lo, by_hi);      // HIB: :1047 on the high dwords of h (hg_dev.h)
     const int nan_key = GLOBALREC ? -1 : ((int)0x80000000u | (RECS * 48) | 1);      // ("no triangle" is unsafe: its pixels must come out as offset 0xffffffff)
     const int row_base = rr * CAPR;
@@ -406,7 +407,7 @@ int launch_pw_patch(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl, 
     PwFrames frs = fr;
     frs.sub_groups = sub_groups_of(fr, gpx);
     const dim3 grid((unsigned)padded_groups(gpx, frs.sub_groups) * (unsigned)nx * (unsigned)fr.n_frames);
-    const bool hib = !fr.no_hi_bounds && hi_bounds_ok(mesh.min_src_x, (int64_t)mesh.W + mesh.min_src_x, mesh.min_src_y, (int64_t)mesh.H + mesh.min_src_y);
+    const bool hib = !fr.no_hi_bounds && set_hi_bounds_ok(mesh, fr);
 #define HG_PATCH(G, HB, PBV, SF) do { code = ((G) ? 800000 : 400000) + (PBV) * 1000 + ((HB) ? 10 : 0) + ((SF) ? 1 : 0); \
         hipLaunchKernelGGL((k_pw_patch<G, HB, PBV, SF>), grid, dim3(256), 0, stream, mesh, frs, rl, out, gpx, status_next); } while (0)
     // ONE depth: 8 column blocks per gather / store phase (the census of round 6 found the 1- / 2- / 4-block instantiations never picked

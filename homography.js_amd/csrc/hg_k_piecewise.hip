@@ -15,13 +15,13 @@ constexpr int kBandMax = 2048;                 // candidate bands per frame the 
 // One triangle of one frame: solves, edge equations, row range, column reach; returns false when the triangle has no rows or is irregular.
 __device__ __forceinline__ bool tri_setup_one(const PwMesh &mesh, const PwFrames &fr, int f, int t, const FrameDesc &fd, TriRange &tr)
 {
-    const float *dp = fr.dst_pts + (size_t)f * mesh.n_pts * 2;
+    const float *dp = fr.dst_pts + (size_t)f * mesh.n_pts * 2, *sp = frame_src(mesh, fr, f);
     float s[6], d[6];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         const uint32_t v = mesh.tris[3 * (size_t)t + k];
         if (v < (uint32_t)mesh.n_pts) {
-            s[2 * k] = mesh.src_pts[2 * (size_t)v]; s[2 * k + 1] = mesh.src_pts[2 * (size_t)v + 1];
+            s[2 * k] = sp[2 * (size_t)v]; s[2 * k + 1] = sp[2 * (size_t)v + 1];
             d[2 * k] = dp[2 * (size_t)v];           d[2 * k + 1] = dp[2 * (size_t)v + 1];
         } else {                                   // typed-array read past the end: undefined -> NaN in the Float32Array(6)
             s[2 * k] = s[2 * k + 1] = d[2 * k] = d[2 * k + 1] = NAN;
@@ -223,8 +223,9 @@ __global__ __launch_bounds__(256) void k_pw_fused(PwMesh mesh, PwFrames fr, uint
     uint32_t *__restrict__ orow = reinterpret_cast<uint32_t *>(out + fd.out_off) + row0;
     const bool vec_ok = ((W & 3) == 0) && ((fd.out_off & 15) == 0);
     const double y = (double)(r + fd.y_off);
-    const double bx0 = (double)mesh.min_src_x, bx1 = (double)mesh.W + (double)mesh.min_src_x;    // :1047
-    const double by0 = (double)mesh.min_src_y, by1 = (double)mesh.H + (double)mesh.min_src_y;
+    const int2 ms = frame_min_src(mesh, fr, f);              // this frame's source minima
+    const double bx0 = (double)ms.x, bx1 = (double)mesh.W + (double)ms.x;    // :1047
+    const double by0 = (double)ms.y, by1 = (double)mesh.H + (double)ms.y;
 
     for (int w = wave; w < nwin; w += 4) {
         const int c0 = w << 8, cq = c0 + (lane << 2);
@@ -288,13 +289,13 @@ __global__ __launch_bounds__(256) void k_tri_spans(PwMesh mesh, PwFrames fr, Row
 {
     const int t = blockIdx.x, f = blockIdx.y;
     const FrameDesc fd = fr.frames[f];
-    const float *dp = fr.dst_pts + (size_t)f * mesh.n_pts * 2;
+    const float *dp = fr.dst_pts + (size_t)f * mesh.n_pts * 2, *sp = frame_src(mesh, fr, f);
     float s[6], d[6];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         const uint32_t v = mesh.tris[3 * (size_t)t + k];
         if (v < (uint32_t)mesh.n_pts) {
-            s[2 * k] = mesh.src_pts[2 * (size_t)v]; s[2 * k + 1] = mesh.src_pts[2 * (size_t)v + 1];
+            s[2 * k] = sp[2 * (size_t)v]; s[2 * k + 1] = sp[2 * (size_t)v + 1];
             d[2 * k] = dp[2 * (size_t)v];           d[2 * k + 1] = dp[2 * (size_t)v + 1];
         } else {
             s[2 * k] = s[2 * k + 1] = d[2 * k] = d[2 * k + 1] = NAN;
@@ -374,13 +375,13 @@ __global__ __launch_bounds__(kTriGroupThreads) void k_tri_spans_grouped(PwMesh m
     const int64_t len = (int64_t)W * fd.obj_h;
     if (tid < kTriGroup && t0 + tid < mesh.n_tris) {
         const int t = t0 + tid;
-        const float *dp = fr.dst_pts + (size_t)f * mesh.n_pts * 2;
+        const float *dp = fr.dst_pts + (size_t)f * mesh.n_pts * 2, *sp = frame_src(mesh, fr, f);
         float s[6], d[6];
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             const uint32_t v = mesh.tris[3 * (size_t)t + k];
             if (v < (uint32_t)mesh.n_pts) {
-                s[2 * k] = mesh.src_pts[2 * (size_t)v]; s[2 * k + 1] = mesh.src_pts[2 * (size_t)v + 1];
+                s[2 * k] = sp[2 * (size_t)v]; s[2 * k + 1] = sp[2 * (size_t)v + 1];
                 d[2 * k] = dp[2 * (size_t)v];           d[2 * k + 1] = dp[2 * (size_t)v + 1];
             } else {
                 s[2 * k] = s[2 * k + 1] = d[2 * k] = d[2 * k + 1] = NAN;
@@ -474,6 +475,7 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
     //  source rows in the XCD's L2 from frame to frame: C3 0.551 fixed, 0.607 rotating.  The host decides, hg_api_piecewise.hip.)
     const int r0 = gi * rows_per_group;
     const FrameDesc fd = fr.frames[f];
+    const int2 ms = frame_min_src(mesh, fr, f);              // the source minima of :1047: the mesh's, or this frame's own (two scalars, fetched by the decoded frame index)
     // housekeeping for the NEXT step (saves its memset): the next status set is cleared here, and every workgroup zeroes the
     // span counters of its rows in the OTHER of the two counter sets -- the one the previous step consumed and the next step's
     // k_tri_spans will count into (ping-pong: nobody reads it during this launch, so no ordering against this launch's readers)
@@ -531,11 +533,11 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
     // All four are tested on the doubles: the rounded coordinates are only 32-bit (a source row of 300 * 2^24 must be
     // rejected, not wrapped back into the image); what the range check of the buffer load still provides is the `undefined`
     // -> 0 of flat indices that pass :1047 and yet fall outside the array (sx in [W - 0.5, W) on the last row).
-    const double bx_lo = sgpr_f64((double)mesh.min_src_x + 0.5), bx_hi = sgpr_f64((double)mesh.W + (double)mesh.min_src_x + 0.5);
-    const double by_lo = sgpr_f64((double)mesh.min_src_y + 0.5), by_hi = sgpr_f64((double)mesh.H + (double)mesh.min_src_y + 0.5);
+    const double bx_lo = sgpr_f64((double)ms.x + 0.5), bx_hi = sgpr_f64((double)mesh.W + (double)ms.x + 0.5);
+    const double by_lo = sgpr_f64((double)ms.y + 0.5), by_hi = sgpr_f64((double)mesh.H + (double)ms.y + 0.5);
     // HIB (host: hi_bounds_ok): the same four tests as two 32-bit compares on the high dwords of h (hg_dev.h)
-    const HiBounds hb = make_hi_bounds((double)mesh.min_src_x + 0.5, (double)mesh.W + (double)mesh.min_src_x + 0.5,
-                                       (double)mesh.min_src_y + 0.5, (double)mesh.H + (double)mesh.min_src_y + 0.5);
+    const HiBounds hb = make_hi_bounds((double)ms.x + 0.5, (double)mesh.W + (double)ms.x + 0.5,
+                                       (double)ms.y + 0.5, (double)mesh.H + (double)ms.y + 0.5);
     // 1 unless both end pixels lo, hi - 1 of a span with record {m0, m2*y, m4, m1, m3*y, m5} are inside the source window, computed as
     // the pixel body computes them (same fma, same rounding, same compares)
     const bool flag_spans = fr.safe_spans != 0;             // (wave-uniform; host: by the rows' span density)
@@ -975,6 +977,14 @@ bool pw_fast_ok(const PwMesh &mesh, int max_obj_w)
            (((int64_t)mesh.H + std::abs(mesh.min_src_y) + 2) * mesh.W + std::abs(mesh.min_src_x) + 2) * 4 < ((int64_t)1 << 31);
 }
 
+bool pw_fast_ok(const PwMesh &mesh, const PwFrames &fr, int max_obj_w)
+{
+    if (!fr.min_src) return pw_fast_ok(mesh, max_obj_w);
+    PwMesh lo = mesh, hi = mesh;                             // (the limits are on |minimum|: both ends of the set's range)
+    lo.min_src_x = fr.min_src_lo_x; lo.min_src_y = fr.min_src_lo_y; hi.min_src_x = fr.min_src_hi_x; hi.min_src_y = fr.min_src_hi_y;
+    return pw_fast_ok(lo, max_obj_w) && pw_fast_ok(hi, max_obj_w);
+}
+
 void launch_tri_spans(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl, hipStream_t stream)
 {
     if (mesh.n_tris <= 0 || fr.n_frames <= 0) return;
@@ -1010,7 +1020,7 @@ int launch_pw_rows(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl, u
     dim3 grid((unsigned)padded_groups(rpx, frs.sub_groups) * (unsigned)nx * (unsigned)fr.n_frames);
     // bounds :1047 on the high dwords of the rounded coordinates (hg_dev.h) whenever the source window allows it; the fp64
     // compares otherwise (negative source minimum, sources beyond 2^20 pixels a side) and in the parity-tap instantiations
-    const bool hib = !fr.no_hi_bounds && hi_bounds_ok(mesh.min_src_x, (int64_t)mesh.W + mesh.min_src_x, mesh.min_src_y, (int64_t)mesh.H + mesh.min_src_y);
+    const bool hib = !fr.no_hi_bounds && set_hi_bounds_ok(mesh, fr);
     const dim3 block(256);
     const size_t pad = (size_t)fr.lds_pad_kb * 1024;
 #define HG_ROWS(CAP, MAPF, PHV, CMP, HB, SF) do { code = 100000 + ((CAP) > kRowSpanCapFast ? 10000 : 0) + (PHV) * 1000 + ((CMP) ? 100 : 0) + ((HB) ? 10 : 0) + (int)(SF) + ((MAPF) ? 50 : 0); \

@@ -37,6 +37,7 @@ __global__ __launch_bounds__(256) void k_pw_tile(PwMesh mesh, PwFrames fr, RowLi
     if (!frame_group(fr, xcd, bg, groups_per_xcd, f, gi)) return;           // (bands, rotating bands or dealt sub-bands: hg_dev.h)
     const int r0 = gi * kTileRows, t0 = ct * tile_cols;                     // (tile_cols: the frame width split evenly, a multiple of 64, <= kTileCols)
     const FrameDesc fd = fr.frames[f];
+    const int2 ms = frame_min_src(mesh, fr, f);              // the source minima of :1047: the mesh's, or this frame's own (scalars, by the decoded frame index)
     if (bid == 0 && status_next) for (int i = threadIdx.x; i < fr.n_frames; i += 256) status_next[i] = 0;   // (see k_pw_rows)
     // the OTHER counter set, every row of the frame's block: clean for the next step (ping-pong, see k_pw_rows; the band counters live there)
     if (ct == 0 && (int)threadIdx.x < kTileRows && r0 + (int)threadIdx.x < rl.row_stride) rl.cnt_clear[(size_t)f * rl.row_stride + r0 + threadIdx.x] = 0;
@@ -191,8 +192,8 @@ __global__ __launch_bounds__(256) void k_pw_tile(PwMesh mesh, PwFrames fr, RowLi
     const int c = lane & 7, q = lane >> 3;
     const __amdgpu_buffer_rsrc_t src = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(frame_img(mesh, f)), 4, mesh.W * mesh.H, 0x00020000);   // (records of 4 bytes: gathers by pixel index, hg_struct_load_u32)
     const __amdgpu_buffer_rsrc_t dst = __builtin_amdgcn_make_buffer_rsrc(out + fd.out_off + (int64_t)r0 * W * 4, 0, nrows * W * 4, 0x00020000);
-    const double bx_lo = (double)mesh.min_src_x + 0.5, bx_hi = (double)mesh.W + (double)mesh.min_src_x + 0.5;
-    const double by_lo = (double)mesh.min_src_y + 0.5, by_hi = (double)mesh.H + (double)mesh.min_src_y + 0.5;
+    const double bx_lo = (double)ms.x + 0.5, bx_hi = (double)mesh.W + (double)ms.x + 0.5;
+    const double by_lo = (double)ms.y + 0.5, by_hi = (double)mesh.H + (double)ms.y + 0.5;
     const HiBounds hb = make_hi_bounds(bx_lo, bx_hi, by_lo, by_hi);
     const int nan_key = (int)0x80000000u | (kTileRecs * 48);
     uint32_t *tile = s_tile + wave * (kTileRows * kTilePitch);
@@ -325,7 +326,7 @@ int launch_pw_tile(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl, u
     PwFrames frs = fr;
     frs.sub_groups = sub_groups_of(fr, gpx);
     const dim3 grid((unsigned)padded_groups(gpx, frs.sub_groups) * (unsigned)nx * (unsigned)cts * (unsigned)fr.n_frames);
-    const bool hib = !fr.no_hi_bounds && hi_bounds_ok(mesh.min_src_x, (int64_t)mesh.W + mesh.min_src_x, mesh.min_src_y, (int64_t)mesh.H + mesh.min_src_y);
+    const bool hib = !fr.no_hi_bounds && set_hi_bounds_ok(mesh, fr);
     if (hib) hipLaunchKernelGGL((k_pw_tile<true>), grid, dim3(256), 0, stream, mesh, frs, rl, out, gpx, cts, tile_cols, status_next);
     else     hipLaunchKernelGGL((k_pw_tile<false>), grid, dim3(256), 0, stream, mesh, frs, rl, out, gpx, cts, tile_cols, status_next);
     return 500000 + kTilePB * 1000 + (hib ? 11 : 1);         // (variant code: see launch_pw_rows)

@@ -32,7 +32,7 @@ constexpr int kRowSpanCapDense = 512; // ... by its dense instantiation (README-
 constexpr int kRowGroup = 4;            // output rows per k_pw_rows workgroup (64 LDS slots each in packed mode)
 constexpr int kInvStride = 8;       // floats per inverse matrix on the device (6 used; 32-byte rows)
 
-struct PwMesh {                     // source side of the mesh + source image (shared by all frames)
+struct PwMesh {                     // source side of the mesh + source image (shared by all frames unless the frame set brings its own: PwFrames::src_pts)
     const float *src_pts;           // n_pts x 2
     const uint32_t *tris;           // n_tris x 3
     int32_t n_pts, n_tris;
@@ -49,9 +49,17 @@ __host__ __device__ __forceinline__ const uint8_t *frame_img(const PwMesh &m, in
     return m.n_imgs > 1 ? m.img + (uint64_t)(f % m.n_imgs) * m.img_stride : m.img;
 }
 
+struct PwFrames;
+// source points / source minima of frame f (frame sets with a source side of their own; f is uniform for the workgroup in every caller)
+__device__ __forceinline__ const float *frame_src(const PwMesh &m, const PwFrames &fr, int f);
+__device__ __forceinline__ int2 frame_min_src(const PwMesh &m, const PwFrames &fr, int f);
+
 struct PwFrames {                   // per-frame device arrays, frame-major
     const FrameDesc *frames;
     const float *dst_pts;           // F x n_pts x 2
+    const float *src_pts;           // F x n_pts x 2: frame f's own source points (hg_piecewise_set_frames_src); nullptr: the mesh's, for every frame
+    const int2 *min_src;            // F: frame f's {minSrcX, minSrcY} of the bounds test :1047; nullptr: the mesh's
+    int32_t min_src_lo_x, min_src_hi_x, min_src_lo_y, min_src_hi_y;   // host: extremes of min_src over the set (what the launchers decide the bounds form by)
     TriRange *trir;                 // F x n_tris
     int2 *trix;                     // F x n_tris: {floor(min x) - 1, ceil(max x) + 1} of the triangle's destiny vertices (column reach of its spans; k_pw_tile)
     Seg *segs;                      // F x n_tris x 3
@@ -89,6 +97,18 @@ struct PwFrames {                   // per-frame device arrays, frame-major
     int32_t band_stride, n_bands, band_cap, band_rows_log2;
 };
 
+__device__ __forceinline__ const float *frame_src(const PwMesh &m, const PwFrames &fr, int f)
+{
+    return fr.src_pts ? fr.src_pts + (size_t)f * m.n_pts * 2 : m.src_pts;
+}
+// (scalar registers: the pointer is a kernel argument and f is decoded from the block id -- the readfirstlanes only tell the compiler so)
+__device__ __forceinline__ int2 frame_min_src(const PwMesh &m, const PwFrames &fr, int f)
+{
+    if (!fr.min_src) return make_int2(m.min_src_x, m.min_src_y);
+    const int2 v = fr.min_src[__builtin_amdgcn_readfirstlane(f)];
+    return make_int2(__builtin_amdgcn_readfirstlane(v.x), __builtin_amdgcn_readfirstlane(v.y));
+}
+
 // Per-output-row span lists of the fast path (k_tri_spans -> k_pw_rows), in global memory.
 // Two entry formats, chosen per frame set (RowLists::compact):
 //   full    32 bytes: cells [lo,hi) of the row (16 bits each), triangle id, the triangle's inverse matrix.  Sparse rows
@@ -123,6 +143,8 @@ void launch_pw_fused(const PwMesh &mesh, const PwFrames &fr, uint8_t *out, int16
 
 // Fast path (see hg_k_piecewise.hip): eligibility, span-list build (includes the per-triangle solves), row warp.
 bool pw_fast_ok(const PwMesh &mesh, int max_obj_w);
+// ... for a whole frame set: with per-frame source minima, at both extremes of the set
+bool pw_fast_ok(const PwMesh &mesh, const PwFrames &fr, int max_obj_w);
 void launch_tri_spans(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl, hipStream_t stream);
 int launch_pw_rows(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl, uint8_t *out, int16_t *map_out, int32_t *status_next, hipStream_t stream);
 // Dense meshes (64..199 spans per row, obj_w <= 8192): 4 rows per workgroup, 16 x 4 pixel gather patches, one matrix record

@@ -867,14 +867,18 @@ static napi_value fn_release_batch(napi_env env, napi_callback_info info)
     return NULL;
 }
 
-enum { JOB_PW_INV, JOB_GEO_INV, JOB_PW_FWD, JOB_GEO_FWD };
-typedef struct { int type, kind; const float *dst, *from, *to; const double *m; int mx, my; size_t per; } batch_job;
+enum { JOB_PW_INV, JOB_GEO_INV, JOB_PW_FWD, JOB_GEO_FWD, JOB_PW_INV_SRC };
+/* src / min_src (JOB_PW_INV_SRC): the frames' own source points (F x 2N) and source minima (F x 2) */
+typedef struct { int type, kind; const float *dst, *from, *to; const double *m; int mx, my; size_t per; const float *src; const int32_t *min_src; } batch_job;
 
 /* frames [f0, f0 + n) of the job into d_out at offs[f0 ..] */
 static int job_launch(handle_t *h, const batch_job *j, const hg_geom *g, const size_t *offs, int f0, int n, void *d_out)
 {
     switch (j->type) {
     case JOB_PW_INV:  return hg_warp_inverse_piecewise_batch_device(h->ctx, j->dst + (size_t)f0 * 2 * h->n_pts, g + f0, offs + f0, n, d_out);
+    case JOB_PW_INV_SRC:
+        return hg_warp_inverse_piecewise_src_batch_device(h->ctx, j->src + (size_t)f0 * 2 * h->n_pts, j->min_src + (size_t)f0 * 2, j->dst + (size_t)f0 * 2 * h->n_pts,
+                                                          g + f0, offs + f0, n, d_out);
     case JOB_PW_FWD:  return hg_warp_forward_piecewise_batch_device(h->ctx, j->dst + (size_t)f0 * 2 * h->n_pts, j->mx, j->my, g + f0, offs + f0, n, d_out);
     case JOB_GEO_FWD: return hg_warp_forward_geometric_batch_device(h->ctx, j->kind, j->m + (size_t)f0 * 8, g + f0, offs + f0, n, d_out);
     default: {
@@ -1006,6 +1010,27 @@ static napi_value fn_warp_inverse_piecewise_batch(napi_env env, napi_callback_in
     if (F <= 0) return throw_str(env, "hgwarp: geoms must hold 4 integers per frame");
     if (h->n_pts == 0 || nd < (size_t)F * 2 * h->n_pts) return throw_str(env, "hgwarp: dstPoints must hold frames x mesh points x,y pairs (piecewiseSetMesh first)");
     return run_batch(env, h, &job, gv, F, 0, a + 3, argc - 3, "warpInversePiecewiseBatch");
+}
+
+/* warpInversePiecewiseSrcBatch(ctx, srcPoints F x 2N float32, minSrc Int32Array F x 2, dstPoints F x 2N float32, geoms Int32Array F x 4
+ * [, ownFrames, images, width, height]): warpInversePiecewiseBatch for frames that bring their own source points and source minima
+ * (hg_warp_inverse_piecewise_src_batch_device; triangles and point count are those of piecewiseSetMesh); same frames, pooling and {images} pipeline */
+static napi_value fn_warp_inverse_piecewise_src_batch(napi_env env, napi_callback_info info)
+{
+    napi_value a[9]; size_t argc = 9;
+    if (napi_get_cb_info(env, info, &argc, a, NULL, NULL) != napi_ok || argc < 5) return throw_str(env, "hgwarp: wrong number of arguments");
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    size_t ns, nm, nd, ng; batch_job job = { JOB_PW_INV_SRC, 0, NULL, NULL, NULL, NULL, 0, 0, 0, NULL, NULL };
+    job.src = (const float *)get_typed(env, a[1], napi_float32_array, &ns, "srcPoints"); if (!job.src) return NULL;
+    job.min_src = (const int32_t *)get_typed(env, a[2], napi_int32_array, &nm, "minSrc"); if (!job.min_src) return NULL;
+    job.dst = (const float *)get_typed(env, a[3], napi_float32_array, &nd, "dstPoints"); if (!job.dst) return NULL;
+    int32_t *gv = (int32_t *)get_typed(env, a[4], napi_int32_array, &ng, "geoms"); if (!gv) return NULL;
+    const int F = (int)(ng / 4);
+    if (F <= 0) return throw_str(env, "hgwarp: geoms must hold 4 integers per frame");
+    if (h->n_pts == 0 || nd < (size_t)F * 2 * h->n_pts || ns < (size_t)F * 2 * h->n_pts)
+        return throw_str(env, "hgwarp: srcPoints and dstPoints must hold frames x mesh points x,y pairs (piecewiseSetMesh first)");
+    if (nm < (size_t)F * 2) return throw_str(env, "hgwarp: minSrc must hold 2 integers per frame");
+    return run_batch(env, h, &job, gv, F, 0, a + 5, argc - 5, "warpInversePiecewiseSrcBatch");
 }
 
 /* warpInverseGeometricBatch(ctx, kind, from, to, geoms [, ownFrames, images, width, height]): from / to = F point sets each (3 or 4 points
@@ -1282,7 +1307,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "setImage", fn_set_image }, { "setImages", fn_set_images }, { "warpInverseGeometric", fn_warp_inverse_geometric },
         { "piecewiseSetMesh", fn_piecewise_set_mesh }, { "piecewisePrepare", fn_piecewise_prepare },
         { "warpInversePiecewise", fn_warp_inverse_piecewise }, { "getTriMap", fn_get_tri_map }, { "getMatrices", fn_get_matrices },
-        { "warpInversePiecewiseBatch", fn_warp_inverse_piecewise_batch }, { "warpInverseGeometricBatch", fn_warp_inverse_geometric_batch },
+        { "warpInversePiecewiseBatch", fn_warp_inverse_piecewise_batch }, { "warpInversePiecewiseSrcBatch", fn_warp_inverse_piecewise_src_batch }, { "warpInverseGeometricBatch", fn_warp_inverse_geometric_batch },
         { "warpForwardGeometric", fn_warp_forward_geometric }, { "warpForwardPiecewise", fn_warp_forward_piecewise },
         { "warpForwardPiecewiseBatch", fn_warp_forward_piecewise_batch }, { "warpForwardGeometricBatch", fn_warp_forward_geometric_batch },
         { "releaseBatch", fn_release_batch }, { "pinnedBuffer", fn_pinned_buffer },

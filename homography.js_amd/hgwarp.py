@@ -35,6 +35,7 @@ EXPORTS = [
     "hg_warp_inverse_geometric_frames_device", "hg_warp_inverse_geometric_batch_device", "hg_pack_offsets",
     "hg_piecewise_set_mesh", "hg_piecewise_prepare", "hg_warp_inverse_piecewise", "hg_warp_inverse_piecewise_device",
     "hg_piecewise_set_frames", "hg_warp_inverse_piecewise_frames_device", "hg_warp_inverse_piecewise_batch_device",
+    "hg_piecewise_set_frames_src", "hg_warp_inverse_piecewise_src_batch_device", "hg_piecewise_frame_min_src",
     "hg_get_tri_map", "hg_get_tri_map_fused", "hg_get_matrices", "hg_warp_inverse_piecewise_via_map",
     "hg_warp_forward_geometric", "hg_warp_forward_piecewise", "hg_warp_forward_geometric_device", "hg_warp_forward_geometric_batch_device",
     "hg_warp_forward_piecewise_device", "hg_warp_forward_piecewise_batch_device",
@@ -109,6 +110,9 @@ def lib():
         "hg_piecewise_set_frames": (i, [vp, f32p, C.POINTER(Geom), C.POINTER(sz), i]),
         "hg_warp_inverse_piecewise_frames_device": (i, [vp, vp]),
         "hg_warp_inverse_piecewise_batch_device": (i, [vp, f32p, C.POINTER(Geom), C.POINTER(sz), i, vp]),
+        "hg_piecewise_set_frames_src": (i, [vp, f32p, C.POINTER(C.c_int32), f32p, C.POINTER(Geom), C.POINTER(sz), i]),
+        "hg_warp_inverse_piecewise_src_batch_device": (i, [vp, f32p, C.POINTER(C.c_int32), f32p, C.POINTER(Geom), C.POINTER(sz), i, vp]),
+        "hg_piecewise_frame_min_src": (i, [f32p, i, C.POINTER(C.c_int32)]),
         "hg_get_tri_map": (i, [vp, C.POINTER(C.c_int16), sz]), "hg_get_tri_map_fused": (i, [vp, C.POINTER(C.c_int16), sz]),
         "hg_get_matrices": (i, [vp, f32p, f32p]), "hg_warp_inverse_piecewise_via_map": (i, [vp, u8p]),
         "hg_last_piecewise_kernel": (i, [vp]), "hg_last_piecewise_variant": (i, [vp]), "hg_last_geometric_kernel": (i, [vp]), "hg_last_piecewise_self": (i, [vp]), "hg_last_piecewise_flag": (i, [vp]), "hg_last_forward_kernel": (i, [vp]), "hg_set_option": (i, [vp, C.c_char_p, i]),
@@ -210,6 +214,14 @@ def minmax_xy(pts):
     out = np.empty(4, np.float64)
     _check(lib().hg_minmax_xy(p, a.size, out.ctypes.data_as(C.POINTER(C.c_double))))
     return out
+
+
+def frame_min_src(src_pts):
+    """(minSrcX, minSrcY) a fresh instance would hold for one frame's source points (hg_piecewise_frame_min_src)."""
+    a, p = _f32(src_pts)
+    out = (C.c_int32 * 2)()
+    _check(lib().hg_piecewise_frame_min_src(p, a.size // 2, out))
+    return int(out[0]), int(out[1])
 
 
 def projective_plain_range(m, geom):
@@ -548,6 +560,30 @@ class Context:
         assert d.size == 2 * self._n_pts * len(geoms), "frames x mesh points x,y pairs"
         offs = (C.c_size_t * len(geoms))(*offsets) if offsets is not None else None
         self._c(lib().hg_piecewise_set_frames(self._h, dp, _geoms(geoms), offs, len(geoms)))
+
+    def _src_args(self, src_pts, min_src, dst_pts, geoms, offsets):
+        (s, sp), (d, dp) = _f32(src_pts), _f32(dst_pts)
+        n = len(geoms)
+        assert s.size == 2 * self._n_pts * n and d.size == 2 * self._n_pts * n, "frames x mesh points x,y pairs on both sides"
+        ms = msp = None
+        if min_src is not None:
+            ms = np.ascontiguousarray(min_src, dtype=np.int32)
+            assert ms.size == 2 * n, "one {minSrcX, minSrcY} pair per frame"
+            msp = ms.ctypes.data_as(C.POINTER(C.c_int32))
+        offs = (C.c_size_t * n)(*offsets) if offsets is not None else None
+        if n == 1:
+            self._geom = Geom(*[int(v) for v in geoms[0]])      # (the single-frame forms and taps describe this frame)
+        return (s, d, ms), (sp, msp, dp, _geoms(geoms), offs, n)
+
+    def piecewise_set_frames_src(self, src_pts, min_src, dst_pts, geoms, offsets=None):
+        """Frames that bring their own source points (hg_piecewise_set_frames_src); min_src=None passes NULL: each frame's minima are
+        the rounded bounding-box minimum of its own source points."""
+        keep, args = self._src_args(src_pts, min_src, dst_pts, geoms, offsets)
+        self._c(lib().hg_piecewise_set_frames_src(self._h, *args))
+
+    def warp_inverse_piecewise_src_batch_device(self, src_pts, min_src, dst_pts, geoms, offsets, d_out):
+        keep, args = self._src_args(src_pts, min_src, dst_pts, geoms, offsets)
+        self._c(lib().hg_warp_inverse_piecewise_src_batch_device(self._h, *args, C.c_void_p(int(d_out))))
 
     def frame_set_args(self, dst_pts, geoms, offsets=None):
         """The ctypes arguments of piecewise_set_frames, built once: a caller that uploads one of a few point sets per step

@@ -301,8 +301,12 @@ class Homography {
      * frame, no fall-back to plain arrays in a loop that never yields (plain `node`, 4K, batches of 8: 0.73 instead of 2.05 ms per frame).
      * The slab counts against Homography.setPinnedLimit(); when it does not fit (or the limit is 0) the batch silently gets own frames.
      * With {images} the pass is pipelined: the upload of source f + 1 overlaps the download of frame f.
+     * {sourcePoints: [...]} (piecewise only; one source point set per destiny point set) = the loop
+     *     for (f) { setSourcePoints(src[f]); setDestinyPoints(dst[f]); warp(image_f); }
+     * -- every frame's landmarks live in its own image -- see _warpBatchMoving.
      */
     warpBatch(dstPointSets, options = {}) {
+        if (options.sourcePoints !== undefined && options.sourcePoints !== null) return this._warpBatchMoving(dstPointSets, options);
         if (this.transform === 'affine' || this.transform === 'projective') return this._warpBatchGeometric(dstPointSets, options);
         if (this.transform !== 'piecewiseaffine') throw ("hgwarp: warpBatch() needs a transform (set the source points first)");
         const F = dstPointSets.length, n = this._srcPoints.length;
@@ -386,6 +390,73 @@ class Homography {
         }
         for (let f = 0; f < F; f++) if (blank[f] === true) frames[f] = makeImageData(new Uint8ClampedArray(4), 1, 1);
         if (F > 0) this._lastPath = forward[F - 1] ? '_piecewiseAffineWarp' : '_inversePiecewiseAffineWarp';   // what the last warp() of the loop leaves behind
+        return this._releasable(frames);
+    }
+
+    /**
+     * warpBatch(dst, {sourcePoints: src}): the loop `setSourcePoints(src[f]); setDestinyPoints(dst[f]); warp(image_f)`, frame for frame.  Both
+     * setters run on the host exactly as in the loop, so every frame sees the instance as the loop would have left it: the source points of
+     * the moment, `_minSrcX / _minSrcY` AS THEY STAND (the reference refreshes them only while its map field is null, :252, :756-758: after
+     * the first frame they are stale, and the stale values are what :1047 tests), the window, and warp()'s dispatch (:421-422).  Frames
+     * that take the inverse loop with current matrices are recorded and go out as ONE batch through warpInversePiecewiseSrcBatch
+     * (hg_warp_inverse_piecewise_src_batch_device: per-frame source points and minima; own or pooled frames, {images} pipelined).  Every
+     * other frame -- the forward loop, a warp over held (stale) matrices, a blank window -- runs at once through warp() itself, in its
+     * place in the order.  Bare strings: a source list of another length, a transform that is not piecewise, {devices}.
+     */
+    _warpBatchMoving(dstPointSets, options) {
+        const srcSets = options.sourcePoints, F = dstPointSets.length;
+        if (this.transform !== 'piecewiseaffine' && this.firstTransformSelected !== 'piecewiseaffine')
+            throw (`hgwarp: warpBatch({sourcePoints}) needs a piecewise affine transform, but ${this.transform} is selected`);
+        if (!Array.isArray(srcSets) || srcSets.length !== F)
+            throw (`hgwarp: warpBatch({sourcePoints}) needs one source point set per destiny point set (${Array.isArray(srcSets) ? srcSets.length : 'none'} for ${F})`);
+        if (options.devices !== undefined && options.devices !== null)
+            throw ("hgwarp: warpBatch({sourcePoints}) runs on this instance's own device; {devices} cannot be combined with it");
+        const images = options.images === undefined || options.images === null ? null : options.images;
+        if (images !== null && (!Array.isArray(images) || images.length === 0)) throw ("hgwarp: warpBatch({images}) needs a non-empty array of ImageData-shaped sources");
+        const frames = new Array(F).fill(null);
+        const reuse = !(options.ownFrames === true || !(options.reuseBatchOutput === undefined ? this.reuseBatchOutput : options.reuseBatchOutput === true));
+        let pending = [], flushed = 0;
+        const flush = (last) => {
+            if (pending.length === 0) return;
+            const K = pending.length, n = pending[0].src.length;
+            const src = new Float32Array(K * n), dst = new Float32Array(K * n), mins = new Int32Array(K * 2), g = new Int32Array(K * 4);
+            pending.forEach((p, k) => { src.set(p.src, k * n); dst.set(p.dst, k * n); mins.set(p.min, 2 * k); g.set(p.win, 4 * k); });
+            // (the instance's one slab serves one native batch: only a batch that is both the first and the last of this call may use it)
+            const own = !(reuse && last && flushed === 0);
+            if (own) { let largest = 0; for (const p of pending) largest = Math.max(largest, p.win[2] * p.win[3] * 4); makeRoomFor(this._native, largest, K); }
+            const tris = pending[0].tris instanceof Uint32Array ? pending[0].tris : Uint32Array.from(pending[0].tris);
+            this._native.piecewiseSetMesh(this._ctx, pending[0].src, tris, pending[0].min[0], pending[0].min[1]);   // triangles + point count; the source side travels per frame
+            let datas;
+            if (images === null) { this._uploadImage(); datas = this._native.warpInversePiecewiseSrcBatch(this._ctx, src, mins, dst, g, own); }
+            else {                                                                                       // (the native side pipelines the uploads with the downloads)
+                datas = this._native.warpInversePiecewiseSrcBatch(this._ctx, src, mins, dst, g, own, pending.map((p) => p.image.data), pending[0].W, pending[0].H);
+                this._uploadedImage = null;                                                              // the next single-image warp uploads again
+            }
+            pending.forEach((p, k) => { frames[p.f] = makeImageData(datas[k], p.win[2], p.win[3]); });
+            pending = []; flushed++;
+        };
+        const i32 = (v) => Number.isInteger(v) && Math.abs(v) < 2147483648;
+        for (let f = 0; f < F; f++) {
+            this.setSourcePoints(srcSets[f]);                                                            // :218-265, as the loop does
+            this.setDestinyPoints(dstPointSets[f], options.pointsAreNormalized === undefined ? null : options.pointsAreNormalized);   // :337-380
+            const image = images ? images[f % images.length] : null;
+            if (image !== null) this.setImage(image);                                                    // warp(image_f) :409
+            else if (this._image === null) throw ("warp() must receive an image if it was not setted before through `setImage(img)` or  `setSourcePoints(points, img)`");
+            const [xo, yo, ow, oh] = this._window();
+            const inverse = options.inverse === true || this._sampling === 'bilinear' || ow > this._width || oh > this._height || ow * 1.2 < this._width || oh * 1.2 < this._height;   // :421-422
+            const batchable = this.transform === 'piecewiseaffine' && inverse && ow * oh >= 1 && (this.repairStaleMap || this._matricesAreCurrent()) &&
+                              i32(this._minSrcX) && i32(this._minSrcY) && ow * oh * 4 <= 2147483647;
+            if (!batchable) { frames[f] = this.warp(null, false, options.inverse === true); continue; }
+            // what _inversePiecewise leaves behind (:847-857)
+            this._lastPath = '_inversePiecewiseAffineWarp';
+            this._map = { kind: 'inverse', pts: Float32Array.from(this._dstPoints), tris: this._triangles, width: ow, height: oh, yOff: yo };
+            // one native batch has one triangle list and one source size
+            if (pending.length && !(sameTriangles(pending[0].tris, this._triangles) && pending[0].src.length === this._srcPoints.length &&
+                                    pending[0].W === this._width && pending[0].H === this._height)) flush(false);
+            pending.push({ f, src: Float32Array.from(this._srcPoints), dst: Float32Array.from(this._dstPoints), min: [this._minSrcX, this._minSrcY],
+                           win: [xo, yo, ow, oh], tris: this._triangles, image, W: this._width, H: this._height });
+        }
+        flush(true);
         return this._releasable(frames);
     }
 

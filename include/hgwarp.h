@@ -223,6 +223,29 @@ int hg_piecewise_set_frames(hg_ctx *ctx, const float *dst_points, const hg_geom 
 int hg_warp_inverse_piecewise_frames_device(hg_ctx *ctx, void *d_out);
 int hg_warp_inverse_piecewise_batch_device(hg_ctx *ctx, const float *dst_points, const hg_geom *geoms,
                                            const size_t *out_offsets, int n_frames, void *d_out);
+/* Frame sets whose frames bring their own SOURCE points -- the reference's loop
+ *     for (f) { h.setSourcePoints(src_f); h.setDestinyPoints(dst_f); out_f = h.warp(image_f); }
+ * (one image per frame through hg_set_images_device: each frame's landmarks live in its own image).  src_points = n_frames x
+ * n_points x,y float32, the source side of frame f; triangles and n_points stay those of hg_piecewise_set_mesh, which must have been
+ * called (HG_ERR_STATE otherwise).  min_src = n_frames x {minSrcX, minSrcY} int32, the values the bounds test :1047 uses for that
+ * frame, passed explicitly like hg_piecewise_set_mesh's (a binding that mirrors the reference's caches hands over what its state
+ * holds, stale values included); NULL = as a fresh instance would: the rounded bounding-box minimum of the frame's own source points
+ * (:758, the rule of hg_minmax_xy; hg_piecewise_frame_min_src is that rule for one frame, on the host).
+ * Frame f == _inversePiecewiseAffineWarp :1029-1058 with _srcPoints = src_f, _dstPoints = dst_f, the mesh's triangles,
+ * _minSrcX/Y = min_src[f], image f % n_images and window geoms[f]: bit-identical in nearest mode, the bilinear rules above otherwise.
+ * Everything downstream treats such a set like any other: hg_warp_inverse_piecewise_frames_device runs it, sets queue 63 deep
+ * without a wait, flagged frames are redone at hg_sync from the staged copy of their own set (source points and minima included), and
+ * with one frame the single-frame forms and taps (hg_warp_inverse_piecewise, _via_map, hg_get_tri_map[_fused], hg_get_matrices)
+ * describe that frame.  A later hg_piecewise_set_frames / hg_piecewise_prepare returns to the mesh-wide source side; the forward
+ * (scatter) entry points always use it.  HG_ERR_INVALID: NULL src_points / dst_points / geoms, n_frames <= 0, a source coordinate that
+ * is infinite or beyond 2^24 in magnitude (NaN stays legal); a refused call leaves the ctx without a frame set.
+ * Layout policy: the fast kernels need every frame's minima inside their ranges (|min| < 2^22), else the whole set takes the general
+ * kernel; the high-dword bounds form needs every frame's minima >= 0. */
+int hg_piecewise_set_frames_src(hg_ctx *ctx, const float *src_points, const int32_t *min_src, const float *dst_points,
+                                const hg_geom *geoms, const size_t *out_offsets, int n_frames);
+int hg_warp_inverse_piecewise_src_batch_device(hg_ctx *ctx, const float *src_points, const int32_t *min_src, const float *dst_points,
+                                               const hg_geom *geoms, const size_t *out_offsets, int n_frames, void *d_out);
+int hg_piecewise_frame_min_src(const float *src_points, int n_points, int32_t out[2]);
 /* Parity taps (debug / tests): the Int16Array map the reference would have built for the prepared frame
  * (len = obj_w*obj_h), via the materialising kernel (atomicMax rasteriser) or via the fused kernel's own lookup;
  * and the per-triangle forward / inverse matrices (n_triangles x 6 float32 each; either may be NULL). */
