@@ -609,7 +609,7 @@ static void run_warp(hg_ctx *c, uint8_t *d_out, int16_t *map_out)
     c->rows_clean = true;
 }
 
-static int check_pw_state(hg_ctx *c)
+int check_pw_state(hg_ctx *c)
 {
     if (!c->d_img) return fail(c, HG_ERR_STATE, "no source image: call hg_set_image first");
     if (!c->have_mesh) return fail(c, HG_ERR_STATE, "no mesh: call hg_piecewise_set_mesh first");

@@ -1,6 +1,6 @@
 // hg_ctx.h -- the context behind the C ABI of include/hgwarp.h and the helpers its translation units share
 // (hg_api.hip: library / context / buffers / host-side solves / source image; hg_api_geometric.hip; hg_api_piecewise.hip;
-// hg_api_forward.hip; hg_api_state.hip).  Internal: nothing here is exported.
+// hg_api_forward.hip; hg_api_state.hip; hg_api_field.hip).  Internal: nothing here is exported.
 #pragma once
 #include "../../include/hgwarp.h"
 #include "hg_kernels.h"
@@ -192,6 +192,12 @@ struct hg_ctx {
     float *d_geo_pts = nullptr; size_t geo_pts_cap = 0;        // F x (from | to) point sets
     int32_t *d_geo_plain = nullptr; size_t geo_plain_cap = 0;  // per-frame "plain division range" flags written by k_solve_frames
 
+    // source fields (hg_api_field.hip): the frame records of a set with the FIELD offsets in out_off, staged like a geometric set
+    FrameDesc *d_field_frames = nullptr; size_t field_frames_cap = 0;
+    GeoStage field_stage[4];
+    int field_stage_cur = -1;
+    uint8_t *d_field_tmp = nullptr; size_t field_tmp_cap = 0; // the host-output forms' device copy
+
     // scratch
     int32_t *d_map32 = nullptr; size_t map32_cap = 0;
     int32_t *d_fmap = nullptr; size_t fmap_cap = 0;            // forward (source-side) triangle map of the current mesh, kept across warps
@@ -292,4 +298,5 @@ int settle_output_conflicts(hg_ctx *c, const void *out, size_t extent, uint64_t 
 int piecewise_set_frames(hg_ctx *c, const float *dst, const hg_geom *geoms, const size_t *offs, int n, bool quick_layout);   // hg_api_piecewise.hip
 PwMesh mesh_of(const hg_ctx *c);                             // hg_api_piecewise.hip: kernel argument blocks of the current mesh / frame set
 PwFrames frames_of(const hg_ctx *c);
+int check_pw_state(hg_ctx *c);                               // hg_api_piecewise.hip: image, mesh and frame set present?
 int redo_forward_frame_staged(hg_ctx *c, int stage, int f, int max_src_x, int max_src_y, uint8_t *d_out);    // hg_api_piecewise.hip, beside its inverse twin

@@ -168,6 +168,21 @@ void launch_map_to_i16(const int32_t *map32, int16_t *map16, size_t n, hipStream
 void launch_map_max_i16(const int32_t *map32, size_t n, int32_t *out, hipStream_t stream);      // *out = largest (int16) value of the first n cells, -1 if none
 void launch_fill_i32(int32_t *p, size_t n, int32_t v, hipStream_t stream);      // grid-stride fill (map / winner-buffer initialisation)
 
+// Source fields (hg_k_field.hip; include/hgwarp.h HG_FIELD_*).  fmt: 0 = HG_FIELD_INDEX (int32 per pixel), 1 = HG_FIELD_COORDS (2 x f32 per pixel).
+// Every frame record handed to these launchers carries the byte offset of the frame's FIELD in out_off (not that of its RGBA).
+struct GeoFieldOne { FrameDesc fd; double m[8]; };          // one frame by value (launch_geo_field with frames == nullptr)
+// k_geo_field: the field of the loop :997-1011 for all frames in one launch; mats = F x 8 doubles (inverse matrices).
+void launch_geo_field(int kind, int fmt, const FrameDesc *frames, const double *mats, const GeoFieldOne &one, int n_frames, int max_h,
+                      int W, int H, uint8_t *field, hipStream_t stream);
+// k_pw_field: the field of the loop :1042-1056 for all frames, behind k_tri_setup; k_pw_fused's prologue, resolve and flag protocol.
+void launch_pw_field(const PwMesh &mesh, const PwFrames &fr, int fmt, uint8_t *field, hipStream_t stream);
+// k_field_from_map: the redo of ONE flagged frame (index f) from the map launch_map_build materialised.
+void launch_field_from_map(const PwMesh &mesh, const PwFrames &fr, int f, const FrameDesc &fd, const int32_t *map32, int fmt, uint8_t *field,
+                           hipStream_t stream);
+// k_remap_index<pixel_bytes>: out[i] = 0 <= field[i] < n_src ? src[field[i]] : 0; k_remap_bilinear_f32<channels>: four clamped taps per pixel.
+void launch_remap_index(const int32_t *field, size_t n, const void *src, size_t n_src, int pixel_bytes, void *out, hipStream_t stream);
+void launch_remap_bilinear_f32(const float *coords, size_t n, const float *src, int W, int H, int channels, float *out, hipStream_t stream);
+
 // k_geo: _inverseGeometricWarp pixel loop :997-1011 for all frames.  mats = F x 8 doubles (inverse matrices).
 // f32_exact: every affine matrix entry is a float value and |x| < 2^28 (lets the kernel use an exact-product fma).
 // n_imgs / img_stride: frame f reads the source at img + (f % n_imgs) * img_stride.

@@ -747,6 +747,44 @@ static napi_value fn_get_tri_map(napi_env env, napi_callback_info info)
     return r;
 }
 
+/* fieldInverseGeometric(handle, kind, matrix, xOff, yOff, objW, objH, format) / fieldInversePiecewise(handle, format): the source field of
+ * the inverse warp (hg_field_*): an Int32Array of objW * objH pixel indices (format 0) or a Float32Array of objW * objH (sx, sy) pairs (1). */
+static napi_value make_field(napi_env env, int fmt, size_t px, void **out)
+{
+    if (fmt == HG_FIELD_INDEX) return make_typed(env, napi_int32_array, px, 4, out);
+    if (fmt == HG_FIELD_COORDS) return make_typed(env, napi_float32_array, 2 * px, 4, out);
+    return throw_str(env, "hgwarp: unknown field format");
+}
+
+static napi_value fn_field_inverse_geometric(napi_env env, napi_callback_info info)
+{
+    napi_value a[8];
+    if (!get_args(env, info, 8, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    int kind, fmt; size_t n; hg_geom g;
+    if (!get_i32(env, a[1], &kind)) return NULL;
+    double *m = (double *)get_typed(env, a[2], napi_float64_array, &n, "matrix"); if (!m) return NULL;
+    if (n < (size_t)(kind == HG_AFFINE ? 6 : 8)) return throw_str(env, "hgwarp: matrix too short");
+    if (!get_geom(env, a + 3, &g) || !get_i32(env, a[7], &fmt)) return NULL;
+    const size_t px = (g.obj_w > 0 && g.obj_h > 0) ? (size_t)g.obj_w * g.obj_h : 0;
+    void *out; napi_value r = make_field(env, fmt, px, &out); if (!r) return NULL;
+    if (px) HG_CALL(h->ctx, "hg_field_inverse_geometric", hg_field_inverse_geometric(h->ctx, kind, m, g, fmt, out));
+    return r;
+}
+
+static napi_value fn_field_inverse_piecewise(napi_env env, napi_callback_info info)
+{
+    napi_value a[2];
+    if (!get_args(env, info, 2, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    int fmt;
+    if (!get_i32(env, a[1], &fmt)) return NULL;
+    const size_t px = (h->obj_w > 0 && h->obj_h > 0) ? (size_t)h->obj_w * h->obj_h : 0;
+    void *out; napi_value r = make_field(env, fmt, px, &out); if (!r) return NULL;
+    if (px) HG_CALL(h->ctx, "hg_field_inverse_piecewise", hg_field_inverse_piecewise(h->ctx, fmt, out));
+    return r;
+}
+
 /* redoneFrames(ctx): frames the fused kernels flagged and hg_sync redid through the map so far (hg_redone_frames; tests) */
 static napi_value fn_redone_frames(napi_env env, napi_callback_info info)
 {
@@ -1311,6 +1349,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "warpForwardGeometric", fn_warp_forward_geometric }, { "warpForwardPiecewise", fn_warp_forward_piecewise },
         { "warpForwardPiecewiseBatch", fn_warp_forward_piecewise_batch }, { "warpForwardGeometricBatch", fn_warp_forward_geometric_batch },
         { "releaseBatch", fn_release_batch }, { "pinnedBuffer", fn_pinned_buffer },
+        { "fieldInverseGeometric", fn_field_inverse_geometric }, { "fieldInversePiecewise", fn_field_inverse_piecewise },
         { "solveAffineTriangles", fn_solve_affine_triangles }, { "warpInversePiecewiseState", fn_warp_inverse_piecewise_state },
         { "warpForwardPiecewiseState", fn_warp_forward_piecewise_state },
         { "release", fn_release }, { "setPinnedLimit", fn_set_pinned_limit }, { "poolStats", fn_pool_stats }, { "redoneFrames", fn_redone_frames }, { "setSampling", fn_set_sampling }, { "multiSetSampling", fn_multi_set_sampling }, { "_poolTestFrames", fn_pool_test_frames }, { "poolPressure", fn_pool_pressure }, { "poolCollected", fn_pool_collected },

@@ -20,6 +20,8 @@ LIB_PATH = os.environ.get("HGWARP_LIB") or os.path.join(HERE, "lib", "libhgwarp.
 HG_AFFINE, HG_PROJECTIVE = 0, 1
 # sampling modes of the inverse warps (hg_set_sampling): nearest is the reference's pixel copy, bilinear is opt-in
 SAMPLE_NEAREST, SAMPLE_BILINEAR = 0, 1
+# formats of the source field of an inverse warp (hg_field_*): int32 pixel index / interleaved float32 (sx, sy) per output pixel
+FIELD_INDEX, FIELD_COORDS = 0, 1
 
 # every symbol include/hgwarp.h declares (tests check that the built library exports all of them)
 EXPORTS = [
@@ -43,6 +45,8 @@ EXPORTS = [
     "hg_upload_on_copy_stream", "hg_fence_copies", "hg_download_behind_warps", "hg_fence_downloads",
     "hg_set_timing", "hg_last_kernel_ms", "hg_kernel_ms_stats", "hg_last_piecewise_kernel", "hg_last_piecewise_variant", "hg_last_geometric_kernel", "hg_last_piecewise_self", "hg_last_piecewise_flag", "hg_last_forward_kernel", "hg_forward_tiles_admissible", "hg_redone_frames", "hg_layout_walks", "hg_set_option", "hg_xcc_count", "hg_selftest_division", "hg_projective_plain_range", "hg_affine_one_fma_form",
     "hg_set_sampling", "hg_get_sampling", "hg_multi_set_sampling",
+    "hg_pack_field_offsets", "hg_field_inverse_geometric", "hg_field_inverse_geometric_device", "hg_field_inverse_geometric_frames_device",
+    "hg_field_inverse_piecewise", "hg_field_inverse_piecewise_frames_device", "hg_remap_index_device", "hg_remap_bilinear_f32_device",
 ]
 
 
@@ -129,6 +133,12 @@ def lib():
         "hg_warp_forward_piecewise_batch_device": (i, [vp, f32p, i, i, C.POINTER(Geom), C.POINTER(sz), i, vp]),
         "hg_upload_on_copy_stream": (i, [vp, vp, vp, sz]), "hg_fence_copies": (i, [vp]), "hg_download_behind_warps": (i, [vp, vp, vp, sz]), "hg_fence_downloads": (i, [vp]),
         "hg_solve_affine_triangles": (i, [f32p, f32p, i, C.POINTER(C.c_uint32), i, f32p]),
+        "hg_pack_field_offsets": (i, [C.POINTER(Geom), i, i, C.POINTER(sz), C.POINTER(sz)]),
+        "hg_field_inverse_geometric": (i, [vp, i, f64p, Geom, i, vp]), "hg_field_inverse_geometric_device": (i, [vp, i, f64p, Geom, i, vp]),
+        "hg_field_inverse_geometric_frames_device": (i, [vp, i, C.POINTER(sz), vp]),
+        "hg_field_inverse_piecewise": (i, [vp, i, vp]), "hg_field_inverse_piecewise_frames_device": (i, [vp, i, C.POINTER(sz), vp]),
+        "hg_remap_index_device": (i, [vp, vp, sz, vp, sz, i, vp]),
+        "hg_remap_bilinear_f32_device": (i, [vp, vp, sz, vp, i, i, i, vp]),
         "hg_warp_inverse_piecewise_state": (i, [vp, f32p, i, C.POINTER(TriMapDef), i, i, Geom, u8p]),
         "hg_warp_forward_piecewise_state": (i, [vp, f32p, i, C.POINTER(TriMapDef), i, i, i, i, Geom, u8p]),
     }
@@ -264,6 +274,19 @@ def pack_offsets(geoms):
     total = C.c_size_t(0)
     _check(lib().hg_pack_offsets(g, len(geoms), offs, C.byref(total)))
     return list(offs), total.value
+
+
+def pack_field_offsets(geoms, fmt):
+    """(offsets, total bytes) of the packed field layout of a frame set: 256-byte aligned starts, 4 (FIELD_INDEX) or 8 (FIELD_COORDS) bytes per pixel."""
+    g = _geoms(geoms)
+    offs = (C.c_size_t * max(len(geoms), 1))()
+    total = C.c_size_t(0)
+    _check(lib().hg_pack_field_offsets(g, len(geoms), int(fmt), offs, C.byref(total)))
+    return list(offs)[:len(geoms)], total.value
+
+
+def _field_array(fmt, h, w):
+    return np.empty((max(h, 0), max(w, 0)), np.int32) if int(fmt) == FIELD_INDEX else np.empty((max(h, 0), max(w, 0), 2), np.float32)
 
 
 def device_count():
@@ -512,6 +535,48 @@ class Context:
 
     def warp_inverse_geometric_frames_device(self, d_out):
         self._c(lib().hg_warp_inverse_geometric_frames_device(self._h, C.c_void_p(int(d_out))))
+
+    # ---- source fields and remaps (include/hgwarp.h, HG_FIELD_*)
+    def field_inverse_geometric(self, kind, m, geom, fmt):
+        """The source field of warp_inverse_geometric(kind, m, geom): (h, w) int32 (FIELD_INDEX) or (h, w, 2) float32 (FIELD_COORDS)."""
+        a, p = _f64(m)
+        assert a.size >= (6 if int(kind) == 0 else 8)
+        g = Geom(*[int(v) for v in geom])
+        out = _field_array(fmt, g.obj_h, g.obj_w)
+        self._c(lib().hg_field_inverse_geometric(self._h, int(kind), p, g, int(fmt), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def field_inverse_geometric_device(self, kind, m, geom, fmt, d_field):
+        a, p = _f64(m)
+        assert a.size >= (6 if int(kind) == 0 else 8)
+        self._c(lib().hg_field_inverse_geometric_device(self._h, int(kind), p, Geom(*[int(v) for v in geom]), int(fmt), C.c_void_p(int(d_field))))
+
+    def field_inverse_geometric_frames_device(self, fmt, d_field, offsets=None):
+        """The fields of the staged geometric frame set; offsets=None: packed as pack_field_offsets does."""
+        offs = (C.c_size_t * len(offsets))(*offsets) if offsets is not None else None
+        self._c(lib().hg_field_inverse_geometric_frames_device(self._h, int(fmt), offs, C.c_void_p(int(d_field))))
+
+    def field_inverse_piecewise(self, fmt):
+        """The source field of the prepared piecewise frame: (h, w) int32 or (h, w, 2) float32."""
+        g = self._geom
+        out = _field_array(fmt, g.obj_h, g.obj_w)
+        self._c(lib().hg_field_inverse_piecewise(self._h, int(fmt), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def field_inverse_piecewise_frames_device(self, fmt, d_field, offsets=None):
+        """The fields of the staged piecewise frame set (settled inside the call); offsets=None: packed as pack_field_offsets does."""
+        offs = (C.c_size_t * len(offsets))(*offsets) if offsets is not None else None
+        self._c(lib().hg_field_inverse_piecewise_frames_device(self._h, int(fmt), offs, C.c_void_p(int(d_field))))
+
+    def remap_index_device(self, d_field, n_px, d_src, n_src_px, pixel_bytes, d_out):
+        """out[i] = src[field[i]] where 0 <= field[i] < n_src_px, else zeros; pixels of 1, 2, 4, 8 or 16 bytes (asynchronous)."""
+        self._c(lib().hg_remap_index_device(self._h, C.c_void_p(int(d_field)), int(n_px), C.c_void_p(int(d_src)), int(n_src_px), int(pixel_bytes),
+                                            C.c_void_p(int(d_out))))
+
+    def remap_bilinear_f32_device(self, d_coords, n_px, d_src, w, h, channels, d_out):
+        """Bilinear gather of 1..4 interleaved float32 channels of a w x h source through a FIELD_COORDS field (asynchronous)."""
+        self._c(lib().hg_remap_bilinear_f32_device(self._h, C.c_void_p(int(d_coords)), int(n_px), C.c_void_p(int(d_src)), int(w), int(h), int(channels),
+                                                   C.c_void_p(int(d_out))))
 
     # ---- piecewise
     def piecewise_set_mesh(self, src_pts, tris, min_src_x, min_src_y):

@@ -280,6 +280,44 @@ class Homography {
     }
 
     /**
+     * The SOURCE FIELD of the inverse loop for the instance's current transform and points, over the window warp() would use (not part of
+     * the reference; include/hgwarp.h, HG_FIELD_*): for every output pixel, which source pixel `warp(null, false, true)` copies.
+     *   'index'   Int32Array, one flat pixel index per output pixel, -1 where the loop writes nothing or reads outside the array:
+     *             out32[i] = data[i] >= 0 ? image32[data[i]] : 0 is warp(null, false, true).data, byte for byte;
+     *   'coords'  Float32Array, (sx, sy) per output pixel (the loop's f64 coordinate rounded once), NaN where the loop's test fails.
+     * Always the inverse loop, whatever warp() would dispatch to; independent of the sampling mode; records neither a map nor a path
+     * (the reference-visible state stays that of the last warp).  Masks, depth maps, labels go through the picture's geometry by a gather over `data`.
+     * Returns { data, width, height }.  Throws a string for an unknown format, and for the reference-state quirks (matrices of an older
+     * point set after setSourcePoints / setTriangles without a setDestinyPoints): call setDestinyPoints first.
+     */
+    sourceField(format = 'index') {
+        if (format !== 'index' && format !== 'coords') throw ("sourceField: format must be 'index' or 'coords'");
+        if (this._image === null) throw ("sourceField() needs an image: call `setImage(img)` or `setSourcePoints(points, img)` first");
+        const fmt = format === 'index' ? 0 : 1;
+        const [xo, yo, ow, oh] = this._window();
+        const empty = () => ({ data: fmt === 0 ? new Int32Array(0) : new Float32Array(0), width: 0, height: 0 });
+        let data;
+        if (this.transform === 'piecewiseaffine') {
+            if (!(this.repairStaleMap || this._matricesAreCurrent()))
+                throw ("sourceField: the piecewise matrices belong to an older point set (call setDestinyPoints first)");
+            if (!(ow * oh >= 1)) return empty();
+            checkedMapLength(ow * oh);
+            this._uploadImage();
+            this._uploadMesh();
+            this._native.piecewisePrepare(this._ctx, asF32(this._dstPoints), xo, yo, ow, oh);
+            data = this._native.fieldInversePiecewise(this._ctx, fmt);
+        } else {
+            this._alignRanges();
+            const inv = this._solve(this._dstPoints, this._srcPoints);
+            if (!(ow * oh >= 1)) return empty();
+            checkedMapLength(ow * oh);
+            this._uploadImage();
+            data = this._native.fieldInverseGeometric(this._ctx, this.transform === 'affine' ? AFFINE : PROJECTIVE, Float64Array.from(inv), xo, yo, ow, oh, fmt);
+        }
+        return { data, width: ow, height: oh };
+    }
+
+    /**
      * The benchmarked caller loop `for (f) { setDestinyPoints(dst[f]); warp(); }` (test/benchmark.js:107-110) as GPU batches.
      * dstPointSets: array of point sets.  Returns an array of ImageData-shaped frames, frame f identical to what the loop returns
      * for it -- INCLUDING warp()'s choice between the inverse and the forward (scatter-semantics) loop, made per frame on that

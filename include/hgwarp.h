@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define HG_VERSION 100          /* 0.1.0 (sampling modes are detected by the presence of hg_set_sampling) */
+#define HG_VERSION 100          /* 0.1.0 (sampling modes are detected by the presence of hg_set_sampling, source fields by that of hg_field_inverse_geometric) */
 
 enum {
     HG_OK = 0,
@@ -50,6 +50,10 @@ enum { HG_AFFINE = 0, HG_PROJECTIVE = 1 };
 
 /* Sampling modes of the inverse warps (hg_set_sampling).  Not part of the reference, which always copies the nearest pixel. */
 enum { HG_SAMPLE_NEAREST = 0, HG_SAMPLE_BILINEAR = 1 };
+
+/* Formats of the SOURCE FIELD of an inverse warp (hg_field_*): for every output pixel, which source pixel the nearest loop reads
+ * (HG_FIELD_INDEX, one int32) or where it looks (HG_FIELD_COORDS, two float32).  Not part of the reference. */
+enum { HG_FIELD_INDEX = 0, HG_FIELD_COORDS = 1 };
 
 typedef struct hg_ctx hg_ctx;
 
@@ -255,6 +259,58 @@ int hg_get_matrices(hg_ctx *ctx, float *fwd, float *inv);
 /* Same warp through the materialised map (map build kernel + map-reading warp kernel).  Always available; it is also
  * what the library itself re-runs for a frame whose rows overflow the fused kernel's LDS span list. */
 int hg_warp_inverse_piecewise_via_map(hg_ctx *ctx, uint8_t *out_host);
+
+/* ------------------------------------------------------------------------------------------------ source fields and remaps
+ * The geometry of an inverse warp without its pixels: callers that hold a mask, a depth or flow map, a label image or float features
+ * beside the picture send those planes through exactly the picture's geometry by a gather (hg_remap_*), or hand the field to their own
+ * code.  A field is computed from the f64 source coordinate (sx, sy) of the loops :997-1011 / :1042-1056 -- JS operation order, contraction
+ * off, the very value the warp kernels round -- and the coverage test of the loop (:1001; :1045-1047 with the frame's minSrc for piecewise).
+ *   HG_FIELD_INDEX   one int32 per output pixel: the flat PIXEL index Math.round(sy) * W + Math.round(sx) the nearest loop reads (:1005 /
+ *                    :1049; no minSrc subtraction) where the pixel passes the coverage test AND the index lies in [0, W*H); else -1 (no
+ *                    triangle, a coordinate out of bounds or NaN, or an index outside the array, which JS reads as undefined -> 0).  Hence
+ *                        out32[i] = idx[i] >= 0 ? img32[idx[i]] : 0
+ *                    IS the nearest warp, byte for byte, the reference's wrap of sx in [W - 0.5, W) into the next row included.  With
+ *                    hg_set_images_device the index of frame f is relative to image f % n_images.  A source of 2^31 pixels or more:
+ *                    HG_ERR_INVALID for this format.
+ *   HG_FIELD_COORDS  two float32 per output pixel, interleaved (sx, sy): the f64 coordinate rounded ONCE to f32, for every pixel that
+ *                    passes the coverage test; every other pixel holds 0x7fc00000 (a quiet NaN, that exact pattern) in both words.  A
+ *                    covered pixel whose index falls outside the array is still covered here: index >= 0 implies "not NaN", not the
+ *                    other way round.  A coordinate just below W may round to W itself in f32 (likewise H): consumers clamp their taps,
+ *                    as hg_remap_bilinear_f32_device does.
+ * Both are independent of hg_set_sampling: the mode is neither read nor changed.  Field calls leave hg_last_piecewise_kernel / _variant /
+ * _self, hg_last_geometric_kernel, hg_last_forward_kernel and the layout the policy learned for the mesh as they found them.
+ * Layout: frame f is row-major obj_w x obj_h at field_offsets[f] bytes into d_field (NULL: packed as hg_pack_field_offsets does; the RGBA
+ * out_offsets of the frame set play no part); offsets are multiples of the pixel size (4 / 8 bytes; HG_ERR_INVALID otherwise), d_field is
+ * aligned to 16 bytes or more (any hg_device_alloc / hipMalloc pointer).  Bytes between frames are never written; empty frames write nothing.
+ * HG_ERR_INVALID: unknown format, NULL pointers.  HG_ERR_STATE: no source image (its size is needed), no mesh, no frame set. */
+/* Host only: offsets[i] = start of frame i's field (256-byte aligned), *total = bytes needed; 4 (index) or 8 (coords) bytes per pixel. */
+int hg_pack_field_offsets(const hg_geom *geoms, int n_frames, int format, size_t *offsets, size_t *total);
+/* The field of hg_warp_inverse_geometric(kind, m, geom): synchronous into host memory, or asynchronous into GPU memory.  Neither touches
+ * a staged frame set. */
+int hg_field_inverse_geometric(hg_ctx *ctx, int kind, const double *m, hg_geom geom, int format, void *out_host);
+int hg_field_inverse_geometric_device(hg_ctx *ctx, int kind, const double *m, hg_geom geom, int format, void *d_field);
+/* ... of the staged set of hg_geometric_set_frames[_points], all frames in one launch (point sets: the matrices are solved on the device
+ * first, as at the head of every warp of the set).  Asynchronous. */
+int hg_field_inverse_geometric_frames_device(hg_ctx *ctx, int format, const size_t *field_offsets, void *d_field);
+/* The field of hg_warp_inverse_piecewise for the prepared frame (exactly one frame staged), into host memory. */
+int hg_field_inverse_piecewise(hg_ctx *ctx, int format, void *out_host);
+/* ... of the staged set of hg_piecewise_set_frames / _set_frames_src / hg_piecewise_prepare; per-frame source points and min_src are
+ * honoured.  Runs on the general path and is SETTLED INSIDE THE CALL, as bilinear piecewise warps are: queued warp runs are settled first
+ * (they keep their own results); a frame with a row of more than 1024 spans, or with irregular triangles, is only flagged by the kernel and
+ * redone through the materialised map before the call returns (counted in hg_redone_frames).  The field is final on return. */
+int hg_field_inverse_piecewise_frames_device(hg_ctx *ctx, int format, const size_t *field_offsets, void *d_field);
+/* out[i] = 0 <= field[i] < n_src_px ? src[field[i]] : all-zero, for i < n_px, pixels being opaque blocks of pixel_bytes = 1, 2, 4, 8 or 16
+ * bytes (anything else: HG_ERR_INVALID); d_src and d_out aligned to the block size, d_field (int32) to 4 bytes.  Asynchronous on the ctx
+ * stream.  No read ever leaves [0, n_src_px), whatever the field holds: caller-made fields are legal.  With 4-byte pixels and the RGBA
+ * source this is the nearest warp. */
+int hg_remap_index_device(hg_ctx *ctx, const void *d_field, size_t n_px, const void *d_src, size_t n_src_px, int pixel_bytes, void *d_out);
+/* Bilinear gather of `channels` (1..4) interleaved float32 planes of a W x H source (W, H >= 1) through a HG_FIELD_COORDS field (or any
+ * caller-made (sx, sy) list; 8-byte aligned).  Asynchronous on the ctx stream.  Pixel i: if sx or sy is NaN or infinite every channel is 0;
+ * otherwise x0 = floorf(sx), fx = sx - x0, tap columns clamp(x0, 0, W-1) and clamp(x0 + 1.0f, 0, W-1), rows alike -- clamped in float before
+ * the integer conversion, so that 1e30 is a legal coordinate -- and per channel in f32, contraction off,
+ *     v = (p00*(1-fx) + p01*fx)*(1-fy) + (p10*(1-fx) + p11*fx)*fy,
+ * stored as it is (no rounding, no clamping): the operation order of the bilinear sampling mode, so a float32 model matches bit for bit. */
+int hg_remap_bilinear_f32_device(hg_ctx *ctx, const void *d_coords, size_t n_px, const float *d_src, int W, int H, int channels, float *d_out);
 
 /* ------------------------------------------------------------------------------------------------ forward (scatter) paths
  * What warp() dispatches to when the output is not larger than the input (:421, :426).  `m` is the FORWARD matrix
