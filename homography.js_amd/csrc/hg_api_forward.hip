@@ -69,10 +69,15 @@ extern "C" int hg_forward_tiles_admissible(int kind, const double *m, int W, int
     return P.use_inv ? 2 : 1;
 }
 
-extern "C" int hg_warp_forward_geometric_batch_device(hg_ctx *c, int kind, const double *m, const hg_geom *geoms, const size_t *offs, int n, void *d_out)
+// _geometricWarp :911-932 for n matrices.  field: the frames' SOURCE FIELDS instead of their pictures (hg_field_forward_geometric_batch_device):
+// the same limits, the same path selection and the same launches with the field tails; d_out is then the field buffer, offs the field offsets
+// (an index field has 4 bytes per pixel like a picture, so fill_frames packs and checks them as hg_pack_field_offsets would), and the tap
+// written is the field's own (hg_last_forward_field_kernel), not hg_last_forward_kernel.
+static int forward_geometric_batch(hg_ctx *c, int kind, const double *m, const hg_geom *geoms, const size_t *offs, int n, void *d_out, bool field)
 {
     HG_TRY(bind(c));
-    if ((kind != HG_AFFINE && kind != HG_PROJECTIVE) || !m || !geoms || n <= 0 || !d_out) return fail(c, HG_ERR_INVALID, "hg_warp_forward_geometric: bad arguments");
+    if ((kind != HG_AFFINE && kind != HG_PROJECTIVE) || !m || !geoms || n <= 0 || !d_out)
+        return fail(c, HG_ERR_INVALID, field ? "hg_field_forward_geometric: bad arguments" : "hg_warp_forward_geometric: bad arguments");
     if (!c->d_img) return fail(c, HG_ERR_STATE, "no source image: call hg_set_image first");
     HG_TRY(forward_limits(c, c->W, c->H, "the source image"));
     std::vector<FrameDesc> fds;
@@ -111,23 +116,54 @@ extern "C" int hg_warp_forward_geometric_batch_device(hg_ctx *c, int kind, const
                 batch.params = reinterpret_cast<const FwdParam *>(c->d_fwd_par);
                 batch.frames = reinterpret_cast<const FrameDesc *>(c->d_fwd_par + sizeof(FwdParam) * n);
             }
-            launch_fwd_tiles(kind, batch, n, mw, mh, c->d_img, c->n_imgs, c->img_stride, c->W, c->H, static_cast<uint8_t *>(d_out), c->stream);
+            if (field) launch_fwd_tiles_field(kind, batch, n, mw, mh, c->W, c->H, static_cast<uint8_t *>(d_out), c->stream);
+            else launch_fwd_tiles(kind, batch, n, mw, mh, c->d_img, c->n_imgs, c->img_stride, c->W, c->H, static_cast<uint8_t *>(d_out), c->stream);
             HIP_TRY(c, hipGetLastError());
-            c->fwd_last_kernel = 2;
+            (field ? c->fwd_field_last_kernel : c->fwd_last_kernel) = 2;
             return HG_OK;
         }
     }
-    c->fwd_last_kernel = 1;
+    (field ? c->fwd_field_last_kernel : c->fwd_last_kernel) = 1;
     HG_TRY(ensure(c, c->d_mats, c->mats_cap, (size_t)8 * n));
     HG_TRY(ensure(c, c->d_win32, c->win32_cap, max_px));
     HIP_TRY(c, hipMemcpyAsync(c->d_mats, m, sizeof(double) * 8 * n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));         // caller memory is not retained
     c->geo_frames.clear();                               // the uploaded geometric frame set was overwritten
-    for (int f = 0; f < n; f++)                          // frames run back to back on the stream (one winner buffer, reused in order)
-        launch_fwd_geo(kind, c->d_mats + 8 * (size_t)f, frame_img(mesh_of(c), f), c->W, c->H, fds[f], c->d_win32, static_cast<uint8_t *>(d_out), c->stream);
+    for (int f = 0; f < n; f++) {                        // frames run back to back on the stream (one winner buffer, reused in order)
+        if (field) launch_fwd_geo_field(kind, c->d_mats + 8 * (size_t)f, c->W, c->H, fds[f], c->d_win32, static_cast<uint8_t *>(d_out), c->stream);
+        else launch_fwd_geo(kind, c->d_mats + 8 * (size_t)f, frame_img(mesh_of(c), f), c->W, c->H, fds[f], c->d_win32, static_cast<uint8_t *>(d_out), c->stream);
+    }
     HIP_TRY(c, hipGetLastError());
     return HG_OK;
 }
+
+extern "C" int hg_warp_forward_geometric_batch_device(hg_ctx *c, int kind, const double *m, const hg_geom *geoms, const size_t *offs, int n, void *d_out)
+{
+    return forward_geometric_batch(c, kind, m, geoms, offs, n, d_out, false);
+}
+
+extern "C" int hg_field_forward_geometric_batch_device(hg_ctx *c, int kind, const double *m, const hg_geom *geoms, const size_t *field_offsets, int n, void *d_field)
+{
+    return forward_geometric_batch(c, kind, m, geoms, field_offsets, n, d_field, true);
+}
+
+extern "C" int hg_field_forward_geometric(hg_ctx *c, int kind, const double *m, hg_geom geom, void *out_host)
+{
+    HG_TRY(bind(c));
+    if ((kind != HG_AFFINE && kind != HG_PROJECTIVE) || !m || !out_host) return fail(c, HG_ERR_INVALID, "hg_field_forward_geometric: bad arguments");
+    double m8[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    std::memcpy(m8, m, sizeof(double) * (kind == HG_AFFINE ? 6 : 8));
+    const size_t bytes = (geom.obj_w > 0 && geom.obj_h > 0) ? (size_t)geom.obj_w * geom.obj_h * 4 : 0;
+    HG_TRY(ensure(c, c->d_field_tmp, c->field_tmp_cap, std::max(bytes, (size_t)8)));
+    const size_t zero = 0;
+    HG_TRY(forward_geometric_batch(c, kind, m8, &geom, &zero, 1, c->d_field_tmp, true));
+    if (bytes == 0) return HG_OK;
+    HIP_TRY(c, hipMemcpyAsync(out_host, c->d_field_tmp, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HG_OK;
+}
+
+extern "C" int hg_last_forward_field_kernel(hg_ctx *c) { return c ? c->fwd_field_last_kernel : 0; }
 
 extern "C" int hg_warp_forward_geometric_device(hg_ctx *c, int kind, const double *m, hg_geom geom, void *d_out)
 {
@@ -176,17 +212,60 @@ static int ensure_fwd_rowext(hg_ctx *c, int map_w, int map_h)
     return HG_OK;
 }
 
+// The tile path of a forward piecewise FIELD call, settled before it returns: k_fwd_pw_bins + k_fwd_pw_tiles<FIELD> flag into p.status (n words
+// of the call's own, zeroed by the caller), one read-back, what the flags say about the mesh is learned FIRST (so that a failing redo does not
+// lose the finding), then every flagged frame goes through the scatter path into the field, from the context's current frame set (the one the
+// call has just staged), counted in hg_redone_frames.
+static int settle_forward_field_tiles(hg_ctx *c, const FwdPwTiles &p, int n, int mw, int mh, uint8_t *d_field)
+{
+    launch_fwd_pw_tiles_field(p, n, mw, mh, c->W, c->H, d_field, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    c->fwd_field_last_kernel = 2;
+    std::vector<int32_t> st((size_t)n);
+    HIP_TRY(c, hipMemcpyAsync(st.data(), p.status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    bool overflow = false, unbounded = false;
+    for (int f = 0; f < n; f++) {
+        if (st[f] & FWD_OVERFLOW) overflow = true;
+        if (st[f] & FWD_FALLBACK) unbounded = true;
+    }
+    learn_forward_tiles(c, overflow, unbounded);
+    bool redone = false;
+    for (int f = 0; f < n; f++) {
+        const FrameDesc &fd = c->pw_frames[f];
+        if (st[f] == 0 || fd.obj_w <= 0 || fd.obj_h <= 0) continue;
+        HG_TRY(ensure(c, c->d_win32, c->win32_cap, (size_t)fd.obj_w * fd.obj_h));
+        launch_fwd_pw_field(c->d_fmap, c->d_fwd + (size_t)f * c->n_tris * 6, c->W, c->H, c->min_src_x, c->min_src_y, p.map_w, p.map_h,
+                            fd, c->d_win32, d_field, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        c->pw_redone++;
+        redone = true;
+    }
+    if (redone) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HG_OK;
+}
+
 // _piecewiseAffineWarp :948-972 for n destination point sets on the current mesh (the caller loop `setDestinyPoints(d_f); warp()`
 // when warp() takes the forward path, :421), asynchronous, frames in GPU memory.
-extern "C" int hg_warp_forward_piecewise_batch_device(hg_ctx *c, const float *dst_points, int max_src_x, int max_src_y, const hg_geom *geoms,
-                                                      const size_t *offs, int n, void *d_out)
+// field: the frames' SOURCE FIELDS instead (hg_field_forward_piecewise_batch_device): same limits, same staging, same forward map, same path
+// selection.  Unlike a warp the field call leaves no deferred redo behind: queued runs are settled first by hg_sync (they keep their own
+// results and their own status sets; a deferred error of theirs is returned here, as hg_sync would return it, and the field is then not
+// computed), and the tile path is settled inside the call (settle_forward_field_tiles).  The scatter path has nothing to redo: its launches
+// are queued on the stream like a warp's.
+static int forward_piecewise_batch(hg_ctx *c, const float *dst_points, int max_src_x, int max_src_y, const hg_geom *geoms,
+                                   const size_t *offs, int n, void *d_out, bool field)
 {
     HG_TRY(bind(c));
-    if (!dst_points || !geoms || n <= 0 || !d_out) return fail(c, HG_ERR_INVALID, "hg_warp_forward_piecewise: bad arguments");
+    if (!dst_points || !geoms || n <= 0 || !d_out)
+        return fail(c, HG_ERR_INVALID, field ? "hg_field_forward_piecewise: bad arguments" : "hg_warp_forward_piecewise: bad arguments");
     if (!c->d_img) return fail(c, HG_ERR_STATE, "no source image: call hg_set_image first");
     if (!c->have_mesh) return fail(c, HG_ERR_STATE, "no mesh: call hg_piecewise_set_mesh first");
     const int64_t map_w = (int64_t)max_src_x - c->min_src_x, map_h = (int64_t)max_src_y - c->min_src_y;
     HG_TRY(forward_limits(c, map_w, map_h, "the source-point bounding box"));
+    if (field) {
+        if ((int64_t)c->W * c->H >= ((int64_t)1 << 31)) return fail(c, HG_ERR_INVALID, "the source image has 2^31 pixels or more (an int32 cannot index it)");
+        HG_TRY(hg_sync(c));
+    }
     const size_t n_map = (map_w > 0 && map_h > 0) ? (size_t)map_w * map_h : 0;
     // (A) forward triangle map over the source bbox: _buildTrianglesCorrespondencesMatrix :817-832 == the same
     //     rasteriser on the SOURCE triangles with width maxSrcX-minSrcX and y offset minSrcY.  It depends on the mesh only,
@@ -240,7 +319,10 @@ extern "C" int hg_warp_forward_piecewise_batch_device(hg_ctx *c, const float *ds
             { const size_t cap0 = c->ftile_cnt_cap;
               HG_TRY(ensure(c, c->d_ftile_cnt, c->ftile_cnt_cap, per));
               if (c->ftile_cnt_cap != cap0) HIP_TRY(c, hipMemsetAsync(c->d_ftile_cnt, 0, sizeof(int32_t) * c->ftile_cnt_cap, c->stream)); }
-            if (c->fwd_pending.size() >= kFwdStatusRing - 1 || (size_t)n > c->fwd_status_stride) {
+            if (field) {
+                HG_TRY(ensure(c, c->d_ffield_status, c->ffield_status_cap, (size_t)n));
+                HIP_TRY(c, hipMemsetAsync(c->d_ffield_status, 0, sizeof(int32_t) * n, c->stream));
+            } else if (c->fwd_pending.size() >= kFwdStatusRing - 1 || (size_t)n > c->fwd_status_stride) {
                 HG_TRY(hg_sync(c));                              // ring full, or a larger batch than the ring's sets were laid out for
                 if ((size_t)n > c->fwd_status_stride) {
                     HG_TRY(ensure(c, c->d_fwd_status, c->fwd_status_cap, (size_t)n * kFwdStatusRing));
@@ -248,7 +330,7 @@ extern "C" int hg_warp_forward_piecewise_batch_device(hg_ctx *c, const float *ds
                     HIP_TRY(c, hipMemsetAsync(c->d_fwd_status, 0, sizeof(int32_t) * c->fwd_status_cap, c->stream));
                 }
             }
-            c->fwd_slot = (c->fwd_slot + 1) % (int)kFwdStatusRing;
+            if (!field) c->fwd_slot = (c->fwd_slot + 1) % (int)kFwdStatusRing;
             HG_TRY(ensure(c, c->d_ftile_ent, c->ftile_ent_cap, per * (size_t)c->fwd_pw_cap));
             FwdPwTiles p;
             p.fmap = c->d_fmap; p.fwd = c->d_fwd; p.bbox = c->d_fbbox; p.frames = c->d_pw_frames; p.rowext = c->d_frowext; p.rowoff = c->d_frowoff;
@@ -256,6 +338,10 @@ extern "C" int hg_warp_forward_piecewise_batch_device(hg_ctx *c, const float *ds
             p.host_flag = c->h_flag ? c->h_flag + 1 : nullptr;
             p.T = c->n_tris; p.min_src_x = c->min_src_x; p.min_src_y = c->min_src_y; p.map_w = (int)map_w; p.map_h = (int)map_h;
             p.tsx = tsx; p.tsy = tsy; p.cap = c->fwd_pw_cap;
+            if (field) {
+                p.status = c->d_ffield_status; p.host_flag = nullptr;
+                return settle_forward_field_tiles(c, p, n, mw, mh, static_cast<uint8_t *>(d_out));
+            }
             launch_fwd_pw_tiles(p, n, mw, mh, c->d_img, c->n_imgs, c->img_stride, c->W, c->H, static_cast<uint8_t *>(d_out), c->stream);
             HIP_TRY(c, hipGetLastError());
             { hg_ctx::FwdPending fp;
@@ -265,14 +351,44 @@ extern "C" int hg_warp_forward_piecewise_batch_device(hg_ctx *c, const float *ds
             c->fwd_last_kernel = 2;
             return HG_OK;
         }
-        c->fwd_last_kernel = 1;
+        (field ? c->fwd_field_last_kernel : c->fwd_last_kernel) = 1;
         HG_TRY(settle_output_conflicts(c, d_out, out_extent, 0));      // (this path keeps no pending record: nothing queued may be redone over it later)
         HG_TRY(ensure(c, c->d_win32, c->win32_cap, max_px));
-        for (int f = 0; f < n; f++)
-            launch_fwd_pw(c->d_fmap, c->d_fwd + (size_t)f * c->n_tris * 6, frame_img(mesh_of(c), f), c->W, c->H, c->min_src_x, c->min_src_y, (int)map_w, (int)map_h,
-                          c->pw_frames[f], c->d_win32, static_cast<uint8_t *>(d_out), c->stream);
+        for (int f = 0; f < n; f++) {
+            if (field) launch_fwd_pw_field(c->d_fmap, c->d_fwd + (size_t)f * c->n_tris * 6, c->W, c->H, c->min_src_x, c->min_src_y, (int)map_w, (int)map_h,
+                                           c->pw_frames[f], c->d_win32, static_cast<uint8_t *>(d_out), c->stream);
+            else launch_fwd_pw(c->d_fmap, c->d_fwd + (size_t)f * c->n_tris * 6, frame_img(mesh_of(c), f), c->W, c->H, c->min_src_x, c->min_src_y, (int)map_w, (int)map_h,
+                               c->pw_frames[f], c->d_win32, static_cast<uint8_t *>(d_out), c->stream);
+        }
     }
     HIP_TRY(c, hipGetLastError());
+    return HG_OK;
+}
+
+extern "C" int hg_warp_forward_piecewise_batch_device(hg_ctx *c, const float *dst_points, int max_src_x, int max_src_y, const hg_geom *geoms,
+                                                      const size_t *offs, int n, void *d_out)
+{
+    return forward_piecewise_batch(c, dst_points, max_src_x, max_src_y, geoms, offs, n, d_out, false);
+}
+
+extern "C" int hg_field_forward_piecewise_batch_device(hg_ctx *c, const float *dst_points, int max_src_x, int max_src_y, const hg_geom *geoms,
+                                                       const size_t *field_offsets, int n, void *d_field)
+{
+    return forward_piecewise_batch(c, dst_points, max_src_x, max_src_y, geoms, field_offsets, n, d_field, true);
+}
+
+extern "C" int hg_field_forward_piecewise(hg_ctx *c, const float *dst_points, int max_src_x, int max_src_y, hg_geom geom, void *out_host)
+{
+    HG_TRY(bind(c));
+    if (!out_host) return fail(c, HG_ERR_INVALID, "hg_field_forward_piecewise: bad arguments");
+    if (geom.obj_w <= 0 || geom.obj_h <= 0) return HG_OK;    // (an empty window writes nothing, like hg_warp_forward_piecewise)
+    const size_t bytes = (geom.obj_w > 0 && geom.obj_h > 0) ? (size_t)geom.obj_w * geom.obj_h * 4 : 0;
+    HG_TRY(ensure(c, c->d_field_tmp, c->field_tmp_cap, std::max(bytes, (size_t)8)));
+    const size_t zero = 0;
+    HG_TRY(forward_piecewise_batch(c, dst_points, max_src_x, max_src_y, &geom, &zero, 1, c->d_field_tmp, true));
+    if (bytes == 0) return HG_OK;
+    HIP_TRY(c, hipMemcpyAsync(out_host, c->d_field_tmp, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return HG_OK;
 }
 

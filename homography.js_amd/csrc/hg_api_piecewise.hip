@@ -853,11 +853,7 @@ extern "C" int hg_sync(hg_ctx *c)
             HIP_TRY(c, hipMemsetAsync(c->d_fwd_status, 0, sizeof(int32_t) * c->fwd_status_cap, c->stream));   // (zero between calls)
             HIP_TRY(c, hipStreamSynchronize(c->stream));
         }
-        if (overflow) {
-            if (c->fwd_pw_cap < kFwdPwCapMax) c->fwd_pw_cap = std::min(kFwdPwCapMax, c->fwd_pw_cap * 2);
-            else c->fwd_pw_tiles_disabled = true;
-        }
-        if (unbounded) c->fwd_pw_tiles_disabled = true;      // (a degenerate triangle in this mesh: do not pay for both paths again)
+        learn_forward_tiles(c, overflow, unbounded);
     }
     const int d = c->deferred;
     c->deferred = HG_OK;

@@ -219,6 +219,8 @@ struct hg_ctx {
     int fwd_slot = 0;
     int opt_fwd_tiles = -1;                                    // forward paths: -1 auto, 0 scatter + gather, 1 tiles whenever admissible
     int fwd_last_kernel = 0;                                   // 1 scatter + gather, 2 k_fwd_tiles (hg_last_kernel-style tap for the tests)
+    int fwd_field_last_kernel = 0;                             // the same tap of the forward FIELD calls (hg_last_forward_field_kernel): they leave fwd_last_kernel alone
+    int32_t *d_ffield_status = nullptr; size_t ffield_status_cap = 0;   // status words of ONE forward piecewise field call (read inside the call; not the ring of queued warps)
     int16_t *d_map16 = nullptr; size_t map16_cap = 0;
     uint8_t *d_out_tmp = nullptr; size_t out_tmp_cap = 0;
 
@@ -274,6 +276,18 @@ inline int ensure(hg_ctx *c, T *&p, size_t &cap, size_t need)
     if (e != hipSuccess) return fail(c, HG_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
     p = static_cast<T *>(q); cap = n;
     return HG_OK;
+}
+
+// What a forward piecewise tile run's flags say about the MESH, whoever ran it (hg_sync for queued warps, a forward field call for itself): an
+// overfull tile list doubles the capacity up to kFwdPwCapMax, then switches the tile path off; a triangle the bins kernel could not bound
+// switches it off at once (until hg_piecewise_set_mesh or option "fwd_tiles" re-arms it).
+inline void learn_forward_tiles(hg_ctx *c, bool overflow, bool unbounded)
+{
+    if (overflow) {
+        if (c->fwd_pw_cap < kFwdPwCapMax) c->fwd_pw_cap = std::min(kFwdPwCapMax, c->fwd_pw_cap * 2);
+        else c->fwd_pw_tiles_disabled = true;
+    }
+    if (unbounded) c->fwd_pw_tiles_disabled = true;          // (a degenerate triangle in this mesh: do not pay for both paths again)
 }
 
 inline int bind(hg_ctx *c)

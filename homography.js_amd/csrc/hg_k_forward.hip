@@ -85,6 +85,25 @@ __global__ __launch_bounds__(256) void k_fwd_gather(const int32_t *__restrict__ 
     reinterpret_cast<uint32_t *>(out + fd.out_off)[i] = px;
 }
 
+// The scatter path's field tail: winner ranks -> flat source indices (geometric: the rank is the index; piecewise: map cell -> :960), -1 where
+// nobody writes or the winner reads outside the source array.  `field` + fd.out_off: the frame's int32 field.
+__global__ __launch_bounds__(256) void k_fwd_win_field(const int32_t *__restrict__ win, int W, int H, int piecewise, int min_src_x, int min_src_y, int map_w,
+                                                       FrameDesc fd, uint8_t *__restrict__ field)
+{
+    const int64_t n = (int64_t)fd.obj_w * fd.obj_h;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int w = win[i];
+    int v = -1;
+    if (w >= 0) {
+        int64_t sidx;
+        if (piecewise) { const int my = w / map_w, mx = w - my * map_w; sidx = (int64_t)(my + min_src_y) * W + (mx + min_src_x); }   // :960
+        else sidx = w;
+        if (sidx >= 0 && sidx < (int64_t)W * H) v = (int)sidx;
+    }
+    __builtin_nontemporal_store(v, reinterpret_cast<int *>(field + fd.out_off) + i);
+}
+
 // ------------------------------------------------------------------------------------------------ k_fwd_tiles
 // The forward warps without global atomics and without the winner buffer: one workgroup per 64 x 64 tile of OUTPUT pixels
 // gathers the source pixels that land in its tile.  The candidates are enumerated conservatively -- per source row the x
@@ -97,7 +116,9 @@ __global__ __launch_bounds__(256) void k_fwd_gather(const int32_t *__restrict__ 
 // reference does not check x): tiles near the left / right edge also enumerate those aliased rectangles (kFwdWrap columns;
 // the host only takes this path when no source pixel can land further out).  Then each cell copies its winner's pixel.
 // Traffic per frame: source once + output once (scatter path: + 4 x the winner buffer).
-template <int KIND, bool ONE>      // ONE: a single frame whose parameters travel in the kernel arguments (no upload, no sync)
+// FIELD: the forward SOURCE FIELD instead of the picture -- each cell stores its winner's flat source index (-1: nobody writes), an int32
+// at the frame's field offset (fd.out_off), and no pixel is loaded (img is not read).
+template <int KIND, bool ONE, bool FIELD = false>      // ONE: a single frame whose parameters travel in the kernel arguments (no upload, no sync)
 __global__ __launch_bounds__(256) void k_fwd_tiles(FwdBatch batch, const uint8_t *__restrict__ img, int n_imgs, uint64_t img_stride, int W, int H, uint8_t *__restrict__ out)
 {
     __shared__ int s_win[kFwdTileW * kFwdTileH];
@@ -231,7 +252,8 @@ __global__ __launch_bounds__(256) void k_fwd_tiles(FwdBatch batch, const uint8_t
     for (int cy = tid >> 6; cy < ty1 - ty0; cy += 4) {
         if (tx0 + cx >= tx1) continue;
         const int w = s_win[cy * kFwdTileW + cx];
-        o32[(size_t)(ty0 + cy) * fd.obj_w + tx0 + cx] = w >= 0 ? img32[w] : 0u;
+        if (FIELD) __builtin_nontemporal_store((w >= 0 && (int64_t)w < (int64_t)W * H) ? w : -1, reinterpret_cast<int *>(o32) + (size_t)(ty0 + cy) * fd.obj_w + tx0 + cx);
+        else o32[(size_t)(ty0 + cy) * fd.obj_w + tx0 + cx] = w >= 0 ? img32[w] : 0u;
     }
 }
 
@@ -377,6 +399,9 @@ constexpr int kPwSegCap = 1024;            // segments per round (16 384 candida
 constexpr int kPwUnroll = 2;               // candidates in flight per lane (4: 70 VGPRs, 7 waves per SIMD; 2 with the cap below: 8)
 static_assert(kFwdPwCapMax <= kPwT && kPwT == 512, "row records carry the row's slot in 9 bits");
 
+// FIELD: the forward source field -- the tail decodes each winner key to the flat source index (my + minSrcY) W + mx + minSrcX and stores it
+// (-1: no writer, or an index outside [0, W H)) as an int32 at the frame's field offset; no pixel is loaded.
+template <bool FIELD>
 __global__ __launch_bounds__(kPwT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_fwd_pw_tiles(FwdPwTiles p, const uint8_t *__restrict__ img, int n_imgs, uint64_t img_stride, int W, int H, uint8_t *__restrict__ out)
 {
     __shared__ uint32_t s_win[kFwdTileW * kFwdTileH];                  // 0 = no writer, else ((map row << 16) | map column) + 1
@@ -525,6 +550,20 @@ __global__ __launch_bounds__(kPwT) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     uint32_t *__restrict__ o32 = reinterpret_cast<uint32_t *>(out + fd.out_off);
     const int cxl = tid & (kFwdTileW - 1);
     if (tx0 + cxl >= tx1) return;
+    if (FIELD) {
+        int *__restrict__ fo = reinterpret_cast<int *>(o32);
+        for (int cyl = tid / kFwdTileW; cyl < ty1 - ty0; cyl += kPwT / kFwdTileW) {
+            const uint32_t w = s_win[cyl * kFwdTileW + cxl];
+            int v = -1;
+            if (w != 0u) {
+                const int my = (int)((w - 1u) >> 16), mx = (int)((w - 1u) & 0xffffu);
+                const int64_t sidx = (int64_t)(my + p.min_src_y) * W + (mx + p.min_src_x);                // :960
+                if (sidx >= 0 && sidx < (int64_t)W * H) v = (int)sidx;
+            }
+            __builtin_nontemporal_store(v, fo + (size_t)(ty0 + cyl) * fd.obj_w + tx0 + cxl);
+        }
+        return;
+    }
     constexpr int kRowsPerStep = 4, kRowStride = kPwT / kFwdTileW;     // source reads of 4 tile rows in flight per lane
 #pragma unroll 1
     for (int cy0 = tid / kFwdTileW; cy0 < ty1 - ty0; cy0 += kRowStride * kRowsPerStep) {
@@ -593,7 +632,52 @@ void launch_fwd_pw_tiles(const FwdPwTiles &p, int n_frames, int max_w, int max_h
 {
     if (n_frames <= 0 || max_w <= 0 || max_h <= 0) return;
     if (p.T > 0) hipLaunchKernelGGL(k_fwd_pw_bins, dim3((p.T + 3) / 4, n_frames), dim3(64, 4), 0, stream, p);
-    hipLaunchKernelGGL(k_fwd_pw_tiles, dim3(p.tsx, p.tsy, n_frames), dim3(kPwT), 0, stream, p, img, n_imgs, img_stride, W, H, out);
+    hipLaunchKernelGGL(k_fwd_pw_tiles<false>, dim3(p.tsx, p.tsy, n_frames), dim3(kPwT), 0, stream, p, img, n_imgs, img_stride, W, H, out);
+}
+
+// ---- the forward source fields: the same launches with the field tails (frame records carry FIELD offsets in out_off)
+void launch_fwd_tiles_field(int kind, const FwdBatch &batch, int n_frames, int max_w, int max_h, int W, int H, uint8_t *field, hipStream_t stream)
+{
+    if (n_frames <= 0 || max_w <= 0 || max_h <= 0) return;
+    const dim3 grid((max_w + kFwdTileW - 1) / kFwdTileW, (max_h + kFwdTileH - 1) / kFwdTileH, n_frames);
+    const uint8_t *none = nullptr;
+    if (batch.params) {
+        if (kind == 0) hipLaunchKernelGGL((k_fwd_tiles<0, false, true>), grid, dim3(256), 0, stream, batch, none, 1, (uint64_t)0, W, H, field);
+        else           hipLaunchKernelGGL((k_fwd_tiles<1, false, true>), grid, dim3(256), 0, stream, batch, none, 1, (uint64_t)0, W, H, field);
+    } else {
+        if (kind == 0) hipLaunchKernelGGL((k_fwd_tiles<0, true, true>), grid, dim3(256), 0, stream, batch, none, 1, (uint64_t)0, W, H, field);
+        else           hipLaunchKernelGGL((k_fwd_tiles<1, true, true>), grid, dim3(256), 0, stream, batch, none, 1, (uint64_t)0, W, H, field);
+    }
+}
+
+void launch_fwd_pw_tiles_field(const FwdPwTiles &p, int n_frames, int max_w, int max_h, int W, int H, uint8_t *field, hipStream_t stream)
+{
+    if (n_frames <= 0 || max_w <= 0 || max_h <= 0) return;
+    const uint8_t *none = nullptr;
+    if (p.T > 0) hipLaunchKernelGGL(k_fwd_pw_bins, dim3((p.T + 3) / 4, n_frames), dim3(64, 4), 0, stream, p);
+    hipLaunchKernelGGL(k_fwd_pw_tiles<true>, dim3(p.tsx, p.tsy, n_frames), dim3(kPwT), 0, stream, p, none, 1, (uint64_t)0, W, H, field);
+}
+
+void launch_fwd_geo_field(int kind, const double *d_mat, int W, int H, const FrameDesc &fd, int32_t *win, uint8_t *field, hipStream_t stream)
+{
+    const int64_t n = (fd.obj_w > 0 && fd.obj_h > 0) ? (int64_t)fd.obj_w * fd.obj_h : 0;
+    if (n == 0) return;
+    launch_fill_i32(win, (size_t)n, -1, stream);
+    dim3 grid((W + 255) / 256, H);
+    if (kind == 0) hipLaunchKernelGGL(k_fwd_scatter_geo<0>, grid, dim3(256), 0, stream, d_mat, W, H, fd, win);
+    else           hipLaunchKernelGGL(k_fwd_scatter_geo<1>, grid, dim3(256), 0, stream, d_mat, W, H, fd, win);
+    hipLaunchKernelGGL(k_fwd_win_field, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, win, W, H, 0, 0, 0, 1, fd, field);
+}
+
+void launch_fwd_pw_field(const int32_t *fmap, const float *fwd, int W, int H, int min_src_x, int min_src_y, int map_w, int map_h,
+                         const FrameDesc &fd, int32_t *win, uint8_t *field, hipStream_t stream)
+{
+    const int64_t n = (fd.obj_w > 0 && fd.obj_h > 0) ? (int64_t)fd.obj_w * fd.obj_h : 0;
+    if (n == 0) return;
+    launch_fill_i32(win, (size_t)n, -1, stream);
+    if (map_w > 0 && map_h > 0)
+        hipLaunchKernelGGL(k_fwd_scatter_pw, dim3((map_w + 255) / 256, map_h), dim3(256), 0, stream, fmap, fwd, min_src_x, min_src_y, map_w, map_h, fd, win);
+    hipLaunchKernelGGL(k_fwd_win_field, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, win, W, H, 1, min_src_x, min_src_y, map_w > 0 ? map_w : 1, fd, field);
 }
 
 void launch_fwd_pw(const int32_t *fmap, const float *fwd, const uint8_t *img, int W, int H, int min_src_x, int min_src_y, int map_w, int map_h,

@@ -228,5 +228,14 @@ void launch_fwd_pw_tiles(const FwdPwTiles &p, int n_frames, int max_w, int max_h
 void launch_fwd_geo(int kind, const double *d_mat, const uint8_t *img, int W, int H, const FrameDesc &fd, int32_t *win, uint8_t *out, hipStream_t stream);
 void launch_fwd_pw(const int32_t *fmap, const float *fwd, const uint8_t *img, int W, int H, int min_src_x, int min_src_y, int map_w, int map_h,
                    const FrameDesc &fd, int32_t *win, uint8_t *out, hipStream_t stream);
+// The forward SOURCE FIELD (include/hgwarp.h, hg_field_forward_*): one int32 per output pixel, the flat source index of the pixel the forward loop's
+// last writer reads, -1 where nobody writes or that read is outside the source array.  The same launches as above with field tails
+// (k_fwd_tiles<.., FIELD>, k_fwd_pw_tiles<FIELD>; scatter path: k_fwd_win_field instead of k_fwd_gather); out_off of every frame record is the
+// byte offset of the frame's FIELD.  Only the source's size is read, never its pixels.
+void launch_fwd_tiles_field(int kind, const FwdBatch &batch, int n_frames, int max_w, int max_h, int W, int H, uint8_t *field, hipStream_t stream);
+void launch_fwd_pw_tiles_field(const FwdPwTiles &p, int n_frames, int max_w, int max_h, int W, int H, uint8_t *field, hipStream_t stream);
+void launch_fwd_geo_field(int kind, const double *d_mat, int W, int H, const FrameDesc &fd, int32_t *win, uint8_t *field, hipStream_t stream);
+void launch_fwd_pw_field(const int32_t *fmap, const float *fwd, int W, int H, int min_src_x, int min_src_y, int map_w, int map_h,
+                         const FrameDesc &fd, int32_t *win, uint8_t *field, hipStream_t stream);
 
 } // namespace hg

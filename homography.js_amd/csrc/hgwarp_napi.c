@@ -785,6 +785,41 @@ static napi_value fn_field_inverse_piecewise(napi_env env, napi_callback_info in
     return r;
 }
 
+/* fieldForwardGeometric(handle, kind, forwardMatrix, xOff, yOff, objW, objH) / fieldForwardPiecewise(handle, dstPoints, maxSrcX, maxSrcY, xOff,
+ * yOff, objW, objH): the source field of the FORWARD warp (hg_field_forward_*): an Int32Array of objW * objH flat source pixel indices, -1
+ * where the forward loop leaves a hole or its last writer reads outside the source. */
+static napi_value fn_field_forward_geometric(napi_env env, napi_callback_info info)
+{
+    napi_value a[7];
+    if (!get_args(env, info, 7, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    int kind; size_t n; hg_geom g;
+    if (!get_i32(env, a[1], &kind)) return NULL;
+    double *m = (double *)get_typed(env, a[2], napi_float64_array, &n, "matrix"); if (!m) return NULL;
+    if (n < (size_t)(kind == HG_AFFINE ? 6 : 8)) return throw_str(env, "hgwarp: matrix too short");
+    if (!get_geom(env, a + 3, &g)) return NULL;
+    const size_t px = (g.obj_w > 0 && g.obj_h > 0) ? (size_t)g.obj_w * g.obj_h : 0;
+    void *out; napi_value r = make_field(env, HG_FIELD_INDEX, px, &out); if (!r) return NULL;
+    if (px) HG_CALL(h->ctx, "hg_field_forward_geometric", hg_field_forward_geometric(h->ctx, kind, m, g, out));
+    return r;
+}
+
+static napi_value fn_field_forward_piecewise(napi_env env, napi_callback_info info)
+{
+    napi_value a[8];
+    if (!get_args(env, info, 8, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    size_t n; int mx, my; hg_geom g;
+    float *dst = (float *)get_typed(env, a[1], napi_float32_array, &n, "dstPoints"); if (!dst) return NULL;
+    if (!get_i32(env, a[2], &mx) || !get_i32(env, a[3], &my)) return NULL;
+    if (!get_geom(env, a + 4, &g)) return NULL;
+    if (h->n_pts == 0 || n < 2 * h->n_pts) return throw_str(env, "hgwarp: dstPoints must hold one x,y pair per mesh point (piecewiseSetMesh first)");
+    const size_t px = (g.obj_w > 0 && g.obj_h > 0) ? (size_t)g.obj_w * g.obj_h : 0;
+    void *out; napi_value r = make_field(env, HG_FIELD_INDEX, px, &out); if (!r) return NULL;
+    if (px) HG_CALL(h->ctx, "hg_field_forward_piecewise", hg_field_forward_piecewise(h->ctx, dst, mx, my, g, out));
+    return r;
+}
+
 /* redoneFrames(ctx): frames the fused kernels flagged and hg_sync redid through the map so far (hg_redone_frames; tests) */
 static napi_value fn_redone_frames(napi_env env, napi_callback_info info)
 {
@@ -1350,6 +1385,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "warpForwardPiecewiseBatch", fn_warp_forward_piecewise_batch }, { "warpForwardGeometricBatch", fn_warp_forward_geometric_batch },
         { "releaseBatch", fn_release_batch }, { "pinnedBuffer", fn_pinned_buffer },
         { "fieldInverseGeometric", fn_field_inverse_geometric }, { "fieldInversePiecewise", fn_field_inverse_piecewise },
+        { "fieldForwardGeometric", fn_field_forward_geometric }, { "fieldForwardPiecewise", fn_field_forward_piecewise },
         { "solveAffineTriangles", fn_solve_affine_triangles }, { "warpInversePiecewiseState", fn_warp_inverse_piecewise_state },
         { "warpForwardPiecewiseState", fn_warp_forward_piecewise_state },
         { "release", fn_release }, { "setPinnedLimit", fn_set_pinned_limit }, { "poolStats", fn_pool_stats }, { "redoneFrames", fn_redone_frames }, { "setSampling", fn_set_sampling }, { "multiSetSampling", fn_multi_set_sampling }, { "_poolTestFrames", fn_pool_test_frames }, { "poolPressure", fn_pool_pressure }, { "poolCollected", fn_pool_collected },

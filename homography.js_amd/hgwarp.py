@@ -47,6 +47,8 @@ EXPORTS = [
     "hg_set_sampling", "hg_get_sampling", "hg_multi_set_sampling",
     "hg_pack_field_offsets", "hg_field_inverse_geometric", "hg_field_inverse_geometric_device", "hg_field_inverse_geometric_frames_device",
     "hg_field_inverse_piecewise", "hg_field_inverse_piecewise_frames_device", "hg_remap_index_device", "hg_remap_bilinear_f32_device",
+    "hg_field_forward_geometric", "hg_field_forward_geometric_batch_device", "hg_field_forward_piecewise", "hg_field_forward_piecewise_batch_device",
+    "hg_last_forward_field_kernel",
 ]
 
 
@@ -137,6 +139,11 @@ def lib():
         "hg_field_inverse_geometric": (i, [vp, i, f64p, Geom, i, vp]), "hg_field_inverse_geometric_device": (i, [vp, i, f64p, Geom, i, vp]),
         "hg_field_inverse_geometric_frames_device": (i, [vp, i, C.POINTER(sz), vp]),
         "hg_field_inverse_piecewise": (i, [vp, i, vp]), "hg_field_inverse_piecewise_frames_device": (i, [vp, i, C.POINTER(sz), vp]),
+        "hg_field_forward_geometric": (i, [vp, i, f64p, Geom, vp]),
+        "hg_field_forward_geometric_batch_device": (i, [vp, i, f64p, C.POINTER(Geom), C.POINTER(sz), i, vp]),
+        "hg_field_forward_piecewise": (i, [vp, f32p, i, i, Geom, vp]),
+        "hg_field_forward_piecewise_batch_device": (i, [vp, f32p, i, i, C.POINTER(Geom), C.POINTER(sz), i, vp]),
+        "hg_last_forward_field_kernel": (i, [vp]),
         "hg_remap_index_device": (i, [vp, vp, sz, vp, sz, i, vp]),
         "hg_remap_bilinear_f32_device": (i, [vp, vp, sz, vp, i, i, i, vp]),
         "hg_warp_inverse_piecewise_state": (i, [vp, f32p, i, C.POINTER(TriMapDef), i, i, Geom, u8p]),
@@ -567,6 +574,42 @@ class Context:
         """The fields of the staged piecewise frame set (settled inside the call); offsets=None: packed as pack_field_offsets does."""
         offs = (C.c_size_t * len(offsets))(*offsets) if offsets is not None else None
         self._c(lib().hg_field_inverse_piecewise_frames_device(self._h, int(fmt), offs, C.c_void_p(int(d_field))))
+
+    # the source field of the FORWARD warps: (h, w) int32, the flat source index the last writer of each output pixel reads, -1 where none
+    def field_forward_geometric(self, kind, m, geom):
+        a, p = _f64(m)
+        assert a.size >= (6 if int(kind) == 0 else 8)
+        g = Geom(*[int(v) for v in geom])
+        out = _field_array(FIELD_INDEX, g.obj_h, g.obj_w)
+        self._c(lib().hg_field_forward_geometric(self._h, int(kind), p, g, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def field_forward_geometric_batch_device(self, kind, mats, geoms, offsets, d_field):
+        """offsets=None: packed as pack_field_offsets(geoms, FIELD_INDEX) does (asynchronous)."""
+        m, p = _f64(mats)
+        assert m.size == 8 * len(geoms)
+        offs = (C.c_size_t * len(geoms))(*offsets) if offsets is not None else None
+        self._c(lib().hg_field_forward_geometric_batch_device(self._h, int(kind), p, _geoms(geoms), offs, len(geoms), C.c_void_p(int(d_field))))
+
+    def field_forward_piecewise(self, dst_pts, max_src_x, max_src_y, geom):
+        d, dp = _f32(dst_pts)
+        assert d.size == 2 * self._n_pts, "one x,y pair per mesh point"
+        g = Geom(*[int(v) for v in geom])
+        out = _field_array(FIELD_INDEX, g.obj_h, g.obj_w)
+        self._c(lib().hg_field_forward_piecewise(self._h, dp, int(max_src_x), int(max_src_y), g, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def field_forward_piecewise_batch_device(self, dst_pts, max_src_x, max_src_y, geoms, offsets, d_field):
+        """No deferred redo: queued runs are settled first, frames the tile kernels flag are redone before it returns; on the scatter path the
+        launches are asynchronous on the stream.  offsets=None: packed."""
+        d, dp = _f32(dst_pts)
+        assert d.size == 2 * self._n_pts * len(geoms), "frames x mesh points x,y pairs"
+        offs = (C.c_size_t * len(geoms))(*offsets) if offsets is not None else None
+        self._c(lib().hg_field_forward_piecewise_batch_device(self._h, dp, int(max_src_x), int(max_src_y), _geoms(geoms), offs, len(geoms), C.c_void_p(int(d_field))))
+
+    def last_forward_field_kernel(self):
+        """0 = no forward field yet, 1 = scatter + winner buffer, 2 = the tile-binned kernels (include/hgwarp.h)."""
+        return lib().hg_last_forward_field_kernel(self._h)
 
     def remap_index_device(self, d_field, n_px, d_src, n_src_px, pixel_bytes, d_out):
         """out[i] = src[field[i]] where 0 <= field[i] < n_src_px, else zeros; pixels of 1, 2, 4, 8 or 16 bytes (asynchronous)."""

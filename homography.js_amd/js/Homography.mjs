@@ -258,17 +258,14 @@ class Homography {
             throw ("warp() must receive an image if it was not setted before through `setImage(img)` or  `setSourcePoints(points, img)`");
         }
         if (asHTMLPromise) throw ("hgwarp: asHTMLPromise needs a browser DOM; use the returned ImageData-shaped object");
-        if (this._sampling === 'bilinear') applyAlwaysInverse = true;                                  // (the forward loops have nothing to blend)
+        const forward = this._dispatchesForward(applyAlwaysInverse);
         let out;
         switch (this.transform) {
             case 'piecewiseaffine':
-                out = (applyAlwaysInverse || (this._objectiveWidth > this._width || this._objectiveHeight > this._height ||
-                       this._objectiveWidth * 1.2 < this._width || this._objectiveHeight * 1.2 < this._height))
-                    ? this._inversePiecewise() : this._forwardPiecewise();
+                out = forward ? this._forwardPiecewise() : this._inversePiecewise();
                 break;
             case 'affine':
-                out = (applyAlwaysInverse || (this._objectiveWidth !== this._width || this._objectiveHeight !== this._height))
-                    ? this._inverseGeometric() : this._forwardGeometric();
+                out = forward ? this._forwardGeometric() : this._inverseGeometric();
                 break;
             case 'projective':
                 out = this._inverseGeometric();
@@ -279,24 +276,67 @@ class Homography {
         return makeImageData(new Uint8ClampedArray(4), 1, 1);                                           // :440
     }
 
+    /** Does warp(null, false, applyAlwaysInverse) take a forward (scatter) loop for the current state?  (:421-422, :426-427, :431; bilinear
+     *  sampling always takes the inverse loop: the forward loops have nothing to blend.) */
+    _dispatchesForward(applyAlwaysInverse = false) {
+        if (applyAlwaysInverse || this._sampling === 'bilinear') return false;
+        if (this.transform === 'piecewiseaffine')
+            return !(this._objectiveWidth > this._width || this._objectiveHeight > this._height ||
+                     this._objectiveWidth * 1.2 < this._width || this._objectiveHeight * 1.2 < this._height);
+        if (this.transform === 'affine') return !(this._objectiveWidth !== this._width || this._objectiveHeight !== this._height);
+        return false;
+    }
+
     /**
      * The SOURCE FIELD of the inverse loop for the instance's current transform and points, over the window warp() would use (not part of
      * the reference; include/hgwarp.h, HG_FIELD_*): for every output pixel, which source pixel `warp(null, false, true)` copies.
      *   'index'   Int32Array, one flat pixel index per output pixel, -1 where the loop writes nothing or reads outside the array:
      *             out32[i] = data[i] >= 0 ? image32[data[i]] : 0 is warp(null, false, true).data, byte for byte;
      *   'coords'  Float32Array, (sx, sy) per output pixel (the loop's f64 coordinate rounded once), NaN where the loop's test fails.
-     * Always the inverse loop, whatever warp() would dispatch to; independent of the sampling mode; records neither a map nor a path
-     * (the reference-visible state stays that of the last warp).  Masks, depth maps, labels go through the picture's geometry by a gather over `data`.
-     * Returns { data, width, height }.  Throws a string for an unknown format, and for the reference-state quirks (matrices of an older
-     * point set after setSourcePoints / setTriangles without a setDestinyPoints): call setDestinyPoints first.
+     * options.loop picks the loop whose field this is:
+     *   'inverse' (default)  always the inverse loop, whatever warp() would dispatch to;
+     *   'warp'               the loop warp() would dispatch to for the current state (the same tests as warp(), bilinear sampling -> inverse
+     *                        included): gathered over the image, `data` IS warp().data -- for a same-size piecewise or affine frame that
+     *                        is the forward (scatter) loop, holes, overwritten pixels and aliased columns included;
+     *   'forward'            always the forward loop (_piecewiseAffineWarp / _geometricWarp with the forward matrix).
+     * A forward field is 'index' only (the forward loops copy whole pixels from integer positions: (i % width, i / width) of the source is
+     * the coordinate): data[p] is the flat source index the LAST writer of output pixel p reads, -1 where nobody writes or that read lies
+     * outside the image.  The reference-state forms of the forward loop (a stale map or stale matrices, as warp() would replay them) have
+     * no field.
+     * Independent of the sampling mode otherwise; records neither a map nor a path (the reference-visible state stays that of the last
+     * warp).  Masks, depth maps, labels go through the picture's geometry by a gather over `data`.
+     * Returns { data, width, height }.  Throws a string for an unknown format or loop, for 'coords' with a forward loop, and for the
+     * reference-state quirks unless `repairStaleMap` is set (matrices of an older point set after setSourcePoints / setTriangles without a
+     * setDestinyPoints; for a forward piecewise loop also a map field that does not hold the forward map of the current mesh, e.g. after an
+     * inverse warp): call setDestinyPoints / setSourcePoints first.
      */
-    sourceField(format = 'index') {
+    sourceField(format = 'index', options = {}) {
         if (format !== 'index' && format !== 'coords') throw ("sourceField: format must be 'index' or 'coords'");
+        const loop = options === null || options === undefined || options.loop === undefined ? 'inverse' : options.loop;
+        if (loop !== 'inverse' && loop !== 'warp' && loop !== 'forward') throw ("sourceField: options.loop must be 'inverse', 'warp' or 'forward'");
         if (this._image === null) throw ("sourceField() needs an image: call `setImage(img)` or `setSourcePoints(points, img)` first");
         const fmt = format === 'index' ? 0 : 1;
         const [xo, yo, ow, oh] = this._window();
         const empty = () => ({ data: fmt === 0 ? new Int32Array(0) : new Float32Array(0), width: 0, height: 0 });
         let data;
+        if (loop === 'forward' || (loop === 'warp' && this._dispatchesForward())) {
+            if (fmt !== 0) throw ("sourceField: a forward loop has an 'index' field only (it copies whole pixels from integer positions)");
+            if (this.transform === 'piecewiseaffine') {
+                if (!(this.repairStaleMap || (this._mapIsCurrentForward() && this._matricesAreCurrent())))
+                    throw ("sourceField: the forward loop would read a stale map or matrices of an older point set (call setSourcePoints / setDestinyPoints first)");
+                if (!(ow * oh >= 1)) return empty();
+                checkedMapLength(ow * oh);
+                this._uploadImage();
+                this._uploadMesh();
+                data = this._native.fieldForwardPiecewise(this._ctx, asF32(this._dstPoints), this._maxSrcX, this._maxSrcY, xo, yo, ow, oh);
+            } else {
+                if (!(ow * oh >= 1)) return empty();
+                checkedMapLength(ow * oh);
+                this._uploadImage();
+                data = this._native.fieldForwardGeometric(this._ctx, this.transform === 'affine' ? AFFINE : PROJECTIVE, Float64Array.from(this._transformMatrix), xo, yo, ow, oh);
+            }
+            return { data, width: ow, height: oh };
+        }
         if (this.transform === 'piecewiseaffine') {
             if (!(this.repairStaleMap || this._matricesAreCurrent()))
                 throw ("sourceField: the piecewise matrices belong to an older point set (call setDestinyPoints first)");

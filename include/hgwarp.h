@@ -33,7 +33,8 @@
 extern "C" {
 #endif
 
-#define HG_VERSION 100          /* 0.1.0 (sampling modes are detected by the presence of hg_set_sampling, source fields by that of hg_field_inverse_geometric) */
+#define HG_VERSION 100          /* 0.1.0 (sampling modes are detected by the presence of hg_set_sampling, source fields by that of hg_field_inverse_geometric,
+                                   the forward source fields by that of hg_field_forward_geometric) */
 
 enum {
     HG_OK = 0,
@@ -311,6 +312,40 @@ int hg_remap_index_device(hg_ctx *ctx, const void *d_field, size_t n_px, const v
  *     v = (p00*(1-fx) + p01*fx)*(1-fy) + (p10*(1-fx) + p11*fx)*fy,
  * stored as it is (no rounding, no clamping): the operation order of the bilinear sampling mode, so a float32 model matches bit for bit. */
 int hg_remap_bilinear_f32_device(hg_ctx *ctx, const void *d_coords, size_t n_px, const float *d_src, int W, int H, int channels, float *d_out);
+/* The source field of the FORWARD warps (next section): what hg_warp_forward_* would paint, as geometry.  HG_FIELD_INDEX only, hence no
+ * format argument: the forward loops copy whole pixels from integer positions, (s % W, s / W) IS the coordinate.  One int32 per output pixel
+ * p, row-major obj_w x obj_h: let w be the LAST writer, in the loop's raster order (:919-930 over y < H, x < W; :955-969 over the cells of
+ * the source-point bounding box whose forward-map id is > -1), among the source pixels whose flat destination index -- formed as the
+ * reference forms it (:924-926 / :962-964: Math.round, `<< 2` on ToInt32, u outside [0, objW) aliasing into the neighbouring rows) -- equals
+ * 4p and passes the typed-array bound, and s the flat source pixel index that writer reads (geometric: y W + x; piecewise :960:
+ * (cell_y + minSrcY) W + cell_x + minSrcX, which may wrap into a neighbouring source row or leave the array).  field[p] = s if a writer
+ * exists and 0 <= s < W H, else -1 (nobody writes, or the last writer reads undefined -> 0, which still overwrites earlier writers).  Hence
+ *     out32[p] = field[p] >= 0 ? img32[field[p]] : 0
+ * IS the forward warp, byte for byte, holes and overwritten pixels included; hg_remap_index_device sends any other plane the same way.
+ * With hg_set_images_device the index of frame f is relative to image f % n_images; only the source's SIZE is read.
+ * Layout as above (field_offsets NULL: packed as hg_pack_field_offsets(.., HG_FIELD_INDEX, ..) packs; multiples of 4, HG_ERR_INVALID
+ * otherwise; bytes between frames are never written, empty frames write nothing).  Limits and refusals are those of the forward warps
+ * (HG_ERR_STATE: no image / no mesh; HG_ERR_INVALID: NULL pointers, unknown kind, a source or source box of 2^31 pixels or more or taller than
+ * 65535 rows).  The PATH is chosen exactly as the corresponding forward warp chooses it (option "fwd_tiles", hg_forward_tiles_admissible,
+ * the piecewise size / density test) and reported by hg_last_forward_field_kernel: 0 none yet, 1 scatter + winner buffer, 2 the tile-binned
+ * kernels.  hg_last_forward_kernel, hg_last_piecewise_*, hg_last_geometric_kernel and the sampling mode stay as they were.  Staged frame sets
+ * and the forward triangle map are treated as the corresponding forward warp entry point treats them.
+ * Geometric: `m` is the FORWARD matrix (6 / 8 doubles; batch: n x 8).  The host form is synchronous; the batch form is asynchronous on the
+ * ctx stream after settling queued runs (nothing of it is ever redone).
+ * Piecewise: leaves NO DEFERRED REDO, like hg_field_inverse_piecewise_frames_device: queued warp runs are settled first, as by hg_sync, and
+ * keep their own results -- a deferred error of such an earlier run surfaces HERE, as it would from hg_sync, and the field is then not
+ * computed; on the tile path the call is settled before it returns, on the scatter path (nothing can be redone) its launches are
+ * asynchronous on the ctx stream like a warp's; the tile kernels flag into a status set of the call's own; a frame they flag (a triangle they cannot bound, an overfull tile
+ * list) is redone through the scatter path into the field before the call returns and counted in hg_redone_frames.  What such a flag says
+ * about the MESH is learned exactly as hg_sync learns it from a warp (capacity 64 -> 128 -> 256 after an overflow; the tile path off for
+ * the mesh after an unboundable triangle or an overflow at 256), so warps and field calls find each other's findings. */
+int hg_field_forward_geometric(hg_ctx *ctx, int kind, const double *m, hg_geom geom, void *out_host);
+int hg_field_forward_geometric_batch_device(hg_ctx *ctx, int kind, const double *m, const hg_geom *geoms, const size_t *field_offsets,
+                                            int n_frames, void *d_field);
+int hg_field_forward_piecewise(hg_ctx *ctx, const float *dst_points, int max_src_x, int max_src_y, hg_geom geom, void *out_host);
+int hg_field_forward_piecewise_batch_device(hg_ctx *ctx, const float *dst_points, int max_src_x, int max_src_y, const hg_geom *geoms,
+                                            const size_t *field_offsets, int n_frames, void *d_field);
+int hg_last_forward_field_kernel(hg_ctx *ctx);
 
 /* ------------------------------------------------------------------------------------------------ forward (scatter) paths
  * What warp() dispatches to when the output is not larger than the input (:421, :426).  `m` is the FORWARD matrix
