@@ -10,28 +10,12 @@ from hgtest import edges as E
 from hgtest import hip
 from hgtest import oracle as O
 from hgtest import workloads as WL
+from hgtest.pw_kernels import FRAME_SET_KERNELS, PW_KERNELS, SELF_LABELS
 
 pytestmark = pytest.mark.gpu
 
 HG = hip.load()
 NEAR, BIL = HG.SAMPLE_NEAREST, HG.SAMPLE_BILINEAR
-
-# Piecewise instantiations (include/hgwarp.h variant codes): label -> (options, variant with bounds on the high dwords, variant with the
-# fp64 bounds).  The ten of test_gpu_parity.DEFAULT_POLICY; the fp64 form of the list-reading k_pw_rows is its one-window instantiation.
-PW_KERNELS = {
-    "rows4": ({"self_spans": 0, "patch": 0, "tile": 0, "phase": 4, "compact": 0, "min_row_groups": 0}, 104010, 101000),
-    "rows_s80": ({"self_spans": 0, "patch": 0, "tile": 0, "phase": 2, "compact": 0, "min_row_groups": 0}, 302010, 101000),
-    "rows_self": ({"self_spans": 1, "patch": 0, "tile": 0, "compact": 0, "min_row_groups": 0}, 104011, 101001),
-    "rows_self_unsafe": ({"self_spans": 1, "patch": 0, "tile": 0, "compact": 0, "min_row_groups": 0, "safe_spans": 0}, 104011, 101001),
-    "rows_self_safe": ({"self_spans": 1, "patch": 0, "tile": 0, "compact": 0, "min_row_groups": 0, "safe_spans": 1}, 104011, 101001),
-    "tile_self": ({"self_spans": 1, "patch": 1, "tile": 1, "min_row_groups": 0}, 504011, 504001),
-    "patch_self": ({"self_spans": 1, "patch": 1, "tile": 0, "min_row_groups": 0}, 408011, 401001),
-    "rows_compact": ({"self_spans": 0, "patch": 0, "tile": 0, "compact": 1, "phase": 2}, 102110, 101100),
-    "patch_lists": ({"self_spans": 0, "patch": 1, "tile": 0}, 408010, 401000),
-    "rows1": ({"self_spans": 0, "patch": 0, "tile": 0, "phase": 1, "compact": 0}, 101010, 101000),
-    "rows_dense": ({"self_spans": 0, "patch": 0, "tile": 0, "compact": 1}, 111110, 111100),        # (mesh "dense" only: 512-slot rows)
-}
-SELF_LABELS = {"rows_self", "rows_self_unsafe", "rows_self_safe", "tile_self", "patch_self"}
 
 
 def _same(got, want, what):
@@ -124,9 +108,6 @@ def test_piecewise_edges_maps_general_and_bilinear(name, twin):
         assert np.array_equal(c.get_tri_map(fused=True), wmap)
     finally:
         c.close()
-
-
-FRAME_SET_KERNELS = ["default", "rows_self_safe", "rows_self_unsafe", "tile_self", "patch_self", "rows4"]
 
 
 @pytest.mark.parametrize("distinct", [False, True], ids=["shared", "distinct"])

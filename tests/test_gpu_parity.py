@@ -949,6 +949,80 @@ def _nan_eq64(a, b):
     return bool(np.all((a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))))
 
 
+def _lu_squares(n_each, seed):
+    """n_each squares of each family of test_cabi_cpu's register-LU test: generic, near-rectangles (exact zeros and ties in the pivot
+    search), normalised coordinates, repeated / collinear points (singular systems), wide dynamic range."""
+    rng = np.random.default_rng(seed)
+    S, D = [], []
+    for trial in range(5 * n_each):
+        kind = trial % 5
+        if kind == 0:
+            s = rng.uniform(-2000, 4000, 8); d = rng.uniform(-2000, 4000, 8)
+        elif kind == 1:
+            w, h = rng.integers(1, 4000, 2)
+            s = np.array([0, 0, 0, h, w, 0, w, h], float); d = s + rng.integers(-3, 4, 8)
+        elif kind == 2:
+            s = rng.uniform(0, 1, 8); d = rng.uniform(0, 1, 8)
+        elif kind == 3:
+            s = rng.integers(0, 4, 8).astype(float); d = rng.integers(0, 4, 8).astype(float)
+        else:
+            s = rng.uniform(-1, 1, 8) * 10.0 ** rng.integers(-6, 7, 8); d = rng.uniform(-1, 1, 8) * 10.0 ** rng.integers(-6, 7, 8)
+        S.append(s.astype(np.float32)); D.append(d.astype(np.float32))
+    return np.stack(S), np.stack(D)
+
+
+def test_device_lu_on_degenerate_squares():
+    """k_solve_frames on 400 squares of each of the five families the host LU is tested on, in one call: the bits of the host solve,
+    NaN positions included."""
+    S, D = _lu_squares(400, 4321)
+    n = S.shape[0]
+    host = np.stack([HG.solve_projective(S[k], D[k]) for k in range(n)])
+    singular = ~np.isfinite(host).all(1)
+    assert singular.sum() > 10, int(singular.sum())
+    c = HG.Context(0)
+    try:
+        c.set_image(G.lcg_image(64, 48, 9))
+        c.geometric_set_frames_points(1, S.ravel(), D.ravel(), [(0, 0, 4, 4)] * n)
+        got = c.get_geometric_matrices(n)
+    finally:
+        c.close()
+    bad = [k for k in range(n) if not _nan_eq64(got[k], host[k])]
+    assert not bad, (len(bad), bad[:8], got[bad[0]], host[bad[0]], S[bad[0]], D[bad[0]])
+
+
+def test_singular_frames_of_a_device_solved_set_come_out_blank():
+    """Six frames solved on the device from point sets, frames 2 and 4 from degenerate quads (coincident / collinear points: every entry of
+    the host solve is NaN): those frames are blank, every other frame is the oracle's on the host-solved matrix."""
+    W, H, F = 320, 200, 6
+    img = G.lcg_image(W, H, 31)
+    s4 = WL.corners(W, H)
+    d4s = [WL.projective_dst(W, H, 0.03 * k) for k in range(F)]
+    d4s[2] = np.float32([50, 50] * 4)
+    d4s[4] = np.float32([10, 10, 100, 100, 200, 200, 300, 300])
+    mats = [HG.solve_projective(d4, s4) for d4 in d4s]
+    assert all(np.isnan(mats[k]).all() == (k in (2, 4)) for k in range(F))
+    geoms = [(0, 0, W, H) if k in (2, 4) else tuple(int(v) for v in O.transform_limits(1, O.projective_from_squares(s4, d4s[k]), W, H)) for k in range(F)]
+    offs, total = HG.pack_offsets(geoms)
+    c = HG.Context(0)
+    d_out = c.alloc(total)
+    try:
+        c.set_image(img)
+        c.to_device(d_out, np.full(total, 0xA5, np.uint8))          # (a blank frame has to be written, not left over)
+        c.geometric_set_frames_points(1, np.concatenate(d4s), np.tile(s4, F), geoms, offs)
+        c.warp_inverse_geometric_frames_device(d_out)
+        c.sync()
+        got_m = c.get_geometric_matrices(F)
+        for k in range(F):
+            g = geoms[k]
+            assert _nan_eq64(got_m[k], mats[k]), k
+            got = c.to_host(d_out, g[2] * g[3] * 4, offs[k]).reshape(g[3], g[2], 4)
+            want = O.warp_inverse_geometric(1, mats[k], img, *g)
+            assert want.any() == (k not in (2, 4)), k
+            assert np.array_equal(got, want), k
+    finally:
+        c.free(d_out); c.close()
+
+
 def test_failed_set_frames_leaves_no_frame_set(ctx):
     """A frame set that fails validation part-way (offset beyond 2^26 in the LAST frame) must not leave the new
     host-side frames over device buffers sized for the old set: the next warp reports HG_ERR_STATE."""
