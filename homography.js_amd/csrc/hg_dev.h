@@ -344,3 +344,5 @@ __device__ __forceinline__ void span_max4d(int best[4], int d0, int d1, int d2, 
 }
 
 } // namespace hg
+
+#include "hg_spans.h"      // the span machinery of the inverse piecewise kernels (uses the helpers above)

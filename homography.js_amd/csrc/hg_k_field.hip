@@ -135,39 +135,9 @@ __global__ __launch_bounds__(256) void k_pw_field(PwMesh mesh, PwFrames fr, uint
 
     __shared__ int s_lo[kRowSpanCap], s_hi[kRowSpanCap], s_id[kRowSpanCap];
     __shared__ int s_cnt;
-    if (threadIdx.x == 0) s_cnt = 0;
-    __syncthreads();
-
     const int T = mesh.n_tris, W = fd.obj_w;
-    const int64_t len = (int64_t)W * fd.obj_h;
-    const int64_t row0 = (int64_t)r * W, row1 = row0 + W;
-    const TriRange *__restrict__ trir = fr.trir + (size_t)f * T;
-    const Seg *__restrict__ segs = fr.segs + (size_t)f * T * 3;
-
-    for (int t = threadIdx.x; t < T; t += 256) {
-        const TriRange tr = trir[t];
-        if (tr.y_end <= tr.y_min) continue;
-#pragma unroll 1
-        for (int image = 0; image < 2; image++) {    // 0: indices >= 0;  1: negative indices wrapped by +len (= +objH rows)
-            const int64_t shift = image ? fd.obj_h : 0;
-            int64_t ylo = (int64_t)r - tr.a - shift + fd.y_off, yhi = (int64_t)r - tr.b - shift + fd.y_off;
-            if (ylo < tr.y_min) ylo = tr.y_min;
-            if (yhi > (int64_t)tr.y_end - 1) yhi = (int64_t)tr.y_end - 1;
-#pragma unroll 1
-            for (int64_t y = ylo; y <= yhi; y++) {
-                int64_t k, fin;
-                span_cells(segs + 3 * (size_t)t, (double)y, (double)fd.y_off, (double)W, len, k, fin);
-                if (k < row0) k = row0;
-                if (fin > row1) fin = row1;
-                if (k < fin) {
-                    const int slot = atomicAdd(&s_cnt, 1);
-                    if (slot < kRowSpanCap) { s_lo[slot] = (int)(k - row0); s_hi[slot] = (int)(fin - row0); s_id[slot] = t; }
-                }
-            }
-        }
-    }
-    __syncthreads();
-    const int cnt = s_cnt;
+    const int64_t row0 = (int64_t)r * W;
+    const int cnt = fused_row_spans(fr, f, T, fd, r, s_lo, s_hi, s_id, &s_cnt);
     if (cnt > kRowSpanCap) {                         // the frame is redone through the materialised map by the host
         if (threadIdx.x == 0) flag_frame(fr, f, FRAME_LDS_OVERFLOW);
         return;
@@ -187,23 +157,8 @@ __global__ __launch_bounds__(256) void k_pw_field(PwMesh mesh, PwFrames fr, uint
 
     for (int w = wave; w < nwin; w += 4) {
         const int c0 = w << 8, cq = c0 + (lane << 2);
-        int tid[4] = { -1, -1, -1, -1 };
-        for (int j = 0; j < cnt; j += 64) {
-            const int idx = j + lane;
-            int lo = 0x7fffffff, hi = 0;
-            if (idx < cnt) { lo = s_lo[idx]; hi = s_hi[idx]; }
-            unsigned long long mask = __ballot(lo < c0 + 256 && hi > c0);
-            while (mask) {
-                const int b = __ffsll((long long)mask) - 1;
-                mask &= mask - 1;
-                const int sl = s_lo[j + b], id = s_id[j + b];
-                const unsigned span = (unsigned)(s_hi[j + b] - sl);
-                const int d = cq - sl;
-#pragma unroll
-                for (int k = 0; k < 4; k++)
-                    if ((unsigned)(d + k) < span) tid[k] = max(tid[k], id);
-            }
-        }
+        int tid[4];
+        fused_resolve_quad(s_lo, s_hi, s_id, cnt, c0, lane, tid);
         if (cq < W) {
             int vx[4], vy[4];
             MatCache mc; mc.id = -1;

@@ -83,43 +83,9 @@ __global__ __launch_bounds__(256) void k_pw_patch(PwMesh mesh, PwFrames fr, RowL
         if (threadIdx.x == 0) { s_ncand = 0; s_fail = nbins > kPatchBins ? 1 : 0; }
         if (threadIdx.x < 3) reinterpret_cast<double2 *>(s_rec + RECS * 6)[threadIdx.x] = make_double2(NAN, NAN);
         __syncthreads();
-        // (1) candidates: can a row of the triangle write into rows r0 .. r0 + nrows - 1?  (see k_pw_rows<SELF>; int32 throughout)
-        const int lane_ = threadIdx.x & 63;
-        const int g_lo = r0 + fd.y_off, g_hi = r0 + nrows - 1 + fd.y_off;
+        // (1) candidates: can a row of the triangle write into rows r0 .. r0 + nrows - 1?  (self_candidates, hg_spans.h; entries of up to 4 source rows)
         const int T = mesh.n_tris;
-        int n_src = T;
-        const int4 *__restrict__ bent = nullptr;
-        if (fr.band_ent) {
-            const int band = r0 >> fr.band_rows_log2;
-            n_src = min(fr.band_cnt[(size_t)f * fr.band_stride + band], fr.band_cap);      // (an overfull band flagged the frame in k_tri_setup)
-            bent = fr.band_ent + ((size_t)f * fr.n_bands + band) * fr.band_cap * 2;        // (two int4 per entry; the second holds the column reach k_pw_tile uses)
-        }
-        const TriRange *__restrict__ trir = fr.trir + (size_t)f * T;
-        for (int i0 = 0; i0 < n_src; i0 += 256) {
-            const int i = i0 + (int)threadIdx.x;
-            int t = i; TriRange tr = TriRange{0, 0, 0, 0};
-            if (i < n_src) {
-                if (bent) { const int4 e = bent[2 * i]; t = e.x; tr.y_min = e.y; tr.y_end = e.z; tr.a = (int16_t)(e.w & 0xffff); tr.b = e.w >> 16; }
-                else tr = trir[i];
-            }
-            const int ylo0 = max(g_lo - tr.a, tr.y_min), n0 = min(g_hi - tr.b, tr.y_end - 1) - ylo0 + 1;
-            const int ylo1 = max(g_lo - tr.a - fd.obj_h, tr.y_min), n1 = min(g_hi - tr.b - fd.obj_h, tr.y_end - 1) - ylo1 + 1;
-            const unsigned long long m0 = __ballot(n0 > 0), m1 = __ballot(n1 > 0);
-            if ((m0 | m1) == 0ull) continue;                // (wave-uniform)
-            const unsigned long long m0b = __ballot(n0 > 4), m1b = __ballot(n1 > 4);
-            const int c0 = __popcll(m0), c0b = __popcll(m0b), c1 = __popcll(m1), c1b = __popcll(m1b);
-            int base = 0;
-            if (lane_ == 0) base = atomicAdd(&s_ncand, c0 + c0b + c1 + c1b);
-            base = __builtin_amdgcn_readfirstlane(base);
-            auto below = [&](unsigned long long m) { return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); };
-            auto file = [&](int at, int y0, int n) { if (at < RECS) { s_cand_tn[at] = t | (min(n, 0xffff) << 16); s_cand_y[at] = y0; } };
-            if (n0 > 0) file(base + below(m0), ylo0, min(n0, 4));
-            if (n0 > 4) file(base + c0 + below(m0b), ylo0 + 4, n0 - 4);
-            if (m1) {
-                if (n1 > 0) file(base + c0 + c0b + below(m1), ylo1, min(n1, 4));
-                if (n1 > 4) file(base + c0 + c0b + c1 + below(m1b), ylo1 + 4, n1 - 4);
-            }
-        }
+        self_candidates(fr, f, T, fd, r0, nrows, 4, 256, &s_ncand, s_cand_tn, s_cand_y, RECS, AnyColumn());
         __syncthreads();
         const int nc = s_ncand;
         if (nc > RECS) { if (threadIdx.x == 0) s_fail = 1 | (nc << 8); }
@@ -142,31 +108,11 @@ __global__ __launch_bounds__(256) void k_pw_patch(PwMesh mesh, PwFrames fr, RowL
             const Seg *__restrict__ sg = gseg + (size_t)t * 3;
             for (int j = jj; j < n; j += 4) {
                 const int ys = ylo + j;
-                const double y = (double)ys;
-                double mn = INFINITY, mx = -INFINITY;       // predictXLimits :1172-1197 (the lean form of span_cells, see k_pw_rows<SELF>)
-                auto edge = [&](const Seg &q) {
-                    const double x = q.m == INFINITY ? q.b : (y - q.b) / q.m;
-                    const bool use = (y >= q.minY) & (y <= q.maxY) & !(q.m == 0.0);
-                    mn = (use & (x < mn)) ? x : mn;
-                    mx = (use & (x > mx)) ? x : mx;
-                };
-                if constexpr (PB >= 8) {                    // the 8-blocks-per-phase main loop holds 86 registers anyway: all three edge
-                    const Seg q0 = sg[0], q1 = sg[1], q2 = sg[2];       // equations in one round trip
-                    edge(q0); edge(q1); edge(q2);
-                } else {
-#pragma unroll 1
-                    for (int e = 0; e < 3; e++) edge(sg[e]);
-                }
-                const double base = (y - (double)fd.y_off) * fW;               // :1124 under TypedArray.fill's index rules
-                double rk = floor(mn); rk += (mn - rk >= 0.5) ? 1.0 : 0.0;
-                double rf = floor(mx); rf += (mx - rf >= 0.5) ? 1.0 : 0.0;
-                double vk = trunc(base + rk), vf = trunc(base + rf);
-                vk = vk < 0.0 ? flen + vk : vk; vf = vf < 0.0 ? flen + vf : vf;
-                const int k = (int)fmin(fmax(vk, 0.0), flen), fin = (int)fmin(fmax(vf, 0.0), flen);
-                if (k >= fin) continue;
-                int r = ys - fd.y_off;
-                if (r < 0) r += fd.obj_h;
-                if ((unsigned)r >= (unsigned)fd.obj_h || (unsigned)(k - r * W) >= (unsigned)W) r = k / W;
+                // predictXLimits :1172-1197 + the fill() indices :1124 (span_cells_lean, hg_math.h).  The 8-blocks-per-phase main loop holds 86
+                // registers anyway: there, all three edge equations in one round trip
+                int k, fin;
+                if (!span_cells_lean<(PB >= 8)>(sg, (double)ys, (double)fd.y_off, fW, flen, k, fin)) continue;
+                int r = span_first_row(ys, fd.y_off, fd.obj_h, W, k);
                 if (r < r0) r = r0;
                 for (; r < r0 + nrows; r++) {
                     const int rb = r * W;
@@ -177,19 +123,10 @@ __global__ __launch_bounds__(256) void k_pw_patch(PwMesh mesh, PwFrames fr, RowL
                     const int slot = atomicAdd(&s_rowcnt[row], 1);
                     if (slot >= CAPR - 1) continue;         // (counted: the check below fails the group)
                     s_lohi[row * CAPR + slot] = (uint32_t)lo | ((uint32_t)hi << 16);
-                    // bit 0 "unsafe" (record offsets are multiples of 48): clear only when BOTH end pixels of the piece pass the source bounds
-                    // test :1047, evaluated exactly as the pixel body evaluates them -- then every pixel between them passes (k_pw_rows)
-                    int unsafe = 1;
-                    if (flag_spans) {
-                        const double yr = (double)(r + fd.y_off), xa = (double)(lo + fd.x_off), xb = (double)(hi - 1 + fd.x_off);
-                        const double cy0 = (double)ma.z * yr, cy1 = (double)ma.w * yr;
-                        double h[4] = { fma((double)ma.x, xa, cy0) + (double)mb.x, fma((double)ma.y, xa, cy1) + (double)mb.y,
-                                        fma((double)ma.x, xb, cy0) + (double)mb.x, fma((double)ma.y, xb, cy1) + (double)mb.y }, rd[4];
-                        round_x4(h, rd);
-                        const bool ia = HIB ? hi_inb(hb0, h[0], h[1]) : (bool)((int)(h[0] >= bx_lo0) & (int)(h[0] < bx_hi0) & (int)(h[1] >= by_lo0) & (int)(h[1] < by_hi0));
-                        const bool ib = HIB ? hi_inb(hb0, h[2], h[3]) : (bool)((int)(h[2] >= bx_lo0) & (int)(h[2] < bx_hi0) & (int)(h[3] >= by_lo0) & (int)(h[3] < by_hi0));
-                        unsafe = (ia && ib) ? 0 : 1;
-                    }
+                    // bit 0 "unsafe" (record offsets are multiples of 48; span_unsafe, hg_spans.h)
+                    const double yr = (double)(r + fd.y_off);
+                    const int unsafe = span_unsafe<HIB>(flag_spans, hb0, bx_lo0, bx_hi0, by_lo0, by_hi0, fd.x_off, (double)ma.x, (double)ma.z * yr, (double)mb.x,
+                                                        (double)ma.y, (double)ma.w * yr, (double)mb.y, lo, hi);
                     s_key[row * CAPR + slot] = (t << kKeyShift) | (c * 48) | unsafe;
                 }
             }

@@ -15,34 +15,11 @@ constexpr int kBandMax = 2048;                 // candidate bands per frame the 
 // One triangle of one frame: solves, edge equations, row range, column reach; returns false when the triangle has no rows or is irregular.
 __device__ __forceinline__ bool tri_setup_one(const PwMesh &mesh, const PwFrames &fr, int f, int t, const FrameDesc &fd, TriRange &tr)
 {
-    const float *dp = fr.dst_pts + (size_t)f * mesh.n_pts * 2, *sp = frame_src(mesh, fr, f);
-    float s[6], d[6];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const uint32_t v = mesh.tris[3 * (size_t)t + k];
-        if (v < (uint32_t)mesh.n_pts) {
-            s[2 * k] = sp[2 * (size_t)v]; s[2 * k + 1] = sp[2 * (size_t)v + 1];
-            d[2 * k] = dp[2 * (size_t)v];           d[2 * k + 1] = dp[2 * (size_t)v + 1];
-        } else {                                   // typed-array read past the end: undefined -> NaN in the Float32Array(6)
-            s[2 * k] = s[2 * k + 1] = d[2 * k] = d[2 * k + 1] = NAN;
-        }
-    }
+    float d[6], inv[6];
+    Seg seg[3];
+    tri_solve(mesh, fr, f, t, true, d, inv, seg);
     const size_t ft = (size_t)f * mesh.n_tris + t;
-    float fwd[6], inv[6];
-    solve_affine(s, d, fwd);
-    invert_affine(fwd, inv);
-#pragma unroll
-    for (int k = 0; k < 6; k++) fr.fwd[ft * 6 + k] = fwd[k];
-    *reinterpret_cast<float4 *>(fr.inv + ft * kInvStride) = make_float4(inv[0], inv[1], inv[2], inv[3]);
-    *reinterpret_cast<float4 *>(fr.inv + ft * kInvStride + 4) = make_float4(inv[4], inv[5], 0.f, 0.f);
     const bool one_fma = affine_fusable(inv, coord_bits(fd.x_off, fd.obj_w), coord_bits(fd.y_off, fd.obj_h));     // (hg_math.h)
-
-    Seg *sg = fr.segs + ft * 3;
-    Seg a, b, c;
-    define_seg(d[0], d[1], d[2], d[3], a);          // p0->p1
-    define_seg(d[0], d[1], d[4], d[5], b);          // p0->p2
-    define_seg(d[2], d[3], d[4], d[5], c);          // p1->p2
-    sg[0] = a; sg[1] = b; sg[2] = c;
 
     tri_rows_tight(d[1], d[3], d[5], tr.y_min, tr.y_end);    // (without the leading row that cannot have a span, hg_math.h)
     tr.a = 0; tr.b = 0;
@@ -177,39 +154,9 @@ __global__ __launch_bounds__(256) void k_pw_fused(PwMesh mesh, PwFrames fr, uint
 
     __shared__ int s_lo[kRowSpanCap], s_hi[kRowSpanCap], s_id[kRowSpanCap];
     __shared__ int s_cnt;
-    if (threadIdx.x == 0) s_cnt = 0;
-    __syncthreads();
-
     const int T = mesh.n_tris, W = fd.obj_w;
-    const int64_t len = (int64_t)W * fd.obj_h;
-    const int64_t row0 = (int64_t)r * W, row1 = row0 + W;
-    const TriRange *__restrict__ trir = fr.trir + (size_t)f * T;
-    const Seg *__restrict__ segs = fr.segs + (size_t)f * T * 3;
-
-    for (int t = threadIdx.x; t < T; t += 256) {
-        const TriRange tr = trir[t];
-        if (tr.y_end <= tr.y_min) continue;
-#pragma unroll 1
-        for (int image = 0; image < 2; image++) {    // 0: indices >= 0;  1: negative indices wrapped by +len (= +objH rows)
-            const int64_t shift = image ? fd.obj_h : 0;
-            int64_t ylo = (int64_t)r - tr.a - shift + fd.y_off, yhi = (int64_t)r - tr.b - shift + fd.y_off;
-            if (ylo < tr.y_min) ylo = tr.y_min;
-            if (yhi > (int64_t)tr.y_end - 1) yhi = (int64_t)tr.y_end - 1;
-#pragma unroll 1
-            for (int64_t y = ylo; y <= yhi; y++) {
-                int64_t k, fin;
-                span_cells(segs + 3 * (size_t)t, (double)y, (double)fd.y_off, (double)W, len, k, fin);
-                if (k < row0) k = row0;
-                if (fin > row1) fin = row1;
-                if (k < fin) {
-                    const int slot = atomicAdd(&s_cnt, 1);
-                    if (slot < kRowSpanCap) { s_lo[slot] = (int)(k - row0); s_hi[slot] = (int)(fin - row0); s_id[slot] = t; }
-                }
-            }
-        }
-    }
-    __syncthreads();
-    const int cnt = s_cnt;
+    const int64_t row0 = (int64_t)r * W;
+    const int cnt = fused_row_spans(fr, f, T, fd, r, s_lo, s_hi, s_id, &s_cnt);
     if (cnt > kRowSpanCap) {                         // frame is redone through the materialised-map path by the host
         if (threadIdx.x == 0) flag_frame(fr, f, FRAME_LDS_OVERFLOW);
         return;
@@ -229,23 +176,8 @@ __global__ __launch_bounds__(256) void k_pw_fused(PwMesh mesh, PwFrames fr, uint
 
     for (int w = wave; w < nwin; w += 4) {
         const int c0 = w << 8, cq = c0 + (lane << 2);
-        int tid[4] = { -1, -1, -1, -1 };
-        for (int j = 0; j < cnt; j += 64) {
-            const int idx = j + lane;
-            int lo = 0x7fffffff, hi = 0;
-            if (idx < cnt) { lo = s_lo[idx]; hi = s_hi[idx]; }
-            unsigned long long mask = __ballot(lo < c0 + 256 && hi > c0);
-            while (mask) {
-                const int b = __ffsll((long long)mask) - 1;
-                mask &= mask - 1;
-                const int sl = s_lo[j + b], id = s_id[j + b];
-                const unsigned span = (unsigned)(s_hi[j + b] - sl);
-                const int d = cq - sl;
-#pragma unroll
-                for (int k = 0; k < 4; k++)
-                    if ((unsigned)(d + k) < span) tid[k] = max(tid[k], id);
-            }
-        }
+        int tid[4];
+        fused_resolve_quad(s_lo, s_hi, s_id, cnt, c0, lane, tid);
         if (cq < W) {
             uint32_t px[4];
             MatCache mc; mc.id = -1;
@@ -289,34 +221,13 @@ __global__ __launch_bounds__(256) void k_tri_spans(PwMesh mesh, PwFrames fr, Row
 {
     const int t = blockIdx.x, f = blockIdx.y;
     const FrameDesc fd = fr.frames[f];
-    const float *dp = fr.dst_pts + (size_t)f * mesh.n_pts * 2, *sp = frame_src(mesh, fr, f);
-    float s[6], d[6];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const uint32_t v = mesh.tris[3 * (size_t)t + k];
-        if (v < (uint32_t)mesh.n_pts) {
-            s[2 * k] = sp[2 * (size_t)v]; s[2 * k + 1] = sp[2 * (size_t)v + 1];
-            d[2 * k] = dp[2 * (size_t)v];           d[2 * k + 1] = dp[2 * (size_t)v + 1];
-        } else {
-            s[2 * k] = s[2 * k + 1] = d[2 * k] = d[2 * k + 1] = NAN;
-        }
-    }
-    float fwd[6], inv[6];
-    solve_affine(s, d, fwd);                       // every thread redundantly: cheaper than a broadcast through LDS
-    invert_affine(fwd, inv);
+    float d[6], inv[6];
     Seg seg[3];
-    define_seg(d[0], d[1], d[2], d[3], seg[0]);     // p0->p1
-    define_seg(d[0], d[1], d[4], d[5], seg[1]);     // p0->p2
-    define_seg(d[2], d[3], d[4], d[5], seg[2]);     // p1->p2
+    tri_solve(mesh, fr, f, t, threadIdx.x == 0, d, inv, seg);     // every thread redundantly: cheaper than a broadcast through LDS; thread 0 stores
     int32_t y_min, y_end;
     tri_rows(d[1], d[3], d[5], y_min, y_end);
     const size_t ft = (size_t)f * mesh.n_tris + t;
-    if (threadIdx.x == 0) {                        // taps + inputs of the map path
-#pragma unroll
-        for (int k = 0; k < 6; k++) fr.fwd[ft * 6 + k] = fwd[k];
-        *reinterpret_cast<float4 *>(fr.inv + ft * kInvStride) = make_float4(inv[0], inv[1], inv[2], inv[3]);
-        *reinterpret_cast<float4 *>(fr.inv + ft * kInvStride + 4) = make_float4(inv[4], inv[5], 0.f, 0.f);
-        fr.segs[ft * 3] = seg[0]; fr.segs[ft * 3 + 1] = seg[1]; fr.segs[ft * 3 + 2] = seg[2];
+    if (threadIdx.x == 0) {
         TriRange tr; tr.y_min = y_min; tr.y_end = y_end; tr.a = 0; tr.b = 0;
         fr.trir[ft] = tr;
     }
@@ -330,25 +241,7 @@ __global__ __launch_bounds__(256) void k_tri_spans(PwMesh mesh, PwFrames fr, Row
     for (int64_t y = y_first + threadIdx.x; y < y_stop; y += blockDim.x) {
         int64_t k, fin;
         span_cells(seg, (double)y, (double)fd.y_off, (double)W, len, k, fin);
-        if (k >= fin) continue;
-        // usual case: the span sits in output row (y - yOff) (+objH when it wrapped); otherwise divide
-        int64_t r = y - fd.y_off;
-        if (r < 0) r += fd.obj_h;
-        if (r < 0 || r >= fd.obj_h || k < r * W || k >= (r + 1) * W) r = k / W;
-        for (; r * W < fin; r++) {
-            const int64_t lo = (k > r * W ? k : r * W) - r * W, hi = (fin < (r + 1) * W ? fin : (r + 1) * W) - r * W;
-            const int slot = atomicAdd(&rowcnt[r], 1);
-            if (slot < rl.cap) {
-                const size_t idx = ent0 + (size_t)r * rl.cap + slot;
-                const uint32_t lh = (uint32_t)lo | ((uint32_t)hi << 16);
-                if (COMPACT) static_cast<uint2 *>(rl.ent)[idx] = make_uint2(lh, (uint32_t)t);
-                else {
-                    uint4 *dst = static_cast<uint4 *>(rl.ent) + 2 * idx;
-                    dst[0] = make_uint4(lh, (uint32_t)t, __float_as_uint(inv[0]), __float_as_uint(inv[1]));
-                    dst[1] = make_uint4(__float_as_uint(inv[2]), __float_as_uint(inv[3]), __float_as_uint(inv[4]), __float_as_uint(inv[5]));
-                }
-            }
-        }
+        if (k < fin) file_row_span<COMPACT>(k, fin, y - fd.y_off, fd.obj_h, W, rowcnt, ent0, rl, t, inv);
     }
 }
 
@@ -375,32 +268,12 @@ __global__ __launch_bounds__(kTriGroupThreads) void k_tri_spans_grouped(PwMesh m
     const int64_t len = (int64_t)W * fd.obj_h;
     if (tid < kTriGroup && t0 + tid < mesh.n_tris) {
         const int t = t0 + tid;
-        const float *dp = fr.dst_pts + (size_t)f * mesh.n_pts * 2, *sp = frame_src(mesh, fr, f);
-        float s[6], d[6];
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const uint32_t v = mesh.tris[3 * (size_t)t + k];
-            if (v < (uint32_t)mesh.n_pts) {
-                s[2 * k] = sp[2 * (size_t)v]; s[2 * k + 1] = sp[2 * (size_t)v + 1];
-                d[2 * k] = dp[2 * (size_t)v];           d[2 * k + 1] = dp[2 * (size_t)v + 1];
-            } else {
-                s[2 * k] = s[2 * k + 1] = d[2 * k] = d[2 * k + 1] = NAN;
-            }
-        }
-        float fwd[6], inv[6];
-        solve_affine(s, d, fwd); invert_affine(fwd, inv);
+        float d[6], inv[6];
         Seg seg[3];
-        define_seg(d[0], d[1], d[2], d[3], seg[0]);     // p0->p1
-        define_seg(d[0], d[1], d[4], d[5], seg[1]);     // p0->p2
-        define_seg(d[2], d[3], d[4], d[5], seg[2]);     // p1->p2
+        tri_solve(mesh, fr, f, t, true, d, inv, seg);
         int32_t y_min, y_end;
         tri_rows(d[1], d[3], d[5], y_min, y_end);
         const size_t ft = (size_t)f * mesh.n_tris + t;
-#pragma unroll
-        for (int k = 0; k < 6; k++) fr.fwd[ft * 6 + k] = fwd[k];                                 // taps + inputs of the map path
-        *reinterpret_cast<float4 *>(fr.inv + ft * kInvStride) = make_float4(inv[0], inv[1], inv[2], inv[3]);
-        *reinterpret_cast<float4 *>(fr.inv + ft * kInvStride + 4) = make_float4(inv[4], inv[5], 0.f, 0.f);
-        fr.segs[ft * 3] = seg[0]; fr.segs[ft * 3 + 1] = seg[1]; fr.segs[ft * 3 + 2] = seg[2];
         TriRange tr; tr.y_min = y_min; tr.y_end = y_end; tr.a = 0; tr.b = 0;
         fr.trir[ft] = tr;
         int64_t y_first = y_min, y_stop = y_end;
@@ -432,25 +305,7 @@ __global__ __launch_bounds__(kTriGroupThreads) void k_tri_spans_grouped(PwMesh m
         for (int64_t y = y_first + lane; y < y_stop; y += 64) {
             int64_t k, fin;
             span_cells(seg, (double)y, (double)fd.y_off, (double)W, len, k, fin);
-            if (k >= fin) continue;
-            // usual case: the span sits in output row (y - yOff) (+objH when it wrapped); otherwise divide
-            int64_t r = y - fd.y_off;
-            if (r < 0) r += fd.obj_h;
-            if (r < 0 || r >= fd.obj_h || k < r * W || k >= (r + 1) * W) r = k / W;
-            for (; r * W < fin; r++) {
-                const int64_t lo = (k > r * W ? k : r * W) - r * W, hi = (fin < (r + 1) * W ? fin : (r + 1) * W) - r * W;
-                const int slot = atomicAdd(&rowcnt[r], 1);
-                if (slot < rl.cap) {
-                    const size_t idx = ent0 + (size_t)r * rl.cap + slot;
-                    const uint32_t lh = (uint32_t)lo | ((uint32_t)hi << 16);
-                    if (COMPACT) static_cast<uint2 *>(rl.ent)[idx] = make_uint2(lh, (uint32_t)t);
-                    else {
-                        uint4 *dst = static_cast<uint4 *>(rl.ent) + 2 * idx;
-                        dst[0] = make_uint4(lh, (uint32_t)t, __float_as_uint(inv[0]), __float_as_uint(inv[1]));
-                        dst[1] = make_uint4(__float_as_uint(inv[2]), __float_as_uint(inv[3]), __float_as_uint(inv[4]), __float_as_uint(inv[5]));
-                    }
-                }
-            }
+            if (k < fin) file_row_span<COMPACT>(k, fin, y - fd.y_off, fd.obj_h, W, rowcnt, ent0, rl, t, inv);
         }
     }
 }
@@ -538,8 +393,6 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
     // HIB (host: hi_bounds_ok): the same four tests as two 32-bit compares on the high dwords of h (hg_dev.h)
     const HiBounds hb = make_hi_bounds((double)ms.x + 0.5, (double)mesh.W + (double)ms.x + 0.5,
                                        (double)ms.y + 0.5, (double)mesh.H + (double)ms.y + 0.5);
-    // 1 unless both end pixels lo, hi - 1 of a span with record {m0, m2*y, m4, m1, m3*y, m5} are inside the source window, computed as
-    // the pixel body computes them (same fma, same rounding, same compares)
     const bool flag_spans = fr.safe_spans != 0;             // (wave-uniform; host: by the rows' span density)
     // One fma per coordinate for the whole frame: (m0 x) + (m2 y) + m4 of :1383 rounds twice, but where m0 x + m2 y and m2 y + m4 are exactly
     // representable for every pixel of the window -- k_tri_setup checked every triangle of the frame that has rows (affine_fusable, hg_math.h:
@@ -547,14 +400,9 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
     // bits.  The span records of such a frame hold {m0, A, m1, B}: 32 bytes of LDS per pixel instead of 48, which is what this kernel runs
     // on (EXPERIMENTS.md R5.8).  Uniform for the workgroup; the row lists (small frame sets) keep the long form.
     const bool one_fma = SELF != 0 && fr.two_round && __builtin_amdgcn_readfirstlane(fr.two_round[f]) != fr.gen;
-    auto span_unsafe = [&](double m0, double m2y, double m4, double m1, double m3y, double m5, int lo, int hi) -> int {
-        if (!flag_spans) return 1;
-        const double xa = (double)(lo + fd.x_off), xb = (double)(hi - 1 + fd.x_off);
-        double h[4] = { fma(m0, xa, m2y) + m4, fma(m1, xa, m3y) + m5, fma(m0, xb, m2y) + m4, fma(m1, xb, m3y) + m5 }, rd[4];
-        round_x4(h, rd);
-        const bool a = HIB ? hi_inb(hb, h[0], h[1]) : (bool)((int)(h[0] >= bx_lo) & (int)(h[0] < bx_hi) & (int)(h[1] >= by_lo) & (int)(h[1] < by_hi));
-        const bool b = HIB ? hi_inb(hb, h[2], h[3]) : (bool)((int)(h[2] >= bx_lo) & (int)(h[2] < bx_hi) & (int)(h[3] >= by_lo) & (int)(h[3] < by_hi));
-        return (a && b) ? 0 : 1;
+    // bit 0 of a span's key (span_unsafe, hg_spans.h), for a span with record {m0, m2*y, m4, m1, m3*y, m5}
+    auto unsafe_bit = [&](double m0, double m2y, double m4, double m1, double m3y, double m5, int lo, int hi) -> int {
+        return span_unsafe<HIB>(flag_spans, hb, bx_lo, bx_hi, by_lo, by_hi, fd.x_off, m0, m2y, m4, m1, m3y, m5, lo, hi);
     };
 
     const float *__restrict__ ginv = fr.inv + (size_t)f * mesh.n_tris * kInvStride;
@@ -580,7 +428,7 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
             }
             const int elo = (int)(lh & 0xffffu), ehi = (int)(lh >> 16);
             s_lo[base + i] = elo; s_hi[base + i] = ehi; s_len[base + i] = ehi - elo;
-            s_key[base + i] = ((int)id << KS) | ((base + i) * 48) | span_unsafe(m0, m2 * y, m4, m1, m3 * y, m5, elo, ehi);
+            s_key[base + i] = ((int)id << KS) | ((base + i) * 48) | unsafe_bit(m0, m2 * y, m4, m1, m3 * y, m5, elo, ehi);
             double2 *mrec = reinterpret_cast<double2 *>(s_m + (base + i) * 6);
             mrec[0] = make_double2(m0, m2 * y);              // {m0, m2*y, m1, m3*y, m4, m5}: m2*y and m3*y are the separately
             mrec[1] = make_double2(m1, m3 * y);              // rounded products of :1383-1384
@@ -608,48 +456,9 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
         }
         __syncthreads();
         const int T = mesh.n_tris;
-        const TriRange *__restrict__ trir = fr.trir + (size_t)f * T;
-        // (int32 throughout: |yOff|, objH and the clamped row ranges are below 2^26 -- coordinates are limited to 2^24, hg_math.h --
-        //  and a, b are cell offsets / W of a map with fewer than 2^31 cells)
-        const int g_lo = r0 + fd.y_off, g_hi = r0 + nrows - 1 + fd.y_off;
-        // Candidate entries carry up to `chunk` source rows (4 for 4-row groups, 1 for one-row groups: one lane per row below); a
-        // triangle that reaches more rows -- window borders, spans spilling over the row end (x-offset quirk) -- files a second entry
-        // for the rest, whose lanes loop if that is still more than `chunk` (a - b > 1: triangles wider than the map; rare).
+        // (1) candidates (self_candidates, hg_spans.h): entries of up to `chunk` source rows -- 4 for 4-row groups, 1 for one-row groups: one lane per row below
         const int chunk_log2 = packed ? 2 : 0, chunk = 1 << chunk_log2;
-        // (meshes beyond 1024 triangles: not the whole mesh but the entries k_tri_setup filed under this group's 64-row band, as in k_pw_patch<SELF>)
-        int n_src = T;
-        const int4 *__restrict__ bent = nullptr;
-        if (fr.band_ent) {
-            const int bandi = r0 >> fr.band_rows_log2;      // (row groups never straddle a band)
-            n_src = min(fr.band_cnt[(size_t)f * fr.band_stride + bandi], fr.band_cap);
-            bent = fr.band_ent + ((size_t)f * fr.n_bands + bandi) * fr.band_cap * 2;
-        }
-        for (int t0 = 0; t0 < n_src; t0 += nthreads) {
-            const int i = t0 + (int)threadIdx.x;
-            int t = i;
-            TriRange tr = TriRange{0, 0, 0, 0};
-            if (i < n_src) {
-                if (bent) { const int4 e = bent[2 * i]; t = e.x; tr.y_min = e.y; tr.y_end = e.z; tr.a = (int16_t)(e.w & 0xffff); tr.b = e.w >> 16; }
-                else tr = trir[i];
-            }
-            const int ylo0 = max(g_lo - tr.a, tr.y_min), n0 = min(g_hi - tr.b, tr.y_end - 1) - ylo0 + 1;
-            const int ylo1 = max(g_lo - tr.a - fd.obj_h, tr.y_min), n1 = min(g_hi - tr.b - fd.obj_h, tr.y_end - 1) - ylo1 + 1;
-            const unsigned long long m0 = __ballot(n0 > 0), m1 = __ballot(n1 > 0);
-            if ((m0 | m1) == 0ull) continue;                // (wave-uniform)
-            const unsigned long long m0b = __ballot(n0 > chunk), m1b = __ballot(n1 > chunk);
-            const int c0 = __popcll(m0), c0b = __popcll(m0b), c1 = __popcll(m1), c1b = __popcll(m1b);
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&s_ncand, c0 + c0b + c1 + c1b);
-            base = __builtin_amdgcn_readfirstlane(base);
-            auto below = [&](unsigned long long m) { return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); };
-            auto file = [&](int at, int y0, int n) { if (at < kCandCap) { s_cand_tn[at] = t | (min(n, 0xffff) << 16); s_cand_y[at] = y0; } };
-            if (n0 > 0) file(base + below(m0), ylo0, min(n0, chunk));
-            if (n0 > chunk) file(base + c0 + below(m0b), ylo0 + chunk, n0 - chunk);
-            if (m1) {
-                if (n1 > 0) file(base + c0 + c0b + below(m1), ylo1, min(n1, chunk));
-                if (n1 > chunk) file(base + c0 + c0b + c1 + below(m1b), ylo1 + chunk, n1 - chunk);
-            }
-        }
+        self_candidates(fr, f, T, fd, r0, nrows, chunk, nthreads, &s_ncand, s_cand_tn, s_cand_y, kCandCap, AnyColumn());
         __syncthreads();
         const int nc = s_ncand;
         if (nc > kCandCap) return false;
@@ -668,34 +477,10 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
             const float2 mb = *reinterpret_cast<const float2 *>(ginv + (size_t)t * kInvStride + 4);
             for (int j = jj; j < n; j += lpc) {
                 const int ys = ylo + j;
-                const double y = (double)ys;
-                // predictXLimits :1172-1197, the lean form of span_cells (hg_math.h; same comparisons, same division, same results for
-                // every input -- NaN compares false and leaves mn / mx alone, a division by m = 0 is computed and discarded)
-                double mn = INFINITY, mx = -INFINITY;
-                auto edge = [&](const Seg &q) {
-                    const double x = q.m == INFINITY ? q.b : (y - q.b) / q.m;
-                    const bool use = (y >= q.minY) & (y <= q.maxY) & !(q.m == 0.0);
-                    mn = (use & (x < mn)) ? x : mn;
-                    mx = (use & (x > mx)) ? x : mx;
-                };
-                // one edge at a time: with all three in flight the prologue would need 14 registers more than the pixel loop does
-                // (72 instead of 56-58: 7 waves per SIMD instead of 8).  The three dependent round trips this costs are NOT what the
-                // prologue's time is made of (EXPERIMENTS.md R4.8: forming the edges from the vertices in one round trip changed nothing)
-#pragma unroll 1
-                for (int e = 0; e < 3; e++) edge(sg[e]);
-                // the two flat fill() indices :1124 = (y - yOffset) * W + Math.round(x) under TypedArray.fill's index rules: NaN -> 0,
-                // trunc, negative counts from the end, clamp to [0, len] (js_fill_index, hg_math.h; maxNum / minNum absorb the NaN)
-                const double base = (y - (double)fd.y_off) * fW;
-                double rk = floor(mn); rk += (mn - rk >= 0.5) ? 1.0 : 0.0;      // Math.round (floor of +-Inf / NaN / |x| >= 2^52 is the value itself)
-                double rf = floor(mx); rf += (mx - rf >= 0.5) ? 1.0 : 0.0;
-                double vk = trunc(base + rk), vf = trunc(base + rf);
-                vk = vk < 0.0 ? flen + vk : vk; vf = vf < 0.0 ? flen + vf : vf;
-                const int k = (int)fmin(fmax(vk, 0.0), flen), fin = (int)fmin(fmax(vf, 0.0), flen);
-                if (k >= fin) continue;
-                // usual case: the span sits in output row (y - yOff) (+objH when it wrapped); otherwise divide
-                int r = ys - fd.y_off;
-                if (r < 0) r += fd.obj_h;
-                if ((unsigned)r >= (unsigned)fd.obj_h || (unsigned)(k - r * W) >= (unsigned)W) r = k / W;
+                // predictXLimits :1172-1197 + the two flat fill() indices :1124, one edge at a time (span_cells_lean, hg_math.h)
+                int k, fin;
+                if (!span_cells_lean<false>(sg, (double)ys, (double)fd.y_off, fW, flen, k, fin)) continue;
+                int r = span_first_row(ys, fd.y_off, fd.obj_h, W, k);
                 if (r < r0) r = r0;                          // (pieces in rows above the group belong to other workgroups)
                 for (; r < r0 + nrows; r++) {
                     const int rb = r * W;
@@ -709,7 +494,7 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
                     const double yr = (double)(r + fd.y_off);
                     const double m2y = (double)ma.z * yr, m3y = (double)ma.w * yr;
                     s_lo[at] = lo; s_hi[at] = hi; s_len[at] = hi - lo;
-                    s_key[at] = (t << KS) | (at * 48) | span_unsafe((double)ma.x, m2y, (double)mb.x, (double)ma.y, m3y, (double)mb.y, lo, hi);
+                    s_key[at] = (t << KS) | (at * 48) | unsafe_bit((double)ma.x, m2y, (double)mb.x, (double)ma.y, m3y, (double)mb.y, lo, hi);
                     double2 *mrec = reinterpret_cast<double2 *>(s_m + at * 6);
                     if (one_fma) {                                               // {m0, A, m1, B}
                         mrec[0] = make_double2((double)ma.x, m2y + (double)mb.x);

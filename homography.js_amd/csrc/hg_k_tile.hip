@@ -63,63 +63,28 @@ __global__ __launch_bounds__(256) void k_pw_tile(PwMesh mesh, PwFrames fr, RowLi
     if (threadIdx.x < 3) reinterpret_cast<double2 *>(s_rec + kTileRecs * 6)[threadIdx.x] = make_double2(NAN, NAN);
     __syncthreads();
 
-    // ---- (1) candidates: triangles one of whose rows can write into rows r0 .. r0 + nrows - 1 (see k_pw_rows<SELF>) AND whose cells can
-    // lie in columns [t0, t0 + ncols): a row's cells are (y - yOff) W + round(x), x between the vertex x's (+-1), so their columns are
-    // [xlo, xhi] modulo W -- one interval, or two when it wraps over the row end (x-offset quirk, Appendix A-Q4).  Generous, never missing.
+    // ---- (1) candidates: triangles one of whose rows can write into rows r0 .. r0 + nrows - 1 (self_candidates, hg_spans.h; entries of up to
+    // kTileRows source rows; 8-row tiles never straddle a 64-row band) AND whose cells can lie in columns [t0, t0 + ncols): a row's cells are
+    // (y - yOff) W + round(x), x between the vertex x's (+-1), so their columns are [xlo, xhi] modulo W -- one interval, or two when it wraps
+    // over the row end (x-offset quirk, Appendix A-Q4).  Generous, never missing.
     const int T = mesh.n_tris;
-    const int g_lo = r0 + fd.y_off, g_hi = r0 + nrows - 1 + fd.y_off;
-    int n_src = T;
-    const int4 *__restrict__ bent = nullptr;
-    if (fr.band_ent) {
-        const int bandi = r0 >> fr.band_rows_log2;          // (8-row tiles never straddle a 64-row band)
-        n_src = min(fr.band_cnt[(size_t)f * fr.band_stride + bandi], fr.band_cap);
-        bent = fr.band_ent + ((size_t)f * fr.n_bands + bandi) * fr.band_cap * 2;
-    }
-    const TriRange *__restrict__ trir = fr.trir + (size_t)f * T;
     const int2 *__restrict__ trix = fr.trix + (size_t)f * T;
-    for (int i0 = 0; i0 < n_src; i0 += 256) {
-        const int i = i0 + (int)threadIdx.x;
-        int t = i, xlo = 0, xhi = -1;
-        TriRange tr = TriRange{0, 0, 0, 0};
-        if (i < n_src) {
-            if (bent) {
-                const int4 e = bent[2 * i], x = bent[2 * i + 1];
-                t = e.x; tr.y_min = e.y; tr.y_end = e.z; tr.a = (int16_t)(e.w & 0xffff); tr.b = e.w >> 16; xlo = x.x; xhi = x.y;
-            } else { tr = trir[i]; const int2 x = trix[i]; xlo = x.x; xhi = x.y; }
-        }
-        bool cols = false;
-        if (xhi >= xlo) {
-            if (xhi - xlo + 1 >= W) cols = true;
-            else {
-                int cl = xlo % W; if (cl < 0) cl += W;       // column of xlo
-                const int ch = cl + (xhi - xlo);             // < 2 W
-                cols = (cl < t0 + ncols && ch >= t0) || (cl - W < t0 + ncols && ch - W >= t0);
-            }
-        }
-        int ylo0 = max(g_lo - tr.a, tr.y_min), n0 = min(g_hi - tr.b, tr.y_end - 1) - ylo0 + 1;
-        int ylo1 = max(g_lo - tr.a - fd.obj_h, tr.y_min), n1 = min(g_hi - tr.b - fd.obj_h, tr.y_end - 1) - ylo1 + 1;
-        if (!cols) { n0 = 0; n1 = 0; }
-        const unsigned long long m0 = __ballot(n0 > 0), m1 = __ballot(n1 > 0);
-        if ((m0 | m1) == 0ull) continue;                    // (wave-uniform)
-        const unsigned long long m0b = __ballot(n0 > kTileRows), m1b = __ballot(n1 > kTileRows);
-        const int c0 = __popcll(m0), c0b = __popcll(m0b), c1 = __popcll(m1), c1b = __popcll(m1b);
-        int base = 0;
-        if (lane == 0) base = atomicAdd(&s_ncand, c0 + c0b + c1 + c1b);
-        base = __builtin_amdgcn_readfirstlane(base);
-        auto below = [&](unsigned long long m) { return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); };
-        auto file = [&](int at, int y0, int n) { if (at < kTileCands) { s_cand_tn[at] = t | (min(n, 0xffff) << 16); s_cand_y[at] = y0; } };
-        if (n0 > 0) file(base + below(m0), ylo0, min(n0, kTileRows));
-        if (n0 > kTileRows) file(base + c0 + below(m0b), ylo0 + kTileRows, n0 - kTileRows);
-        if (m1) {
-            if (n1 > 0) file(base + c0 + c0b + below(m1), ylo1, min(n1, kTileRows));
-            if (n1 > kTileRows) file(base + c0 + c0b + c1 + below(m1b), ylo1 + kTileRows, n1 - kTileRows);
-        }
-    }
+    auto in_columns = [&](int i, const int4 *__restrict__ bent) -> bool {
+        int xlo, xhi;
+        if (bent) { const int4 x = bent[2 * i + 1]; xlo = x.x; xhi = x.y; }
+        else { const int2 x = trix[i]; xlo = x.x; xhi = x.y; }
+        if (xhi < xlo) return false;
+        if (xhi - xlo + 1 >= W) return true;
+        int cl = xlo % W; if (cl < 0) cl += W;           // column of xlo
+        const int ch = cl + (xhi - xlo);                 // < 2 W
+        return (cl < t0 + ncols && ch >= t0) || (cl - W < t0 + ncols && ch - W >= t0);
+    };
+    self_candidates(fr, f, T, fd, r0, nrows, kTileRows, 256, &s_ncand, s_cand_tn, s_cand_y, kTileCands, in_columns);
     __syncthreads();
     const int nc = s_ncand;
     if (nc > kTileRecs) { if (threadIdx.x == 0) s_fail = 1 | (nc << 8); }
-    // ---- (2) spans: 8 lanes per candidate entry, one source row each (predictXLimits :1172-1197 + the fill() indices :1124, the lean
-    // form of span_cells: see k_pw_rows<SELF>); pieces cut at output-row boundaries, then to the tile's columns
+    // ---- (2) spans: 8 lanes per candidate entry, one source row each (predictXLimits :1172-1197 + the fill() indices :1124, all three edges
+    // in one round trip: span_cells_lean, hg_math.h); pieces cut at output-row boundaries, then to the tile's columns
     const float *__restrict__ ginv = fr.inv + (size_t)f * T * kInvStride;
     const double flen = (double)((int64_t)W * fd.obj_h), fW = (double)W;
     const Seg *__restrict__ gseg = fr.segs + (size_t)f * T * 3;
@@ -139,26 +104,9 @@ __global__ __launch_bounds__(256) void k_pw_tile(PwMesh mesh, PwFrames fr, RowLi
         const Seg *__restrict__ sg = gseg + (size_t)t * 3;
         for (int j = jj; j < n; j += 8) {
             const int ys = ylo + j;
-            const double y = (double)ys;
-            double mn = INFINITY, mx = -INFINITY;
-            const Seg q0 = sg[0], q1 = sg[1], q2 = sg[2];
-            auto edge = [&](const Seg &q) {
-                const double x = q.m == INFINITY ? q.b : (y - q.b) / q.m;
-                const bool use = (y >= q.minY) & (y <= q.maxY) & !(q.m == 0.0);
-                mn = (use & (x < mn)) ? x : mn;
-                mx = (use & (x > mx)) ? x : mx;
-            };
-            edge(q0); edge(q1); edge(q2);
-            const double base = (y - (double)fd.y_off) * fW;
-            double rk = floor(mn); rk += (mn - rk >= 0.5) ? 1.0 : 0.0;
-            double rf = floor(mx); rf += (mx - rf >= 0.5) ? 1.0 : 0.0;
-            double vk = trunc(base + rk), vf = trunc(base + rf);
-            vk = vk < 0.0 ? flen + vk : vk; vf = vf < 0.0 ? flen + vf : vf;
-            const int k = (int)fmin(fmax(vk, 0.0), flen), fin = (int)fmin(fmax(vf, 0.0), flen);
-            if (k >= fin) continue;
-            int r = ys - fd.y_off;
-            if (r < 0) r += fd.obj_h;
-            if ((unsigned)r >= (unsigned)fd.obj_h || (unsigned)(k - r * W) >= (unsigned)W) r = k / W;
+            int k, fin;
+            if (!span_cells_lean<true>(sg, (double)ys, (double)fd.y_off, fW, flen, k, fin)) continue;
+            int r = span_first_row(ys, fd.y_off, fd.obj_h, W, k);
             if (r < r0) r = r0;
             for (; r < r0 + nrows; r++) {
                 const int rb = r * W;

@@ -216,6 +216,52 @@ HG_HD void span_cells(const Seg *seg, double y, double y_off, double map_w, int6
     fin = js_fill_index(base + js_round(mx), len);
 }
 
+// The lean form of span_cells the self-span prologues run (k_pw_rows<SELF>, k_pw_patch<SELF>, k_pw_tile): same comparisons, same division --
+// NaN compares false and leaves mn / mx alone, a division by m = 0 is computed and discarded -- for maps of flen = len < 2^31 cells
+// (fill_frames), ends as int.  Returns k < fin; where that holds, k and fin are span_cells' (tests/cpp/span_lean_check.cpp); the ends of an
+// empty span are not.  The expressions are the contract: contraction is off, keep the operation order.
+// EDGES_TOGETHER: all three edge equations loaded first (one round trip) instead of one edge at a time -- with all three in flight the
+// prologue of k_pw_rows<SELF> would need 14 registers more than its pixel loop does (72 instead of 56-58: 7 waves per SIMD instead of 8).  The
+// three dependent round trips this costs are NOT what that prologue's time is made of (EXPERIMENTS.md R4.8: forming the edges from the
+// vertices in one round trip changed nothing).
+template <bool EDGES_TOGETHER>
+HG_HD bool span_cells_lean(const Seg *sg, double y, double y_off, double fW, double flen, int &k, int &fin)
+{
+    double mn = INFINITY, mx = -INFINITY;           // predictXLimits :1172-1197
+    auto edge = [&](const Seg &q) {
+        const double x = q.m == INFINITY ? q.b : (y - q.b) / q.m;
+        const bool use = (y >= q.minY) & (y <= q.maxY) & !(q.m == 0.0);
+        mn = (use & (x < mn)) ? x : mn;
+        mx = (use & (x > mx)) ? x : mx;
+    };
+    if (EDGES_TOGETHER) {
+        const Seg q0 = sg[0], q1 = sg[1], q2 = sg[2];
+        edge(q0); edge(q1); edge(q2);
+    } else {
+#pragma unroll 1
+        for (int e = 0; e < 3; e++) edge(sg[e]);
+    }
+    // the two flat fill() indices :1124 = (y - yOffset) * W + Math.round(x) under TypedArray.fill's index rules: NaN -> 0,
+    // trunc, negative counts from the end, clamp to [0, len] (js_fill_index; maxNum / minNum absorb the NaN)
+    const double base = (y - y_off) * fW;
+    double rk = floor(mn); rk += (mn - rk >= 0.5) ? 1.0 : 0.0;      // Math.round (floor of +-Inf / NaN / |x| >= 2^52 is the value itself)
+    double rf = floor(mx); rf += (mx - rf >= 0.5) ? 1.0 : 0.0;
+    double vk = trunc(base + rk), vf = trunc(base + rf);
+    vk = vk < 0.0 ? flen + vk : vk; vf = vf < 0.0 ? flen + vf : vf;
+    k = (int)fmin(fmax(vk, 0.0), flen); fin = (int)fmin(fmax(vf, 0.0), flen);
+    return k < fin;
+}
+
+// First output row of the non-empty span [k, ...) of source row ys.  Usual case: the span sits in output row (ys - yOff) (+objH when it
+// wrapped); otherwise divide.
+HG_HD int span_first_row(int ys, int y_off, int obj_h, int W, int k)
+{
+    int r = ys - y_off;
+    if (r < 0) r += obj_h;
+    if ((unsigned)r >= (unsigned)obj_h || (unsigned)(k - r * W) >= (unsigned)W) r = k / W;
+    return r;
+}
+
 // Row range of fillTriangle :1113-1120: y from ~~min(y) while y < ceil(max(y)).  y_end is clamped to int range;
 // NaN (no rows) gives y_end = y_min.
 HG_HD void tri_rows(double y0, double y1, double y2, int32_t &y_min, int32_t &y_end)
