@@ -29,9 +29,30 @@ static int check_field_source(hg_ctx *c, int fmt)
     return HG_OK;
 }
 
+// A frame table (a multiple of 8 bytes) to the device: copied into page-locked staging and uploaded stream-ordered, like the frame sets
+// themselves (no GPU wait unless the upload that used the staging slot four calls ago is still queued).
+static int upload_frame_table(hg_ctx *c, void *d_dst, const void *src, size_t bytes)
+{
+    const int slot = (c->field_stage_cur + 1) % 4;
+    hg_ctx::GeoStage &gs = c->field_stage[slot];
+    if (!gs.done) HIP_TRY(c, hipEventCreateWithFlags(&gs.done, hipEventDisableTiming));
+    if (gs.used) HIP_TRY(c, hipEventSynchronize(gs.done));
+    if (bytes > gs.cap) {
+        if (gs.h) { HIP_TRY(c, hipHostFree(gs.h)); gs.h = nullptr; gs.cap = 0; }
+        void *q = nullptr;
+        hipError_t e = hipHostMalloc(&q, bytes + bytes / 4, hipHostMallocDefault);
+        if (e != hipSuccess) return fail(c, HG_ERR_NOMEM, std::string("hipHostMalloc (field frame staging): ") + hipGetErrorString(e));
+        gs.h = static_cast<uint8_t *>(q); gs.cap = bytes + bytes / 4;
+    }
+    c->field_stage_cur = slot;
+    std::memcpy(gs.h, src, bytes);
+    HG_TRY(upload_staged(c, d_dst, gs.h, bytes));
+    HIP_TRY(c, hipEventRecord(gs.done, c->stream)); gs.used = true;
+    return HG_OK;
+}
+
 // The frame records of `frames` with the FIELD offsets in out_off (offs, or packed as hg_pack_field_offsets does), on the host in *recs and on
-// the device in c->d_field_frames: copied into page-locked staging and uploaded stream-ordered, like the frame sets themselves (no GPU wait
-// unless the upload that used the staging slot four calls ago is still queued).
+// the device in c->d_field_frames (upload_frame_table).
 static int stage_field_frames(hg_ctx *c, const std::vector<FrameDesc> &frames, int fmt, const size_t *offs, std::vector<FrameDesc> *recs)
 {
     const size_t F = frames.size(), px = field_px_bytes(fmt);
@@ -45,23 +66,7 @@ static int stage_field_frames(hg_ctx *c, const std::vector<FrameDesc> &frames, i
         off += (bytes + 255) & ~(size_t)255;
     }
     HG_TRY(ensure(c, c->d_field_frames, c->field_frames_cap, F));
-    const int slot = (c->field_stage_cur + 1) % 4;
-    hg_ctx::GeoStage &gs = c->field_stage[slot];
-    const size_t bytes = sizeof(FrameDesc) * F;
-    if (!gs.done) HIP_TRY(c, hipEventCreateWithFlags(&gs.done, hipEventDisableTiming));
-    if (gs.used) HIP_TRY(c, hipEventSynchronize(gs.done));
-    if (bytes > gs.cap) {
-        if (gs.h) { HIP_TRY(c, hipHostFree(gs.h)); gs.h = nullptr; gs.cap = 0; }
-        void *q = nullptr;
-        hipError_t e = hipHostMalloc(&q, bytes + bytes / 4, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(c, HG_ERR_NOMEM, std::string("hipHostMalloc (field frame staging): ") + hipGetErrorString(e));
-        gs.h = static_cast<uint8_t *>(q); gs.cap = bytes + bytes / 4;
-    }
-    c->field_stage_cur = slot;
-    std::memcpy(gs.h, recs->data(), bytes);
-    HG_TRY(upload_staged(c, c->d_field_frames, gs.h, bytes));
-    HIP_TRY(c, hipEventRecord(gs.done, c->stream)); gs.used = true;
-    return HG_OK;
+    return upload_frame_table(c, c->d_field_frames, recs->data(), sizeof(FrameDesc) * F);
 }
 
 // ------------------------------------------------------------------------------------------------ affine / projective
@@ -221,6 +226,140 @@ extern "C" int hg_remap_bilinear_f32_device(hg_ctx *c, const void *d_coords, siz
     if ((reinterpret_cast<uintptr_t>(d_coords) & 7) || (reinterpret_cast<uintptr_t>(d_src) & 3) || (reinterpret_cast<uintptr_t>(d_out) & 3))
         return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_f32_device: d_coords must be aligned to 8 bytes, d_src / d_out to 4");
     launch_remap_bilinear_f32(static_cast<const float *>(d_coords), n_px, d_src, W, H, channels, d_out, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return HG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ remaps of whole frame sets
+extern "C" int hg_pack_plane_offsets(const hg_geom *g, int n, size_t px_bytes, size_t *offsets, size_t *total)
+{
+    if (!g || n < 0 || px_bytes < 1 || !offsets || !total) return fail(nullptr, HG_ERR_INVALID, "hg_pack_plane_offsets: bad arguments");
+    size_t off = 0;
+    for (int i = 0; i < n; i++) {
+        offsets[i] = off;
+        const size_t bytes = (g[i].obj_w > 0 && g[i].obj_h > 0) ? (size_t)g[i].obj_w * (size_t)g[i].obj_h * px_bytes : 0;
+        off += (bytes + 255) & ~(size_t)255;
+    }
+    *total = off;
+    return HG_OK;
+}
+
+static bool misaligned(const void *p, size_t align) { return (reinterpret_cast<uintptr_t>(p) & (align - 1)) != 0; }      // (align: a power of two)
+
+// The frame table of a frames remap: flat lists of obj_w * obj_h pixels, fields of fld_px bytes per pixel at foffs (NULL: packed as
+// hg_pack_field_offsets does), outputs of out_px bytes per pixel at ooffs (NULL: packed as hg_pack_plane_offsets does; else multiples of
+// out_align, a power of two), frame f on plane f % n_planes.  *extent: the bytes the call writes from d_out on.
+static int remap_frame_table(hg_ctx *c, const hg_geom *geoms, int n, size_t fld_px, const size_t *foffs, size_t out_px, size_t out_align,
+                             const size_t *ooffs, int n_planes, std::vector<RemapFrame> *recs, size_t *extent)
+{
+    recs->resize((size_t)n);
+    size_t foff = 0, ooff = 0;
+    *extent = 0;
+    for (int f = 0; f < n; f++) {
+        RemapFrame &r = (*recs)[(size_t)f];
+        r.n_px = (geoms[f].obj_w > 0 && geoms[f].obj_h > 0) ? (uint64_t)geoms[f].obj_w * (uint64_t)geoms[f].obj_h : 0;
+        r.fld_off = foffs ? foffs[f] : foff;
+        r.out_off = ooffs ? ooffs[f] : ooff;
+        r.blk0 = 0; r.plane = (uint32_t)(f % n_planes);
+        if (r.fld_off & (fld_px - 1)) return fail(c, HG_ERR_INVALID, "field offsets must be multiples of the field's pixel size (4 or 8 bytes)");
+        if (r.out_off & (out_align - 1)) return fail(c, HG_ERR_INVALID, "output offsets must be multiples of pixel_bytes (index) or of the element size (bilinear)");
+        foff += ((size_t)r.n_px * fld_px + 255) & ~(size_t)255;
+        ooff += ((size_t)r.n_px * out_px + 255) & ~(size_t)255;
+        if (r.n_px) *extent = std::max(*extent, (size_t)r.out_off + (size_t)r.n_px * out_px);
+    }
+    return HG_OK;
+}
+
+// Blocks of blk_px pixels over the frames, in frame order: blk0 of every record, the grid size.  blk_px starts at base_px (a multiple of 1024)
+// and doubles until the grid fits 2^30 blocks (only sets far beyond any memory get there).
+static void assign_remap_blocks(std::vector<RemapFrame> &recs, uint64_t base_px, uint64_t *blk_px, uint32_t *n_blocks)
+{
+    for (uint64_t px = base_px;; px *= 2) {
+        uint64_t b = 0;
+        for (RemapFrame &r : recs) {
+            r.blk0 = (uint32_t)b;
+            b += (r.n_px + px - 1) / px;
+            if (b > ((uint64_t)1 << 30)) break;
+        }
+        if (b <= ((uint64_t)1 << 30)) { *blk_px = px; *n_blocks = (uint32_t)b; return; }
+    }
+}
+
+// Settle what could still land on the output, then put the table on the device.
+static int stage_remap_frames(hg_ctx *c, const std::vector<RemapFrame> &recs, const void *d_out, size_t extent)
+{
+    if (!c->pw_pending_out.empty() || !c->fwd_pending.empty()) HG_TRY(settle_output_conflicts(c, d_out, extent, 0));
+    HG_TRY(ensure(c, c->d_remap_frames, c->remap_frames_cap, recs.size()));
+    return upload_frame_table(c, c->d_remap_frames, recs.data(), sizeof(RemapFrame) * recs.size());
+}
+
+extern "C" int hg_remap_index_frames_device(hg_ctx *c, const hg_geom *geoms, int n_frames, const void *d_field, const size_t *field_offsets,
+                                            const void *d_planes, size_t n_src_px, int n_planes, size_t plane_stride_bytes, int pixel_bytes,
+                                            void *d_out, const size_t *out_offsets)
+{
+    HG_TRY(bind(c));
+    if (pixel_bytes != 1 && pixel_bytes != 2 && pixel_bytes != 4 && pixel_bytes != 8 && pixel_bytes != 16)
+        return fail(c, HG_ERR_INVALID, "hg_remap_index_frames_device: pixel_bytes must be 1, 2, 4, 8 or 16");
+    if (n_planes < 1) return fail(c, HG_ERR_INVALID, "hg_remap_index_frames_device: n_planes must be >= 1");
+    if (n_frames < 0 || n_frames > 65535) return fail(c, HG_ERR_INVALID, "hg_remap_index_frames_device: n_frames must be 0..65535");
+    if (n_frames == 0) return HG_OK;
+    if (!geoms || !d_field || !d_out || (!d_planes && n_src_px > 0)) return fail(c, HG_ERR_INVALID, "hg_remap_index_frames_device: NULL pointer");
+    const size_t px = (size_t)pixel_bytes;
+    if (misaligned(d_field, 4) || misaligned(d_planes, px) || misaligned(d_out, px) || (plane_stride_bytes & (px - 1)))
+        return fail(c, HG_ERR_INVALID, "hg_remap_index_frames_device: d_planes / d_out / plane_stride_bytes must be aligned to pixel_bytes, d_field to 4 bytes");
+    std::vector<RemapFrame> recs;
+    size_t extent = 0;
+    HG_TRY(remap_frame_table(c, geoms, n_frames, 4, field_offsets, px, px, out_offsets, n_planes, &recs, &extent));
+    if (extent == 0) return HG_OK;                           // (every frame is empty)
+    const bool packed = remap_index_packs(pixel_bytes) && c->opt_remap_pack != 0;      // (option "remap_pack" 0: one pixel per lane, for measurements)
+    uint64_t blk_px = 0; uint32_t n_blocks = 0;
+    assign_remap_blocks(recs, packed ? 4096 : 1024, &blk_px, &n_blocks);
+    HG_TRY(stage_remap_frames(c, recs, d_out, extent));
+    launch_remap_index_frames(c->d_remap_frames, n_frames, n_blocks, blk_px, packed, static_cast<const uint8_t *>(d_field),
+                              static_cast<const uint8_t *>(d_planes), n_src_px, plane_stride_bytes, pixel_bytes, static_cast<uint8_t *>(d_out), c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return HG_OK;
+}
+
+extern "C" int hg_remap_bilinear_frames_device(hg_ctx *c, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
+                                               const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
+                                               void *d_out, const size_t *out_offsets)
+{
+    HG_TRY(bind(c));
+    if (elem != HG_ELEM_F32 && elem != HG_ELEM_U8) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_frames_device: unknown elem (HG_ELEM_F32 or HG_ELEM_U8)");
+    if (channels < 1 || channels > 4 || W < 1 || H < 1) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_frames_device: channels must be 1..4, W and H >= 1");
+    if (n_planes < 1) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_frames_device: n_planes must be >= 1");
+    if (n_frames < 0 || n_frames > 65535) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_frames_device: n_frames must be 0..65535");
+    if (n_frames == 0) return HG_OK;
+    if (!geoms || !d_coords || !d_planes || !d_out) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_frames_device: NULL pointer");
+    const size_t es = elem == HG_ELEM_F32 ? 4 : 1;
+    if (misaligned(d_coords, 8) || misaligned(d_planes, es) || misaligned(d_out, es) || (plane_stride_bytes & (es - 1)))
+        return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_frames_device: d_coords must be aligned to 8 bytes, d_planes / d_out / plane_stride_bytes to the element size");
+    std::vector<RemapFrame> recs;
+    size_t extent = 0;
+    HG_TRY(remap_frame_table(c, geoms, n_frames, 8, field_offsets, es * (size_t)channels, es, out_offsets, n_planes, &recs, &extent));
+    if (extent == 0) return HG_OK;
+    uint64_t blk_px = 0; uint32_t n_blocks = 0;
+    assign_remap_blocks(recs, 1024, &blk_px, &n_blocks);
+    HG_TRY(stage_remap_frames(c, recs, d_out, extent));
+    launch_remap_bilinear_frames(c->d_remap_frames, RemapFrame{}, n_frames, n_blocks, blk_px, static_cast<const uint8_t *>(d_coords),
+                                 static_cast<const uint8_t *>(d_planes), plane_stride_bytes, W, H, elem, channels, static_cast<uint8_t *>(d_out), c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return HG_OK;
+}
+
+extern "C" int hg_remap_bilinear_u8_device(hg_ctx *c, const void *d_coords, size_t n_px, const uint8_t *d_src, int W, int H, int channels, uint8_t *d_out)
+{
+    HG_TRY(bind(c));
+    if (channels < 1 || channels > 4 || W < 1 || H < 1) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_u8_device: channels must be 1..4, W and H >= 1");
+    if (n_px == 0) return HG_OK;
+    if (!d_coords || !d_src || !d_out) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_u8_device: NULL pointer");
+    if (misaligned(d_coords, 8)) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_u8_device: d_coords must be aligned to 8 bytes");
+    std::vector<RemapFrame> one(1);
+    one[0] = RemapFrame{0, 0, (uint64_t)n_px, 0, 0};
+    uint64_t blk_px = 0; uint32_t n_blocks = 0;
+    assign_remap_blocks(one, 1024, &blk_px, &n_blocks);
+    launch_remap_bilinear_frames(nullptr, one[0], 1, n_blocks, blk_px, static_cast<const uint8_t *>(d_coords), d_src, 0, W, H, HG_ELEM_U8, channels, d_out, c->stream);
     HIP_TRY(c, hipGetLastError());
     return HG_OK;
 }

@@ -197,6 +197,8 @@ struct hg_ctx {
     GeoStage field_stage[4];
     int field_stage_cur = -1;
     uint8_t *d_field_tmp = nullptr; size_t field_tmp_cap = 0; // the host-output forms' device copy
+    RemapFrame *d_remap_frames = nullptr; size_t remap_frames_cap = 0;   // the frame table of a frames remap (hg_remap_*_frames_device), staged through field_stage
+    int opt_remap_pack = -1;                                   // k_remap_index_frames: 0 = one pixel per lane even for the pixel sizes that carry the packed form (measurements)
 
     // scratch
     int32_t *d_map32 = nullptr; size_t map32_cap = 0;

@@ -182,6 +182,21 @@ void launch_field_from_map(const PwMesh &mesh, const PwFrames &fr, int f, const 
 // k_remap_index<pixel_bytes>: out[i] = 0 <= field[i] < n_src ? src[field[i]] : 0; k_remap_bilinear_f32<channels>: four clamped taps per pixel.
 void launch_remap_index(const int32_t *field, size_t n, const void *src, size_t n_src, int pixel_bytes, void *out, hipStream_t stream);
 void launch_remap_bilinear_f32(const float *coords, size_t n, const float *src, int W, int H, int channels, float *out, hipStream_t stream);
+// The remaps of a whole frame set in one launch.  A frame is a flat list of n_px pixels: its field at fld_off and its output at out_off
+// (bytes), read from plane `plane`; blocks [blk0, next frame's blk0) of the grid cover it, blk_px pixels each (a multiple of 1024), so the
+// frame of a block is found by a binary search over blk0 -- empty frames own no block.
+struct RemapFrame { uint64_t fld_off, out_off, n_px; uint32_t blk0, plane; };
+// k_remap_index_frames<pixel_bytes, packed>: per pixel k_remap_index.  packed: a lane takes 4 consecutive pixels of its frame -- one 16-byte
+// field load, four gathers, one store of 4 * pixel_bytes -- in frames whose field and output starts are aligned for it, and one pixel per
+// lane elsewhere.  packed is honoured for the pixel sizes remap_index_packs() names; the others always take one pixel per lane.
+bool remap_index_packs(int pixel_bytes);                    // does this build carry the packed form for the pixel size? (those measured to win)
+void launch_remap_index_frames(const RemapFrame *frames, int n_frames, uint32_t n_blocks, uint64_t blk_px, bool packed, const uint8_t *field,
+                               const uint8_t *planes, size_t n_src, size_t plane_stride, int pixel_bytes, uint8_t *out, hipStream_t stream);
+// k_remap_bilinear_frames<element, channels>: per pixel k_remap_bilinear_f32; elem 1 (u8) rounds the blend as blend4 does and stores the
+// channel bytes of a pixel packed.  frames == nullptr: the one frame `one`, by value (blk0 = 0).
+void launch_remap_bilinear_frames(const RemapFrame *frames, const RemapFrame &one, int n_frames, uint32_t n_blocks, uint64_t blk_px,
+                                  const uint8_t *coords, const uint8_t *planes, size_t plane_stride, int W, int H, int elem, int channels,
+                                  uint8_t *out, hipStream_t stream);
 
 // k_geo: _inverseGeometricWarp pixel loop :997-1011 for all frames.  mats = F x 8 doubles (inverse matrices).
 // f32_exact: every affine matrix entry is a float value and |x| < 2^28 (lets the kernel use an exact-product fma).

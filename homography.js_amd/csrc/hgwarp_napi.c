@@ -36,18 +36,20 @@ static napi_value throw_hg(napi_env env, hg_ctx *ctx, const char *what, int code
 /* d_batch: device buffer the frames of warpInversePiecewiseBatch are produced in (kept between calls, grown as needed) */
 /* n_pts / n_tris: the mesh last set, so that point-set and matrix buffers can be checked before the C ABI reads / fills them */
 /* d_imgs: device buffer of the per-frame sources of setImages() (kept, grown as needed) */
+/* d_remap: device scratch of the remap* functions: the field, the plane and the result (kept, grown as needed) */
 /* slab: page-locked memory behind ONE external ArrayBuffer whose views are the frames of a batch (see "batches" below) */
 typedef struct { void *ptr; size_t cap; napi_ref ab; } slab_t;
-typedef struct { hg_ctx *ctx; int obj_w, obj_h; void *d_batch; size_t d_batch_cap; size_t n_pts, n_tris; void *d_imgs; size_t d_imgs_cap; slab_t slab[2]; } handle_t;
+typedef struct { hg_ctx *ctx; int obj_w, obj_h; void *d_batch; size_t d_batch_cap; size_t n_pts, n_tris; void *d_imgs; size_t d_imgs_cap; slab_t slab[2]; void *d_remap; size_t d_remap_cap; } handle_t;
 
 static void release_ctx(handle_t *h)
 {
     if (h->ctx) {
         if (h->d_batch) hg_device_free(h->ctx, h->d_batch);
+        if (h->d_remap) hg_device_free(h->ctx, h->d_remap);
         if (h->d_imgs) hg_device_free(h->ctx, h->d_imgs);      /* (waits for the stream; the context that aliases it goes next) */
         hg_destroy(h->ctx);
     }
-    h->ctx = NULL; h->d_batch = NULL; h->d_batch_cap = 0; h->d_imgs = NULL; h->d_imgs_cap = 0;
+    h->ctx = NULL; h->d_batch = NULL; h->d_batch_cap = 0; h->d_imgs = NULL; h->d_imgs_cap = 0; h->d_remap = NULL; h->d_remap_cap = 0;
 }
 
 static void slab_drop(napi_env env, slab_t *sl, int detach);
@@ -820,6 +822,125 @@ static napi_value fn_field_forward_piecewise(napi_env env, napi_callback_info in
     return r;
 }
 
+/* remapInverseGeometric(<fieldInverseGeometric's arguments>, plane, channels, W, H) / remapInversePiecewise(handle, format, plane, channels, W, H) /
+ * remapForwardGeometric(<fieldForwardGeometric's>, plane, channels, W, H) / remapForwardPiecewise(<fieldForwardPiecewise's>, plane, channels, W, H):
+ * one plane of the W x H source (W * H * channels elements of any TypedArray class) through the field the field* twin would return, on the
+ * device.  The field is computed into device scratch by the _device forms (forward: the _batch_device forms with one frame) and never comes
+ * to the host: the plane goes up, hg_remap_index_device (format 0: pixels are opaque blocks of channels * BYTES_PER_ELEMENT = 1, 2, 4, 8 or 16
+ * bytes) or hg_remap_bilinear_f32_device / _u8_device (format 1: Float32Array / Uint8Array / Uint8ClampedArray, 1..4 channels) runs, and the
+ * result comes down as a TypedArray of the plane's class with objW * objH * channels elements. */
+typedef struct { napi_typedarray_type type; void *data; size_t len, elem; int channels, W, H; void *d_field, *d_plane, *d_out, *out; size_t px; napi_value result; } remap_job;
+
+static int remap_begin(napi_env env, handle_t *h, napi_value *a, int fmt, size_t px, remap_job *j)
+{
+    static const size_t elem_of[] = { 1, 1, 1, 2, 2, 4, 4, 4, 8, 8, 8 };       /* napi_int8_array .. napi_biguint64_array */
+    bool is = false; napi_value ab; size_t off = 0;
+    memset(j, 0, sizeof *j);
+    if (napi_is_typedarray(env, a[0], &is) != napi_ok || !is || napi_get_typedarray_info(env, a[0], &j->type, &j->len, &j->data, &ab, &off) != napi_ok ||
+        (size_t)j->type >= sizeof elem_of / sizeof elem_of[0]) { throw_str(env, "hgwarp: argument 'plane' must be a TypedArray"); return 0; }
+    j->elem = elem_of[j->type];
+    if (!get_i32(env, a[1], &j->channels) || !get_i32(env, a[2], &j->W) || !get_i32(env, a[3], &j->H)) return 0;
+    if (fmt != HG_FIELD_INDEX && fmt != HG_FIELD_COORDS) { throw_str(env, "hgwarp: unknown field format"); return 0; }
+    const size_t pb = (size_t)(j->channels > 0 ? j->channels : 0) * j->elem;
+    if (fmt == HG_FIELD_INDEX ? !(pb == 1 || pb == 2 || pb == 4 || pb == 8 || pb == 16)
+                              : !(j->channels >= 1 && j->channels <= 4 && (j->type == napi_float32_array || j->type == napi_uint8_array || j->type == napi_uint8_clamped_array))) {
+        throw_str(env, "hgwarp: this plane class and channel count cannot be remapped in this format"); return 0;
+    }
+    if (j->W < 1 || j->H < 1 || j->len != (size_t)j->W * (size_t)j->H * (size_t)j->channels) { throw_str(env, "hgwarp: plane must hold W * H * channels elements"); return 0; }
+    j->px = px;
+    j->result = make_typed(env, j->type, px * (size_t)j->channels, j->elem, &j->out);
+    if (!j->result) return 0;
+    if (!px) return 1;
+    const size_t fb = (px * (fmt == HG_FIELD_INDEX ? 4 : 8) + 255) & ~(size_t)255, pl = (j->len * j->elem + 255) & ~(size_t)255, ob = px * pb;
+    if (fb + pl + ob > h->d_remap_cap) {
+        if (h->d_remap) { hg_device_free(h->ctx, h->d_remap); h->d_remap = NULL; h->d_remap_cap = 0; }
+        int rc = hg_device_alloc(h->ctx, fb + pl + ob, &h->d_remap);
+        if (rc != HG_OK) { throw_hg(env, h->ctx, "hg_device_alloc", rc); return 0; }
+        h->d_remap_cap = fb + pl + ob;
+    }
+    j->d_field = h->d_remap; j->d_plane = (uint8_t *)h->d_remap + fb; j->d_out = (uint8_t *)h->d_remap + fb + pl;
+    int rc = hg_copy_to_device(h->ctx, j->d_plane, j->data, j->len * j->elem);
+    if (rc != HG_OK) { throw_hg(env, h->ctx, "hg_copy_to_device", rc); return 0; }
+    return 1;
+}
+
+static napi_value remap_finish(napi_env env, handle_t *h, int fmt, const remap_job *j)
+{
+    if (!j->px) return j->result;
+    const size_t pb = (size_t)j->channels * j->elem;
+    if (fmt == HG_FIELD_INDEX)
+        HG_CALL(h->ctx, "hg_remap_index_device", hg_remap_index_device(h->ctx, j->d_field, j->px, j->d_plane, (size_t)j->W * (size_t)j->H, (int)pb, j->d_out));
+    else if (j->type == napi_float32_array)
+        HG_CALL(h->ctx, "hg_remap_bilinear_f32_device", hg_remap_bilinear_f32_device(h->ctx, j->d_field, j->px, (const float *)j->d_plane, j->W, j->H, j->channels, (float *)j->d_out));
+    else
+        HG_CALL(h->ctx, "hg_remap_bilinear_u8_device", hg_remap_bilinear_u8_device(h->ctx, j->d_field, j->px, (const uint8_t *)j->d_plane, j->W, j->H, j->channels, (uint8_t *)j->d_out));
+    HG_CALL(h->ctx, "hg_copy_to_host", hg_copy_to_host(h->ctx, j->out, j->d_out, j->px * pb));
+    return j->result;
+}
+
+static napi_value fn_remap_inverse_geometric(napi_env env, napi_callback_info info)
+{
+    napi_value a[12];
+    if (!get_args(env, info, 12, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    int kind, fmt; size_t n; hg_geom g; remap_job j;
+    if (!get_i32(env, a[1], &kind)) return NULL;
+    double *m = (double *)get_typed(env, a[2], napi_float64_array, &n, "matrix"); if (!m) return NULL;
+    if (n < (size_t)(kind == HG_AFFINE ? 6 : 8)) return throw_str(env, "hgwarp: matrix too short");
+    if (!get_geom(env, a + 3, &g) || !get_i32(env, a[7], &fmt)) return NULL;
+    const size_t px = (g.obj_w > 0 && g.obj_h > 0) ? (size_t)g.obj_w * g.obj_h : 0;
+    if (!remap_begin(env, h, a + 8, fmt, px, &j)) return NULL;
+    if (px) HG_CALL(h->ctx, "hg_field_inverse_geometric_device", hg_field_inverse_geometric_device(h->ctx, kind, m, g, fmt, j.d_field));
+    return remap_finish(env, h, fmt, &j);
+}
+
+static napi_value fn_remap_inverse_piecewise(napi_env env, napi_callback_info info)
+{
+    napi_value a[6];
+    if (!get_args(env, info, 6, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    int fmt; remap_job j;
+    if (!get_i32(env, a[1], &fmt)) return NULL;
+    const size_t px = (h->obj_w > 0 && h->obj_h > 0) ? (size_t)h->obj_w * h->obj_h : 0, zero = 0;
+    if (!remap_begin(env, h, a + 2, fmt, px, &j)) return NULL;
+    if (px) HG_CALL(h->ctx, "hg_field_inverse_piecewise_frames_device", hg_field_inverse_piecewise_frames_device(h->ctx, fmt, &zero, j.d_field));
+    return remap_finish(env, h, fmt, &j);
+}
+
+static napi_value fn_remap_forward_geometric(napi_env env, napi_callback_info info)
+{
+    napi_value a[11];
+    if (!get_args(env, info, 11, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    int kind; size_t n; hg_geom g; remap_job j;
+    if (!get_i32(env, a[1], &kind)) return NULL;
+    double *m = (double *)get_typed(env, a[2], napi_float64_array, &n, "matrix"); if (!m) return NULL;
+    if (n < (size_t)(kind == HG_AFFINE ? 6 : 8)) return throw_str(env, "hgwarp: matrix too short");
+    if (!get_geom(env, a + 3, &g)) return NULL;
+    double m8[8] = { 0 };
+    for (int k = 0; k < (kind == HG_AFFINE ? 6 : 8); k++) m8[k] = m[k];
+    const size_t px = (g.obj_w > 0 && g.obj_h > 0) ? (size_t)g.obj_w * g.obj_h : 0, zero = 0;
+    if (!remap_begin(env, h, a + 7, HG_FIELD_INDEX, px, &j)) return NULL;
+    if (px) HG_CALL(h->ctx, "hg_field_forward_geometric_batch_device", hg_field_forward_geometric_batch_device(h->ctx, kind, m8, &g, &zero, 1, j.d_field));
+    return remap_finish(env, h, HG_FIELD_INDEX, &j);
+}
+
+static napi_value fn_remap_forward_piecewise(napi_env env, napi_callback_info info)
+{
+    napi_value a[12];
+    if (!get_args(env, info, 12, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    size_t n; int mx, my; hg_geom g; remap_job j;
+    float *dst = (float *)get_typed(env, a[1], napi_float32_array, &n, "dstPoints"); if (!dst) return NULL;
+    if (!get_i32(env, a[2], &mx) || !get_i32(env, a[3], &my)) return NULL;
+    if (!get_geom(env, a + 4, &g)) return NULL;
+    if (h->n_pts == 0 || n < 2 * h->n_pts) return throw_str(env, "hgwarp: dstPoints must hold one x,y pair per mesh point (piecewiseSetMesh first)");
+    const size_t px = (g.obj_w > 0 && g.obj_h > 0) ? (size_t)g.obj_w * g.obj_h : 0, zero = 0;
+    if (!remap_begin(env, h, a + 8, HG_FIELD_INDEX, px, &j)) return NULL;
+    if (px) HG_CALL(h->ctx, "hg_field_forward_piecewise_batch_device", hg_field_forward_piecewise_batch_device(h->ctx, dst, mx, my, &g, &zero, 1, j.d_field));
+    return remap_finish(env, h, HG_FIELD_INDEX, &j);
+}
+
 /* redoneFrames(ctx): frames the fused kernels flagged and hg_sync redid through the map so far (hg_redone_frames; tests) */
 static napi_value fn_redone_frames(napi_env env, napi_callback_info info)
 {
@@ -1386,6 +1507,8 @@ static napi_value init(napi_env env, napi_value exports)
         { "releaseBatch", fn_release_batch }, { "pinnedBuffer", fn_pinned_buffer },
         { "fieldInverseGeometric", fn_field_inverse_geometric }, { "fieldInversePiecewise", fn_field_inverse_piecewise },
         { "fieldForwardGeometric", fn_field_forward_geometric }, { "fieldForwardPiecewise", fn_field_forward_piecewise },
+        { "remapInverseGeometric", fn_remap_inverse_geometric }, { "remapInversePiecewise", fn_remap_inverse_piecewise },
+        { "remapForwardGeometric", fn_remap_forward_geometric }, { "remapForwardPiecewise", fn_remap_forward_piecewise },
         { "solveAffineTriangles", fn_solve_affine_triangles }, { "warpInversePiecewiseState", fn_warp_inverse_piecewise_state },
         { "warpForwardPiecewiseState", fn_warp_forward_piecewise_state },
         { "release", fn_release }, { "setPinnedLimit", fn_set_pinned_limit }, { "poolStats", fn_pool_stats }, { "redoneFrames", fn_redone_frames }, { "setSampling", fn_set_sampling }, { "multiSetSampling", fn_multi_set_sampling }, { "_poolTestFrames", fn_pool_test_frames }, { "poolPressure", fn_pool_pressure }, { "poolCollected", fn_pool_collected },

@@ -22,6 +22,8 @@ HG_AFFINE, HG_PROJECTIVE = 0, 1
 SAMPLE_NEAREST, SAMPLE_BILINEAR = 0, 1
 # formats of the source field of an inverse warp (hg_field_*): int32 pixel index / interleaved float32 (sx, sy) per output pixel
 FIELD_INDEX, FIELD_COORDS = 0, 1
+# element types of the planes of a bilinear remap (hg_remap_bilinear_frames_device)
+ELEM_F32, ELEM_U8 = 0, 1
 
 # every symbol include/hgwarp.h declares (tests check that the built library exports all of them)
 EXPORTS = [
@@ -49,6 +51,7 @@ EXPORTS = [
     "hg_field_inverse_piecewise", "hg_field_inverse_piecewise_frames_device", "hg_remap_index_device", "hg_remap_bilinear_f32_device",
     "hg_field_forward_geometric", "hg_field_forward_geometric_batch_device", "hg_field_forward_piecewise", "hg_field_forward_piecewise_batch_device",
     "hg_last_forward_field_kernel",
+    "hg_pack_plane_offsets", "hg_remap_index_frames_device", "hg_remap_bilinear_frames_device", "hg_remap_bilinear_u8_device",
 ]
 
 
@@ -146,6 +149,10 @@ def lib():
         "hg_last_forward_field_kernel": (i, [vp]),
         "hg_remap_index_device": (i, [vp, vp, sz, vp, sz, i, vp]),
         "hg_remap_bilinear_f32_device": (i, [vp, vp, sz, vp, i, i, i, vp]),
+        "hg_remap_bilinear_u8_device": (i, [vp, vp, sz, vp, i, i, i, vp]),
+        "hg_pack_plane_offsets": (i, [C.POINTER(Geom), i, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "hg_remap_index_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, sz, i, sz, i, vp, C.POINTER(sz)]),
+        "hg_remap_bilinear_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, i, i, i, sz, i, i, vp, C.POINTER(sz)]),
         "hg_warp_inverse_piecewise_state": (i, [vp, f32p, i, C.POINTER(TriMapDef), i, i, Geom, u8p]),
         "hg_warp_forward_piecewise_state": (i, [vp, f32p, i, C.POINTER(TriMapDef), i, i, i, i, Geom, u8p]),
     }
@@ -289,6 +296,15 @@ def pack_field_offsets(geoms, fmt):
     offs = (C.c_size_t * max(len(geoms), 1))()
     total = C.c_size_t(0)
     _check(lib().hg_pack_field_offsets(g, len(geoms), int(fmt), offs, C.byref(total)))
+    return list(offs)[:len(geoms)], total.value
+
+
+def pack_plane_offsets(geoms, px_bytes):
+    """(offsets, total bytes) of the packed OUTPUT layout of a frames remap: 256-byte aligned starts, px_bytes per pixel."""
+    g = _geoms(geoms)
+    offs = (C.c_size_t * max(len(geoms), 1))()
+    total = C.c_size_t(0)
+    _check(lib().hg_pack_plane_offsets(g, len(geoms), int(px_bytes), offs, C.byref(total)))
     return list(offs)[:len(geoms)], total.value
 
 
@@ -620,6 +636,30 @@ class Context:
         """Bilinear gather of 1..4 interleaved float32 channels of a w x h source through a FIELD_COORDS field (asynchronous)."""
         self._c(lib().hg_remap_bilinear_f32_device(self._h, C.c_void_p(int(d_coords)), int(n_px), C.c_void_p(int(d_src)), int(w), int(h), int(channels),
                                                    C.c_void_p(int(d_out))))
+
+    def remap_bilinear_u8_device(self, d_coords, n_px, d_src, w, h, channels, d_out):
+        """The same gather for 1..4 interleaved uint8 channels: the f32 blend, then min(255, floor(v + 0.5)) (asynchronous)."""
+        self._c(lib().hg_remap_bilinear_u8_device(self._h, C.c_void_p(int(d_coords)), int(n_px), C.c_void_p(int(d_src)), int(w), int(h), int(channels),
+                                                  C.c_void_p(int(d_out))))
+
+    def remap_index_frames_device(self, geoms, d_field, d_planes, n_src_px, n_planes, plane_stride_bytes, pixel_bytes, d_out,
+                                  field_offsets=None, out_offsets=None):
+        """remap_index_device for a whole frame set in one launch: frame f is the flat list of obj_w * obj_h pixels of geoms[f] and reads plane
+        f % n_planes.  field_offsets=None: packed as pack_field_offsets does; out_offsets=None: as pack_plane_offsets(geoms, pixel_bytes) does."""
+        fo = (C.c_size_t * len(geoms))(*field_offsets) if field_offsets is not None else None
+        oo = (C.c_size_t * len(geoms))(*out_offsets) if out_offsets is not None else None
+        self._c(lib().hg_remap_index_frames_device(self._h, _geoms(geoms), len(geoms), C.c_void_p(int(d_field)), fo, C.c_void_p(int(d_planes)),
+                                                   int(n_src_px), int(n_planes), int(plane_stride_bytes), int(pixel_bytes), C.c_void_p(int(d_out)), oo))
+
+    def remap_bilinear_frames_device(self, geoms, d_coords, d_planes, w, h, n_planes, plane_stride_bytes, elem, channels, d_out,
+                                     field_offsets=None, out_offsets=None):
+        """remap_bilinear_f32_device (elem ELEM_F32) or remap_bilinear_u8_device (ELEM_U8) for a whole frame set in one launch;
+        out_offsets=None: packed as pack_plane_offsets(geoms, channels * element size) does."""
+        fo = (C.c_size_t * len(geoms))(*field_offsets) if field_offsets is not None else None
+        oo = (C.c_size_t * len(geoms))(*out_offsets) if out_offsets is not None else None
+        self._c(lib().hg_remap_bilinear_frames_device(self._h, _geoms(geoms), len(geoms), C.c_void_p(int(d_coords)), fo, C.c_void_p(int(d_planes)),
+                                                      int(w), int(h), int(n_planes), int(plane_stride_bytes), int(elem), int(channels),
+                                                      C.c_void_p(int(d_out)), oo))
 
     # ---- piecewise
     def piecewise_set_mesh(self, src_pts, tris, min_src_x, min_src_y):

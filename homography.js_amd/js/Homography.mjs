@@ -312,49 +312,96 @@ class Homography {
      */
     sourceField(format = 'index', options = {}) {
         if (format !== 'index' && format !== 'coords') throw ("sourceField: format must be 'index' or 'coords'");
-        const loop = options === null || options === undefined || options.loop === undefined ? 'inverse' : options.loop;
-        if (loop !== 'inverse' && loop !== 'warp' && loop !== 'forward') throw ("sourceField: options.loop must be 'inverse', 'warp' or 'forward'");
-        if (this._image === null) throw ("sourceField() needs an image: call `setImage(img)` or `setSourcePoints(points, img)` first");
         const fmt = format === 'index' ? 0 : 1;
+        const call = this._fieldCall('sourceField', fmt, options);
+        if (call === null) return { data: fmt === 0 ? new Int32Array(0) : new Float32Array(0), width: 0, height: 0 };
+        return { data: this._native['field' + call.entry](this._ctx, ...call.args), width: call.width, height: call.height };
+    }
+
+    /**
+     * One plane that lies beside the picture -- a mask, labels, depth, float features, a second picture -- through the geometry
+     * sourceField() would export for the current state, ON THE DEVICE (not part of the reference): the field is computed into device
+     * memory and never comes to the host; the plane goes up, the library's remap runs, the result comes down.
+     *   plane             a typed array of width * height * channels elements over the instance's image size;
+     *   options.channels  interleaved channels per pixel (default 1);
+     *   options.sampling  'nearest' (default): through the 'index' field; pixels are opaque blocks of channels * BYTES_PER_ELEMENT bytes
+     *                     (1, 2, 4, 8 or 16), any typed array class -- remap(new Uint32Array(image.data.buffer)) IS warp(null, false, true);
+     *                     'bilinear': through the 'coords' field; a Float32Array, Uint8Array or Uint8ClampedArray of 1..4 channels, blended
+     *                     in f32 in the operation order of the bilinear sampling mode; bytes are rounded min(255, floor(v + 0.5)), 4 channels
+     *                     being straight (not premultiplied) RGBA; an uncovered pixel is 0 in every channel;
+     *   options.loop      'inverse' (default), 'warp' or 'forward': sourceField's meaning, refusals and stale-state rules; 'bilinear' with a
+     *                     forward loop throws, as 'coords' does there.
+     * Independent of the instance's sampling mode; records neither a map nor a path.
+     * Returns { data, width, height, channels }, `data` being of the plane's own class; an empty window gives empty data, width and height 0.
+     */
+    remap(plane, options = {}) {
+        if (options === null || options === undefined) options = {};
+        const sampling = options.sampling === undefined ? 'nearest' : options.sampling;
+        if (sampling !== 'nearest' && sampling !== 'bilinear') throw ("remap: options.sampling must be 'nearest' or 'bilinear'");
+        const channels = options.channels === undefined ? 1 : options.channels;
+        if (!ArrayBuffer.isView(plane) || plane instanceof DataView) throw ("remap: plane must be a typed array");
+        if (!Number.isInteger(channels) || channels < 1) throw ("remap: options.channels must be a positive integer");
+        if (sampling === 'bilinear') {
+            if (!(plane instanceof Float32Array || plane instanceof Uint8Array || plane instanceof Uint8ClampedArray))
+                throw ("remap: a 'bilinear' plane must be a Float32Array, Uint8Array or Uint8ClampedArray");
+            if (channels > 4) throw ("remap: a 'bilinear' plane has 1 to 4 channels");
+        } else if (![1, 2, 4, 8, 16].includes(channels * plane.BYTES_PER_ELEMENT)) {
+            throw ("remap: a 'nearest' pixel (channels * BYTES_PER_ELEMENT) must be 1, 2, 4, 8 or 16 bytes");
+        }
+        const fmt = sampling === 'nearest' ? 0 : 1;
+        const call = this._fieldCall('remap', fmt, options);          // (throws without an image)
+        if (plane.length !== this._width * this._height * channels) throw ("remap: plane must hold width * height * channels elements of the instance's image size");
+        if (call === null) return { data: new plane.constructor(0), width: 0, height: 0, channels };
+        const data = this._native['remap' + call.entry](this._ctx, ...call.args, plane, channels, this._width, this._height);
+        return { data, width: call.width, height: call.height, channels };
+    }
+
+    /**
+     * What sourceField() and remap() share: which field entry point of the addon the current state and options.loop lead to, with its
+     * arguments after the context -- { entry, args, width, height }; the addon's functions are 'field' + entry and 'remap' + entry -- after
+     * the refusals, the solves and the uploads that field needs.  null: the window is empty.  fmt: 0 = index, 1 = coords.
+     */
+    _fieldCall(who, fmt, options) {
+        const loop = options === null || options === undefined || options.loop === undefined ? 'inverse' : options.loop;
+        if (loop !== 'inverse' && loop !== 'warp' && loop !== 'forward') throw (who + ": options.loop must be 'inverse', 'warp' or 'forward'");
+        if (this._image === null) throw (who + "() needs an image: call `setImage(img)` or `setSourcePoints(points, img)` first");
         const [xo, yo, ow, oh] = this._window();
-        const empty = () => ({ data: fmt === 0 ? new Int32Array(0) : new Float32Array(0), width: 0, height: 0 });
-        let data;
+        let entry, args;
         if (loop === 'forward' || (loop === 'warp' && this._dispatchesForward())) {
-            if (fmt !== 0) throw ("sourceField: a forward loop has an 'index' field only (it copies whole pixels from integer positions)");
+            if (fmt !== 0) throw (who === 'remap' ? "remap: a forward loop remaps 'nearest' only (it copies whole pixels from integer positions)"
+                                                  : "sourceField: a forward loop has an 'index' field only (it copies whole pixels from integer positions)");
             if (this.transform === 'piecewiseaffine') {
                 if (!(this.repairStaleMap || (this._mapIsCurrentForward() && this._matricesAreCurrent())))
-                    throw ("sourceField: the forward loop would read a stale map or matrices of an older point set (call setSourcePoints / setDestinyPoints first)");
-                if (!(ow * oh >= 1)) return empty();
+                    throw (who + ": the forward loop would read a stale map or matrices of an older point set (call setSourcePoints / setDestinyPoints first)");
+                if (!(ow * oh >= 1)) return null;
                 checkedMapLength(ow * oh);
                 this._uploadImage();
                 this._uploadMesh();
-                data = this._native.fieldForwardPiecewise(this._ctx, asF32(this._dstPoints), this._maxSrcX, this._maxSrcY, xo, yo, ow, oh);
+                entry = 'ForwardPiecewise'; args = [asF32(this._dstPoints), this._maxSrcX, this._maxSrcY, xo, yo, ow, oh];
             } else {
-                if (!(ow * oh >= 1)) return empty();
+                if (!(ow * oh >= 1)) return null;
                 checkedMapLength(ow * oh);
                 this._uploadImage();
-                data = this._native.fieldForwardGeometric(this._ctx, this.transform === 'affine' ? AFFINE : PROJECTIVE, Float64Array.from(this._transformMatrix), xo, yo, ow, oh);
+                entry = 'ForwardGeometric'; args = [this.transform === 'affine' ? AFFINE : PROJECTIVE, Float64Array.from(this._transformMatrix), xo, yo, ow, oh];
             }
-            return { data, width: ow, height: oh };
-        }
-        if (this.transform === 'piecewiseaffine') {
+        } else if (this.transform === 'piecewiseaffine') {
             if (!(this.repairStaleMap || this._matricesAreCurrent()))
-                throw ("sourceField: the piecewise matrices belong to an older point set (call setDestinyPoints first)");
-            if (!(ow * oh >= 1)) return empty();
+                throw (who + ": the piecewise matrices belong to an older point set (call setDestinyPoints first)");
+            if (!(ow * oh >= 1)) return null;
             checkedMapLength(ow * oh);
             this._uploadImage();
             this._uploadMesh();
             this._native.piecewisePrepare(this._ctx, asF32(this._dstPoints), xo, yo, ow, oh);
-            data = this._native.fieldInversePiecewise(this._ctx, fmt);
+            entry = 'InversePiecewise'; args = [fmt];
         } else {
             this._alignRanges();
             const inv = this._solve(this._dstPoints, this._srcPoints);
-            if (!(ow * oh >= 1)) return empty();
+            if (!(ow * oh >= 1)) return null;
             checkedMapLength(ow * oh);
             this._uploadImage();
-            data = this._native.fieldInverseGeometric(this._ctx, this.transform === 'affine' ? AFFINE : PROJECTIVE, Float64Array.from(inv), xo, yo, ow, oh, fmt);
+            entry = 'InverseGeometric'; args = [this.transform === 'affine' ? AFFINE : PROJECTIVE, Float64Array.from(inv), xo, yo, ow, oh, fmt];
         }
-        return { data, width: ow, height: oh };
+        return { entry, args, width: ow, height: oh };
     }
 
     /**

@@ -55,6 +55,8 @@ enum { HG_SAMPLE_NEAREST = 0, HG_SAMPLE_BILINEAR = 1 };
 /* Formats of the SOURCE FIELD of an inverse warp (hg_field_*): for every output pixel, which source pixel the nearest loop reads
  * (HG_FIELD_INDEX, one int32) or where it looks (HG_FIELD_COORDS, two float32).  Not part of the reference. */
 enum { HG_FIELD_INDEX = 0, HG_FIELD_COORDS = 1 };
+/* Element types of the planes a bilinear remap reads and writes (hg_remap_bilinear_frames_device). */
+enum { HG_ELEM_F32 = 0, HG_ELEM_U8 = 1 };
 
 typedef struct hg_ctx hg_ctx;
 
@@ -312,6 +314,43 @@ int hg_remap_index_device(hg_ctx *ctx, const void *d_field, size_t n_px, const v
  *     v = (p00*(1-fx) + p01*fx)*(1-fy) + (p10*(1-fx) + p11*fx)*fy,
  * stored as it is (no rounding, no clamping): the operation order of the bilinear sampling mode, so a float32 model matches bit for bit. */
 int hg_remap_bilinear_f32_device(hg_ctx *ctx, const void *d_coords, size_t n_px, const float *d_src, int W, int H, int channels, float *d_out);
+/* The same gather for 8-bit planes (a matte, a grey image, straight -- not premultiplied -- RGBA): taps and fractions are those of the f32
+ * form, all in f32; each channel's four taps are converted to float and blended in the same operation order, contraction off, then
+ *     out = (uint8)min(255, floor(v + 0.5f))          (the rounding of the bilinear sampling mode's blend4)
+ * A NaN or infinite coordinate gives 0 in every channel.  d_coords is aligned to 8 bytes, d_src and d_out to nothing.  Asynchronous. */
+int hg_remap_bilinear_u8_device(hg_ctx *ctx, const void *d_coords, size_t n_px, const uint8_t *d_src, int W, int H, int channels, uint8_t *d_out);
+/* The remaps for a WHOLE FRAME SET in one launch: what a loop of n_frames single-list calls over the fields of a *_frames_device /
+ * *_batch_device field call would do.  The geoms are passed explicitly and no staged frame set is consulted -- a forward field or a
+ * caller-made one is as legal as an inverse one -- and only obj_w and obj_h of each are read: frame f is a flat list of obj_w * obj_h
+ * pixels; a frame with obj_w <= 0 or obj_h <= 0 is empty and writes nothing.
+ *   field_offsets  where frame f's field starts in d_field / d_coords, in bytes.  NULL: packed as hg_pack_field_offsets does for the format
+ *                  the call reads; otherwise multiples of 4 (index) or 8 (coords).
+ *   out_offsets    where frame f's output starts in d_out, in bytes.  NULL: packed as hg_pack_plane_offsets does with px_bytes =
+ *                  pixel_bytes (index) or channels * element size (bilinear: 4 for HG_ELEM_F32, 1 for HG_ELEM_U8); otherwise multiples
+ *                  of pixel_bytes resp. of the element size.
+ *   planes         frame f reads plane f % n_planes (n_planes >= 1) at d_planes + (f % n_planes) * plane_stride_bytes: the rule
+ *                  hg_set_images_device gives images.  plane_stride_bytes is a multiple of pixel_bytes resp. the element size; d_planes
+ *                  and d_out are aligned as the single forms demand.
+ * Per pixel the index form is exactly hg_remap_index_device with n_src_px pixels per plane -- no read leaves that plane's [0, n_src_px),
+ * whatever the field holds --, the bilinear form exactly hg_remap_bilinear_f32_device (elem HG_ELEM_F32) or hg_remap_bilinear_u8_device
+ * (HG_ELEM_U8), bit for bit.  Bytes between frames are never written.  n_frames == 0: HG_OK, nothing happens.
+ * HG_ERR_INVALID: n_frames negative or above 65535; NULL pointers with n_frames > 0; an unknown elem; channels outside 1..4; pixel_bytes
+ * not 1, 2, 4, 8 or 16; W or H below 1; n_planes below 1; a misaligned pointer, offset or stride.
+ * Asynchronous on the ctx stream: geoms and offsets are copied before the call returns, the frame table goes up through page-locked staging,
+ * stream-ordered; no GPU wait in the steady state.  Before launching, queued runs whose deferred redo could land on the bytes the call
+ * writes in d_out are settled, as the field calls do.  Source planes that are themselves outputs of queued warps are the caller's to settle
+ * (hg_sync) -- the contract of the single remaps, which settle nothing.  Like the field calls, none of the remaps touches hg_last_*_kernel,
+ * the sampling mode or the layout state. */
+/* Host only: offsets[i] = start of frame i's OUTPUT plane (256-byte aligned), *total = bytes needed; px_bytes = bytes per output pixel (>= 1). */
+int hg_pack_plane_offsets(const hg_geom *geoms, int n_frames, size_t px_bytes, size_t *offsets, size_t *total);
+int hg_remap_index_frames_device(hg_ctx *ctx, const hg_geom *geoms, int n_frames,
+                                 const void *d_field, const size_t *field_offsets,
+                                 const void *d_planes, size_t n_src_px, int n_planes, size_t plane_stride_bytes,
+                                 int pixel_bytes, void *d_out, const size_t *out_offsets);
+int hg_remap_bilinear_frames_device(hg_ctx *ctx, const hg_geom *geoms, int n_frames,
+                                    const void *d_coords, const size_t *field_offsets,
+                                    const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes,
+                                    int elem, int channels, void *d_out, const size_t *out_offsets);
 /* The source field of the FORWARD warps (next section): what hg_warp_forward_* would paint, as geometry.  HG_FIELD_INDEX only, hence no
  * format argument: the forward loops copy whole pixels from integer positions, (s % W, s / W) IS the coordinate.  One int32 per output pixel
  * p, row-major obj_w x obj_h: let w be the LAST writer, in the loop's raster order (:919-930 over y < H, x < W; :955-969 over the cells of
@@ -539,7 +578,9 @@ long hg_layout_walks(hg_ctx *ctx);
  *           estimate says a tile row holds its spans; 1 = whenever k_pw_patch<SELF> would run; 0 never): k_pw_tile instead of k_pw_patch -- 8 x 2048-pixel tiles, gathers in 8-pixel runs along the source
  *           rows; a tile beyond its limits (96 spans per row and tile, 128 triangle pieces) flags its frame, hg_sync
  *           redoes it and the mesh goes back to k_pw_patch;
- *   "fwd_tiles": see hg_last_forward_kernel.
+ *   "fwd_tiles": see hg_last_forward_kernel;
+ *   "remap_pack" (default -1 = on): hg_remap_index_frames_device gives a lane 4 consecutive 1-byte pixels and one packed store (the
+ *           only pixel size for which that was measured to win); 0: one pixel per lane, for measurements.
  * Unknown keys are refused (HG_ERR_INVALID). */
 int hg_set_option(hg_ctx *ctx, const char *key, int value);
 /* Number of XCCs the ctx maps row bands to (what hg_create read from the device, or the "xcc" option). */
