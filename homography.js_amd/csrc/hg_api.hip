@@ -60,24 +60,13 @@ extern "C" void hg_destroy(hg_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream || !c->own_stream) (void)hipStreamSynchronize(c->stream);
-    if (c->d_img && !c->img_aliased) (void)hipFree(c->d_img);
-    void *ptrs[] = { c->d_src, c->d_tris, c->d_set, c->d_trir, c->d_trix, c->d_segs, c->d_fwd, c->d_inv, c->d_status, c->d_two_round, c->d_rowcnt, c->d_rowent, c->d_bands,
-                     c->d_geo_frames, c->d_mats, c->d_geo_pts, c->d_geo_plain, c->d_map32, c->d_fmap, c->d_win32, c->d_fwd_par, c->d_fbbox, c->d_frowoff, c->d_frowext, c->d_ftile_cnt, c->d_fwd_status, c->d_ftile_ent, c->d_map16, c->d_out_tmp, c->d_field_frames, c->d_field_tmp, c->d_ffield_status, c->d_remap_frames };
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (c->h_status) (void)hipHostFree(c->h_status);
-    if (c->h_flag) (void)hipHostFree(c->h_flag);
-    for (hg_ctx::Stage &st : c->stage) { if (st.h) (void)hipHostFree(st.h); if (st.done) (void)hipEventDestroy(st.done); }
-    for (hg_ctx::GeoStage &gs : c->geo_stage) { if (gs.h) (void)hipHostFree(gs.h); if (gs.done) (void)hipEventDestroy(gs.done); }
-    for (hg_ctx::GeoStage &gs : c->field_stage) { if (gs.h) (void)hipHostFree(gs.h); if (gs.done) (void)hipEventDestroy(gs.done); }
-    { void *rp[] = { c->d_redo_frame, c->d_redo_dst, c->d_redo_src, c->d_redo_min, c->d_redo_trir, c->d_redo_trix, c->d_redo_segs, c->d_redo_fwd, c->d_redo_inv, c->d_redo_status, c->d_st_pts, c->d_st_tris, c->d_st_mats };
-      for (void *q : rp) if (q) (void)hipFree(q); }
     for (int i = 0; i < hg_ctx::kEvRing; i++) { if (c->ev0[i]) (void)hipEventDestroy(c->ev0[i]); if (c->ev1[i]) (void)hipEventDestroy(c->ev1[i]); }
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
     if (c->copy_event) (void)hipEventDestroy(c->copy_event);
     if (c->down_stream) { (void)hipStreamSynchronize(c->down_stream); (void)hipStreamDestroy(c->down_stream); }
     if (c->down_event) (void)hipEventDestroy(c->down_event);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                            // (buffers, staging rings and pinned blocks free themselves: hg_mem.h)
 }
 
 extern "C" const char *hg_last_error(const hg_ctx *c) { return c ? c->err.c_str() : g_err.c_str(); }
@@ -385,13 +374,7 @@ extern "C" int hg_minmax_xy(const float *p, int n, double out[4])
 extern "C" int hg_pack_offsets(const hg_geom *g, int n, size_t *offsets, size_t *total)
 {
     if ((!g && n > 0) || n < 0) return fail(nullptr, HG_ERR_INVALID, "bad arguments");
-    size_t off = 0;
-    for (int i = 0; i < n; i++) {
-        if (offsets) offsets[i] = off;
-        const size_t bytes = (g[i].obj_w > 0 && g[i].obj_h > 0) ? (size_t)g[i].obj_w * (size_t)g[i].obj_h * 4 : 0;
-        off += (bytes + 255) & ~(size_t)255;
-    }
-    if (total) *total = off;
+    pack_offsets(g, n, 4, offsets, total);
     return HG_OK;
 }
 
@@ -402,8 +385,7 @@ extern "C" int hg_set_image(hg_ctx *c, const uint8_t *rgba, int w, int h)
     if (!rgba || w <= 0 || h <= 0) return fail(c, HG_ERR_INVALID, "hg_set_image: bad image");
     HG_TRY(hg_sync(c));                                 // settle queued runs before their source is replaced
     const size_t bytes = (size_t)w * h * 4;
-    if (c->img_aliased) { c->d_img = nullptr; c->img_cap = 0; c->img_aliased = false; }
-    HG_TRY(ensure(c, c->d_img, c->img_cap, bytes));
+    HG_TRY(ensure(c, c->d_img, bytes));                 // (a borrowed image is dropped, not freed)
     HIP_TRY(c, hipMemcpyAsync(c->d_img, rgba, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));       // caller memory is not retained after return
     c->W = w; c->H = h; c->n_imgs = 1; c->img_stride = 0;
@@ -415,9 +397,8 @@ extern "C" int hg_set_image_device(hg_ctx *c, const void *d_rgba, int w, int h)
     HG_TRY(bind(c));
     if (!d_rgba || w <= 0 || h <= 0) return fail(c, HG_ERR_INVALID, "hg_set_image_device: bad image");
     HG_TRY(hg_sync(c));
-    if (c->d_img && !c->img_aliased) { HIP_TRY(c, hipStreamSynchronize(c->stream)); HIP_TRY(c, hipFree(c->d_img)); }
-    c->d_img = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_rgba));
-    c->img_cap = 0; c->img_aliased = true;
+    if (c->d_img.cap) HIP_TRY(c, hipStreamSynchronize(c->stream));     // (an image of the context's own goes)
+    c->d_img.borrow(const_cast<uint8_t *>(static_cast<const uint8_t *>(d_rgba)));
     c->W = w; c->H = h; c->n_imgs = 1; c->img_stride = 0;
     return HG_OK;
 }
@@ -464,7 +445,7 @@ int fill_frames(hg_ctx *c, std::vector<FrameDesc> &v, const hg_geom *geoms, cons
     for (int i = 0; i < n; i++) {
         FrameDesc &d = v[i];
         d.x_off = geoms[i].x_off; d.y_off = geoms[i].y_off; d.obj_w = geoms[i].obj_w; d.obj_h = geoms[i].obj_h;
-        const size_t px = (d.obj_w > 0 && d.obj_h > 0) ? (size_t)d.obj_w * (size_t)d.obj_h : 0;
+        const size_t px = frame_px(d.obj_w, d.obj_h);
         if (px > ((size_t)1 << 31)) return fail(c, HG_ERR_INVALID, "frame larger than 2^31 pixels");
         // pixel coordinates x = xOff + column stay exact integers in every kernel (int32 sums, f32-matrix * x products in fp64)
         if (std::abs((int64_t)d.x_off) > (1 << 26) || std::abs((int64_t)d.y_off) > (1 << 26))
@@ -472,7 +453,7 @@ int fill_frames(hg_ctx *c, std::vector<FrameDesc> &v, const hg_geom *geoms, cons
         d.out_off = offs ? offs[i] : off;
         if (d.out_off & 3) return fail(c, HG_ERR_INVALID, "output offsets must be multiples of 4 bytes");
         d.map_off = moff;
-        off += (px * 4 + 255) & ~(size_t)255;
+        off += pad256(px * 4);
         moff += px;
     }
     return HG_OK;

@@ -9,13 +9,7 @@ static size_t field_px_bytes(int fmt) { return fmt == HG_FIELD_INDEX ? 4 : 8; }
 extern "C" int hg_pack_field_offsets(const hg_geom *g, int n, int fmt, size_t *offsets, size_t *total)
 {
     if (!g || n < 0 || !field_fmt_ok(fmt) || !offsets || !total) return fail(nullptr, HG_ERR_INVALID, "hg_pack_field_offsets: bad arguments");
-    size_t off = 0;
-    for (int i = 0; i < n; i++) {
-        offsets[i] = off;
-        const size_t bytes = (g[i].obj_w > 0 && g[i].obj_h > 0) ? (size_t)g[i].obj_w * (size_t)g[i].obj_h * field_px_bytes(fmt) : 0;
-        off += (bytes + 255) & ~(size_t)255;
-    }
-    *total = off;
+    pack_offsets(g, n, field_px_bytes(fmt), offsets, total);
     return HG_OK;
 }
 
@@ -33,22 +27,11 @@ static int check_field_source(hg_ctx *c, int fmt)
 // themselves (no GPU wait unless the upload that used the staging slot four calls ago is still queued).
 static int upload_frame_table(hg_ctx *c, void *d_dst, const void *src, size_t bytes)
 {
-    const int slot = (c->field_stage_cur + 1) % 4;
-    hg_ctx::GeoStage &gs = c->field_stage[slot];
-    if (!gs.done) HIP_TRY(c, hipEventCreateWithFlags(&gs.done, hipEventDisableTiming));
-    if (gs.used) HIP_TRY(c, hipEventSynchronize(gs.done));
-    if (bytes > gs.cap) {
-        if (gs.h) { HIP_TRY(c, hipHostFree(gs.h)); gs.h = nullptr; gs.cap = 0; }
-        void *q = nullptr;
-        hipError_t e = hipHostMalloc(&q, bytes + bytes / 4, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(c, HG_ERR_NOMEM, std::string("hipHostMalloc (field frame staging): ") + hipGetErrorString(e));
-        gs.h = static_cast<uint8_t *>(q); gs.cap = bytes + bytes / 4;
-    }
-    c->field_stage_cur = slot;
-    std::memcpy(gs.h, src, bytes);
-    HG_TRY(upload_staged(c, d_dst, gs.h, bytes));
-    HIP_TRY(c, hipEventRecord(gs.done, c->stream)); gs.used = true;
-    return HG_OK;
+    StageSlot *gs = nullptr;
+    HG_TRY(c->field_stage.acquire(c, bytes, "field frame staging", &gs));
+    std::memcpy(gs->h, src, bytes);
+    HG_TRY(upload_staged(c, d_dst, gs->h, bytes));
+    return c->field_stage.commit(c, gs);
 }
 
 // The frame records of `frames` with the FIELD offsets in out_off (offs, or packed as hg_pack_field_offsets does), on the host in *recs and on
@@ -62,10 +45,9 @@ static int stage_field_frames(hg_ctx *c, const std::vector<FrameDesc> &frames, i
         FrameDesc &d = (*recs)[f];
         d.out_off = offs ? offs[f] : off;
         if (d.out_off & (px - 1)) return fail(c, HG_ERR_INVALID, "field offsets must be multiples of the field's pixel size (4 or 8 bytes)");
-        const size_t bytes = (d.obj_w > 0 && d.obj_h > 0) ? (size_t)d.obj_w * (size_t)d.obj_h * px : 0;
-        off += (bytes + 255) & ~(size_t)255;
+        off += pad256(frame_px(d.obj_w, d.obj_h) * px);
     }
-    HG_TRY(ensure(c, c->d_field_frames, c->field_frames_cap, F));
+    HG_TRY(ensure(c, c->d_field_frames, F));
     return upload_frame_table(c, c->d_field_frames, recs->data(), sizeof(FrameDesc) * F);
 }
 
@@ -76,7 +58,7 @@ static int settle_field_conflicts(hg_ctx *c, const void *d_field, const std::vec
     if (c->pw_pending_out.empty() && c->fwd_pending.empty()) return HG_OK;
     size_t extent = 0;
     for (const FrameDesc &d : recs)
-        if (d.obj_w > 0 && d.obj_h > 0) extent = std::max(extent, (size_t)d.out_off + (size_t)d.obj_w * (size_t)d.obj_h * field_px_bytes(fmt));
+        if (frame_px(d.obj_w, d.obj_h)) extent = std::max(extent, (size_t)d.out_off + frame_px(d.obj_w, d.obj_h) * field_px_bytes(fmt));
     return settle_output_conflicts(c, d_field, extent, 0);
 }
 
@@ -105,8 +87,8 @@ extern "C" int hg_field_inverse_geometric(hg_ctx *c, int kind, const double *m, 
     HG_TRY(bind(c));
     if (!out_host) return fail(c, HG_ERR_INVALID, "out is NULL");
     if (!field_fmt_ok(fmt)) return fail(c, HG_ERR_INVALID, "unknown field format (HG_FIELD_INDEX or HG_FIELD_COORDS)");
-    const size_t bytes = (geom.obj_w > 0 && geom.obj_h > 0) ? (size_t)geom.obj_w * geom.obj_h * field_px_bytes(fmt) : 0;
-    HG_TRY(ensure(c, c->d_field_tmp, c->field_tmp_cap, std::max(bytes, (size_t)8)));
+    const size_t bytes = frame_px(geom.obj_w, geom.obj_h) * field_px_bytes(fmt);
+    HG_TRY(ensure(c, c->d_field_tmp, std::max(bytes, (size_t)8)));
     HG_TRY(hg_field_inverse_geometric_device(c, kind, m, geom, fmt, c->d_field_tmp));
     if (bytes == 0) return HG_OK;
     HIP_TRY(c, hipMemcpyAsync(out_host, c->d_field_tmp, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -155,25 +137,25 @@ extern "C" int hg_field_inverse_piecewise_frames_device(hg_ctx *c, int fmt, cons
     PwMesh mesh = mesh_of(c);
     PwFrames fr = frames_of(c);
     fr.frames = c->d_field_frames;                           // the same windows, field offsets
-    fr.status = c->d_status; fr.host_flag = nullptr;         // a status set of this call's own, read right below
+    fr.status = c->solve.status; fr.host_flag = nullptr;         // a status set of this call's own, read right below
     fr.two_round = nullptr;                                  // (outside the frame set's step numbering, like the deferred redo)
     fr.self_spans = 0; fr.band_ent = nullptr; fr.band_cnt = nullptr; fr.n_bands = 0;     // k_tri_setup without candidate bands
     uint8_t *field = static_cast<uint8_t *>(d_field);
-    HIP_TRY(c, hipMemsetAsync(c->d_status, 0, sizeof(int32_t) * F, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->solve.status, 0, sizeof(int32_t) * F, c->stream));
     launch_tri_setup(mesh, fr, c->stream);
     HG_TRY(time_begin(c));
     launch_pw_field(mesh, fr, fmt, field, c->stream);
     HG_TRY(time_end(c));
     HIP_TRY(c, hipGetLastError());
     std::vector<int32_t> status(F);
-    HIP_TRY(c, hipMemcpyAsync(status.data(), c->d_status, sizeof(int32_t) * F, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(status.data(), c->solve.status, sizeof(int32_t) * F, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     bool redone = false;
     for (size_t f = 0; f < F; f++) {
         if (status[f] == FRAME_OK) continue;
         const FrameDesc &fd = recs[f];
         if (fd.obj_w <= 0 || fd.obj_h <= 0) continue;
-        HG_TRY(ensure(c, c->d_map32, c->map32_cap, (size_t)fd.obj_w * fd.obj_h));
+        HG_TRY(ensure(c, c->d_map32, (size_t)fd.obj_w * fd.obj_h));
         launch_map_build(mesh, fr, (int)f, fd, c->d_map32, c->stream);      // (k_tri_setup's edge equations and row ranges of frame f)
         launch_field_from_map(mesh, fr, (int)f, fd, c->d_map32, fmt, field, c->stream);
         HIP_TRY(c, hipGetLastError());
@@ -192,8 +174,8 @@ extern "C" int hg_field_inverse_piecewise(hg_ctx *c, int fmt, void *out_host)
     HG_TRY(check_pw_state(c));
     if (c->pw_frames.size() != 1) return fail(c, HG_ERR_STATE, "this call needs exactly one prepared frame (hg_piecewise_prepare)");
     const FrameDesc &fd = c->pw_frames[0];
-    const size_t bytes = (fd.obj_w > 0 && fd.obj_h > 0) ? (size_t)fd.obj_w * fd.obj_h * field_px_bytes(fmt) : 0;
-    HG_TRY(ensure(c, c->d_field_tmp, c->field_tmp_cap, std::max(bytes, (size_t)8)));
+    const size_t bytes = frame_px(fd.obj_w, fd.obj_h) * field_px_bytes(fmt);
+    HG_TRY(ensure(c, c->d_field_tmp, std::max(bytes, (size_t)8)));
     const size_t zero = 0;
     HG_TRY(hg_field_inverse_piecewise_frames_device(c, fmt, &zero, c->d_field_tmp));
     if (bytes == 0) return HG_OK;
@@ -234,13 +216,7 @@ extern "C" int hg_remap_bilinear_f32_device(hg_ctx *c, const void *d_coords, siz
 extern "C" int hg_pack_plane_offsets(const hg_geom *g, int n, size_t px_bytes, size_t *offsets, size_t *total)
 {
     if (!g || n < 0 || px_bytes < 1 || !offsets || !total) return fail(nullptr, HG_ERR_INVALID, "hg_pack_plane_offsets: bad arguments");
-    size_t off = 0;
-    for (int i = 0; i < n; i++) {
-        offsets[i] = off;
-        const size_t bytes = (g[i].obj_w > 0 && g[i].obj_h > 0) ? (size_t)g[i].obj_w * (size_t)g[i].obj_h * px_bytes : 0;
-        off += (bytes + 255) & ~(size_t)255;
-    }
-    *total = off;
+    pack_offsets(g, n, px_bytes, offsets, total);
     return HG_OK;
 }
 
@@ -257,14 +233,14 @@ static int remap_frame_table(hg_ctx *c, const hg_geom *geoms, int n, size_t fld_
     *extent = 0;
     for (int f = 0; f < n; f++) {
         RemapFrame &r = (*recs)[(size_t)f];
-        r.n_px = (geoms[f].obj_w > 0 && geoms[f].obj_h > 0) ? (uint64_t)geoms[f].obj_w * (uint64_t)geoms[f].obj_h : 0;
+        r.n_px = frame_px(geoms[f].obj_w, geoms[f].obj_h);
         r.fld_off = foffs ? foffs[f] : foff;
         r.out_off = ooffs ? ooffs[f] : ooff;
         r.blk0 = 0; r.plane = (uint32_t)(f % n_planes);
         if (r.fld_off & (fld_px - 1)) return fail(c, HG_ERR_INVALID, "field offsets must be multiples of the field's pixel size (4 or 8 bytes)");
         if (r.out_off & (out_align - 1)) return fail(c, HG_ERR_INVALID, "output offsets must be multiples of pixel_bytes (index) or of the element size (bilinear)");
-        foff += ((size_t)r.n_px * fld_px + 255) & ~(size_t)255;
-        ooff += ((size_t)r.n_px * out_px + 255) & ~(size_t)255;
+        foff += pad256((size_t)r.n_px * fld_px);
+        ooff += pad256((size_t)r.n_px * out_px);
         if (r.n_px) *extent = std::max(*extent, (size_t)r.out_off + (size_t)r.n_px * out_px);
     }
     return HG_OK;
@@ -289,7 +265,7 @@ static void assign_remap_blocks(std::vector<RemapFrame> &recs, uint64_t base_px,
 static int stage_remap_frames(hg_ctx *c, const std::vector<RemapFrame> &recs, const void *d_out, size_t extent)
 {
     if (!c->pw_pending_out.empty() || !c->fwd_pending.empty()) HG_TRY(settle_output_conflicts(c, d_out, extent, 0));
-    HG_TRY(ensure(c, c->d_remap_frames, c->remap_frames_cap, recs.size()));
+    HG_TRY(ensure(c, c->d_remap_frames, recs.size()));
     return upload_frame_table(c, c->d_remap_frames, recs.data(), sizeof(RemapFrame) * recs.size());
 }
 

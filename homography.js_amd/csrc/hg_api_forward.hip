@@ -83,7 +83,7 @@ static int forward_geometric_batch(hg_ctx *c, int kind, const double *m, const h
     std::vector<FrameDesc> fds;
     HG_TRY(fill_frames(c, fds, geoms, offs, n));
     size_t max_px = 0;
-    for (const FrameDesc &fd : fds) if (fd.obj_w > 0 && fd.obj_h > 0) max_px = std::max(max_px, (size_t)fd.obj_w * fd.obj_h);
+    for (const FrameDesc &fd : fds) max_px = std::max(max_px, frame_px(fd.obj_w, fd.obj_h));
     if (max_px == 0) return HG_OK;
     HG_TRY(hg_sync(c));
     // Tile-binned gather (k_fwd_tiles, all frames in one launch) when every frame is admissible and the windows are large
@@ -107,13 +107,13 @@ static int forward_geometric_batch(hg_ctx *c, int kind, const double *m, const h
             if (n == 1) { batch.p0 = par[0]; batch.f0 = fds[0]; }
             else {
                 const size_t bytes = sizeof(FwdParam) * n + sizeof(FrameDesc) * n;
-                HG_TRY(ensure(c, c->d_fwd_par, c->fwd_par_cap, bytes));
+                HG_TRY(ensure(c, c->d_fwd_par, bytes));
                 std::vector<uint8_t> blob(bytes);
                 std::memcpy(blob.data(), par.data(), sizeof(FwdParam) * n);
                 std::memcpy(blob.data() + sizeof(FwdParam) * n, fds.data(), sizeof(FrameDesc) * n);
                 HIP_TRY(c, hipMemcpyAsync(c->d_fwd_par, blob.data(), bytes, hipMemcpyHostToDevice, c->stream));
                 HIP_TRY(c, hipStreamSynchronize(c->stream)); // caller / local memory is not retained
-                batch.params = reinterpret_cast<const FwdParam *>(c->d_fwd_par);
+                batch.params = reinterpret_cast<const FwdParam *>(c->d_fwd_par.p);
                 batch.frames = reinterpret_cast<const FrameDesc *>(c->d_fwd_par + sizeof(FwdParam) * n);
             }
             if (field) launch_fwd_tiles_field(kind, batch, n, mw, mh, c->W, c->H, static_cast<uint8_t *>(d_out), c->stream);
@@ -124,8 +124,8 @@ static int forward_geometric_batch(hg_ctx *c, int kind, const double *m, const h
         }
     }
     (field ? c->fwd_field_last_kernel : c->fwd_last_kernel) = 1;
-    HG_TRY(ensure(c, c->d_mats, c->mats_cap, (size_t)8 * n));
-    HG_TRY(ensure(c, c->d_win32, c->win32_cap, max_px));
+    HG_TRY(ensure(c, c->d_mats, (size_t)8 * n));
+    HG_TRY(ensure(c, c->d_win32, max_px));
     HIP_TRY(c, hipMemcpyAsync(c->d_mats, m, sizeof(double) * 8 * n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));         // caller memory is not retained
     c->geo_frames.clear();                               // the uploaded geometric frame set was overwritten
@@ -153,8 +153,8 @@ extern "C" int hg_field_forward_geometric(hg_ctx *c, int kind, const double *m, 
     if ((kind != HG_AFFINE && kind != HG_PROJECTIVE) || !m || !out_host) return fail(c, HG_ERR_INVALID, "hg_field_forward_geometric: bad arguments");
     double m8[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     std::memcpy(m8, m, sizeof(double) * (kind == HG_AFFINE ? 6 : 8));
-    const size_t bytes = (geom.obj_w > 0 && geom.obj_h > 0) ? (size_t)geom.obj_w * geom.obj_h * 4 : 0;
-    HG_TRY(ensure(c, c->d_field_tmp, c->field_tmp_cap, std::max(bytes, (size_t)8)));
+    const size_t bytes = frame_px(geom.obj_w, geom.obj_h) * 4;
+    HG_TRY(ensure(c, c->d_field_tmp, std::max(bytes, (size_t)8)));
     const size_t zero = 0;
     HG_TRY(forward_geometric_batch(c, kind, m8, &geom, &zero, 1, c->d_field_tmp, true));
     if (bytes == 0) return HG_OK;
@@ -180,7 +180,7 @@ extern "C" int hg_warp_forward_geometric(hg_ctx *c, int kind, const double *m, h
     if (!out_host) return fail(c, HG_ERR_INVALID, "hg_warp_forward_geometric: bad arguments");
     if (geom.obj_w <= 0 || geom.obj_h <= 0) return HG_OK;
     const size_t n = (size_t)geom.obj_w * geom.obj_h;
-    HG_TRY(ensure(c, c->d_out_tmp, c->out_tmp_cap, n * 4));
+    HG_TRY(ensure(c, c->d_out_tmp, n * 4));
     HG_TRY(hg_warp_forward_geometric_device(c, kind, m, geom, c->d_out_tmp));
     HIP_TRY(c, hipMemcpyAsync(out_host, c->d_out_tmp, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -202,8 +202,8 @@ static int ensure_fwd_rowext(hg_ctx *c, int map_w, int map_h)
         if (bb[4 * (size_t)t + 3] >= bb[4 * (size_t)t + 1]) total += (uint64_t)(bb[4 * (size_t)t + 3] - bb[4 * (size_t)t + 1] + 1);
         if (total > ((uint64_t)1 << 27)) { c->fwd_pw_tiles_disabled = true; return HG_OK; }   // fill() wrap-around quirks made the boxes absurdly tall: scatter path
     }
-    HG_TRY(ensure(c, c->d_frowoff, c->frowoff_cap, (size_t)c->n_tris));
-    HG_TRY(ensure(c, c->d_frowext, c->frowext_cap, (size_t)2 * std::max<uint64_t>(total, 1)));
+    HG_TRY(ensure(c, c->d_frowoff, (size_t)c->n_tris));
+    HG_TRY(ensure(c, c->d_frowext, (size_t)2 * std::max<uint64_t>(total, 1)));
     HIP_TRY(c, hipMemcpyAsync(c->d_frowoff, off.data(), sizeof(uint32_t) * off.size(), hipMemcpyHostToDevice, c->stream));
     launch_fmap_rowext(c->d_fmap, map_w, map_h, c->d_fbbox, c->d_frowoff, c->d_frowext, (size_t)total, c->n_tris, c->stream);
     HIP_TRY(c, hipGetLastError());
@@ -234,8 +234,8 @@ static int settle_forward_field_tiles(hg_ctx *c, const FwdPwTiles &p, int n, int
     for (int f = 0; f < n; f++) {
         const FrameDesc &fd = c->pw_frames[f];
         if (st[f] == 0 || fd.obj_w <= 0 || fd.obj_h <= 0) continue;
-        HG_TRY(ensure(c, c->d_win32, c->win32_cap, (size_t)fd.obj_w * fd.obj_h));
-        launch_fwd_pw_field(c->d_fmap, c->d_fwd + (size_t)f * c->n_tris * 6, c->W, c->H, c->min_src_x, c->min_src_y, p.map_w, p.map_h,
+        HG_TRY(ensure(c, c->d_win32, (size_t)fd.obj_w * fd.obj_h));
+        launch_fwd_pw_field(c->d_fmap, c->solve.fwd + (size_t)f * c->n_tris * 6, c->W, c->H, c->min_src_x, c->min_src_y, p.map_w, p.map_h,
                             fd, c->d_win32, d_field, c->stream);
         HIP_TRY(c, hipGetLastError());
         c->pw_redone++;
@@ -266,7 +266,7 @@ static int forward_piecewise_batch(hg_ctx *c, const float *dst_points, int max_s
         if ((int64_t)c->W * c->H >= ((int64_t)1 << 31)) return fail(c, HG_ERR_INVALID, "the source image has 2^31 pixels or more (an int32 cannot index it)");
         HG_TRY(hg_sync(c));
     }
-    const size_t n_map = (map_w > 0 && map_h > 0) ? (size_t)map_w * map_h : 0;
+    const size_t n_map = frame_px(map_w, map_h);
     // (A) forward triangle map over the source bbox: _buildTrianglesCorrespondencesMatrix :817-832 == the same
     //     rasteriser on the SOURCE triangles with width maxSrcX-minSrcX and y offset minSrcY.  It depends on the mesh only,
     //     so it is kept until the mesh (or the bbox) changes -- like the reference's cached _trianglesCorrespondencesMatrix.
@@ -276,12 +276,12 @@ static int forward_piecewise_batch(hg_ctx *c, const float *dst_points, int max_s
     if (n_map && !(c->fmap_valid && c->fmap_w == map_w && c->fmap_h == map_h)) {
         if (!c->fwd_pending.empty()) HG_TRY(hg_sync(c));     // (queued batches are redone over the map they ran on)
         HG_TRY(hg_piecewise_set_frames(c, c->h_src.data(), &gmap, &zero, 1));
-        c->status_ptr = c->d_status;
-        HIP_TRY(c, hipMemsetAsync(c->d_status, 0, sizeof(int32_t), c->stream));
+        c->status_ptr = c->solve.status;
+        HIP_TRY(c, hipMemsetAsync(c->solve.status, 0, sizeof(int32_t), c->stream));
         { PwFrames fr_ = frames_of(c); fr_.band_ent = nullptr; fr_.two_round = nullptr; launch_tri_setup(mesh_of(c), fr_, c->stream); }   // (no candidate bands: the forward kernels have their own tile lists)
-        HG_TRY(ensure(c, c->d_fmap, c->fmap_cap, n_map));
+        HG_TRY(ensure(c, c->d_fmap, n_map));
         launch_map_build(mesh_of(c), frames_of(c), 0, c->pw_frames[0], c->d_fmap, c->stream);
-        HG_TRY(ensure(c, c->d_fbbox, c->fbbox_cap, (size_t)4 * std::max(c->n_tris, 1)));
+        HG_TRY(ensure(c, c->d_fbbox, (size_t)4 * std::max(c->n_tris, 1)));
         launch_fmap_bbox(c->d_fmap, (int)map_w, (int)map_h, c->d_fbbox, c->n_tris, c->stream);     // (for the tile-binned frames below)
         HIP_TRY(c, hipGetLastError());
         c->fmap_valid = true; c->fmap_w = (int)map_w; c->fmap_h = (int)map_h;
@@ -289,14 +289,14 @@ static int forward_piecewise_batch(hg_ctx *c, const float *dst_points, int max_s
     }
     // (B) forward matrices of every frame (:785-804) in one launch, then scatter + gather frame after frame
     HG_TRY(piecewise_set_frames(c, dst_points, geoms, offs, n, true));     // (the inverse kernels' layout estimate is not needed here: no host walk over the triangles)
-    c->status_ptr = c->d_status;                             // (k_tri_setup only ORs flags into these words and nothing on the forward path reads them: not cleared)
+    c->status_ptr = c->solve.status;                             // (k_tri_setup only ORs flags into these words and nothing on the forward path reads them: not cleared)
     { PwFrames fr_ = frames_of(c); fr_.band_ent = nullptr; fr_.two_round = nullptr; launch_tri_setup(mesh_of(c), fr_, c->stream); }   // (no candidate bands: the forward kernels have their own tile lists)
     c->pw_setup_done = false;
     size_t out_extent = 0;
     uint64_t out_layout = 0;
     output_layout(c->pw_frames, &out_extent, &out_layout);
     size_t max_px = 0;
-    for (const FrameDesc &fd : c->pw_frames) if (fd.obj_w > 0 && fd.obj_h > 0) max_px = std::max(max_px, (size_t)fd.obj_w * fd.obj_h);
+    for (const FrameDesc &fd : c->pw_frames) max_px = std::max(max_px, frame_px(fd.obj_w, fd.obj_h));
     if (max_px) {
         // Tile-binned gather (k_fwd_pw_bins + k_fwd_pw_tiles, all frames in two launches) when the batch has enough tiles;
         // frames the device cannot bound (flagged in their status word) are redone through scatter + gather by hg_sync.
@@ -316,24 +316,24 @@ static int forward_piecewise_batch(hg_ctx *c, const float *dst_points, int max_s
             // tile it consumes, hg_sync the status words it found set -- no memset in front of every batch (two stream operations
             // less per call: they were a fifth of a single 4K frame's time).  Status words: a ring of sets, one per queued batch.
             const size_t per = (size_t)n * tsx * tsy;
-            { const size_t cap0 = c->ftile_cnt_cap;
-              HG_TRY(ensure(c, c->d_ftile_cnt, c->ftile_cnt_cap, per));
-              if (c->ftile_cnt_cap != cap0) HIP_TRY(c, hipMemsetAsync(c->d_ftile_cnt, 0, sizeof(int32_t) * c->ftile_cnt_cap, c->stream)); }
+            { const size_t cap0 = c->d_ftile_cnt.cap;
+              HG_TRY(ensure(c, c->d_ftile_cnt, per));
+              if (c->d_ftile_cnt.cap != cap0) HIP_TRY(c, hipMemsetAsync(c->d_ftile_cnt, 0, sizeof(int32_t) * c->d_ftile_cnt.cap, c->stream)); }
             if (field) {
-                HG_TRY(ensure(c, c->d_ffield_status, c->ffield_status_cap, (size_t)n));
+                HG_TRY(ensure(c, c->d_ffield_status, (size_t)n));
                 HIP_TRY(c, hipMemsetAsync(c->d_ffield_status, 0, sizeof(int32_t) * n, c->stream));
             } else if (c->fwd_pending.size() >= kFwdStatusRing - 1 || (size_t)n > c->fwd_status_stride) {
                 HG_TRY(hg_sync(c));                              // ring full, or a larger batch than the ring's sets were laid out for
                 if ((size_t)n > c->fwd_status_stride) {
-                    HG_TRY(ensure(c, c->d_fwd_status, c->fwd_status_cap, (size_t)n * kFwdStatusRing));
-                    c->fwd_status_stride = c->fwd_status_cap / kFwdStatusRing;
-                    HIP_TRY(c, hipMemsetAsync(c->d_fwd_status, 0, sizeof(int32_t) * c->fwd_status_cap, c->stream));
+                    HG_TRY(ensure(c, c->d_fwd_status, (size_t)n * kFwdStatusRing));
+                    c->fwd_status_stride = c->d_fwd_status.cap / kFwdStatusRing;
+                    HIP_TRY(c, hipMemsetAsync(c->d_fwd_status, 0, sizeof(int32_t) * c->d_fwd_status.cap, c->stream));
                 }
             }
             if (!field) c->fwd_slot = (c->fwd_slot + 1) % (int)kFwdStatusRing;
-            HG_TRY(ensure(c, c->d_ftile_ent, c->ftile_ent_cap, per * (size_t)c->fwd_pw_cap));
+            HG_TRY(ensure(c, c->d_ftile_ent, per * (size_t)c->fwd_pw_cap));
             FwdPwTiles p;
-            p.fmap = c->d_fmap; p.fwd = c->d_fwd; p.bbox = c->d_fbbox; p.frames = c->d_pw_frames; p.rowext = c->d_frowext; p.rowoff = c->d_frowoff;
+            p.fmap = c->d_fmap; p.fwd = c->solve.fwd; p.bbox = c->d_fbbox; p.frames = c->d_pw_frames; p.rowext = c->d_frowext; p.rowoff = c->d_frowoff;
             p.tile_cnt = c->d_ftile_cnt; p.tile_ent = c->d_ftile_ent; p.status = c->d_fwd_status + (size_t)c->fwd_slot * c->fwd_status_stride;
             p.host_flag = c->h_flag ? c->h_flag + 1 : nullptr;
             p.T = c->n_tris; p.min_src_x = c->min_src_x; p.min_src_y = c->min_src_y; p.map_w = (int)map_w; p.map_h = (int)map_h;
@@ -345,7 +345,7 @@ static int forward_piecewise_batch(hg_ctx *c, const float *dst_points, int max_s
             launch_fwd_pw_tiles(p, n, mw, mh, c->d_img, c->n_imgs, c->img_stride, c->W, c->H, static_cast<uint8_t *>(d_out), c->stream);
             HIP_TRY(c, hipGetLastError());
             { hg_ctx::FwdPending fp;
-              fp.out = static_cast<uint8_t *>(d_out); fp.n = n; fp.slot = c->fwd_slot; fp.stage = c->stage_cur; fp.max_src_x = max_src_x; fp.max_src_y = max_src_y;
+              fp.out = static_cast<uint8_t *>(d_out); fp.n = n; fp.slot = c->fwd_slot; fp.stage = c->stage.cur; fp.max_src_x = max_src_x; fp.max_src_y = max_src_y;
               fp.extent = out_extent; fp.layout = out_layout;
               c->fwd_pending.push_back(fp); }
             c->fwd_last_kernel = 2;
@@ -353,11 +353,11 @@ static int forward_piecewise_batch(hg_ctx *c, const float *dst_points, int max_s
         }
         (field ? c->fwd_field_last_kernel : c->fwd_last_kernel) = 1;
         HG_TRY(settle_output_conflicts(c, d_out, out_extent, 0));      // (this path keeps no pending record: nothing queued may be redone over it later)
-        HG_TRY(ensure(c, c->d_win32, c->win32_cap, max_px));
+        HG_TRY(ensure(c, c->d_win32, max_px));
         for (int f = 0; f < n; f++) {
-            if (field) launch_fwd_pw_field(c->d_fmap, c->d_fwd + (size_t)f * c->n_tris * 6, c->W, c->H, c->min_src_x, c->min_src_y, (int)map_w, (int)map_h,
+            if (field) launch_fwd_pw_field(c->d_fmap, c->solve.fwd + (size_t)f * c->n_tris * 6, c->W, c->H, c->min_src_x, c->min_src_y, (int)map_w, (int)map_h,
                                            c->pw_frames[f], c->d_win32, static_cast<uint8_t *>(d_out), c->stream);
-            else launch_fwd_pw(c->d_fmap, c->d_fwd + (size_t)f * c->n_tris * 6, frame_img(mesh_of(c), f), c->W, c->H, c->min_src_x, c->min_src_y, (int)map_w, (int)map_h,
+            else launch_fwd_pw(c->d_fmap, c->solve.fwd + (size_t)f * c->n_tris * 6, frame_img(mesh_of(c), f), c->W, c->H, c->min_src_x, c->min_src_y, (int)map_w, (int)map_h,
                                c->pw_frames[f], c->d_win32, static_cast<uint8_t *>(d_out), c->stream);
         }
     }
@@ -382,8 +382,8 @@ extern "C" int hg_field_forward_piecewise(hg_ctx *c, const float *dst_points, in
     HG_TRY(bind(c));
     if (!out_host) return fail(c, HG_ERR_INVALID, "hg_field_forward_piecewise: bad arguments");
     if (geom.obj_w <= 0 || geom.obj_h <= 0) return HG_OK;    // (an empty window writes nothing, like hg_warp_forward_piecewise)
-    const size_t bytes = (geom.obj_w > 0 && geom.obj_h > 0) ? (size_t)geom.obj_w * geom.obj_h * 4 : 0;
-    HG_TRY(ensure(c, c->d_field_tmp, c->field_tmp_cap, std::max(bytes, (size_t)8)));
+    const size_t bytes = frame_px(geom.obj_w, geom.obj_h) * 4;
+    HG_TRY(ensure(c, c->d_field_tmp, std::max(bytes, (size_t)8)));
     const size_t zero = 0;
     HG_TRY(forward_piecewise_batch(c, dst_points, max_src_x, max_src_y, &geom, &zero, 1, c->d_field_tmp, true));
     if (bytes == 0) return HG_OK;
@@ -404,7 +404,7 @@ extern "C" int hg_warp_forward_piecewise(hg_ctx *c, const float *dst_points, int
     if (!out_host) return fail(c, HG_ERR_INVALID, "hg_warp_forward_piecewise: bad arguments");
     if (geom.obj_w <= 0 || geom.obj_h <= 0) return HG_OK;
     const size_t n = (size_t)geom.obj_w * geom.obj_h;
-    HG_TRY(ensure(c, c->d_out_tmp, c->out_tmp_cap, n * 4));
+    HG_TRY(ensure(c, c->d_out_tmp, n * 4));
     HG_TRY(hg_warp_forward_piecewise_device(c, dst_points, max_src_x, max_src_y, geom, c->d_out_tmp));
     HG_TRY(hg_sync(c));                                      // (settles a frame the tile kernels handed to the scatter path)
     HIP_TRY(c, hipMemcpyAsync(out_host, c->d_out_tmp, n * 4, hipMemcpyDeviceToHost, c->stream));

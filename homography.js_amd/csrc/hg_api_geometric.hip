@@ -18,30 +18,10 @@ extern "C" int hg_selftest_division(hg_ctx *c, uint64_t samples, uint64_t seed, 
 {
     HG_TRY(bind(c));
     if (!mismatches) return fail(c, HG_ERR_INVALID, "mismatches is NULL");
-    unsigned long long *d = nullptr;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&d), sizeof(unsigned long long)));
+    DevBuf<unsigned long long> d;
+    HG_TRY(ensure(c, d, 1));
     *mismatches = run_selftest_division(seed, samples, d, c->stream);
-    HIP_TRY(c, hipFree(d));
     HIP_TRY(c, hipGetLastError());
-    return HG_OK;
-}
-
-// Next staging slot with room for `bytes` (waits only if the upload that last used this slot -- eight sets ago -- is still queued).
-static int geo_stage_slot(hg_ctx *c, size_t bytes, hg_ctx::GeoStage **out)
-{
-    const int slot = (c->geo_stage_cur + 1) % 8;
-    hg_ctx::GeoStage &gs = c->geo_stage[slot];
-    if (!gs.done) HIP_TRY(c, hipEventCreateWithFlags(&gs.done, hipEventDisableTiming));
-    if (gs.used) HIP_TRY(c, hipEventSynchronize(gs.done));
-    if (bytes > gs.cap) {
-        if (gs.h) { HIP_TRY(c, hipHostFree(gs.h)); gs.h = nullptr; gs.cap = 0; }
-        void *q = nullptr;
-        hipError_t e = hipHostMalloc(&q, bytes + bytes / 4, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(c, HG_ERR_NOMEM, std::string("hipHostMalloc (frame-set staging): ") + hipGetErrorString(e));
-        gs.h = static_cast<uint8_t *>(q); gs.cap = bytes + bytes / 4;
-    }
-    c->geo_stage_cur = slot;
-    *out = &gs;
     return HG_OK;
 }
 
@@ -55,15 +35,15 @@ extern "C" int hg_geometric_set_frames(hg_ctx *c, int kind, const double *m, con
     c->geo_frames.clear();
     std::vector<FrameDesc> fresh;
     HG_TRY(fill_frames(c, fresh, geoms, offs, n));
-    HG_TRY(ensure(c, c->d_geo_frames, c->geo_frames_cap, (size_t)n));
-    HG_TRY(ensure(c, c->d_mats, c->mats_cap, (size_t)n * 8));
+    HG_TRY(ensure(c, c->d_geo_frames, (size_t)n));
+    HG_TRY(ensure(c, c->d_mats, (size_t)n * 8));
     const size_t fd_bytes = sizeof(FrameDesc) * (size_t)n, m_bytes = sizeof(double) * 8 * (size_t)n;
-    hg_ctx::GeoStage *gs = nullptr;
-    HG_TRY(geo_stage_slot(c, fd_bytes + m_bytes, &gs));
+    StageSlot *gs = nullptr;
+    HG_TRY(c->geo_stage.acquire(c, fd_bytes + m_bytes, "frame-set staging", &gs));
     std::memcpy(gs->h, fresh.data(), fd_bytes);
     std::memcpy(gs->h + fd_bytes, m, m_bytes);
     HG_TRY(upload_staged(c, c->d_geo_frames, gs->h, fd_bytes, c->d_mats, gs->h + fd_bytes, m_bytes));
-    HIP_TRY(c, hipEventRecord(gs->done, c->stream)); gs->used = true;
+    HG_TRY(c->geo_stage.commit(c, gs));
     c->geo_frames.swap(fresh);
     c->geo_kind = kind; c->geo_from_points = false;
     bool exact = kind == HG_AFFINE;
@@ -87,19 +67,19 @@ extern "C" int hg_geometric_set_frames_points(hg_ctx *c, int kind, const float *
     c->geo_frames.clear();                                  // transactional, like hg_geometric_set_frames
     std::vector<FrameDesc> fresh;
     HG_TRY(fill_frames(c, fresh, geoms, offs, n));
-    HG_TRY(ensure(c, c->d_geo_frames, c->geo_frames_cap, (size_t)n));
-    HG_TRY(ensure(c, c->d_mats, c->mats_cap, (size_t)n * 8));
-    HG_TRY(ensure(c, c->d_geo_pts, c->geo_pts_cap, (size_t)n * 16));
-    HG_TRY(ensure(c, c->d_geo_plain, c->geo_plain_cap, (size_t)n));
+    HG_TRY(ensure(c, c->d_geo_frames, (size_t)n));
+    HG_TRY(ensure(c, c->d_mats, (size_t)n * 8));
+    HG_TRY(ensure(c, c->d_geo_pts, (size_t)n * 16));
+    HG_TRY(ensure(c, c->d_geo_plain, (size_t)n));
     const size_t fd_bytes = sizeof(FrameDesc) * (size_t)n, p_bytes = sizeof(float) * per * (size_t)n;
-    hg_ctx::GeoStage *gs = nullptr;
-    HG_TRY(geo_stage_slot(c, fd_bytes + 2 * p_bytes, &gs));
+    StageSlot *gs = nullptr;
+    HG_TRY(c->geo_stage.acquire(c, fd_bytes + 2 * p_bytes, "frame-set staging", &gs));
     std::memcpy(gs->h, fresh.data(), fd_bytes);
     std::memcpy(gs->h + fd_bytes, from, p_bytes);
     std::memcpy(gs->h + fd_bytes + p_bytes, to, p_bytes);
     HG_TRY(upload_staged(c, c->d_geo_frames, gs->h, fd_bytes, c->d_geo_pts, gs->h + fd_bytes, p_bytes,
                          c->d_geo_pts + (size_t)n * 8, gs->h + fd_bytes + p_bytes, p_bytes));
-    HIP_TRY(c, hipEventRecord(gs->done, c->stream)); gs->used = true;
+    HG_TRY(c->geo_stage.commit(c, gs));
     c->geo_frames.swap(fresh);
     c->geo_kind = kind; c->geo_from_points = true;
     bool exact = kind == HG_AFFINE;                          // affine: the solve stores float32 values; x stays below 2^28?
@@ -170,8 +150,8 @@ extern "C" int hg_warp_inverse_geometric(hg_ctx *c, int kind, const double *m, h
     HG_TRY(bind(c));
     if (!out_host) return fail(c, HG_ERR_INVALID, "out is NULL");
     if (geom.obj_w <= 0 || geom.obj_h <= 0) return HG_OK;
-    const size_t bytes = (size_t)geom.obj_w * geom.obj_h * 4;
-    HG_TRY(ensure(c, c->d_out_tmp, c->out_tmp_cap, bytes));
+    const size_t bytes = frame_px(geom.obj_w, geom.obj_h) * 4;
+    HG_TRY(ensure(c, c->d_out_tmp, bytes));
     HG_TRY(hg_warp_inverse_geometric_device(c, kind, m, geom, c->d_out_tmp));
     HIP_TRY(c, hipMemcpyAsync(out_host, c->d_out_tmp, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));

@@ -3,14 +3,6 @@
 #include "hg_ctx.h"
 
 // ------------------------------------------------------------------------------------------------ piecewise affine
-// NaN is a legal (if useless) coordinate -- the reference then simply draws nothing for that triangle -- but magnitudes beyond
-// kMaxCoord (Infinity included) are refused: the row loops of the rasterisers are bounded under that assumption (hg_math.h).
-static bool coords_ok(const float *p, size_t n)
-{
-    for (size_t i = 0; i < n; i++) if (std::fabs((double)p[i]) > kMaxCoord) return false;      // (NaN compares false)
-    return true;
-}
-
 extern "C" int hg_piecewise_set_mesh(hg_ctx *c, const float *src, int n_pts, const uint32_t *tris, int n_tris, int msx, int msy)
 {
     HG_TRY(bind(c));
@@ -24,8 +16,8 @@ extern "C" int hg_piecewise_set_mesh(hg_ctx *c, const float *src, int n_pts, con
         (n_tris == 0 || std::memcmp(tris, c->h_tris.data(), sizeof(uint32_t) * 3 * (size_t)n_tris) == 0))
         return HG_OK;
     HG_TRY(hg_sync(c));
-    HG_TRY(ensure(c, c->d_src, c->src_cap, (size_t)n_pts * 2));
-    HG_TRY(ensure(c, c->d_tris, c->tris_cap, (size_t)std::max(n_tris, 1) * 3));
+    HG_TRY(ensure(c, c->d_src, (size_t)n_pts * 2));
+    HG_TRY(ensure(c, c->d_tris, (size_t)std::max(n_tris, 1) * 3));
     HIP_TRY(c, hipMemcpyAsync(c->d_src, src, sizeof(float) * 2 * n_pts, hipMemcpyHostToDevice, c->stream));
     if (n_tris > 0) HIP_TRY(c, hipMemcpyAsync(c->d_tris, tris, sizeof(uint32_t) * 3 * n_tris, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -177,7 +169,7 @@ static int pw_set_frames_impl(hg_ctx *c, bool own_src, const float *src, const i
     // staged copy of the set it warped (deferred redo, hg_sync).  Only a staging slot that a queued run still refers to forces a
     // settlement first (a caller that uploads 64 sets per run).
     const size_t T = (size_t)std::max(c->n_tris, 1), F = (size_t)n;
-    const int slot = (c->stage_cur + 1) % (int)kStatusRing;
+    const int slot = c->stage.next();
     for (const hg_ctx::Pending &pd : c->pw_pending_out) if (pd.stage == slot) { HG_TRY(hg_sync(c)); break; }
     for (const hg_ctx::FwdPending &pd : c->fwd_pending) if (pd.stage == slot) { HG_TRY(hg_sync(c)); break; }   // (their redo reads the staged set too)
     std::vector<FrameDesc> fresh;
@@ -185,49 +177,29 @@ static int pw_set_frames_impl(hg_ctx *c, bool own_src, const float *src, const i
     // the set's block: frame records, destiny points and -- a set with its own source side -- source points and source minima
     const size_t fd_bytes = sizeof(FrameDesc) * F, pt_bytes = sizeof(float) * 2 * c->n_pts * F, ms_bytes = src ? sizeof(int2) * F : 0;
     const size_t set_bytes = fd_bytes + pt_bytes + (src ? pt_bytes + ms_bytes : 0);
-    HG_TRY(ensure(c, c->d_set, c->set_cap, set_bytes));
-    HG_TRY(ensure(c, c->d_trir, c->trir_cap, F * T));
-    HG_TRY(ensure(c, c->d_trix, c->trix_cap, F * T));
-    HG_TRY(ensure(c, c->d_segs, c->segs_cap, F * T * 3));
-    HG_TRY(ensure(c, c->d_fwd, c->fwd_cap, F * T * 6));
-    HG_TRY(ensure(c, c->d_inv, c->inv_cap, F * T * kInvStride));
-    HG_TRY(ensure(c, c->d_status, c->status_cap, F));
-    HG_TRY(ensure(c, c->d_two_round, c->two_round_cap, F));   // (never cleared: a stale word can only equal the step number by accident, which costs speed, not bits)
+    HG_TRY(ensure(c, c->d_set, set_bytes));
+    HG_TRY(c->solve.ensure(c, F, T));
+    HG_TRY(ensure(c, c->d_two_round, F));   // (never cleared: a stale word can only equal the step number by accident, which costs speed, not bits)
     if (!c->h_flag) {
-        void *q = nullptr;
-        hipError_t e = hipHostMalloc(&q, 64, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(c, HG_ERR_NOMEM, std::string("hipHostMalloc (flag word): ") + hipGetErrorString(e));
-        c->h_flag = static_cast<int32_t *>(q); c->h_flag[0] = 0; c->h_flag[1] = 0;      // [0] inverse fused kernels, [1] forward tile kernels
+        HG_TRY(c->h_flag.alloc(c, 16, "flag word"));
+        c->h_flag[0] = 0; c->h_flag[1] = 0;                 // [0] inverse fused kernels, [1] forward tile kernels
     }
-    if (F * kStatusRing > c->h_status_cap) {
+    if (F * kStatusRing > c->h_status.cap) {
         HG_TRY(hg_sync(c));
-        if (c->h_status) HIP_TRY(c, hipHostFree(c->h_status));
-        c->h_status = nullptr; c->h_status_cap = 0;
-        void *q = nullptr;
-        HIP_TRY(c, hipHostMalloc(&q, sizeof(int32_t) * F * kStatusRing, hipHostMallocDefault));
-        c->h_status = static_cast<int32_t *>(q); c->h_status_cap = F * kStatusRing;
+        HG_TRY(c->h_status.alloc(c, F * kStatusRing, "status words"));
     }
-    hg_ctx::Stage &st = c->stage[slot];
     // An older upload out of this slot may still be queued (no queued run refers to the slot -- checked above -- but its DMA reads
-    // it): wait for THAT copy, not for the stream.  64 sets back it has long run in any loop that also launches kernels.
-    if (!st.done) HIP_TRY(c, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
-    if (st.used) HIP_TRY(c, hipEventSynchronize(st.done));
-    if (set_bytes > st.cap) {
-        if (st.h) { HIP_TRY(c, hipHostFree(st.h)); st.h = nullptr; st.cap = 0; }
-        void *q = nullptr;
-        const size_t want = set_bytes + set_bytes / 4;
-        hipError_t e = hipHostMalloc(&q, want, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(c, HG_ERR_NOMEM, std::string("hipHostMalloc (frame-set staging): ") + hipGetErrorString(e));
-        st.h = static_cast<uint8_t *>(q); st.cap = want;
-    }
-    std::memcpy(st.h, fresh.data(), fd_bytes);
-    std::memcpy(st.h + fd_bytes, dst, pt_bytes);
+    // it): acquire waits for THAT copy, not for the stream.  64 sets back it has long run in any loop that also launches kernels.
+    hg_ctx::Stage *st = nullptr;
+    HG_TRY(c->stage.acquire(c, set_bytes, "frame-set staging", &st));
+    std::memcpy(st->h, fresh.data(), fd_bytes);
+    std::memcpy(st->h + fd_bytes, dst, pt_bytes);
     // Device layout of the staged block: FrameDesc[F] | destiny points F x n_pts x 2 f32 | (own source side only:) source points F x n_pts x 2 f32 |
     // source minima F x {minSrcX, minSrcY} int32.  Every part is a multiple of 8 bytes.
     int ms_lo_x = 0, ms_hi_x = 0, ms_lo_y = 0, ms_hi_y = 0;
     if (src) {
-        std::memcpy(st.h + fd_bytes + pt_bytes, src, pt_bytes);
-        int32_t *ms = reinterpret_cast<int32_t *>(st.h + fd_bytes + 2 * pt_bytes);
+        std::memcpy(st->h + fd_bytes + pt_bytes, src, pt_bytes);
+        int32_t *ms = reinterpret_cast<int32_t *>(st->h + fd_bytes + 2 * pt_bytes);
         for (size_t f = 0; f < F; f++) {
             if (min_src) { ms[2 * f] = min_src[2 * f]; ms[2 * f + 1] = min_src[2 * f + 1]; }
             else HG_TRY(hg_piecewise_frame_min_src(src + f * (size_t)c->n_pts * 2, c->n_pts, ms + 2 * f));
@@ -236,18 +208,16 @@ static int pw_set_frames_impl(hg_ctx *c, bool own_src, const float *src, const i
             ms_lo_y = std::min(ms_lo_y, ms[2 * f + 1]); ms_hi_y = std::max(ms_hi_y, ms[2 * f + 1]);
         }
     }
-    st.n = n; st.n_pts = c->n_pts; st.moving = src != nullptr;
+    st->n = n; st->n_pts = c->n_pts; st->moving = src != nullptr;
     static_assert(sizeof(FrameDesc) % 8 == 0 && sizeof(int2) == 8, "the parts of the block keep 8-byte alignment");
-    c->d_pw_frames = reinterpret_cast<FrameDesc *>(c->d_set); c->d_dst = reinterpret_cast<float *>(c->d_set + fd_bytes);
+    c->d_pw_frames = reinterpret_cast<FrameDesc *>(c->d_set.p); c->d_dst = reinterpret_cast<float *>(c->d_set + fd_bytes);
     c->pw_moving = src != nullptr;
     c->d_srcf = src ? reinterpret_cast<float *>(c->d_set + fd_bytes + pt_bytes) : nullptr;
     c->d_min_src = src ? reinterpret_cast<int2 *>(c->d_set + fd_bytes + 2 * pt_bytes) : nullptr;
     c->ms_lo_x = ms_lo_x; c->ms_hi_x = ms_hi_x; c->ms_lo_y = ms_lo_y; c->ms_hi_y = ms_hi_y;
-    HG_TRY(upload_staged(c, c->d_set, st.h, set_bytes));     // (one copy: the staged block has the device layout)
-    HIP_TRY(c, hipEventRecord(st.done, c->stream));
-    st.used = true;
+    HG_TRY(upload_staged(c, c->d_set, st->h, set_bytes));     // (one copy: the staged block has the device layout)
+    HG_TRY(c->stage.commit(c, st));
     c->pw_frames.swap(fresh);
-    c->stage_cur = slot;
     PwShape s;
     s.n = n;
     int64_t total_px = 0;
@@ -322,8 +292,9 @@ PwFrames frames_of(const hg_ctx *c)
     f.host_flag = c->h_flag;                                 // (always armed: whether hg_sync may skip the status ring must not depend on an option that can change while runs are queued)
     f.src_pts = c->pw_moving ? c->d_srcf : nullptr; f.min_src = c->pw_moving ? c->d_min_src : nullptr;
     f.min_src_lo_x = c->ms_lo_x; f.min_src_hi_x = c->ms_hi_x; f.min_src_lo_y = c->ms_lo_y; f.min_src_hi_y = c->ms_hi_y;
-    f.frames = c->d_pw_frames; f.dst_pts = c->d_dst; f.trir = c->d_trir; f.trix = c->d_trix; f.segs = c->d_segs; f.fwd = c->d_fwd; f.inv = c->d_inv;
-    f.status = c->status_ptr ? c->status_ptr : c->d_status; f.n_frames = (int)c->pw_frames.size();
+    f.frames = c->d_pw_frames; f.dst_pts = c->d_dst; c->solve.point(f);
+    if (c->status_ptr) f.status = c->status_ptr;
+    f.n_frames = (int)c->pw_frames.size();
     f.two_round = c->d_two_round; f.gen = c->pw_gen;
     f.max_obj_h = c->pw_shape.max_h;
     f.row_group = p.row_group; f.tri_threads = p.tri_threads; f.tri_group = p.tri_group; f.phase = p.phase;
@@ -544,8 +515,8 @@ static int run_setup(hg_ctx *c, bool for_tap = false)
     if (p.kernel == PwKernel::Fused) {
         HG_TRY(hg_sync(c));                                  // (queued fast-path runs are settled against their own status ring first)
         c->rows_clean = false;                               // (the next fast-path set starts from freshly zeroed counters)
-        c->status_ptr = c->d_status;
-        HIP_TRY(c, hipMemsetAsync(c->d_status, 0, sizeof(int32_t) * F, c->stream));
+        c->status_ptr = c->solve.status;
+        HIP_TRY(c, hipMemsetAsync(c->solve.status, 0, sizeof(int32_t) * F, c->stream));
         launch_tri_setup(mesh_of(c), frames_of(c), c->stream);
         HIP_TRY(c, hipGetLastError());
         c->pw_setup_done = true;
@@ -556,8 +527,8 @@ static int run_setup(hg_ctx *c, bool for_tap = false)
     if (p.bands) {
         if (p.band_cap > c->band_cap) c->band_cap = p.band_cap;
         const size_t need = F * (size_t)p.n_bands * (size_t)c->band_cap * 2;      // (two int4 per entry)
-        if (need > c->bands_cap) HG_TRY(hg_sync(c));
-        HG_TRY(ensure(c, c->d_bands, c->bands_cap, need));
+        if (need > c->d_bands.cap) HG_TRY(hg_sync(c));
+        HG_TRY(ensure(c, c->d_bands, need));
     }
     RowLists rl = rows_of(c);
     // Two sets of row counters (ping-pong) + kStatusRing sets of per-frame status words share one allocation.  It is zeroed by a
@@ -565,9 +536,9 @@ static int run_setup(hg_ctx *c, bool for_tap = false)
     // counter set -- the one the previous step consumed, the one the next step counts into -- and the next status set.
     const int32_t *before = c->d_rowcnt;
     const size_t ent_bytes = p.self ? 0 : F * (size_t)rl.row_stride * rl.cap * (p.compact ? sizeof(RowEnt8) : sizeof(RowEnt));
-    if (2 * F * rl.row_stride + kStatusRing * F > c->rowcnt_cap || ent_bytes > c->rowent_cap) HG_TRY(hg_sync(c));   // (queued runs flag into the old ring)
-    HG_TRY(ensure(c, c->d_rowcnt, c->rowcnt_cap, 2 * F * rl.row_stride + kStatusRing * F));
-    HG_TRY(ensure(c, c->d_rowent, c->rowent_cap, ent_bytes));
+    if (2 * F * rl.row_stride + kStatusRing * F > c->d_rowcnt.cap || ent_bytes > c->d_rowent.cap) HG_TRY(hg_sync(c));   // (queued runs flag into the old ring)
+    HG_TRY(ensure(c, c->d_rowcnt, 2 * F * rl.row_stride + kStatusRing * F));
+    HG_TRY(ensure(c, c->d_rowent, ent_bytes));
     if (before != c->d_rowcnt || c->rows_F != F || c->rows_stride != rl.row_stride || c->rows_cap != rl.cap) c->rows_clean = false;
     c->rows_F = F; c->rows_stride = rl.row_stride; c->rows_cap = rl.cap;
     if (c->rows_clean) { c->status_slot = (c->status_slot + 1) % (int)kStatusRing; c->rows_parity ^= 1; }
@@ -621,9 +592,9 @@ int check_pw_state(hg_ctx *c)
 static int run_frame_via_map(hg_ctx *c, int f, uint8_t *d_out)
 {
     const FrameDesc &fd = c->pw_frames[f];
-    const size_t n = (fd.obj_w > 0 && fd.obj_h > 0) ? (size_t)fd.obj_w * fd.obj_h : 0;
+    const size_t n = frame_px(fd.obj_w, fd.obj_h);
     if (n == 0) return HG_OK;
-    HG_TRY(ensure(c, c->d_map32, c->map32_cap, n));
+    HG_TRY(ensure(c, c->d_map32, n));
     PwMesh mesh = mesh_of(c);
     mesh.img = frame_img(mesh, f); mesh.n_imgs = 1;          // this frame's own source
     launch_map_build(mesh, frames_of(c), f, fd, c->d_map32, c->stream);
@@ -637,20 +608,15 @@ static int run_frame_via_map(hg_ctx *c, int f, uint8_t *d_out)
 // window; an empty one has nothing to redo (nothing is set up).
 static int load_redo_frame(hg_ctx *c, int stage, int f, const char *what, FrameDesc *fd, PwFrames *fr)
 {
-    if (stage < 0 || !c->stage[stage].h || f >= c->stage[stage].n || c->stage[stage].n_pts != c->n_pts)
+    if (stage < 0 || !c->stage.slot[stage].h || f >= c->stage.slot[stage].n || c->stage.slot[stage].n_pts != c->n_pts)
         return fail(c, HG_ERR_STATE, std::string(what) + ": the staged frame set is gone");
-    const hg_ctx::Stage &st = c->stage[stage];
+    const hg_ctx::Stage &st = c->stage.slot[stage];
     *fd = reinterpret_cast<const FrameDesc *>(st.h)[f];
     if (fd->obj_w <= 0 || fd->obj_h <= 0) return HG_OK;
     const size_t T = (size_t)std::max(c->n_tris, 1);
-    HG_TRY(ensure(c, c->d_redo_frame, c->redo_frame_cap, (size_t)1));
-    HG_TRY(ensure(c, c->d_redo_dst, c->redo_dst_cap, (size_t)c->n_pts * 2));
-    HG_TRY(ensure(c, c->d_redo_trir, c->redo_trir_cap, T));
-    HG_TRY(ensure(c, c->d_redo_trix, c->redo_trix_cap, T));
-    HG_TRY(ensure(c, c->d_redo_segs, c->redo_segs_cap, T * 3));
-    HG_TRY(ensure(c, c->d_redo_fwd, c->redo_fwd_cap, T * 6));
-    HG_TRY(ensure(c, c->d_redo_inv, c->redo_inv_cap, T * kInvStride));
-    HG_TRY(ensure(c, c->d_redo_status, c->redo_status_cap, (size_t)1));
+    HG_TRY(ensure(c, c->d_redo_frame, (size_t)1));
+    HG_TRY(ensure(c, c->d_redo_dst, (size_t)c->n_pts * 2));
+    HG_TRY(c->redo.ensure(c, 1, T));
     const float *pts = reinterpret_cast<const float *>(st.h + sizeof(FrameDesc) * (size_t)st.n) + (size_t)f * c->n_pts * 2;
     HIP_TRY(c, hipMemcpyAsync(c->d_redo_frame, st.h + sizeof(FrameDesc) * (size_t)f, sizeof(FrameDesc), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_redo_dst, pts, sizeof(float) * 2 * c->n_pts, hipMemcpyHostToDevice, c->stream));
@@ -659,15 +625,15 @@ static int load_redo_frame(hg_ctx *c, int stage, int f, const char *what, FrameD
     if (st.moving) {
         const size_t pt_all = sizeof(float) * 2 * (size_t)c->n_pts * (size_t)st.n;
         const uint8_t *src0 = st.h + sizeof(FrameDesc) * (size_t)st.n + pt_all;
-        HG_TRY(ensure(c, c->d_redo_src, c->redo_src_cap, (size_t)c->n_pts * 2));
-        HG_TRY(ensure(c, c->d_redo_min, c->redo_min_cap, (size_t)1));
+        HG_TRY(ensure(c, c->d_redo_src, (size_t)c->n_pts * 2));
+        HG_TRY(ensure(c, c->d_redo_min, (size_t)1));
         HIP_TRY(c, hipMemcpyAsync(c->d_redo_src, src0 + sizeof(float) * 2 * (size_t)c->n_pts * (size_t)f, sizeof(float) * 2 * c->n_pts, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(c->d_redo_min, src0 + pt_all + sizeof(int2) * (size_t)f, sizeof(int2), hipMemcpyHostToDevice, c->stream));
         fr->src_pts = c->d_redo_src; fr->min_src = c->d_redo_min;
     }
     fr->two_round = nullptr;                                 // (a set-up of its own, outside the frame set's step numbering)
-    fr->frames = c->d_redo_frame; fr->dst_pts = c->d_redo_dst; fr->trir = c->d_redo_trir; fr->trix = c->d_redo_trix; fr->band_ent = nullptr; fr->host_flag = nullptr; fr->segs = c->d_redo_segs; fr->fwd = c->d_redo_fwd;
-    fr->inv = c->d_redo_inv; fr->status = c->d_redo_status; fr->n_frames = 1; fr->max_obj_h = fd->obj_h;
+    fr->frames = c->d_redo_frame; fr->dst_pts = c->d_redo_dst; c->redo.point(*fr); fr->band_ent = nullptr; fr->host_flag = nullptr;
+    fr->n_frames = 1; fr->max_obj_h = fd->obj_h;
     return HG_OK;
 }
 
@@ -679,10 +645,10 @@ static int redo_frame_staged(hg_ctx *c, int stage, int f, uint8_t *d_out, int sa
     FrameDesc fd;
     PwFrames fr;
     HG_TRY(load_redo_frame(c, stage, f, "deferred redo", &fd, &fr));
-    const size_t n = (fd.obj_w > 0 && fd.obj_h > 0) ? (size_t)fd.obj_w * fd.obj_h : 0;
+    const size_t n = frame_px(fd.obj_w, fd.obj_h);
     if (n == 0) return HG_OK;
-    HG_TRY(ensure(c, c->d_map32, c->map32_cap, n));
-    HIP_TRY(c, hipMemsetAsync(c->d_redo_status, 0, sizeof(int32_t), c->stream));
+    HG_TRY(ensure(c, c->d_map32, n));
+    HIP_TRY(c, hipMemsetAsync(c->redo.status, 0, sizeof(int32_t), c->stream));
     PwMesh mesh = mesh_of(c);
     mesh.img = frame_img(mesh, f); mesh.n_imgs = 1;          // this frame's own source
     launch_tri_setup(mesh, fr, c->stream);
@@ -700,11 +666,11 @@ int redo_forward_frame_staged(hg_ctx *c, int stage, int f, int max_src_x, int ma
     FrameDesc fd;
     PwFrames fr;
     HG_TRY(load_redo_frame(c, stage, f, "deferred forward redo", &fd, &fr));
-    const size_t n = (fd.obj_w > 0 && fd.obj_h > 0) ? (size_t)fd.obj_w * fd.obj_h : 0;
+    const size_t n = frame_px(fd.obj_w, fd.obj_h);
     if (n == 0) return HG_OK;
-    HG_TRY(ensure(c, c->d_win32, c->win32_cap, n));
+    HG_TRY(ensure(c, c->d_win32, n));
     launch_tri_setup(mesh_of(c), fr, c->stream);
-    launch_fwd_pw(c->d_fmap, c->d_redo_fwd, frame_img(mesh_of(c), f), c->W, c->H, c->min_src_x, c->min_src_y, max_src_x - c->min_src_x, max_src_y - c->min_src_y,
+    launch_fwd_pw(c->d_fmap, c->redo.fwd, frame_img(mesh_of(c), f), c->W, c->H, c->min_src_x, c->min_src_y, max_src_x - c->min_src_x, max_src_y - c->min_src_y,
                   fd, c->d_win32, d_out, c->stream);
     HIP_TRY(c, hipGetLastError());
     return HG_OK;
@@ -728,11 +694,11 @@ extern "C" int hg_warp_inverse_piecewise_frames_device(hg_ctx *c, void *d_out)
     HIP_TRY(c, hipGetLastError());
     const PwPlan &p = c->pw_plan;
     const uint8_t mode = (uint8_t)c->sampling;
-    if (p.kernel != PwKernel::Fused) c->pw_pending_out.push_back({static_cast<uint8_t *>(d_out), c->status_slot, c->stage_cur, extent, layout, p.kernel, p.self, mode});
+    if (p.kernel != PwKernel::Fused) c->pw_pending_out.push_back({static_cast<uint8_t *>(d_out), c->status_slot, c->stage.cur, extent, layout, p.kernel, p.self, mode});
     else {                                                   // general path: one status set, checked right away
         HIP_TRY(c, hipMemcpyAsync(c->h_status, c->status_ptr, sizeof(int32_t) * c->pw_frames.size(), hipMemcpyDeviceToHost, c->stream));
         c->status_base = nullptr;
-        c->pw_pending_out.push_back({static_cast<uint8_t *>(d_out), 0, c->stage_cur, extent, layout, p.kernel, p.self, mode});
+        c->pw_pending_out.push_back({static_cast<uint8_t *>(d_out), 0, c->stage.cur, extent, layout, p.kernel, p.self, mode});
         HG_TRY(hg_sync(c));
     }
     return HG_OK;
@@ -744,7 +710,7 @@ struct FrameRange { const uint8_t *lo, *hi; };
 static bool queued_frame_range(const hg_ctx *c, int stage, int f, const uint8_t *out, FrameRange *r)
 {
     const FrameDesc *fd = nullptr;
-    if (stage >= 0 && c->stage[stage].h) { if (f < c->stage[stage].n) fd = reinterpret_cast<const FrameDesc *>(c->stage[stage].h) + f; }
+    if (stage >= 0 && c->stage.slot[stage].h) { if (f < c->stage.slot[stage].n) fd = reinterpret_cast<const FrameDesc *>(c->stage.slot[stage].h) + f; }
     else if (f < (int)c->pw_frames.size()) fd = &c->pw_frames[f];
     if (!fd || fd->obj_w <= 0 || fd->obj_h <= 0) return false;
     r->lo = out + fd->out_off; r->hi = r->lo + (size_t)fd->obj_w * fd->obj_h * 4;
@@ -799,7 +765,7 @@ extern "C" int hg_sync(hg_ctx *c)
         bool redo = false;
         // (all queued runs share one layout of the status ring: a set with another frame count settles them before it runs)
         const int st0 = pending.front().stage;
-        const size_t F = (st0 >= 0 && c->stage[st0].h) ? (size_t)c->stage[st0].n : c->pw_frames.size();
+        const size_t F = (st0 >= 0 && c->stage.slot[st0].h) ? (size_t)c->stage.slot[st0].n : c->pw_frames.size();
         const bool none_flagged = c->status_base && c->h_flag && *c->h_flag == 0;
         if (c->status_base && !none_flagged) {
             HIP_TRY(c, hipMemcpy(c->h_status, c->status_base, sizeof(int32_t) * F * kStatusRing, hipMemcpyDeviceToHost));
@@ -827,7 +793,7 @@ extern "C" int hg_sync(hg_ctx *c)
         // may have been uploaded since).  The forward map is the context's: a new mesh settles queued runs first.
         std::vector<hg_ctx::FwdPending> pending;
         pending.swap(c->fwd_pending);
-        std::vector<int32_t> st(c->fwd_status_cap);
+        std::vector<int32_t> st(c->d_fwd_status.cap);
         // (as above: the status words are read only when a forward tile kernel set its host-visible flag word)
         const bool none_flagged = c->h_flag && c->h_flag[1] == 0;
         if (!none_flagged) {
@@ -850,7 +816,7 @@ extern "C" int hg_sync(hg_ctx *c)
                                  [&](size_t i, int f) { c->pw_redone++;
                                                         return redo_forward_frame_staged(c, pending[i].stage, f, pending[i].max_src_x, pending[i].max_src_y, pending[i].out); }));
         if (any) {
-            HIP_TRY(c, hipMemsetAsync(c->d_fwd_status, 0, sizeof(int32_t) * c->fwd_status_cap, c->stream));   // (zero between calls)
+            HIP_TRY(c, hipMemsetAsync(c->d_fwd_status, 0, sizeof(int32_t) * c->d_fwd_status.cap, c->stream));   // (zero between calls)
             HIP_TRY(c, hipStreamSynchronize(c->stream));
         }
         learn_forward_tiles(c, overflow, unbounded);
@@ -880,7 +846,7 @@ static int single_frame_bytes(hg_ctx *c, size_t *bytes)
     HG_TRY(check_pw_state(c));
     if (c->pw_frames.size() != 1) return fail(c, HG_ERR_STATE, "this call needs exactly one prepared frame (hg_piecewise_prepare)");
     const FrameDesc &fd = c->pw_frames[0];
-    *bytes = (fd.obj_w > 0 && fd.obj_h > 0) ? (size_t)fd.obj_w * fd.obj_h * 4 : 0;
+    *bytes = frame_px(fd.obj_w, fd.obj_h) * 4;
     return HG_OK;
 }
 
@@ -893,7 +859,7 @@ extern "C" int hg_warp_inverse_piecewise(hg_ctx *c, uint8_t *out_host)
     if (bytes == 0) return HG_OK;
     const uint64_t keep = c->pw_frames[0].out_off;
     if (keep != 0) return fail(c, HG_ERR_STATE, "prepared frame has a non-zero output offset");
-    HG_TRY(ensure(c, c->d_out_tmp, c->out_tmp_cap, bytes));
+    HG_TRY(ensure(c, c->d_out_tmp, bytes));
     HG_TRY(hg_warp_inverse_piecewise_frames_device(c, c->d_out_tmp));
     HG_TRY(hg_sync(c));
     HIP_TRY(c, hipMemcpy(out_host, c->d_out_tmp, bytes, hipMemcpyDeviceToHost));
@@ -908,7 +874,7 @@ extern "C" int hg_warp_inverse_piecewise_via_map(hg_ctx *c, uint8_t *out_host)
     HG_TRY(single_frame_bytes(c, &bytes));
     if (bytes == 0) return HG_OK;
     HG_TRY(hg_sync(c));
-    HG_TRY(ensure(c, c->d_out_tmp, c->out_tmp_cap, bytes));
+    HG_TRY(ensure(c, c->d_out_tmp, bytes));
     HG_TRY(run_setup(c));
     HG_TRY(run_frame_via_map(c, 0, c->d_out_tmp));
     HIP_TRY(c, hipMemcpyAsync(out_host, c->d_out_tmp, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -926,8 +892,8 @@ extern "C" int hg_get_tri_map(hg_ctx *c, int16_t *out, size_t len)
     if (n == 0) return HG_OK;
     HG_TRY(hg_sync(c));
     HG_TRY(run_setup(c));
-    HG_TRY(ensure(c, c->d_map32, c->map32_cap, n));
-    HG_TRY(ensure(c, c->d_map16, c->map16_cap, n));
+    HG_TRY(ensure(c, c->d_map32, n));
+    HG_TRY(ensure(c, c->d_map16, n));
     launch_map_build(mesh_of(c), frames_of(c), 0, c->pw_frames[0], c->d_map32, c->stream);
     launch_map_to_i16(c->d_map32, c->d_map16, n, c->stream);
     HIP_TRY(c, hipGetLastError());
@@ -945,8 +911,8 @@ extern "C" int hg_get_tri_map_fused(hg_ctx *c, int16_t *out, size_t len)
     if (!out || len != n) return fail(c, HG_ERR_INVALID, "hg_get_tri_map_fused: len must be obj_w*obj_h");
     if (n == 0) return HG_OK;
     HG_TRY(hg_sync(c));
-    HG_TRY(ensure(c, c->d_out_tmp, c->out_tmp_cap, bytes));
-    HG_TRY(ensure(c, c->d_map16, c->map16_cap, n));
+    HG_TRY(ensure(c, c->d_out_tmp, bytes));
+    HG_TRY(ensure(c, c->d_map16, n));
     HG_TRY(run_setup(c, true));
     run_warp(c, c->d_out_tmp, c->d_map16);
     HIP_TRY(c, hipGetLastError());
@@ -968,9 +934,9 @@ extern "C" int hg_get_matrices(hg_ctx *c, float *fwd, float *inv)
     if (!c->pw_setup_done) HG_TRY(run_setup(c));
     const size_t T = (size_t)c->n_tris;
     if (T == 0) return HG_OK;
-    if (fwd) HIP_TRY(c, hipMemcpyAsync(fwd, c->d_fwd, sizeof(float) * 6 * T, hipMemcpyDeviceToHost, c->stream));
+    if (fwd) HIP_TRY(c, hipMemcpyAsync(fwd, c->solve.fwd, sizeof(float) * 6 * T, hipMemcpyDeviceToHost, c->stream));
     std::vector<float> tmp;
-    if (inv) { tmp.resize(T * kInvStride); HIP_TRY(c, hipMemcpyAsync(tmp.data(), c->d_inv, sizeof(float) * kInvStride * T, hipMemcpyDeviceToHost, c->stream)); }
+    if (inv) { tmp.resize(T * kInvStride); HIP_TRY(c, hipMemcpyAsync(tmp.data(), c->solve.inv, sizeof(float) * kInvStride * T, hipMemcpyDeviceToHost, c->stream)); }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (inv) for (size_t t = 0; t < T; t++) std::memcpy(inv + 6 * t, tmp.data() + kInvStride * t, sizeof(float) * 6);
     return HG_OK;

@@ -21,12 +21,6 @@ extern "C" int hg_solve_affine_triangles(const float *src, const float *dst, int
     return HG_OK;
 }
 
-static bool state_coords_ok(const float *p, size_t n)
-{
-    for (size_t i = 0; i < n; i++) if (std::fabs((double)p[i]) > kMaxCoord) return false;      // (NaN compares false: legal)
-    return true;
-}
-
 // The Int16Array the shared field holds, as int32 cells in c->d_map32: `cells` cells in all, the first width * height of them
 // rasterised from the map's own point set and triangles (fillTriangle :1111-1126 with TypedArray.fill's index rules against THAT
 // length), the rest -1 (reads past the end of the reference's array give `undefined`, which fails both `> -1` and `>= 0`).
@@ -34,38 +28,33 @@ static int build_state_map(hg_ctx *c, const hg_tri_map_def *map, size_t cells)
 {
     if (!map || map->n_points < 0 || map->n_triangles < 0 || (map->n_points > 0 && !map->points) || (map->n_triangles > 0 && !map->triangles))
         return fail(c, HG_ERR_INVALID, "reference-state warp: bad map definition");
-    if (!state_coords_ok(map->points, (size_t)map->n_points * 2))
+    if (!coords_ok(map->points, (size_t)map->n_points * 2))
         return fail(c, HG_ERR_INVALID, "reference-state warp: a map coordinate is infinite or beyond 2^24 in magnitude");
     const int64_t mw = map->width, mh = map->height;
     if (mw > 0 && mh > 0 && mw * mh >= ((int64_t)1 << 31)) return fail(c, HG_ERR_INVALID, "reference-state warp: the map has 2^31 cells or more");
     if (std::abs((int64_t)map->y_off) > ((int64_t)1 << 26)) return fail(c, HG_ERR_INVALID, "reference-state warp: map y offset beyond 2^26");
-    const size_t own = (mw > 0 && mh > 0) ? (size_t)(mw * mh) : 0;
-    HG_TRY(ensure(c, c->d_map32, c->map32_cap, std::max(std::max(own, cells), (size_t)1)));
+    const size_t own = frame_px(mw, mh);
+    HG_TRY(ensure(c, c->d_map32, std::max(std::max(own, cells), (size_t)1)));
     if (cells > own) launch_fill_i32(c->d_map32 + own, cells - own, -1, c->stream);
     if (own == 0) { HIP_TRY(c, hipGetLastError()); return HG_OK; }
     const size_t T = (size_t)std::max(map->n_triangles, 1), N = (size_t)std::max(map->n_points, 1);
-    HG_TRY(ensure(c, c->d_st_pts, c->st_pts_cap, N * 2));
-    HG_TRY(ensure(c, c->d_st_tris, c->st_tris_cap, T * 3));
-    HG_TRY(ensure(c, c->d_redo_frame, c->redo_frame_cap, (size_t)1));
-    HG_TRY(ensure(c, c->d_redo_trir, c->redo_trir_cap, T));
-    HG_TRY(ensure(c, c->d_redo_trix, c->redo_trix_cap, T));
-    HG_TRY(ensure(c, c->d_redo_segs, c->redo_segs_cap, T * 3));
-    HG_TRY(ensure(c, c->d_redo_fwd, c->redo_fwd_cap, T * 6));
-    HG_TRY(ensure(c, c->d_redo_inv, c->redo_inv_cap, T * kInvStride));
-    HG_TRY(ensure(c, c->d_redo_status, c->redo_status_cap, (size_t)1));
+    HG_TRY(ensure(c, c->d_st_pts, N * 2));
+    HG_TRY(ensure(c, c->d_st_tris, T * 3));
+    HG_TRY(ensure(c, c->d_redo_frame, (size_t)1));
+    HG_TRY(c->redo.ensure(c, 1, T));
     FrameDesc fd; fd.x_off = 0; fd.y_off = map->y_off; fd.obj_w = map->width; fd.obj_h = map->height; fd.out_off = 0; fd.map_off = 0;
     if (map->n_points > 0) HIP_TRY(c, hipMemcpyAsync(c->d_st_pts, map->points, sizeof(float) * 2 * (size_t)map->n_points, hipMemcpyHostToDevice, c->stream));
     if (map->n_triangles > 0) HIP_TRY(c, hipMemcpyAsync(c->d_st_tris, map->triangles, sizeof(uint32_t) * 3 * (size_t)map->n_triangles, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_redo_frame, &fd, sizeof fd, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_redo_status, 0, sizeof(int32_t), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->redo.status, 0, sizeof(int32_t), c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));             // (fd is local, the caller's arrays are not retained)
     PwMesh mesh = mesh_of(c);
     mesh.src_pts = c->d_st_pts; mesh.tris = c->d_st_tris; mesh.n_pts = map->n_points; mesh.n_tris = map->n_triangles;
     PwFrames fr = frames_of(c);
     fr.two_round = nullptr;                                  // (a set-up of its own, outside the frame set's step numbering)
     fr.src_pts = nullptr; fr.min_src = nullptr;              // (the caller's state, not the uploaded frame set's source side)
-    fr.frames = c->d_redo_frame; fr.dst_pts = c->d_st_pts; fr.trir = c->d_redo_trir; fr.trix = c->d_redo_trix; fr.band_ent = nullptr; fr.host_flag = nullptr;
-    fr.segs = c->d_redo_segs; fr.fwd = c->d_redo_fwd; fr.inv = c->d_redo_inv; fr.status = c->d_redo_status; fr.n_frames = 1; fr.max_obj_h = fd.obj_h;
+    fr.frames = c->d_redo_frame; fr.dst_pts = c->d_st_pts; c->redo.point(fr); fr.band_ent = nullptr; fr.host_flag = nullptr;
+    fr.n_frames = 1; fr.max_obj_h = fd.obj_h;
     if (map->n_triangles > 0) launch_tri_setup(mesh, fr, c->stream);       // edge equations + row ranges of the map's own triangles (its solves are not used)
     launch_map_build(mesh, fr, 0, fd, c->d_map32, c->stream);               // :822 / :850 fill(-1), then the rasteriser
     HIP_TRY(c, hipGetLastError());
@@ -75,10 +64,10 @@ static int build_state_map(hg_ctx *c, const hg_tri_map_def *map, size_t cells)
 // Would a cell the loop reads name a matrix that does not exist?  (-> HG_ERR_RANGE: the reference throws at that pixel.)
 static int check_state_ids(hg_ctx *c, size_t cells_read, int n_mats)
 {
-    HG_TRY(ensure(c, c->d_redo_status, c->redo_status_cap, (size_t)1));
-    launch_map_max_i16(c->d_map32, cells_read, c->d_redo_status, c->stream);
+    HG_TRY(ensure(c, c->redo.status, (size_t)1));
+    launch_map_max_i16(c->d_map32, cells_read, c->redo.status, c->stream);
     int32_t top = -1;
-    HIP_TRY(c, hipMemcpyAsync(&top, c->d_redo_status, sizeof top, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&top, c->redo.status, sizeof top, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (top >= n_mats) return fail(c, HG_ERR_RANGE, "reference-state warp: the map names triangle " + std::to_string(top) + " but only " + std::to_string(n_mats) +
                                                      " matrices exist (the reference throws a TypeError at that pixel)");
@@ -93,7 +82,7 @@ static int state_common(hg_ctx *c, const float *fwd_mats, int n_mats, hg_geom ge
     std::vector<FrameDesc> one;
     const size_t zero = 0;
     HG_TRY(fill_frames(c, one, &geom, &zero, 1));            // (the window limits of every other entry point)
-    *bytes = (geom.obj_w > 0 && geom.obj_h > 0) ? (size_t)geom.obj_w * geom.obj_h * 4 : 0;
+    *bytes = frame_px(geom.obj_w, geom.obj_h) * 4;
     HG_TRY(hg_sync(c));                                      // queued runs own the scratch buffers used below
     return HG_OK;
 }
@@ -113,8 +102,8 @@ extern "C" int hg_warp_inverse_piecewise_state(hg_ctx *c, const float *fwd_mats,
     const size_t T = (size_t)std::max(n_mats, 1);
     std::vector<float> inv(T * kInvStride, 0.f);
     for (int t = 0; t < n_mats; t++) invert_affine(fwd_mats + 6 * (size_t)t, inv.data() + kInvStride * (size_t)t);
-    HG_TRY(ensure(c, c->d_st_mats, c->st_mats_cap, T * kInvStride));
-    HG_TRY(ensure(c, c->d_out_tmp, c->out_tmp_cap, bytes));
+    HG_TRY(ensure(c, c->d_st_mats, T * kInvStride));
+    HG_TRY(ensure(c, c->d_out_tmp, bytes));
     HIP_TRY(c, hipMemcpyAsync(c->d_st_mats, inv.data(), sizeof(float) * inv.size(), hipMemcpyHostToDevice, c->stream));
     PwMesh mesh = mesh_of(c);
     mesh.img = frame_img(mesh, 0); mesh.n_imgs = 1; mesh.min_src_x = msx; mesh.min_src_y = msy; mesh.n_tris = n_mats;
@@ -140,18 +129,18 @@ extern "C" int hg_warp_forward_piecewise_state(hg_ctx *c, const float *fwd_mats,
         if (bw * bh >= ((int64_t)1 << 31)) return fail(c, HG_ERR_INVALID, "the source-point bounding box has 2^31 pixels or more: the forward path ranks source pixels in 32 bits");
         if (bh > 65535) return fail(c, HG_ERR_INVALID, "the source-point bounding box is taller than 65535 rows: not supported by the forward path");
     }
-    const size_t cells = (bw > 0 && bh > 0) ? (size_t)(bw * bh) : 0;
+    const size_t cells = frame_px(bw, bh);
     HG_TRY(build_state_map(c, map, cells));
-    const size_t own = (map->width > 0 && map->height > 0) ? (size_t)map->width * map->height : 0;
+    const size_t own = frame_px(map->width, map->height);
     HG_TRY(check_state_ids(c, std::min(own, cells), n_mats));
     // A blank output window (:440) does not stop the reference's loop: it still walks the source bounding box, reads the held map and
     // throws at a cell that names a missing matrix -- hence the check above runs first; with every id in range the loop's stores all
     // miss the empty array and nothing is left to do.
     if (bytes == 0) return HG_OK;
     const size_t T = (size_t)std::max(n_mats, 1);
-    HG_TRY(ensure(c, c->d_st_mats, c->st_mats_cap, T * kInvStride));
-    HG_TRY(ensure(c, c->d_out_tmp, c->out_tmp_cap, bytes));
-    HG_TRY(ensure(c, c->d_win32, c->win32_cap, bytes / 4));
+    HG_TRY(ensure(c, c->d_st_mats, T * kInvStride));
+    HG_TRY(ensure(c, c->d_out_tmp, bytes));
+    HG_TRY(ensure(c, c->d_win32, bytes / 4));
     if (n_mats > 0) HIP_TRY(c, hipMemcpyAsync(c->d_st_mats, fwd_mats, sizeof(float) * 6 * (size_t)n_mats, hipMemcpyHostToDevice, c->stream));
     FrameDesc fd; fd.x_off = geom.x_off; fd.y_off = geom.y_off; fd.obj_w = geom.obj_w; fd.obj_h = geom.obj_h; fd.out_off = 0; fd.map_off = 0;
     launch_fwd_pw(c->d_map32, c->d_st_mats, frame_img(mesh_of(c), 0), c->W, c->H, msx, msy, (int)std::max<int64_t>(bw, 0), (int)std::max<int64_t>(bh, 0),

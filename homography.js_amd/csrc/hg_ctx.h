@@ -1,9 +1,10 @@
 // hg_ctx.h -- the context behind the C ABI of include/hgwarp.h and the helpers its translation units share
 // (hg_api.hip: library / context / buffers / host-side solves / source image; hg_api_geometric.hip; hg_api_piecewise.hip;
-// hg_api_forward.hip; hg_api_state.hip; hg_api_field.hip).  Internal: nothing here is exported.
+// hg_api_forward.hip; hg_api_state.hip; hg_api_field.hip).  Its memory is owned through hg_mem.h.  Internal: nothing here is exported.
 #pragma once
 #include "../../include/hgwarp.h"
 #include "hg_kernels.h"
+#include "hg_mem.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -61,6 +62,19 @@ struct PwPlan {
     int tri_group = 0, phase = 2, xcc_rotate = 0, sub_bands = 0, sgpr_cap = 1, lds_pad_kb = 0, no_hi_bounds = 0, safe_spans = 0, safe_spans_patch = 1;
 };
 
+// The per-triangle solve arrays of F frames of T triangles (k_tri_setup / k_tri_spans write them): the frame set's, and the one-frame scratch
+// of the deferred redo and the reference-state maps.
+struct PwSolve {
+    DevBuf<TriRange> trir; DevBuf<int2> trix; DevBuf<Seg> segs; DevBuf<float> fwd, inv; DevBuf<int32_t> status;
+    int ensure(hg_ctx *c, size_t F, size_t T)
+    {
+        HG_TRY(::ensure(c, trir, F * T)); HG_TRY(::ensure(c, trix, F * T)); HG_TRY(::ensure(c, segs, F * T * 3));
+        HG_TRY(::ensure(c, fwd, F * T * 6)); HG_TRY(::ensure(c, inv, F * T * kInvStride));
+        return ::ensure(c, status, F);
+    }
+    void point(PwFrames &f) const { f.trir = trir; f.trix = trix; f.segs = segs; f.fwd = fwd; f.inv = inv; f.status = status; }
+};
+
 struct hg_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -73,13 +87,13 @@ struct hg_ctx {
     int deferred = HG_OK;
 
     // source image
-    uint8_t *d_img = nullptr; size_t img_cap = 0; bool img_aliased = false;
+    DevBuf<uint8_t> d_img;                                     // owned (hg_set_image) or borrowed from the caller (hg_set_image_device)
     int W = 0, H = 0;
     int n_imgs = 1; size_t img_stride = 0;                     // hg_set_images_device: frame f reads image f % n_imgs
 
     // mesh (source side)
-    float *d_src = nullptr; size_t src_cap = 0;
-    uint32_t *d_tris = nullptr; size_t tris_cap = 0;
+    DevBuf<float> d_src;
+    DevBuf<uint32_t> d_tris;
     std::vector<uint32_t> h_tris;                              // host copies (row-density / shear estimates in hg_piecewise_set_frames)
     std::vector<float> h_src;
     int n_pts = 0, n_tris = 0, min_src_x = 0, min_src_y = 0;
@@ -87,7 +101,7 @@ struct hg_ctx {
 
     // piecewise frames
     std::vector<FrameDesc> pw_frames;          // host copy
-    uint8_t *d_set = nullptr; size_t set_cap = 0;             // the frame set in ONE block: F frame records, then F x n_pts x 2 destiny floats (one upload)
+    DevBuf<uint8_t> d_set;                                     // the frame set in ONE block: F frame records, then F x n_pts x 2 destiny floats (one upload)
     FrameDesc *d_pw_frames = nullptr;                         // = d_set
     float *d_dst = nullptr;                                   // = d_set + F * sizeof(FrameDesc)
     // a frame set with a source side of its own (hg_piecewise_set_frames_src): F x n_pts x 2 source floats and F {minSrcX, minSrcY} pairs behind the
@@ -95,20 +109,15 @@ struct hg_ctx {
     bool pw_moving = false;
     float *d_srcf = nullptr; int2 *d_min_src = nullptr;
     int ms_lo_x = 0, ms_hi_x = 0, ms_lo_y = 0, ms_hi_y = 0;
-    TriRange *d_trir = nullptr; size_t trir_cap = 0;
-    int2 *d_trix = nullptr; size_t trix_cap = 0;
-    Seg *d_segs = nullptr; size_t segs_cap = 0;
-    float *d_fwd = nullptr; size_t fwd_cap = 0;
-    float *d_inv = nullptr; size_t inv_cap = 0;
-    int32_t *d_status = nullptr; size_t status_cap = 0;
-    int32_t *d_two_round = nullptr; size_t two_round_cap = 0; int32_t pw_gen = 0;   // PwFrames::two_round / gen
-    int32_t *status_ptr = nullptr;                             // where this frame set's status words live (d_status, or the tail of d_rowcnt)
-    int32_t *h_status = nullptr; size_t h_status_cap = 0;      // pinned
-    int32_t *h_flag = nullptr;                                 // pinned, device-visible: set to 1 by any fused kernel that flags a frame (PwFrames::host_flag)
+    PwSolve solve;                                             // the per-triangle solves of the frame set
+    DevBuf<int32_t> d_two_round; int32_t pw_gen = 0;           // PwFrames::two_round / gen
+    int32_t *status_ptr = nullptr;                             // where this frame set's status words live (solve.status, or the tail of d_rowcnt)
+    PinnedBuf<int32_t> h_status;                               // kStatusRing sets of status words, read back by hg_sync
+    PinnedBuf<int32_t> h_flag;                                 // device-visible: set to 1 by any fused kernel that flags a frame (PwFrames::host_flag)
     bool pw_setup_done = false;                                // the per-triangle solves ran for the uploaded frames
     // fast path: per-output-row span lists
-    int32_t *d_rowcnt = nullptr; size_t rowcnt_cap = 0;
-    uint8_t *d_rowent = nullptr; size_t rowent_cap = 0;        // bytes
+    DevBuf<int32_t> d_rowcnt;
+    DevBuf<uint8_t> d_rowent;                                  // bytes
     int row_cap = 64;                                          // entries per row; grows (sticky) after an overflow
     bool rows_clean = false;                                   // span counters + the next status set were zeroed by the last k_pw_rows
     int status_slot = 0;                                       // which of the kStatusRing status-word sets the current step uses
@@ -140,32 +149,24 @@ struct hg_ctx {
     // points; `moving` sets: then the F x n_pts x 2 source points and the F source minima): hg_piecewise_set_frames copies the caller's arrays there and queues stream-ordered uploads -- it neither waits
     // for the GPU nor keeps caller memory.  A staged set stays intact until every run that used it has been settled, so frames a
     // fused run flagged can still be redone (through the materialised map) after newer sets were uploaded.
-    // `done` is recorded behind the slot's upload: the slot's bytes are not rewritten before the DMA that reads them has run
-    // (paths that keep no pending record -- the forward scatter path -- could otherwise lap the ring with uploads still queued)
-    struct Stage { uint8_t *h = nullptr; size_t cap = 0; int n = 0, n_pts = 0; hipEvent_t done = nullptr; bool used = false; bool moving = false; };
-    Stage stage[kStatusRing];
-    int stage_cur = -1;
+    // (StageRing, hg_mem.h; n / n_pts / moving: what the deferred redo needs to find a frame in the slot)
+    struct Stage : StageSlot { int n = 0, n_pts = 0; bool moving = false; };
+    StageRing<(int)kStatusRing, Stage> stage;
     // scratch of the deferred redo (one frame): its FrameDesc, points, solves
-    FrameDesc *d_redo_frame = nullptr; size_t redo_frame_cap = 0;
-    float *d_redo_dst = nullptr; size_t redo_dst_cap = 0;
-    float *d_redo_src = nullptr; size_t redo_src_cap = 0;      // (frames of a set with its own source side)
-    int2 *d_redo_min = nullptr; size_t redo_min_cap = 0;
-    TriRange *d_redo_trir = nullptr; size_t redo_trir_cap = 0;
-    int2 *d_redo_trix = nullptr; size_t redo_trix_cap = 0;
-    Seg *d_redo_segs = nullptr; size_t redo_segs_cap = 0;
-    float *d_redo_fwd = nullptr; size_t redo_fwd_cap = 0;
-    float *d_redo_inv = nullptr; size_t redo_inv_cap = 0;
-    int32_t *d_redo_status = nullptr; size_t redo_status_cap = 0;
+    DevBuf<FrameDesc> d_redo_frame;
+    DevBuf<float> d_redo_dst, d_redo_src;                      // (d_redo_src, d_redo_min: frames of a set with its own source side)
+    DevBuf<int2> d_redo_min;
+    PwSolve redo;
     // reference-state warps (hg_api_state.hip): the map's own point set and triangles, the cached matrices handed over by the caller
-    float *d_st_pts = nullptr; size_t st_pts_cap = 0;
-    uint32_t *d_st_tris = nullptr; size_t st_tris_cap = 0;
-    float *d_st_mats = nullptr; size_t st_mats_cap = 0;
+    DevBuf<float> d_st_pts;
+    DevBuf<uint32_t> d_st_tris;
+    DevBuf<float> d_st_mats;
     // layout of the row counters / status ring as of their last memset (a frame set with the same layout reuses them as they are)
     size_t rows_F = 0; int rows_stride = 0, rows_cap = 0;
     // self-span path (k_tri_setup -> k_pw_rows<SELF>, hg_kernels.h): the row workgroups evaluate their own spans, no row lists
     int pw_last_variant = 0;                                   // variant code of the last piecewise warp kernel launched (launch_pw_rows; hg_last_piecewise_variant)
     int opt_tile = -1;                                         // option "tile": 1 whenever k_pw_patch<SELF> would run, 0 never, -1 by policy
-    int4 *d_bands = nullptr; size_t bands_cap = 0;             // F x n_bands x band_cap entries of the candidate bands (hg_kernels.h)
+    DevBuf<int4> d_bands;                                      // F x n_bands x band_cap entries of the candidate bands (hg_kernels.h)
     int band_cap = 0;                                          // entries per band; grows (sticky)
     int opt_self = -1;                                         // option "self_spans": 1 whenever eligible, 0 never, -1 by policy (plan_piecewise)
     int rows_parity = 0;                                       // which of the two counter sets the current step counts into (ping-pong, hg_kernels.h)
@@ -179,40 +180,37 @@ struct hg_ctx {
 
     // geometric frame sets arrive like the piecewise ones: copied into page-locked staging, uploaded stream-ordered, no GPU wait
     // (nothing refers back to a staged geometric set, so a slot is simply reused once its own upload has completed)
-    struct GeoStage { uint8_t *h = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false; };
-    GeoStage geo_stage[8];
-    int geo_stage_cur = -1;
+    StageRing<8> geo_stage;
     // geometric frames
     int geo_kind = 0;
     bool geo_f32_exact = false;                                // affine matrices hold float values, |x| < 2^28
     std::vector<FrameDesc> geo_frames;
-    FrameDesc *d_geo_frames = nullptr; size_t geo_frames_cap = 0;
-    double *d_mats = nullptr; size_t mats_cap = 0;
+    DevBuf<FrameDesc> d_geo_frames;
+    DevBuf<double> d_mats;
     bool geo_from_points = false;                              // matrices are (re)solved on the device at every warp (hg_geometric_set_frames_points)
-    float *d_geo_pts = nullptr; size_t geo_pts_cap = 0;        // F x (from | to) point sets
-    int32_t *d_geo_plain = nullptr; size_t geo_plain_cap = 0;  // per-frame "plain division range" flags written by k_solve_frames
+    DevBuf<float> d_geo_pts;                                   // F x (from | to) point sets
+    DevBuf<int32_t> d_geo_plain;                               // per-frame "plain division range" flags written by k_solve_frames
 
     // source fields (hg_api_field.hip): the frame records of a set with the FIELD offsets in out_off, staged like a geometric set
-    FrameDesc *d_field_frames = nullptr; size_t field_frames_cap = 0;
-    GeoStage field_stage[4];
-    int field_stage_cur = -1;
-    uint8_t *d_field_tmp = nullptr; size_t field_tmp_cap = 0; // the host-output forms' device copy
-    RemapFrame *d_remap_frames = nullptr; size_t remap_frames_cap = 0;   // the frame table of a frames remap (hg_remap_*_frames_device), staged through field_stage
+    DevBuf<FrameDesc> d_field_frames;
+    StageRing<4> field_stage;
+    DevBuf<uint8_t> d_field_tmp;                               // the host-output forms' device copy
+    DevBuf<RemapFrame> d_remap_frames;                         // the frame table of a frames remap (hg_remap_*_frames_device), staged through field_stage
     int opt_remap_pack = -1;                                   // k_remap_index_frames: 0 = one pixel per lane even for the pixel sizes that carry the packed form (measurements)
 
     // scratch
-    int32_t *d_map32 = nullptr; size_t map32_cap = 0;
-    int32_t *d_fmap = nullptr; size_t fmap_cap = 0;            // forward (source-side) triangle map of the current mesh, kept across warps
+    DevBuf<int32_t> d_map32;
+    DevBuf<int32_t> d_fmap;                                    // forward (source-side) triangle map of the current mesh, kept across warps
     bool fmap_valid = false; int fmap_w = 0, fmap_h = 0;
-    int32_t *d_win32 = nullptr; size_t win32_cap = 0;
-    uint8_t *d_fwd_par = nullptr; size_t fwd_par_cap = 0;      // k_fwd_tiles: FwdParam[n] then FrameDesc[n]
-    int32_t *d_fbbox = nullptr; size_t fbbox_cap = 0;          // forward piecewise tiles: per-matrix cell bbox of the forward map (valid with it)
-    uint32_t *d_frowoff = nullptr; size_t frowoff_cap = 0;     // ... offset of its per-row extents
-    int32_t *d_frowext = nullptr; size_t frowext_cap = 0;      // ... {min mx, max mx} per (matrix index, map row of its bbox)
+    DevBuf<int32_t> d_win32;
+    DevBuf<uint8_t> d_fwd_par;                                 // k_fwd_tiles: FwdParam[n] then FrameDesc[n]
+    DevBuf<int32_t> d_fbbox;                                   // forward piecewise tiles: per-matrix cell bbox of the forward map (valid with it)
+    DevBuf<uint32_t> d_frowoff;                                // ... offset of its per-row extents
+    DevBuf<int32_t> d_frowext;                                 // ... {min mx, max mx} per (matrix index, map row of its bbox)
     bool fwd_rowext_ok = false;
-    int32_t *d_ftile_cnt = nullptr; size_t ftile_cnt_cap = 0;  // F x tiles counters (zero between calls)
-    int32_t *d_fwd_status = nullptr; size_t fwd_status_cap = 0, fwd_status_stride = 0;   // kFwdStatusRing sets of `stride` status words of tile-binned forward piecewise batches (zero between calls)
-    int32_t *d_ftile_ent = nullptr; size_t ftile_ent_cap = 0;  // F x tiles x fwd_pw_cap entries
+    DevBuf<int32_t> d_ftile_cnt;                               // F x tiles counters (zero between calls)
+    DevBuf<int32_t> d_fwd_status; size_t fwd_status_stride = 0;   // kFwdStatusRing sets of `stride` status words of tile-binned forward piecewise batches (zero between calls)
+    DevBuf<int32_t> d_ftile_ent;                               // F x tiles x fwd_pw_cap entries
     int fwd_pw_cap = 64;                                       // entries per tile (doubles after an overflow, up to kFwdPwCapMax)
     bool fwd_pw_tiles_disabled = false;                        // overflowed at the largest capacity once: stay with the scatter path for this mesh
     // queued tile-binned forward piecewise batches: status set `slot` of the forward status ring, frame set in staging slot `stage`
@@ -222,9 +220,9 @@ struct hg_ctx {
     int opt_fwd_tiles = -1;                                    // forward paths: -1 auto, 0 scatter + gather, 1 tiles whenever admissible
     int fwd_last_kernel = 0;                                   // 1 scatter + gather, 2 k_fwd_tiles (hg_last_kernel-style tap for the tests)
     int fwd_field_last_kernel = 0;                             // the same tap of the forward FIELD calls (hg_last_forward_field_kernel): they leave fwd_last_kernel alone
-    int32_t *d_ffield_status = nullptr; size_t ffield_status_cap = 0;   // status words of ONE forward piecewise field call (read inside the call; not the ring of queued warps)
-    int16_t *d_map16 = nullptr; size_t map16_cap = 0;
-    uint8_t *d_out_tmp = nullptr; size_t out_tmp_cap = 0;
+    DevBuf<int32_t> d_ffield_status;                           // status words of ONE forward piecewise field call (read inside the call; not the ring of queued warps)
+    DevBuf<int16_t> d_map16;
+    DevBuf<uint8_t> d_out_tmp;
 
     // timing of the dominant kernel: a ring of event pairs recorded around each launch of it
     static constexpr int kEvRing = 256;
@@ -240,14 +238,28 @@ inline int fail(hg_ctx *c, int code, const std::string &msg)
     return code;
 }
 
-#define HIP_TRY(c, expr)                                                                                     \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess)                                                                                \
-            return fail((c), HG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                 \
-    } while (0)
+inline hipStream_t stream_of(const hg_ctx *c) { return c->stream; }
 
-#define HG_TRY(expr) do { int s_ = (expr); if (s_ != HG_OK) return s_; } while (0)
+// Pixels of a w x h window (none if either is not positive); `bytes` rounded up to the 256-byte grain frames are packed at.
+inline size_t frame_px(int64_t w, int64_t h) { return (w > 0 && h > 0) ? (size_t)w * (size_t)h : 0; }
+inline size_t pad256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+// n windows of px_bytes per pixel packed back to back at that grain (offsets, total: either may be NULL).
+inline void pack_offsets(const hg_geom *g, int n, size_t px_bytes, size_t *offsets, size_t *total)
+{
+    size_t off = 0;
+    for (int i = 0; i < n; i++) {
+        if (offsets) offsets[i] = off;
+        off += pad256(frame_px(g[i].obj_w, g[i].obj_h) * px_bytes);
+    }
+    if (total) *total = off;
+}
+// NaN is a legal (if useless) coordinate -- the reference then simply draws nothing for that triangle -- but magnitudes beyond
+// kMaxCoord (Infinity included) are refused: the row loops of the rasterisers are bounded under that assumption (hg_math.h).
+inline bool coords_ok(const float *p, size_t n)
+{
+    for (size_t i = 0; i < n; i++) if (std::fabs((double)p[i]) > kMaxCoord) return false;      // (NaN compares false)
+    return true;
+}
 
 // A staged block (page-locked, device-visible) to the device, stream-ordered: up to 1 MB by k_upload -- a kernel that reads the host block --,
 // beyond that (or with option "upload_kernel" = 0) by the copy engine, whose start-up latency is what a 36-KB frame set paid for (R4.13).
@@ -264,19 +276,6 @@ inline int upload_staged(hg_ctx *c, void *d0, const void *s0, size_t b0, void *d
         if (b1) HIP_TRY(c, hipMemcpyAsync(d1, s1, b1, hipMemcpyHostToDevice, c->stream));
         if (b2) HIP_TRY(c, hipMemcpyAsync(d2, s2, b2, hipMemcpyHostToDevice, c->stream));
     }
-    return HG_OK;
-}
-
-template <typename T>
-inline int ensure(hg_ctx *c, T *&p, size_t &cap, size_t need)
-{
-    if (need <= cap) return HG_OK;
-    const size_t n = std::max(need, cap + cap / 2);          // geometric growth from the OLD capacity
-    if (p) { HIP_TRY(c, hipStreamSynchronize(c->stream)); HIP_TRY(c, hipFree(p)); p = nullptr; cap = 0; }
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, n * sizeof(T));
-    if (e != hipSuccess) return fail(c, HG_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    p = static_cast<T *>(q); cap = n;
     return HG_OK;
 }
 
