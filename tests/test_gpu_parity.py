@@ -298,7 +298,8 @@ def _fwd_pw_oracle(sp, dp, tris, img, geom):
 def test_forward_piecewise_tiles_match_scatter_and_oracle():
     """The tile-binned forward piecewise warp (k_fwd_pw_bins + k_fwd_pw_tiles) == scatter + gather == the oracle's sequential
     loop: jittered / folded / shuffled meshes, source bbox off the image corner, degenerate source triangles (Inf / NaN matrices:
-    the frame is flagged on the device and redone by hg_sync), tile lists that overflow (capacity grows), 4K frames and batches."""
+    the frame is flagged on the device and redone by hg_sync), tile lists that overflow (capacity grows), 4K frames and batches.
+    (Every mesh here is a positive scale of its source; turns, mirrors, shears and slopes: tests/test_gpu_forward_turns.py.)"""
     rng = np.random.default_rng(31337)
     c = HG.Context(0)
     try:
