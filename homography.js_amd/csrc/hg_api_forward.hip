@@ -245,22 +245,16 @@ static int settle_forward_field_tiles(hg_ctx *c, const FwdPwTiles &p, int n, int
     return HG_OK;
 }
 
-// _piecewiseAffineWarp :948-972 for n destination point sets on the current mesh (the caller loop `setDestinyPoints(d_f); warp()`
-// when warp() takes the forward path, :421), asynchronous, frames in GPU memory.
-// field: the frames' SOURCE FIELDS instead (hg_field_forward_piecewise_batch_device): same limits, same staging, same forward map, same path
-// selection.  Unlike a warp the field call leaves no deferred redo behind: queued runs are settled first by hg_sync (they keep their own
-// results and their own status sets; a deferred error of theirs is returned here, as hg_sync would return it, and the field is then not
-// computed), and the tile path is settled inside the call (settle_forward_field_tiles).  The scatter path has nothing to redo: its launches
-// are queued on the stream like a warp's.
-static int forward_piecewise_batch(hg_ctx *c, const float *dst_points, int max_src_x, int max_src_y, const hg_geom *geoms,
-                                   const size_t *offs, int n, void *d_out, bool field)
+// Steps (A) and (B) of a forward piecewise call, shared by the warps, the fields and the point lists (hg_api_points.hip): the state checks
+// and limits, the forward triangle map of the mesh (built once and cached), then the call's frame set staged and k_tri_setup queued for its
+// forward matrices.  field: the call settles queued runs first (the field and point-list forms).  *map_w / *map_h: the map's size in cells.
+int forward_piecewise_stage(hg_ctx *c, const float *dst_points, int max_src_x, int max_src_y, const hg_geom *geoms, const size_t *offs, int n,
+                            bool field, int64_t *map_w_out, int64_t *map_h_out)
 {
-    HG_TRY(bind(c));
-    if (!dst_points || !geoms || n <= 0 || !d_out)
-        return fail(c, HG_ERR_INVALID, field ? "hg_field_forward_piecewise: bad arguments" : "hg_warp_forward_piecewise: bad arguments");
     if (!c->d_img) return fail(c, HG_ERR_STATE, "no source image: call hg_set_image first");
     if (!c->have_mesh) return fail(c, HG_ERR_STATE, "no mesh: call hg_piecewise_set_mesh first");
     const int64_t map_w = (int64_t)max_src_x - c->min_src_x, map_h = (int64_t)max_src_y - c->min_src_y;
+    *map_w_out = map_w; *map_h_out = map_h;
     HG_TRY(forward_limits(c, map_w, map_h, "the source-point bounding box"));
     if (field) {
         if ((int64_t)c->W * c->H >= ((int64_t)1 << 31)) return fail(c, HG_ERR_INVALID, "the source image has 2^31 pixels or more (an int32 cannot index it)");
@@ -292,6 +286,25 @@ static int forward_piecewise_batch(hg_ctx *c, const float *dst_points, int max_s
     c->status_ptr = c->solve.status;                             // (k_tri_setup only ORs flags into these words and nothing on the forward path reads them: not cleared)
     { PwFrames fr_ = frames_of(c); fr_.band_ent = nullptr; fr_.two_round = nullptr; launch_tri_setup(mesh_of(c), fr_, c->stream); }   // (no candidate bands: the forward kernels have their own tile lists)
     c->pw_setup_done = false;
+    return HG_OK;
+}
+
+// _piecewiseAffineWarp :948-972 for n destination point sets on the current mesh (the caller loop `setDestinyPoints(d_f); warp()`
+// when warp() takes the forward path, :421), asynchronous, frames in GPU memory.
+// field: the frames' SOURCE FIELDS instead (hg_field_forward_piecewise_batch_device): same limits, same staging, same forward map, same path
+// selection.  Unlike a warp the field call leaves no deferred redo behind: queued runs are settled first by hg_sync (they keep their own
+// results and their own status sets; a deferred error of theirs is returned here, as hg_sync would return it, and the field is then not
+// computed), and the tile path is settled inside the call (settle_forward_field_tiles).  The scatter path has nothing to redo: its launches
+// are queued on the stream like a warp's.
+static int forward_piecewise_batch(hg_ctx *c, const float *dst_points, int max_src_x, int max_src_y, const hg_geom *geoms,
+                                   const size_t *offs, int n, void *d_out, bool field)
+{
+    HG_TRY(bind(c));
+    if (!dst_points || !geoms || n <= 0 || !d_out)
+        return fail(c, HG_ERR_INVALID, field ? "hg_field_forward_piecewise: bad arguments" : "hg_warp_forward_piecewise: bad arguments");
+    int64_t map_w = 0, map_h = 0;
+    HG_TRY(forward_piecewise_stage(c, dst_points, max_src_x, max_src_y, geoms, offs, n, field, &map_w, &map_h));
+    const size_t n_map = frame_px(map_w, map_h);
     size_t out_extent = 0;
     uint64_t out_layout = 0;
     output_layout(c->pw_frames, &out_extent, &out_layout);

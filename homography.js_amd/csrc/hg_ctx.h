@@ -315,3 +315,7 @@ PwMesh mesh_of(const hg_ctx *c);                             // hg_api_piecewise
 PwFrames frames_of(const hg_ctx *c);
 int check_pw_state(hg_ctx *c);                               // hg_api_piecewise.hip: image, mesh and frame set present?
 int redo_forward_frame_staged(hg_ctx *c, int stage, int f, int max_src_x, int max_src_y, uint8_t *d_out);    // hg_api_piecewise.hip, beside its inverse twin
+// hg_api_forward.hip: steps (A) and (B) of a forward piecewise call -- checks and limits, the cached forward triangle map, the frame set staged
+// and its forward matrices queued (k_tri_setup) -- for the warps, the fields and the point lists
+int forward_piecewise_stage(hg_ctx *c, const float *dst_points, int max_src_x, int max_src_y, const hg_geom *geoms, const size_t *offs, int n,
+                            bool field, int64_t *map_w, int64_t *map_h);

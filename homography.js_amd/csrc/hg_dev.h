@@ -133,6 +133,29 @@ __device__ __forceinline__ uint32_t pw_pixel(int tid_raw, int x, double y, MatCa
     return 0u;
 }
 
+// pw_pixel's arithmetic up to the coordinate and the bounds test, for consumers that want the coordinate itself at a position that need not
+// be a pixel (the point lists, hg_k_points.hip): the Int16Array conversion of the id, :1045, the triangle's inverse matrix (cached per lane
+// while the id repeats), applyAffineTransformToPoint :1383-1384 on (xd, y) and :1047.  false: no triangle, or outside the source window.
+// (pw_pixel and pw_pixel_bilinear keep their own text of these lines: folding them onto this function renumbers the registers of
+//  k_pw_from_map and k_pw_field, and their ISA is pinned.  The texts stay in step: tests/test_gpu_points.py compares this one with k_pw_field bit for bit.
+//  FOLLOW-UP: when the ISA of those kernels is next re-baselined (any change that touches k_pw_from_map / k_pw_field anyway), make pw_pixel,
+//  pw_pixel_bilinear and pw_field_px call pw_coord, so that the lines :1045-1047 / :1383-1384 exist once.)
+__device__ __forceinline__ bool pw_coord(int tid_raw, double xd, double y, MatCache &mc, const float *__restrict__ invm,
+                                         double bx0, double bx1, double by0, double by1, double &sx, double &sy)
+{
+    const int t16 = (int)(int16_t)tid_raw;          // Int16Array element conversion (ids >= 32768 wrap, Appendix A-Q9)
+    if (t16 < 0) return false;                      // :1045
+    if (t16 != mc.id) {
+        const float4 lo = *reinterpret_cast<const float4 *>(invm + (size_t)t16 * kInvStride);
+        const float2 hi = *reinterpret_cast<const float2 *>(invm + (size_t)t16 * kInvStride + 4);
+        mc.m[0] = lo.x; mc.m[1] = lo.y; mc.m[2] = lo.z; mc.m[3] = lo.w; mc.m[4] = hi.x; mc.m[5] = hi.y;
+        mc.id = t16;
+    }
+    sx = (mc.m[0] * xd) + (mc.m[2] * y) + mc.m[4];      // :1383
+    sy = (mc.m[1] * xd) + (mc.m[3] * y) + mc.m[5];      // :1384
+    return sx >= bx0 && sx < bx1 && sy >= by0 && sy < by1;              // :1047 (unrounded; NaN fails)
+}
+
 // ------------------------------------------------------------------------------------------------ bilinear sampling (HG_SAMPLE_BILINEAR)
 // Not the reference's: an opt-in mode of the inverse warps (include/hgwarp.h).  Straight RGBA, each channel in f32, contraction off:
 //   v = (p00*(1-fx) + p01*fx)*(1-fy) + (p10*(1-fx) + p11*fx)*fy,   out = min(255, floor(v + 0.5f))

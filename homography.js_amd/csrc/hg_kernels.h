@@ -198,6 +198,22 @@ void launch_remap_bilinear_frames(const RemapFrame *frames, const RemapFrame &on
                                   const uint8_t *coords, const uint8_t *planes, size_t plane_stride, int W, int H, int elem, int channels,
                                   uint8_t *out, hipStream_t stream);
 
+// Point lists (hg_k_points.hip; include/hgwarp.h hg_points_*): n_sets lists of n_points interleaved (x, y) floats, frame f reads list
+// f % n_sets and writes n_points (x, y) pairs at f * n_points of `out`; an unmapped point is the quiet NaN of HG_FIELD_COORDS in both words.
+// k_geo_points<kind, dir>: dir 0 = to source (mats: the inverse matrices, W x H the source's size: coverage test :1001), dir 1 = to output
+// (mats: the forward matrices, W x H the domain of the loop :919-920).  frames: x_off, y_off, obj_w, obj_h of every frame are read.
+void launch_geo_points(int kind, int dir, const FrameDesc *frames, const double *mats, int n_frames, int W, int H, const float *points, int n_points,
+                       int n_sets, float *out, hipStream_t stream);
+// k_pw_points_src: to source through the staged piecewise set, behind k_tri_setup, no map; frames flagged FRAME_IRREGULAR are left to
+// k_points_from_map: ONE frame (index f) from the map launch_map_build materialised.  points / out: the bases of all lists / all results.
+void launch_pw_points_src(const PwMesh &mesh, const PwFrames &fr, const float *points, int n_points, int n_sets, float *out, hipStream_t stream);
+void launch_points_from_map(const PwMesh &mesh, const PwFrames &fr, int f, const FrameDesc &fd, const int32_t *map32, const float *points,
+                            int n_points, int n_sets, float *out, hipStream_t stream);
+// k_pw_points_out: to output through the forward triangle map (map_w x map_h cells from (min_src_x, min_src_y)) and the forward matrices
+// fwd = F x T x 6 floats of k_tri_setup.
+void launch_pw_points_out(const int32_t *fmap, const float *fwd, const FrameDesc *frames, int n_frames, int T, int min_src_x, int min_src_y,
+                          int map_w, int map_h, const float *points, int n_points, int n_sets, float *out, hipStream_t stream);
+
 // k_geo: _inverseGeometricWarp pixel loop :997-1011 for all frames.  mats = F x 8 doubles (inverse matrices).
 // f32_exact: every affine matrix entry is a float value and |x| < 2^28 (lets the kernel use an exact-product fma).
 // n_imgs / img_stride: frame f reads the source at img + (f % n_imgs) * img_stride.

@@ -941,6 +941,113 @@ static napi_value fn_remap_forward_piecewise(napi_env env, napi_callback_info in
     return remap_finish(env, h, HG_FIELD_INDEX, &j);
 }
 
+/* pointsInverseGeometric(<fieldInverseGeometric's arguments>, points) / pointsInversePiecewise(handle, format, points) /
+ * pointsForwardGeometric(<fieldForwardGeometric's>, points) / pointsForwardPiecewise(<fieldForwardPiecewise's>, points): a list of x,y pairs
+ * (Float32Array) through the geometry the field* twin would export, one frame (hg_points_*): Inverse = to source (window positions ->
+ * source coordinates), Forward = to output (source positions -> window-relative output positions).  The format argument of the inverse
+ * twins is accepted and ignored.  The points go up into device scratch, the _device form runs, the results come down as a Float32Array of
+ * the same length, NaN (0x7fc00000) in both words of an unmapped point.
+ * Unlike its twin fieldInverseGeometric, which has a single-frame C entry point, pointsInverseGeometric STAGES the frame as a one-frame
+ * geometric set (hg_geometric_set_frames; the C ABI has no single-frame points form): a geometric frame set the context held before is
+ * replaced.  Every batch function of this addon stages its own set inside the call, so nothing here depends on one surviving.
+ * pointsForwardPiecewise stages its frame as the piecewise set, as fieldForwardPiecewise does. */
+typedef struct { float *pts; size_t n; void *d_pts, *d_out, *out; napi_value result; } points_job;
+
+static int points_begin(napi_env env, handle_t *h, napi_value arg, points_job *j)
+{
+    size_t len = 0;
+    memset(j, 0, sizeof *j);
+    j->pts = (float *)get_typed(env, arg, napi_float32_array, &len, "points");
+    if (!j->pts) return 0;
+    if (len & 1) { throw_str(env, "hgwarp: points must hold x,y pairs"); return 0; }
+    if (len / 2 > ((size_t)1 << 24)) { throw_str(env, "hgwarp: more than 2^24 points"); return 0; }
+    j->n = len / 2;
+    j->result = make_typed(env, napi_float32_array, len, 4, &j->out);
+    if (!j->result) return 0;
+    if (!j->n) return 1;
+    const size_t pb = (len * 4 + 255) & ~(size_t)255;
+    if (2 * pb > h->d_remap_cap) {
+        if (h->d_remap) { hg_device_free(h->ctx, h->d_remap); h->d_remap = NULL; h->d_remap_cap = 0; }
+        int rc = hg_device_alloc(h->ctx, 2 * pb, &h->d_remap);
+        if (rc != HG_OK) { throw_hg(env, h->ctx, "hg_device_alloc", rc); return 0; }
+        h->d_remap_cap = 2 * pb;
+    }
+    j->d_pts = h->d_remap; j->d_out = (uint8_t *)h->d_remap + pb;
+    int rc = hg_copy_to_device(h->ctx, j->d_pts, j->pts, len * 4);
+    if (rc != HG_OK) { throw_hg(env, h->ctx, "hg_copy_to_device", rc); return 0; }
+    return 1;
+}
+
+static napi_value points_finish(napi_env env, handle_t *h, const points_job *j)
+{
+    if (j->n) HG_CALL(h->ctx, "hg_copy_to_host", hg_copy_to_host(h->ctx, j->out, j->d_out, j->n * 8));
+    return j->result;
+}
+
+static napi_value fn_points_inverse_geometric(napi_env env, napi_callback_info info)
+{
+    napi_value a[9];
+    if (!get_args(env, info, 9, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    int kind; size_t n; hg_geom g; points_job j;
+    if (!get_i32(env, a[1], &kind)) return NULL;
+    double *m = (double *)get_typed(env, a[2], napi_float64_array, &n, "matrix"); if (!m) return NULL;
+    if (n < (size_t)(kind == HG_AFFINE ? 6 : 8)) return throw_str(env, "hgwarp: matrix too short");
+    if (!get_geom(env, a + 3, &g)) return NULL;
+    double m8[8] = { 0 };
+    for (int k = 0; k < (kind == HG_AFFINE ? 6 : 8); k++) m8[k] = m[k];
+    const size_t zero = 0;
+    if (!points_begin(env, h, a[8], &j)) return NULL;
+    if (j.n) {
+        HG_CALL(h->ctx, "hg_geometric_set_frames", hg_geometric_set_frames(h->ctx, kind, m8, &g, &zero, 1));
+        HG_CALL(h->ctx, "hg_points_to_source_geometric_frames_device", hg_points_to_source_geometric_frames_device(h->ctx, j.d_pts, (int)j.n, 1, j.d_out));
+    }
+    return points_finish(env, h, &j);
+}
+
+static napi_value fn_points_inverse_piecewise(napi_env env, napi_callback_info info)
+{
+    napi_value a[3];
+    if (!get_args(env, info, 3, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    points_job j;
+    if (!points_begin(env, h, a[2], &j)) return NULL;
+    if (j.n) HG_CALL(h->ctx, "hg_points_to_source_piecewise_frames_device", hg_points_to_source_piecewise_frames_device(h->ctx, j.d_pts, (int)j.n, 1, j.d_out));
+    return points_finish(env, h, &j);
+}
+
+static napi_value fn_points_forward_geometric(napi_env env, napi_callback_info info)
+{
+    napi_value a[8];
+    if (!get_args(env, info, 8, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    int kind; size_t n; hg_geom g; points_job j;
+    if (!get_i32(env, a[1], &kind)) return NULL;
+    double *m = (double *)get_typed(env, a[2], napi_float64_array, &n, "matrix"); if (!m) return NULL;
+    if (n < (size_t)(kind == HG_AFFINE ? 6 : 8)) return throw_str(env, "hgwarp: matrix too short");
+    if (!get_geom(env, a + 3, &g)) return NULL;
+    double m8[8] = { 0 };
+    for (int k = 0; k < (kind == HG_AFFINE ? 6 : 8); k++) m8[k] = m[k];
+    if (!points_begin(env, h, a[7], &j)) return NULL;
+    if (j.n) HG_CALL(h->ctx, "hg_points_to_output_geometric_batch_device", hg_points_to_output_geometric_batch_device(h->ctx, kind, m8, &g, 1, j.d_pts, (int)j.n, 1, j.d_out));
+    return points_finish(env, h, &j);
+}
+
+static napi_value fn_points_forward_piecewise(napi_env env, napi_callback_info info)
+{
+    napi_value a[9];
+    if (!get_args(env, info, 9, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    size_t n; int mx, my; hg_geom g; points_job j;
+    float *dst = (float *)get_typed(env, a[1], napi_float32_array, &n, "dstPoints"); if (!dst) return NULL;
+    if (!get_i32(env, a[2], &mx) || !get_i32(env, a[3], &my)) return NULL;
+    if (!get_geom(env, a + 4, &g)) return NULL;
+    if (h->n_pts == 0 || n < 2 * h->n_pts) return throw_str(env, "hgwarp: dstPoints must hold one x,y pair per mesh point (piecewiseSetMesh first)");
+    if (!points_begin(env, h, a[8], &j)) return NULL;
+    if (j.n) HG_CALL(h->ctx, "hg_points_to_output_piecewise_batch_device", hg_points_to_output_piecewise_batch_device(h->ctx, dst, mx, my, &g, 1, j.d_pts, (int)j.n, 1, j.d_out));
+    return points_finish(env, h, &j);
+}
+
 /* redoneFrames(ctx): frames the fused kernels flagged and hg_sync redid through the map so far (hg_redone_frames; tests) */
 static napi_value fn_redone_frames(napi_env env, napi_callback_info info)
 {
@@ -1509,6 +1616,8 @@ static napi_value init(napi_env env, napi_value exports)
         { "fieldForwardGeometric", fn_field_forward_geometric }, { "fieldForwardPiecewise", fn_field_forward_piecewise },
         { "remapInverseGeometric", fn_remap_inverse_geometric }, { "remapInversePiecewise", fn_remap_inverse_piecewise },
         { "remapForwardGeometric", fn_remap_forward_geometric }, { "remapForwardPiecewise", fn_remap_forward_piecewise },
+        { "pointsInverseGeometric", fn_points_inverse_geometric }, { "pointsInversePiecewise", fn_points_inverse_piecewise },
+        { "pointsForwardGeometric", fn_points_forward_geometric }, { "pointsForwardPiecewise", fn_points_forward_piecewise },
         { "solveAffineTriangles", fn_solve_affine_triangles }, { "warpInversePiecewiseState", fn_warp_inverse_piecewise_state },
         { "warpForwardPiecewiseState", fn_warp_forward_piecewise_state },
         { "release", fn_release }, { "setPinnedLimit", fn_set_pinned_limit }, { "poolStats", fn_pool_stats }, { "redoneFrames", fn_redone_frames }, { "setSampling", fn_set_sampling }, { "multiSetSampling", fn_multi_set_sampling }, { "_poolTestFrames", fn_pool_test_frames }, { "poolPressure", fn_pool_pressure }, { "poolCollected", fn_pool_collected },

@@ -52,6 +52,8 @@ EXPORTS = [
     "hg_field_forward_geometric", "hg_field_forward_geometric_batch_device", "hg_field_forward_piecewise", "hg_field_forward_piecewise_batch_device",
     "hg_last_forward_field_kernel",
     "hg_pack_plane_offsets", "hg_remap_index_frames_device", "hg_remap_bilinear_frames_device", "hg_remap_bilinear_u8_device",
+    "hg_points_to_source_geometric_frames_device", "hg_points_to_source_piecewise_frames_device",
+    "hg_points_to_output_geometric_batch_device", "hg_points_to_output_piecewise_batch_device",
 ]
 
 
@@ -153,6 +155,10 @@ def lib():
         "hg_pack_plane_offsets": (i, [C.POINTER(Geom), i, sz, C.POINTER(sz), C.POINTER(sz)]),
         "hg_remap_index_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, sz, i, sz, i, vp, C.POINTER(sz)]),
         "hg_remap_bilinear_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, i, i, i, sz, i, i, vp, C.POINTER(sz)]),
+        "hg_points_to_source_geometric_frames_device": (i, [vp, vp, i, i, vp]),
+        "hg_points_to_source_piecewise_frames_device": (i, [vp, vp, i, i, vp]),
+        "hg_points_to_output_geometric_batch_device": (i, [vp, i, f64p, C.POINTER(Geom), i, vp, i, i, vp]),
+        "hg_points_to_output_piecewise_batch_device": (i, [vp, f32p, i, i, C.POINTER(Geom), i, vp, i, i, vp]),
         "hg_warp_inverse_piecewise_state": (i, [vp, f32p, i, C.POINTER(TriMapDef), i, i, Geom, u8p]),
         "hg_warp_forward_piecewise_state": (i, [vp, f32p, i, C.POINTER(TriMapDef), i, i, i, i, Geom, u8p]),
     }
@@ -626,6 +632,30 @@ class Context:
     def last_forward_field_kernel(self):
         """0 = no forward field yet, 1 = scatter + winner buffer, 2 = the tile-binned kernels (include/hgwarp.h)."""
         return lib().hg_last_forward_field_kernel(self._h)
+
+    # ---- point lists (include/hgwarp.h, hg_points_*): n_sets lists of n_points interleaved x,y float32 in GPU memory, frame f reads list
+    # f % n_sets; d_out receives frames x n_points x 2 float32, both words 0x7fc00000 where a point is unmapped
+    def points_to_source_geometric_frames_device(self, d_points, n_points, n_sets, d_out):
+        """Output-window positions -> source coordinates through the staged geometric frame set (asynchronous)."""
+        self._c(lib().hg_points_to_source_geometric_frames_device(self._h, C.c_void_p(d_points), int(n_points), int(n_sets), C.c_void_p(d_out)))
+
+    def points_to_source_piecewise_frames_device(self, d_points, n_points, n_sets, d_out):
+        """Output-window positions -> source coordinates through the staged piecewise frame set (settled inside the call)."""
+        self._c(lib().hg_points_to_source_piecewise_frames_device(self._h, C.c_void_p(d_points), int(n_points), int(n_sets), C.c_void_p(d_out)))
+
+    def points_to_output_geometric_batch_device(self, kind, mats, geoms, d_points, n_points, n_sets, d_out):
+        """Source positions -> window-relative output positions under len(geoms) x 8 FORWARD matrices (asynchronous)."""
+        m, p = _f64(mats)
+        assert m.size == 8 * len(geoms)
+        self._c(lib().hg_points_to_output_geometric_batch_device(self._h, int(kind), p, _geoms(geoms), len(geoms), C.c_void_p(d_points),
+                                                                 int(n_points), int(n_sets), C.c_void_p(d_out)))
+
+    def points_to_output_piecewise_batch_device(self, dst_pts, max_src_x, max_src_y, geoms, d_points, n_points, n_sets, d_out):
+        """Source positions -> window-relative output positions through the forward map and the frames' forward matrices (asynchronous)."""
+        d, dp = _f32(dst_pts)
+        assert d.size == 2 * self._n_pts * len(geoms), "frames x mesh points x,y pairs"
+        self._c(lib().hg_points_to_output_piecewise_batch_device(self._h, dp, int(max_src_x), int(max_src_y), _geoms(geoms), len(geoms),
+                                                                 C.c_void_p(d_points), int(n_points), int(n_sets), C.c_void_p(d_out)))
 
     def remap_index_device(self, d_field, n_px, d_src, n_src_px, pixel_bytes, d_out):
         """out[i] = src[field[i]] where 0 <= field[i] < n_src_px, else zeros; pixels of 1, 2, 4, 8 or 16 bytes (asynchronous)."""

@@ -357,6 +357,33 @@ class Homography {
     }
 
     /**
+     * A list of points through the geometry sourceField() would export for the current state, on the device (not part of the reference):
+     * landmarks, box corners, contour vertices, a click position.
+     *   points       a Float32Array or an array of x,y pairs, in pixels;
+     *   options.to   'output' (default): source-image positions -> positions in the output window (the forward loop: the value it hands to
+     *                Math.round, window-relative, reported whether or not it falls inside the window); a point maps iff its cell
+     *                (Math.round of each coordinate) lies in the forward loop's domain -- the image for affine / projective, a covered cell
+     *                of the source mesh for piecewise;
+     *                'source': positions in the output window (output pixel (i, j) is the point (i, j)) -> source coordinates (the inverse
+     *                loop); a point maps iff its cell lies in the window and its coordinate passes the loop's coverage test -- for integer
+     *                positions the value of sourceField('coords') at that pixel, bit for bit.
+     * Refusals, stale-state rules (`repairStaleMap`), solves and uploads are sourceField's for loop 'forward' resp. 'inverse'.  Records
+     * neither a map nor a path.  Returns a Float32Array of the same length, NaN in both coordinates of an unmapped point; an empty window
+     * gives all NaN.  Throws a string for an unknown `to` or a list that does not hold pairs.
+     */
+    transformPoints(points, options = {}) {
+        if (options === null || options === undefined) options = {};
+        const to = options.to === undefined ? 'output' : options.to;
+        if (to !== 'output' && to !== 'source') throw ("transformPoints: options.to must be 'output' or 'source'");
+        if (!(points instanceof Float32Array) && !Array.isArray(points)) throw ("transformPoints: points must be a Float32Array or an array of x,y pairs");
+        const pts = points instanceof Float32Array ? points : Float32Array.from(points.flat());
+        if (pts.length % 2 !== 0) throw ("transformPoints: points must hold x,y pairs");
+        const call = this._fieldCall('transformPoints', to === 'output' ? 0 : 1, { loop: to === 'output' ? 'forward' : 'inverse' });
+        if (call === null || pts.length === 0) return new Float32Array(pts.length).fill(NaN);
+        return this._native['points' + call.entry](this._ctx, ...call.args, pts);
+    }
+
+    /**
      * What sourceField() and remap() share: which field entry point of the addon the current state and options.loop lead to, with its
      * arguments after the context -- { entry, args, width, height }; the addon's functions are 'field' + entry and 'remap' + entry -- after
      * the refusals, the solves and the uploads that field needs.  null: the window is empty.  fmt: 0 = index, 1 = coords.

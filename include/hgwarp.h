@@ -34,7 +34,8 @@ extern "C" {
 #endif
 
 #define HG_VERSION 100          /* 0.1.0 (sampling modes are detected by the presence of hg_set_sampling, source fields by that of hg_field_inverse_geometric,
-                                   the forward source fields by that of hg_field_forward_geometric) */
+                                   the forward source fields by that of hg_field_forward_geometric, point lists by that of
+                                   hg_points_to_source_geometric_frames_device) */
 
 enum {
     HG_OK = 0,
@@ -385,6 +386,60 @@ int hg_field_forward_piecewise(hg_ctx *ctx, const float *dst_points, int max_src
 int hg_field_forward_piecewise_batch_device(hg_ctx *ctx, const float *dst_points, int max_src_x, int max_src_y, const hg_geom *geoms,
                                             const size_t *field_offsets, int n_frames, void *d_field);
 int hg_last_forward_field_kernel(hg_ctx *ctx);
+
+/* ------------------------------------------------------------------------------------------------ point lists
+ * The annotation callers most often hold beside a picture is not a raster but a list of points: landmarks, box corners, contour vertices, a
+ * click position.  These calls send such lists through the geometry of a frame set, in either direction, without a field: "which source
+ * position lies under this output position" (to source) and "where does this source position land in frame f's output" (to output).  Not
+ * part of the reference; geometry only, like the fields: only the source's SIZE is read.
+ * Points are interleaved (x, y) float32 in GPU memory, 8-byte aligned.  d_points holds n_sets lists of n_points points each, tightly packed;
+ * frame f reads list f % n_sets, the rule hg_set_images_device gives images (n_sets == 1: one list for every frame).  d_out receives
+ * n_frames x n_points x 2 float32, tightly packed: frame f starts at f * n_points * 8 bytes.  An UNMAPPED point holds 0x7fc00000 in both
+ * words, the exact pattern of HG_FIELD_COORDS.  All arithmetic is f64 in the reference's operation order, contraction off; each result is
+ * rounded once to f32.
+ * The CELL of a point is (Math.round(x), Math.round(y)), ties toward +Infinity: -0.5 belongs to cell 0, k + 0.5 to cell k + 1.  It is formed
+ * and tested in floating point before any integer conversion, so NaN, +-Infinity and 1e30 are legal inputs that simply fall outside.
+ * TO SOURCE (output position -> source coordinate; the inverse loops :997-1011 and :1042-1056).  The input (u, v) is in the output WINDOW's
+ * pixel coordinates: output pixel (i, j) is the point (i, j).  The point maps iff its cell lies in [0, obj_w) x [0, obj_h) and
+ *   geometric  (sx, sy) = transform(inverse matrix, (double)u + x_off, (double)v + y_off) passes the coverage test :1001;
+ *   piecewise  the triangle is the id the reference's map holds AT THE POINT'S CELL (the largest id whose fillTriangle spans cover flat index
+ *              r * obj_w + c, fill()'s wrap of negative indices included; ids as the coords field treats them), (sx, sy) is that
+ *              triangle's inverse matrix applied to the point itself, ((double)u + x_off, (double)v + y_off), and passes :1047 with the
+ *              frame's minSrc.  Per-frame source points and minima (hg_piecewise_set_frames_src) are honoured.
+ * The result is ((float)sx, (float)sy).  Hence for integer (u, v) inside the window it is the HG_FIELD_COORDS field's value at that pixel,
+ * bit for bit, NaN pattern included.
+ * TO OUTPUT (source position -> output position; the forward loops :919-926 and :955-964).  The input (px, py) is in source-image pixels.
+ *   geometric  the point maps iff its cell lies in [0, W) x [0, H), the loop's domain; (nx, ny) = transform(forward matrix, px, py);
+ *   piecewise  mx = cell_x - minSrcX, my = cell_y - minSrcY must lie in the forward map [0, maxSrcX - minSrcX) x [0, maxSrcY - minSrcY) and
+ *              the cell must hold an id > -1 (the map of :817-832 the forward warps build and cache); (nx, ny) is that id's forward matrix
+ *              (:785-804, f32 entries widened) applied to the point itself.  The mesh-wide source side only, as every forward entry point.
+ * The result is ((float)(nx - x_off), (float)(ny - y_off)), the value :924 / :962 hands to Math.round: window-relative, and reported whether
+ * or not it falls inside the window -- that is the caller's business.
+ * Each entry point follows its field counterpart in what it demands of the context (HG_ERR_STATE: no source image, no mesh, no frame set),
+ * in its limits, in what it settles before launching and in how staged frame sets and the forward-map cache are treated; none touches
+ * hg_last_*_kernel / _variant / _self, the sampling mode, the plan of the last warp or what the policy learned.  All run on the ctx stream.
+ *   hg_points_to_source_geometric_frames_device  the staged set of hg_geometric_set_frames[_points]; asynchronous (as
+ *              hg_field_inverse_geometric_frames_device).
+ *   hg_points_to_source_piecewise_frames_device  the staged set of hg_piecewise_set_frames / _set_frames_src / hg_piecewise_prepare; SETTLED
+ *              INSIDE THE CALL as hg_field_inverse_piecewise_frames_device is: queued warp runs are settled first, and a frame with
+ *              irregular triangles (a NaN vertex is legal input) is redone through the materialised map before the call returns and counted
+ *              in hg_redone_frames.  The kernel resolves the id of a cell by walking the mesh's triangles, with no map and no span list (hence
+ *              no overflow): made for short lists on small meshes.  MEASURED (EXPERIMENTS.md P, 64 4K frames): at 65536 points per frame
+ *              and 5000 triangles it is 33x SLOWER than the full-frame hg_field_inverse_piecewise_frames_device(HG_FIELD_COORDS) call it
+ *              stands in for (79 ms against 2.4 ms), 3.5x slower at 65536 points and 200 triangles, 1.7x slower at 68 points and 5000
+ *              triangles; it wins at 68 points and 200 triangles (0.22 of the field call).  Beyond that, export the field and gather.
+ *   hg_points_to_output_geometric_batch_device   m: n_frames x 8 FORWARD matrices (affine in the first 6 of each 8); limits as
+ *              hg_field_forward_geometric_batch_device; queued runs are settled, then asynchronous.  No staged set is touched.
+ *   hg_points_to_output_piecewise_batch_device   as hg_field_forward_piecewise_batch_device up to the launch: the forward map is built or
+ *              reused from the cache, the frames become the staged piecewise set; nothing is ever redone; asynchronous.
+ * n_points == 0: HG_OK, nothing happens.  HG_ERR_INVALID: NULL pointers with work to do, n_points negative or above 2^24, n_sets below 1,
+ * a pointer not aligned to 8 bytes, and what the counterpart refuses. */
+int hg_points_to_source_geometric_frames_device(hg_ctx *ctx, const void *d_points, int n_points, int n_sets, void *d_out);
+int hg_points_to_source_piecewise_frames_device(hg_ctx *ctx, const void *d_points, int n_points, int n_sets, void *d_out);
+int hg_points_to_output_geometric_batch_device(hg_ctx *ctx, int kind, const double *m, const hg_geom *geoms, int n_frames,
+                                               const void *d_points, int n_points, int n_sets, void *d_out);
+int hg_points_to_output_piecewise_batch_device(hg_ctx *ctx, const float *dst_points, int max_src_x, int max_src_y, const hg_geom *geoms,
+                                               int n_frames, const void *d_points, int n_points, int n_sets, void *d_out);
 
 /* ------------------------------------------------------------------------------------------------ forward (scatter) paths
  * What warp() dispatches to when the output is not larger than the input (:421, :426).  `m` is the FORWARD matrix
