@@ -339,3 +339,121 @@ extern "C" int hg_remap_bilinear_u8_device(hg_ctx *c, const void *d_coords, size
     HIP_TRY(c, hipGetLastError());
     return HG_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ mip pyramids and the trilinear remap
+extern "C" int hg_pyramid_levels(int W, int H)
+{
+    if (W < 1 || H < 1) return 0;
+    int n = 1;
+    for (; W > 1 || H > 1; n++) { W = (W + 1) >> 1; H = (H + 1) >> 1; }
+    return n;
+}
+
+static bool plane_fmt_ok(int elem, int channels) { return (elem == HG_ELEM_F32 || elem == HG_ELEM_U8) && channels >= 1 && channels <= 4; }
+
+// offs[k], k = 1 .. levels - 1, and the bytes of one pyramid (levels already checked against hg_pyramid_levels).
+static size_t pyramid_offsets(int W, int H, size_t px_bytes, int levels, size_t *offs)
+{
+    size_t off = 0;
+    offs[0] = 0;
+    for (int k = 1; k < levels; k++) {
+        W = (W + 1) >> 1; H = (H + 1) >> 1;
+        offs[k] = off;
+        off += pad256((size_t)W * (size_t)H * px_bytes);
+    }
+    return off;
+}
+
+extern "C" int hg_pyramid_layout(int W, int H, int elem, int channels, int levels, size_t *offsets, size_t *total)
+{
+    if (!plane_fmt_ok(elem, channels) || levels < 1 || levels > hg_pyramid_levels(W, H) || !offsets || !total)
+        return fail(nullptr, HG_ERR_INVALID, "hg_pyramid_layout: bad arguments");
+    *total = pyramid_offsets(W, H, (elem == HG_ELEM_F32 ? 4 : 1) * (size_t)channels, levels, offsets);
+    return HG_OK;
+}
+
+// What the pyramid calls check of the pyramids of a plane set (written: the call writes them, so every pyramid needs its room);
+// *total: the bytes of one pyramid, offs: its level offsets (room for 32).
+static int check_pyramid(hg_ctx *c, const char *who, int W, int H, int elem, int channels, int levels, const void *d_pyr, size_t pyr_stride_bytes,
+                         bool written, size_t *offs, size_t *total)
+{
+    if (levels < 1 || levels > hg_pyramid_levels(W, H)) return fail(c, HG_ERR_INVALID, std::string(who) + ": levels must lie in 1..hg_pyramid_levels(W, H)");
+    const size_t es = elem == HG_ELEM_F32 ? 4 : 1;
+    *total = pyramid_offsets(W, H, es * (size_t)channels, levels, offs);
+    if (levels == 1) return HG_OK;                           // (no pyramid is read or written)
+    if (!d_pyr) return fail(c, HG_ERR_INVALID, std::string(who) + ": d_pyr is NULL with levels > 1");
+    if (misaligned(d_pyr, es) || (pyr_stride_bytes & (es - 1))) return fail(c, HG_ERR_INVALID, std::string(who) + ": d_pyr / pyr_stride_bytes must be aligned to the element size");
+    if (written && pyr_stride_bytes < *total) return fail(c, HG_ERR_INVALID, std::string(who) + ": pyr_stride_bytes is smaller than one pyramid (hg_pyramid_layout's total)");
+    return HG_OK;
+}
+
+extern "C" int hg_pyramid_build_device(hg_ctx *c, const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
+                                       int levels, void *d_pyr, size_t pyr_stride_bytes)
+{
+    HG_TRY(bind(c));
+    if (!plane_fmt_ok(elem, channels) || W < 1 || H < 1) return fail(c, HG_ERR_INVALID, "hg_pyramid_build_device: elem must be HG_ELEM_F32 or HG_ELEM_U8, channels 1..4, W and H >= 1");
+    if (n_planes < 1) return fail(c, HG_ERR_INVALID, "hg_pyramid_build_device: n_planes must be >= 1");
+    size_t offs[32], total = 0;
+    HG_TRY(check_pyramid(c, "hg_pyramid_build_device", W, H, elem, channels, levels, d_pyr, pyr_stride_bytes, true, offs, &total));
+    if (levels == 1) return HG_OK;
+    const size_t es = elem == HG_ELEM_F32 ? 4 : 1;
+    if (!d_planes) return fail(c, HG_ERR_INVALID, "hg_pyramid_build_device: d_planes is NULL");
+    if (misaligned(d_planes, es) || (plane_stride_bytes & (es - 1))) return fail(c, HG_ERR_INVALID, "hg_pyramid_build_device: d_planes / plane_stride_bytes must be aligned to the element size");
+    const uint8_t *src = static_cast<const uint8_t *>(d_planes);
+    uint8_t *pyr = static_cast<uint8_t *>(d_pyr);
+    size_t src_stride = plane_stride_bytes;
+    int ws = W, hs = H;
+    for (int k = 1; k < levels; k++) {                       // one launch per level, each reading the level before it
+        const int wd = (ws + 1) >> 1, hd = (hs + 1) >> 1;
+        launch_pyr_down(src, src_stride, ws, hs, pyr + offs[k], pyr_stride_bytes, wd, hd, n_planes, elem, channels, c->stream);
+        src = pyr + offs[k]; src_stride = pyr_stride_bytes; ws = wd; hs = hd;
+    }
+    HIP_TRY(c, hipGetLastError());
+    return HG_OK;
+}
+
+extern "C" int hg_remap_trilinear_frames_device(hg_ctx *c, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
+                                                const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
+                                                void *d_out, const size_t *out_offsets, const void *d_pyr, size_t pyr_stride_bytes, int levels)
+{
+    HG_TRY(bind(c));
+    if (elem != HG_ELEM_F32 && elem != HG_ELEM_U8) return fail(c, HG_ERR_INVALID, "hg_remap_trilinear_frames_device: unknown elem (HG_ELEM_F32 or HG_ELEM_U8)");
+    if (channels < 1 || channels > 4 || W < 1 || H < 1) return fail(c, HG_ERR_INVALID, "hg_remap_trilinear_frames_device: channels must be 1..4, W and H >= 1");
+    if (n_planes < 1) return fail(c, HG_ERR_INVALID, "hg_remap_trilinear_frames_device: n_planes must be >= 1");
+    if (n_frames < 0 || n_frames > 65535) return fail(c, HG_ERR_INVALID, "hg_remap_trilinear_frames_device: n_frames must be 0..65535");
+    size_t lvl[32] = {0}, total = 0;
+    HG_TRY(check_pyramid(c, "hg_remap_trilinear_frames_device", W, H, elem, channels, levels, d_pyr, pyr_stride_bytes, false, lvl, &total));
+    if (n_frames == 0) return HG_OK;
+    if (!geoms || !d_coords || !d_planes || !d_out) return fail(c, HG_ERR_INVALID, "hg_remap_trilinear_frames_device: NULL pointer");
+    const size_t es = elem == HG_ELEM_F32 ? 4 : 1;
+    if (misaligned(d_coords, 8) || misaligned(d_planes, es) || misaligned(d_out, es) || (plane_stride_bytes & (es - 1)))
+        return fail(c, HG_ERR_INVALID, "hg_remap_trilinear_frames_device: d_coords must be aligned to 8 bytes, d_planes / d_out / plane_stride_bytes to the element size");
+    std::vector<RemapFrame> recs;
+    size_t extent = 0;
+    HG_TRY(remap_frame_table(c, geoms, n_frames, 8, field_offsets, es * (size_t)channels, es, out_offsets, n_planes, &recs, &extent));
+    if (extent == 0) return HG_OK;
+    uint64_t blk_px = 0; uint32_t n_blocks = 0;
+    assign_remap_blocks(recs, 1024, &blk_px, &n_blocks);
+    if (!c->pw_pending_out.empty() || !c->fwd_pending.empty()) HG_TRY(settle_output_conflicts(c, d_out, extent, 0));
+    // the device table: 32 level offsets, then one record per frame
+    static_assert(sizeof(TriRemapFrame) % 8 == 0, "the table is staged in 8-byte words");
+    const size_t words = 32 + (size_t)n_frames * (sizeof(TriRemapFrame) / 8);
+    HG_TRY(ensure(c, c->d_tri_table, words));
+    StageSlot *gs = nullptr;
+    HG_TRY(c->field_stage.acquire(c, words * 8, "field frame staging", &gs));
+    uint64_t *tab = reinterpret_cast<uint64_t *>(gs->h);
+    for (int k = 0; k < 32; k++) tab[k] = lvl[k];
+    TriRemapFrame *tf = reinterpret_cast<TriRemapFrame *>(tab + 32);
+    for (int f = 0; f < n_frames; f++) {
+        const RemapFrame &r = recs[(size_t)f];
+        tf[f] = TriRemapFrame{r.fld_off, r.out_off, r.n_px, (uint64_t)r.plane * plane_stride_bytes, (uint64_t)r.plane * pyr_stride_bytes, r.blk0,
+                              (uint32_t)std::max(geoms[f].obj_w, 0), (uint32_t)std::max(geoms[f].obj_h, 0), 0};
+    }
+    HG_TRY(upload_staged(c, c->d_tri_table, gs->h, words * 8));
+    HG_TRY(c->field_stage.commit(c, gs));
+    launch_remap_trilinear_frames(reinterpret_cast<const TriRemapFrame *>(c->d_tri_table.p + 32), n_frames, n_blocks, blk_px, c->d_tri_table, levels,
+                                  static_cast<const uint8_t *>(d_coords), static_cast<const uint8_t *>(d_planes), static_cast<const uint8_t *>(d_pyr),
+                                  W, H, elem, channels, static_cast<uint8_t *>(d_out), c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return HG_OK;
+}

@@ -198,6 +198,19 @@ void launch_remap_bilinear_frames(const RemapFrame *frames, const RemapFrame &on
                                   const uint8_t *coords, const uint8_t *planes, size_t plane_stride, int W, int H, int elem, int channels,
                                   uint8_t *out, hipStream_t stream);
 
+// Mip pyramids and the trilinear remap (hg_k_pyramid.hip; include/hgwarp.h hg_pyramid_* / hg_remap_trilinear_frames_device).
+// k_pyr_down<element, channels>: level k (Wd x Hd) of every plane from level k - 1 (Ws x Hs): src / dst are the levels of plane 0, the
+// other planes lie src_stride / dst_stride bytes apart.
+void launch_pyr_down(const uint8_t *src, size_t src_stride, int Ws, int Hs, uint8_t *dst, size_t dst_stride, int Wd, int Hd, int n_planes,
+                     int elem, int channels, hipStream_t stream);
+// A frame of the trilinear remap: RemapFrame's flat list read as obj_w x obj_h, its plane at plane_off and that plane's pyramid at pyr_off
+// (bytes from the bases the kernel gets).
+struct TriRemapFrame { uint64_t fld_off, out_off, n_px, plane_off, pyr_off; uint32_t blk0, obj_w, obj_h, pad; };
+// k_remap_trilinear_frames<element, channels>: lvl_off = `levels` byte offsets on the device (hg_pyramid_layout's; entry 0 unused).
+void launch_remap_trilinear_frames(const TriRemapFrame *frames, int n_frames, uint32_t n_blocks, uint64_t blk_px, const uint64_t *lvl_off, int levels,
+                                   const uint8_t *coords, const uint8_t *planes, const uint8_t *pyrs, int W, int H, int elem, int channels,
+                                   uint8_t *out, hipStream_t stream);
+
 // Point lists (hg_k_points.hip; include/hgwarp.h hg_points_*): n_sets lists of n_points interleaved (x, y) floats, frame f reads list
 // f % n_sets and writes n_points (x, y) pairs at f * n_points of `out`; an unmapped point is the quiet NaN of HG_FIELD_COORDS in both words.
 // k_geo_points<kind, dir>: dir 0 = to source (mats: the inverse matrices, W x H the source's size: coverage test :1001), dir 1 = to output

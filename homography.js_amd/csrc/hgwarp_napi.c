@@ -829,9 +829,10 @@ static napi_value fn_field_forward_piecewise(napi_env env, napi_callback_info in
  * to the host: the plane goes up, hg_remap_index_device (format 0: pixels are opaque blocks of channels * BYTES_PER_ELEMENT = 1, 2, 4, 8 or 16
  * bytes) or hg_remap_bilinear_f32_device / _u8_device (format 1: Float32Array / Uint8Array / Uint8ClampedArray, 1..4 channels) runs, and the
  * result comes down as a TypedArray of the plane's class with objW * objH * channels elements. */
-typedef struct { napi_typedarray_type type; void *data; size_t len, elem; int channels, W, H; void *d_field, *d_plane, *d_out, *out; size_t px; napi_value result; } remap_job;
+typedef struct { napi_typedarray_type type; void *data; size_t len, elem; int channels, W, H; void *d_field, *d_plane, *d_out, *out; size_t px; napi_value result;
+                 int levels; void *d_pyr; size_t pyr_bytes; hg_geom geom; } remap_job;      /* levels > 0: the trilinear remap, its pyramid behind the result */
 
-static int remap_begin(napi_env env, handle_t *h, napi_value *a, int fmt, size_t px, remap_job *j)
+static int remap_begin(napi_env env, handle_t *h, napi_value *a, int fmt, size_t px, int trilinear, remap_job *j)
 {
     static const size_t elem_of[] = { 1, 1, 1, 2, 2, 4, 4, 4, 8, 8, 8 };       /* napi_int8_array .. napi_biguint64_array */
     bool is = false; napi_value ab; size_t off = 0;
@@ -851,14 +852,22 @@ static int remap_begin(napi_env env, handle_t *h, napi_value *a, int fmt, size_t
     j->result = make_typed(env, j->type, px * (size_t)j->channels, j->elem, &j->out);
     if (!j->result) return 0;
     if (!px) return 1;
-    const size_t fb = (px * (fmt == HG_FIELD_INDEX ? 4 : 8) + 255) & ~(size_t)255, pl = (j->len * j->elem + 255) & ~(size_t)255, ob = px * pb;
-    if (fb + pl + ob > h->d_remap_cap) {
-        if (h->d_remap) { hg_device_free(h->ctx, h->d_remap); h->d_remap = NULL; h->d_remap_cap = 0; }
-        int rc = hg_device_alloc(h->ctx, fb + pl + ob, &h->d_remap);
-        if (rc != HG_OK) { throw_hg(env, h->ctx, "hg_device_alloc", rc); return 0; }
-        h->d_remap_cap = fb + pl + ob;
+    size_t fb = (px * (fmt == HG_FIELD_INDEX ? 4 : 8) + 255) & ~(size_t)255, pl = (j->len * j->elem + 255) & ~(size_t)255, ob = px * pb;
+    if (trilinear) {                                           /* the full pyramid, all hg_pyramid_levels(W, H) levels */
+        size_t offs[32];
+        j->levels = hg_pyramid_levels(j->W, j->H);
+        if (fmt != HG_FIELD_COORDS || hg_pyramid_layout(j->W, j->H, j->type == napi_float32_array ? HG_ELEM_F32 : HG_ELEM_U8, j->channels, j->levels, offs, &j->pyr_bytes) != HG_OK) {
+            throw_str(env, "hgwarp: a trilinear remap needs the coords format"); return 0;
+        }
+        ob = (ob + 255) & ~(size_t)255;
     }
-    j->d_field = h->d_remap; j->d_plane = (uint8_t *)h->d_remap + fb; j->d_out = (uint8_t *)h->d_remap + fb + pl;
+    if (fb + pl + ob + j->pyr_bytes > h->d_remap_cap) {
+        if (h->d_remap) { hg_device_free(h->ctx, h->d_remap); h->d_remap = NULL; h->d_remap_cap = 0; }
+        int rc = hg_device_alloc(h->ctx, fb + pl + ob + j->pyr_bytes, &h->d_remap);
+        if (rc != HG_OK) { throw_hg(env, h->ctx, "hg_device_alloc", rc); return 0; }
+        h->d_remap_cap = fb + pl + ob + j->pyr_bytes;
+    }
+    j->d_field = h->d_remap; j->d_plane = (uint8_t *)h->d_remap + fb; j->d_out = (uint8_t *)h->d_remap + fb + pl; j->d_pyr = (uint8_t *)j->d_out + ob;
     int rc = hg_copy_to_device(h->ctx, j->d_plane, j->data, j->len * j->elem);
     if (rc != HG_OK) { throw_hg(env, h->ctx, "hg_copy_to_device", rc); return 0; }
     return 1;
@@ -868,7 +877,13 @@ static napi_value remap_finish(napi_env env, handle_t *h, int fmt, const remap_j
 {
     if (!j->px) return j->result;
     const size_t pb = (size_t)j->channels * j->elem;
-    if (fmt == HG_FIELD_INDEX)
+    if (j->levels > 0) {
+        const int elem = j->type == napi_float32_array ? HG_ELEM_F32 : HG_ELEM_U8;
+        const size_t zero = 0;
+        HG_CALL(h->ctx, "hg_pyramid_build_device", hg_pyramid_build_device(h->ctx, j->d_plane, j->W, j->H, 1, 0, elem, j->channels, j->levels, j->d_pyr, j->pyr_bytes));
+        HG_CALL(h->ctx, "hg_remap_trilinear_frames_device", hg_remap_trilinear_frames_device(h->ctx, &j->geom, 1, j->d_field, &zero, j->d_plane, j->W, j->H, 1, 0, elem,
+                                                                                             j->channels, j->d_out, &zero, j->d_pyr, j->pyr_bytes, j->levels));
+    } else if (fmt == HG_FIELD_INDEX)
         HG_CALL(h->ctx, "hg_remap_index_device", hg_remap_index_device(h->ctx, j->d_field, j->px, j->d_plane, (size_t)j->W * (size_t)j->H, (int)pb, j->d_out));
     else if (j->type == napi_float32_array)
         HG_CALL(h->ctx, "hg_remap_bilinear_f32_device", hg_remap_bilinear_f32_device(h->ctx, j->d_field, j->px, (const float *)j->d_plane, j->W, j->H, j->channels, (float *)j->d_out));
@@ -878,7 +893,7 @@ static napi_value remap_finish(napi_env env, handle_t *h, int fmt, const remap_j
     return j->result;
 }
 
-static napi_value fn_remap_inverse_geometric(napi_env env, napi_callback_info info)
+static napi_value remap_inverse_geometric(napi_env env, napi_callback_info info, int trilinear)
 {
     napi_value a[12];
     if (!get_args(env, info, 12, a)) return NULL;
@@ -889,12 +904,13 @@ static napi_value fn_remap_inverse_geometric(napi_env env, napi_callback_info in
     if (n < (size_t)(kind == HG_AFFINE ? 6 : 8)) return throw_str(env, "hgwarp: matrix too short");
     if (!get_geom(env, a + 3, &g) || !get_i32(env, a[7], &fmt)) return NULL;
     const size_t px = (g.obj_w > 0 && g.obj_h > 0) ? (size_t)g.obj_w * g.obj_h : 0;
-    if (!remap_begin(env, h, a + 8, fmt, px, &j)) return NULL;
+    if (!remap_begin(env, h, a + 8, fmt, px, trilinear, &j)) return NULL;
+    j.geom = g;
     if (px) HG_CALL(h->ctx, "hg_field_inverse_geometric_device", hg_field_inverse_geometric_device(h->ctx, kind, m, g, fmt, j.d_field));
     return remap_finish(env, h, fmt, &j);
 }
 
-static napi_value fn_remap_inverse_piecewise(napi_env env, napi_callback_info info)
+static napi_value remap_inverse_piecewise(napi_env env, napi_callback_info info, int trilinear)
 {
     napi_value a[6];
     if (!get_args(env, info, 6, a)) return NULL;
@@ -902,10 +918,18 @@ static napi_value fn_remap_inverse_piecewise(napi_env env, napi_callback_info in
     int fmt; remap_job j;
     if (!get_i32(env, a[1], &fmt)) return NULL;
     const size_t px = (h->obj_w > 0 && h->obj_h > 0) ? (size_t)h->obj_w * h->obj_h : 0, zero = 0;
-    if (!remap_begin(env, h, a + 2, fmt, px, &j)) return NULL;
+    if (!remap_begin(env, h, a + 2, fmt, px, trilinear, &j)) return NULL;
+    j.geom.x_off = 0; j.geom.y_off = 0; j.geom.obj_w = h->obj_w; j.geom.obj_h = h->obj_h;
     if (px) HG_CALL(h->ctx, "hg_field_inverse_piecewise_frames_device", hg_field_inverse_piecewise_frames_device(h->ctx, fmt, &zero, j.d_field));
     return remap_finish(env, h, fmt, &j);
 }
+
+/* remapTrilinearInverseGeometric / remapTrilinearInversePiecewise: the arguments of remapInverseGeometric / remapInversePiecewise (format 1),
+ * the plane through hg_pyramid_build_device (all levels, in device scratch) and hg_remap_trilinear_frames_device with the window as one frame. */
+static napi_value fn_remap_inverse_geometric(napi_env env, napi_callback_info info) { return remap_inverse_geometric(env, info, 0); }
+static napi_value fn_remap_inverse_piecewise(napi_env env, napi_callback_info info) { return remap_inverse_piecewise(env, info, 0); }
+static napi_value fn_remap_trilinear_inverse_geometric(napi_env env, napi_callback_info info) { return remap_inverse_geometric(env, info, 1); }
+static napi_value fn_remap_trilinear_inverse_piecewise(napi_env env, napi_callback_info info) { return remap_inverse_piecewise(env, info, 1); }
 
 static napi_value fn_remap_forward_geometric(napi_env env, napi_callback_info info)
 {
@@ -920,7 +944,7 @@ static napi_value fn_remap_forward_geometric(napi_env env, napi_callback_info in
     double m8[8] = { 0 };
     for (int k = 0; k < (kind == HG_AFFINE ? 6 : 8); k++) m8[k] = m[k];
     const size_t px = (g.obj_w > 0 && g.obj_h > 0) ? (size_t)g.obj_w * g.obj_h : 0, zero = 0;
-    if (!remap_begin(env, h, a + 7, HG_FIELD_INDEX, px, &j)) return NULL;
+    if (!remap_begin(env, h, a + 7, HG_FIELD_INDEX, px, 0, &j)) return NULL;
     if (px) HG_CALL(h->ctx, "hg_field_forward_geometric_batch_device", hg_field_forward_geometric_batch_device(h->ctx, kind, m8, &g, &zero, 1, j.d_field));
     return remap_finish(env, h, HG_FIELD_INDEX, &j);
 }
@@ -936,7 +960,7 @@ static napi_value fn_remap_forward_piecewise(napi_env env, napi_callback_info in
     if (!get_geom(env, a + 4, &g)) return NULL;
     if (h->n_pts == 0 || n < 2 * h->n_pts) return throw_str(env, "hgwarp: dstPoints must hold one x,y pair per mesh point (piecewiseSetMesh first)");
     const size_t px = (g.obj_w > 0 && g.obj_h > 0) ? (size_t)g.obj_w * g.obj_h : 0, zero = 0;
-    if (!remap_begin(env, h, a + 8, HG_FIELD_INDEX, px, &j)) return NULL;
+    if (!remap_begin(env, h, a + 8, HG_FIELD_INDEX, px, 0, &j)) return NULL;
     if (px) HG_CALL(h->ctx, "hg_field_forward_piecewise_batch_device", hg_field_forward_piecewise_batch_device(h->ctx, dst, mx, my, &g, &zero, 1, j.d_field));
     return remap_finish(env, h, HG_FIELD_INDEX, &j);
 }
@@ -1616,6 +1640,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "fieldForwardGeometric", fn_field_forward_geometric }, { "fieldForwardPiecewise", fn_field_forward_piecewise },
         { "remapInverseGeometric", fn_remap_inverse_geometric }, { "remapInversePiecewise", fn_remap_inverse_piecewise },
         { "remapForwardGeometric", fn_remap_forward_geometric }, { "remapForwardPiecewise", fn_remap_forward_piecewise },
+        { "remapTrilinearInverseGeometric", fn_remap_trilinear_inverse_geometric }, { "remapTrilinearInversePiecewise", fn_remap_trilinear_inverse_piecewise },
         { "pointsInverseGeometric", fn_points_inverse_geometric }, { "pointsInversePiecewise", fn_points_inverse_piecewise },
         { "pointsForwardGeometric", fn_points_forward_geometric }, { "pointsForwardPiecewise", fn_points_forward_piecewise },
         { "solveAffineTriangles", fn_solve_affine_triangles }, { "warpInversePiecewiseState", fn_warp_inverse_piecewise_state },

@@ -54,6 +54,7 @@ EXPORTS = [
     "hg_pack_plane_offsets", "hg_remap_index_frames_device", "hg_remap_bilinear_frames_device", "hg_remap_bilinear_u8_device",
     "hg_points_to_source_geometric_frames_device", "hg_points_to_source_piecewise_frames_device",
     "hg_points_to_output_geometric_batch_device", "hg_points_to_output_piecewise_batch_device",
+    "hg_pyramid_levels", "hg_pyramid_layout", "hg_pyramid_build_device", "hg_remap_trilinear_frames_device",
 ]
 
 
@@ -155,6 +156,10 @@ def lib():
         "hg_pack_plane_offsets": (i, [C.POINTER(Geom), i, sz, C.POINTER(sz), C.POINTER(sz)]),
         "hg_remap_index_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, sz, i, sz, i, vp, C.POINTER(sz)]),
         "hg_remap_bilinear_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, i, i, i, sz, i, i, vp, C.POINTER(sz)]),
+        "hg_pyramid_levels": (i, [i, i]),
+        "hg_pyramid_layout": (i, [i, i, i, i, i, C.POINTER(sz), C.POINTER(sz)]),
+        "hg_pyramid_build_device": (i, [vp, vp, i, i, i, sz, i, i, i, vp, sz]),
+        "hg_remap_trilinear_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, i, i, i, sz, i, i, vp, C.POINTER(sz), vp, sz, i]),
         "hg_points_to_source_geometric_frames_device": (i, [vp, vp, i, i, vp]),
         "hg_points_to_source_piecewise_frames_device": (i, [vp, vp, i, i, vp]),
         "hg_points_to_output_geometric_batch_device": (i, [vp, i, f64p, C.POINTER(Geom), i, vp, i, i, vp]),
@@ -312,6 +317,20 @@ def pack_plane_offsets(geoms, px_bytes):
     total = C.c_size_t(0)
     _check(lib().hg_pack_plane_offsets(g, len(geoms), int(px_bytes), offs, C.byref(total)))
     return list(offs)[:len(geoms)], total.value
+
+
+def pyramid_levels(w, h):
+    """Levels of the full mip pyramid of a w x h plane: 1 + ceil(log2(max(w, h))); 0 for w or h < 1."""
+    return lib().hg_pyramid_levels(int(w), int(h))
+
+
+def pyramid_layout(w, h, elem, channels, levels):
+    """(offsets, total bytes) of ONE pyramid buffer: offsets[k], k = 1 .. levels-1, is where level k starts (256-byte aligned); offsets[0] = 0
+    is unused -- level 0 stays the caller's plane."""
+    offs = (C.c_size_t * max(int(levels), 1))()
+    total = C.c_size_t(0)
+    _check(lib().hg_pyramid_layout(int(w), int(h), int(elem), int(channels), int(levels), offs, C.byref(total)))
+    return list(offs)[:int(levels)], total.value
 
 
 def _field_array(fmt, h, w):
@@ -690,6 +709,22 @@ class Context:
         self._c(lib().hg_remap_bilinear_frames_device(self._h, _geoms(geoms), len(geoms), C.c_void_p(int(d_coords)), fo, C.c_void_p(int(d_planes)),
                                                       int(w), int(h), int(n_planes), int(plane_stride_bytes), int(elem), int(channels),
                                                       C.c_void_p(int(d_out)), oo))
+
+    def pyramid_build_device(self, d_planes, w, h, n_planes, plane_stride_bytes, elem, channels, levels, d_pyr, pyr_stride_bytes):
+        """Levels 1 .. levels-1 of the mip pyramid of every plane, pyramid p at d_pyr + p * pyr_stride_bytes in pyramid_layout's layout;
+        asynchronous, one launch per level."""
+        self._c(lib().hg_pyramid_build_device(self._h, C.c_void_p(int(d_planes)), int(w), int(h), int(n_planes), int(plane_stride_bytes), int(elem),
+                                              int(channels), int(levels), C.c_void_p(int(d_pyr)), int(pyr_stride_bytes)))
+
+    def remap_trilinear_frames_device(self, geoms, d_coords, d_planes, w, h, n_planes, plane_stride_bytes, elem, channels, d_out,
+                                      d_pyr, pyr_stride_bytes, levels, field_offsets=None, out_offsets=None):
+        """remap_bilinear_frames_device with minification filtering: every pixel reads the pyramid level(s) its footprint in the field asks
+        for (frames are read as obj_w x obj_h arrays); levels == 1 is the bilinear frames remap, bit for bit."""
+        fo = (C.c_size_t * len(geoms))(*field_offsets) if field_offsets is not None else None
+        oo = (C.c_size_t * len(geoms))(*out_offsets) if out_offsets is not None else None
+        self._c(lib().hg_remap_trilinear_frames_device(self._h, _geoms(geoms), len(geoms), C.c_void_p(int(d_coords)), fo, C.c_void_p(int(d_planes)),
+                                                       int(w), int(h), int(n_planes), int(plane_stride_bytes), int(elem), int(channels),
+                                                       C.c_void_p(int(d_out)), oo, C.c_void_p(int(d_pyr)), int(pyr_stride_bytes), int(levels)))
 
     # ---- piecewise
     def piecewise_set_mesh(self, src_pts, tris, min_src_x, min_src_y):

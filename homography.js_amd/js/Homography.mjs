@@ -329,22 +329,26 @@ class Homography {
      *                     'bilinear': through the 'coords' field; a Float32Array, Uint8Array or Uint8ClampedArray of 1..4 channels, blended
      *                     in f32 in the operation order of the bilinear sampling mode; bytes are rounded min(255, floor(v + 0.5)), 4 channels
      *                     being straight (not premultiplied) RGBA; an uncovered pixel is 0 in every channel;
-     *   options.loop      'inverse' (default), 'warp' or 'forward': sourceField's meaning, refusals and stale-state rules; 'bilinear' with a
-     *                     forward loop throws, as 'coords' does there.
+     *                     'trilinear': 'bilinear' with minification filtering -- the same planes, field and refusals; the plane's mip
+     *                     pyramid (all levels) is built in device scratch and every pixel blends the two levels that match the field's
+     *                     own footprint there (include/hgwarp.h, hg_remap_trilinear_frames_device), so a shrink no longer aliases; where
+     *                     the field does not shrink the result is 'bilinear''s, bit for bit;
+     *   options.loop      'inverse' (default), 'warp' or 'forward': sourceField's meaning, refusals and stale-state rules; 'bilinear' and
+     *                     'trilinear' with a forward loop throw, as 'coords' does there.
      * Independent of the instance's sampling mode; records neither a map nor a path.
      * Returns { data, width, height, channels }, `data` being of the plane's own class; an empty window gives empty data, width and height 0.
      */
     remap(plane, options = {}) {
         if (options === null || options === undefined) options = {};
         const sampling = options.sampling === undefined ? 'nearest' : options.sampling;
-        if (sampling !== 'nearest' && sampling !== 'bilinear') throw ("remap: options.sampling must be 'nearest' or 'bilinear'");
+        if (sampling !== 'nearest' && sampling !== 'bilinear' && sampling !== 'trilinear') throw ("remap: options.sampling must be 'nearest', 'bilinear' or 'trilinear'");
         const channels = options.channels === undefined ? 1 : options.channels;
         if (!ArrayBuffer.isView(plane) || plane instanceof DataView) throw ("remap: plane must be a typed array");
         if (!Number.isInteger(channels) || channels < 1) throw ("remap: options.channels must be a positive integer");
-        if (sampling === 'bilinear') {
+        if (sampling !== 'nearest') {
             if (!(plane instanceof Float32Array || plane instanceof Uint8Array || plane instanceof Uint8ClampedArray))
-                throw ("remap: a 'bilinear' plane must be a Float32Array, Uint8Array or Uint8ClampedArray");
-            if (channels > 4) throw ("remap: a 'bilinear' plane has 1 to 4 channels");
+                throw (`remap: a '${sampling}' plane must be a Float32Array, Uint8Array or Uint8ClampedArray`);
+            if (channels > 4) throw (`remap: a '${sampling}' plane has 1 to 4 channels`);
         } else if (![1, 2, 4, 8, 16].includes(channels * plane.BYTES_PER_ELEMENT)) {
             throw ("remap: a 'nearest' pixel (channels * BYTES_PER_ELEMENT) must be 1, 2, 4, 8 or 16 bytes");
         }
@@ -352,7 +356,7 @@ class Homography {
         const call = this._fieldCall('remap', fmt, options);          // (throws without an image)
         if (plane.length !== this._width * this._height * channels) throw ("remap: plane must hold width * height * channels elements of the instance's image size");
         if (call === null) return { data: new plane.constructor(0), width: 0, height: 0, channels };
-        const data = this._native['remap' + call.entry](this._ctx, ...call.args, plane, channels, this._width, this._height);
+        const data = this._native[(sampling === 'trilinear' ? 'remapTrilinear' : 'remap') + call.entry](this._ctx, ...call.args, plane, channels, this._width, this._height);
         return { data, width: call.width, height: call.height, channels };
     }
 

@@ -35,7 +35,7 @@ extern "C" {
 
 #define HG_VERSION 100          /* 0.1.0 (sampling modes are detected by the presence of hg_set_sampling, source fields by that of hg_field_inverse_geometric,
                                    the forward source fields by that of hg_field_forward_geometric, point lists by that of
-                                   hg_points_to_source_geometric_frames_device) */
+                                   hg_points_to_source_geometric_frames_device, mip pyramids and the trilinear remap by that of hg_pyramid_build_device) */
 
 enum {
     HG_OK = 0,
@@ -352,6 +352,55 @@ int hg_remap_bilinear_frames_device(hg_ctx *ctx, const hg_geom *geoms, int n_fra
                                     const void *d_coords, const size_t *field_offsets,
                                     const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes,
                                     int elem, int channels, void *d_out, const size_t *out_offsets);
+/* MINIFICATION on the field seam: the mip pyramid of a plane and a trilinear remap through it.  The remaps above read at most four source
+ * pixels per output pixel, so a shrink aliases (a one-pixel checkerboard shrunk 8x comes out 0 / 255); the trilinear remap reads the pyramid
+ * level(s) that match the field's own footprint (the same checkerboard: 128 everywhere).  Planes are those of the bilinear remaps: `channels`
+ * (1..4) interleaved elements per pixel, elem HG_ELEM_F32 or HG_ELEM_U8, W x H.
+ * Level sizes: W_0 = W, H_0 = H, W_k = (W_{k-1} + 1) >> 1, H_k alike; the full pyramid has Lmax = 1 + ceil(log2(max(W, H))) levels, the last
+ * one 1 x 1.  Level k >= 1, pixel (x, y), per channel: the taps are the level k-1 pixels at columns min(2x, W_{k-1}-1) and min(2x+1, W_{k-1}-1)
+ * and rows alike, a b / c d;  u8: out = ((a + b) + (c + d) + 2) >> 2 in integers;  f32: out = ((a + b) + (c + d)) * 0.25f, in that order,
+ * contraction off.
+ * hg_pyramid_levels (host only): Lmax, or 0 for W or H < 1.
+ * hg_pyramid_layout (host only): offsets[k], k = 1 .. levels-1, is the byte offset of level k inside ONE pyramid buffer: 256-byte aligned,
+ * a level tightly packed, ascending; offsets[0] = 0 and is unused (level 0 is never copied: it stays the caller's plane); *total = the bytes
+ * of one pyramid (0 for levels == 1).  levels must lie in 1..Lmax.  HG_ERR_INVALID: an unknown elem, channels outside 1..4, levels outside
+ * 1..Lmax (W or H < 1 included), NULL offsets or total.
+ * hg_pyramid_build_device: builds levels 1 .. levels-1 of every one of the n_planes planes (plane p at d_planes + p * plane_stride_bytes),
+ * pyramid p going to d_pyr + p * pyr_stride_bytes in hg_pyramid_layout's layout.  Asynchronous on the ctx stream: one launch per level covers
+ * all planes, each launch reading the level before it.  levels == 1: HG_OK, nothing happens.  d_planes, d_pyr and both strides are aligned
+ * to the element size (the rules of hg_remap_bilinear_frames_device); pyr_stride_bytes >= *total.  The call settles nothing: source planes
+ * that are outputs of queued warps are the caller's to settle (hg_sync), as for every remap.  HG_ERR_INVALID: what the layout refuses, W or H
+ * or n_planes < 1, NULL or misaligned pointers, a misaligned or too small stride.
+ * hg_remap_trilinear_frames_device: hg_remap_bilinear_frames_device's arguments, then the pyramids hg_pyramid_build_device made of the same
+ * planes (d_pyr, pyr_stride_bytes; frame f reads pyramid f % n_planes) and the number of levels to use.  Offset defaults, the f % n_planes
+ * rule, refusals, staging through the page-locked ring, "settle queued runs whose redo could land on d_out" and "no effect on hg_last_*, the
+ * sampling mode or the layout state" are those of hg_remap_bilinear_frames_device.  Unlike the other remaps it reads a frame as a 2-D
+ * obj_w x obj_h array, row-major.  Pixel (i, j) of a frame, (sx, sy) its f32 coordinate:
+ *   1. sx or sy NaN or infinite: every channel is 0.
+ *   2. Footprint, all in f32, contraction off.  Horizontal neighbour: pixel (i+1, j) if i+1 < obj_w and both its words are finite, otherwise
+ *      pixel (i-1, j) under the same conditions, otherwise none; vertical neighbour likewise with j+1, then j-1.  For a neighbour (nx, ny):
+ *      dx = nx - sx, dy = ny - sy, q_dir = dx*dx + dy*dy; a missing neighbour gives 0.  q = fmaxf(q_h, q_v); an overflow to +Inf is legal.
+ *   3. Level.  !(q > 1.0f): level 0 only.  Otherwise e = the unbiased binary exponent of q (q = m 2^e, m in [1, 2)) and k = e >> 1;
+ *      k >= levels-1: level levels-1 only; otherwise levels k and k+1 are blended with t = (ldexpf(q, -2k) - 1.0f) * 0.33333334f -- linear in
+ *      the squared scale: 0 at a shrink factor of 2^k, approaching 1 at 2^(k+1).
+ *   4. Sampling a level, per channel, unrounded f32: level 0 uses (sx, sy) as they are, level k >= 1 uses u = ((sx + 0.5f) * 2^-k) - 0.5f and
+ *      v likewise from sy; then exactly the rule of hg_remap_bilinear_f32_device on W_k x H_k (floorf, fraction, both taps clamped in float
+ *      before the integer conversion, (p00*(1-fx) + p01*fx)*(1-fy) + (p10*(1-fx) + p11*fx)*fy, u8 taps widened to float first).
+ *   5. One level: r = v_k.  Two levels: r = v_k + (v_{k+1} - v_k) * t.  f32 stores r; u8 stores (uint8)min(255, floor(r + 0.5f)).
+ * Hence with levels == 1, or a field that nowhere shrinks, the output IS hg_remap_bilinear_frames_device's, bit for bit (d_pyr may then be
+ * NULL); a constant plane comes out constant; coordinates of 1e30 are legal.  HG_ERR_INVALID: levels outside 1..Lmax, d_pyr NULL with
+ * levels > 1, a misaligned d_pyr or pyr_stride_bytes, and everything the bilinear frames form refuses.
+ * Cost (MI355X, 64 frames out of 8 planes of 3840 x 2160, a 4x shrink and a projective set; EXPERIMENTS.md F.5): the pyramids of 8 such planes build in 0.11-0.16 ms
+ * (1.7-2.3 TB/s of plane bytes); the trilinear remap takes 1.27-1.77 x the time of hg_remap_bilinear_frames_device on the same fields and planes. */
+int hg_pyramid_levels(int W, int H);
+int hg_pyramid_layout(int W, int H, int elem, int channels, int levels, size_t *offsets, size_t *total);
+int hg_pyramid_build_device(hg_ctx *ctx, const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
+                            int levels, void *d_pyr, size_t pyr_stride_bytes);
+int hg_remap_trilinear_frames_device(hg_ctx *ctx, const hg_geom *geoms, int n_frames,
+                                     const void *d_coords, const size_t *field_offsets,
+                                     const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes,
+                                     int elem, int channels, void *d_out, const size_t *out_offsets,
+                                     const void *d_pyr, size_t pyr_stride_bytes, int levels);
 /* The source field of the FORWARD warps (next section): what hg_warp_forward_* would paint, as geometry.  HG_FIELD_INDEX only, hence no
  * format argument: the forward loops copy whole pixels from integer positions, (s % W, s / W) IS the coordinate.  One int32 per output pixel
  * p, row-major obj_w x obj_h: let w be the LAST writer, in the loop's raster order (:919-930 over y < H, x < W; :955-969 over the cells of

@@ -1,0 +1,582 @@
+"""The mip pyramids and the trilinear remap on the GPU (include/hgwarp.h: hg_pyramid_build_device, hg_remap_trilinear_frames_device) against
+the numpy model of tests/hgtest/trilinear.py -- level by level and frame by frame, byte for byte (bit for bit for f32) --, against
+hg_remap_bilinear_frames_device where the two must agree, and the drop-in class on the real addon against the ctypes result.
+tests/test_trilinear_cpu.py pins the model itself against a scalar model written from the header."""
+import base64
+import functools
+import hashlib
+import json
+import os
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "homography.js_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import hgwarp as HG                          # noqa: E402
+from hgtest import oracle as O               # noqa: E402
+from hgtest import remap_frames as RF        # noqa: E402
+from hgtest import trilinear as TM           # noqa: E402
+from hgtest import workloads as WL           # noqa: E402
+
+pytestmark = pytest.mark.gpu
+CO = HG.FIELD_COORDS
+F32E, U8E = HG.ELEM_F32, HG.ELEM_U8
+F32 = np.float32
+INVALID = 1
+FILL, POISON = 0xA5, 0xEE                    # the output and the pyramids before a call; the bytes around the source planes
+SW, SH = 600, 40                             # the source of the remap tests: 11 levels
+LMAX = 11
+GRID = [(0, 0, w, h) for h in (1, 2, 5) for w in (1, 3, 63, 64, 65, 257)]
+assert TM.n_levels(SW, SH) == LMAX and len(GRID) == 18
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = HG.Context(0)
+    yield c
+    c.close()
+
+
+def _es(elem):
+    return 1 if elem == U8E else 4
+
+
+# ------------------------------------------------------------------------------------------------ inputs, made once and never modified
+@functools.lru_cache(maxsize=None)
+def _planes(elem, ch, w=SW, h=SH, n=3):
+    """n planes (h, w, ch); no byte of a uint8 plane (nor of a blend of its bytes) equals FILL or POISON; f32: normal-range values."""
+    rng = np.random.default_rng(2000 + 10 * ch + elem + w * 7 + h)
+    if elem == U8E:
+        ps = [rng.integers(1, 160, (h, w, ch), dtype=np.uint8) for _ in range(n)]
+    else:
+        ps = [(rng.standard_normal((h, w, ch)) * 40 + 3).astype(F32) for _ in range(n)]
+        assert all((np.abs(p) > 1e-30).all() for p in ps)
+    for p in ps:
+        p.setflags(write=False)
+    return tuple(ps)
+
+
+@functools.lru_cache(maxsize=None)
+def _pyrs(elem, ch, levels, w=SW, h=SH, n=3):
+    return tuple(TM.pyramid(p, levels) for p in _planes(elem, ch, w, h, n))
+
+
+def _split(raw, offs, geoms):
+    out = []
+    for o, g in zip(offs, geoms):
+        a = raw[o:o + RF.n_px(g) * 8].view(F32).reshape(-1, 2).copy()
+        a.setflags(write=False)
+        out.append(a)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _library_fields():
+    """The HG_FIELD_COORDS fields the library makes for three frame sets over the SW x SH source, downloaded once: an affine shrink of 0.23
+    and a projective set on GRID, and a shrinking piecewise set whose windows reach beyond the mesh (uncovered pixels are NaN)."""
+    out = {}
+    with HG.Context(0) as c:
+        c.set_image(np.zeros((SH, SW, 4), np.uint8))             # (a field reads the source's SIZE only)
+        s = 1 / 0.23
+        aff = np.concatenate([[s, 0.01 * f, -0.02, s, 0.3 * f, 0.1, 0, 0] for f in range(len(GRID))])
+        pro = np.concatenate([[1.2, 0.02, 0.5, 0.01 * f, 1.2, 0.25, -1 / (270 + f), 0.0002] for f in range(len(GRID))])
+        offs, total = HG.pack_field_offsets(GRID, CO)
+        for name, kind, mats in (("affine", 0, aff), ("projective", 1, pro)):
+            d = c.alloc(total)
+            try:
+                c.geometric_set_frames(kind, mats, GRID)
+                c.field_inverse_geometric_frames_device(CO, d)
+                c.sync()
+                out[name] = (GRID, _split(c.to_host(d, total), offs, GRID))
+            finally:
+                c.free(d)
+        nx, ny = 6, 2
+        sp, tris = WL.grid_points(SW, SH, nx, ny), WL.grid_triangles(nx, ny)
+        p = sp.reshape(-1, 2).astype(np.float64)
+        dps = [np.stack([p[:, 0] * k + 4, p[:, 1] * k + 3 + 1.5 * np.sin(p[:, 0] / 70 + f)], 1).astype(F32).ravel() for f, k in enumerate((0.3, 0.12, 0.3))]
+        geoms = [(0, 0, 200, 20), (-2, -1, 90, 14), (1, 2, 65, 5)]
+        offs, total = HG.pack_field_offsets(geoms, CO)
+        d = c.alloc(total)
+        try:
+            c.piecewise_set_mesh(sp, tris, *WL.src_min(sp))
+            c.piecewise_set_frames(np.concatenate(dps), geoms)
+            c.field_inverse_piecewise_frames_device(CO, d)
+            c.sync()
+            out["piecewise"] = (geoms, _split(c.to_host(d, total), offs, geoms))
+        finally:
+            c.free(d)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _caller_fields():
+    """Caller-made fields on GRID: steps from below one pixel to the whole source, with NaN, +-Inf and 1e30 entries in the larger frames."""
+    rng = np.random.default_rng(31)
+    out = []
+    for f, (_, _, w, h) in enumerate(GRID):
+        i, j = np.meshgrid(np.arange(w), np.arange(h))
+        sx = 0.05 * (np.exp(i / 22.0) - 1) * (1 + 0.3 * j) + f
+        co = np.stack([sx, 0.4 * j * (1 + i / 40.0) + 0.3 * f], -1).astype(F32)
+        if w >= 63:
+            co[rng.random((h, w)) < 0.04] = np.nan
+            co[0, 5:13] = [[np.nan, 3], [3, np.nan], [np.inf, 2], [2, -np.inf], [1e30, 5], [5, -1e30], [-1e30, 1e30], [3e38, -3e38]]
+            co[h - 1, 20] = [1e30, 1e30]
+            co[h - 1, w - 1] = np.inf
+            co[0, 0] = np.nan
+        co = co.reshape(-1, 2)
+        co.setflags(write=False)
+        out.append(co)
+    return out
+
+
+def _place(parts, offs, total, fill):
+    buf = np.full(total, fill, np.uint8)
+    for p, o in zip(parts, offs):
+        b = np.ascontiguousarray(p).view(np.uint8).ravel()
+        buf[o:o + b.size] = b
+    return buf
+
+
+def _run(ctx, geoms, fields, planes, elem, ch, levels, foffs=None, ooffs=None, stride=None, front=256, pyr_slack=256, call=None):
+    """Upload the fields (at foffs, or packed) and the planes (inside an allocation full of POISON, `front` bytes in, `stride` apart), fill
+    the pyramids and the output with FILL, build the pyramids, remap, and return (output bytes, output offsets, pyramid bytes, pyramid stride)."""
+    px = ch * _es(elem)
+    h, w = planes[0].shape[:2]
+    fo = list(foffs) if foffs is not None else RF.pack(geoms, 8)[0]
+    oo = list(ooffs) if ooffs is not None else RF.pack(geoms, px)[0]
+    plane_bytes = planes[0].nbytes
+    stride = stride if stride is not None else (plane_bytes + 255) // 256 * 256 + 256
+    pyr_total = TM.layout(w, h, px, levels)[1]
+    pyr_stride = pyr_total + pyr_slack
+    f_total = max([o + RF.n_px(g) * 8 for o, g in zip(fo, geoms)] + [0]) + 256
+    o_total = max([o + RF.n_px(g) * px for o, g in zip(oo, geoms)] + [0]) + 512
+    p_total = front + stride * len(planes) + 256
+    y_total = pyr_stride * len(planes) + 256
+    d_f, d_p, d_o, d_y = ctx.alloc(f_total), ctx.alloc(p_total), ctx.alloc(o_total), ctx.alloc(y_total)
+    try:
+        ctx.to_device(d_f, _place(fields, fo, f_total, 0x11))
+        ctx.to_device(d_p, _place(planes, [front + k * stride for k in range(len(planes))], p_total, POISON))
+        ctx.to_device(d_o, np.full(o_total, FILL, np.uint8))
+        ctx.to_device(d_y, np.full(y_total, FILL, np.uint8))
+        ctx.pyramid_build_device(d_p + front, w, h, len(planes), stride, elem, ch, levels, d_y, pyr_stride)
+        if call is not None:
+            call(d_f, d_p + front, stride, d_o, d_y, pyr_stride)
+        else:
+            ctx.remap_trilinear_frames_device(geoms, d_f, d_p + front, w, h, len(planes), stride, elem, ch, d_o, d_y, pyr_stride, levels, foffs, ooffs)
+        ctx.sync()
+        return ctx.to_host(d_o, o_total), oo, ctx.to_host(d_y, y_total), pyr_stride
+    finally:
+        for p in (d_f, d_p, d_o, d_y):
+            ctx.free(p)
+
+
+def _check(raw, oo, geoms, want, px_bytes, what):
+    """Every frame equals the model, bit for bit, and every byte outside the frames is still FILL."""
+    untouched = np.ones(raw.size, bool)
+    for f, g in enumerate(geoms):
+        n = RF.n_px(g) * px_bytes
+        untouched[oo[f]:oo[f] + n] = False
+        w = np.ascontiguousarray(want[f]).view(np.uint8).ravel()
+        assert w.size == n, (what, f)
+        got = raw[oo[f]:oo[f] + n]
+        if not np.array_equal(got, w):
+            bad = np.flatnonzero(got != w)
+            raise AssertionError(f"{what}: frame {f} {g}: {bad.size} of {n} bytes differ, first at pixel {int(bad[0]) // px_bytes}: "
+                                 f"got {got[bad[:8]].tolist()}, want {w[bad[:8]].tolist()}")
+    assert (raw[untouched] == FILL).all(), (what, "bytes between the frames, the padding and the tail must not be written")
+
+
+def _check_pyramids(raw, stride, pyrs, px_bytes, what):
+    """Every level of every pyramid equals the model and every other byte of the allocation is still FILL."""
+    h, w = pyrs[0][0].shape[:2]
+    offs, _ = TM.layout(w, h, px_bytes, len(pyrs[0]))
+    untouched = np.ones(raw.size, bool)
+    for p, pyr in enumerate(pyrs):
+        for k in range(1, len(pyr)):
+            want = np.ascontiguousarray(pyr[k]).view(np.uint8).ravel()
+            at = p * stride + offs[k]
+            untouched[at:at + want.size] = False
+            got = raw[at:at + want.size]
+            assert np.array_equal(got, want), (what, "plane", p, "level", k, int((got != want).sum()), got[:8].tolist(), want[:8].tolist())
+    assert (raw[untouched] == FILL).all(), (what, "bytes between the levels, the slack between pyramids and the tail must not be written")
+
+
+# ------------------------------------------------------------------------------------------------ the pyramid
+@pytest.mark.parametrize("channels", (1, 2, 3, 4))
+@pytest.mark.parametrize("elem", (F32E, U8E))
+def test_pyramid_build(ctx, elem, channels):
+    es, px = _es(elem), channels * _es(elem)
+    for w, h in ((1, 1), (2, 2), (3, 5), (64, 3), (65, 67), (257, 130)):
+        lmax = TM.n_levels(w, h)
+        assert HG.pyramid_levels(w, h) == lmax
+        for n_planes in (1, 3):
+            planes = _planes(elem, channels, w, h)[:n_planes]
+            for levels in sorted({min(2, lmax), lmax}):
+                offs, total = HG.pyramid_layout(w, h, elem, channels, levels)
+                assert (offs, total) == TM.layout(w, h, px, levels)
+                stride = planes[0].nbytes + 3 * es                # slack between the planes; for bytes a stride that breaks every alignment
+                front = 256 + es                                   # ... and a start that is aligned to the element only
+                pyr_stride = total + 256 + 3 * es
+                d_p, d_y = ctx.alloc(front + stride * n_planes + 256), ctx.alloc(pyr_stride * n_planes + 512)
+                try:
+                    src = _place(planes, [front + k * stride for k in range(n_planes)], front + stride * n_planes + 256, POISON)
+                    ctx.to_device(d_p, src)
+                    ctx.to_device(d_y, np.full(pyr_stride * n_planes + 512, FILL, np.uint8))
+                    ctx.pyramid_build_device(d_p + front, w, h, n_planes, stride, elem, channels, levels, d_y + es, pyr_stride)
+                    ctx.sync()
+                    raw = ctx.to_host(d_y, pyr_stride * n_planes + 512)
+                    assert raw[:es].tolist() == [FILL] * es
+                    _check_pyramids(raw[es:], pyr_stride, [TM.pyramid(p, levels) for p in planes], px, (w, h, elem, channels, n_planes, levels))
+                    assert np.array_equal(ctx.to_host(d_p, src.size), src)         # the planes and the bytes around them are only read
+                    if elem == U8E:
+                        assert not (raw == POISON).any()
+                finally:
+                    ctx.free(d_p)
+                    ctx.free(d_y)
+
+
+# ------------------------------------------------------------------------------------------------ the remap against the model
+@pytest.mark.parametrize("channels", (1, 2, 3, 4))
+@pytest.mark.parametrize("elem", (F32E, U8E))
+def test_trilinear_frames_of_the_librarys_geometric_fields(ctx, elem, channels):
+    px = channels * _es(elem)
+    for name in ("affine", "projective"):
+        geoms, fields = _library_fields()[name]
+        planes = _planes(elem, channels)
+        for levels in (1, 2, LMAX):
+            want = TM.trilinear_frames(geoms, fields, _pyrs(elem, channels, levels))
+            raw, oo, pyr, pstride = _run(ctx, geoms, fields, planes, elem, channels, levels)
+            _check(raw, oo, geoms, want, px, (name, elem, channels, levels))
+            _check_pyramids(pyr, pstride, _pyrs(elem, channels, levels), px, (name, elem, channels, levels))
+
+
+def test_the_premises_of_the_librarys_fields():
+    """The affine set shrinks by about 0.23 (q about 18.9: levels 2 and 3), the projective footprint spans at least three levels, the
+    piecewise set has uncovered pixels beside covered ones, and all three have pixels that sample."""
+    lib = _library_fields()
+    for name in ("affine", "projective", "piecewise"):
+        geoms, fields = lib[name]
+        ks = set()
+        nan = fin = 0
+        for g, co in zip(geoms, fields):
+            co = co.reshape(g[3], g[2], 2)
+            ok = np.isfinite(co).all(-1)
+            k, two, _ = TM.level_choice(TM.footprint(co), LMAX)
+            ks |= set(k[ok].tolist()) | set((k[ok & two] + 1).tolist())
+            nan, fin = nan + int((~ok).sum()), fin + int(ok.sum())
+            if name == "affine" and g[2] >= 63 and g[3] >= 2:
+                q = TM.footprint(co)[ok]
+                assert (np.abs(np.sqrt(q[q > 0]) - 1 / 0.23) < 0.2).all()
+        assert fin > 500, (name, fin)
+        if name == "affine":
+            assert {2, 3} <= ks, ks
+        if name == "projective":
+            assert len(ks) >= 3, ks
+        if name == "piecewise":
+            assert nan > 500 and len(ks) >= 2, (nan, ks)
+
+
+@pytest.mark.parametrize("elem,channels", ((U8E, 4), (F32E, 1), (U8E, 3), (F32E, 2)))
+def test_trilinear_frames_of_a_piecewise_field_with_uncovered_pixels(ctx, elem, channels):
+    geoms, fields = _library_fields()["piecewise"]
+    px = channels * _es(elem)
+    for n_planes in (1, 3):
+        planes = _planes(elem, channels)[:n_planes]
+        want = TM.trilinear_frames(geoms, fields, _pyrs(elem, channels, LMAX)[:n_planes])
+        assert any(not w_[~np.isfinite(f).all(-1)].any() and w_.any() for w_, f in zip(want, fields))
+        raw, oo, _, _ = _run(ctx, geoms, fields, planes, elem, channels, LMAX)
+        _check(raw, oo, geoms, want, px, ("piecewise", elem, channels, n_planes))
+
+
+@pytest.mark.parametrize("elem,channels", ((U8E, 1), (U8E, 2), (U8E, 4), (F32E, 1), (F32E, 3), (F32E, 4)))
+def test_caller_made_fields_with_nan_infinite_and_huge_coordinates(ctx, elem, channels):
+    px = channels * _es(elem)
+    fields = _caller_fields()
+    planes = _planes(elem, channels)
+    for levels in (2, LMAX):
+        want = TM.trilinear_frames(GRID, fields, _pyrs(elem, channels, levels))
+        f17 = fields[17].reshape(5, 257, 2)
+        assert not want[17].reshape(5, 257, channels)[0, 5:9].any() and want[17].reshape(5, 257, channels)[0, 9:13].any()      # NaN / Inf: zeros; 1e30: clamped taps
+        assert np.isnan(f17).any() and np.isinf(f17).any() and (np.abs(f17[np.isfinite(f17)]) >= 1e30).any()
+        raw, oo, _, _ = _run(ctx, GRID, fields, planes, elem, channels, levels, stride=planes[0].nbytes, front=16)      # planes back to back, poison in front and behind
+        _check(raw, oo, GRID, want, px, ("caller-made", elem, channels, levels))
+        if elem == U8E:
+            assert not (raw == POISON).any()
+    k, two, _ = TM.level_choice(np.concatenate([TM.footprint(f.reshape(g[3], g[2], 2)).ravel() for f, g in zip(fields, GRID)]), LMAX)
+    assert set(range(8)) <= set(k.tolist()) and two.any() and (~two).any()
+
+
+def test_explicit_offsets_and_strides_that_break_every_wider_alignment(ctx):
+    fields = _caller_fields()
+    fo8 = [o + 8 * (2 * f + 1) + 512 * f for f, o in enumerate(RF.pack(GRID, 8)[0])]            # odd multiples of 8: no 16-byte alignment
+    assert all(o % 8 == 0 and o % 16 != 0 for o in fo8)
+    for elem in (U8E, F32E):
+        es = _es(elem)
+        for ch in (1, 2, 3, 4):
+            planes = _planes(elem, ch)
+            oo = [o + 640 * f + es * (2 * f + 1) for f, o in enumerate(RF.pack(GRID, ch * es)[0])]  # odd element offsets: multiples of 4 (f32) but never of 8 or 16; no 2- or 4-byte store fits (u8)
+            assert all(o % es == 0 and (o // es) % 2 == 1 for o in oo)
+            stride = planes[0].nbytes + 256 + es * 3
+            want = TM.trilinear_frames(GRID, fields, _pyrs(elem, ch, LMAX))
+            raw, used, pyr, pstride = _run(ctx, GRID, fields, planes, elem, ch, LMAX, fo8, oo, stride, front=256 + es, pyr_slack=256 + es * 3)
+            _check(raw, used, GRID, want, ch * es, ("explicit offsets", elem, ch))
+            _check_pyramids(pyr, pstride, _pyrs(elem, ch, LMAX), ch * es, ("explicit offsets", elem, ch))
+
+
+# ------------------------------------------------------------------------------------------------ where it IS the bilinear remap
+@pytest.mark.parametrize("elem,channels", ((U8E, 1), (U8E, 4), (F32E, 1), (F32E, 4), (U8E, 3), (F32E, 2)))
+def test_one_level_and_magnifying_fields_equal_the_bilinear_frames_remap(ctx, elem, channels):
+    planes = _planes(elem, channels)
+    mag = []
+    for f, (_, _, w, h) in enumerate(GRID):
+        i, j = np.meshgrid(np.arange(w), np.arange(h))
+        co = np.stack([0.6 * i + 0.3 * j + 5 * f - 2, 0.7 * j - 0.2 * i + f], -1).astype(F32)
+        assert (TM.footprint(co) <= 1).all()
+        if w >= 63:
+            co[0, 7] = np.nan                                   # (a hole only removes neighbours)
+        mag.append(co.reshape(-1, 2))
+
+    def bilinear(d_f, d_p, stride, d_o, d_y, pyr_stride):
+        ctx.remap_bilinear_frames_device(GRID, d_f, d_p, SW, SH, 3, stride, elem, channels, d_o)
+
+    for name, fields, levels in (("levels == 1", _caller_fields(), 1), ("magnifying", mag, LMAX), ("magnifying, 2 levels", mag, 2)):
+        a, _, _, _ = _run(ctx, GRID, fields, planes, elem, channels, levels)
+        b, _, _, _ = _run(ctx, GRID, fields, planes, elem, channels, levels, call=bilinear)
+        assert np.array_equal(a, b) and (a != FILL).any(), (name, int((a != b).sum()))
+    # levels == 1 needs no pyramid at all
+    def no_pyramid(d_f, d_p, stride, d_o, d_y, pyr_stride):
+        ctx.remap_trilinear_frames_device(GRID, d_f, d_p, SW, SH, 3, stride, elem, channels, d_o, 0, 0, 1)
+
+    c, _, _, _ = _run(ctx, GRID, _caller_fields(), planes, elem, channels, 1, call=no_pyramid)
+    d, _, _, _ = _run(ctx, GRID, _caller_fields(), planes, elem, channels, 1, call=bilinear)
+    assert np.array_equal(c, d)
+
+
+def test_the_checkerboard_shrunk_8x_is_grey_on_the_device(ctx):
+    n = 256
+    y, x = np.mgrid[0:n, 0:n]
+    board = np.ascontiguousarray((((x + y) & 1) * 255).astype(np.uint8)[..., None])
+    i, j = np.meshgrid(np.arange(n // 8), np.arange(n // 8))
+    g = [(0, 0, n // 8, n // 8)]
+    co = [np.stack([8.0 * i + 1, 8.0 * j], -1).astype(F32).reshape(-1, 2)]
+    tri, oo, _, _ = _run(ctx, g, co, (board,), U8E, 1, TM.n_levels(n, n))
+    bil, _, _, _ = _run(ctx, g, co, (board,), U8E, 1, TM.n_levels(n, n),
+                        call=lambda d_f, d_p, stride, d_o, d_y, ps: ctx.remap_bilinear_frames_device(g, d_f, d_p, n, n, 1, stride, U8E, 1, d_o))
+    assert (tri[:1024] == 128).all() and (bil[:1024] == 255).all()
+
+
+# ------------------------------------------------------------------------------------------------ refusals
+def _code(fn, *a):
+    with pytest.raises(HG.HgError) as e:
+        fn(*a)
+    return e.value.code
+
+
+def test_refusals():
+    g = [(0, 0, 8, 2), (0, 0, 4, 1)]
+    W, H = 8, 4                                                  # 4 levels
+    with HG.Context(0) as c:
+        d = c.alloc(16384)
+        d_f, d_p, d_o, d_y = d, d + 4096, d + 8192, d + 12288
+        co = (np.random.default_rng(2).random((20, 2)) * [7, 3]).astype(F32)
+        plane = np.arange(1, 33, dtype=np.float32).reshape(H, W, 1)
+        c.to_device(d_f, _place([co[:16], co[16:]], [0, 256], 512, 0))
+        c.to_device(d_p, plane)
+        want = TM.trilinear_frames(g, [co[:16], co[16:]], [TM.pyramid(plane, 4)])
+
+        def still_works():
+            c.to_device(d_o, np.full(512, FILL, np.uint8))
+            c.pyramid_build_device(d_p, W, H, 1, 0, F32E, 1, 4, d_y, 1024)
+            c.remap_trilinear_frames_device(g, d_f, d_p, W, H, 1, 0, F32E, 1, d_o, d_y, 1024, 4)
+            c.sync()
+            raw = c.to_host(d_o, 512)
+            assert np.array_equal(raw[:64].view(F32), want[0].ravel()) and np.array_equal(raw[256:272].view(F32), want[1].ravel()) and (raw[64:256] == FILL).all()
+
+        def refused(fn, *a):
+            assert _code(fn, *a) == INVALID, a
+            still_works()
+
+        rt, pb = c.remap_trilinear_frames_device, c.pyramid_build_device
+        try:
+            still_works()
+            assert HG.pyramid_layout(W, H, F32E, 1, 4)[1] == 768
+            # build: (d_planes, w, h, n_planes, plane_stride, elem, channels, levels, d_pyr, pyr_stride)
+            for levels in (0, 5, -1, 33):
+                refused(pb, d_p, W, H, 1, 0, F32E, 1, levels, d_y, 1024)
+            for elem in (2, -1):
+                refused(pb, d_p, W, H, 1, 0, elem, 1, 4, d_y, 1024)
+            for ch in (0, 5):
+                refused(pb, d_p, W, H, 1, 0, F32E, ch, 4, d_y, 4096)
+            for w, h in ((0, 4), (8, 0), (-1, 4)):
+                refused(pb, d_p, w, h, 1, 0, F32E, 1, 1, d_y, 1024)
+            refused(pb, d_p, W, H, 0, 0, F32E, 1, 4, d_y, 1024)               # n_planes
+            refused(pb, 0, W, H, 1, 0, F32E, 1, 4, d_y, 1024)                 # NULL pointers
+            refused(pb, d_p, W, H, 1, 0, F32E, 1, 4, 0, 1024)
+            refused(pb, d_p + 2, W, H, 1, 0, F32E, 1, 4, d_y, 1024)           # misaligned pointers and strides
+            refused(pb, d_p, W, H, 1, 0, F32E, 1, 4, d_y + 1, 1024)
+            refused(pb, d_p, W, H, 2, 130, F32E, 1, 4, d_y, 1024)
+            refused(pb, d_p, W, H, 1, 0, F32E, 1, 4, d_y, 1026)
+            refused(pb, d_p, W, H, 1, 0, F32E, 1, 4, d_y, 764)                # smaller than one pyramid
+            pb(d_p, W, H, 1, 0, F32E, 1, 1, 0, 0)                             # levels == 1: nothing to do, whatever d_pyr is
+            # remap: (geoms, d_coords, d_planes, w, h, n_planes, stride, elem, channels, d_out, d_pyr, pyr_stride, levels, field_offsets, out_offsets)
+            for levels in (0, 5, -1, 33):
+                refused(rt, g, d_f, d_p, W, H, 1, 0, F32E, 1, d_o, d_y, 1024, levels)
+            refused(rt, g, d_f, d_p, W, H, 1, 0, F32E, 1, d_o, 0, 1024, 2)    # d_pyr NULL with levels > 1
+            refused(rt, g, d_f, d_p, W, H, 1, 0, F32E, 1, d_o, d_y + 2, 1024, 4)     # a misaligned pyramid / stride
+            refused(rt, g, d_f, d_p, W, H, 1, 0, F32E, 1, d_o, d_y, 1026, 4)
+            # ... and everything the bilinear frames form refuses
+            for elem in (2, -1):
+                refused(rt, g, d_f, d_p, W, H, 1, 0, elem, 1, d_o, d_y, 1024, 4)
+            for ch in (0, 5):
+                refused(rt, g, d_f, d_p, W, H, 1, 0, F32E, ch, d_o, d_y, 4096, 4)
+            for w, h in ((0, 4), (8, 0), (-1, 4)):
+                refused(rt, g, d_f, d_p, w, h, 1, 0, F32E, 1, d_o, d_y, 1024, 1)
+            refused(rt, g, d_f, d_p, W, H, 0, 0, F32E, 1, d_o, d_y, 1024, 4)   # n_planes
+            refused(rt, g, 0, d_p, W, H, 1, 0, F32E, 1, d_o, d_y, 1024, 4)     # NULL pointers
+            refused(rt, g, d_f, 0, W, H, 1, 0, F32E, 1, d_o, d_y, 1024, 4)
+            refused(rt, g, d_f, d_p, W, H, 1, 0, F32E, 1, 0, d_y, 1024, 4)
+            refused(rt, g, d_f + 4, d_p, W, H, 1, 0, F32E, 1, d_o, d_y, 1024, 4)     # misaligned coordinates, planes, output, stride, offsets
+            refused(rt, g, d_f, d_p + 2, W, H, 1, 0, F32E, 1, d_o, d_y, 1024, 4)
+            refused(rt, g, d_f, d_p, W, H, 1, 0, F32E, 1, d_o + 1, d_y, 1024, 4)
+            refused(rt, g, d_f, d_p, W, H, 2, 130, F32E, 1, d_o, d_y, 1024, 4)
+            refused(rt, g, d_f, d_p, W, H, 1, 0, F32E, 1, d_o, d_y, 1024, 4, [0, 260])
+            refused(rt, g, d_f, d_p, W, H, 1, 0, F32E, 1, d_o, d_y, 1024, 4, None, [0, 258])
+            L = HG.lib()
+            geoms = HG._geoms(g)
+            vp = HG.C.c_void_p
+            assert L.hg_remap_trilinear_frames_device(c._h, geoms, -1, vp(d_f), None, vp(d_p), W, H, 1, 0, 0, 1, vp(d_o), None, vp(d_y), 1024, 4) == INVALID
+            assert L.hg_remap_trilinear_frames_device(c._h, geoms, 65536, vp(d_f), None, vp(d_p), W, H, 1, 0, 0, 1, vp(d_o), None, vp(d_y), 1024, 4) == INVALID
+            assert L.hg_remap_trilinear_frames_device(c._h, None, 2, vp(d_f), None, vp(d_p), W, H, 1, 0, 0, 1, vp(d_o), None, vp(d_y), 1024, 4) == INVALID
+            assert L.hg_remap_trilinear_frames_device(c._h, None, 0, None, None, None, W, H, 1, 0, 0, 1, None, None, None, 0, 1) == 0      # n_frames == 0
+            still_works()
+        finally:
+            c.free(d)
+
+
+# ------------------------------------------------------------------------------------------------ what the calls leave alone
+def _state(c):
+    return (c.last_piecewise_kernel(), c.last_piecewise_variant(), c.last_piecewise_self(), c.last_piecewise_flag(), c.last_geometric_kernel(),
+            c.last_forward_kernel(), c.last_forward_field_kernel(), c.sampling, c.redone_frames(), c.layout_walks())
+
+
+def test_state_is_untouched_and_a_queued_nearest_warp_keeps_its_bytes():
+    W, H, F = 256, 160, 3
+    img = WL.lcg_image(W, H, 81)
+    s4 = WL.corners(W, H)
+    d4s = [WL.projective_dst(W, H, 0.03 * k) * 0.3 for k in range(F)]                         # a shrink: the inverse loop
+    gg = [tuple(int(v) for v in O.transform_limits(1, O.projective_from_squares(s4, d4), W, H)) for d4 in d4s]
+    offs, total = HG.pack_offsets(gg)
+    levels = HG.pyramid_levels(W, H)
+    _, ptotal = HG.pyramid_layout(W, H, U8E, 4, levels)
+    with HG.Context(0) as c:
+        d_src, d_f, d_w, d_r, d_y = c.alloc(img.nbytes), c.alloc(2 * total), c.alloc(total), c.alloc(total), c.alloc(ptotal)
+        try:
+            c.set_sampling(HG.SAMPLE_BILINEAR)
+            c.set_sampling(HG.SAMPLE_NEAREST)
+            c.to_device(d_src, img)
+            c.set_image_device(d_src, W, H)
+            c.geometric_set_frames_points(1, np.concatenate(d4s), np.tile(s4, F), gg, offs)
+            c.warp_inverse_geometric_frames_device(d_w)
+            c.sync()
+            alone = c.to_host(d_w, total)
+            assert alone.any()
+            c.field_inverse_geometric_frames_device(CO, d_f)
+            c.sync()
+            fo = HG.pack_field_offsets(gg, CO)[0]
+            fields = _split(c.to_host(d_f, 2 * total), fo, gg)
+            c.to_device(d_w, np.zeros(total, np.uint8))
+            c.warp_inverse_geometric_frames_device(d_w)                   # queued ...
+            mid = _state(c)
+            c.pyramid_build_device(d_src, W, H, 1, 0, U8E, 4, levels, d_y, ptotal)
+            c.remap_trilinear_frames_device(gg, d_f, d_src, W, H, 1, 0, U8E, 4, d_r, d_y, ptotal, levels)      # ... in front of the remap of the picture itself
+            assert _state(c) == mid
+            c.sync()
+            assert _state(c) == mid and c.sampling == HG.SAMPLE_NEAREST
+            again = c.to_host(d_w, total)
+            for f, g in enumerate(gg):                                    # (the padding between frames is nobody's)
+                assert np.array_equal(again[offs[f]:offs[f] + RF.n_px(g) * 4], alone[offs[f]:offs[f] + RF.n_px(g) * 4]) and again[offs[f]:offs[f] + RF.n_px(g) * 4].any(), f
+            want = TM.trilinear_frames(gg, fields, [TM.pyramid(img.reshape(H, W, 4), levels)])
+            got = c.to_host(d_r, total)
+            for f, g in enumerate(gg):
+                assert np.array_equal(got[offs[f]:offs[f] + RF.n_px(g) * 4], want[f].ravel()), f
+        finally:
+            c.set_image(img)
+            for p in (d_src, d_f, d_w, d_r, d_y):
+                c.free(p)
+
+
+def test_a_queued_redo_never_lands_on_a_later_trilinear_remap():
+    """A piecewise warp whose rows carry 1100 spans is queued into buffer B (its frame is flagged, to be redone through the map at hg_sync); a
+    trilinear remap then writes B.  After hg_sync B holds the remap."""
+    n, W2, H2 = 1100, 2400, 8
+    img = WL.lcg_image(W2, H2, 10)
+    xs = np.linspace(0, W2, n + 1)
+    sp = np.stack([np.repeat(xs, 2), np.tile([0.0, H2], n + 1)], 1).astype(np.float32).ravel()
+    tr = np.array([[2 * i, 2 * i + 2, 2 * i + 1] for i in range(n)], np.uint32).ravel()
+    dp = sp.copy()
+    dp[1::2] *= 1.5
+    mm, md = O.minmax_xy(sp), O.minmax_xy(dp)
+    g = (int(md[0]), int(md[1]), int(md[2] - md[0]), int(md[3] - md[1]))
+    npx = g[2] * g[3]
+    i, j = np.meshgrid(np.arange(g[2]), np.arange(g[3]))
+    co = np.stack([(i * 3.3) % W2, j * 0.6], -1).astype(F32).reshape(-1, 2)
+    levels = 5
+    want = TM.trilinear_frames([g], [co], [TM.pyramid(img.reshape(H2, W2, 4), levels)])[0]
+    _, ptotal = HG.pyramid_layout(W2, H2, U8E, 4, levels)
+    with HG.Context(0) as c:
+        d_src, d_f, d_b, d_y = c.alloc(img.nbytes), c.alloc(npx * 8), c.alloc(npx * 4), c.alloc(ptotal)
+        try:
+            c.to_device(d_src, img)
+            c.to_device(d_f, co)
+            c.set_image_device(d_src, W2, H2)
+            c.piecewise_set_mesh(sp, tr, int(mm[0]), int(mm[1]))
+            c.piecewise_set_frames(dp, [g], [0])
+            r0 = c.redone_frames()
+            c.pyramid_build_device(d_src, W2, H2, 1, 0, U8E, 4, levels, d_y, ptotal)
+            c.warp_inverse_piecewise_frames_device(d_b)
+            c.remap_trilinear_frames_device([g], d_f, d_src, W2, H2, 1, 0, U8E, 4, d_b, d_y, ptotal, levels)
+            c.sync()
+            assert c.redone_frames() > r0                      # the warp's frame WAS flagged and redone ...
+            got = c.to_host(d_b, npx * 4).reshape(npx, 4)
+            assert np.array_equal(got, want)                   # ... and the remap stands
+        finally:
+            c.set_image(img)
+            for p in (d_src, d_f, d_b, d_y):
+                c.free(p)
+
+
+# ------------------------------------------------------------------------------------------------ the drop-in class
+def test_js_class_trilinear_matches_the_ctypes_result(ctx):
+    """tests/js/trilinear_gpu.mjs: remap(plane, {sampling: 'trilinear'}) of js/Homography.mjs on the real addon for an affine, a projective
+    and a piecewise shrink; it prints its coordinate fields and the SHA-256 of every result, and the same planes through the same fields
+    by ctypes (all levels) must hash alike -- and equal the model."""
+    node = shutil.which("node")
+    addon = os.path.join(ROOT, "homography.js_amd", "lib", "hgwarp.node")
+    assert node is not None and os.path.exists(addon), "node and the N-API addon are needed on a GPU box"
+    p = subprocess.run([node, os.path.join(ROOT, "tests", "js", "trilinear_gpu.mjs")], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert line, p.stdout[-2000:] + p.stderr[-2000:]
+    res = json.loads(line[-1])
+    assert p.returncode == 0 and res["ok"] and not res["fails"], (res["fails"], p.stderr[-2000:])
+    W, H = res["W"], res["H"]
+    idx = np.arange(W * H * 4, dtype=np.int64)
+    u8 = ((idx * 7 + (idx >> 3) * 13) & 255).astype(np.uint8).reshape(H, W, 4)
+    f32 = ((idx[:W * H] * 37 % 1001) * 0.25 - 100).astype(F32).reshape(H, W, 1)
+    levels = HG.pyramid_levels(W, H)
+    assert set(res["cases"]) == {"affine", "projective", "piecewise"}
+    for name, case in res["cases"].items():
+        g = [(0, 0, case["width"], case["height"])]
+        co = np.frombuffer(base64.b64decode(case["coords"]), F32).reshape(-1, 2)
+        assert co.shape[0] == case["width"] * case["height"] and np.isfinite(co).any()
+        k, two, _ = TM.level_choice(TM.footprint(co.reshape(case["height"], case["width"], 2)), levels)
+        assert (k[np.isfinite(co).all(-1).reshape(k.shape)] >= 1).any(), name        # the case does shrink
+        for key, plane, elem, ch in (("u8x4", u8, U8E, 4), ("f32x1", f32, F32E, 1)):
+            raw, oo, _, _ = _run(ctx, g, [co], (plane,), elem, ch, levels)
+            got = raw[:co.shape[0] * ch * _es(elem)]
+            assert hashlib.sha256(got.tobytes()).hexdigest() == case[key], (name, key)
+            assert np.array_equal(got, TM.trilinear_frames(g, [co], [TM.pyramid(plane, levels)])[0].view(np.uint8).ravel()), (name, key)

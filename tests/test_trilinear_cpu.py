@@ -1,0 +1,426 @@
+"""CPU-side checks of the mip pyramids and the trilinear remap (include/hgwarp.h, hg_pyramid_* / hg_remap_trilinear_frames_device):
+declarations, exports and NULL handles, the host-only pyramid geometry, the vectorised numpy model of tests/hgtest/trilinear.py against a
+scalar model written from the header text, the model's own properties (levels == 1 and magnifying fields ARE the bilinear remap, constants
+stay constant, the one-pixel checkerboard shrunk 8x is grey), and the class's remap() with sampling 'trilinear' over a recording mock."""
+import ctypes as C
+import functools
+import json
+import math
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "homography.js_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import hgwarp as HG                          # noqa: E402
+from hgtest import remap_frames as RF        # noqa: E402
+from hgtest import trilinear as TM           # noqa: E402
+
+NEW = ["hg_pyramid_levels", "hg_pyramid_layout", "hg_pyramid_build_device", "hg_remap_trilinear_frames_device"]
+INVALID = 1
+F32 = np.float32
+SIZES = [(1, 1), (1, 9), (2, 2), (7, 5), (64, 3), (257, 130), (3840, 2160)]
+
+
+# ------------------------------------------------------------------------------------------------ symbols
+def test_header_declares_and_library_exports_the_new_entry_points():
+    text = open(os.path.join(ROOT, "include", "hgwarp.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    declared = set(re.findall(r"\b(hg_[a-z0-9_]+)\s*\(", code))
+    L = HG.lib()
+    for name in NEW:
+        assert name in declared and hasattr(L, name) and name in HG.EXPORTS, name
+    assert "hg_pyramid_build_device" in text[text.index("#define HG_VERSION"):text.index("enum {")]       # how the feature is detected
+    for name in ("pyramid_build_device", "remap_trilinear_frames_device"):
+        assert callable(getattr(HG.Context, name)), name
+    assert callable(HG.pyramid_levels) and callable(HG.pyramid_layout)
+
+
+def test_a_null_context_is_refused():
+    L = HG.lib()
+    g = (HG.Geom * 1)(HG.Geom(0, 0, 4, 4))
+    p = C.c_void_p(4096)
+    assert L.hg_pyramid_build_device(None, p, 4, 4, 1, 64, HG.ELEM_U8, 1, 2, p, 256) == INVALID
+    assert L.hg_remap_trilinear_frames_device(None, g, 1, p, None, p, 4, 4, 1, 64, HG.ELEM_U8, 1, p, None, p, 256, 2) == INVALID
+
+
+# ------------------------------------------------------------------------------------------------ the pyramid's geometry
+@pytest.mark.parametrize("w,h", SIZES)
+def test_pyramid_levels_and_layout(w, h):
+    lmax = HG.pyramid_levels(w, h)
+    assert lmax == 1 + math.ceil(math.log2(max(w, h))) == TM.n_levels(w, h)
+    sizes = TM.level_sizes(w, h, lmax)
+    assert sizes[0] == (w, h) and sizes[-1] == (1, 1) and (lmax == 1 or sizes[-2] != (1, 1))
+    for k in range(1, lmax):
+        assert sizes[k] == ((sizes[k - 1][0] + 1) >> 1, (sizes[k - 1][1] + 1) >> 1)
+    for elem, es in ((HG.ELEM_U8, 1), (HG.ELEM_F32, 4)):
+        for ch in (1, 2, 3, 4):
+            for levels in sorted({1, 2, lmax} & set(range(1, lmax + 1))):
+                offs, total = HG.pyramid_layout(w, h, elem, ch, levels)
+                assert (offs, total) == TM.layout(w, h, es * ch, levels)
+                assert len(offs) == levels and offs[0] == 0
+                end = 0
+                for k in range(1, levels):
+                    assert offs[k] % 256 == 0 and offs[k] >= end and (k == 1 or offs[k] > offs[k - 1])      # aligned, ascending, no overlap
+                    end = offs[k] + sizes[k][0] * sizes[k][1] * es * ch
+                    assert offs[k] - (offs[k - 1] + (sizes[k - 1][0] * sizes[k - 1][1] * es * ch if k > 1 else 0)) < 256      # packed: less than one alignment step of slack
+                assert end <= total < end + 256 and total % 256 == 0
+                assert (levels > 1) == (total > 0)
+
+
+def test_pyramid_geometry_refusals():
+    L = HG.lib()
+    assert [HG.pyramid_levels(w, h) for w, h in ((0, 5), (5, 0), (-1, 4), (4, -7), (0, 0))] == [0] * 5
+    offs, total = (C.c_size_t * 40)(), C.c_size_t(7)
+    assert L.hg_pyramid_layout(7, 5, HG.ELEM_U8, 1, 4, offs, C.byref(total)) == 0 and total.value == 768
+    for bad in ((7, 5, HG.ELEM_U8, 1, 0), (7, 5, HG.ELEM_U8, 1, 5), (7, 5, HG.ELEM_U8, 1, -1), (7, 5, 2, 1, 2), (7, 5, -1, 1, 2),
+                (7, 5, HG.ELEM_F32, 0, 2), (7, 5, HG.ELEM_F32, 5, 2), (0, 5, HG.ELEM_U8, 1, 1), (7, 0, HG.ELEM_U8, 1, 1), (1, 1, HG.ELEM_U8, 1, 2)):
+        assert L.hg_pyramid_layout(*bad, offs, C.byref(total)) == INVALID, bad
+    assert L.hg_pyramid_layout(7, 5, HG.ELEM_U8, 1, 2, None, C.byref(total)) == INVALID
+    assert L.hg_pyramid_layout(7, 5, HG.ELEM_U8, 1, 2, offs, None) == INVALID
+    with pytest.raises(HG.HgError) as e:
+        HG.pyramid_layout(7, 5, HG.ELEM_U8, 1, 9)
+    assert e.value.code == INVALID
+
+
+def test_down_on_hand_computed_cases():
+    a = np.array([[[1], [2], [4]], [[8], [16], [33]], [[100], [101], [255]]], np.uint8)      # 3 x 3: the odd column and row repeat
+    # (1 + 2 + 8 + 16 + 2) >> 2 = 7; (4 + 4 + 33 + 33 + 2) >> 2 = 19; (100 + 101) * 2 + 2 >> 2 = 101; (255 * 4 + 2) >> 2 = 255
+    assert TM.down(a)[..., 0].tolist() == [[7, 19], [101, 255]]
+    assert TM.down(np.array([[[0], [1]]], np.uint8))[..., 0].tolist() == [[1]]                # (0 + 1 + 0 + 1 + 2) >> 2: the tie rounds up
+    f = np.array([[[1.0], [2.0]], [[3.0], [4.5]]], F32)
+    assert TM.down(f)[..., 0].tolist() == [[2.625]]
+    assert [p.shape[:2] for p in TM.pyramid(np.zeros((5, 7, 2), np.uint8), 4)] == [(5, 7), (3, 4), (2, 2), (1, 1)]
+
+
+# ------------------------------------------------------------------------------------------------ the scalar model, from the header text
+def _finite(c):
+    return bool(np.isfinite(c[0]) and np.isfinite(c[1]))
+
+
+def _scalar_q(co, i, j):
+    """Step 2 of the header: q of pixel (i, j) of the (h, w, 2) float32 frame co."""
+    h, w, _ = co.shape
+    sx, sy = co[j, i]
+
+    def q_dir(cands):
+        for exists, (x, y) in cands:
+            if exists and _finite(co[y, x]):
+                dx = co[y, x, 0] - sx
+                dy = co[y, x, 1] - sy
+                return F32(F32(dx * dx) + F32(dy * dy))
+        return F32(0)
+
+    with np.errstate(all="ignore"):
+        qh = q_dir([(i + 1 < w, (min(i + 1, w - 1), j)), (i - 1 >= 0, (max(i - 1, 0), j))])
+        qv = q_dir([(j + 1 < h, (i, min(j + 1, h - 1))), (j - 1 >= 0, (i, max(j - 1, 0)))])
+    return max(qh, qv)
+
+
+def _scalar_bilinear(level, u, v):
+    """hg_remap_bilinear_f32_device's rule on one level ((H, W, C) float32) at the finite float32 coordinate (u, v)."""
+    H, W, _ = level.shape
+    x0, y0 = F32(math.floor(u)), F32(math.floor(v))
+    fx, fy = F32(u - x0), F32(v - y0)
+    gx, gy = F32(F32(1) - fx), F32(F32(1) - fy)
+
+    def tap(t, n):
+        return min(int(min(max(t, F32(0)), F32(2147483520.0))), n - 1)
+
+    c0, c1, r0, r1 = tap(x0, W), tap(F32(x0 + F32(1)), W), tap(y0, H), tap(F32(y0 + F32(1)), H)
+    out = []
+    for p00, p01, p10, p11 in zip(level[r0, c0], level[r0, c1], level[r1, c0], level[r1, c1]):
+        top = F32(F32(F32(p00 * gx) + F32(p01 * fx)) * gy)
+        bot = F32(F32(F32(p10 * gx) + F32(p11 * fx)) * fy)
+        out.append(F32(top + bot))
+    return out
+
+
+def _scalar_pixel(co, i, j, pyr_f32, is_u8, seen):
+    levels = len(pyr_f32)
+    C_ = pyr_f32[0].shape[2]
+    sx, sy = co[j, i]
+    if not _finite((sx, sy)):
+        return [0] * C_
+    q = _scalar_q(co, i, j)
+
+    def at(k):
+        if k == 0:
+            return _scalar_bilinear(pyr_f32[0], sx, sy)
+        inv = F32(1.0 / (1 << k))
+        return _scalar_bilinear(pyr_f32[k], F32(F32(F32(sx + F32(0.5)) * inv) - F32(0.5)), F32(F32(F32(sy + F32(0.5)) * inv) - F32(0.5)))
+
+    if not q > F32(1):
+        r = at(0)
+        seen.add((0, "one"))
+    else:
+        k = 64 if math.isinf(q) else (math.frexp(float(q))[1] - 1) >> 1       # frexp: q = m 2^ex with m in [0.5, 1), so e = ex - 1
+        if k >= levels - 1:
+            r = at(levels - 1)
+            seen.add((levels - 1, "one"))
+        else:
+            t = F32(F32(F32(math.ldexp(float(q), -2 * k)) - F32(1)) * F32(0.33333334))
+            lo, hi = at(k), at(k + 1)
+            r = [F32(a + F32(F32(b - a) * t)) for a, b in zip(lo, hi)]
+            seen.add((k, "t == 0" if t == 0 else "t > 0"))
+    if is_u8:
+        return [int(min(F32(255), F32(math.floor(F32(v + F32(0.5)))))) for v in r]
+    return r
+
+
+SW, SH = 61, 43                               # the source of the model tests: 7 levels
+
+
+@functools.lru_cache(maxsize=None)
+def _model_planes():
+    rng = np.random.default_rng(5)
+    u8 = rng.integers(0, 256, (SH, SW, 2), dtype=np.uint8)
+    f32 = (rng.standard_normal((SH, SW, 1)) * 50).astype(F32)
+    for a in (u8, f32):
+        a.setflags(write=False)
+    return u8, f32
+
+
+@functools.lru_cache(maxsize=None)
+def _model_frames():
+    """(name, (h, w, 2) float32) frames: steps that grow from a fraction of a pixel to the whole source and beyond (every level), exact
+    steps of 2 and 4 (t == 0), NaN / infinite / 1e30 entries with neighbours on every side, and 1 x N / N x 1 frames."""
+    rng = np.random.default_rng(6)
+    out = []
+    w, h = 260, 180
+    i, j = np.meshgrid(np.arange(w), np.arange(h))
+    sx = 0.02 * (np.exp(i / 20.0) - 1) * (1 + j / h)          # horizontal step 0.001 .. > 400 source pixels
+    sy = 0.3 * j + 0.001 * i * j
+    grow = np.stack([sx, sy], -1).astype(F32)
+    holes = rng.random((h, w)) < 0.02
+    grow[holes] = np.nan
+    grow[rng.random((h, w)) < 0.005] = [np.inf, 3]
+    grow[rng.random((h, w)) < 0.005] = [2, -np.inf]
+    grow[5:9, 0] = np.nan                                        # non-finite pixels ON every frame edge, and next to it
+    grow[5:9, w - 1] = np.nan
+    grow[0, 20:24] = np.nan
+    grow[h - 1, 20:24] = np.nan
+    grow[40:44, 1] = np.nan
+    grow[40:44, w - 2] = np.nan
+    grow[1, 60:64] = np.nan
+    grow[h - 2, 60:64] = np.nan
+    grow[100, 100:104] = [[1e30, 5], [5, -1e30], [-1e30, 1e30], [3e38, 3e38]]
+    out.append(("growing steps", grow))
+    w2, h2 = 40, 30
+    i, j = np.meshgrid(np.arange(w2), np.arange(h2))
+    out.append(("exact step 2", np.stack([2.0 * i + 0.5, 1.0 * j + 0.25], -1).astype(F32)))
+    out.append(("exact step 4", np.stack([1.0 * i, 4.0 * j + 0.5], -1).astype(F32)))
+    out.append(("magnifying", np.stack([0.5 * i + 3, 0.25 * j + 1], -1).astype(F32)))
+    line = np.stack([np.linspace(-3, SW + 3, 300) ** 1.0, np.full(300, 7.3)], -1).astype(F32)
+    line[::37] = np.nan
+    out.append(("1 x N", (line * [1, 1]).astype(F32).reshape(300, 1, 2)))          # one column: obj_w = 1
+    out.append(("N x 1", np.ascontiguousarray(line[:, ::-1] * F32(3)).reshape(1, 300, 2)))      # one row: obj_h = 1, steps of ~0.7 in sy
+    out.append(("1 x 1", np.array([[[3.5, 2.5]]], F32)))
+    for _, a in out:
+        a.setflags(write=False)
+    return out
+
+
+def test_the_vectorised_model_matches_the_scalar_model():
+    u8, f32 = _model_planes()
+    levels = TM.n_levels(SW, SH)
+    assert levels == 7
+    total = 0
+    seen = set()
+    for plane in (u8, f32):
+        pyr = TM.pyramid(plane, levels)
+        pyr_f32 = [p.astype(F32) for p in pyr]
+        for name, co in _model_frames():
+            if plane is f32 and name == "growing steps":
+                co = co[:60]                                     # (the f32 plane on a band of the large frame: the pixel count stays moderate)
+            h, w, _ = co.shape
+            got = TM.remap_trilinear(co, pyr)
+            want = np.array([_scalar_pixel(co, i, j, pyr_f32, plane is u8, seen) for j in range(h) for i in range(w)], plane.dtype)
+            assert got.dtype == plane.dtype and got.shape == want.shape
+            same = got.view(np.uint32) == want.view(np.uint32) if plane is f32 else got == want
+            assert same.all(), (name, plane.dtype, np.argwhere(~same)[:5].tolist())
+            total += h * w
+    assert total >= 50000, total
+    # the premises: every level alone or as the lower of two, t == 0 and t > 0, and the non-finite / missing neighbour cases
+    assert {k for k, _ in seen} == set(range(levels)), seen
+    assert {w for _, w in seen} == {"one", "t == 0", "t > 0"}, seen
+    grow = dict(_model_frames())["growing steps"]
+    fin = np.isfinite(grow).all(-1)
+    assert np.isnan(grow).any() and np.isinf(grow).any() and (np.abs(grow[fin]) >= 1e30).any()
+    assert (fin[:, :-1] & ~fin[:, 1:]).any() and (fin[:-1] & ~fin[1:]).any()                    # a finite pixel whose next neighbour is not
+    assert (fin[:, 1] & ~fin[:, 0]).any() and (fin[:, -2] & ~fin[:, -1]).any() and (fin[1] & ~fin[0]).any() and (fin[-2] & ~fin[-1]).any()
+    assert fin[:, 0].any() and fin[:, -1].any() and fin[0].any() and fin[-1].any()              # missing neighbours on all four frame edges
+    shapes = [a.shape[:2] for _, a in _model_frames()]
+    assert any(s[1] == 1 and s[0] > 1 for s in shapes) and any(s[0] == 1 and s[1] > 1 for s in shapes) and (1, 1) in shapes
+
+
+def test_footprint_and_level_choice_on_hand_computed_cases():
+    co = np.zeros((2, 3, 2), F32)
+    co[..., 0] = [[0, 3, 7], [0, 3, 7]]                        # horizontal steps 3, 4 (and 4 backwards at the last column)
+    co[..., 1] = [[0, 0, 0], [1, 1, 1]]                        # vertical step 1
+    assert TM.footprint(co).tolist() == [[9, 16, 16], [9, 16, 16]]
+    k, two, t = TM.level_choice(np.array([0.5, 1.0, 1.5, 4.0, 9.0, 16.0, 64.0, np.inf, 3.9999998], F32), 3)
+    assert k.tolist() == [0, 0, 0, 1, 1, 2, 2, 2, 0] and two.tolist() == [False, False, True, True, True, False, False, False, True]
+    assert t[:2].tolist() == [0, 0] and t[3] == 0 and t[2] == F32(F32(0.5) * F32(0.33333334)) and t[4] == F32(F32(1.25) * F32(0.33333334))
+    assert 0.99 < t[8] <= 1.0
+    co[0, 1] = np.nan                                            # (1, 0) missing: (0, 0) has no horizontal neighbour, (2, 0) looks back and finds none
+    q = TM.footprint(co)
+    assert q[0, 0] == 1 and q[0, 2] == 1 and q[1, 1] == 16      # ... and (1, 1) looks up instead of down: none below, (1, 0) above is NaN -> q_v = 0
+
+
+# ------------------------------------------------------------------------------------------------ properties of the model
+def _bilinear(co, plane):
+    fn = RF.remap_bilinear_u8 if plane.dtype == np.uint8 else RF.FM.remap_bilinear_f32
+    return fn(co.reshape(-1, 2), plane)
+
+
+def test_one_level_and_magnifying_fields_are_the_bilinear_remap():
+    for plane in _model_planes():
+        for name, co in _model_frames():
+            one = TM.remap_trilinear(co, TM.pyramid(plane, 1))
+            assert np.array_equal(one.view(np.uint8), _bilinear(co, plane).view(np.uint8)), name
+        pyr = TM.pyramid(plane, TM.n_levels(SW, SH))
+        h, w = 50, 70
+        i, j = np.meshgrid(np.arange(w), np.arange(h))
+        for name, co in (("identity", np.stack([i, j], -1)), ("magnifying", np.stack([0.37 * i + 0.6 * j / h, 0.8 * j - 3], -1)),
+                         ("rotation", np.stack([0.594 * i - 0.792 * j + 20, 0.792 * i + 0.594 * j - 10], -1))):
+            co = co.astype(F32)
+            assert (TM.footprint(co) <= 1).all(), name
+            assert np.array_equal(TM.remap_trilinear(co, pyr).view(np.uint8), _bilinear(co, plane).view(np.uint8)), name
+
+
+def test_a_constant_plane_stays_constant():
+    """u8: exactly.  f32: every level of the pyramid is the constant exactly (a + a, 2a + 2a and 4a * 0.25 are exact), and a pixel is the
+    constant up to the roundings of the blend -- a sample is c (gx + fx)(gy + fy) with 1 rounding in each of gx, gy and 7 in the products and
+    sums, |v - c| <= 9 * 2^-24 |c|; two such samples, their difference, its product with t <= 1 and the last sum stay within 2 * 9 + 3 more
+    -- so 21 * 2^-24 |c| bounds it."""
+    co = dict(_model_frames())["growing steps"]
+    fin = np.isfinite(co).all(-1).ravel()
+    for value, dtype in ((0, np.uint8), (1, np.uint8), (127, np.uint8), (255, np.uint8), (0, F32), (0.1, F32), (-3.75e7, F32), (1e-20, F32), (1.0, F32)):
+        plane = np.full((SH, SW, 3), value, dtype)
+        c = plane[0, 0, 0]
+        pyr = TM.pyramid(plane, TM.n_levels(SW, SH))
+        assert all((p == c).all() for p in pyr), (value, "the pyramid of a constant")
+        out = TM.remap_trilinear(co, pyr)
+        assert not out[~fin].any(), value
+        if dtype == np.uint8:
+            assert (out[fin] == c).all(), value
+        else:
+            assert (np.abs(out[fin].astype(np.float64) - float(c)) <= 21 * 2.0 ** -24 * abs(float(c))).all(), value
+
+
+def test_the_checkerboard_shrunk_8x_is_grey_where_bilinear_aliases():
+    n = 256
+    y, x = np.mgrid[0:n, 0:n]
+    board = (((x + y) & 1) * 255).astype(np.uint8)[..., None]
+    i, j = np.meshgrid(np.arange(n // 8), np.arange(n // 8))
+    pyr = TM.pyramid(board, TM.n_levels(n, n))
+    assert all((p == 128).all() for p in pyr[1:])
+    seen = set()
+    for phase in (0, 1):                                         # the exact 1/8 shrink, landing on the even and on the odd source pixels
+        co = np.stack([8.0 * i + phase, 8.0 * j], -1).astype(F32)
+        assert (TM.footprint(co) == 64).all()
+        assert (TM.remap_trilinear(co, pyr) == 128).all()
+        seen |= set(np.unique(RF.remap_bilinear_u8(co.reshape(-1, 2), board)).tolist())
+    assert seen == {0, 255}                                      # bilinear: whichever colour the sample lands on, never grey
+
+
+# ------------------------------------------------------------------------------------------------ the kernels' text on the host
+CLANGXX = next((p for p in ("/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++", shutil.which("clang++")) if p and os.path.exists(p)), None)
+
+
+@pytest.mark.skipif(CLANGXX is None, reason="clang++ (ROCm's) not available")
+def test_kernel_source_text_on_the_host_under_sanitizers(tmp_path):
+    """tests/cpp/trilinear_check.cpp: the text of k_pyr_down and k_remap_trilinear_frames, cut out of hg_k_pyramid.hip, compiled for the CPU
+    behind a thread-index shim and run under ASan + UBSan on exact-size buffers -- no byte outside a buffer is touched, whatever the
+    alignment -- and what it computes is the model's, bit for bit: every element type and channel count, misaligned planes, pyramids,
+    offsets and strides, the frames of the model test (every level, NaN / infinite / huge coordinates, 1 x N and N x 1)."""
+    src = open(os.path.join(ROOT, "homography.js_amd", "csrc", "hg_k_pyramid.hip")).read()
+    body = src[src.index("// Size of level k of a pyramid"):src.index("// ------------------------------------------------------------------------------------------------ launchers")]
+    assert "k_pyr_down" in body and "k_remap_trilinear_frames" in body
+    (tmp_path / "pyramid_kernels.inc").write_text(body)
+    exe = str(tmp_path / "trilinear_check")
+    subprocess.run([CLANGXX, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-Wno-everything", "-I", str(tmp_path), os.path.join(ROOT, "tests", "cpp", "trilinear_check.cpp"), "-o", exe],
+                   check=True, cwd=str(tmp_path), timeout=600)
+    frames = [co for _, co in _model_frames()]
+    frames[0] = frames[0][:40]
+    geoms = [(0, 0, co.shape[1], co.shape[0]) for co in frames] + [(0, 0, 0, 3)]
+    fields = [co.reshape(-1, 2) for co in frames] + [np.zeros((0, 2), F32)]
+    rng = np.random.default_rng(8)
+    for case, (elem, ch, n_planes, levels, misalign) in enumerate(((1, 1, 1, 7, 0), (1, 2, 3, 7, 1), (1, 3, 2, 7, 1), (1, 4, 3, 7, 1), (1, 4, 1, 7, 0), (1, 2, 1, 2, 0),
+                                                                 (0, 1, 3, 7, 1), (0, 2, 1, 7, 0), (0, 3, 2, 3, 1), (0, 4, 3, 7, 1), (1, 4, 2, 1, 1))):
+        es = 1 if elem else 4
+        px = es * ch
+        if elem:
+            planes = [rng.integers(0, 256, (SH, SW, ch), dtype=np.uint8) for _ in range(n_planes)]
+        else:
+            planes = [(rng.standard_normal((SH, SW, ch)) * 30).astype(F32) for _ in range(n_planes)]
+        blk_px = 1024
+        plane_stride = planes[0].nbytes + (256 + 3 * es if misalign else 0)
+        plane_front, pyr_front = (16 + es, 16 + es) if misalign else (16, 16)
+        offs, total = TM.layout(SW, SH, px, levels)
+        pyr_stride = total + (3 * es if misalign else 0)
+        fo, oo, f_end, o_end = [], [], 0, 0
+        for f, g in enumerate(geoms):
+            fo.append(f_end + (8 * (2 * f + 1) if misalign else 0))
+            oo.append(o_end + (es * (2 * f + 1) if misalign else 0))
+            f_end = fo[-1] + RF.n_px(g) * 8
+            o_end = oo[-1] + RF.n_px(g) * px + (7 * es if misalign else 0)
+        head = np.array([elem, ch, SW, SH, levels, n_planes, len(geoms), plane_front], np.int32).tobytes()
+        head += np.array([blk_px, plane_stride, pyr_front, pyr_stride, f_end, o_end], np.uint64).tobytes()
+        for g, a, b in zip(geoms, fo, oo):
+            head += np.array([g[2], g[3]], np.int32).tobytes() + np.array([a, b], np.uint64).tobytes()
+        fld = np.zeros(f_end, np.uint8)
+        for co, a in zip(fields, fo):
+            fld[a:a + co.size * 4] = np.ascontiguousarray(co).view(np.uint8).ravel()
+        pl = np.full((n_planes - 1) * plane_stride + planes[0].nbytes, 0xEE, np.uint8)
+        for k, p_ in enumerate(planes):
+            pl[k * plane_stride:k * plane_stride + p_.nbytes] = p_.view(np.uint8).ravel()
+        fin, fout = tmp_path / f"case{case}.in", tmp_path / f"case{case}.out"
+        fin.write_bytes(head + fld.tobytes() + pl.tobytes())
+        p = subprocess.run([exe, str(fin), str(fout)], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0 and "host check ran" in p.stdout, (case, (p.stdout + p.stderr)[-3000:])
+        assert "runtime error" not in p.stdout + p.stderr and "AddressSanitizer" not in p.stderr, (case, (p.stdout + p.stderr)[-3000:])
+        raw = np.frombuffer(fout.read_bytes(), np.uint8)
+        pyr_bytes = (n_planes - 1) * pyr_stride + total if levels > 1 else 0
+        assert raw.size == pyr_bytes + o_end, case
+        pyrs = [TM.pyramid(p_, levels) for p_ in planes]
+        untouched = np.ones(pyr_bytes, bool)
+        for k, pyr in enumerate(pyrs):
+            for lv in range(1, levels):
+                w_ = pyr[lv].view(np.uint8).ravel()
+                at = k * pyr_stride + offs[lv]
+                untouched[at:at + w_.size] = False
+                assert np.array_equal(raw[at:at + w_.size], w_), (case, "plane", k, "level", lv)
+        assert (raw[:pyr_bytes][untouched] == 0xA5).all(), case
+        out = raw[pyr_bytes:]
+        want = TM.trilinear_frames(geoms, fields, pyrs)
+        untouched = np.ones(o_end, bool)
+        for f, g in enumerate(geoms):
+            n = RF.n_px(g) * px
+            untouched[oo[f]:oo[f] + n] = False
+            w_ = np.ascontiguousarray(want[f]).view(np.uint8).ravel()
+            got = out[oo[f]:oo[f] + n]
+            assert np.array_equal(got, w_), (case, "frame", f, g, int((got != w_).sum()), np.flatnonzero(got != w_)[:4].tolist())
+        assert (out[untouched] == 0xA5).all(), case
+
+
+# ------------------------------------------------------------------------------------------------ the drop-in class
+@pytest.mark.skipif(shutil.which("node") is None, reason="node is missing")
+def test_js_class_trilinear_over_the_recording_mock_addon():
+    """tests/js/trilinear_class.mjs: sampling 'trilinear' reaches 'remapTrilinear' + entry with the bilinear call's arguments, refuses what
+    'bilinear' refuses, and leaves the calls of 'nearest' and 'bilinear' as they were."""
+    p = subprocess.run([shutil.which("node"), os.path.join(ROOT, "tests", "js", "trilinear_class.mjs")], capture_output=True, text=True, timeout=300,
+                       cwd=ROOT, env=dict(os.environ, HGWARP_ADDON=os.path.join(ROOT, "tests", "js", "mock_trilinear_addon.cjs")))
+    line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert line, p.stdout[-2000:] + p.stderr[-2000:]
+    res = json.loads(line[-1])
+    assert res["failures"] == [] and p.returncode == 0, (res["failures"], p.stderr[-2000:])
+    assert res["checks"] >= 60
