@@ -412,22 +412,24 @@ extern "C" int hg_pyramid_build_device(hg_ctx *c, const void *d_planes, int W, i
     return HG_OK;
 }
 
-extern "C" int hg_remap_trilinear_frames_device(hg_ctx *c, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
-                                                const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
-                                                void *d_out, const size_t *out_offsets, const void *d_pyr, size_t pyr_stride_bytes, int levels)
+// The trilinear and the anisotropic frames remap (who: the entry point's name): one set of checks, one table, one staging; max_aniso == 0
+// launches the trilinear kernel, 1..16 the anisotropic one.
+static int remap_mip_frames(hg_ctx *c, const std::string &who, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
+                            const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
+                            void *d_out, const size_t *out_offsets, const void *d_pyr, size_t pyr_stride_bytes, int levels, int max_aniso)
 {
     HG_TRY(bind(c));
-    if (elem != HG_ELEM_F32 && elem != HG_ELEM_U8) return fail(c, HG_ERR_INVALID, "hg_remap_trilinear_frames_device: unknown elem (HG_ELEM_F32 or HG_ELEM_U8)");
-    if (channels < 1 || channels > 4 || W < 1 || H < 1) return fail(c, HG_ERR_INVALID, "hg_remap_trilinear_frames_device: channels must be 1..4, W and H >= 1");
-    if (n_planes < 1) return fail(c, HG_ERR_INVALID, "hg_remap_trilinear_frames_device: n_planes must be >= 1");
-    if (n_frames < 0 || n_frames > 65535) return fail(c, HG_ERR_INVALID, "hg_remap_trilinear_frames_device: n_frames must be 0..65535");
+    if (elem != HG_ELEM_F32 && elem != HG_ELEM_U8) return fail(c, HG_ERR_INVALID, who + ": unknown elem (HG_ELEM_F32 or HG_ELEM_U8)");
+    if (channels < 1 || channels > 4 || W < 1 || H < 1) return fail(c, HG_ERR_INVALID, who + ": channels must be 1..4, W and H >= 1");
+    if (n_planes < 1) return fail(c, HG_ERR_INVALID, who + ": n_planes must be >= 1");
+    if (n_frames < 0 || n_frames > 65535) return fail(c, HG_ERR_INVALID, who + ": n_frames must be 0..65535");
     size_t lvl[32] = {0}, total = 0;
-    HG_TRY(check_pyramid(c, "hg_remap_trilinear_frames_device", W, H, elem, channels, levels, d_pyr, pyr_stride_bytes, false, lvl, &total));
+    HG_TRY(check_pyramid(c, who.c_str(), W, H, elem, channels, levels, d_pyr, pyr_stride_bytes, false, lvl, &total));
     if (n_frames == 0) return HG_OK;
-    if (!geoms || !d_coords || !d_planes || !d_out) return fail(c, HG_ERR_INVALID, "hg_remap_trilinear_frames_device: NULL pointer");
+    if (!geoms || !d_coords || !d_planes || !d_out) return fail(c, HG_ERR_INVALID, who + ": NULL pointer");
     const size_t es = elem == HG_ELEM_F32 ? 4 : 1;
     if (misaligned(d_coords, 8) || misaligned(d_planes, es) || misaligned(d_out, es) || (plane_stride_bytes & (es - 1)))
-        return fail(c, HG_ERR_INVALID, "hg_remap_trilinear_frames_device: d_coords must be aligned to 8 bytes, d_planes / d_out / plane_stride_bytes to the element size");
+        return fail(c, HG_ERR_INVALID, who + ": d_coords must be aligned to 8 bytes, d_planes / d_out / plane_stride_bytes to the element size");
     std::vector<RemapFrame> recs;
     size_t extent = 0;
     HG_TRY(remap_frame_table(c, geoms, n_frames, 8, field_offsets, es * (size_t)channels, es, out_offsets, n_planes, &recs, &extent));
@@ -451,9 +453,27 @@ extern "C" int hg_remap_trilinear_frames_device(hg_ctx *c, const hg_geom *geoms,
     }
     HG_TRY(upload_staged(c, c->d_tri_table, gs->h, words * 8));
     HG_TRY(c->field_stage.commit(c, gs));
-    launch_remap_trilinear_frames(reinterpret_cast<const TriRemapFrame *>(c->d_tri_table.p + 32), n_frames, n_blocks, blk_px, c->d_tri_table, levels,
-                                  static_cast<const uint8_t *>(d_coords), static_cast<const uint8_t *>(d_planes), static_cast<const uint8_t *>(d_pyr),
-                                  W, H, elem, channels, static_cast<uint8_t *>(d_out), c->stream);
+    const TriRemapFrame *d_frames = reinterpret_cast<const TriRemapFrame *>(c->d_tri_table.p + 32);
+    const uint8_t *co = static_cast<const uint8_t *>(d_coords), *pl = static_cast<const uint8_t *>(d_planes), *py = static_cast<const uint8_t *>(d_pyr);
+    if (max_aniso == 0) launch_remap_trilinear_frames(d_frames, n_frames, n_blocks, blk_px, c->d_tri_table, levels, co, pl, py, W, H, elem, channels, static_cast<uint8_t *>(d_out), c->stream);
+    else launch_remap_aniso_frames(d_frames, n_frames, n_blocks, blk_px, c->d_tri_table, levels, max_aniso, co, pl, py, W, H, elem, channels, static_cast<uint8_t *>(d_out), c->stream);
     HIP_TRY(c, hipGetLastError());
     return HG_OK;
+}
+
+extern "C" int hg_remap_trilinear_frames_device(hg_ctx *c, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
+                                                const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
+                                                void *d_out, const size_t *out_offsets, const void *d_pyr, size_t pyr_stride_bytes, int levels)
+{
+    return remap_mip_frames(c, "hg_remap_trilinear_frames_device", geoms, n_frames, d_coords, field_offsets, d_planes, W, H, n_planes, plane_stride_bytes,
+                            elem, channels, d_out, out_offsets, d_pyr, pyr_stride_bytes, levels, 0);
+}
+
+extern "C" int hg_remap_aniso_frames_device(hg_ctx *c, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
+                                            const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
+                                            void *d_out, const size_t *out_offsets, const void *d_pyr, size_t pyr_stride_bytes, int levels, int max_aniso)
+{
+    if (max_aniso < 1 || max_aniso > 16) return fail(c, HG_ERR_INVALID, "hg_remap_aniso_frames_device: max_aniso must lie in 1..16");
+    return remap_mip_frames(c, "hg_remap_aniso_frames_device", geoms, n_frames, d_coords, field_offsets, d_planes, W, H, n_planes, plane_stride_bytes,
+                            elem, channels, d_out, out_offsets, d_pyr, pyr_stride_bytes, levels, max_aniso);
 }

@@ -208,6 +208,7 @@ __global__ __launch_bounds__(256) void k_remap_trilinear_frames(const TriRemapFr
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
+#ifndef HG_PYRAMID_NO_LAUNCHERS      // (hg_k_aniso.hip includes this file for the per-level helpers above: one text for both kernels)
 void launch_pyr_down(const uint8_t *src, size_t src_stride, int Ws, int Hs, uint8_t *dst, size_t dst_stride, int Wd, int Hd, int n_planes,
                      int elem, int channels, hipStream_t stream)
 {
@@ -231,5 +232,6 @@ void launch_remap_trilinear_frames(const TriRemapFrame *frames, int n_frames, ui
 #undef HG_TE
 #undef HG_TF
 }
+#endif
 
 } // namespace hg

@@ -210,6 +210,11 @@ struct TriRemapFrame { uint64_t fld_off, out_off, n_px, plane_off, pyr_off; uint
 void launch_remap_trilinear_frames(const TriRemapFrame *frames, int n_frames, uint32_t n_blocks, uint64_t blk_px, const uint64_t *lvl_off, int levels,
                                    const uint8_t *coords, const uint8_t *planes, const uint8_t *pyrs, int W, int H, int elem, int channels,
                                    uint8_t *out, hipStream_t stream);
+// k_remap_aniso_frames<element, channels> (hg_k_aniso.hip; hg_remap_aniso_frames_device): the trilinear launch plus max_aniso (1..16), the
+// cap on the probes a pixel takes along its longer step.
+void launch_remap_aniso_frames(const TriRemapFrame *frames, int n_frames, uint32_t n_blocks, uint64_t blk_px, const uint64_t *lvl_off, int levels,
+                               int max_aniso, const uint8_t *coords, const uint8_t *planes, const uint8_t *pyrs, int W, int H, int elem, int channels,
+                               uint8_t *out, hipStream_t stream);
 
 // Point lists (hg_k_points.hip; include/hgwarp.h hg_points_*): n_sets lists of n_points interleaved (x, y) floats, frame f reads list
 // f % n_sets and writes n_points (x, y) pairs at f * n_points of `out`; an unmapped point is the quiet NaN of HG_FIELD_COORDS in both words.

@@ -830,9 +830,9 @@ static napi_value fn_field_forward_piecewise(napi_env env, napi_callback_info in
  * bytes) or hg_remap_bilinear_f32_device / _u8_device (format 1: Float32Array / Uint8Array / Uint8ClampedArray, 1..4 channels) runs, and the
  * result comes down as a TypedArray of the plane's class with objW * objH * channels elements. */
 typedef struct { napi_typedarray_type type; void *data; size_t len, elem; int channels, W, H; void *d_field, *d_plane, *d_out, *out; size_t px; napi_value result;
-                 int levels; void *d_pyr; size_t pyr_bytes; hg_geom geom; } remap_job;      /* levels > 0: the trilinear remap, its pyramid behind the result */
+                 int levels, max_aniso; void *d_pyr; size_t pyr_bytes; hg_geom geom; } remap_job;      /* levels > 0: the trilinear remap, its pyramid behind the result; max_aniso > 0: the anisotropic one */
 
-static int remap_begin(napi_env env, handle_t *h, napi_value *a, int fmt, size_t px, int trilinear, remap_job *j)
+static int remap_begin(napi_env env, handle_t *h, napi_value *a, int fmt, size_t px, int mip, remap_job *j)      /* mip: 0 none, 1 trilinear, 2 anisotropic (a[4] = maxAniso) */
 {
     static const size_t elem_of[] = { 1, 1, 1, 2, 2, 4, 4, 4, 8, 8, 8 };       /* napi_int8_array .. napi_biguint64_array */
     bool is = false; napi_value ab; size_t off = 0;
@@ -848,16 +848,20 @@ static int remap_begin(napi_env env, handle_t *h, napi_value *a, int fmt, size_t
         throw_str(env, "hgwarp: this plane class and channel count cannot be remapped in this format"); return 0;
     }
     if (j->W < 1 || j->H < 1 || j->len != (size_t)j->W * (size_t)j->H * (size_t)j->channels) { throw_str(env, "hgwarp: plane must hold W * H * channels elements"); return 0; }
+    if (mip == 2) {
+        if (!get_i32(env, a[4], &j->max_aniso)) return 0;
+        if (j->max_aniso < 1 || j->max_aniso > 16) { throw_str(env, "hgwarp: maxAniso must lie in 1..16"); return 0; }
+    }
     j->px = px;
     j->result = make_typed(env, j->type, px * (size_t)j->channels, j->elem, &j->out);
     if (!j->result) return 0;
     if (!px) return 1;
     size_t fb = (px * (fmt == HG_FIELD_INDEX ? 4 : 8) + 255) & ~(size_t)255, pl = (j->len * j->elem + 255) & ~(size_t)255, ob = px * pb;
-    if (trilinear) {                                           /* the full pyramid, all hg_pyramid_levels(W, H) levels */
+    if (mip) {                                                 /* the full pyramid, all hg_pyramid_levels(W, H) levels */
         size_t offs[32];
         j->levels = hg_pyramid_levels(j->W, j->H);
         if (fmt != HG_FIELD_COORDS || hg_pyramid_layout(j->W, j->H, j->type == napi_float32_array ? HG_ELEM_F32 : HG_ELEM_U8, j->channels, j->levels, offs, &j->pyr_bytes) != HG_OK) {
-            throw_str(env, "hgwarp: a trilinear remap needs the coords format"); return 0;
+            throw_str(env, mip == 2 ? "hgwarp: an anisotropic remap needs the coords format" : "hgwarp: a trilinear remap needs the coords format"); return 0;
         }
         ob = (ob + 255) & ~(size_t)255;
     }
@@ -881,6 +885,10 @@ static napi_value remap_finish(napi_env env, handle_t *h, int fmt, const remap_j
         const int elem = j->type == napi_float32_array ? HG_ELEM_F32 : HG_ELEM_U8;
         const size_t zero = 0;
         HG_CALL(h->ctx, "hg_pyramid_build_device", hg_pyramid_build_device(h->ctx, j->d_plane, j->W, j->H, 1, 0, elem, j->channels, j->levels, j->d_pyr, j->pyr_bytes));
+        if (j->max_aniso > 0)
+            HG_CALL(h->ctx, "hg_remap_aniso_frames_device", hg_remap_aniso_frames_device(h->ctx, &j->geom, 1, j->d_field, &zero, j->d_plane, j->W, j->H, 1, 0, elem,
+                                                                                         j->channels, j->d_out, &zero, j->d_pyr, j->pyr_bytes, j->levels, j->max_aniso));
+        else
         HG_CALL(h->ctx, "hg_remap_trilinear_frames_device", hg_remap_trilinear_frames_device(h->ctx, &j->geom, 1, j->d_field, &zero, j->d_plane, j->W, j->H, 1, 0, elem,
                                                                                              j->channels, j->d_out, &zero, j->d_pyr, j->pyr_bytes, j->levels));
     } else if (fmt == HG_FIELD_INDEX)
@@ -893,10 +901,10 @@ static napi_value remap_finish(napi_env env, handle_t *h, int fmt, const remap_j
     return j->result;
 }
 
-static napi_value remap_inverse_geometric(napi_env env, napi_callback_info info, int trilinear)
+static napi_value remap_inverse_geometric(napi_env env, napi_callback_info info, int mip)
 {
-    napi_value a[12];
-    if (!get_args(env, info, 12, a)) return NULL;
+    napi_value a[13];
+    if (!get_args(env, info, mip == 2 ? 13 : 12, a)) return NULL;
     handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
     int kind, fmt; size_t n; hg_geom g; remap_job j;
     if (!get_i32(env, a[1], &kind)) return NULL;
@@ -904,32 +912,35 @@ static napi_value remap_inverse_geometric(napi_env env, napi_callback_info info,
     if (n < (size_t)(kind == HG_AFFINE ? 6 : 8)) return throw_str(env, "hgwarp: matrix too short");
     if (!get_geom(env, a + 3, &g) || !get_i32(env, a[7], &fmt)) return NULL;
     const size_t px = (g.obj_w > 0 && g.obj_h > 0) ? (size_t)g.obj_w * g.obj_h : 0;
-    if (!remap_begin(env, h, a + 8, fmt, px, trilinear, &j)) return NULL;
+    if (!remap_begin(env, h, a + 8, fmt, px, mip, &j)) return NULL;
     j.geom = g;
     if (px) HG_CALL(h->ctx, "hg_field_inverse_geometric_device", hg_field_inverse_geometric_device(h->ctx, kind, m, g, fmt, j.d_field));
     return remap_finish(env, h, fmt, &j);
 }
 
-static napi_value remap_inverse_piecewise(napi_env env, napi_callback_info info, int trilinear)
+static napi_value remap_inverse_piecewise(napi_env env, napi_callback_info info, int mip)
 {
-    napi_value a[6];
-    if (!get_args(env, info, 6, a)) return NULL;
+    napi_value a[7];
+    if (!get_args(env, info, mip == 2 ? 7 : 6, a)) return NULL;
     handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
     int fmt; remap_job j;
     if (!get_i32(env, a[1], &fmt)) return NULL;
     const size_t px = (h->obj_w > 0 && h->obj_h > 0) ? (size_t)h->obj_w * h->obj_h : 0, zero = 0;
-    if (!remap_begin(env, h, a + 2, fmt, px, trilinear, &j)) return NULL;
+    if (!remap_begin(env, h, a + 2, fmt, px, mip, &j)) return NULL;
     j.geom.x_off = 0; j.geom.y_off = 0; j.geom.obj_w = h->obj_w; j.geom.obj_h = h->obj_h;
     if (px) HG_CALL(h->ctx, "hg_field_inverse_piecewise_frames_device", hg_field_inverse_piecewise_frames_device(h->ctx, fmt, &zero, j.d_field));
     return remap_finish(env, h, fmt, &j);
 }
 
 /* remapTrilinearInverseGeometric / remapTrilinearInversePiecewise: the arguments of remapInverseGeometric / remapInversePiecewise (format 1),
- * the plane through hg_pyramid_build_device (all levels, in device scratch) and hg_remap_trilinear_frames_device with the window as one frame. */
+ * the plane through hg_pyramid_build_device (all levels, in device scratch) and hg_remap_trilinear_frames_device with the window as one frame.
+ * remapAnisoInverseGeometric / remapAnisoInversePiecewise: the same arguments followed by maxAniso (1..16), through hg_remap_aniso_frames_device. */
 static napi_value fn_remap_inverse_geometric(napi_env env, napi_callback_info info) { return remap_inverse_geometric(env, info, 0); }
 static napi_value fn_remap_inverse_piecewise(napi_env env, napi_callback_info info) { return remap_inverse_piecewise(env, info, 0); }
 static napi_value fn_remap_trilinear_inverse_geometric(napi_env env, napi_callback_info info) { return remap_inverse_geometric(env, info, 1); }
 static napi_value fn_remap_trilinear_inverse_piecewise(napi_env env, napi_callback_info info) { return remap_inverse_piecewise(env, info, 1); }
+static napi_value fn_remap_aniso_inverse_geometric(napi_env env, napi_callback_info info) { return remap_inverse_geometric(env, info, 2); }
+static napi_value fn_remap_aniso_inverse_piecewise(napi_env env, napi_callback_info info) { return remap_inverse_piecewise(env, info, 2); }
 
 static napi_value fn_remap_forward_geometric(napi_env env, napi_callback_info info)
 {
@@ -1641,6 +1652,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "remapInverseGeometric", fn_remap_inverse_geometric }, { "remapInversePiecewise", fn_remap_inverse_piecewise },
         { "remapForwardGeometric", fn_remap_forward_geometric }, { "remapForwardPiecewise", fn_remap_forward_piecewise },
         { "remapTrilinearInverseGeometric", fn_remap_trilinear_inverse_geometric }, { "remapTrilinearInversePiecewise", fn_remap_trilinear_inverse_piecewise },
+        { "remapAnisoInverseGeometric", fn_remap_aniso_inverse_geometric }, { "remapAnisoInversePiecewise", fn_remap_aniso_inverse_piecewise },
         { "pointsInverseGeometric", fn_points_inverse_geometric }, { "pointsInversePiecewise", fn_points_inverse_piecewise },
         { "pointsForwardGeometric", fn_points_forward_geometric }, { "pointsForwardPiecewise", fn_points_forward_piecewise },
         { "solveAffineTriangles", fn_solve_affine_triangles }, { "warpInversePiecewiseState", fn_warp_inverse_piecewise_state },

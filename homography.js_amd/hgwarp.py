@@ -54,7 +54,7 @@ EXPORTS = [
     "hg_pack_plane_offsets", "hg_remap_index_frames_device", "hg_remap_bilinear_frames_device", "hg_remap_bilinear_u8_device",
     "hg_points_to_source_geometric_frames_device", "hg_points_to_source_piecewise_frames_device",
     "hg_points_to_output_geometric_batch_device", "hg_points_to_output_piecewise_batch_device",
-    "hg_pyramid_levels", "hg_pyramid_layout", "hg_pyramid_build_device", "hg_remap_trilinear_frames_device",
+    "hg_pyramid_levels", "hg_pyramid_layout", "hg_pyramid_build_device", "hg_remap_trilinear_frames_device", "hg_remap_aniso_frames_device",
 ]
 
 
@@ -160,6 +160,7 @@ def lib():
         "hg_pyramid_layout": (i, [i, i, i, i, i, C.POINTER(sz), C.POINTER(sz)]),
         "hg_pyramid_build_device": (i, [vp, vp, i, i, i, sz, i, i, i, vp, sz]),
         "hg_remap_trilinear_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, i, i, i, sz, i, i, vp, C.POINTER(sz), vp, sz, i]),
+        "hg_remap_aniso_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, i, i, i, sz, i, i, vp, C.POINTER(sz), vp, sz, i, i]),
         "hg_points_to_source_geometric_frames_device": (i, [vp, vp, i, i, vp]),
         "hg_points_to_source_piecewise_frames_device": (i, [vp, vp, i, i, vp]),
         "hg_points_to_output_geometric_batch_device": (i, [vp, i, f64p, C.POINTER(Geom), i, vp, i, i, vp]),
@@ -725,6 +726,16 @@ class Context:
         self._c(lib().hg_remap_trilinear_frames_device(self._h, _geoms(geoms), len(geoms), C.c_void_p(int(d_coords)), fo, C.c_void_p(int(d_planes)),
                                                        int(w), int(h), int(n_planes), int(plane_stride_bytes), int(elem), int(channels),
                                                        C.c_void_p(int(d_out)), oo, C.c_void_p(int(d_pyr)), int(pyr_stride_bytes), int(levels)))
+
+    def remap_aniso_frames_device(self, geoms, d_coords, d_planes, w, h, n_planes, plane_stride_bytes, elem, channels, d_out,
+                                  d_pyr, pyr_stride_bytes, levels, max_aniso, field_offsets=None, out_offsets=None):
+        """remap_trilinear_frames_device with anisotropic filtering: up to max_aniso (1..16) probes along the longer of a pixel's two steps
+        in the field, each from the finer level(s) the shorter step allows, averaged; max_aniso == 1 is the trilinear remap, bit for bit."""
+        fo = (C.c_size_t * len(geoms))(*field_offsets) if field_offsets is not None else None
+        oo = (C.c_size_t * len(geoms))(*out_offsets) if out_offsets is not None else None
+        self._c(lib().hg_remap_aniso_frames_device(self._h, _geoms(geoms), len(geoms), C.c_void_p(int(d_coords)), fo, C.c_void_p(int(d_planes)),
+                                                   int(w), int(h), int(n_planes), int(plane_stride_bytes), int(elem), int(channels),
+                                                   C.c_void_p(int(d_out)), oo, C.c_void_p(int(d_pyr)), int(pyr_stride_bytes), int(levels), int(max_aniso)))
 
     # ---- piecewise
     def piecewise_set_mesh(self, src_pts, tris, min_src_x, min_src_y):

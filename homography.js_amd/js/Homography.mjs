@@ -333,15 +333,22 @@ class Homography {
      *                     pyramid (all levels) is built in device scratch and every pixel blends the two levels that match the field's
      *                     own footprint there (include/hgwarp.h, hg_remap_trilinear_frames_device), so a shrink no longer aliases; where
      *                     the field does not shrink the result is 'bilinear''s, bit for bit;
-     *   options.loop      'inverse' (default), 'warp' or 'forward': sourceField's meaning, refusals and stale-state rules; 'bilinear' and
-     *                     'trilinear' with a forward loop throw, as 'coords' does there.
+     *                     'anisotropic': 'trilinear' for oblique views -- up to options.maxAniso probes along the longer of a pixel's two
+     *                     steps in the field, each from the finer level(s) the shorter step allows, averaged (include/hgwarp.h,
+     *                     hg_remap_aniso_frames_device), so the axis that shrinks less stays sharp; maxAniso 1 is 'trilinear', bit for bit;
+     *   options.maxAniso  'anisotropic' only: an integer in 1..16 (default 8), the most probes a pixel takes;
+     *   options.loop      'inverse' (default), 'warp' or 'forward': sourceField's meaning, refusals and stale-state rules; 'bilinear',
+     *                     'trilinear' and 'anisotropic' with a forward loop throw, as 'coords' does there.
      * Independent of the instance's sampling mode; records neither a map nor a path.
      * Returns { data, width, height, channels }, `data` being of the plane's own class; an empty window gives empty data, width and height 0.
      */
     remap(plane, options = {}) {
         if (options === null || options === undefined) options = {};
         const sampling = options.sampling === undefined ? 'nearest' : options.sampling;
-        if (sampling !== 'nearest' && sampling !== 'bilinear' && sampling !== 'trilinear') throw ("remap: options.sampling must be 'nearest', 'bilinear' or 'trilinear'");
+        if (sampling !== 'nearest' && sampling !== 'bilinear' && sampling !== 'trilinear' && sampling !== 'anisotropic')
+            throw ("remap: options.sampling must be 'nearest', 'bilinear', 'trilinear' or 'anisotropic'");
+        const maxAniso = options.maxAniso === undefined ? 8 : options.maxAniso;
+        if (sampling === 'anisotropic' && !(Number.isInteger(maxAniso) && maxAniso >= 1 && maxAniso <= 16)) throw ("remap: options.maxAniso must be an integer in 1..16");
         const channels = options.channels === undefined ? 1 : options.channels;
         if (!ArrayBuffer.isView(plane) || plane instanceof DataView) throw ("remap: plane must be a typed array");
         if (!Number.isInteger(channels) || channels < 1) throw ("remap: options.channels must be a positive integer");
@@ -356,7 +363,9 @@ class Homography {
         const call = this._fieldCall('remap', fmt, options);          // (throws without an image)
         if (plane.length !== this._width * this._height * channels) throw ("remap: plane must hold width * height * channels elements of the instance's image size");
         if (call === null) return { data: new plane.constructor(0), width: 0, height: 0, channels };
-        const data = this._native[(sampling === 'trilinear' ? 'remapTrilinear' : 'remap') + call.entry](this._ctx, ...call.args, plane, channels, this._width, this._height);
+        const data = sampling === 'anisotropic'
+            ? this._native['remapAniso' + call.entry](this._ctx, ...call.args, plane, channels, this._width, this._height, maxAniso)
+            : this._native[(sampling === 'trilinear' ? 'remapTrilinear' : 'remap') + call.entry](this._ctx, ...call.args, plane, channels, this._width, this._height);
         return { data, width: call.width, height: call.height, channels };
     }
 

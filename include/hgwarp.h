@@ -35,7 +35,8 @@ extern "C" {
 
 #define HG_VERSION 100          /* 0.1.0 (sampling modes are detected by the presence of hg_set_sampling, source fields by that of hg_field_inverse_geometric,
                                    the forward source fields by that of hg_field_forward_geometric, point lists by that of
-                                   hg_points_to_source_geometric_frames_device, mip pyramids and the trilinear remap by that of hg_pyramid_build_device) */
+                                   hg_points_to_source_geometric_frames_device, mip pyramids and the trilinear remap by that of hg_pyramid_build_device,
+                                   the anisotropic remap by that of hg_remap_aniso_frames_device) */
 
 enum {
     HG_OK = 0,
@@ -401,6 +402,40 @@ int hg_remap_trilinear_frames_device(hg_ctx *ctx, const hg_geom *geoms, int n_fr
                                      const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes,
                                      int elem, int channels, void *d_out, const size_t *out_offsets,
                                      const void *d_pyr, size_t pyr_stride_bytes, int levels);
+/* ANISOTROPIC remap on the field seam.  The trilinear rule chooses one footprint size, q = max(q_h, q_v), so a field that shrinks one axis
+ * much more than the other (a plane seen obliquely) is blurred along the axis that did not need it: one-pixel vertical stripes shrunk 8x
+ * vertically and not at all horizontally come out 128 everywhere.  hg_remap_aniso_frames_device takes up to max_aniso probes along the longer
+ * of the field's two steps, each from the finer level(s) the shorter step allows, and averages them (the same stripes: the stripes).
+ * Its arguments are hg_remap_trilinear_frames_device's, followed by max_aniso, which must lie in 1..16 (else HG_ERR_INVALID).  Offset
+ * defaults, the f % n_planes rule, alignment rules and refusals, staging through the page-locked ring, "settle queued runs whose redo could
+ * land on d_out" and "no effect on hg_last_*, the sampling mode, the plan or what the policy learned" are those of the trilinear form (one
+ * host path serves both).  All of the rule is f32 in the written order, contraction off.  Pixel (i, j) of a frame read as obj_w x obj_h,
+ * (sx, sy) its coordinate:
+ *   1. sx or sy NaN or infinite: every channel is 0.
+ *   2. Steps.  The horizontal neighbour is chosen exactly as trilinear step 2 chooses it: (i+1, j) if it exists and is finite, else (i-1, j)
+ *      under the same conditions, else none.  hx = nx - sx, hy = ny - sy, q_h = hx*hx + hy*hy; a missing neighbour gives hx = hy = q_h = 0.
+ *      The vertical neighbour likewise gives vx, vy, q_v.
+ *   3. Axes.  q_h >= q_v: major (mx, my) = (hx, hy), qM = q_h, qm = q_v.  Otherwise the major is the vertical step, qM = q_v, qm = q_h.
+ *   4. Probe count N.  !(qM > 1.0f), or qM not finite: N = 1.  Otherwise qm' = fmaxf(qm, 1.0f) (anisotropy never asks for detail finer than
+ *      level 0) and N is the smallest n in 1..max_aniso with (float)(n*n) * qm' >= qM; if there is none, N = max_aniso.
+ *   5. Level.  q' = qM / (float)(N*N), an IEEE division.  k, "one level or two" and t are trilinear step 3 applied to q' with `levels`.
+ *   6. Probes.  N == 1: the single probe is (sx, sy) itself.  Otherwise, for p = 0..N-1: o = (((float)p + 0.5f) / (float)N) - 0.5f and probe p
+ *      is (sx + mx*o, sy + my*o), multiply then add.  Each probe is sampled by trilinear steps 4 and 5: r_p = v_k, or v_k + (v_{k+1} - v_k) * t,
+ *      unrounded f32 per channel.
+ *   7. Average.  acc = r_0, then acc = acc + r_p in ascending p; r = acc / (float)N.  f32 stores r; u8 stores (uint8)min(255, floor(r + 0.5f)).
+ * Hence: with max_aniso == 1 the output IS hg_remap_trilinear_frames_device's, bit for bit (N is 1, q' = qM = max(q_h, q_v), acc / 1 is
+ * exact); hence with max_aniso == 1 and levels == 1, or, whatever max_aniso is, where the field nowhere shrinks (every N is 1), it is
+ * hg_remap_bilinear_frames_device's (levels == 1 with more probes averages bilinear samples of the plane); a constant u8 plane stays
+ * constant; coordinates of 1e30 and steps that overflow are legal, and no tap leaves a level.
+ * Cost (MI355X, 64 frames out of 8 planes of 3840 x 2160; EXPERIMENTS.md F.6): where every pixel takes one probe (max_aniso = 1, or an
+ * isotropic 4x shrink at any max_aniso) the anisotropic remap takes 1.24-1.31 x the time of hg_remap_trilinear_frames_device on the same
+ * fields, planes and pyramids; 1.99-2.30 x on a projective set whose pixels take 2 probes; 2.92-4.16 x on an 8x-by-1x shrink (8 probes from
+ * level 0, or 4 from two levels with max_aniso = 4). */
+int hg_remap_aniso_frames_device(hg_ctx *ctx, const hg_geom *geoms, int n_frames,
+                                 const void *d_coords, const size_t *field_offsets,
+                                 const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes,
+                                 int elem, int channels, void *d_out, const size_t *out_offsets,
+                                 const void *d_pyr, size_t pyr_stride_bytes, int levels, int max_aniso);
 /* The source field of the FORWARD warps (next section): what hg_warp_forward_* would paint, as geometry.  HG_FIELD_INDEX only, hence no
  * format argument: the forward loops copy whole pixels from integer positions, (s % W, s / W) IS the coordinate.  One int32 per output pixel
  * p, row-major obj_w x obj_h: let w be the LAST writer, in the loop's raster order (:919-930 over y < H, x < W; :955-969 over the cells of
