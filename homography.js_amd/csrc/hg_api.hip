@@ -242,7 +242,10 @@ extern "C" int hg_set_option(hg_ctx *c, const char *key, int value)
         while ((1 << c->xcc_log2) < value) c->xcc_log2++;
     }
     else if (!std::strcmp(key, "fwd_tiles")) { c->opt_fwd_tiles = value; c->fwd_pw_tiles_disabled = false; }
+    else if (!std::strcmp(key, "span_cache")) c->opt_span_cache = value < 0 ? -1 : (value ? 1 : 0);
+    else if (!std::strcmp(key, "span_cache_mb")) c->opt_span_cache_mb = value;
     else return fail(c, HG_ERR_INVALID, std::string("hg_set_option: unknown key ") + key);
+    c->pw_epoch++;                                            // (an option may change the plan or the span flags: cached spans are rebuilt)
     return HG_OK;
 }
 
@@ -252,6 +255,7 @@ extern "C" int hg_set_sampling(hg_ctx *c, int mode)
 {
     if (!c) return fail(nullptr, HG_ERR_INVALID, "ctx is NULL");
     if (mode != HG_SAMPLE_NEAREST && mode != HG_SAMPLE_BILINEAR) return fail(c, HG_ERR_INVALID, "hg_set_sampling: unknown mode " + std::to_string(mode));
+    if (mode != c->sampling) c->pw_epoch++;
     c->sampling = mode;                                       // (queued runs keep the mode they were queued with: nothing to settle)
     return HG_OK;
 }
@@ -388,6 +392,7 @@ extern "C" int hg_set_image(hg_ctx *c, const uint8_t *rgba, int w, int h)
     HG_TRY(ensure(c, c->d_img, bytes));                 // (a borrowed image is dropped, not freed)
     HIP_TRY(c, hipMemcpyAsync(c->d_img, rgba, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));       // caller memory is not retained after return
+    if (w != c->W || h != c->H || c->n_imgs != 1) c->pw_epoch++;      // (new content in the same dimensions changes no geometry)
     c->W = w; c->H = h; c->n_imgs = 1; c->img_stride = 0;
     return HG_OK;
 }
@@ -399,6 +404,7 @@ extern "C" int hg_set_image_device(hg_ctx *c, const void *d_rgba, int w, int h)
     HG_TRY(hg_sync(c));
     if (c->d_img.cap) HIP_TRY(c, hipStreamSynchronize(c->stream));     // (an image of the context's own goes)
     c->d_img.borrow(const_cast<uint8_t *>(static_cast<const uint8_t *>(d_rgba)));
+    if (w != c->W || h != c->H || c->n_imgs != 1) c->pw_epoch++;      // (another pointer with the same dimensions changes no geometry)
     c->W = w; c->H = h; c->n_imgs = 1; c->img_stride = 0;
     return HG_OK;
 }
@@ -408,6 +414,7 @@ extern "C" int hg_set_images_device(hg_ctx *c, const void *d_rgba, int w, int h,
     if (n_images <= 0 || (w > 0 && h > 0 && n_images > 1 && (stride_bytes < (size_t)w * h * 4 || (stride_bytes & 3))))
         return fail(c, HG_ERR_INVALID, "hg_set_images_device: n_images must be >= 1 and the stride a multiple of 4 bytes >= width*height*4");
     HG_TRY(hg_set_image_device(c, d_rgba, w, h));
+    if (n_images != 1) c->pw_epoch++;
     c->n_imgs = n_images; c->img_stride = n_images > 1 ? stride_bytes : 0;
     return HG_OK;
 }

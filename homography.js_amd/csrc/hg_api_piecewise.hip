@@ -26,7 +26,7 @@ extern "C" int hg_piecewise_set_mesh(hg_ctx *c, const float *src, int n_pts, con
     c->h_src.assign(src, src + (size_t)2 * n_pts);
     c->fmap_valid = false;
     c->have_mesh = true;
-    c->mesh_gen++;
+    c->mesh_gen++; c->pw_epoch++;
     c->fwd_pw_tiles_disabled = false; c->fwd_pw_cap = 64;     // (learned on the previous mesh)
     c->pw_learned = PwLearned{};
     c->pw_frames.clear(); c->pw_setup_done = false; c->pw_moving = false;
@@ -124,6 +124,7 @@ static int set_frames_transaction(hg_ctx *c, bool own_src, const float *src, con
         const std::string why = c->err;
         (void)hg_sync(c);                                   // queued runs of the old set are settled against the old set
         c->pw_frames.clear(); c->pw_setup_done = false; c->rows_clean = false; c->pw_moving = false;
+        c->pw_epoch++;
         c->err = why; g_err = why;
     }
     return rc;
@@ -169,6 +170,7 @@ static int pw_set_frames_impl(hg_ctx *c, bool own_src, const float *src, const i
     // staged copy of the set it warped (deferred redo, hg_sync).  Only a staging slot that a queued run still refers to forces a
     // settlement first (a caller that uploads 64 sets per run).
     const size_t T = (size_t)std::max(c->n_tris, 1), F = (size_t)n;
+    c->pw_epoch++;                                           // (a new frame set, whatever becomes of it: cached spans belong to the old one)
     const int slot = c->stage.next();
     for (const hg_ctx::Pending &pd : c->pw_pending_out) if (pd.stage == slot) { HG_TRY(hg_sync(c)); break; }
     for (const hg_ctx::FwdPending &pd : c->fwd_pending) if (pd.stage == slot) { HG_TRY(hg_sync(c)); break; }   // (their redo reads the staged set too)
@@ -485,6 +487,7 @@ static void learn_from_overflows(hg_ctx *c, const std::vector<hg_ctx::Pending> &
             self |= r.self;
         }
     if (!over) return;
+    c->pw_epoch++;
     if (patch) c->pw_learned.patch_disabled = true;
     if (c->row_cap < kRowSpanCapDense)                       // denser mesh than assumed: larger lists next time
         c->row_cap = c->row_cap < kRowSpanCapFast ? kRowSpanCapFast : kRowSpanCapDense;
@@ -562,13 +565,87 @@ static int run_setup(hg_ctx *c, bool for_tap = false)
 }
 
 // The warp kernel of the stored plan (map_out: the parity tap, whose plan is k_pw_rows or k_pw_fused).
-static void run_warp(hg_ctx *c, uint8_t *d_out, int16_t *map_out)
+// ---- span cache (hg_span_cache.h): Off, Build or Use for the warp that run_setup has just planned; on Build the buffers are sized and the
+// directory cleared.  Only hg_warp_inverse_piecewise_frames_device asks: taps, fields, point lists and forward warps neither use nor count.
+static SpanPlanKey span_key_of(const hg_ctx *c)
+{
+    const PwPlan &p = c->pw_plan;
+    SpanPlanKey k;
+    k.eligible = p.kernel == PwKernel::Rows && p.self && p.row_group == kRowGroup && c->n_imgs <= 1;
+    k.W = c->W; k.H = c->H;
+    if (c->pw_moving) { k.ms_lo_x = c->ms_lo_x; k.ms_hi_x = c->ms_hi_x; k.ms_lo_y = c->ms_lo_y; k.ms_hi_y = c->ms_hi_y; }
+    else { k.ms_lo_x = k.ms_hi_x = c->min_src_x; k.ms_lo_y = k.ms_hi_y = c->min_src_y; }
+    k.hi_bounds = p.no_hi_bounds ? 0 : 1;                    // (with the source's size and minima above: the launcher's choice of the bounds form)
+    k.safe_spans = p.safe_spans; k.bands = p.bands ? 1 : 0; k.n_bands = p.n_bands;
+    k.n_frames = (int)c->pw_frames.size(); k.max_h = c->pw_shape.max_h;
+    return k;
+}
+
+static int span_cache_prepare(hg_ctx *c, SpanCacheDev *sc)
+{
+    *sc = SpanCacheDev();
+    c->span_last = 0;
+    if (c->opt_span_cache == 0) return HG_OK;
+    const SpanPlanKey key = span_key_of(c);
+    if (!key.eligible) return HG_OK;
+    const PwShape &s = c->pw_shape;
+    // the host's estimate: every row of every group at the estimated longest span list, long-form records
+    const uint64_t estimate = (uint64_t)s.groups * kRowGroup * (uint64_t)std::min(s.cover + 1, 63) * (kSpanRecWordsLong * 16);
+    const bool force = c->opt_span_cache_mb < 0;
+    const uint64_t budget = force ? (uint64_t)(-(int64_t)c->opt_span_cache_mb) << 10 : (uint64_t)c->opt_span_cache_mb << 20;
+    const SpanCacheMode mode = span_cache_decide(c->span_state, c->pw_epoch, key, c->opt_span_cache, budget, estimate, force);
+    if (mode == SpanCacheMode::Build) {
+        const uint64_t bytes = std::min<uint64_t>(force ? budget : std::min(budget, estimate), ((uint64_t)1 << 36) - 16);
+        const int gpf = (std::max(s.max_h, 1) + kRowGroup - 1) / kRowGroup;
+        const size_t entries = 1 + (size_t)key.n_frames * gpf;
+        HG_TRY(ensure(c, c->d_span_rec, (size_t)std::max<uint64_t>(bytes / 16, 1)));        // (growing drains the stream first: once per build)
+        HG_TRY(ensure(c, c->d_span_dir, entries));
+        HIP_TRY(c, hipMemsetAsync(c->d_span_dir, 0, sizeof(int4) * entries, c->stream));   // cursor 0, every group "not cached"
+        c->span_cap16 = (uint32_t)(bytes / 16); c->span_gpf = gpf;
+        c->span_builds++;
+    }
+    span_cache_commit(c->span_state, c->pw_epoch, key, c->opt_span_cache, mode);
+    if (mode == SpanCacheMode::Off) return HG_OK;
+    if (mode == SpanCacheMode::Use) c->span_uses++;
+    c->span_last = (int)mode;
+    sc->dir = c->d_span_dir + 1; sc->rec = c->d_span_rec; sc->cursor = reinterpret_cast<unsigned long long *>(c->d_span_dir.p);
+    sc->cap16 = c->span_cap16; sc->groups_per_frame = c->span_gpf; sc->mode = (int)mode;
+    return HG_OK;
+}
+
+// builds, calls that ran Use, groups valid, groups not cached (of the build the context holds), bytes held, state of the last warp (0 off, 1 build, 2 use)
+extern "C" int hg_span_cache_stats(hg_ctx *c, int64_t out[6])
+{
+    HG_TRY(bind(c));
+    if (!out) return fail(c, HG_ERR_INVALID, "hg_span_cache_stats: out is NULL");
+    out[0] = c->span_builds; out[1] = c->span_uses; out[2] = 0; out[3] = 0; out[4] = 0; out[5] = c->span_last;
+    const SpanCacheState &st = c->span_state;
+    if (!st.built || st.epoch != c->pw_epoch || !c->d_span_dir.cap || (size_t)st.key.n_frames != c->pw_frames.size()) return HG_OK;
+    const size_t entries = 1 + (size_t)st.key.n_frames * c->span_gpf;
+    std::vector<int4> dir(entries);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(dir.data(), c->d_span_dir, sizeof(int4) * entries, hipMemcpyDeviceToHost));
+    for (size_t f = 0; f < c->pw_frames.size(); f++) {
+        const FrameDesc &fd = c->pw_frames[f];
+        if (fd.obj_w <= 0 || fd.obj_h <= 0) continue;
+        for (int g = 0; g < (fd.obj_h + kRowGroup - 1) / kRowGroup; g++) {
+            const int32_t state = dir[1 + f * (size_t)c->span_gpf + g].x;
+            if (state == SPAN_DIR_VALID) out[2]++; else if (state == SPAN_DIR_NOT_CACHED) out[3]++;
+        }
+    }
+    unsigned long long cursor = 0;
+    std::memcpy(&cursor, dir.data(), sizeof cursor);
+    out[4] = (int64_t)(std::min<unsigned long long>(cursor, c->span_cap16) * 16 + sizeof(int4) * entries);
+    return HG_OK;
+}
+
+static void run_warp(hg_ctx *c, uint8_t *d_out, int16_t *map_out, const SpanCacheDev &sc = SpanCacheDev())
 {
     const PwPlan &p = c->pw_plan;
     c->pw_last_kernel = kernel_code(p);
     switch (p.kernel) {
     case PwKernel::Rows:
-        c->pw_last_variant = launch_pw_rows(mesh_of(c), frames_of(c), rows_of(c), d_out, map_out, c->status_next, c->stream); break;
+        c->pw_last_variant = launch_pw_rows(mesh_of(c), frames_of(c), rows_of(c), d_out, map_out, c->status_next, c->stream, sc); break;
     case PwKernel::Patch: case PwKernel::PatchGlobal:
         c->pw_last_variant = launch_pw_patch(mesh_of(c), frames_of(c), rows_of(c), d_out, c->status_next, p.kernel == PwKernel::PatchGlobal, c->stream); break;
     case PwKernel::Tile:
@@ -688,8 +765,10 @@ extern "C" int hg_warp_inverse_piecewise_frames_device(hg_ctx *c, void *d_out)
     // The reference recomputes the per-triangle matrices on every setDestinyPoints and the map + inverses on every
     // warp(): both are part of the per-frame step, so both run here every time.
     HG_TRY(run_setup(c));
+    SpanCacheDev sc;
+    HG_TRY(span_cache_prepare(c, &sc));
     HG_TRY(time_begin(c));
-    run_warp(c, static_cast<uint8_t *>(d_out), nullptr);
+    run_warp(c, static_cast<uint8_t *>(d_out), nullptr, sc);
     HG_TRY(time_end(c));
     HIP_TRY(c, hipGetLastError());
     const PwPlan &p = c->pw_plan;

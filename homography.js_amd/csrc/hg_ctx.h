@@ -173,6 +173,15 @@ struct hg_ctx {
     int opt_tri_group = -1;                                    // k_tri_spans_grouped: 16 / 64 triangles per workgroup, 0 never, -1 by mesh size
     int opt_upload_kernel = -1;                                // frame-set blocks up to 1 MB go up by k_upload (default) instead of hipMemcpyAsync (0)
     int opt_safe_spans = -1;                                   // option "safe_spans": span flags + bounds-test-free windows in k_pw_rows: 1 / 0, -1 by the spans-per-window estimate
+    // span cache of k_pw_rows<SELF> in packed 4-row groups (hg_span_cache.h; span_cache_prepare in hg_api_piecewise.hip)
+    DevBuf<uint4> d_span_rec;                                  // records, 16-byte words
+    DevBuf<int4> d_span_dir;                                   // entry 0: the cursor (first 8 bytes), then one SpanDirEnt per (frame, 4-row group)
+    uint32_t span_cap16 = 0; int span_gpf = 0;                 // words the build may hand out; groups per frame of the directory
+    uint64_t pw_epoch = 1;                                     // frame-set epoch: bumped by whatever can change an input of k_tri_setup or of the span prologue
+    SpanCacheState span_state;
+    int opt_span_cache = -1;                                   // option "span_cache": -1 build on the second warp of a set, 0 off, 1 build on the first
+    int opt_span_cache_mb = 256;                               // option "span_cache_mb": budget in MB; negative: -KB, and the host's estimate does not veto the build
+    long span_builds = 0, span_uses = 0; int span_last = 0;    // hg_span_cache_stats
     // layout estimates of the last frame set, reused for the next set of the same shape (the kernels check the real counts)
     struct LayoutKey { int n = -1, n_tris = -1, max_w = -1, max_h = -1; uint64_t mesh_gen = 0; bool quick = false; } layout_key;
     uint64_t mesh_gen = 0; int layout_age = 0;

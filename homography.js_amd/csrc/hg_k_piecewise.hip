@@ -311,10 +311,10 @@ __global__ __launch_bounds__(kTriGroupThreads) void k_tri_spans_grouped(PwMesh m
 }
 
 
-template <int CAP, bool MAP, int PH, bool COMPACT, bool HIB, int SELF>      // SELF: 0 row lists, 1 own spans
+template <int CAP, bool MAP, int PH, bool COMPACT, bool HIB, int SELF>      // SELF: 0 row lists, 1 own spans, 2 own spans written to the span cache, 3 spans from the cache
 __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl, uint8_t *__restrict__ out,
                                              int16_t *__restrict__ map_out, int groups_per_xcd, int rows_per_group,
-                                             int32_t *__restrict__ status_next)
+                                             int32_t *__restrict__ status_next, const SpanCacheDev &sc)
 {
     // A workgroup owns rows_per_group consecutive output rows: kRowGroup = 4 when the host expects short span lists, 1
     // for dense meshes (there, rows that share source lines should run side by side in different workgroups).  1-D grid decoded so that XCD x (= block id % number of XCCs of the device -- hipDeviceAttributeNumberOfXccs, hg_create --, the observed
@@ -673,6 +673,93 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
     // waves/SIMD) and a phased variant (4 windows resolved, then 16 gathers, then 16 stores) are both ~4 % slower: with
     // 8 waves/SIMD the other waves already cover a window's memory latency, and reads + writes together run at ~5.2 TB/s.
     if (SELF) {
+        bool have = false;                                  // (workgroup-uniform) the slots are in LDS already
+        if constexpr (SELF >= 2) {
+            // Span cache (hg_span_cache.h; host: packed 4-row groups only).  The records are read with ordinary loads: non-temporal ones crept at
+            // some 0.4 GB per ms here (C3 + 0.24 ms for 95 MB of records), and the fetch counters show the sub-band's slice of the source staying in
+            // the L2 beside them (EXPERIMENTS.md S.2).  The build writes them out non-temporally, once.
+            typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+            // (directory index, words per record, and the row whose slot `lane` this thread copies: one thread per slot of the four 64-slot blocks.
+            //  Lambdas, evaluated where they are needed: nothing of the cache is live across the prologue)
+            auto dir_at = [&]() -> size_t { return (size_t)__builtin_amdgcn_readfirstlane(f) * sc.groups_per_frame + __builtin_amdgcn_readfirstlane(gi); };
+            auto rec_words = [&]() -> int { return one_fma ? kSpanRecWordsFma : kSpanRecWordsLong; };
+            if constexpr (SELF == 3) {
+                const size_t di = dir_at();
+                const int recw = rec_words(), crow = wave;
+                const int4 e = sc.dir[di];
+                const int state = __builtin_amdgcn_readfirstlane(e.x);
+                if (packed && state == SPAN_DIR_OVERFLOWED) {           // what the prologue of the build found: the same flag, every call
+                    if (threadIdx.x == 0) flag_frame(fr, f, FRAME_LDS_OVERFLOW);
+                    return;
+                }
+                if (packed && state == SPAN_DIR_VALID && __builtin_amdgcn_readfirstlane(e.w) == recw) {     // (records of the form this step's k_tri_setup decided for the frame)
+                    const uint32_t off16 = (uint32_t)__builtin_amdgcn_readfirstlane(e.y), counts = (uint32_t)__builtin_amdgcn_readfirstlane(e.z);
+                    // Wave j copies row j's slots into row j's block and is the only reader of that block (packed groups: wave j walks row
+                    // r0 + j alone): no barrier, a wave starts on its row as soon as its own records have landed.
+                    if (lane < 3) reinterpret_cast<double2 *>(s_m + (crow * 64 + 63) * 6)[lane] = make_double2(NAN, NAN);     // the row block's NaN record, as the prologue leaves it
+                    int before = 0;
+#pragma unroll
+                    for (int j = 0; j < RG; j++) { cnts[j] = span_count(counts, j); before += j < crow ? cnts[j] : 0; }
+                    if (lane < span_count(counts, crow)) {
+                        const v4u *p = reinterpret_cast<const v4u *>(sc.rec) + off16 + (size_t)(before + lane) * recw;
+                        const v4u a = p[0], b = p[1];
+                        const int at = crow * 64 + lane, lo = span_lo(a.x), hi = span_hi(a.x);
+                        s_lo[at] = lo; s_hi[at] = hi; s_len[at] = hi - lo;
+                        s_key[at] = (span_id(a.y) << KS) | (at * 48) | span_unsafe_bit(a.y);
+                        double2 *mrec = reinterpret_cast<double2 *>(s_m + at * 6);
+                        mrec[0] = make_double2((double)__uint_as_float(a.z), __hiloint2double((int)b.y, (int)b.x));
+                        mrec[1] = make_double2((double)__uint_as_float(a.w), __hiloint2double((int)b.w, (int)b.z));
+                        if (!one_fma) {
+                            const v4u c = p[2];
+                            mrec[2] = make_double2((double)__uint_as_float(c.x), (double)__uint_as_float(c.y));
+                        }
+                    }
+                    have = true;
+                }
+            }
+            if (!have) {
+                const bool ok = self_prologue();
+                if (SELF == 2 && packed) {                  // build: the group's slots out, then its directory entry
+                    const size_t di = dir_at();
+                    const int recw = rec_words(), crow = wave;
+                    if (threadIdx.x == 0) {
+                        SpanDirEnt d{ok ? SPAN_DIR_NOT_CACHED : SPAN_DIR_OVERFLOWED, 0u, 0u, 0u};
+                        if (ok) {
+                            const unsigned long long need = (unsigned long long)(cnts[0] + cnts[1] + cnts[2] + cnts[3]) * recw;
+                            const unsigned long long at16 = atomicAdd(sc.cursor, need);       // one device-scope atomic per workgroup, once per frame set
+                            if (at16 + need <= sc.cap16) { d.state = SPAN_DIR_VALID; d.off16 = (uint32_t)at16; d.counts = span_pack_counts(cnts[0], cnts[1], cnts[2], cnts[3]); }
+                        }
+                        sc.dir[di] = make_int4(d.state, (int)d.off16, (int)d.counts, recw);
+                        s_cand_tn[0] = d.state; s_cand_y[0] = (int)d.off16;       // (the candidate list is done with)
+                    }
+                    __syncthreads();
+                    if (s_cand_tn[0] == SPAN_DIR_VALID) {
+                        const uint32_t off16 = (uint32_t)s_cand_y[0];
+                        int before = 0, mine = 0;
+#pragma unroll
+                        for (int j = 0; j < RG; j++) { before += j < crow ? cnts[j] : 0; mine += j == crow ? cnts[j] : 0; }
+                        if (lane < mine) {
+                            v4u *p = reinterpret_cast<v4u *>(sc.rec) + off16 + (size_t)(before + lane) * recw;
+                            const int at = crow * 64 + lane, key = s_key[at];
+                            const double2 *mrec = reinterpret_cast<const double2 *>(s_m + at * 6);
+                            const double2 ra = mrec[0], rb = mrec[1];
+                            const v4u a = { span_pack_lo_hi(s_lo[at], s_hi[at]), span_pack_id(key >> KS, key & 1), __float_as_uint((float)ra.x), __float_as_uint((float)rb.x) };
+                            const v4u b = { (uint32_t)__double2loint(ra.y), (uint32_t)__double2hiint(ra.y), (uint32_t)__double2loint(rb.y), (uint32_t)__double2hiint(rb.y) };
+                            __builtin_nontemporal_store(a, p); __builtin_nontemporal_store(b, p + 1);
+                            if (!one_fma) {
+                                const double2 rc = mrec[2];
+                                const v4u c = { __float_as_uint((float)rc.x), __float_as_uint((float)rc.y), 0u, 0u };
+                                __builtin_nontemporal_store(c, p + 2);
+                            }
+                        }
+                    }
+                }
+                if (!ok) {
+                    if (threadIdx.x == 0) flag_frame(fr, f, FRAME_LDS_OVERFLOW);
+                    return;
+                }
+            }
+        } else
         if (!self_prologue()) {                             // more candidates / spans than the LDS holds: the host redoes the frame through the map
             if (threadIdx.x == 0) flag_frame(fr, f, FRAME_LDS_OVERFLOW);
             return;
@@ -701,7 +788,16 @@ template <int CAP, bool MAP, int PH = 1, bool COMPACT = false, bool HIB = false,
 __global__ __launch_bounds__(256) void k_pw_rows(PwMesh mesh, PwFrames fr, RowLists rl, uint8_t *__restrict__ out, int16_t *__restrict__ map_out,
                                                  int groups_per_xcd, int rows_per_group, int32_t *__restrict__ status_next)
 {
-    pw_rows_body<CAP, MAP, PH, COMPACT, HIB, SELF>(mesh, fr, rl, out, map_out, groups_per_xcd, rows_per_group, status_next);
+    pw_rows_body<CAP, MAP, PH, COMPACT, HIB, SELF>(mesh, fr, rl, out, map_out, groups_per_xcd, rows_per_group, status_next, SpanCacheDev());
+}
+
+// The packed 4-row self-span form with the span cache behind it (SELF 2: build, 3: use).
+template <int PH, bool HIB, int SELF>
+__global__ __launch_bounds__(256) void k_pw_rows_cached(PwMesh mesh, PwFrames fr, RowLists rl, uint8_t *__restrict__ out, int groups_per_xcd, int rows_per_group,
+                                                        int32_t *__restrict__ status_next, SpanCacheDev sc)
+{
+    static_assert(SELF == 2 || SELF == 3, "build or use");
+    pw_rows_body<kRowSpanCapFast, false, PH, false, HIB, SELF>(mesh, fr, rl, out, nullptr, groups_per_xcd, rows_per_group, status_next, sc);
 }
 
 // The same kernel held to 80 SGPRs.  A 256-thread workgroup puts one wave on each SIMD and a SIMD has 800 SGPRs, allocated in
@@ -713,7 +809,7 @@ template <int CAP, bool MAP, int PH = 1, bool COMPACT = false, bool HIB = false,
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_pw_rows_s80(PwMesh mesh, PwFrames fr, RowLists rl, uint8_t *__restrict__ out,
                                                  int16_t *__restrict__ map_out, int groups_per_xcd, int rows_per_group, int32_t *__restrict__ status_next)
 {
-    pw_rows_body<CAP, MAP, PH, COMPACT, HIB, SELF>(mesh, fr, rl, out, map_out, groups_per_xcd, rows_per_group, status_next);
+    pw_rows_body<CAP, MAP, PH, COMPACT, HIB, SELF>(mesh, fr, rl, out, map_out, groups_per_xcd, rows_per_group, status_next, SpanCacheDev());
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
@@ -793,7 +889,8 @@ void launch_tri_spans(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl
 // Returns the variant code of the instantiation it launched (hg_last_piecewise_variant; tools/census.py): kind * 100000 + (512-slot rows) * 10000 +
 // windows-or-blocks per phase * 1000 + (8-byte entries) * 100 + (bounds on the high dwords) * 10 + self-span form; kind 1 k_pw_rows,
 // 3 k_pw_rows_s80, 4 k_pw_patch, 5 k_pw_tile, 6 k_pw_fused, 8 k_pw_patch with global records; + 50 for a parity-tap (map) instantiation.
-int launch_pw_rows(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl, uint8_t *out, int16_t *map_out, int32_t *status_next, hipStream_t stream)
+int launch_pw_rows(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl, uint8_t *out, int16_t *map_out, int32_t *status_next, hipStream_t stream,
+                   const SpanCacheDev &sc)
 {
     if (fr.n_frames <= 0 || fr.max_obj_h <= 0) return 0;
     int code = 0;
@@ -814,6 +911,14 @@ int launch_pw_rows(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl, u
     if (fr.self_spans) {                                     // spans evaluated by the row workgroups themselves (sparse meshes: CAP 256, no row lists, k_tri_setup in front)
         // ONE depth: 4 windows per phase (R4.10: a wash to a slight gain over 2 for every self-span set; the census of round 6 found the
         // 1- / 2-window, the 80-SGPR and the three-edges-in-flight instantiations never picked: deleted, EXPERIMENTS.md R6.6)
+        // span cache (host: packed 4-row groups, no tap): the same two forms with the cache behind them; the code reported is the uncached form's
+        if (sc.mode && !map_out && rg == kRowGroup && sc.dir && sc.rec && sc.cursor) {
+#define HG_ROWS_SC(PHV, HB, SF) hipLaunchKernelGGL((k_pw_rows_cached<PHV, HB, SF>), grid, block, pad, stream, mesh, frs, rl, out, rpx, rg, status_next, sc)
+            if (!hib) { code = 101001; if (sc.mode == 1) HG_ROWS_SC(1, false, 2); else HG_ROWS_SC(1, false, 3); }
+            else      { code = 104011; if (sc.mode == 1) HG_ROWS_SC(4, true, 2); else HG_ROWS_SC(4, true, 3); }
+#undef HG_ROWS_SC
+            return code;
+        }
         if (map_out) HG_ROWS(kRowSpanCapFast, true, 1, false, false, 1);
         else if (!hib) HG_ROWS(kRowSpanCapFast, false, 1, false, false, 1);
         else HG_ROWS(kRowSpanCapFast, false, 4, false, true, 1);

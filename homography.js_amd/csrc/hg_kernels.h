@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hg_math.h"
+#include "hg_span_cache.h"
 
 namespace hg {
 
@@ -146,7 +147,18 @@ bool pw_fast_ok(const PwMesh &mesh, int max_obj_w);
 // ... for a whole frame set: with per-frame source minima, at both extremes of the set
 bool pw_fast_ok(const PwMesh &mesh, const PwFrames &fr, int max_obj_w);
 void launch_tri_spans(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl, hipStream_t stream);
-int launch_pw_rows(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl, uint8_t *out, int16_t *map_out, int32_t *status_next, hipStream_t stream);
+// The span cache of the packed 4-row self-span form (hg_span_cache.h): mode 0 none, 1 build (the prologue's slots are also written out),
+// 2 use (groups whose directory entry is valid copy their slots in instead of evaluating spans).
+struct SpanCacheDev {
+    int4 *dir = nullptr;                        // n_frames x groups_per_frame SpanDirEnt
+    uint4 *rec = nullptr;                       // cap16 16-byte words of records
+    unsigned long long *cursor = nullptr;       // words handed out (may run past cap16: those groups are "not cached")
+    uint32_t cap16 = 0;
+    int32_t groups_per_frame = 0;
+    int32_t mode = 0;
+};
+int launch_pw_rows(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl, uint8_t *out, int16_t *map_out, int32_t *status_next, hipStream_t stream,
+                   const SpanCacheDev &sc = SpanCacheDev());
 // Dense meshes (64..199 spans per row, obj_w <= 8192): 4 rows per workgroup, 16 x 4 pixel gather patches, one matrix record
 // per triangle of the group.  Same row lists, same status protocol as launch_pw_rows; no map tap.
 // (limits on the HOST ESTIMATES, which run ~10 % above the real counts the kernel enforces: 199 spans per row, 208 triangles

@@ -1094,6 +1094,24 @@ static napi_value fn_redone_frames(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* spanCacheStats(ctx): hg_span_cache_stats as an array of six numbers -- builds, warps that ran from the cache, groups valid, groups not cached,
+ * bytes held, state of the last inverse piecewise warp (0 off, 1 build, 2 use); null if the call failed */
+static napi_value fn_span_cache_stats(napi_env env, napi_callback_info info)
+{
+    napi_value a[1];
+    if (!get_args(env, info, 1, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    int64_t st[6] = { 0, 0, 0, 0, 0, 0 };
+    napi_value out, v;
+    if (hg_span_cache_stats(h->ctx, st) != HG_OK) { NAPI_OK(napi_get_null(env, &out)); return out; }
+    NAPI_OK(napi_create_array_with_length(env, 6, &out));
+    for (uint32_t i = 0; i < 6; i++) {
+        NAPI_OK(napi_create_double(env, (double)st[i], &v));
+        NAPI_OK(napi_set_element(env, out, i, v));
+    }
+    return out;
+}
+
 /* setSampling(handle, mode): HG_SAMPLE_NEAREST (0) / HG_SAMPLE_BILINEAR (1) for the inverse warps called from now on */
 static napi_value fn_set_sampling(napi_env env, napi_callback_info info)
 {
@@ -1657,7 +1675,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "pointsForwardGeometric", fn_points_forward_geometric }, { "pointsForwardPiecewise", fn_points_forward_piecewise },
         { "solveAffineTriangles", fn_solve_affine_triangles }, { "warpInversePiecewiseState", fn_warp_inverse_piecewise_state },
         { "warpForwardPiecewiseState", fn_warp_forward_piecewise_state },
-        { "release", fn_release }, { "setPinnedLimit", fn_set_pinned_limit }, { "poolStats", fn_pool_stats }, { "redoneFrames", fn_redone_frames }, { "setSampling", fn_set_sampling }, { "multiSetSampling", fn_multi_set_sampling }, { "_poolTestFrames", fn_pool_test_frames }, { "poolPressure", fn_pool_pressure }, { "poolCollected", fn_pool_collected },
+        { "release", fn_release }, { "setPinnedLimit", fn_set_pinned_limit }, { "poolStats", fn_pool_stats }, { "redoneFrames", fn_redone_frames }, { "spanCacheStats", fn_span_cache_stats }, { "setSampling", fn_set_sampling }, { "multiSetSampling", fn_multi_set_sampling }, { "_poolTestFrames", fn_pool_test_frames }, { "poolPressure", fn_pool_pressure }, { "poolCollected", fn_pool_collected },
         { "multiCreate", fn_multi_create }, { "multiDestroy", fn_multi_destroy }, { "multiSetImage", fn_multi_set_image },
         { "multiSetMesh", fn_multi_set_mesh }, { "multiWarpBatch", fn_multi_warp_batch }, { "multiWarpGeometricBatch", fn_multi_warp_geometric_batch },
     };

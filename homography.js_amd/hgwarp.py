@@ -45,7 +45,7 @@ EXPORTS = [
     "hg_warp_forward_piecewise_device", "hg_warp_forward_piecewise_batch_device",
     "hg_solve_affine_triangles", "hg_warp_inverse_piecewise_state", "hg_warp_forward_piecewise_state",
     "hg_upload_on_copy_stream", "hg_fence_copies", "hg_download_behind_warps", "hg_fence_downloads",
-    "hg_set_timing", "hg_last_kernel_ms", "hg_kernel_ms_stats", "hg_last_piecewise_kernel", "hg_last_piecewise_variant", "hg_last_geometric_kernel", "hg_last_piecewise_self", "hg_last_piecewise_flag", "hg_last_forward_kernel", "hg_forward_tiles_admissible", "hg_redone_frames", "hg_layout_walks", "hg_set_option", "hg_xcc_count", "hg_selftest_division", "hg_projective_plain_range", "hg_affine_one_fma_form",
+    "hg_set_timing", "hg_last_kernel_ms", "hg_kernel_ms_stats", "hg_last_piecewise_kernel", "hg_last_piecewise_variant", "hg_last_geometric_kernel", "hg_last_piecewise_self", "hg_last_piecewise_flag", "hg_last_forward_kernel", "hg_forward_tiles_admissible", "hg_redone_frames", "hg_layout_walks", "hg_span_cache_stats", "hg_set_option", "hg_xcc_count", "hg_selftest_division", "hg_projective_plain_range", "hg_affine_one_fma_form",
     "hg_set_sampling", "hg_get_sampling", "hg_multi_set_sampling",
     "hg_pack_field_offsets", "hg_field_inverse_geometric", "hg_field_inverse_geometric_device", "hg_field_inverse_geometric_frames_device",
     "hg_field_inverse_piecewise", "hg_field_inverse_piecewise_frames_device", "hg_remap_index_device", "hg_remap_bilinear_f32_device",
@@ -129,6 +129,7 @@ def lib():
         "hg_get_matrices": (i, [vp, f32p, f32p]), "hg_warp_inverse_piecewise_via_map": (i, [vp, u8p]),
         "hg_last_piecewise_kernel": (i, [vp]), "hg_last_piecewise_variant": (i, [vp]), "hg_last_geometric_kernel": (i, [vp]), "hg_last_piecewise_self": (i, [vp]), "hg_last_piecewise_flag": (i, [vp]), "hg_last_forward_kernel": (i, [vp]), "hg_set_option": (i, [vp, C.c_char_p, i]),
         "hg_set_sampling": (i, [vp, i]), "hg_get_sampling": (i, [vp, C.POINTER(i)]), "hg_multi_set_sampling": (i, [vp, i]), "hg_redone_frames": (C.c_long, [vp]), "hg_layout_walks": (C.c_long, [vp]), "hg_xcc_count": (i, [vp]),
+        "hg_span_cache_stats": (i, [vp, C.POINTER(C.c_int64)]),
         "hg_selftest_division": (i, [vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
         "hg_projective_plain_range": (i, [f64p, Geom]), "hg_affine_one_fma_form": (i, [f32p, Geom]), "hg_forward_tiles_admissible": (i, [i, f64p, i, i, Geom]),
         "hg_set_timing": (i, [vp, i]), "hg_last_kernel_ms": (i, [vp, f32p]),
@@ -450,6 +451,14 @@ class Context:
     def layout_walks(self):
         """Host walks over the triangles of a frame set (layout estimates) since the context was created."""
         return lib().hg_layout_walks(self._h)
+
+    def span_cache_stats(self):
+        """The span cache of the row warp kernel: builds, warps that ran from it, groups valid / not cached and bytes held of the current
+        build, and the state of the last inverse piecewise warp ("off", "build", "use")."""
+        out = (C.c_int64 * 6)()
+        self._c(lib().hg_span_cache_stats(self._h, out))
+        return {"builds": out[0], "use_calls": out[1], "groups_valid": out[2], "groups_not_cached": out[3], "bytes": out[4],
+                "state": ("off", "build", "use")[out[5]]}
 
     def xcc_count(self):
         """XCCs the warp kernels' block id -> row band mapping assumes (read from the device at creation, or option 'xcc')."""

@@ -673,6 +673,12 @@ long hg_redone_frames(hg_ctx *ctx);
 /* Host-side walks over every triangle of a frame set (the layout estimate of hg_piecewise_set_frames) since the ctx was created:
  * a caller that uploads fresh points of one mesh and window shape per step should see this stand still. */
 long hg_layout_walks(hg_ctx *ctx);
+/* The span cache of k_pw_rows<SELF> in packed 4-row groups (options "span_cache", "span_cache_mb"): while the frame set, the mesh, the source's
+ * dimensions and the plan stay the same, warps of the set copy the per-row span slots an earlier warp of it wrote to device memory instead of
+ * evaluating the spans again.  out: builds since the ctx was created, warps that ran from the cache, and -- of the build the ctx holds for the
+ * current frame set, 0 without one -- 4-row groups with valid records, groups that found no room, bytes held; then the state of the last
+ * inverse piecewise warp (0 off, 1 build, 2 use).  Waits for the stream.  Results never depend on the cache. */
+int hg_span_cache_stats(hg_ctx *ctx, int64_t out[6]);
 /* Layout knobs of the piecewise fast path; they never change results (tests run the parity suite under each setting), only
  * which kernel layout the next hg_piecewise_set_frames picks:
  *   "min_row_groups" (default 1152): frame sets with fewer 4-row groups run one row per workgroup on row lists (k_pw_patch sets keep
@@ -712,6 +718,11 @@ long hg_layout_walks(hg_ctx *ctx);
  *           pixels pass the source bounds test :1047 (then every pixel between them does: the affine coordinates are monotone along a row) and
  *           runs windows made only of such spans without the per-pixel test, Math.round with one add per coordinate;
  *           k_pw_patch<SELF> does the same per 64-pixel x 4-row block (on unless the option says 0);
+ *   "span_cache" (default -1): the span cache of k_pw_rows<SELF> in 4-row groups on a shared source (hg_span_cache_stats): -1 the second warp
+ *           of a frame set writes the per-row span slots to device memory and the warps after it copy them instead of evaluating spans, 0 off
+ *           (the launches of a library without it), 1 the first warp builds (tests, fuzzers);
+ *   "span_cache_mb" (default 256): its budget in MB; a set whose estimated records exceed it is not cached at all.  A negative value is a budget
+ *           of that many KB which the estimate does not veto: the groups that find room are cached, the others evaluate their spans as ever;
  *   "tile" (default -1 = wherever k_pw_patch would evaluate its own spans and either every frame reads its own source or, on a shared
  *           source, the mesh is steeply sheared (estimate >= 0.3) or packs more than two spans into a 64-pixel block -- and the host's
  *           estimate says a tile row holds its spans; 1 = whenever k_pw_patch<SELF> would run; 0 never): k_pw_tile instead of k_pw_patch -- 8 x 2048-pixel tiles, gathers in 8-pixel runs along the source

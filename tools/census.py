@@ -5,7 +5,7 @@
   * every inverse piecewise warp of the 144 golden cases,
 the variant code of the kernel instantiation that ran (hg_last_piecewise_variant) and whether a frame was redone.  Prints one line per
 (variant, count, examples); instantiations and option keys that never show up here and lost wherever they were tried are what gets deleted.
---per-set also prints one JSON line per frame set (label, variant, kernel, self, redone): two builds of the policy compare line by line.
+--per-set also prints one JSON line per frame set (label, variant, kernel, self, redone, span-cache state of the last warp): two builds of the policy compare line by line.
     python tools/census.py [--quick] [--per-set]        (GPU box)"""
 import collections, importlib.util, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,7 +42,8 @@ def main():
     def note(ctx, what):
         code, redone = ctx.last_piecewise_variant(), ctx.redone_frames()
         if per_set:
-            print(json.dumps({"set": what, "variant": code, "kernel": ctx.last_piecewise_kernel(), "self": ctx.last_piecewise_self(), "redone": redone}), flush=True)
+            print(json.dumps({"set": what, "variant": code, "kernel": ctx.last_piecewise_kernel(), "self": ctx.last_piecewise_self(), "redone": redone,
+                              "span_cache": ctx.span_cache_stats()["state"]}), flush=True)
         e = seen.setdefault(code, {"n": 0, "ex": [], "redone": 0})
         e["n"] += 1; e["redone"] += redone
         if len(e["ex"]) < 6: e["ex"].append(what)

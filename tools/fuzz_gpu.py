@@ -19,8 +19,14 @@ ROWS = bool(os.environ.get("FUZZ_ROWS"))
 TILE = bool(os.environ.get("FUZZ_TILE")) or ROWS
 bad = 0
 seen = {}                                                  # kernel id -> batch runs that went through it
+cached = {"off": 0, "build": 0, "use": 0}                  # span-cache state of the last warp of each batch
 overflow = 0
+redone = 0
 for t in range(trials):
+    if ROWS and t:                                         # a context per trial: the row-list capacity a dense mesh asks for is sticky, and with it the self-span
+        redone += ctx.redone_frames()                      # form -- and its span cache -- would be out of reach for the rest of the run
+        ctx.close()
+        ctx = HG.Context(0)
     W, H = int(rng.integers(8, 700)), int(rng.integers(8, 400))
     if TILE: W, H = int(rng.integers(300, 1500)), int(rng.integers(24, 260))
     img = G.lcg_image(W, H, 9000 + t)
@@ -42,6 +48,7 @@ for t in range(trials):
     ctx.set_option("tri_group", int(rng.choice([-1, 0, 16, 64])))
     ctx.set_option("compact", int(rng.choice([-1, -1, 0, 1])))
     ctx.set_option("xcc", int(rng.choice([8, 8, 1, 2, 4, 16])))
+    ctx.set_option("span_cache", int(rng.choice([-1, 1, 1, 0])))                            # (the batches below warp a set three times: the last warp runs from the cache)
     nx, ny = int(rng.integers(1, 24)), int(rng.integers(1, 16))
     if mode == 6:
         nx, ny = int(rng.integers(30, 140)), int(rng.integers(1, 6))                      # dense rows: 1 row per workgroup, > 63 spans per row
@@ -89,7 +96,9 @@ for t in range(trials):
             ctx.piecewise_set_frames(np.concatenate(frames), geoms, offs)
             ctx.warp_inverse_piecewise_frames_device(d_out)
             ctx.warp_inverse_piecewise_frames_device(d_out)                                 # queued twice: self-cleaning counters
+            ctx.warp_inverse_piecewise_frames_device(d_out)                                 # ... and a third time: span cache off / build / use by default, build / use / use when eager
             ctx.sync()
+            cached[ctx.span_cache_stats()["state"]] += 1
             seen[ctx.last_piecewise_kernel()] = seen.get(ctx.last_piecewise_kernel(), 0) + 1
             if os.environ.get("FUZZ_DEBUG"): print("batch", t, mode, "kernel", ctx.last_piecewise_kernel(), "self", ctx.last_piecewise_self(), "geoms", geoms, "tris", tris.size // 3, "redone", ctx.redone_frames(), "flag", hex(ctx.last_piecewise_flag()), flush=True)
             for f, g in enumerate(geoms):
@@ -159,5 +168,5 @@ for t in range(trials):
     if not ok:
         bad += 1
         print("MISMATCH trial", t, "mode", mode, W, H, nx, ny, geom, flush=True)
-print(f"fuzz done: {trials} trials, {bad} mismatches, {overflow} frames through the map-path fallback, batch runs by kernel id {dict(sorted(seen.items()))}, redone frames {ctx.redone_frames()}")
+print(f"fuzz done: {trials} trials, {bad} mismatches, {overflow} frames through the map-path fallback, batch runs by kernel id {dict(sorted(seen.items()))}, span cache {cached}, redone frames {redone + ctx.redone_frames()}")
 sys.exit(1 if bad else 0)

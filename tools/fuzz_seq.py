@@ -113,7 +113,7 @@ for seq in range(n_seq):
                     c.piecewise_set_mesh(sp32, tris, int(ms[0]), int(ms[1]))
                 continue
             if r < 0.3:
-                c.set_option(str(rng.choice(["phase", "patch", "tri_group", "xcc_rotate", "self_spans", "tile", "min_row_groups"])), int(rng.choice([-1, 0, 1, 2])))
+                c.set_option(str(rng.choice(["phase", "patch", "tri_group", "xcc_rotate", "self_spans", "tile", "min_row_groups", "span_cache"])), int(rng.choice([-1, 0, 1, 2])))
                 continue
             k = int(rng.integers(0, 3))
             n = int(rng.integers(1, 4))
@@ -138,7 +138,8 @@ for seq in range(n_seq):
                 continue
             if r < 0.65 or fmap is None or len(imgs) > 1:    # inverse batch (the forward warps take one source image)
                 c.piecewise_set_frames(np.concatenate(frames), geoms, offs)
-                c.warp_inverse_piecewise_frames_device(bufs[k])
+                for _ in range(int(rng.integers(1, 4))):     # one to three warps of the set: the span cache builds on the first or second and is used from the next
+                    c.warp_inverse_piecewise_frames_device(bufs[k])
                 for f, g in enumerate(geoms):
                     w = O.warp_inverse_piecewise(sp32, frames[f], tris, imgs[f % len(imgs)], int(ms[0]), int(ms[1]), *g)
                     want[k][offs[f]:offs[f] + g[2] * g[3] * 4] = w.ravel()

@@ -81,7 +81,8 @@ def main():
                     dt = (time.perf_counter() - t0) / 100 * 1e3
                     tot, n = ctx.kernel_ms_stats()
                 print(json.dumps({"config": config, "F": F, "sources": src, **dict(zip(knobs, combo)), "kernel": ctx.last_piecewise_kernel(),
-                                  "kernel_ms": round(tot / n, 4), "step_ms": round(dt, 4), "same_bytes": same, "redone": ctx.redone_frames()}), flush=True)
+                                  "kernel_ms": round(tot / n, 4), "step_ms": round(dt, 4), "same_bytes": same, "redone": ctx.redone_frames(),
+                                  **({"span_cache": ctx.span_cache_stats()} if not proj and hasattr(hg.lib(), "hg_span_cache_stats") else {})}), flush=True)
                 ctx.close()
 
 if __name__ == "__main__":
