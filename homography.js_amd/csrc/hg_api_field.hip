@@ -1,4 +1,5 @@
-// hg_api_field.hip -- the C ABI, part 6: the source field of the inverse warps (HG_FIELD_INDEX / HG_FIELD_COORDS) and the remaps through it.
+// hg_api_field.hip -- the C ABI, part 6: the source field of the inverse warps (HG_FIELD_INDEX / HG_FIELD_COORDS), the remaps through it and
+// the mosaic of a frame set (hg_mosaic_frames_device).
 // A field call computes where the inverse loops would read, never what: it needs the source's SIZE only, is independent of the sampling
 // mode, and leaves the warp paths' taps (hg_last_*_kernel) and the piecewise layout state as it found them.
 #include "hg_ctx.h"
@@ -476,4 +477,54 @@ extern "C" int hg_remap_aniso_frames_device(hg_ctx *c, const hg_geom *geoms, int
     if (max_aniso < 1 || max_aniso > 16) return fail(c, HG_ERR_INVALID, "hg_remap_aniso_frames_device: max_aniso must lie in 1..16");
     return remap_mip_frames(c, "hg_remap_aniso_frames_device", geoms, n_frames, d_coords, field_offsets, d_planes, W, H, n_planes, plane_stride_bytes,
                             elem, channels, d_out, out_offsets, d_pyr, pyr_stride_bytes, levels, max_aniso);
+}
+
+// ------------------------------------------------------------------------------------------------ the mosaic
+extern "C" int hg_mosaic_frames_device(hg_ctx *c, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
+                                       const void *d_frames, const size_t *frame_offsets, int elem, int channels, int W, int H,
+                                       int mode, float feather, hg_geom canvas, void *d_canvas, float *d_weight)
+{
+    HG_TRY(bind(c));
+    if (n_frames < 0 || n_frames > 65535) return fail(c, HG_ERR_INVALID, "hg_mosaic_frames_device: n_frames must be 0..65535");
+    if (!d_canvas) return fail(c, HG_ERR_INVALID, "hg_mosaic_frames_device: d_canvas is NULL");
+    if (elem != HG_ELEM_F32 && elem != HG_ELEM_U8) return fail(c, HG_ERR_INVALID, "hg_mosaic_frames_device: unknown elem (HG_ELEM_F32 or HG_ELEM_U8)");
+    if (mode != HG_MOSAIC_LAST && mode != HG_MOSAIC_MEAN && mode != HG_MOSAIC_FEATHER)
+        return fail(c, HG_ERR_INVALID, "hg_mosaic_frames_device: unknown mode (HG_MOSAIC_LAST, HG_MOSAIC_MEAN or HG_MOSAIC_FEATHER)");
+    if (channels < 1 || channels > 4 || W < 1 || H < 1) return fail(c, HG_ERR_INVALID, "hg_mosaic_frames_device: channels must be 1..4, W and H >= 1");
+    if (mode == HG_MOSAIC_FEATHER && !(feather > 0.0f)) return fail(c, HG_ERR_INVALID, "hg_mosaic_frames_device: feather must be > 0 (+Inf: uncapped)");
+    if (n_frames > 0 && (!geoms || !d_coords || !d_frames)) return fail(c, HG_ERR_INVALID, "hg_mosaic_frames_device: NULL pointer");
+    const size_t es = elem == HG_ELEM_F32 ? 4 : 1, px = es * (size_t)channels;
+    if (misaligned(d_coords, 8) || misaligned(d_frames, es) || misaligned(d_canvas, es) || misaligned(d_weight, 4))
+        return fail(c, HG_ERR_INVALID, "hg_mosaic_frames_device: d_coords must be aligned to 8 bytes, d_frames / d_canvas to the element size, d_weight to 4");
+    std::vector<FrameDesc> lim;                               // (the window limits of the canvas and of every frame)
+    const size_t zero = 0;
+    HG_TRY(fill_frames(c, lim, &canvas, &zero, 1));
+    if (n_frames > 0) HG_TRY(fill_frames(c, lim, geoms, nullptr, n_frames));
+    const size_t n_quads = ((size_t)n_frames + 3) / 4;
+    std::vector<MosaicFrame4> quads(n_quads, MosaicFrame4{});      // (the fill of the last quad: empty frames)
+    size_t foff = 0, poff = 0;
+    for (int f = 0; f < n_frames; f++) {
+        const hg_geom &g = geoms[f];
+        MosaicFrame &r = quads[(size_t)f / 4].f[f % 4];
+        r = MosaicFrame{field_offsets ? field_offsets[f] : foff, frame_offsets ? frame_offsets[f] : poff, g.x_off, g.y_off, g.obj_w, g.obj_h};
+        if (r.fld_off & 7) return fail(c, HG_ERR_INVALID, "field offsets must be multiples of the field's pixel size (8 bytes)");
+        if (r.pix_off & (es - 1)) return fail(c, HG_ERR_INVALID, "hg_mosaic_frames_device: frame offsets must be multiples of the element size");
+        foff += pad256(frame_px(g.obj_w, g.obj_h) * 8);
+        poff += pad256(frame_px(g.obj_w, g.obj_h) * px);
+    }
+    const size_t n_px = frame_px(canvas.obj_w, canvas.obj_h);
+    if (n_px == 0) return HG_OK;
+    if (!c->pw_pending_out.empty() || !c->fwd_pending.empty()) {
+        HG_TRY(settle_output_conflicts(c, d_canvas, n_px * px, 0));
+        if (d_weight) HG_TRY(settle_output_conflicts(c, d_weight, n_px * 4, 0));
+    }
+    if (n_quads > 0) {
+        static_assert(sizeof(MosaicFrame4) == 128, "the table is staged in 8-byte words");
+        HG_TRY(ensure(c, c->d_mosaic_frames, n_quads));
+        HG_TRY(upload_frame_table(c, c->d_mosaic_frames, quads.data(), sizeof(MosaicFrame4) * n_quads));
+    }
+    launch_mosaic_frames(c->d_mosaic_frames, (int)n_quads, static_cast<const uint8_t *>(d_coords), static_cast<const uint8_t *>(d_frames), W, H, elem, channels,
+                         mode, feather, canvas.x_off, canvas.y_off, canvas.obj_w, canvas.obj_h, static_cast<uint8_t *>(d_canvas), d_weight, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return HG_OK;
 }

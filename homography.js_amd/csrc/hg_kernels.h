@@ -228,6 +228,17 @@ void launch_remap_aniso_frames(const TriRemapFrame *frames, int n_frames, uint32
                                int max_aniso, const uint8_t *coords, const uint8_t *planes, const uint8_t *pyrs, int W, int H, int elem, int channels,
                                uint8_t *out, hipStream_t stream);
 
+// The mosaic (hg_k_mosaic.hip; include/hgwarp.h hg_mosaic_frames_device).  A frame: its HG_FIELD_COORDS field at fld_off and its pixels at
+// pix_off (bytes from the bases the kernel gets), row-major obj_w x obj_h, pixel (i, j) at destination position (x_off + i, y_off + j).
+struct MosaicFrame { uint64_t fld_off, pix_off; int32_t x_off, y_off, obj_w, obj_h; };
+// The table goes four records at a time (one round trip of scalar loads per four window tests): the last quad is filled with empty frames.
+struct MosaicFrame4 { MosaicFrame f[4]; };
+// k_mosaic_frames<element, channels>: every pixel of the canvas window (cx, cy, cw, ch), tightly packed at `canvas`, from the frames that
+// cover it -- mode 0 the last one's pixel, 1 their mean, 2 their mean weighted by the distance to the W x H source's border capped at
+// `feather`; weight (or nullptr): one float per canvas pixel.  n_quads == 0 zeroes the canvas (frames, coords and pixels are not read).
+void launch_mosaic_frames(const MosaicFrame4 *frames, int n_quads, const uint8_t *coords, const uint8_t *pixels, int W, int H, int elem, int channels,
+                          int mode, float feather, int cx, int cy, int cw, int ch, uint8_t *canvas, float *weight, hipStream_t stream);
+
 // Point lists (hg_k_points.hip; include/hgwarp.h hg_points_*): n_sets lists of n_points interleaved (x, y) floats, frame f reads list
 // f % n_sets and writes n_points (x, y) pairs at f * n_points of `out`; an unmapped point is the quiet NaN of HG_FIELD_COORDS in both words.
 // k_geo_points<kind, dir>: dir 0 = to source (mats: the inverse matrices, W x H the source's size: coverage test :1001), dir 1 = to output

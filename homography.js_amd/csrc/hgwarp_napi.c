@@ -36,7 +36,7 @@ static napi_value throw_hg(napi_env env, hg_ctx *ctx, const char *what, int code
 /* d_batch: device buffer the frames of warpInversePiecewiseBatch are produced in (kept between calls, grown as needed) */
 /* n_pts / n_tris: the mesh last set, so that point-set and matrix buffers can be checked before the C ABI reads / fills them */
 /* d_imgs: device buffer of the per-frame sources of setImages() (kept, grown as needed) */
-/* d_remap: device scratch of the remap* functions: the field, the plane and the result (kept, grown as needed) */
+/* d_remap: device scratch of the remap* functions: the field, the plane and the result; of mosaic*: the fields, the canvas, the weights (kept, grown as needed) */
 /* slab: page-locked memory behind ONE external ArrayBuffer whose views are the frames of a batch (see "batches" below) */
 typedef struct { void *ptr; size_t cap; napi_ref ab; } slab_t;
 typedef struct { hg_ctx *ctx; int obj_w, obj_h; void *d_batch; size_t d_batch_cap; size_t n_pts, n_tris; void *d_imgs; size_t d_imgs_cap; slab_t slab[2]; void *d_remap; size_t d_remap_cap; } handle_t;
@@ -1408,6 +1408,96 @@ static napi_value fn_warp_inverse_geometric_batch(napi_env env, napi_callback_in
     return run_batch(env, h, &job, gv, F, 0, a + 5, argc - 5, "warpInverseGeometricBatch");
 }
 
+/* mosaicInverseGeometric(ctx, kind, from, to, geoms, mode, feather, canvas, wantWeight, W, H) /
+ * mosaicInversePiecewise(ctx, dstPoints, geoms, mode, feather, canvas, wantWeight, W, H): the inverse batch of warpInverseGeometricBatch /
+ * warpInversePiecewiseBatch (the bound source(s): setImage / setImages) blended into ONE picture on the device.  The set is staged and warped
+ * into device scratch, its coords fields are exported beside it, hg_sync settles both, hg_mosaic_frames_device (mode: HG_MOSAIC_*; W x H: the
+ * source's size) blends them over `canvas` (Int32Array x, y, width, height) and only the canvas comes down: { data: Uint8ClampedArray
+ * [, weight: Float32Array] }. */
+static napi_value run_mosaic(napi_env env, handle_t *h, const batch_job *job, const int32_t *gv, int F, const napi_value *a, const char *what)
+{
+    const hg_geom *g = (const hg_geom *)gv;
+    int mode, W, H; double feather; size_t nc; bool want_weight = false;
+    if (!get_i32(env, a[0], &mode)) return NULL;
+    if (napi_get_value_double(env, a[1], &feather) != napi_ok) return throw_str(env, "hgwarp: feather must be a number");
+    const int32_t *cv = (const int32_t *)get_typed(env, a[2], napi_int32_array, &nc, "canvas"); if (!cv) return NULL;
+    if (nc != 4) return throw_str(env, "hgwarp: canvas must hold x, y, width, height");
+    if (napi_get_value_bool(env, a[3], &want_weight) != napi_ok) return throw_str(env, "hgwarp: wantWeight must be a boolean");
+    if (!get_i32(env, a[4], &W) || !get_i32(env, a[5], &H)) return NULL;
+    const hg_geom canvas = { cv[0], cv[1], cv[2], cv[3] };
+    const size_t n = (canvas.obj_w > 0 && canvas.obj_h > 0) ? (size_t)canvas.obj_w * (size_t)canvas.obj_h : 0;
+    void *data = NULL, *wdata = NULL;
+    napi_value result, pixels = make_typed(env, napi_uint8_clamped_array, n * 4, 1, &data), weights = NULL;
+    if (!pixels) return NULL;
+    if (want_weight && !(weights = make_typed(env, napi_float32_array, n, 4, &wdata))) return NULL;
+    NAPI_OK(napi_create_object(env, &result));
+    NAPI_OK(napi_set_named_property(env, result, "data", pixels));
+    if (want_weight) NAPI_OK(napi_set_named_property(env, result, "weight", weights));
+    if (!n) return result;
+    size_t *offs = (size_t *)malloc(sizeof(size_t) * 2 * (size_t)F);
+    if (!offs) return throw_str(env, "hgwarp: out of memory (frame offsets)");
+    size_t *foffs = offs + F, total = 0, ftotal = 0;
+    hg_pack_offsets(g, F, offs, &total);
+    int rc = hg_pack_field_offsets(g, F, HG_FIELD_COORDS, foffs, &ftotal);
+    if (rc == HG_OK && total > h->d_batch_cap) {
+        if (h->d_batch) hg_device_free(h->ctx, h->d_batch);
+        h->d_batch = NULL; h->d_batch_cap = 0;
+        rc = hg_device_alloc(h->ctx, total, &h->d_batch);
+        if (rc == HG_OK) h->d_batch_cap = total;
+    }
+    const size_t cb = (n * 4 + 255) & ~(size_t)255, need = ftotal + cb + (want_weight ? n * 4 : 0);
+    if (rc == HG_OK && need > h->d_remap_cap) {
+        if (h->d_remap) hg_device_free(h->ctx, h->d_remap);
+        h->d_remap = NULL; h->d_remap_cap = 0;
+        rc = hg_device_alloc(h->ctx, need, &h->d_remap);
+        if (rc == HG_OK) h->d_remap_cap = need;
+    }
+    uint8_t *d_field = (uint8_t *)h->d_remap, *d_canvas = d_field + ftotal;
+    float *d_weight = want_weight ? (float *)(d_canvas + cb) : NULL;
+    if (rc == HG_OK) rc = job_launch(h, job, g, offs, 0, F, h->d_batch);
+    if (rc == HG_OK) rc = job->type == JOB_PW_INV ? hg_field_inverse_piecewise_frames_device(h->ctx, HG_FIELD_COORDS, foffs, d_field)
+                                                  : hg_field_inverse_geometric_frames_device(h->ctx, HG_FIELD_COORDS, foffs, d_field);
+    if (rc == HG_OK) rc = hg_sync(h->ctx);
+    if (rc == HG_OK) rc = hg_mosaic_frames_device(h->ctx, g, F, d_field, foffs, h->d_batch, offs, HG_ELEM_U8, 4, W, H, mode, (float)feather, canvas, d_canvas, d_weight);
+    if (rc == HG_OK) rc = hg_copy_to_host(h->ctx, data, d_canvas, n * 4);
+    if (rc == HG_OK && want_weight) rc = hg_copy_to_host(h->ctx, wdata, d_weight, n * 4);
+    free(offs);
+    if (rc != HG_OK) return throw_hg(env, h->ctx, what, rc);
+    return result;
+}
+
+static napi_value fn_mosaic_inverse_geometric(napi_env env, napi_callback_info info)
+{
+    napi_value a[11];
+    if (!get_args(env, info, 11, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    size_t nf, nt, ng; batch_job job = { JOB_GEO_INV, 0, NULL, NULL, NULL, NULL, 0, 0, 0 };
+    if (!get_i32(env, a[1], &job.kind)) return NULL;
+    if (job.kind != HG_AFFINE && job.kind != HG_PROJECTIVE) return throw_str(env, "hgwarp: kind must be 0 (affine) or 1 (projective)");
+    job.from = (const float *)get_typed(env, a[2], napi_float32_array, &nf, "fromPoints"); if (!job.from) return NULL;
+    job.to = (const float *)get_typed(env, a[3], napi_float32_array, &nt, "toPoints"); if (!job.to) return NULL;
+    int32_t *gv = (int32_t *)get_typed(env, a[4], napi_int32_array, &ng, "geoms"); if (!gv) return NULL;
+    const int F = (int)(ng / 4);
+    job.per = job.kind == HG_AFFINE ? 6 : 8;
+    if (F <= 0) return throw_str(env, "hgwarp: geoms must hold 4 integers per frame");
+    if (nf < (size_t)F * job.per || nt < (size_t)F * job.per) return throw_str(env, "hgwarp: point sets must hold frames x points x,y pairs");
+    return run_mosaic(env, h, &job, gv, F, a + 5, "mosaicInverseGeometric");
+}
+
+static napi_value fn_mosaic_inverse_piecewise(napi_env env, napi_callback_info info)
+{
+    napi_value a[9];
+    if (!get_args(env, info, 9, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    size_t nd, ng; batch_job job = { JOB_PW_INV, 0, NULL, NULL, NULL, NULL, 0, 0, 0 };
+    job.dst = (const float *)get_typed(env, a[1], napi_float32_array, &nd, "dstPoints"); if (!job.dst) return NULL;
+    int32_t *gv = (int32_t *)get_typed(env, a[2], napi_int32_array, &ng, "geoms"); if (!gv) return NULL;
+    const int F = (int)(ng / 4);
+    if (F <= 0) return throw_str(env, "hgwarp: geoms must hold 4 integers per frame");
+    if (h->n_pts == 0 || nd < (size_t)F * 2 * h->n_pts) return throw_str(env, "hgwarp: dstPoints must hold frames x mesh points x,y pairs (piecewiseSetMesh first)");
+    return run_mosaic(env, h, &job, gv, F, a + 3, "mosaicInversePiecewise");
+}
+
 /* warpForwardPiecewiseBatch(ctx, dstPoints, maxSrcX, maxSrcY, geoms [, ownFrames, images, width, height]): the frames warp() sends down the
  * FORWARD piecewise path (:421-422: output not larger than the input and at least input / 1.2) */
 static napi_value fn_warp_forward_piecewise_batch(napi_env env, napi_callback_info info)
@@ -1671,6 +1761,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "remapForwardGeometric", fn_remap_forward_geometric }, { "remapForwardPiecewise", fn_remap_forward_piecewise },
         { "remapTrilinearInverseGeometric", fn_remap_trilinear_inverse_geometric }, { "remapTrilinearInversePiecewise", fn_remap_trilinear_inverse_piecewise },
         { "remapAnisoInverseGeometric", fn_remap_aniso_inverse_geometric }, { "remapAnisoInversePiecewise", fn_remap_aniso_inverse_piecewise },
+        { "mosaicInverseGeometric", fn_mosaic_inverse_geometric }, { "mosaicInversePiecewise", fn_mosaic_inverse_piecewise },
         { "pointsInverseGeometric", fn_points_inverse_geometric }, { "pointsInversePiecewise", fn_points_inverse_piecewise },
         { "pointsForwardGeometric", fn_points_forward_geometric }, { "pointsForwardPiecewise", fn_points_forward_piecewise },
         { "solveAffineTriangles", fn_solve_affine_triangles }, { "warpInversePiecewiseState", fn_warp_inverse_piecewise_state },

@@ -24,6 +24,8 @@ SAMPLE_NEAREST, SAMPLE_BILINEAR = 0, 1
 FIELD_INDEX, FIELD_COORDS = 0, 1
 # element types of the planes of a bilinear remap (hg_remap_bilinear_frames_device)
 ELEM_F32, ELEM_U8 = 0, 1
+# blend modes of the mosaic (hg_mosaic_frames_device): the last contributor's pixel, the contributors' mean, their feathered mean
+MOSAIC_LAST, MOSAIC_MEAN, MOSAIC_FEATHER = 0, 1, 2
 
 # every symbol include/hgwarp.h declares (tests check that the built library exports all of them)
 EXPORTS = [
@@ -55,6 +57,7 @@ EXPORTS = [
     "hg_points_to_source_geometric_frames_device", "hg_points_to_source_piecewise_frames_device",
     "hg_points_to_output_geometric_batch_device", "hg_points_to_output_piecewise_batch_device",
     "hg_pyramid_levels", "hg_pyramid_layout", "hg_pyramid_build_device", "hg_remap_trilinear_frames_device", "hg_remap_aniso_frames_device",
+    "hg_mosaic_frames_device",
 ]
 
 
@@ -162,6 +165,7 @@ def lib():
         "hg_pyramid_build_device": (i, [vp, vp, i, i, i, sz, i, i, i, vp, sz]),
         "hg_remap_trilinear_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, i, i, i, sz, i, i, vp, C.POINTER(sz), vp, sz, i]),
         "hg_remap_aniso_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, i, i, i, sz, i, i, vp, C.POINTER(sz), vp, sz, i, i]),
+        "hg_mosaic_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, C.POINTER(sz), i, i, i, i, i, C.c_float, Geom, vp, vp]),
         "hg_points_to_source_geometric_frames_device": (i, [vp, vp, i, i, vp]),
         "hg_points_to_source_piecewise_frames_device": (i, [vp, vp, i, i, vp]),
         "hg_points_to_output_geometric_batch_device": (i, [vp, i, f64p, C.POINTER(Geom), i, vp, i, i, vp]),
@@ -745,6 +749,19 @@ class Context:
         self._c(lib().hg_remap_aniso_frames_device(self._h, _geoms(geoms), len(geoms), C.c_void_p(int(d_coords)), fo, C.c_void_p(int(d_planes)),
                                                    int(w), int(h), int(n_planes), int(plane_stride_bytes), int(elem), int(channels),
                                                    C.c_void_p(int(d_out)), oo, C.c_void_p(int(d_pyr)), int(pyr_stride_bytes), int(levels), int(max_aniso)))
+
+    def mosaic_frames_device(self, geoms, d_coords, d_frames, elem, channels, w, h, mode, feather, canvas, d_canvas, d_weight=0,
+                             field_offsets=None, frame_offsets=None):
+        """The frames of a set blended into ONE canvas (asynchronous): frame f's pixels (obj_w x obj_h, `channels` elements of `elem`) lie at
+        (x_off, y_off) of destination space and count where its FIELD_COORDS field is finite.  mode MOSAIC_LAST paints in frame order,
+        MOSAIC_MEAN averages, MOSAIC_FEATHER weights by the distance to the w x h source's border, capped at `feather`.  canvas = (x, y, width,
+        height): d_canvas gets every pixel of it tightly packed, d_weight (0: none) one float32 per pixel.  field_offsets=None: packed as
+        pack_field_offsets does; frame_offsets=None: as pack_plane_offsets(geoms, channels * element size) does."""
+        fo = (C.c_size_t * len(geoms))(*field_offsets) if field_offsets is not None else None
+        po = (C.c_size_t * len(geoms))(*frame_offsets) if frame_offsets is not None else None
+        self._c(lib().hg_mosaic_frames_device(self._h, _geoms(geoms) if len(geoms) else None, len(geoms), C.c_void_p(int(d_coords) or None), fo,
+                                              C.c_void_p(int(d_frames) or None), po, int(elem), int(channels), int(w), int(h), int(mode), float(feather),
+                                              Geom(*[int(v) for v in canvas]), C.c_void_p(int(d_canvas) or None), C.c_void_p(int(d_weight) or None)))
 
     # ---- piecewise
     def piecewise_set_mesh(self, src_pts, tris, min_src_x, min_src_y):

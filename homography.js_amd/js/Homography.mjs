@@ -559,6 +559,99 @@ class Homography {
     }
 
     /**
+     * The loop `for (f) { setDestinyPoints(dst[f]); warp(image_f, false, true); }` with all frames blended into ONE picture on the device
+     * (not part of the reference; include/hgwarp.h, hg_mosaic_frames_device): a panorama, a stack of aligned exposures, a stabilised clip
+     * pasted on one canvas.  The frames are warped into device memory (in the instance's sampling mode), their coordinate fields are
+     * exported beside them, and only the canvas comes down.  Piecewise, affine and projective transforms.
+     *   options.blend     'feather' (default): every frame weighs in by the distance of the pixel's SOURCE position to the border of the
+     *                     source image, in source pixels, capped at options.feather -- seams fade; 'mean': plain average of the frames
+     *                     that cover the pixel; 'last': the last frame that covers it (painter's order);
+     *   options.feather   the cap of the 'feather' weight, a number > 0 (default Infinity: uncapped);
+     *   options.canvas    { x, y, width, height } in the windows' coordinate system (four integers); default: the bounding box of the
+     *                     non-blank windows;
+     *   options.images    the loop warp(image_f): frame f reads images[f % images.length];
+     *   options.pointsAreNormalized   the second argument of every setDestinyPoints;
+     *   options.weight    true: also return the weight plane (the sum of the weights per canvas pixel; 0 where no frame covers).
+     * Every setDestinyPoints(dst[f]) runs on the host exactly as in warpBatch(dstPointSets, {inverse: true}), so the instance ends in the
+     * state that call leaves.  A pixel no frame covers is 0 in every channel; where exactly one frame covers it, its bytes are that frame's.
+     * Returns { data: Uint8ClampedArray, width, height, x, y [, weight: Float32Array] }.  Throws a string for an unknown blend, a bad
+     * feather, a canvas that is not four integers, and for `devices` and `sourcePoints` (the mosaic runs on this instance's own device,
+     * over one source point set).
+     */
+    mosaic(dstPointSets, options = {}) {
+        if (options === null || options === undefined) options = {};
+        const blend = options.blend === undefined ? 'feather' : options.blend;
+        const mode = ['last', 'mean', 'feather'].indexOf(blend);
+        if (mode < 0) throw ("mosaic: options.blend must be 'feather', 'mean' or 'last'");
+        const feather = options.feather === undefined ? Infinity : options.feather;
+        if (typeof feather !== 'number' || !(feather > 0)) throw ("mosaic: options.feather must be a number > 0 (Infinity: uncapped)");
+        let canvas = null;
+        if (options.canvas !== undefined && options.canvas !== null) {
+            const c = options.canvas;
+            canvas = [c.x, c.y, c.width, c.height];
+            if (!canvas.every((v) => Number.isInteger(v) && Math.abs(v) <= 0x7fffffff)) throw ("mosaic: options.canvas must be { x, y, width, height }, four integers");
+        }
+        if (options.devices !== undefined && options.devices !== null) throw ("mosaic: runs on this instance's own device; {devices} is not supported");
+        if (options.sourcePoints !== undefined && options.sourcePoints !== null) throw ("mosaic: one source point set for all frames; {sourcePoints} is not supported");
+        if (!Array.isArray(dstPointSets)) throw ("mosaic: needs an array of destiny point sets");
+        const geometric = this.transform === 'affine' || this.transform === 'projective';
+        if (!geometric && this.transform !== 'piecewiseaffine') throw ("hgwarp: mosaic() needs a transform (set the source points first)");
+        const images = options.images === undefined ? null : options.images;
+        const F = dstPointSets.length, n = geometric ? (this.transform === 'affine' ? 6 : 8) : this._srcPoints.length;
+        const dsts = new Float32Array(F * n), srcPts = new Float32Array(geometric ? F * n : 0), geoms = new Int32Array(F * 4), keep = [];
+        for (let f = 0; f < F; f++) {                            // warpBatch(dstPointSets, {inverse: true})'s host loop, frame for frame
+            this.setDestinyPoints(dstPointSets[f], options.pointsAreNormalized === undefined ? null : options.pointsAreNormalized);
+            if (this._image === null && !images) throw ("warp() must receive an image if it was not setted before through `setImage(img)` or  `setSourcePoints(points, img)`");
+            const [xo, yo, ow, oh] = this._window();
+            if (geometric) {
+                this._alignRanges();                                                                     // :993
+                dsts.set(asF32(this._dstPoints).subarray(0, n), f * n);                                    // inverse: dst -> src (:994)
+                srcPts.set(asF32(this._srcPoints).subarray(0, n), f * n);
+            } else {
+                dsts.set(asF32(this._dstPoints), f * n);
+                checkedMapLength(ow * oh);
+                this._map = { kind: 'inverse', pts: dsts.subarray(f * n, (f + 1) * n), tris: this._triangles, width: ow, height: oh, yOff: yo };
+            }
+            if (!(ow * oh >= 1)) continue;                                                               // :440: a blank frame covers nothing
+            checkedLength(ow * oh * 4);
+            geoms.set([xo, yo, ow, oh], f * 4);
+            keep.push(f);
+        }
+        if (F > 0) this._lastPath = geometric ? '_inverseGeometricWarp' : '_inversePiecewiseAffineWarp';
+        if (canvas === null) {
+            let x0 = Infinity, y0 = Infinity, x1 = -Infinity, y1 = -Infinity;
+            for (const f of keep) {
+                x0 = Math.min(x0, geoms[4 * f]); y0 = Math.min(y0, geoms[4 * f + 1]);
+                x1 = Math.max(x1, geoms[4 * f] + geoms[4 * f + 2]); y1 = Math.max(y1, geoms[4 * f + 1] + geoms[4 * f + 3]);
+            }
+            canvas = keep.length ? [x0, y0, x1 - x0, y1 - y0] : [0, 0, 0, 0];
+        }
+        const [cx, cy] = canvas, cw = Math.max(canvas[2], 0), ch = Math.max(canvas[3], 0);
+        const out = { data: null, width: cw, height: ch, x: cx, y: cy };
+        checkedLength(cw * ch * 4);
+        if (keep.length === 0 || cw * ch === 0) {                // nothing to blend: the zero canvas
+            out.data = new Uint8ClampedArray(cw * ch * 4);
+            if (options.weight === true) out.weight = new Float32Array(cw * ch);
+            return out;
+        }
+        const sub = (arr, w) => { if (keep.length === F) return arr; const o = new arr.constructor(keep.length * w); keep.forEach((f, k) => o.set(arr.subarray(f * w, (f + 1) * w), k * w)); return o; };
+        const tail = [mode, feather, Int32Array.from([cx, cy, cw, ch]), options.weight === true, this._width, this._height];
+        const srcs = images === null ? null : keep.map((f) => images[f % images.length]);
+        let res;
+        if (geometric) {
+            this._uploadSources(srcs);
+            res = this._native.mosaicInverseGeometric(this._ctx, this.transform === 'affine' ? AFFINE : PROJECTIVE, sub(dsts, n), sub(srcPts, n), sub(geoms, 4), ...tail);
+        } else {
+            this._uploadMesh();
+            this._uploadSources(srcs);
+            res = this._native.mosaicInversePiecewise(this._ctx, sub(dsts, n), sub(geoms, 4), ...tail);
+        }
+        out.data = res.data;
+        if (options.weight === true) out.weight = res.weight;
+        return out;
+    }
+
+    /**
      * warpBatch(dst, {sourcePoints: src}): the loop `setSourcePoints(src[f]); setDestinyPoints(dst[f]); warp(image_f)`, frame for frame.  Both
      * setters run on the host exactly as in the loop, so every frame sees the instance as the loop would have left it: the source points of
      * the moment, `_minSrcX / _minSrcY` AS THEY STAND (the reference refreshes them only while its map field is null, :252, :756-758: after

@@ -36,7 +36,7 @@ extern "C" {
 #define HG_VERSION 100          /* 0.1.0 (sampling modes are detected by the presence of hg_set_sampling, source fields by that of hg_field_inverse_geometric,
                                    the forward source fields by that of hg_field_forward_geometric, point lists by that of
                                    hg_points_to_source_geometric_frames_device, mip pyramids and the trilinear remap by that of hg_pyramid_build_device,
-                                   the anisotropic remap by that of hg_remap_aniso_frames_device) */
+                                   the anisotropic remap by that of hg_remap_aniso_frames_device, mosaics by the presence of hg_mosaic_frames_device) */
 
 enum {
     HG_OK = 0,
@@ -436,6 +436,54 @@ int hg_remap_aniso_frames_device(hg_ctx *ctx, const hg_geom *geoms, int n_frames
                                  const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes,
                                  int elem, int channels, void *d_out, const size_t *out_offsets,
                                  const void *d_pyr, size_t pyr_stride_bytes, int levels, int max_aniso);
+/* MOSAIC on the field seam: the frames of a set blended into ONE canvas on the device (a panorama, a stack of aligned exposures, a
+ * stabilised clip pasted on one picture).  Every warp and remap above leaves F frames, each in its own window of destination space;
+ * hg_mosaic_frames_device joins them, so that only the canvas has to come down.
+ *   geoms[f]        ALL FOUR words are read: pixel (i, j) of frame f lies at destination position (x_off + i, y_off + j); obj_w <= 0 or
+ *                   obj_h <= 0 is an empty frame.
+ *   d_coords,       the frames' HG_FIELD_COORDS fields under hg_remap_bilinear_frames_device's rules (NULL offsets: packed as
+ *   field_offsets   hg_pack_field_offsets packs; otherwise multiples of 8; d_coords aligned to 8 bytes).  A frame pixel COVERS iff both words
+ *                   of its coordinate are finite.  Caller-made fields are legal, 1e30 included.
+ *   d_frames,       the frames' pixels: `channels` (1..4) interleaved elements of `elem` (HG_ELEM_F32 / HG_ELEM_U8), row-major obj_w x obj_h.
+ *   frame_offsets   NULL: packed as hg_pack_plane_offsets packs with px_bytes = channels * element size -- with u8 x 4 the default layout of
+ *                   the RGBA warps, whose output is a legal input as it stands; otherwise multiples of the element size.
+ *   W, H            >= 1, the source's size: read only by HG_MOSAIC_FEATHER; no ctx state is consulted.
+ *   canvas          a window of the same destination space.  d_canvas receives obj_w x obj_h pixels of the frames' elem / channels, tightly
+ *                   packed, and EVERY pixel is written.  d_weight may be NULL; otherwise one float32 per canvas pixel (below).
+ * The hg_geom limits apply to canvas and to every frame.  All arithmetic is f32 in the written order, contraction off.  Canvas pixel (i, j):
+ *   1. X = canvas.x_off + i, Y = canvas.y_off + j (64-bit integers).
+ *   2. Frame f is a CANDIDATE iff it is not empty and 0 <= u < obj_w, 0 <= v < obj_h for u = X - x_off_f, v = Y - y_off_f.
+ *   3. A candidate is a CONTRIBUTOR iff the coordinate (sx, sy) at (u, v) of its field covers.  p_c is channel c of its pixel at (u, v),
+ *      widened to float for u8.
+ *   4. No contributor: every channel is 0, the weight is 0.
+ *   5. HG_MOSAIC_LAST: the pixel of the contributor with the largest f, copied bit for bit (painter's order); weight 1.0f.
+ *   6. HG_MOSAIC_MEAN: w_f = 1.0f.  HG_MOSAIC_FEATHER: dx = fminf(sx + 1.0f, (float)W - sx), dy = fminf(sy + 1.0f, (float)H - sy),
+ *      w_f = fmaxf(fminf(fminf(dx, dy), feather), 0x1p-10f) -- under the geometric coverage test 0 <= sx < W "source pixels to the nearest
+ *      border, counting this one", capped at feather (+Inf: uncapped); the floor keeps every contributor's weight positive (piecewise
+ *      frames test against the minSrc bounds, and a coordinate may round to W in f32).
+ *   7. MEAN / FEATHER: in ascending f, acc_c = acc_c + w_f * p_c (multiply, then add) and wsum = wsum + w_f, both from 0.0f.  EXACTLY ONE
+ *      contributor: r_c = p_c of that contributor, bit for bit (no multiply, no divide: a mosaic of frames that do not overlap is a paste).
+ *      Otherwise r_c = acc_c / wsum, an IEEE division.  f32 stores r_c; u8 stores (uint8)min(255, floor(r_c + 0.5f)).  Weight = wsum.
+ * n_frames == 0 is legal: the canvas is zeroed, and geoms / d_coords / d_frames may be NULL.  An empty canvas: HG_OK, nothing is written.
+ * HG_ERR_INVALID: n_frames negative or above 65535; d_canvas NULL; geoms / d_coords / d_frames NULL with n_frames > 0; an unknown elem or
+ * mode; channels outside 1..4; W or H < 1; in HG_MOSAIC_FEATHER mode a feather that is NaN or <= 0 (ignored otherwise); misaligned pointers
+ * or offsets (8 for the coordinates, the element size for frames and canvas, 4 for d_weight); a canvas or a frame beyond the hg_geom limits.
+ * Asynchronous on the ctx stream; the frame table goes up through the page-locked staging ring as the frames remaps' does; queued runs whose
+ * deferred redo could land on d_canvas or d_weight are settled first; frames or fields that are outputs of queued warps are the caller's to
+ * settle (hg_sync), as for every remap.  No effect on hg_last_*, the sampling mode, the plan, what the policy learned or staged frame sets.
+ * Cost (MI355X; EXPERIMENTS.md F.7): u8 x 4 frames with the weight plane, medians of 31 regions.  64 frames with identical 3840 x 2160 windows: MEAN 1.58 ms,
+ * FEATHER 1.59 ms -- 0.54-0.55 x the time of hg_remap_bilinear_frames_device over the same frames and fields, 2.0 x the byte floor (coordinates and
+ * pixels of every candidate once plus the canvas, at 8 TB/s) --, LAST 0.17 ms (it reads one frame).  A strip of 16 frames of 1920 x 1080, each shifted
+ * by 60 % of its width (canvas 19200 x 1080): LAST 0.18, MEAN 0.24, FEATHER 0.24 ms, 0.93-1.24 x that remap, 3.0-4.0 x the floor.  Every block walks the
+ * whole frame table: 4096 frames of 128 x 128 over a 4K canvas take 8.3 / 15.8 / 15.8 ms, 4-8 x that remap -- thousands of small frames are not what
+ * this kernel is laid out for. */
+enum { HG_MOSAIC_LAST = 0, HG_MOSAIC_MEAN = 1, HG_MOSAIC_FEATHER = 2 };
+int hg_mosaic_frames_device(hg_ctx *ctx, const hg_geom *geoms, int n_frames,
+                            const void *d_coords, const size_t *field_offsets,
+                            const void *d_frames, const size_t *frame_offsets,
+                            int elem, int channels, int W, int H,
+                            int mode, float feather,
+                            hg_geom canvas, void *d_canvas, float *d_weight);
 /* The source field of the FORWARD warps (next section): what hg_warp_forward_* would paint, as geometry.  HG_FIELD_INDEX only, hence no
  * format argument: the forward loops copy whole pixels from integer positions, (s % W, s / W) IS the coordinate.  One int32 per output pixel
  * p, row-major obj_w x obj_h: let w be the LAST writer, in the loop's raster order (:919-930 over y < H, x < W; :955-969 over the cells of
