@@ -52,15 +52,22 @@ static int stage_field_frames(hg_ctx *c, const std::vector<FrameDesc> &frames, i
     return upload_frame_table(c, c->d_field_frames, recs->data(), sizeof(FrameDesc) * F);
 }
 
-// ------------------------------------------------------------------------------------------------ affine / projective
-// A queued piecewise run's deferred redo must not land on the field later: runs whose output overlaps [d_field, d_field + extent) are settled first.
-static int settle_field_conflicts(hg_ctx *c, const void *d_field, const std::vector<FrameDesc> &recs, int fmt)
+// A queued run's deferred redo must not land later on what this call writes: queued runs whose output overlaps [ptr, ptr + bytes) are
+// settled first.
+static int settle_pending_on(hg_ctx *c, const void *ptr, size_t bytes)
 {
     if (c->pw_pending_out.empty() && c->fwd_pending.empty()) return HG_OK;
+    return settle_output_conflicts(c, ptr, bytes, 0);
+}
+
+// ------------------------------------------------------------------------------------------------ affine / projective
+// settle_pending_on the extent of a field.
+static int settle_field_conflicts(hg_ctx *c, const void *d_field, const std::vector<FrameDesc> &recs, int fmt)
+{
     size_t extent = 0;
     for (const FrameDesc &d : recs)
         if (frame_px(d.obj_w, d.obj_h)) extent = std::max(extent, (size_t)d.out_off + frame_px(d.obj_w, d.obj_h) * field_px_bytes(fmt));
-    return settle_output_conflicts(c, d_field, extent, 0);
+    return settle_pending_on(c, d_field, extent);
 }
 
 extern "C" int hg_field_inverse_geometric_device(hg_ctx *c, int kind, const double *m, hg_geom geom, int fmt, void *d_field)
@@ -265,7 +272,7 @@ static void assign_remap_blocks(std::vector<RemapFrame> &recs, uint64_t base_px,
 // Settle what could still land on the output, then put the table on the device.
 static int stage_remap_frames(hg_ctx *c, const std::vector<RemapFrame> &recs, const void *d_out, size_t extent)
 {
-    if (!c->pw_pending_out.empty() || !c->fwd_pending.empty()) HG_TRY(settle_output_conflicts(c, d_out, extent, 0));
+    HG_TRY(settle_pending_on(c, d_out, extent));
     HG_TRY(ensure(c, c->d_remap_frames, recs.size()));
     return upload_frame_table(c, c->d_remap_frames, recs.data(), sizeof(RemapFrame) * recs.size());
 }
@@ -294,49 +301,6 @@ extern "C" int hg_remap_index_frames_device(hg_ctx *c, const hg_geom *geoms, int
     HG_TRY(stage_remap_frames(c, recs, d_out, extent));
     launch_remap_index_frames(c->d_remap_frames, n_frames, n_blocks, blk_px, packed, static_cast<const uint8_t *>(d_field),
                               static_cast<const uint8_t *>(d_planes), n_src_px, plane_stride_bytes, pixel_bytes, static_cast<uint8_t *>(d_out), c->stream);
-    HIP_TRY(c, hipGetLastError());
-    return HG_OK;
-}
-
-extern "C" int hg_remap_bilinear_frames_device(hg_ctx *c, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
-                                               const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
-                                               void *d_out, const size_t *out_offsets)
-{
-    HG_TRY(bind(c));
-    if (elem != HG_ELEM_F32 && elem != HG_ELEM_U8) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_frames_device: unknown elem (HG_ELEM_F32 or HG_ELEM_U8)");
-    if (channels < 1 || channels > 4 || W < 1 || H < 1) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_frames_device: channels must be 1..4, W and H >= 1");
-    if (n_planes < 1) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_frames_device: n_planes must be >= 1");
-    if (n_frames < 0 || n_frames > 65535) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_frames_device: n_frames must be 0..65535");
-    if (n_frames == 0) return HG_OK;
-    if (!geoms || !d_coords || !d_planes || !d_out) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_frames_device: NULL pointer");
-    const size_t es = elem == HG_ELEM_F32 ? 4 : 1;
-    if (misaligned(d_coords, 8) || misaligned(d_planes, es) || misaligned(d_out, es) || (plane_stride_bytes & (es - 1)))
-        return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_frames_device: d_coords must be aligned to 8 bytes, d_planes / d_out / plane_stride_bytes to the element size");
-    std::vector<RemapFrame> recs;
-    size_t extent = 0;
-    HG_TRY(remap_frame_table(c, geoms, n_frames, 8, field_offsets, es * (size_t)channels, es, out_offsets, n_planes, &recs, &extent));
-    if (extent == 0) return HG_OK;
-    uint64_t blk_px = 0; uint32_t n_blocks = 0;
-    assign_remap_blocks(recs, 1024, &blk_px, &n_blocks);
-    HG_TRY(stage_remap_frames(c, recs, d_out, extent));
-    launch_remap_bilinear_frames(c->d_remap_frames, RemapFrame{}, n_frames, n_blocks, blk_px, static_cast<const uint8_t *>(d_coords),
-                                 static_cast<const uint8_t *>(d_planes), plane_stride_bytes, W, H, elem, channels, static_cast<uint8_t *>(d_out), c->stream);
-    HIP_TRY(c, hipGetLastError());
-    return HG_OK;
-}
-
-extern "C" int hg_remap_bilinear_u8_device(hg_ctx *c, const void *d_coords, size_t n_px, const uint8_t *d_src, int W, int H, int channels, uint8_t *d_out)
-{
-    HG_TRY(bind(c));
-    if (channels < 1 || channels > 4 || W < 1 || H < 1) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_u8_device: channels must be 1..4, W and H >= 1");
-    if (n_px == 0) return HG_OK;
-    if (!d_coords || !d_src || !d_out) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_u8_device: NULL pointer");
-    if (misaligned(d_coords, 8)) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_u8_device: d_coords must be aligned to 8 bytes");
-    std::vector<RemapFrame> one(1);
-    one[0] = RemapFrame{0, 0, (uint64_t)n_px, 0, 0};
-    uint64_t blk_px = 0; uint32_t n_blocks = 0;
-    assign_remap_blocks(one, 1024, &blk_px, &n_blocks);
-    launch_remap_bilinear_frames(nullptr, one[0], 1, n_blocks, blk_px, static_cast<const uint8_t *>(d_coords), d_src, 0, W, H, HG_ELEM_U8, channels, d_out, c->stream);
     HIP_TRY(c, hipGetLastError());
     return HG_OK;
 }
@@ -413,33 +377,85 @@ extern "C" int hg_pyramid_build_device(hg_ctx *c, const void *d_planes, int W, i
     return HG_OK;
 }
 
-// The trilinear and the anisotropic frames remap (who: the entry point's name): one set of checks, one table, one staging; max_aniso == 0
-// launches the trilinear kernel, 1..16 the anisotropic one.
-static int remap_mip_frames(hg_ctx *c, const std::string &who, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
-                            const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
-                            void *d_out, const size_t *out_offsets, const void *d_pyr, size_t pyr_stride_bytes, int levels, int max_aniso)
+// ------------------------------------------------------------------------------------------------ bilinear, trilinear and anisotropic remaps of whole frame sets
+// What the bilinear, trilinear and anisotropic frames remaps (who: the entry point's name) check of their arguments; lvl (room for 32): the
+// level offsets of one pyramid.  levels == 1: no pyramid, d_pyr is not looked at.  The pointers only matter with frames to remap.
+static int check_remap_frames(hg_ctx *c, const std::string &who, const hg_geom *geoms, int n_frames, const void *d_coords, const void *d_planes, int W, int H,
+                              int n_planes, size_t plane_stride_bytes, int elem, int channels, const void *d_out, const void *d_pyr, size_t pyr_stride_bytes,
+                              int levels, size_t *lvl)
 {
-    HG_TRY(bind(c));
     if (elem != HG_ELEM_F32 && elem != HG_ELEM_U8) return fail(c, HG_ERR_INVALID, who + ": unknown elem (HG_ELEM_F32 or HG_ELEM_U8)");
     if (channels < 1 || channels > 4 || W < 1 || H < 1) return fail(c, HG_ERR_INVALID, who + ": channels must be 1..4, W and H >= 1");
     if (n_planes < 1) return fail(c, HG_ERR_INVALID, who + ": n_planes must be >= 1");
     if (n_frames < 0 || n_frames > 65535) return fail(c, HG_ERR_INVALID, who + ": n_frames must be 0..65535");
-    size_t lvl[32] = {0}, total = 0;
+    size_t total = 0;
     HG_TRY(check_pyramid(c, who.c_str(), W, H, elem, channels, levels, d_pyr, pyr_stride_bytes, false, lvl, &total));
     if (n_frames == 0) return HG_OK;
     if (!geoms || !d_coords || !d_planes || !d_out) return fail(c, HG_ERR_INVALID, who + ": NULL pointer");
     const size_t es = elem == HG_ELEM_F32 ? 4 : 1;
     if (misaligned(d_coords, 8) || misaligned(d_planes, es) || misaligned(d_out, es) || (plane_stride_bytes & (es - 1)))
         return fail(c, HG_ERR_INVALID, who + ": d_coords must be aligned to 8 bytes, d_planes / d_out / plane_stride_bytes to the element size");
+    return HG_OK;
+}
+
+extern "C" int hg_remap_bilinear_frames_device(hg_ctx *c, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
+                                               const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
+                                               void *d_out, const size_t *out_offsets)
+{
+    HG_TRY(bind(c));
+    size_t lvl[32];
+    HG_TRY(check_remap_frames(c, "hg_remap_bilinear_frames_device", geoms, n_frames, d_coords, d_planes, W, H, n_planes, plane_stride_bytes, elem, channels,
+                              d_out, nullptr, 0, 1, lvl));
+    if (n_frames == 0) return HG_OK;
+    const size_t es = elem == HG_ELEM_F32 ? 4 : 1;
     std::vector<RemapFrame> recs;
     size_t extent = 0;
     HG_TRY(remap_frame_table(c, geoms, n_frames, 8, field_offsets, es * (size_t)channels, es, out_offsets, n_planes, &recs, &extent));
     if (extent == 0) return HG_OK;
     uint64_t blk_px = 0; uint32_t n_blocks = 0;
     assign_remap_blocks(recs, 1024, &blk_px, &n_blocks);
-    if (!c->pw_pending_out.empty() || !c->fwd_pending.empty()) HG_TRY(settle_output_conflicts(c, d_out, extent, 0));
+    HG_TRY(stage_remap_frames(c, recs, d_out, extent));
+    launch_remap_bilinear_frames(c->d_remap_frames, RemapFrame{}, n_frames, n_blocks, blk_px, static_cast<const uint8_t *>(d_coords),
+                                 static_cast<const uint8_t *>(d_planes), plane_stride_bytes, W, H, elem, channels, static_cast<uint8_t *>(d_out), c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return HG_OK;
+}
+
+extern "C" int hg_remap_bilinear_u8_device(hg_ctx *c, const void *d_coords, size_t n_px, const uint8_t *d_src, int W, int H, int channels, uint8_t *d_out)
+{
+    HG_TRY(bind(c));
+    if (channels < 1 || channels > 4 || W < 1 || H < 1) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_u8_device: channels must be 1..4, W and H >= 1");
+    if (n_px == 0) return HG_OK;
+    if (!d_coords || !d_src || !d_out) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_u8_device: NULL pointer");
+    if (misaligned(d_coords, 8)) return fail(c, HG_ERR_INVALID, "hg_remap_bilinear_u8_device: d_coords must be aligned to 8 bytes");
+    std::vector<RemapFrame> one(1);
+    one[0] = RemapFrame{0, 0, (uint64_t)n_px, 0, 0};
+    uint64_t blk_px = 0; uint32_t n_blocks = 0;
+    assign_remap_blocks(one, 1024, &blk_px, &n_blocks);
+    launch_remap_bilinear_frames(nullptr, one[0], 1, n_blocks, blk_px, static_cast<const uint8_t *>(d_coords), d_src, 0, W, H, HG_ELEM_U8, channels, d_out, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return HG_OK;
+}
+
+// The trilinear and the anisotropic frames remap (who: the entry point's name): one table, one staging; max_aniso == 0 launches the
+// trilinear kernel, 1..16 the anisotropic one.
+static int remap_mip_frames(hg_ctx *c, const std::string &who, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
+                            const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
+                            void *d_out, const size_t *out_offsets, const void *d_pyr, size_t pyr_stride_bytes, int levels, int max_aniso)
+{
+    HG_TRY(bind(c));
+    size_t lvl[32] = {0};
+    HG_TRY(check_remap_frames(c, who, geoms, n_frames, d_coords, d_planes, W, H, n_planes, plane_stride_bytes, elem, channels, d_out, d_pyr, pyr_stride_bytes, levels, lvl));
+    if (n_frames == 0) return HG_OK;
+    const size_t es = elem == HG_ELEM_F32 ? 4 : 1;
+    std::vector<RemapFrame> recs;
+    size_t extent = 0;
+    HG_TRY(remap_frame_table(c, geoms, n_frames, 8, field_offsets, es * (size_t)channels, es, out_offsets, n_planes, &recs, &extent));
+    if (extent == 0) return HG_OK;
+    uint64_t blk_px = 0; uint32_t n_blocks = 0;
+    assign_remap_blocks(recs, 1024, &blk_px, &n_blocks);
+    HG_TRY(settle_pending_on(c, d_out, extent));
     // the device table: 32 level offsets, then one record per frame
-    static_assert(sizeof(TriRemapFrame) % 8 == 0, "the table is staged in 8-byte words");
     const size_t words = 32 + (size_t)n_frames * (sizeof(TriRemapFrame) / 8);
     HG_TRY(ensure(c, c->d_tri_table, words));
     StageSlot *gs = nullptr;
@@ -514,12 +530,9 @@ extern "C" int hg_mosaic_frames_device(hg_ctx *c, const hg_geom *geoms, int n_fr
     }
     const size_t n_px = frame_px(canvas.obj_w, canvas.obj_h);
     if (n_px == 0) return HG_OK;
-    if (!c->pw_pending_out.empty() || !c->fwd_pending.empty()) {
-        HG_TRY(settle_output_conflicts(c, d_canvas, n_px * px, 0));
-        if (d_weight) HG_TRY(settle_output_conflicts(c, d_weight, n_px * 4, 0));
-    }
+    HG_TRY(settle_pending_on(c, d_canvas, n_px * px));
+    if (d_weight) HG_TRY(settle_pending_on(c, d_weight, n_px * 4));
     if (n_quads > 0) {
-        static_assert(sizeof(MosaicFrame4) == 128, "the table is staged in 8-byte words");
         HG_TRY(ensure(c, c->d_mosaic_frames, n_quads));
         HG_TRY(upload_frame_table(c, c->d_mosaic_frames, quads.data(), sizeof(MosaicFrame4) * n_quads));
     }

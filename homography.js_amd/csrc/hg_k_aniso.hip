@@ -3,28 +3,15 @@
 // field's two steps, from the finer level(s) the shorter step allows, and averages them.
 // Hand-written HIP for gfx950 (MI355X / CDNA4), wave64.  All arithmetic is f32 in the written order (contraction off); the numpy model of
 // tests/hgtest/aniso.py follows it operation by operation.  Design notes: DESIGN.md §4.9, figures: EXPERIMENTS.md F.6.
-// The per-level helpers (pyr_size, pyr_px_load, tri_frame_of, tri_tap, tri_finite, tri_sample) are hg_k_pyramid.hip's own text; its kernel
-// templates are not instantiated here and its launchers are left out.
-#define HG_PYRAMID_NO_LAUNCHERS 1
-#include "hg_k_pyramid.hip"
+#ifdef __HIPCC__
+#include "hg_dev.h"
+#endif
+#include "hg_remap_dev.h"
 
 namespace hg {
 
-// The step from s to the first of the two neighbour candidates that exists and is finite (tri_step2's choice): *dx, *dy and the squared
-// length; all three 0 without one.
-__device__ __forceinline__ float aniso_step(const float2 *__restrict__ cf, float2 s, bool has_a, uint64_t ia, bool has_b, uint64_t ib, float *dx, float *dy)
-{
-    float2 n = make_float2(INFINITY, INFINITY);
-    if (has_a) n = cf[ia];
-    if (!tri_finite(n) && has_b) n = cf[ib];
-    *dx = 0.0f; *dy = 0.0f;
-    if (!tri_finite(n)) return 0.0f;
-    *dx = n.x - s.x; *dy = n.y - s.y;
-    return *dx * *dx + *dy * *dy;
-}
-
-// tri_sample_level with ONE tri_sample body for every level: the level's start, size and coordinate are selected first.  lvl_off[0] is 0
-// and level 0's start is the plane; pyr is only offset, never read, for k == 0.
+// k_remap_trilinear_frames' tri_sample_level with ONE tri_sample body for every level: the level's start, size and coordinate are selected
+// first.  lvl_off[0] is 0 and level 0's start is the plane; pyr is only offset, never read, for k == 0.
 template <typename E, int C>
 __device__ __forceinline__ void aniso_sample_level(const E *__restrict__ plane, bool plane_wide, const uint8_t *__restrict__ pyr, bool pyr_wide,
                                                    const uint64_t *__restrict__ lvl_off, int W, int H, int k, float2 s, float r[C])
@@ -49,7 +36,7 @@ __global__ __launch_bounds__(256) void k_remap_aniso_frames(const TriRemapFrame 
                                                             const uint8_t *__restrict__ coords, const uint8_t *__restrict__ planes,
                                                             const uint8_t *__restrict__ pyrs, int W, int H, uint8_t *__restrict__ out)
 {
-    const TriRemapFrame fr = tri_frame_of(frames, n_frames, blockIdx.x);
+    const TriRemapFrame fr = remap_frame_of(frames, n_frames, blockIdx.x);
     const float2 *__restrict__ cf = reinterpret_cast<const float2 *>(coords + fr.fld_off);
     const E *__restrict__ src = reinterpret_cast<const E *>(planes + fr.plane_off);
     const uint8_t *__restrict__ pyr = pyrs + fr.pyr_off;           // (never read with levels == 1)
@@ -63,17 +50,16 @@ __global__ __launch_bounds__(256) void k_remap_aniso_frames(const TriRemapFrame 
     const uint64_t ow = fr.obj_w, oh = fr.obj_h;
     const uint64_t row0 = p0 / ow, col0 = p0 - row0 * ow;        // (uniform over the block)
     for (uint64_t i = p0 + threadIdx.x; i < end; i += 256) {
-        const uint64_t t = col0 + (i - p0);
-        const uint64_t dj = (t >> 32) ? t / ow : (uint64_t)((uint32_t)t / (uint32_t)ow);
-        const uint64_t px = t - dj * ow, py = row0 + dj;
+        uint64_t px, py;
+        remap_px_xy(col0 + (i - p0), ow, row0, &px, &py);
         const float2 s = cf[i];
         float v[C];
 #pragma unroll
         for (int ch = 0; ch < C; ch++) v[ch] = 0.0f;
-        if (tri_finite(s)) {
+        if (remap_finite(s)) {
             float hx, hy, vx, vy;
-            const float qh = aniso_step(cf, s, px + 1 < ow, i + 1, px >= 1, i - 1, &hx, &hy);
-            const float qv = aniso_step(cf, s, py + 1 < oh, i + ow, py >= 1, i - ow, &vx, &vy);
+            const float qh = remap_step(cf, s, px + 1 < ow, i + 1, px >= 1, i - 1, &hx, &hy);
+            const float qv = remap_step(cf, s, py + 1 < oh, i + ow, py >= 1, i - ow, &vx, &vy);
             const bool hmaj = qh >= qv;
             const float mx = hmaj ? hx : vx, my = hmaj ? hy : vy, qM = hmaj ? qh : qv, qm = hmaj ? qv : qh;
             int N = 1;
@@ -83,14 +69,9 @@ __global__ __launch_bounds__(256) void k_remap_aniso_frames(const TriRemapFrame 
             }
             const float fN = (float)N;
             const float q = N > 1 ? qM / (float)(N * N) : qM;      // (x / 1.0f is x)
-            int k = 0, nl = 1;
-            float w = 0.0f;                                        // weight of level k + 1
-            if (q > 1.0f) {
-                const uint32_t qb = __float_as_uint(q);
-                k = ((int)(qb >> 23) - 127) >> 1;                  // (+Inf: 64)
-                if (k >= levels - 1) k = levels - 1;
-                else { w = (__uint_as_float(qb - ((uint32_t)(2 * k) << 23)) - 1.0f) * 0.33333334f; nl = 2; }      // ldexpf(q, -2k), exact
-            }
+            const RemapLevels lv = remap_levels(q, levels);
+            const int k = lv.k, nl = lv.n;
+            const float w = lv.w;                                  // weight of level k + 1
             for (int p = 0; p < N; p++) {
                 float2 pr = s;
                 if (N > 1) {
@@ -113,35 +94,22 @@ __global__ __launch_bounds__(256) void k_remap_aniso_frames(const TriRemapFrame 
                 for (int ch = 0; ch < C; ch++) v[ch] = v[ch] / fN;
             }
         }
-        if constexpr (sizeof(E) == 4) {
-#pragma unroll
-            for (int ch = 0; ch < C; ch++) o[i * C + ch] = v[ch];
-        } else {
-            uint32_t b[C];
-#pragma unroll
-            for (int ch = 0; ch < C; ch++) b[ch] = (uint32_t)fminf(255.0f, floorf(v[ch] + 0.5f));
-            if constexpr (C == 4) {
-                if (out_wide) { *reinterpret_cast<uint32_t *>(o + i * 4) = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24); continue; }
-            } else if constexpr (C == 2) {
-                if (out_wide) { *reinterpret_cast<uint16_t *>(o + i * 2) = (uint16_t)(b[0] | (b[1] << 8)); continue; }
-            }
-#pragma unroll
-            for (int ch = 0; ch < C; ch++) o[i * C + ch] = (uint8_t)b[ch];
-        }
+        remap_px_store<E, C>(o, i, out_wide, v);
     }
 }
 
 // ------------------------------------------------------------------------------------------------ launcher
+#ifdef __HIPCC__
 void launch_remap_aniso_frames(const TriRemapFrame *frames, int n_frames, uint32_t n_blocks, uint64_t blk_px, const uint64_t *lvl_off, int levels,
                                int max_aniso, const uint8_t *coords, const uint8_t *planes, const uint8_t *pyrs, int W, int H, int elem, int channels,
                                uint8_t *out, hipStream_t stream)
 {
     if (n_frames <= 0 || n_blocks == 0) return;
-#define HG_AF(E, C) hipLaunchKernelGGL((k_remap_aniso_frames<E, C>), dim3(n_blocks), dim3(256), 0, stream, frames, n_frames, blk_px, lvl_off, levels, max_aniso, coords, planes, pyrs, W, H, out)
-#define HG_AE(E) switch (channels) { case 1: HG_AF(E, 1); break; case 2: HG_AF(E, 2); break; case 3: HG_AF(E, 3); break; case 4: HG_AF(E, 4); break; default: break; }
-    if (elem == 0) HG_AE(float) else HG_AE(uint8_t)
-#undef HG_AE
-#undef HG_AF
+    for_elem_channels(elem, channels, [&](auto e, auto c) {
+        hipLaunchKernelGGL((k_remap_aniso_frames<decltype(e), decltype(c)::value>), dim3(n_blocks), dim3(256), 0, stream, frames, n_frames, blk_px, lvl_off, levels,
+                           max_aniso, coords, planes, pyrs, W, H, out);
+    });
 }
+#endif
 
 } // namespace hg

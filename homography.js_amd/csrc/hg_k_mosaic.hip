@@ -2,9 +2,10 @@
 // k_mosaic_frames gathers, per canvas pixel, the pixels of every frame whose window holds it and whose HG_FIELD_COORDS field covers it.
 // Hand-written HIP for gfx950 (MI355X / CDNA4), wave64.  All arithmetic is f32 in the written order (contraction off); the numpy model of
 // tests/hgtest/mosaic.py follows it operation by operation.  Design notes: DESIGN.md §4.11, figures: EXPERIMENTS.md F.7.
-// tri_finite and pyr_px_load are hg_k_pyramid.hip's own text; its kernel templates are not instantiated here and its launchers are left out.
-#define HG_PYRAMID_NO_LAUNCHERS 1
-#include "hg_k_pyramid.hip"
+#ifdef __HIPCC__
+#include "hg_dev.h"
+#endif
+#include "hg_remap_dev.h"
 
 namespace hg {
 
@@ -20,16 +21,16 @@ __device__ __forceinline__ bool mos_hits(const MosaicFrame &fr, int64_t X0, int6
 // start is aligned for it (uniform per frame).
 template <typename E, int C>
 __device__ __forceinline__ bool mos_fetch(const MosaicFrame &fr, int64_t X, int64_t Y, const uint8_t *__restrict__ coords,
-                                          const uint8_t *__restrict__ pixels, float2 *s, std::conditional_t<sizeof(E) == 1, uint32_t, float> p[C])
+                                          const uint8_t *__restrict__ pixels, float2 *s, remap_px_t<E> p[C])
 {
     const int64_t u = X - fr.x_off, v = Y - fr.y_off;
     if (u < 0 || u >= fr.obj_w || v < 0 || v >= fr.obj_h) return false;
     const uint64_t k = (uint64_t)v * (uint64_t)fr.obj_w + (uint64_t)u;       // (< 2^31)
     *s = reinterpret_cast<const float2 *>(coords + fr.fld_off)[k];
-    if (!tri_finite(*s)) return false;
+    if (!remap_finite(*s)) return false;
     const E *__restrict__ px = reinterpret_cast<const E *>(pixels + fr.pix_off);
     const bool wide = sizeof(E) == 1 && (C == 2 || C == 4) && !(reinterpret_cast<uintptr_t>(px) & (C - 1));
-    pyr_px_load<E, C>(px + k * C, wide, p);
+    remap_px_load<E, C>(px + k * C, wide, p);
     return true;
 }
 
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(256) void k_mosaic_frames(const MosaicFrame4 *__res
                                                        int cx, int cy, int cw, int ch, uint32_t tiles_x, uint8_t *__restrict__ canvas,
                                                        float *__restrict__ weight)
 {
-    using V = std::conditional_t<sizeof(E) == 1, uint32_t, float>;
+    using V = remap_px_t<E>;
     const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
     const int64_t i0 = (int64_t)tx * 64, j0 = (int64_t)ty * 4;
     const int64_t X0 = cx + i0, Y0 = cy + j0, X1 = min(X0 + 64, (int64_t)cx + cw), Y1 = min(Y0 + 4, (int64_t)cy + ch);
@@ -122,17 +123,18 @@ __global__ __launch_bounds__(256) void k_mosaic_frames(const MosaicFrame4 *__res
 }
 
 // ------------------------------------------------------------------------------------------------ launcher
+#ifdef __HIPCC__
 void launch_mosaic_frames(const MosaicFrame4 *frames, int n_quads, const uint8_t *coords, const uint8_t *pixels, int W, int H, int elem, int channels,
                           int mode, float feather, int cx, int cy, int cw, int ch, uint8_t *canvas, float *weight, hipStream_t stream)
 {
     if (cw <= 0 || ch <= 0) return;
     const uint32_t tiles_x = (uint32_t)(((int64_t)cw + 63) / 64);
     const uint64_t n_blocks = (uint64_t)tiles_x * (uint64_t)(((int64_t)ch + 3) / 4);      // (< 2^31 for a canvas of at most 2^31 pixels)
-#define HG_MF(E, C) hipLaunchKernelGGL((k_mosaic_frames<E, C>), dim3((uint32_t)n_blocks), dim3(64, 4), 0, stream, frames, n_quads, coords, pixels, W, H, mode, feather, cx, cy, cw, ch, tiles_x, canvas, weight)
-#define HG_ME(E) switch (channels) { case 1: HG_MF(E, 1); break; case 2: HG_MF(E, 2); break; case 3: HG_MF(E, 3); break; case 4: HG_MF(E, 4); break; default: break; }
-    if (elem == 0) HG_ME(float) else HG_ME(uint8_t)
-#undef HG_ME
-#undef HG_MF
+    for_elem_channels(elem, channels, [&](auto e, auto c) {
+        hipLaunchKernelGGL((k_mosaic_frames<decltype(e), decltype(c)::value>), dim3((uint32_t)n_blocks), dim3(64, 4), 0, stream, frames, n_quads, coords, pixels, W, H,
+                           mode, feather, cx, cy, cw, ch, tiles_x, canvas, weight);
+    });
 }
+#endif
 
 } // namespace hg

@@ -3,33 +3,12 @@
 // through a HG_FIELD_COORDS field, choosing the level(s) of every pixel from the field's own footprint.
 // Hand-written HIP for gfx950 (MI355X / CDNA4), wave64.  All arithmetic is f32 in the written order (contraction off); the numpy model of
 // tests/hgtest/trilinear.py follows it operation by operation.  Design notes: DESIGN.md §4.9, figures: EXPERIMENTS.md F.5.
+#ifdef __HIPCC__
 #include "hg_dev.h"
+#endif
+#include "hg_remap_dev.h"
 
 namespace hg {
-
-// Size of level k of a pyramid over n pixels: (n + 1) >> 1 applied k times = ceil(n / 2^k); k <= 31, n < 2^31.
-__device__ __forceinline__ int pyr_size(int n, int k)
-{
-    return (int)(((uint32_t)n + ((1u << k) - 1u)) >> k);
-}
-
-// The C channels of one pixel as 32-bit values (floats, or bytes widened to uint32).  Bytes with 2 or 4 channels: one 2- / 4-byte load
-// where the level's start is aligned for it (wide) -- the rule of k_remap_bilinear_frames' remap_tap_load.
-template <typename E, int C>
-__device__ __forceinline__ void pyr_px_load(const E *__restrict__ p, bool wide, std::conditional_t<sizeof(E) == 1, uint32_t, float> t[C])
-{
-    if constexpr (sizeof(E) == 1 && (C == 2 || C == 4)) {
-        if (wide) {
-            uint32_t w;
-            if constexpr (C == 4) w = *reinterpret_cast<const uint32_t *>(p); else w = *reinterpret_cast<const uint16_t *>(p);
-#pragma unroll
-            for (int ch = 0; ch < C; ch++) t[ch] = (w >> (8 * ch)) & 255u;
-            return;
-        }
-    }
-#pragma unroll
-    for (int ch = 0; ch < C; ch++) t[ch] = p[ch];
-}
 
 // ------------------------------------------------------------------------------------------------ one pyramid level
 // Level k (Wd x Hd) from level k - 1 (Ws x Hs) of every plane: pixel (x, y) averages the pixels at columns min(2x, Ws-1), min(2x+1, Ws-1)
@@ -39,7 +18,7 @@ template <typename E, int C>
 __global__ __launch_bounds__(256) void k_pyr_down(const uint8_t *__restrict__ src, size_t src_stride, int Ws, int Hs, uint8_t *__restrict__ dst,
                                                   size_t dst_stride, int Wd, int Hd, int n_planes)
 {
-    using V = std::conditional_t<sizeof(E) == 1, uint32_t, float>;
+    using V = remap_px_t<E>;
     constexpr bool kBytes = sizeof(E) == 1 && (C == 2 || C == 4);
     const int x = blockIdx.x * 64 + threadIdx.x;
     if (x >= Wd) return;
@@ -52,10 +31,10 @@ __global__ __launch_bounds__(256) void k_pyr_down(const uint8_t *__restrict__ sr
         for (int64_t y = (int64_t)blockIdx.y * 4 + threadIdx.y; y < Hd; y += (int64_t)gridDim.y * 4) {
             const int64_t r0 = min(2 * y, (int64_t)Hs - 1) * Ws, r1 = min(2 * y + 1, (int64_t)Hs - 1) * Ws;
             V a[C], b[C], c[C], e[C];
-            pyr_px_load<E, C>(s + (r0 + c0) * C, s_wide, a);
-            pyr_px_load<E, C>(s + (r0 + c1) * C, s_wide, b);
-            pyr_px_load<E, C>(s + (r1 + c0) * C, s_wide, c);
-            pyr_px_load<E, C>(s + (r1 + c1) * C, s_wide, e);
+            remap_px_load<E, C>(s + (r0 + c0) * C, s_wide, a);
+            remap_px_load<E, C>(s + (r0 + c1) * C, s_wide, b);
+            remap_px_load<E, C>(s + (r1 + c0) * C, s_wide, c);
+            remap_px_load<E, C>(s + (r1 + c1) * C, s_wide, e);
             E *__restrict__ o = d + (y * Wd + x) * C;
             if constexpr (sizeof(E) == 4) {
 #pragma unroll
@@ -77,54 +56,6 @@ __global__ __launch_bounds__(256) void k_pyr_down(const uint8_t *__restrict__ sr
 }
 
 // ------------------------------------------------------------------------------------------------ the trilinear remap
-// Block b belongs to the last frame whose blk0 <= b: k_remap_bilinear_frames' search, over the records of this kernel.
-__device__ __forceinline__ TriRemapFrame tri_frame_of(const TriRemapFrame *__restrict__ frames, int n, uint32_t b)
-{
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (frames[mid].blk0 <= b) lo = mid; else hi = mid;
-    }
-    return frames[lo];
-}
-
-// Column / row of a tap: clamp(v, 0, n - 1) for an integer-valued finite float v, clamped in float first (k_remap_bilinear_f32's remap_tap).
-__device__ __forceinline__ int tri_tap(float v, int n)
-{
-    return min((int)fminf(fmaxf(v, 0.0f), 2147483520.0f), n - 1);
-}
-
-__device__ __forceinline__ bool tri_finite(float2 s) { return fabsf(s.x) < INFINITY && fabsf(s.y) < INFINITY; }      // (NaN compares false)
-
-// Squared distance in source pixels from s to the first of the two neighbour candidates that exists and is finite; 0 without one.
-__device__ __forceinline__ float tri_step2(const float2 *__restrict__ cf, float2 s, bool has_a, uint64_t ia, bool has_b, uint64_t ib)
-{
-    float2 n = make_float2(INFINITY, INFINITY);
-    if (has_a) n = cf[ia];
-    if (!tri_finite(n) && has_b) n = cf[ib];
-    if (!tri_finite(n)) return 0.0f;
-    const float dx = n.x - s.x, dy = n.y - s.y;
-    return dx * dx + dy * dy;
-}
-
-// k_remap_bilinear_frames' pixel on one level: W x H pixels at src, the coordinate (u, v) finite.
-template <typename E, int C>
-__device__ __forceinline__ void tri_sample(const E *__restrict__ src, bool wide, int W, int H, float u, float v, float r[C])
-{
-    using V = std::conditional_t<sizeof(E) == 1, uint32_t, float>;
-    const float x0 = floorf(u), y0 = floorf(v);
-    const float fx = u - x0, fy = v - y0, gx = 1.0f - fx, gy = 1.0f - fy;
-    const int64_t c0 = tri_tap(x0, W), c1 = tri_tap(x0 + 1.0f, W);
-    const int64_t r0 = (int64_t)tri_tap(y0, H) * W, r1 = (int64_t)tri_tap(y0 + 1.0f, H) * W;
-    V p00[C], p01[C], p10[C], p11[C];
-    pyr_px_load<E, C>(src + (r0 + c0) * C, wide, p00);
-    pyr_px_load<E, C>(src + (r0 + c1) * C, wide, p01);
-    pyr_px_load<E, C>(src + (r1 + c0) * C, wide, p10);
-    pyr_px_load<E, C>(src + (r1 + c1) * C, wide, p11);
-#pragma unroll
-    for (int ch = 0; ch < C; ch++) r[ch] = ((float)p00[ch] * gx + (float)p01[ch] * fx) * gy + ((float)p10[ch] * gx + (float)p11[ch] * fx) * fy;
-}
-
 // The coordinate of (sx, sy) on level k >= 1: ((s + 0.5) * 2^-k) - 0.5, and that level of the pyramid at pyr.
 template <typename E, int C>
 __device__ __forceinline__ void tri_sample_level(const E *__restrict__ plane, bool plane_wide, const uint8_t *__restrict__ pyr, bool pyr_wide,
@@ -148,7 +79,7 @@ __global__ __launch_bounds__(256) void k_remap_trilinear_frames(const TriRemapFr
                                                                 const uint8_t *__restrict__ coords, const uint8_t *__restrict__ planes,
                                                                 const uint8_t *__restrict__ pyrs, int W, int H, uint8_t *__restrict__ out)
 {
-    const TriRemapFrame fr = tri_frame_of(frames, n_frames, blockIdx.x);
+    const TriRemapFrame fr = remap_frame_of(frames, n_frames, blockIdx.x);
     const float2 *__restrict__ cf = reinterpret_cast<const float2 *>(coords + fr.fld_off);
     const E *__restrict__ src = reinterpret_cast<const E *>(planes + fr.plane_off);
     const uint8_t *__restrict__ pyr = pyrs + fr.pyr_off;           // (never read with levels == 1)
@@ -162,63 +93,42 @@ __global__ __launch_bounds__(256) void k_remap_trilinear_frames(const TriRemapFr
     const uint64_t ow = fr.obj_w, oh = fr.obj_h;
     const uint64_t row0 = p0 / ow, col0 = p0 - row0 * ow;        // (uniform over the block)
     for (uint64_t i = p0 + threadIdx.x; i < end; i += 256) {
-        const uint64_t t = col0 + (i - p0);
-        const uint64_t dj = (t >> 32) ? t / ow : (uint64_t)((uint32_t)t / (uint32_t)ow);
-        const uint64_t px = t - dj * ow, py = row0 + dj;
+        uint64_t px, py;
+        remap_px_xy(col0 + (i - p0), ow, row0, &px, &py);
         const float2 s = cf[i];
         float v[C];
 #pragma unroll
         for (int ch = 0; ch < C; ch++) v[ch] = 0.0f;
-        if (tri_finite(s)) {
-            const float qh = tri_step2(cf, s, px + 1 < ow, i + 1, px >= 1, i - 1);
-            const float qv = tri_step2(cf, s, py + 1 < oh, i + ow, py >= 1, i - ow);
+        if (remap_finite(s)) {
+            float dx, dy;                                          // (the steps' directions: the anisotropic kernel's business)
+            const float qh = remap_step(cf, s, px + 1 < ow, i + 1, px >= 1, i - 1, &dx, &dy);
+            const float qv = remap_step(cf, s, py + 1 < oh, i + ow, py >= 1, i - ow, &dx, &dy);
             const float q = fmaxf(qh, qv);
-            int k = 0;
-            float w = 0.0f;                                        // weight of level k + 1
-            if (q > 1.0f) {
-                const uint32_t qb = __float_as_uint(q);
-                k = ((int)(qb >> 23) - 127) >> 1;                  // (+Inf: 64)
-                if (k >= levels - 1) k = levels - 1;
-                else w = (__uint_as_float(qb - ((uint32_t)(2 * k) << 23)) - 1.0f) * 0.33333334f;      // ldexpf(q, -2k), exact
-            }
+            const RemapLevels lv = remap_levels(q, levels);
+            const int k = lv.k;
+            const float w = lv.w;                                  // weight of level k + 1
             tri_sample_level<E, C>(src, src_wide, pyr, pyr_wide, lvl_off, W, H, k, s, v);
-            if (q > 1.0f && k < levels - 1) {
+            if (lv.n == 2) {
                 float hi[C];
                 tri_sample_level<E, C>(src, src_wide, pyr, pyr_wide, lvl_off, W, H, k + 1, s, hi);
 #pragma unroll
                 for (int ch = 0; ch < C; ch++) v[ch] = v[ch] + (hi[ch] - v[ch]) * w;
             }
         }
-        if constexpr (sizeof(E) == 4) {
-#pragma unroll
-            for (int ch = 0; ch < C; ch++) o[i * C + ch] = v[ch];
-        } else {
-            uint32_t b[C];
-#pragma unroll
-            for (int ch = 0; ch < C; ch++) b[ch] = (uint32_t)fminf(255.0f, floorf(v[ch] + 0.5f));
-            if constexpr (C == 4) {
-                if (out_wide) { *reinterpret_cast<uint32_t *>(o + i * 4) = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24); continue; }
-            } else if constexpr (C == 2) {
-                if (out_wide) { *reinterpret_cast<uint16_t *>(o + i * 2) = (uint16_t)(b[0] | (b[1] << 8)); continue; }
-            }
-#pragma unroll
-            for (int ch = 0; ch < C; ch++) o[i * C + ch] = (uint8_t)b[ch];
-        }
+        remap_px_store<E, C>(o, i, out_wide, v);
     }
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
-#ifndef HG_PYRAMID_NO_LAUNCHERS      // (hg_k_aniso.hip includes this file for the per-level helpers above: one text for both kernels)
+#ifdef __HIPCC__
 void launch_pyr_down(const uint8_t *src, size_t src_stride, int Ws, int Hs, uint8_t *dst, size_t dst_stride, int Wd, int Hd, int n_planes,
                      int elem, int channels, hipStream_t stream)
 {
     if (n_planes <= 0 || Wd <= 0 || Hd <= 0) return;
     const dim3 grid((unsigned)((Wd + 63) / 64), (unsigned)std::min((Hd + 3) / 4, 65535), (unsigned)std::min(n_planes, 65535));
-#define HG_PD(E, C) hipLaunchKernelGGL((k_pyr_down<E, C>), grid, dim3(64, 4), 0, stream, src, src_stride, Ws, Hs, dst, dst_stride, Wd, Hd, n_planes)
-#define HG_PE(E) switch (channels) { case 1: HG_PD(E, 1); break; case 2: HG_PD(E, 2); break; case 3: HG_PD(E, 3); break; case 4: HG_PD(E, 4); break; default: break; }
-    if (elem == 0) HG_PE(float) else HG_PE(uint8_t)
-#undef HG_PE
-#undef HG_PD
+    for_elem_channels(elem, channels, [&](auto e, auto c) {
+        hipLaunchKernelGGL((k_pyr_down<decltype(e), decltype(c)::value>), grid, dim3(64, 4), 0, stream, src, src_stride, Ws, Hs, dst, dst_stride, Wd, Hd, n_planes);
+    });
 }
 
 void launch_remap_trilinear_frames(const TriRemapFrame *frames, int n_frames, uint32_t n_blocks, uint64_t blk_px, const uint64_t *lvl_off, int levels,
@@ -226,11 +136,10 @@ void launch_remap_trilinear_frames(const TriRemapFrame *frames, int n_frames, ui
                                    uint8_t *out, hipStream_t stream)
 {
     if (n_frames <= 0 || n_blocks == 0) return;
-#define HG_TF(E, C) hipLaunchKernelGGL((k_remap_trilinear_frames<E, C>), dim3(n_blocks), dim3(256), 0, stream, frames, n_frames, blk_px, lvl_off, levels, coords, planes, pyrs, W, H, out)
-#define HG_TE(E) switch (channels) { case 1: HG_TF(E, 1); break; case 2: HG_TF(E, 2); break; case 3: HG_TF(E, 3); break; case 4: HG_TF(E, 4); break; default: break; }
-    if (elem == 0) HG_TE(float) else HG_TE(uint8_t)
-#undef HG_TE
-#undef HG_TF
+    for_elem_channels(elem, channels, [&](auto e, auto c) {
+        hipLaunchKernelGGL((k_remap_trilinear_frames<decltype(e), decltype(c)::value>), dim3(n_blocks), dim3(256), 0, stream, frames, n_frames, blk_px, lvl_off, levels,
+                           coords, planes, pyrs, W, H, out);
+    });
 }
 #endif
 

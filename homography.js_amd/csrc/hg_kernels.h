@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "hg_math.h"
 #include "hg_span_cache.h"
+#include "hg_remap_records.h"
 
 namespace hg {
 
@@ -191,13 +192,11 @@ void launch_pw_field(const PwMesh &mesh, const PwFrames &fr, int fmt, uint8_t *f
 // k_field_from_map: the redo of ONE flagged frame (index f) from the map launch_map_build materialised.
 void launch_field_from_map(const PwMesh &mesh, const PwFrames &fr, int f, const FrameDesc &fd, const int32_t *map32, int fmt, uint8_t *field,
                            hipStream_t stream);
+// The remaps through a field (hg_k_remap.hip).
 // k_remap_index<pixel_bytes>: out[i] = 0 <= field[i] < n_src ? src[field[i]] : 0; k_remap_bilinear_f32<channels>: four clamped taps per pixel.
 void launch_remap_index(const int32_t *field, size_t n, const void *src, size_t n_src, int pixel_bytes, void *out, hipStream_t stream);
 void launch_remap_bilinear_f32(const float *coords, size_t n, const float *src, int W, int H, int channels, float *out, hipStream_t stream);
-// The remaps of a whole frame set in one launch.  A frame is a flat list of n_px pixels: its field at fld_off and its output at out_off
-// (bytes), read from plane `plane`; blocks [blk0, next frame's blk0) of the grid cover it, blk_px pixels each (a multiple of 1024), so the
-// frame of a block is found by a binary search over blk0 -- empty frames own no block.
-struct RemapFrame { uint64_t fld_off, out_off, n_px; uint32_t blk0, plane; };
+// The remaps of a whole frame set in one launch (hg_k_remap.hip; the records: hg_remap_records.h).
 // k_remap_index_frames<pixel_bytes, packed>: per pixel k_remap_index.  packed: a lane takes 4 consecutive pixels of its frame -- one 16-byte
 // field load, four gathers, one store of 4 * pixel_bytes -- in frames whose field and output starts are aligned for it, and one pixel per
 // lane elsewhere.  packed is honoured for the pixel sizes remap_index_packs() names; the others always take one pixel per lane.
@@ -215,9 +214,6 @@ void launch_remap_bilinear_frames(const RemapFrame *frames, const RemapFrame &on
 // other planes lie src_stride / dst_stride bytes apart.
 void launch_pyr_down(const uint8_t *src, size_t src_stride, int Ws, int Hs, uint8_t *dst, size_t dst_stride, int Wd, int Hd, int n_planes,
                      int elem, int channels, hipStream_t stream);
-// A frame of the trilinear remap: RemapFrame's flat list read as obj_w x obj_h, its plane at plane_off and that plane's pyramid at pyr_off
-// (bytes from the bases the kernel gets).
-struct TriRemapFrame { uint64_t fld_off, out_off, n_px, plane_off, pyr_off; uint32_t blk0, obj_w, obj_h, pad; };
 // k_remap_trilinear_frames<element, channels>: lvl_off = `levels` byte offsets on the device (hg_pyramid_layout's; entry 0 unused).
 void launch_remap_trilinear_frames(const TriRemapFrame *frames, int n_frames, uint32_t n_blocks, uint64_t blk_px, const uint64_t *lvl_off, int levels,
                                    const uint8_t *coords, const uint8_t *planes, const uint8_t *pyrs, int W, int H, int elem, int channels,
@@ -228,11 +224,7 @@ void launch_remap_aniso_frames(const TriRemapFrame *frames, int n_frames, uint32
                                int max_aniso, const uint8_t *coords, const uint8_t *planes, const uint8_t *pyrs, int W, int H, int elem, int channels,
                                uint8_t *out, hipStream_t stream);
 
-// The mosaic (hg_k_mosaic.hip; include/hgwarp.h hg_mosaic_frames_device).  A frame: its HG_FIELD_COORDS field at fld_off and its pixels at
-// pix_off (bytes from the bases the kernel gets), row-major obj_w x obj_h, pixel (i, j) at destination position (x_off + i, y_off + j).
-struct MosaicFrame { uint64_t fld_off, pix_off; int32_t x_off, y_off, obj_w, obj_h; };
-// The table goes four records at a time (one round trip of scalar loads per four window tests): the last quad is filled with empty frames.
-struct MosaicFrame4 { MosaicFrame f[4]; };
+// The mosaic (hg_k_mosaic.hip; include/hgwarp.h hg_mosaic_frames_device).
 // k_mosaic_frames<element, channels>: every pixel of the canvas window (cx, cy, cw, ch), tightly packed at `canvas`, from the frames that
 // cover it -- mode 0 the last one's pixel, 1 their mean, 2 their mean weighted by the distance to the W x H source's border capped at
 // `feather`; weight (or nullptr): one float per canvas pixel.  n_quads == 0 zeroes the canvas (frames, coords and pixels are not read).

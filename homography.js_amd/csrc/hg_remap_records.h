@@ -1,0 +1,26 @@
+// hg_remap_records.h -- the device records of the remap family (hg_k_remap.hip, hg_k_pyramid.hip, hg_k_aniso.hip, hg_k_mosaic.hip): what
+// the host stages and the kernels read.  Plain C++ over <cstdint>, no HIP types: the host checks of tests/cpp include this very file.
+#pragma once
+#include <cstdint>
+
+namespace hg {
+
+// The remaps of a whole frame set in one launch.  A frame is a flat list of n_px pixels: its field at fld_off and its output at out_off
+// (bytes), read from plane `plane`; blocks [blk0, next frame's blk0) of the grid cover it, blk_px pixels each (a multiple of 1024), so the
+// frame of a block is found by a binary search over blk0 -- empty frames own no block.
+struct RemapFrame { uint64_t fld_off, out_off, n_px; uint32_t blk0, plane; };
+static_assert(sizeof(RemapFrame) == 32, "the table is staged in 8-byte words and passed by value");
+
+// A frame of the trilinear remap: RemapFrame's flat list read as obj_w x obj_h, its plane at plane_off and that plane's pyramid at pyr_off
+// (bytes from the bases the kernel gets).
+struct TriRemapFrame { uint64_t fld_off, out_off, n_px, plane_off, pyr_off; uint32_t blk0, obj_w, obj_h, pad; };
+static_assert(sizeof(TriRemapFrame) % 8 == 0, "the table is staged in 8-byte words");
+
+// The mosaic (hg_k_mosaic.hip; include/hgwarp.h hg_mosaic_frames_device).  A frame: its HG_FIELD_COORDS field at fld_off and its pixels at
+// pix_off (bytes from the bases the kernel gets), row-major obj_w x obj_h, pixel (i, j) at destination position (x_off + i, y_off + j).
+struct MosaicFrame { uint64_t fld_off, pix_off; int32_t x_off, y_off, obj_w, obj_h; };
+// The table goes four records at a time (one round trip of scalar loads per four window tests): the last quad is filled with empty frames.
+struct MosaicFrame4 { MosaicFrame f[4]; };
+static_assert(sizeof(MosaicFrame4) == 128, "the table is staged in 8-byte words");
+
+} // namespace hg

@@ -1,38 +1,15 @@
 // aniso_check.cpp -- host check of the anisotropic remap kernel (k_remap_aniso_frames; hg_k_aniso.hip) over pyramids built by k_pyr_down.
-// The SOURCE TEXT of both (pyramid_kernels.inc and aniso_kernels.inc: cut out of hg_k_pyramid.hip and hg_k_aniso.hip by
-// tests/test_aniso_cpu.py, everything between each namespace's opening and the launchers) is compiled for the CPU behind a thread-index
-// shim and run block by block, thread by thread, under AddressSanitizer + UndefinedBehaviorSanitizer on exact-size heap buffers: any byte
-// read or written outside a field, a plane, a pyramid, the tables or the output is reported, and so is a misaligned wide load or store.
+// Both kernel files themselves are compiled for the CPU behind the thread-index shim (hip_host_shim.h) and run block by block, thread by
+// thread, under AddressSanitizer + UndefinedBehaviorSanitizer on exact-size heap buffers: any byte read or written outside a field, a
+// plane, a pyramid, the tables or the output is reported, and so is a misaligned wide load or store.
 // The case comes from a file the test writes and the pyramids and the output go back into a file, which the test compares with the numpy
 // model -- x86 f32 arithmetic with contraction off is the GPU's.  A stand-alone program: host code only, no GPU.
 //   in:  int32 elem, C, W, H, levels, n_planes, n_frames, plane_front, max_aniso, pad;  uint64 blk_px, plane_stride, pyr_front, pyr_stride, fld_bytes, out_bytes;
 //        n_frames x { int32 obj_w, obj_h; uint64 fld_off, out_off };  the field buffer;  the planes (n_planes x plane_stride bytes)
 //   out: the pyramid allocation behind pyr_front (n_planes x pyr_stride bytes), then the output buffer (filled with 0xA5 before the run)
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <cmath>
-#include <vector>
-#include <algorithm>
-#include <type_traits>
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-#define __launch_bounds__(x)
-struct dim3s { unsigned x, y, z; };
-static thread_local dim3s threadIdx, blockIdx, gridDim;
-struct float2 { float x, y; };
-static inline float2 make_float2(float a, float b) { return {a, b}; }
-static inline float __uint_as_float(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-static inline uint32_t __float_as_uint(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-using std::min; using std::max;
-namespace hg {
-struct TriRemapFrame { uint64_t fld_off, out_off, n_px, plane_off, pyr_off; uint32_t blk0, obj_w, obj_h, pad; };
-#include "pyramid_kernels.inc"
-#include "aniso_kernels.inc"
-}
+#include "hip_host_shim.h"
+#include "hg_k_pyramid.hip"
+#include "hg_k_aniso.hip"
 using namespace hg;
 
 template <typename T> static T get(FILE *f) { T v; if (fread(&v, sizeof v, 1, f) != 1) { printf("short input\n"); exit(2); } return v; }

@@ -1,40 +1,13 @@
 // mosaic_check.cpp -- host check of the mosaic kernel (k_mosaic_frames; hg_k_mosaic.hip).
-// The SOURCE TEXT of the kernel (mosaic_kernels.inc) and of the helpers it takes from hg_k_pyramid.hip (pyramid_kernels.inc), both cut out
-// by tests/test_mosaic_cpu.py -- everything between each namespace's opening and the launchers --, is compiled for the CPU behind a
-// thread-index shim and run block by block, thread by thread, under AddressSanitizer + UndefinedBehaviorSanitizer on exact-size heap
-// buffers: any byte read or written outside a field, a frame, the table, the canvas or the weight plane is reported, and so is a
+// The kernel file itself is compiled for the CPU behind the thread-index shim (hip_host_shim.h) and run block by block, thread by thread,
+// under AddressSanitizer + UndefinedBehaviorSanitizer on exact-size heap buffers: any byte read or written outside a field, a frame, the table, the canvas or the weight plane is reported, and so is a
 // misaligned wide load or store.  The case comes from a file the test writes and the canvas and the weights go back into a file, which the
 // test compares with the numpy model -- x86 f32 arithmetic with contraction off is the GPU's.  A stand-alone program: host code only, no GPU.
 //   in:  int32 elem, C, W, H, mode, n_frames, cx, cy, cw, ch, pix_front, canvas_front, has_weight, feather (the float's bits);
 //        uint64 fld_bytes, pix_bytes;  n_frames x { int32 x_off, y_off, obj_w, obj_h; uint64 fld_off, pix_off };  the field buffer;  the pixel buffer
 //   out: the canvas (cw x ch pixels), then the weight plane if has_weight (both filled with 0xA5 before the run)
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <cmath>
-#include <vector>
-#include <algorithm>
-#include <type_traits>
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-#define __launch_bounds__(x)
-struct dim3s { unsigned x, y, z; };
-static thread_local dim3s threadIdx, blockIdx, gridDim;
-struct float2 { float x, y; };
-static inline float2 make_float2(float a, float b) { return {a, b}; }
-static inline float __uint_as_float(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-static inline uint32_t __float_as_uint(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-using std::min; using std::max;
-namespace hg {
-struct TriRemapFrame { uint64_t fld_off, out_off, n_px, plane_off, pyr_off; uint32_t blk0, obj_w, obj_h, pad; };
-struct MosaicFrame { uint64_t fld_off, pix_off; int32_t x_off, y_off, obj_w, obj_h; };
-struct MosaicFrame4 { MosaicFrame f[4]; };
-#include "pyramid_kernels.inc"
-#include "mosaic_kernels.inc"
-}
+#include "hip_host_shim.h"
+#include "hg_k_mosaic.hip"
 using namespace hg;
 
 template <typename T> static T get(FILE *f) { T v; if (fread(&v, sizeof v, 1, f) != 1) { printf("short input\n"); exit(2); } return v; }

@@ -1,34 +1,12 @@
-// remap_frames_check.cpp -- host check of the frame-set remap kernels (k_remap_index_frames, k_remap_bilinear_frames; hg_k_field.hip).
-// Their SOURCE TEXT (remap_kernels.inc: cut out of hg_k_field.hip by tests/test_remap_frames_cpu.py, from remap_tap and from the
-// "remaps of whole frame sets" section) is compiled for the CPU behind a thread-index shim and run block by block, thread by thread,
+// remap_frames_check.cpp -- host check of the frame-set remap kernels (k_remap_index_frames, k_remap_bilinear_frames; hg_k_remap.hip).
+// The kernel file itself is compiled for the CPU behind the thread-index shim (hip_host_shim.h) and run block by block, thread by thread,
 // under AddressSanitizer + UndefinedBehaviorSanitizer: exact-size heap buffers, so any byte read or written outside a field, a plane, the
 // frame table or the output is reported, and so is a misaligned wide load or store.  Results are compared with a plain scalar loop on the
 // ragged frame set of tests/test_gpu_remap_frames.py (pixel counts 1, 3, 4, 5, 0, 255, 257, 1021, 60000), packed and deliberately misaligned
 // layouts, 1 and 3 planes, both kernel forms, all pixel sizes / element types / channel counts, and 65535 one-pixel frames.
 // A stand-alone program: host code only, no GPU.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <cmath>
-#include <vector>
-#include <algorithm>
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-#define __launch_bounds__(x)
-struct dim3s { unsigned x, y, z; };
-static thread_local dim3s threadIdx, blockIdx;
-struct uint2 { uint32_t x, y; }; struct uint4 { uint32_t x, y, z, w; }; struct float2 { float x, y; };
-static inline uint2 make_uint2(uint32_t a, uint32_t b) { return {a, b}; }
-static inline uint4 make_uint4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return {a, b, c, d}; }
-using std::min; using std::max;
-namespace hg {
-typedef int v4i __attribute__((ext_vector_type(4)));
-struct RemapFrame { uint64_t fld_off, out_off, n_px; uint32_t blk0, plane; };
-#include "remap_kernels.inc"
-}
+#include "hip_host_shim.h"
+#include "hg_k_remap.hip"
 using namespace hg;
 
 static uint32_t rng_s = 12345;

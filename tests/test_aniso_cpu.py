@@ -318,25 +318,18 @@ def test_a_constant_u8_plane_stays_constant():
 
 # ------------------------------------------------------------------------------------------------ the kernel's text on the host
 CLANGXX = next((p for p in ("/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++", shutil.which("clang++")) if p and os.path.exists(p)), None)
-MARK = "// ------------------------------------------------------------------------------------------------ launcher"
+CSRC = os.path.join(ROOT, "homography.js_amd", "csrc")
 
 
 @pytest.mark.skipif(CLANGXX is None, reason="clang++ (ROCm's) not available")
 def test_kernel_source_text_on_the_host_under_sanitizers(tmp_path):
-    """tests/cpp/aniso_check.cpp: the text of k_remap_aniso_frames, cut out of hg_k_aniso.hip, over the helpers and k_pyr_down cut out of
-    hg_k_pyramid.hip, compiled for the CPU behind a thread-index shim and run under ASan + UBSan on exact-size buffers -- no byte outside a
+    """tests/cpp/aniso_check.cpp: k_remap_aniso_frames over k_pyr_down's pyramids -- hg_k_aniso.hip and hg_k_pyramid.hip themselves --,
+    compiled for the CPU behind a thread-index shim and run under ASan + UBSan on exact-size buffers -- no byte outside a
     buffer is touched, whatever the alignment -- and what it computes is the model's, bit for bit: every element type and channel count,
     misaligned planes, pyramids, offsets and strides, the frames of the model test.  A stand-alone program; nothing is loaded into Python."""
-    csrc = os.path.join(ROOT, "homography.js_amd", "csrc")
-    pyr_src = open(os.path.join(csrc, "hg_k_pyramid.hip")).read()
-    (tmp_path / "pyramid_kernels.inc").write_text(pyr_src[pyr_src.index("// Size of level k of a pyramid"):pyr_src.index(MARK)])
-    src = open(os.path.join(csrc, "hg_k_aniso.hip")).read()
-    body = src[src.index("// The step from s to the first"):src.index(MARK)]
-    assert "k_remap_aniso_frames" in body and "aniso_sample_level" in body and "#include" not in body
-    (tmp_path / "aniso_kernels.inc").write_text(body)
     exe = str(tmp_path / "aniso_check")
     subprocess.run([CLANGXX, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-Wno-everything", "-I", str(tmp_path), os.path.join(ROOT, "tests", "cpp", "aniso_check.cpp"), "-o", exe],
+                    "-Wno-everything", "-I", CSRC, os.path.join(ROOT, "tests", "cpp", "aniso_check.cpp"), "-o", exe],
                    check=True, cwd=str(tmp_path), timeout=600)
     frames = [co for _, co in _model_frames()]
     geoms = [(0, 0, co.shape[1], co.shape[0]) for co in frames] + [(0, 0, 0, 3)]

@@ -237,25 +237,17 @@ def test_a_constant_u8_value_stays_constant_over_any_overlap():
 
 # ------------------------------------------------------------------------------------------------ the kernel's text on the host
 CLANGXX = next((p for p in ("/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++", shutil.which("clang++")) if p and os.path.exists(p)), None)
-MARK = "// ------------------------------------------------------------------------------------------------ launcher"
+CSRC = os.path.join(ROOT, "homography.js_amd", "csrc")
 
 
 @pytest.mark.skipif(CLANGXX is None, reason="clang++ (ROCm's) not available")
 def test_kernel_source_text_on_the_host_under_sanitizers(tmp_path):
-    """tests/cpp/mosaic_check.cpp: the text of k_mosaic_frames, cut out of hg_k_mosaic.hip, over the helpers cut out of hg_k_pyramid.hip,
-    compiled for the CPU behind a thread-index shim and run under ASan + UBSan on exact-size buffers -- no byte outside a buffer is
+    """tests/cpp/mosaic_check.cpp: k_mosaic_frames -- hg_k_mosaic.hip itself --, compiled for the CPU behind a thread-index shim and run under ASan + UBSan on exact-size buffers -- no byte outside a buffer is
     touched, whatever the alignment -- and what it computes is the model's, bit for bit: every element type, channel count and mode,
     misaligned frames and canvases, no frames at all.  A stand-alone program; nothing is loaded into Python."""
-    csrc = os.path.join(ROOT, "homography.js_amd", "csrc")
-    pyr_src = open(os.path.join(csrc, "hg_k_pyramid.hip")).read()
-    (tmp_path / "pyramid_kernels.inc").write_text(pyr_src[pyr_src.index("// Size of level k of a pyramid"):pyr_src.index(MARK)])
-    src = open(os.path.join(csrc, "hg_k_mosaic.hip")).read()
-    body = src[src.index("// Does the window of"):src.index(MARK)]
-    assert "k_mosaic_frames" in body and "mos_fetch" in body and "#include" not in body
-    (tmp_path / "mosaic_kernels.inc").write_text(body)
     exe = str(tmp_path / "mosaic_check")
     subprocess.run([CLANGXX, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-Wno-everything", "-I", str(tmp_path), os.path.join(ROOT, "tests", "cpp", "mosaic_check.cpp"), "-o", exe],
+                    "-Wno-everything", "-I", CSRC, os.path.join(ROOT, "tests", "cpp", "mosaic_check.cpp"), "-o", exe],
                    check=True, cwd=str(tmp_path), timeout=600)
     cases = [(elem, ch, mode, mis, wt, len(MODEL_GEOMS)) for elem in (HG.ELEM_U8, HG.ELEM_F32) for ch in (1, 2, 3, 4)
              for mode, mis, wt in ((MM.LAST, 1, 0), (MM.MEAN, 0, 1), (MM.FEATHER, 1, 1))]

@@ -124,22 +124,17 @@ def test_js_class_remap_over_the_recording_mock_addon():
     assert res["checks"] >= 150
 
 
+CSRC = os.path.join(ROOT, "homography.js_amd", "csrc")
 CLANGXX = next((p for p in ("/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++", shutil.which("clang++")) if p and os.path.exists(p)), None)
 
 
 @pytest.mark.skipif(CLANGXX is None, reason="clang++ (ROCm's) not available")
 def test_kernel_source_text_on_the_host_under_sanitizers(tmp_path):
-    """tests/cpp/remap_frames_check.cpp: the text of the frame-set remap kernels, cut out of hg_k_field.hip, compiled for the CPU behind a
-    thread-index shim and run under ASan + UBSan against a scalar loop -- no byte outside a buffer is touched, whatever the alignment."""
-    src = open(os.path.join(ROOT, "homography.js_amd", "csrc", "hg_k_field.hip")).read()
-    tap = src[src.index("// Column / row of a tap"):src.index("// Bilinear remap of C interleaved f32 channels")]
-    body = src[src.index("// ------------------------------------------------------------------------------------------------ remaps of whole frame sets"):
-               src.index("// ------------------------------------------------------------------------------------------------ launchers")]
-    assert "k_remap_index_frames" in body and "k_remap_bilinear_frames" in body and "remap_tap" in tap
-    (tmp_path / "remap_kernels.inc").write_text(tap + body)
+    """tests/cpp/remap_frames_check.cpp: the frame-set remap kernels -- hg_k_remap.hip itself --, compiled for the CPU behind a thread-index
+    shim and run under ASan + UBSan against a scalar loop -- no byte outside a buffer is touched, whatever the alignment."""
     exe = str(tmp_path / "remap_frames_check")
     subprocess.run([CLANGXX, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-Wno-everything", "-I", str(tmp_path), os.path.join(ROOT, "tests", "cpp", "remap_frames_check.cpp"), "-o", exe],
+                    "-Wno-everything", "-I", CSRC, os.path.join(ROOT, "tests", "cpp", "remap_frames_check.cpp"), "-o", exe],
                    check=True, cwd=str(tmp_path), timeout=600)
     p = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0 and "host check passed" in p.stdout, (p.stdout + p.stderr)[-3000:]

@@ -332,22 +332,19 @@ def test_the_checkerboard_shrunk_8x_is_grey_where_bilinear_aliases():
 
 
 # ------------------------------------------------------------------------------------------------ the kernels' text on the host
+CSRC = os.path.join(ROOT, "homography.js_amd", "csrc")
 CLANGXX = next((p for p in ("/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++", shutil.which("clang++")) if p and os.path.exists(p)), None)
 
 
 @pytest.mark.skipif(CLANGXX is None, reason="clang++ (ROCm's) not available")
 def test_kernel_source_text_on_the_host_under_sanitizers(tmp_path):
-    """tests/cpp/trilinear_check.cpp: the text of k_pyr_down and k_remap_trilinear_frames, cut out of hg_k_pyramid.hip, compiled for the CPU
+    """tests/cpp/trilinear_check.cpp: k_pyr_down and k_remap_trilinear_frames -- hg_k_pyramid.hip itself --, compiled for the CPU
     behind a thread-index shim and run under ASan + UBSan on exact-size buffers -- no byte outside a buffer is touched, whatever the
     alignment -- and what it computes is the model's, bit for bit: every element type and channel count, misaligned planes, pyramids,
     offsets and strides, the frames of the model test (every level, NaN / infinite / huge coordinates, 1 x N and N x 1)."""
-    src = open(os.path.join(ROOT, "homography.js_amd", "csrc", "hg_k_pyramid.hip")).read()
-    body = src[src.index("// Size of level k of a pyramid"):src.index("// ------------------------------------------------------------------------------------------------ launchers")]
-    assert "k_pyr_down" in body and "k_remap_trilinear_frames" in body
-    (tmp_path / "pyramid_kernels.inc").write_text(body)
     exe = str(tmp_path / "trilinear_check")
     subprocess.run([CLANGXX, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-Wno-everything", "-I", str(tmp_path), os.path.join(ROOT, "tests", "cpp", "trilinear_check.cpp"), "-o", exe],
+                    "-Wno-everything", "-I", CSRC, os.path.join(ROOT, "tests", "cpp", "trilinear_check.cpp"), "-o", exe],
                    check=True, cwd=str(tmp_path), timeout=600)
     frames = [co for _, co in _model_frames()]
     frames[0] = frames[0][:40]
