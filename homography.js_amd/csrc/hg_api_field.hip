@@ -377,8 +377,8 @@ extern "C" int hg_pyramid_build_device(hg_ctx *c, const void *d_planes, int W, i
     return HG_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ bilinear, trilinear and anisotropic remaps of whole frame sets
-// What the bilinear, trilinear and anisotropic frames remaps (who: the entry point's name) check of their arguments; lvl (room for 32): the
+// ------------------------------------------------------------------------------------------------ bilinear, bicubic, trilinear and anisotropic remaps of whole frame sets
+// What the bilinear, bicubic, trilinear and anisotropic frames remaps (who: the entry point's name) check of their arguments; lvl (room for 32): the
 // level offsets of one pyramid.  levels == 1: no pyramid, d_pyr is not looked at.  The pointers only matter with frames to remap.
 static int check_remap_frames(hg_ctx *c, const std::string &who, const hg_geom *geoms, int n_frames, const void *d_coords, const void *d_planes, int W, int H,
                               int n_planes, size_t plane_stride_bytes, int elem, int channels, const void *d_out, const void *d_pyr, size_t pyr_stride_bytes,
@@ -398,14 +398,15 @@ static int check_remap_frames(hg_ctx *c, const std::string &who, const hg_geom *
     return HG_OK;
 }
 
-extern "C" int hg_remap_bilinear_frames_device(hg_ctx *c, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
-                                               const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
-                                               void *d_out, const size_t *out_offsets)
+// The bilinear and the bicubic frames remap (who: the entry point's name): one check, one table, one staging; cubic == nullptr launches the
+// bilinear kernel, otherwise the bicubic one with those coefficients.
+static int remap_flat_frames(hg_ctx *c, const char *who, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
+                             const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
+                             void *d_out, const size_t *out_offsets, const CubicCoef *cubic)
 {
     HG_TRY(bind(c));
     size_t lvl[32];
-    HG_TRY(check_remap_frames(c, "hg_remap_bilinear_frames_device", geoms, n_frames, d_coords, d_planes, W, H, n_planes, plane_stride_bytes, elem, channels,
-                              d_out, nullptr, 0, 1, lvl));
+    HG_TRY(check_remap_frames(c, who, geoms, n_frames, d_coords, d_planes, W, H, n_planes, plane_stride_bytes, elem, channels, d_out, nullptr, 0, 1, lvl));
     if (n_frames == 0) return HG_OK;
     const size_t es = elem == HG_ELEM_F32 ? 4 : 1;
     std::vector<RemapFrame> recs;
@@ -415,10 +416,45 @@ extern "C" int hg_remap_bilinear_frames_device(hg_ctx *c, const hg_geom *geoms, 
     uint64_t blk_px = 0; uint32_t n_blocks = 0;
     assign_remap_blocks(recs, 1024, &blk_px, &n_blocks);
     HG_TRY(stage_remap_frames(c, recs, d_out, extent));
-    launch_remap_bilinear_frames(c->d_remap_frames, RemapFrame{}, n_frames, n_blocks, blk_px, static_cast<const uint8_t *>(d_coords),
-                                 static_cast<const uint8_t *>(d_planes), plane_stride_bytes, W, H, elem, channels, static_cast<uint8_t *>(d_out), c->stream);
+    const uint8_t *co = static_cast<const uint8_t *>(d_coords), *pl = static_cast<const uint8_t *>(d_planes);
+    if (cubic) launch_remap_bicubic_frames(c->d_remap_frames, n_frames, n_blocks, blk_px, *cubic, co, pl, plane_stride_bytes, W, H, elem, channels, static_cast<uint8_t *>(d_out), c->stream);
+    else launch_remap_bilinear_frames(c->d_remap_frames, RemapFrame{}, n_frames, n_blocks, blk_px, co, pl, plane_stride_bytes, W, H, elem, channels, static_cast<uint8_t *>(d_out), c->stream);
     HIP_TRY(c, hipGetLastError());
     return HG_OK;
+}
+
+extern "C" int hg_remap_bilinear_frames_device(hg_ctx *c, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
+                                               const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
+                                               void *d_out, const size_t *out_offsets)
+{
+    return remap_flat_frames(c, "hg_remap_bilinear_frames_device", geoms, n_frames, d_coords, field_offsets, d_planes, W, H, n_planes, plane_stride_bytes,
+                             elem, channels, d_out, out_offsets, nullptr);
+}
+
+// The coefficients of the (B, C) cubic: in double from (double)B and (double)C in the header's written order, each rounded once to f32.
+static CubicCoef cubic_coefficients(float Bf, float Cf)
+{
+    const double B = (double)Bf, C = (double)Cf;
+    CubicCoef k;
+    k.p3 = (float)(((12.0 - 9.0 * B) - 6.0 * C) / 6.0);
+    k.p2 = (float)(((-18.0 + 12.0 * B) + 6.0 * C) / 6.0);
+    k.p0 = (float)((6.0 - 2.0 * B) / 6.0);
+    k.q3 = (float)((-B - 6.0 * C) / 6.0);
+    k.q2 = (float)((6.0 * B + 30.0 * C) / 6.0);
+    k.q1 = (float)((-12.0 * B - 48.0 * C) / 6.0);
+    k.q0 = (float)((8.0 * B + 24.0 * C) / 6.0);
+    return k;
+}
+
+extern "C" int hg_remap_bicubic_frames_device(hg_ctx *c, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
+                                              const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
+                                              void *d_out, const size_t *out_offsets, float B, float C)
+{
+    if (!(B >= 0.0f && B <= 1.0f)) return fail(c, HG_ERR_INVALID, "hg_remap_bicubic_frames_device: B must lie in [0, 1]");      // (a NaN compares false)
+    if (!(C >= 0.0f && C <= 1.0f)) return fail(c, HG_ERR_INVALID, "hg_remap_bicubic_frames_device: C must lie in [0, 1]");
+    const CubicCoef k = cubic_coefficients(B, C);
+    return remap_flat_frames(c, "hg_remap_bicubic_frames_device", geoms, n_frames, d_coords, field_offsets, d_planes, W, H, n_planes, plane_stride_bytes,
+                             elem, channels, d_out, out_offsets, &k);
 }
 
 extern "C" int hg_remap_bilinear_u8_device(hg_ctx *c, const void *d_coords, size_t n_px, const uint8_t *d_src, int W, int H, int channels, uint8_t *d_out)

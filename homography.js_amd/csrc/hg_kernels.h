@@ -223,6 +223,11 @@ void launch_remap_trilinear_frames(const TriRemapFrame *frames, int n_frames, ui
 void launch_remap_aniso_frames(const TriRemapFrame *frames, int n_frames, uint32_t n_blocks, uint64_t blk_px, const uint64_t *lvl_off, int levels,
                                int max_aniso, const uint8_t *coords, const uint8_t *planes, const uint8_t *pyrs, int W, int H, int elem, int channels,
                                uint8_t *out, hipStream_t stream);
+// k_remap_bicubic_frames<element, channels> (hg_k_bicubic.hip; hg_remap_bicubic_frames_device): the bilinear frames launch plus the cubic's
+// coefficients by value; 4 x 4 clamped taps of level 0 per pixel, elem 1 (u8) clamped to 0..255 on both sides.
+void launch_remap_bicubic_frames(const RemapFrame *frames, int n_frames, uint32_t n_blocks, uint64_t blk_px, const CubicCoef &k,
+                                 const uint8_t *coords, const uint8_t *planes, size_t plane_stride, int W, int H, int elem, int channels,
+                                 uint8_t *out, hipStream_t stream);
 
 // The mosaic (hg_k_mosaic.hip; include/hgwarp.h hg_mosaic_frames_device).
 // k_mosaic_frames<element, channels>: every pixel of the canvas window (cx, cy, cw, ch), tightly packed at `canvas`, from the frames that

@@ -1,4 +1,4 @@
-// hg_remap_dev.h -- the one text of the remap family's device helpers (hg_k_remap.hip, hg_k_pyramid.hip, hg_k_aniso.hip, hg_k_mosaic.hip):
+// hg_remap_dev.h -- the one text of the remap family's device helpers (hg_k_remap.hip, hg_k_pyramid.hip, hg_k_aniso.hip, hg_k_mosaic.hip, hg_k_bicubic.hip):
 // the frame of a block, taps, pixel loads, the bilinear sample on one level, the field's footprint, the level choice and the store tail.
 // Needs the records and the HIP qualifiers only -- from hg_dev.h under hipcc, from tests/cpp/hip_host_shim.h in the host checks, which
 // compile the kernel files themselves.  All arithmetic is f32 in the written order (contraction off).  Design notes: DESIGN.md §4.9.
@@ -114,8 +114,9 @@ __device__ __forceinline__ RemapLevels remap_levels(float q, int levels)
 }
 
 // Pixel i of the output list o: f32 as it is; u8 as min(255, floor(v + 0.5f)) -- blend4's rounding; v >= 0 always --, the channel bytes in
-// one store where there are 2 or 4 of them and the list's start is aligned for it (wide).
-template <typename E, int C>
+// one store where there are 2 or 4 of them and the list's start is aligned for it (wide).  SIGNED: v may be negative (a filter with negative
+// lobes); u8 is then min(255, max(0, floor(v + 0.5f))), so that the conversion to unsigned stays defined.
+template <typename E, int C, bool SIGNED = false>
 __device__ __forceinline__ void remap_px_store(E *__restrict__ o, uint64_t i, bool wide, const float v[C])
 {
     if constexpr (sizeof(E) == 4) {
@@ -124,7 +125,10 @@ __device__ __forceinline__ void remap_px_store(E *__restrict__ o, uint64_t i, bo
     } else {
         uint32_t b[C];
 #pragma unroll
-        for (int ch = 0; ch < C; ch++) b[ch] = (uint32_t)fminf(255.0f, floorf(v[ch] + 0.5f));
+        for (int ch = 0; ch < C; ch++) {
+            if constexpr (SIGNED) b[ch] = (uint32_t)fminf(255.0f, fmaxf(0.0f, floorf(v[ch] + 0.5f)));
+            else b[ch] = (uint32_t)fminf(255.0f, floorf(v[ch] + 0.5f));
+        }
         if constexpr (C == 4) {
             if (wide) { *reinterpret_cast<uint32_t *>(o + i * 4) = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24); return; }
         } else if constexpr (C == 2) {

@@ -1,4 +1,4 @@
-// hg_remap_records.h -- the device records of the remap family (hg_k_remap.hip, hg_k_pyramid.hip, hg_k_aniso.hip, hg_k_mosaic.hip): what
+// hg_remap_records.h -- the device records of the remap family (hg_k_remap.hip, hg_k_pyramid.hip, hg_k_aniso.hip, hg_k_mosaic.hip, hg_k_bicubic.hip): what
 // the host stages and the kernels read.  Plain C++ over <cstdint>, no HIP types: the host checks of tests/cpp include this very file.
 #pragma once
 #include <cstdint>
@@ -15,6 +15,11 @@ static_assert(sizeof(RemapFrame) == 32, "the table is staged in 8-byte words and
 // (bytes from the bases the kernel gets).
 struct TriRemapFrame { uint64_t fld_off, out_off, n_px, plane_off, pyr_off; uint32_t blk0, obj_w, obj_h, pad; };
 static_assert(sizeof(TriRemapFrame) % 8 == 0, "the table is staged in 8-byte words");
+
+// The bicubic remap's kernel (hg_k_bicubic.hip; include/hgwarp.h hg_remap_bicubic_frames_device): the seven polynomial coefficients of the
+// (B, C) cubic, computed once per call on the host in double and rounded once to f32; passed by value.
+// near(x) = (((p3*x) + p2)*x)*x + p0 on [0, 1], far(x) = ((((q3*x) + q2)*x) + q1)*x + q0 on [1, 2].
+struct CubicCoef { float p3, p2, p0, q3, q2, q1, q0; };
 
 // The mosaic (hg_k_mosaic.hip; include/hgwarp.h hg_mosaic_frames_device).  A frame: its HG_FIELD_COORDS field at fld_off and its pixels at
 // pix_off (bytes from the bases the kernel gets), row-major obj_w x obj_h, pixel (i, j) at destination position (x_off + i, y_off + j).

@@ -830,9 +830,10 @@ static napi_value fn_field_forward_piecewise(napi_env env, napi_callback_info in
  * bytes) or hg_remap_bilinear_f32_device / _u8_device (format 1: Float32Array / Uint8Array / Uint8ClampedArray, 1..4 channels) runs, and the
  * result comes down as a TypedArray of the plane's class with objW * objH * channels elements. */
 typedef struct { napi_typedarray_type type; void *data; size_t len, elem; int channels, W, H; void *d_field, *d_plane, *d_out, *out; size_t px; napi_value result;
-                 int levels, max_aniso; void *d_pyr; size_t pyr_bytes; hg_geom geom; } remap_job;      /* levels > 0: the trilinear remap, its pyramid behind the result; max_aniso > 0: the anisotropic one */
+                 int levels, max_aniso; void *d_pyr; size_t pyr_bytes; hg_geom geom;
+                 int cubic; float cubic_b, cubic_c; } remap_job;      /* levels > 0: the trilinear remap, its pyramid behind the result; max_aniso > 0: the anisotropic one; cubic: the bicubic one */
 
-static int remap_begin(napi_env env, handle_t *h, napi_value *a, int fmt, size_t px, int mip, remap_job *j)      /* mip: 0 none, 1 trilinear, 2 anisotropic (a[4] = maxAniso) */
+static int remap_begin(napi_env env, handle_t *h, napi_value *a, int fmt, size_t px, int mip, remap_job *j)      /* mip: 0 none, 1 trilinear, 2 anisotropic (a[4] = maxAniso), 3 bicubic (a[4] = B, a[5] = C; no pyramid) */
 {
     static const size_t elem_of[] = { 1, 1, 1, 2, 2, 4, 4, 4, 8, 8, 8 };       /* napi_int8_array .. napi_biguint64_array */
     bool is = false; napi_value ab; size_t off = 0;
@@ -851,6 +852,14 @@ static int remap_begin(napi_env env, handle_t *h, napi_value *a, int fmt, size_t
     if (mip == 2) {
         if (!get_i32(env, a[4], &j->max_aniso)) return 0;
         if (j->max_aniso < 1 || j->max_aniso > 16) { throw_str(env, "hgwarp: maxAniso must lie in 1..16"); return 0; }
+    }
+    if (mip == 3) {
+        double b, c;
+        if (napi_get_value_double(env, a[4], &b) != napi_ok || napi_get_value_double(env, a[5], &c) != napi_ok) { throw_str(env, "hgwarp: expected a number"); return 0; }
+        if (!(b >= 0.0 && b <= 1.0) || !(c >= 0.0 && c <= 1.0)) { throw_str(env, "hgwarp: the cubic's B and C must lie in [0, 1]"); return 0; }
+        if (fmt != HG_FIELD_COORDS) { throw_str(env, "hgwarp: a bicubic remap needs the coords format"); return 0; }
+        j->cubic = 1; j->cubic_b = (float)b; j->cubic_c = (float)c;
+        mip = 0;
     }
     j->px = px;
     j->result = make_typed(env, j->type, px * (size_t)j->channels, j->elem, &j->out);
@@ -891,6 +900,11 @@ static napi_value remap_finish(napi_env env, handle_t *h, int fmt, const remap_j
         else
         HG_CALL(h->ctx, "hg_remap_trilinear_frames_device", hg_remap_trilinear_frames_device(h->ctx, &j->geom, 1, j->d_field, &zero, j->d_plane, j->W, j->H, 1, 0, elem,
                                                                                              j->channels, j->d_out, &zero, j->d_pyr, j->pyr_bytes, j->levels));
+    } else if (j->cubic) {
+        const size_t zero = 0;
+        HG_CALL(h->ctx, "hg_remap_bicubic_frames_device", hg_remap_bicubic_frames_device(h->ctx, &j->geom, 1, j->d_field, &zero, j->d_plane, j->W, j->H, 1, 0,
+                                                                                         j->type == napi_float32_array ? HG_ELEM_F32 : HG_ELEM_U8, j->channels, j->d_out, &zero,
+                                                                                         j->cubic_b, j->cubic_c));
     } else if (fmt == HG_FIELD_INDEX)
         HG_CALL(h->ctx, "hg_remap_index_device", hg_remap_index_device(h->ctx, j->d_field, j->px, j->d_plane, (size_t)j->W * (size_t)j->H, (int)pb, j->d_out));
     else if (j->type == napi_float32_array)
@@ -903,8 +917,8 @@ static napi_value remap_finish(napi_env env, handle_t *h, int fmt, const remap_j
 
 static napi_value remap_inverse_geometric(napi_env env, napi_callback_info info, int mip)
 {
-    napi_value a[13];
-    if (!get_args(env, info, mip == 2 ? 13 : 12, a)) return NULL;
+    napi_value a[14];
+    if (!get_args(env, info, mip == 3 ? 14 : mip == 2 ? 13 : 12, a)) return NULL;
     handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
     int kind, fmt; size_t n; hg_geom g; remap_job j;
     if (!get_i32(env, a[1], &kind)) return NULL;
@@ -920,8 +934,8 @@ static napi_value remap_inverse_geometric(napi_env env, napi_callback_info info,
 
 static napi_value remap_inverse_piecewise(napi_env env, napi_callback_info info, int mip)
 {
-    napi_value a[7];
-    if (!get_args(env, info, mip == 2 ? 7 : 6, a)) return NULL;
+    napi_value a[8];
+    if (!get_args(env, info, mip == 3 ? 8 : mip == 2 ? 7 : 6, a)) return NULL;
     handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
     int fmt; remap_job j;
     if (!get_i32(env, a[1], &fmt)) return NULL;
@@ -934,13 +948,17 @@ static napi_value remap_inverse_piecewise(napi_env env, napi_callback_info info,
 
 /* remapTrilinearInverseGeometric / remapTrilinearInversePiecewise: the arguments of remapInverseGeometric / remapInversePiecewise (format 1),
  * the plane through hg_pyramid_build_device (all levels, in device scratch) and hg_remap_trilinear_frames_device with the window as one frame.
- * remapAnisoInverseGeometric / remapAnisoInversePiecewise: the same arguments followed by maxAniso (1..16), through hg_remap_aniso_frames_device. */
+ * remapAnisoInverseGeometric / remapAnisoInversePiecewise: the same arguments followed by maxAniso (1..16), through hg_remap_aniso_frames_device.
+ * remapBicubicInverseGeometric / remapBicubicInversePiecewise: the remap* arguments (format 1) followed by the cubic's B and C (numbers in
+ * [0, 1]), through hg_remap_bicubic_frames_device with the window as one frame; no pyramid. */
 static napi_value fn_remap_inverse_geometric(napi_env env, napi_callback_info info) { return remap_inverse_geometric(env, info, 0); }
 static napi_value fn_remap_inverse_piecewise(napi_env env, napi_callback_info info) { return remap_inverse_piecewise(env, info, 0); }
 static napi_value fn_remap_trilinear_inverse_geometric(napi_env env, napi_callback_info info) { return remap_inverse_geometric(env, info, 1); }
 static napi_value fn_remap_trilinear_inverse_piecewise(napi_env env, napi_callback_info info) { return remap_inverse_piecewise(env, info, 1); }
 static napi_value fn_remap_aniso_inverse_geometric(napi_env env, napi_callback_info info) { return remap_inverse_geometric(env, info, 2); }
 static napi_value fn_remap_aniso_inverse_piecewise(napi_env env, napi_callback_info info) { return remap_inverse_piecewise(env, info, 2); }
+static napi_value fn_remap_bicubic_inverse_geometric(napi_env env, napi_callback_info info) { return remap_inverse_geometric(env, info, 3); }
+static napi_value fn_remap_bicubic_inverse_piecewise(napi_env env, napi_callback_info info) { return remap_inverse_piecewise(env, info, 3); }
 
 static napi_value fn_remap_forward_geometric(napi_env env, napi_callback_info info)
 {
@@ -1761,6 +1779,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "remapForwardGeometric", fn_remap_forward_geometric }, { "remapForwardPiecewise", fn_remap_forward_piecewise },
         { "remapTrilinearInverseGeometric", fn_remap_trilinear_inverse_geometric }, { "remapTrilinearInversePiecewise", fn_remap_trilinear_inverse_piecewise },
         { "remapAnisoInverseGeometric", fn_remap_aniso_inverse_geometric }, { "remapAnisoInversePiecewise", fn_remap_aniso_inverse_piecewise },
+        { "remapBicubicInverseGeometric", fn_remap_bicubic_inverse_geometric }, { "remapBicubicInversePiecewise", fn_remap_bicubic_inverse_piecewise },
         { "mosaicInverseGeometric", fn_mosaic_inverse_geometric }, { "mosaicInversePiecewise", fn_mosaic_inverse_piecewise },
         { "pointsInverseGeometric", fn_points_inverse_geometric }, { "pointsInversePiecewise", fn_points_inverse_piecewise },
         { "pointsForwardGeometric", fn_points_forward_geometric }, { "pointsForwardPiecewise", fn_points_forward_piecewise },

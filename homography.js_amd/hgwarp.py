@@ -26,6 +26,8 @@ FIELD_INDEX, FIELD_COORDS = 0, 1
 ELEM_F32, ELEM_U8 = 0, 1
 # blend modes of the mosaic (hg_mosaic_frames_device): the last contributor's pixel, the contributors' mean, their feathered mean
 MOSAIC_LAST, MOSAIC_MEAN, MOSAIC_FEATHER = 0, 1, 2
+# (B, C) of the named cubics of the bicubic remap (hg_remap_bicubic_frames_device)
+CUBIC_CATMULL_ROM, CUBIC_MITCHELL, CUBIC_BSPLINE = (0.0, 0.5), (1 / 3, 1 / 3), (1.0, 0.0)
 
 # every symbol include/hgwarp.h declares (tests check that the built library exports all of them)
 EXPORTS = [
@@ -58,6 +60,7 @@ EXPORTS = [
     "hg_points_to_output_geometric_batch_device", "hg_points_to_output_piecewise_batch_device",
     "hg_pyramid_levels", "hg_pyramid_layout", "hg_pyramid_build_device", "hg_remap_trilinear_frames_device", "hg_remap_aniso_frames_device",
     "hg_mosaic_frames_device",
+    "hg_remap_bicubic_frames_device",
 ]
 
 
@@ -164,6 +167,7 @@ def lib():
         "hg_pyramid_layout": (i, [i, i, i, i, i, C.POINTER(sz), C.POINTER(sz)]),
         "hg_pyramid_build_device": (i, [vp, vp, i, i, i, sz, i, i, i, vp, sz]),
         "hg_remap_trilinear_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, i, i, i, sz, i, i, vp, C.POINTER(sz), vp, sz, i]),
+        "hg_remap_bicubic_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, i, i, i, sz, i, i, vp, C.POINTER(sz), C.c_float, C.c_float]),
         "hg_remap_aniso_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, i, i, i, sz, i, i, vp, C.POINTER(sz), vp, sz, i, i]),
         "hg_mosaic_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, C.POINTER(sz), i, i, i, i, i, C.c_float, Geom, vp, vp]),
         "hg_points_to_source_geometric_frames_device": (i, [vp, vp, i, i, vp]),
@@ -350,6 +354,15 @@ def device_count():
 
 
 # ------------------------------------------------------------------ context
+
+def _remap_bicubic_frames(handle, geoms, d_coords, d_planes, w, h, n_planes, plane_stride_bytes, elem, channels, d_out, b, c, field_offsets, out_offsets):
+    """hg_remap_bicubic_frames_device for Context.remap_bicubic_frames_device, whose parameter C would hide the ctypes alias."""
+    fo = (C.c_size_t * len(geoms))(*field_offsets) if field_offsets is not None else None
+    oo = (C.c_size_t * len(geoms))(*out_offsets) if out_offsets is not None else None
+    return lib().hg_remap_bicubic_frames_device(handle, _geoms(geoms), len(geoms), C.c_void_p(int(d_coords)), fo, C.c_void_p(int(d_planes)),
+                                                int(w), int(h), int(n_planes), int(plane_stride_bytes), int(elem), int(channels),
+                                                C.c_void_p(int(d_out)), oo, float(b), float(c))
+
 
 class Context:
     """One hg_ctx (one GPU, one stream) == the device side of one Homography instance."""
@@ -723,6 +736,14 @@ class Context:
         self._c(lib().hg_remap_bilinear_frames_device(self._h, _geoms(geoms), len(geoms), C.c_void_p(int(d_coords)), fo, C.c_void_p(int(d_planes)),
                                                       int(w), int(h), int(n_planes), int(plane_stride_bytes), int(elem), int(channels),
                                                       C.c_void_p(int(d_out)), oo))
+
+    def remap_bicubic_frames_device(self, geoms, d_coords, d_planes, w, h, n_planes, plane_stride_bytes, elem, channels, d_out,
+                                    B=0.0, C=0.5, field_offsets=None, out_offsets=None):
+        """remap_bilinear_frames_device with the 4 x 4 taps of the (B, C) cubic, for enlargements: CUBIC_CATMULL_ROM (the default),
+        CUBIC_MITCHELL, CUBIC_BSPLINE or any pair in [0, 1]; reads level 0 only, uint8 results clamped to 0..255 on both sides."""
+        # (the parameter C is the header's name and hides the ctypes alias in here: the call itself is made outside)
+        self._c(_remap_bicubic_frames(self._h, geoms, d_coords, d_planes, w, h, n_planes, plane_stride_bytes, elem, channels, d_out, B, C,
+                                      field_offsets, out_offsets))
 
     def pyramid_build_device(self, d_planes, w, h, n_planes, plane_stride_bytes, elem, channels, levels, d_pyr, pyr_stride_bytes):
         """Levels 1 .. levels-1 of the mip pyramid of every plane, pyramid p at d_pyr + p * pyr_stride_bytes in pyramid_layout's layout;

@@ -63,6 +63,7 @@ function makeRoomFor(native, bytes, n) {
 
 const TRANSFORMS = ['auto', 'piecewiseaffine', 'affine', 'projective'];
 const SAMPLING = ['nearest', 'bilinear'];       // index = HG_SAMPLE_NEAREST / HG_SAMPLE_BILINEAR
+const CUBICS = { 'catmull-rom': [0, 0.5], 'mitchell': [1 / 3, 1 / 3], 'b-spline': [1, 0] };       // (B, C) of remap()'s named cubics
 const CSS_DECIMALS = 5;                 // :31
 const NORMALIZED_MAX = 8.0;             // :36  anything above is taken as pixel coordinates
 const AFFINE = 0, PROJECTIVE = 1;
@@ -336,19 +337,31 @@ class Homography {
      *                     'anisotropic': 'trilinear' for oblique views -- up to options.maxAniso probes along the longer of a pixel's two
      *                     steps in the field, each from the finer level(s) the shorter step allows, averaged (include/hgwarp.h,
      *                     hg_remap_aniso_frames_device), so the axis that shrinks less stays sharp; maxAniso 1 is 'trilinear', bit for bit;
+     *                     'bicubic': 'bilinear' for ENLARGEMENTS -- the same planes, field and refusals; 4 x 4 taps weighted by the cubic
+     *                     options.cubic names (include/hgwarp.h, hg_remap_bicubic_frames_device), so edges and curves survive a 3-4x
+     *                     magnification; bytes are clamped to 0..255 on both sides (the cubic overshoots beside an edge); it reads the
+     *                     plane itself only, so a shrink aliases as 'bilinear' does -- 'trilinear' / 'anisotropic' are for shrinking;
      *   options.maxAniso  'anisotropic' only: an integer in 1..16 (default 8), the most probes a pixel takes;
+     *   options.cubic     'bicubic' only: 'catmull-rom' (default; interpolates: integer coordinates give the source pixel), 'mitchell',
+     *                     'b-spline' (smoothest, never overshoots), or [B, C] with two finite numbers in [0, 1];
      *   options.loop      'inverse' (default), 'warp' or 'forward': sourceField's meaning, refusals and stale-state rules; 'bilinear',
-     *                     'trilinear' and 'anisotropic' with a forward loop throw, as 'coords' does there.
+     *                     'bicubic', 'trilinear' and 'anisotropic' with a forward loop throw, as 'coords' does there.
      * Independent of the instance's sampling mode; records neither a map nor a path.
      * Returns { data, width, height, channels }, `data` being of the plane's own class; an empty window gives empty data, width and height 0.
      */
     remap(plane, options = {}) {
         if (options === null || options === undefined) options = {};
         const sampling = options.sampling === undefined ? 'nearest' : options.sampling;
-        if (sampling !== 'nearest' && sampling !== 'bilinear' && sampling !== 'trilinear' && sampling !== 'anisotropic')
-            throw ("remap: options.sampling must be 'nearest', 'bilinear', 'trilinear' or 'anisotropic'");
+        if (sampling !== 'nearest' && sampling !== 'bilinear' && sampling !== 'bicubic' && sampling !== 'trilinear' && sampling !== 'anisotropic')
+            throw ("remap: options.sampling must be 'nearest', 'bilinear', 'bicubic', 'trilinear' or 'anisotropic'");
         const maxAniso = options.maxAniso === undefined ? 8 : options.maxAniso;
         if (sampling === 'anisotropic' && !(Number.isInteger(maxAniso) && maxAniso >= 1 && maxAniso <= 16)) throw ("remap: options.maxAniso must be an integer in 1..16");
+        let cubic = CUBICS['catmull-rom'];
+        if (sampling === 'bicubic' && options.cubic !== undefined) {
+            cubic = typeof options.cubic === 'string' && Object.prototype.hasOwnProperty.call(CUBICS, options.cubic) ? CUBICS[options.cubic] : options.cubic;
+            if (!(Array.isArray(cubic) && cubic.length === 2 && cubic.every((v) => typeof v === 'number' && v >= 0 && v <= 1)))
+                throw ("remap: options.cubic must be 'catmull-rom', 'mitchell', 'b-spline' or [B, C] with two numbers in [0, 1]");
+        }
         const channels = options.channels === undefined ? 1 : options.channels;
         if (!ArrayBuffer.isView(plane) || plane instanceof DataView) throw ("remap: plane must be a typed array");
         if (!Number.isInteger(channels) || channels < 1) throw ("remap: options.channels must be a positive integer");
@@ -365,6 +378,8 @@ class Homography {
         if (call === null) return { data: new plane.constructor(0), width: 0, height: 0, channels };
         const data = sampling === 'anisotropic'
             ? this._native['remapAniso' + call.entry](this._ctx, ...call.args, plane, channels, this._width, this._height, maxAniso)
+            : sampling === 'bicubic'
+            ? this._native['remapBicubic' + call.entry](this._ctx, ...call.args, plane, channels, this._width, this._height, cubic[0], cubic[1])
             : this._native[(sampling === 'trilinear' ? 'remapTrilinear' : 'remap') + call.entry](this._ctx, ...call.args, plane, channels, this._width, this._height);
         return { data, width: call.width, height: call.height, channels };
     }

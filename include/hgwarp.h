@@ -36,7 +36,8 @@ extern "C" {
 #define HG_VERSION 100          /* 0.1.0 (sampling modes are detected by the presence of hg_set_sampling, source fields by that of hg_field_inverse_geometric,
                                    the forward source fields by that of hg_field_forward_geometric, point lists by that of
                                    hg_points_to_source_geometric_frames_device, mip pyramids and the trilinear remap by that of hg_pyramid_build_device,
-                                   the anisotropic remap by that of hg_remap_aniso_frames_device, mosaics by the presence of hg_mosaic_frames_device) */
+                                   the anisotropic remap by that of hg_remap_aniso_frames_device, mosaics by the presence of hg_mosaic_frames_device,
+                                   the bicubic remap by that of hg_remap_bicubic_frames_device) */
 
 enum {
     HG_OK = 0,
@@ -436,6 +437,45 @@ int hg_remap_aniso_frames_device(hg_ctx *ctx, const hg_geom *geoms, int n_frames
                                  const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes,
                                  int elem, int channels, void *d_out, const size_t *out_offsets,
                                  const void *d_pyr, size_t pyr_stride_bytes, int levels, int max_aniso);
+/* MAGNIFICATION on the field seam: a bicubic remap.  The bilinear remap enlarges with a tent filter: a plane enlarged 3-4x is blurred and shows
+ * a kink at every source pixel.  hg_remap_bicubic_frames_device blends 4 x 4 taps with the weights of the (B, C) family of cubics (Mitchell and
+ * Netravali): (0, 0.5) is Catmull-Rom, (1/3, 1/3) Mitchell, (1, 0) the cubic B-spline.  A 64 x 64 f32 plane 100 sin(2 pi x / 8) cos(2 pi y / 10)
+ * enlarged 4x (pixel centres aligned, the clamped border left out) differs from the function itself by 4.35 RMS through the bilinear remap, 0.49
+ * through Catmull-Rom, 2.89 through Mitchell.
+ * Its arguments are hg_remap_bilinear_frames_device's, followed by B and C.  Argument meaning, offset defaults (hg_pack_field_offsets /
+ * hg_pack_plane_offsets), the f % n_planes rule, alignment rules and refusals, n_frames == 0 (HG_OK, nothing happens), staging of the frame
+ * table through the page-locked ring, "settle queued runs whose redo could land on d_out" and "no effect on hg_last_*, the sampling mode, the
+ * plan, what the policy learned or staged frame sets" are those of the bilinear frames form (one host path serves both).  In addition
+ * HG_ERR_INVALID: B or C NaN or outside [0, 1]; the error text names the parameter.
+ * All of the rule is f32 in the written order, contraction off, except the coefficients.  Pixel i of a frame's flat list, (sx, sy) its coordinate:
+ *   1. sx or sy NaN or infinite: every channel is 0.
+ *   2. Coefficients, once per call on the host, in double from (double)B and (double)C, each rounded once to f32:
+ *        p3 = ((12 - 9B) - 6C)/6    p2 = ((-18 + 12B) + 6C)/6    p0 = (6 - 2B)/6
+ *        q3 = (-B - 6C)/6    q2 = (6B + 30C)/6    q1 = (-12B - 48C)/6    q0 = (8B + 24C)/6
+ *      Catmull-Rom's seven are exact: 1.5, -2.5, 1, -0.5, 2.5, -4, 2.
+ *   3. Fractions: x0 = floorf(sx), fx = sx - x0; y0 and fy likewise (the bilinear remap's).
+ *   4. Weights for t = fx (and t = fy):  near(x) = (((p3*x) + p2)*x)*x + p0,  far(x) = ((((q3*x) + q2)*x) + q1)*x + q0;
+ *      w0 = far(1.0f + t), w1 = near(t), w2 = near(1.0f - t), w3 = far(2.0f - t).
+ *   5. Taps: columns clamp(x0 - 1.0f), clamp(x0), clamp(x0 + 1.0f), clamp(x0 + 2.0f) into 0..W-1, every sum formed in f32 and clamped in float
+ *      before the integer conversion; rows likewise with y0 and H.  No read leaves the plane; 1e30 is a legal coordinate; W = 1 or H = 1 is legal.
+ *   6. Blend per channel, u8 taps widened to float first.  Row n = 0..3 with its taps p[n][0..3]:
+ *        h_n = ((p[n][0]*wx0 + p[n][1]*wx1) + p[n][2]*wx2) + p[n][3]*wx3;   then   r = ((h_0*wy0 + h_1*wy1) + h_2*wy2) + h_3*wy3.
+ *   7. f32 stores r; u8 stores (uint8)fminf(255.0f, fmaxf(0.0f, floorf(r + 0.5f))) -- the lower clamp is this remap's own: the cubic has negative
+ *      lobes, so r can lie below 0 (and above 255) beside an edge.
+ * Hence: with Catmull-Rom, a finite coordinate with integer sx in [0, W-1] and integer sy in [0, H-1] gives the source pixel bit for bit (the
+ * weights are exactly 0, 1, 0, 0), which is also hg_remap_bilinear_frames_device's pixel there; a constant u8 plane stays constant for every
+ * admissible (B, C) (the weight sums differ from 1 by less than 1.1e-6); f32 planes holding NaN or Inf give unspecified payloads.
+ * The filter reads level 0 only: where the field shrinks it aliases as the bilinear remap does -- hg_remap_trilinear_frames_device and
+ * hg_remap_aniso_frames_device are the forms for shrinking.
+ * Cost (MI355X, 64 frames of 3840 x 2160 enlarged 4x out of 8 planes of 960 x 540, and a projective enlargement; EXPERIMENTS.md F.9):
+ * medians of 31 regions, every named cubic alike: u8 x 4 planes take 2.20-2.29 x the time of hg_remap_bilinear_frames_device on the same fields and
+ * planes (6.57 ms against 2.86 ms for the 4x set, 323 GB/s of output), f32 x 1 planes 1.25-1.59 x (2.11 ms against 1.69 ms, 1.0 TB/s of output) -- four
+ * times the taps; the byte kernel pays for unpacking and blending 64 channel taps per pixel, not for memory. */
+int hg_remap_bicubic_frames_device(hg_ctx *ctx, const hg_geom *geoms, int n_frames,
+                                   const void *d_coords, const size_t *field_offsets,
+                                   const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes,
+                                   int elem, int channels, void *d_out, const size_t *out_offsets,
+                                   float B, float C);
 /* MOSAIC on the field seam: the frames of a set blended into ONE canvas on the device (a panorama, a stack of aligned exposures, a
  * stabilised clip pasted on one picture).  Every warp and remap above leaves F frames, each in its own window of destination space;
  * hg_mosaic_frames_device joins them, so that only the canvas has to come down.
