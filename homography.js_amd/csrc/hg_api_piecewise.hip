@@ -589,13 +589,17 @@ static int span_cache_prepare(hg_ctx *c, SpanCacheDev *sc)
     const SpanPlanKey key = span_key_of(c);
     if (!key.eligible) return HG_OK;
     const PwShape &s = c->pw_shape;
-    // the host's estimate: every row of every group at the estimated longest span list, long-form records
-    const uint64_t estimate = (uint64_t)s.groups * kRowGroup * (uint64_t)std::min(s.cover + 1, 63) * (kSpanRecWordsLong * 16);
+    // the host's estimate: every row of every group at the estimated longest span list, long-form records.  It decides whether a build is
+    // started, as it always has.  The records are runs (hg_span_runs.h), and a row's runs can outnumber its spans -- a gap at either end, 2 n + 1
+    // at worst where spans overlap -- so the buffer is sized for that worst case, within the budget: what the budget held in spans it holds in runs.
+    const uint64_t spans_row = (uint64_t)std::min(s.cover + 1, kRunSpanCap), runs_row = std::min<uint64_t>(2 * spans_row + 1, kRunCap);
+    const uint64_t estimate = (uint64_t)s.groups * kRowGroup * spans_row * (kSpanRecWordsLong * 16);
+    const uint64_t worst = (uint64_t)s.groups * kRowGroup * runs_row * (kSpanRecWordsLong * 16);
     const bool force = c->opt_span_cache_mb < 0;
     const uint64_t budget = force ? (uint64_t)(-(int64_t)c->opt_span_cache_mb) << 10 : (uint64_t)c->opt_span_cache_mb << 20;
     const SpanCacheMode mode = span_cache_decide(c->span_state, c->pw_epoch, key, c->opt_span_cache, budget, estimate, force);
     if (mode == SpanCacheMode::Build) {
-        const uint64_t bytes = std::min<uint64_t>(force ? budget : std::min(budget, estimate), ((uint64_t)1 << 36) - 16);
+        const uint64_t bytes = std::min<uint64_t>(force ? budget : std::min(budget, worst), ((uint64_t)1 << 36) - 16);
         const int gpf = (std::max(s.max_h, 1) + kRowGroup - 1) / kRowGroup;
         const size_t entries = 1 + (size_t)key.n_frames * gpf;
         HG_TRY(ensure(c, c->d_span_rec, (size_t)std::max<uint64_t>(bytes / 16, 1)));        // (growing drains the stream first: once per build)

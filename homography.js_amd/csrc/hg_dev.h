@@ -69,6 +69,20 @@ __device__ __forceinline__ HiBounds make_hi_bounds(double lox, double hix, doubl
     b.loy = (uint32_t)__builtin_amdgcn_readfirstlane(__double2hiint(loy)); b.ry = (uint32_t)__builtin_amdgcn_readfirstlane(__double2hiint(hiy)) - b.loy;
     return b;
 }
+// A wave-uniform word into a scalar register whatever the compiler knows about its uniformity: the empty statement hides where the value comes
+// from, so the readfirstlane behind it is not folded away (and is the compiler's own instruction: it keeps the hazards of a hand-written one).
+__device__ __forceinline__ uint32_t pin_u32(uint32_t v)
+{
+    asm volatile("" : "+v"(v));
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+// the same limits held in scalar registers whatever the compiler knows about their uniformity (PIN; otherwise unchanged)
+template <bool PIN>
+__device__ __forceinline__ HiBounds pin_hi_bounds(HiBounds b)
+{
+    if constexpr (PIN) { b.lox = pin_u32(b.lox); b.rx = pin_u32(b.rx); b.loy = pin_u32(b.loy); b.ry = pin_u32(b.ry); }
+    return b;
+}
 __device__ __forceinline__ bool hi_inb(const HiBounds &b, double hx, double hy)
 {
     return (int)(((uint32_t)__double2hiint(hx) - b.lox) < b.rx) & (int)(((uint32_t)__double2hiint(hy) - b.loy) < b.ry);
@@ -239,6 +253,16 @@ __device__ __forceinline__ double sgpr_f64(double v)
     return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
 
+// a wave-uniform double held in scalar registers whatever the compiler knows about its uniformity (PIN; otherwise unchanged)
+template <bool PIN>
+__device__ __forceinline__ double pin_f64(double v)
+{
+    if constexpr (PIN) {
+        return __hiloint2double((int)pin_u32((uint32_t)__double2hiint(v)), (int)pin_u32((uint32_t)__double2loint(v)));
+    }
+    return v;
+}
+
 // Output pixels are written once and never re-read by these kernels: non-temporal stores (aux bit 1 = nt) keep the
 // 34 MB-per-frame output stream from displacing the shared source image in L2 / Infinity Cache (measured -13 % kernel
 // time on C3 versus default-policy stores).
@@ -364,6 +388,28 @@ __device__ __forceinline__ void span_max4d(int best[4], int d0, int d1, int d2, 
         : [b0] "+v"(best[0]), [b1] "+v"(best[1]), [b2] "+v"(best[2]), [b3] "+v"(best[3]), [sv] "=&s"(sv)
         : [d0] "v"(d0), [d1] "v"(d1), [d2] "v"(d2), [d3] "v"(d3), [len] "v"(len), [key] "v"(key)
         : "vcc");
+}
+
+// Run form (hg_span_runs.h): idx[k] += 1 for the pixels k = 0..3 (at q + 64k) at or behind the run start s.  A compare into a scalar pair and an
+// add with carry per pixel.  The four compares go first, so every carry is three instructions old when it is read: written through VCC the
+// compiler puts an s_nop 1 between each compare and its add for this target (seen in its output for gfx950), and this order needs none whatever
+// the exact requirement is.  s itself comes out of a v_readlane: the three scalar subtractions below stand between that and the first compare.
+__device__ __forceinline__ void run_count4(int idx[4], int q, int s)
+{
+    const int s1 = s - 64, s2 = s - 128, s3 = s - 192;
+    unsigned long long c0, c1, c2, c3;
+    asm volatile("v_cmp_le_i32_e64 %[c0], %[s0], %[q]\n\t" "v_cmp_le_i32_e64 %[c1], %[s1], %[q]\n\t"
+        "v_cmp_le_i32_e64 %[c2], %[s2], %[q]\n\t" "v_cmp_le_i32_e64 %[c3], %[s3], %[q]\n\t"
+        "v_addc_co_u32_e64 %[i0], %[c0], 0, %[i0], %[c0]\n\t" "v_addc_co_u32_e64 %[i1], %[c1], 0, %[i1], %[c1]\n\t"
+        "v_addc_co_u32_e64 %[i2], %[c2], 0, %[i2], %[c2]\n\t" "v_addc_co_u32_e64 %[i3], %[c3], 0, %[i3], %[c3]"
+        : [i0] "+v"(idx[0]), [i1] "+v"(idx[1]), [i2] "+v"(idx[2]), [i3] "+v"(idx[3]), [c0] "=&s"(c0), [c1] "=&s"(c1), [c2] "=&s"(c2), [c3] "=&s"(c3)
+        : [q] "v"(q), [s0] "s"(s), [s1] "s"(s1), [s2] "s"(s2), [s3] "s"(s3));
+}
+// off[k] = idx[k] * 48 + base: the LDS record offsets of four run indices (one v_mad_u32_u24 each)
+__device__ __forceinline__ void run_off4(int off[4], const int idx[4], int base)
+{
+#pragma unroll
+    for (int k = 0; k < 4; k++) asm volatile("v_mad_u32_u24 %0, %1, 48, %2" : "=v"(off[k]) : "v"(idx[k]), "s"(base));
 }
 
 } // namespace hg

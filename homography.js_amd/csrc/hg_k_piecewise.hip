@@ -388,11 +388,13 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
     // All four are tested on the doubles: the rounded coordinates are only 32-bit (a source row of 300 * 2^24 must be
     // rejected, not wrapped back into the image); what the range check of the buffer load still provides is the `undefined`
     // -> 0 of flat indices that pass :1047 and yet fall outside the array (sx in [W - 0.5, W) on the last row).
-    const double bx_lo = sgpr_f64((double)ms.x + 0.5), bx_hi = sgpr_f64((double)mesh.W + (double)ms.x + 0.5);
-    const double by_lo = sgpr_f64((double)ms.y + 0.5), by_hi = sgpr_f64((double)mesh.H + (double)ms.y + 0.5);
+    const double bx_lo = pin_f64<SELF == 3>(sgpr_f64((double)ms.x + 0.5)), bx_hi = pin_f64<SELF == 3>(sgpr_f64((double)mesh.W + (double)ms.x + 0.5));
+    const double by_lo = pin_f64<SELF == 3>(sgpr_f64((double)ms.y + 0.5)), by_hi = pin_f64<SELF == 3>(sgpr_f64((double)mesh.H + (double)ms.y + 0.5));
     // HIB (host: hi_bounds_ok): the same four tests as two 32-bit compares on the high dwords of h (hg_dev.h)
-    const HiBounds hb = make_hi_bounds((double)ms.x + 0.5, (double)mesh.W + (double)ms.x + 0.5,
-                                       (double)ms.y + 0.5, (double)mesh.H + (double)ms.y + 0.5);
+    // (SELF 3: pinned, these and the fp64 limits above -- the compiler sees through readfirstlane of a uniform value and keeps the limits in
+    //  vector registers for the whole kernel, which is what stands between the use kernel's two window loops and the parent's occupancy)
+    const HiBounds hb = pin_hi_bounds<SELF == 3>(make_hi_bounds((double)ms.x + 0.5, (double)mesh.W + (double)ms.x + 0.5,
+                                                                (double)ms.y + 0.5, (double)mesh.H + (double)ms.y + 0.5));
     const bool flag_spans = fr.safe_spans != 0;             // (wave-uniform; host: by the rows' span density)
     // One fma per coordinate for the whole frame: (m0 x) + (m2 y) + m4 of :1383 rounds twice, but where m0 x + m2 y and m2 y + m4 are exactly
     // representable for every pixel of the window -- k_tri_setup checked every triangle of the frame that has rows (affine_fusable, hg_math.h:
@@ -514,13 +516,19 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
         return ok;
     };
 
+    // Run form (SELF 3, hg_span_runs.h): the row's records in LDS are disjoint sorted runs, slot == run index, gap runs hold the NaN record; lane i
+    // keeps the start of run i and the runs' unsafe and gap bits are two wave-wide masks.  Workgroup-uniform; false everywhere else.
+    bool runs = false;
+    int run_start_r = 0x7fffffff;
+    unsigned long long run_unsafe_m = 0ull, run_gap_m = 0ull;
+
     // All 256-pixel windows w0, w0 + wstep, ... of one row whose spans sit in LDS slots [base, base + cnt).
     // PH windows per phase: the gathers of PH windows are issued (each right after its window is resolved, so they overlap
     // the next window's arithmetic), then the PH x 4 stores.  On gfx9 loads and stores share one in-order counter (vmcnt): with
     // one window per phase every wait for gather data also waits for the previous window's write acknowledgements, and only 4
     // requests per wave are ever in flight.  A streaming copy in the same instruction forms (tools/calib_fetch: 4 loads + 4
     // stores per step 4.7 TB/s, 16 + 16 per step 5.7 TB/s) shows what that costs once the source comes from HBM.
-    auto do_row = [&](int row, int cnt, int base, int nan_slot, int w0, int wstep) {
+    auto do_row = [&](auto run_tag, int row, int cnt, int base, int nan_slot, int w0, int wstep) {
         // "no triangle": smaller than every real key, its low bits address the NaN record
         const int nan_key = (int)0x80000000u | ((base + nan_slot) * 48) | 1;      // (unsafe: its pixels must come out as offset 0xffffffff)
         const int r = r0 + row;
@@ -536,8 +544,10 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
         // takes the spans that reach a window out of those lanes with v_readlane -- no LDS round trip per (window, span), which was a
         // dependent ds_read + wait in front of every span's four compares (C4: 4.5 spans per window).
         const bool in_regs = cnt <= 64;                     // wave-uniform
+        constexpr bool run_form = decltype(run_tag)::value;  // (SELF 3 only: the caller branches on `runs`, each form has a loop of its own)
         int lo_r = 0x7fffffff, hi_r = 0, key_r = 0;
-        if (in_regs && lane < cnt) { lo_r = s_lo[base + lane]; hi_r = s_hi[base + lane]; key_r = s_key[base + lane]; }
+        if (!run_form && in_regs && lane < cnt) { lo_r = s_lo[base + lane]; hi_r = s_hi[base + lane]; key_r = s_key[base + lane]; }
+        if constexpr (run_form) lo_r = run_start_r;
         for (int wb = w0; wb < nwin; wb += wstep * PH) {
             uint32_t px[PH][4];
             bool empty[PH];                                 // wave-uniform
@@ -550,6 +560,26 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
 #pragma unroll
                 for (int k = 0; k < 4; k++) best[k] = nan_key;
                 unsigned long long any = 0ull;
+                bool safe_w = false;                         // (run form: best[] holds record offsets, and the window's safe decision is made with them)
+                if constexpr (run_form) {
+                    // The run of a pixel by counting run starts: the window's first run and the runs that start inside it are scalars from two
+                    // ballots; per interior start one v_readlane, and per pixel a compare and an add with carry (run_count4, hg_dev.h).  A window inside
+                    // one run has no trip.  Safe and empty are decisions on the runs' masks: every run in range owns a pixel of the window.
+                    const unsigned long long m_le = __ballot(lo_r <= c0), interior = __ballot(lo_r < c0 + 256) & ~m_le;
+                    const int first = __popcll(m_le) - 1;
+                    const int first48 = (base + first) * 48;
+                    if (interior) {
+                        int idx[4] = { 0, 0, 0, 0 };
+                        for (unsigned long long mask = interior; mask; mask &= mask - 1)
+                            run_count4(idx, cq, __builtin_amdgcn_readlane(lo_r, __ffsll((long long)mask) - 1));
+                        run_off4(best, idx, first48);
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 4; k++) best[k] = first48;
+                    }
+                    any = run_window_empty(run_gap_m, first, interior) ? 0ull : 1ull;
+                    safe_w = flag_spans && run_window_safe(run_unsafe_m, run_range(first, interior));
+                } else
                 if (in_regs) {
                     unsigned long long mask = __ballot(lo_r < c0 + 256 && hi_r > c0);
                     any = mask;
@@ -600,7 +630,7 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
                         } else {
 #pragma unroll
                             for (int k = 0; k < N; k++) {
-                                const double2 *mrec = reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(s_m) + (best[k0 + k] & KADDR));
+                                const double2 *mrec = reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(s_m) + (run_form ? best[k0 + k] : (best[k0 + k] & KADDR)));
                                 const double2 ra = mrec[0], rb = mrec[1];
                                 const double xd = xd0 + (double)((k0 + k) * 64);
                                 v[2 * k] = fma(ra.x, xd, ra.y); v[2 * k + 1] = fma(rb.x, xd, rb.y);
@@ -608,7 +638,7 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
                             if (!one_fma) {
 #pragma unroll
                                 for (int k = 0; k < N; k++) {
-                                    const double2 rc = reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(s_m) + (best[k0 + k] & KADDR))[2];
+                                    const double2 rc = reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(s_m) + (run_form ? best[k0 + k] : (best[k0 + k] & KADDR)))[2];
                                     v[2 * k] += rc.x; v[2 * k + 1] += rc.y;
                                 }
                             }
@@ -616,7 +646,7 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
                     };
                     typedef std::integral_constant<int, 2> two_t;
                     typedef std::integral_constant<int, STEP> step_t;
-                    const bool safe = flag_spans && __ballot(((best[0] | best[1] | best[2] | best[3]) & 1) != 0) == 0ull;      // wave-uniform
+                    const bool safe = run_form ? safe_w : flag_spans && __ballot(((best[0] | best[1] | best[2] | best[3]) & 1) != 0) == 0ull;      // wave-uniform
                     if (safe) {
 #pragma unroll
                         for (int kk = 0; kk < 4; kk += 2) {
@@ -660,6 +690,12 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
                 if (w >= nwin) break;
                 const int cq = (w << 8) + lane;
                 if (empty[p] && vec_zero) {                 // 1 KB of zeros: which lane writes which pixel does not matter -> one 16-byte store per lane
+                    if constexpr (run_form) {               // the zeros and the lane's offset are formed here instead of staying in five registers across the pixel bodies
+                        uint32_t z, o;
+                        asm volatile("v_mov_b32 %0, 0\n\tv_lshl_add_u32 %1, %2, 4, %3" : "=&v"(z), "=v"(o) : "v"(lane), "s"(w << 10));
+                        const v4u z4 = { z, z, z, z };
+                        __builtin_amdgcn_raw_buffer_store_b128(z4, dst, (int)o, 0, kStoreNT);
+                    } else
                     __builtin_amdgcn_raw_buffer_store_b128(zero4, dst, ((w << 8) + lane * 4) * 4, 0, kStoreNT);
                 } else {
 #pragma unroll
@@ -696,16 +732,17 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
                     const uint32_t off16 = (uint32_t)__builtin_amdgcn_readfirstlane(e.y), counts = (uint32_t)__builtin_amdgcn_readfirstlane(e.z);
                     // Wave j copies row j's slots into row j's block and is the only reader of that block (packed groups: wave j walks row
                     // r0 + j alone): no barrier, a wave starts on its row as soon as its own records have landed.
-                    if (lane < 3) reinterpret_cast<double2 *>(s_m + (crow * 64 + 63) * 6)[lane] = make_double2(NAN, NAN);     // the row block's NaN record, as the prologue leaves it
+                    // The records are runs (hg_span_runs.h): run i goes to slot i of the block, a gap run's record is all NaN ("no triangle"), and
+                    // nothing but the start stays per lane.
                     int before = 0;
 #pragma unroll
                     for (int j = 0; j < RG; j++) { cnts[j] = span_count(counts, j); before += j < crow ? cnts[j] : 0; }
+                    bool r_unsafe = false, r_gap = false;
                     if (lane < span_count(counts, crow)) {
                         const v4u *p = reinterpret_cast<const v4u *>(sc.rec) + off16 + (size_t)(before + lane) * recw;
                         const v4u a = p[0], b = p[1];
-                        const int at = crow * 64 + lane, lo = span_lo(a.x), hi = span_hi(a.x);
-                        s_lo[at] = lo; s_hi[at] = hi; s_len[at] = hi - lo;
-                        s_key[at] = (span_id(a.y) << KS) | (at * 48) | span_unsafe_bit(a.y);
+                        const int at = crow * 64 + lane;
+                        run_start_r = run_start(a.x); r_gap = run_gap(a.x) != 0; r_unsafe = span_unsafe_bit(a.y) != 0;
                         double2 *mrec = reinterpret_cast<double2 *>(s_m + at * 6);
                         mrec[0] = make_double2((double)__uint_as_float(a.z), __hiloint2double((int)b.y, (int)b.x));
                         mrec[1] = make_double2((double)__uint_as_float(a.w), __hiloint2double((int)b.w, (int)b.z));
@@ -714,6 +751,8 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
                             mrec[2] = make_double2((double)__uint_as_float(c.x), (double)__uint_as_float(c.y));
                         }
                     }
+                    run_unsafe_m = __ballot(r_unsafe); run_gap_m = __ballot(r_gap);
+                    runs = true;
                     have = true;
                 }
             }
@@ -722,12 +761,26 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
                 if (SELF == 2 && packed) {                  // build: the group's slots out, then its directory entry
                     const size_t di = dir_at();
                     const int recw = rec_words(), crow = wave;
+                    // Resolve (hg_span_runs.h): wave j turns the slots of row j into disjoint sorted runs with their winners, all pairs, once per
+                    // frame set.  A row of more than kRunCap runs leaves its group uncached: it goes through the prologue on every warp.
+                    __shared__ uint32_t s_rcand[RG * kRunCands], s_runs[RG * kRunCap];     // the resolve's candidates and runs, per row
+                    __shared__ int s_nruns[RG];
+                    int cnt_mine = 0;
+#pragma unroll
+                    for (int j = 0; j < RG; j++) cnt_mine += j == crow ? cnts[j] : 0;
+                    if (ok) run_candidates(s_lo + crow * 64, s_hi + crow * 64, s_key + crow * 64, cnt_mine, W, KS, lane, s_rcand + crow * kRunCands);
+                    __syncthreads();
+                    if (ok) {
+                        const int nr = run_place(s_rcand + crow * kRunCands, cnt_mine, lane, s_runs + crow * kRunCap);
+                        if (lane == 0) s_nruns[crow] = crow < nrows ? nr : 0;
+                    }
+                    __syncthreads();
                     if (threadIdx.x == 0) {
                         SpanDirEnt d{ok ? SPAN_DIR_NOT_CACHED : SPAN_DIR_OVERFLOWED, 0u, 0u, 0u};
-                        if (ok) {
-                            const unsigned long long need = (unsigned long long)(cnts[0] + cnts[1] + cnts[2] + cnts[3]) * recw;
+                        if (ok && max(max(s_nruns[0], s_nruns[1]), max(s_nruns[2], s_nruns[3])) <= kRunCap) {
+                            const unsigned long long need = (unsigned long long)(s_nruns[0] + s_nruns[1] + s_nruns[2] + s_nruns[3]) * recw;
                             const unsigned long long at16 = atomicAdd(sc.cursor, need);       // one device-scope atomic per workgroup, once per frame set
-                            if (at16 + need <= sc.cap16) { d.state = SPAN_DIR_VALID; d.off16 = (uint32_t)at16; d.counts = span_pack_counts(cnts[0], cnts[1], cnts[2], cnts[3]); }
+                            if (at16 + need <= sc.cap16) { d.state = SPAN_DIR_VALID; d.off16 = (uint32_t)at16; d.counts = span_pack_counts(s_nruns[0], s_nruns[1], s_nruns[2], s_nruns[3]); }
                         }
                         sc.dir[di] = make_int4(d.state, (int)d.off16, (int)d.counts, recw);
                         s_cand_tn[0] = d.state; s_cand_y[0] = (int)d.off16;       // (the candidate list is done with)
@@ -737,13 +790,14 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
                         const uint32_t off16 = (uint32_t)s_cand_y[0];
                         int before = 0, mine = 0;
 #pragma unroll
-                        for (int j = 0; j < RG; j++) { before += j < crow ? cnts[j] : 0; mine += j == crow ? cnts[j] : 0; }
+                        for (int j = 0; j < RG; j++) { before += j < crow ? s_nruns[j] : 0; mine += j == crow ? s_nruns[j] : 0; }
                         if (lane < mine) {
                             v4u *p = reinterpret_cast<v4u *>(sc.rec) + off16 + (size_t)(before + lane) * recw;
-                            const int at = crow * 64 + lane, key = s_key[at];
+                            const uint32_t e = s_runs[crow * kRunCap + lane];
+                            const int gap = run_ent_gap(e), at = crow * 64 + (gap ? 63 : run_ent_slot(e)), key = s_key[crow * 64 + run_ent_slot(e)];      // (gap: the block's NaN record)
                             const double2 *mrec = reinterpret_cast<const double2 *>(s_m + at * 6);
                             const double2 ra = mrec[0], rb = mrec[1];
-                            const v4u a = { span_pack_lo_hi(s_lo[at], s_hi[at]), span_pack_id(key >> KS, key & 1), __float_as_uint((float)ra.x), __float_as_uint((float)rb.x) };
+                            const v4u a = { run_pack_start(run_ent_start(e), gap), span_pack_id(gap ? 0 : key >> KS, run_ent_unsafe(e)), __float_as_uint((float)ra.x), __float_as_uint((float)rb.x) };
                             const v4u b = { (uint32_t)__double2loint(ra.y), (uint32_t)__double2hiint(ra.y), (uint32_t)__double2loint(rb.y), (uint32_t)__double2hiint(rb.y) };
                             __builtin_nontemporal_store(a, p); __builtin_nontemporal_store(b, p + 1);
                             if (!one_fma) {
@@ -769,7 +823,10 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
 #pragma unroll
         for (int j = 0; j < RG; j++) cnt_row += cnts[j] * (row == j);
         const int cnt = __builtin_amdgcn_readfirstlane(cnt_row);
-        if (row < nrows) do_row(row, cnt, packed ? wave * 64 : 0, packed ? 63 : CAP - 1, w_lo + (packed ? 0 : wave), packed ? 1 : nwaves);
+        if (row < nrows) {
+            if constexpr (SELF == 3) { if (runs) { do_row(std::true_type{}, row, cnt, wave * 64, 63, w_lo, 1); return; } }
+            do_row(std::false_type{}, row, cnt, packed ? wave * 64 : 0, packed ? 63 : CAP - 1, w_lo + (packed ? 0 : wave), packed ? 1 : nwaves);
+        }
         return;
     }
     const int npass = packed ? 1 : nrows;
@@ -779,7 +836,7 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
         const int base = packed ? wave * 64 : 0, nan_slot = packed ? 63 : CAP - 1;
         load_row(row, cnt, base, nan_slot, packed ? lane : (int)threadIdx.x, packed ? 64 : nthreads);
         __syncthreads();
-        if (row < nrows) do_row(row, cnt, base, nan_slot, w_lo + (packed ? 0 : wave), packed ? 1 : nwaves);
+        if (row < nrows) do_row(std::false_type{}, row, cnt, base, nan_slot, w_lo + (packed ? 0 : wave), packed ? 1 : nwaves);
         if (!packed) __syncthreads();                       // the next row overwrites the records
     }
 }

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "hg_math.h"
 #include "hg_span_cache.h"
+#include "hg_span_runs.h"
 #include "hg_remap_records.h"
 
 namespace hg {

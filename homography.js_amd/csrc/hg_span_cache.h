@@ -14,11 +14,13 @@
 namespace hg {
 
 // ------------------------------------------------------------------------------------------------ formats
-// Records are runs of 16-byte words; a group's slots lie back to back, row after row, in the order the build's prologue happened to file them.
+// Records are runs of 16-byte words; a group's records lie back to back, row after row.  Since hg_span_runs.h a record stands for a RUN of its
+// row (disjoint, sorted by start, with its winner), not for a span as the prologue filed it: word 0 then begins with run_pack_start() in place of
+// span_pack_lo_hi(), and a row's count in the directory is its number of runs (<= 64).  The span form of word 0 and its helpers stay for the host checks.
 //   word 0: lo | hi << 16 (cells [lo, hi) of the row, hi <= 65535), id << 1 | unsafe bit, m0 and m1 as the f32 they were widened from
 //   word 1: one-fma frame {A, B} = {(m2 y) + m4, (m3 y) + m5}; long form {m2 y, m3 y}: two f64
 //   word 2: long form only: m4, m5 as f32, two unused words
-// The LDS record offset inside a span key is a function of the slot and is rebuilt on the way in.
+// A record's LDS offset is a function of its place: run i of a row goes to slot i of the row's block.
 constexpr int kSpanRecWordsFma = 2, kSpanRecWordsLong = 3;               // 32 / 48 bytes per slot
 struct SpanRecHead { uint32_t lo_hi, id_flag; float m0, m1; };
 
@@ -31,7 +33,7 @@ HG_SC_FN int span_unsafe_bit(uint32_t id_flag) { return (int)(id_flag & 1u); }
 
 // Directory: one entry per (frame, 4-row group), index frame * groups_per_frame + group.
 enum : int32_t { SPAN_DIR_NOT_CACHED = 0, SPAN_DIR_VALID = 1, SPAN_DIR_OVERFLOWED = 2 };
-struct SpanDirEnt { int32_t state; uint32_t off16; uint32_t counts; uint32_t rec_words; };      // off16: first word of the group's records; counts: row j in bits 8j .. 8j + 7 (<= 63); rec_words: 2 or 3
+struct SpanDirEnt { int32_t state; uint32_t off16; uint32_t counts; uint32_t rec_words; };      // off16: first word of the group's records; counts: row j in bits 8j .. 8j + 7 (runs: <= 64); rec_words: 2 or 3
 HG_SC_FN uint32_t span_pack_counts(int c0, int c1, int c2, int c3) { return (uint32_t)c0 | ((uint32_t)c1 << 8) | ((uint32_t)c2 << 16) | ((uint32_t)c3 << 24); }
 HG_SC_FN int span_count(uint32_t counts, int row) { return (int)((counts >> (8 * row)) & 0xffu); }
 
