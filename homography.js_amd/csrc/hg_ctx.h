@@ -206,7 +206,7 @@ struct hg_ctx {
     DevBuf<uint8_t> d_field_tmp;                               // the host-output forms' device copy
     DevBuf<RemapFrame> d_remap_frames;                         // the frame table of a frames remap (hg_remap_*_frames_device), staged through field_stage
     DevBuf<uint64_t> d_tri_table;                              // hg_remap_trilinear_frames_device: 32 level offsets, then the TriRemapFrame records; staged through field_stage
-    DevBuf<MosaicFrame4> d_mosaic_frames;                      // the frame table of hg_mosaic_frames_device (quads of records), staged through field_stage
+    DevBuf<MosaicFrame4> d_mosaic_frames;                      // the frame table of the hg_mosaic_* calls (quads of records) and, behind it, a gained mosaic's gains; staged through field_stage
     int opt_remap_pack = -1;                                   // k_remap_index_frames: 0 = one pixel per lane even for the pixel sizes that carry the packed form (measurements)
 
     // scratch

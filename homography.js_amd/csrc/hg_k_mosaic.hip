@@ -5,33 +5,23 @@
 #ifdef __HIPCC__
 #include "hg_dev.h"
 #endif
-#include "hg_remap_dev.h"
+#include "hg_mosaic_dev.h"
 
 namespace hg {
 
-// Does the window of `fr` meet the canvas tile [X0, X1) x [Y0, Y1) of destination space?  Everything here is uniform over the block: the
-// test runs on the scalar side, from the record alone.
-__device__ __forceinline__ bool mos_hits(const MosaicFrame &fr, int64_t X0, int64_t X1, int64_t Y0, int64_t Y1)
+// Channel c of a contributor as the blend takes it: p_c, or with GAIN q_c = g * p_c on the exposure channels (alpha, channel 3 of 4, as it is).
+template <bool GAIN, int C, typename V>
+__device__ __forceinline__ float mos_value(float g, int c, V p)
 {
-    return fr.obj_w > 0 && fr.obj_h > 0 && fr.x_off < X1 && (int64_t)fr.x_off + fr.obj_w > X0 && fr.y_off < Y1 && (int64_t)fr.y_off + fr.obj_h > Y0;
+    if constexpr (GAIN) { if (c < mos_stat_channels(C)) return g * (float)p; }
+    return (float)p;
 }
-
-// Frame `fr` at destination position (X, Y): false unless the window holds the position and the field covers it there (both coordinate
-// words finite); else the coordinate in *s and the pixel's channels in p.  Bytes with 2 or 4 channels move as one load where the frame's
-// start is aligned for it (uniform per frame).
-template <typename E, int C>
-__device__ __forceinline__ bool mos_fetch(const MosaicFrame &fr, int64_t X, int64_t Y, const uint8_t *__restrict__ coords,
-                                          const uint8_t *__restrict__ pixels, float2 *s, remap_px_t<E> p[C])
+// What LAST and a lone contributor of a gained mosaic store of q_c: itself, or the byte min(255, floor(q_c + 0.5f)) as every u8 result is
+// rounded (an unscaled byte comes back as it was).
+template <typename E>
+__device__ __forceinline__ remap_px_t<E> mos_stored(float q)
 {
-    const int64_t u = X - fr.x_off, v = Y - fr.y_off;
-    if (u < 0 || u >= fr.obj_w || v < 0 || v >= fr.obj_h) return false;
-    const uint64_t k = (uint64_t)v * (uint64_t)fr.obj_w + (uint64_t)u;       // (< 2^31)
-    *s = reinterpret_cast<const float2 *>(coords + fr.fld_off)[k];
-    if (!remap_finite(*s)) return false;
-    const E *__restrict__ px = reinterpret_cast<const E *>(pixels + fr.pix_off);
-    const bool wide = sizeof(E) == 1 && (C == 2 || C == 4) && !(reinterpret_cast<uintptr_t>(px) & (C - 1));
-    remap_px_load<E, C>(px + k * C, wide, p);
-    return true;
+    if constexpr (sizeof(E) == 4) return q; else return (uint32_t)fminf(255.0f, floorf(q + 0.5f));
 }
 
 // One canvas pixel per lane, 64 columns x 4 rows per block (one wave per row: its loads from one frame row are contiguous); block b owns
@@ -41,11 +31,14 @@ __device__ __forceinline__ bool mos_fetch(const MosaicFrame &fr, int64_t X, int6
 // (mean) and 2 (feather): acc_c = acc_c + w * p_c and wsum = wsum + w in ascending f; exactly one contributor stores that pixel as it
 // is, more store acc_c / wsum (u8: min(255, floor(r + 0.5f))).  No contributor: zeros, weight 0.  The accumulators, the first
 // contributor's pixel and the count live in registers; nothing is indexed at run time.
-template <typename E, int C>
+// GAIN (hg_mosaic_frames_gain_device; an instantiation of its own, the plain one's code is what it was): gains[f] is frame f's factor, one
+// per record of the table.  A contributor's exposure channels become q_c = g_f * p_c (one f32 multiply; alpha, channel 3 of 4, passes as
+// it is) before anything else: LAST and a lone contributor store q_c (u8: min(255, floor(q_c + 0.5f))), the sum takes w * q_c.
+template <typename E, int C, bool GAIN = false>
 __global__ __launch_bounds__(256) void k_mosaic_frames(const MosaicFrame4 *__restrict__ frames, int n_quads, const uint8_t *__restrict__ coords,
                                                        const uint8_t *__restrict__ pixels, int W, int H, int mode, float feather,
                                                        int cx, int cy, int cw, int ch, uint32_t tiles_x, uint8_t *__restrict__ canvas,
-                                                       float *__restrict__ weight)
+                                                       float *__restrict__ weight, const float *__restrict__ gains = nullptr)
 {
     using V = remap_px_t<E>;
     const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
@@ -69,7 +62,9 @@ __global__ __launch_bounds__(256) void k_mosaic_frames(const MosaicFrame4 *__res
                 V p[C];
                 if (!mos_fetch<E, C>(fr, X, Y, coords, pixels, &s, p)) continue;
 #pragma unroll
-                for (int c = 0; c < C; c++) r[c] = p[c];
+                for (int c = 0; c < C; c++) {
+                    if constexpr (GAIN) r[c] = mos_stored<E>(mos_value<GAIN, C>(gains[q * 4 + k], c, p[c])); else r[c] = p[c];
+                }
                 wsum = 1.0f;
             }
         }
@@ -88,6 +83,8 @@ __global__ __launch_bounds__(256) void k_mosaic_frames(const MosaicFrame4 *__res
                 float2 s;
                 V p[C];
                 if (!mos_fetch<E, C>(fr, X, Y, coords, pixels, &s, p)) continue;
+                float g = 1.0f;
+                if constexpr (GAIN) g = gains[q * 4 + k];
                 float w = 1.0f;
                 if (mode == 2) {
                     const float dx = fminf(s.x + 1.0f, fw - s.x), dy = fminf(s.y + 1.0f, fh - s.y);
@@ -95,8 +92,9 @@ __global__ __launch_bounds__(256) void k_mosaic_frames(const MosaicFrame4 *__res
                 }
 #pragma unroll
                 for (int c = 0; c < C; c++) {
-                    acc[c] = acc[c] + w * (float)p[c];
-                    if (n == 0) r[c] = p[c];
+                    const float x = mos_value<GAIN, C>(g, c, p[c]);   // p_c, or q_c
+                    acc[c] = acc[c] + w * x;
+                    if (n == 0) { if constexpr (GAIN) r[c] = mos_stored<E>(x); else r[c] = p[c]; }
                 }
                 wsum = wsum + w;
                 n++;
@@ -125,14 +123,18 @@ __global__ __launch_bounds__(256) void k_mosaic_frames(const MosaicFrame4 *__res
 // ------------------------------------------------------------------------------------------------ launcher
 #ifdef __HIPCC__
 void launch_mosaic_frames(const MosaicFrame4 *frames, int n_quads, const uint8_t *coords, const uint8_t *pixels, int W, int H, int elem, int channels,
-                          int mode, float feather, int cx, int cy, int cw, int ch, uint8_t *canvas, float *weight, hipStream_t stream)
+                          int mode, float feather, int cx, int cy, int cw, int ch, uint8_t *canvas, float *weight, const float *gains, hipStream_t stream)
 {
     if (cw <= 0 || ch <= 0) return;
     const uint32_t tiles_x = (uint32_t)(((int64_t)cw + 63) / 64);
     const uint64_t n_blocks = (uint64_t)tiles_x * (uint64_t)(((int64_t)ch + 3) / 4);      // (< 2^31 for a canvas of at most 2^31 pixels)
     for_elem_channels(elem, channels, [&](auto e, auto c) {
-        hipLaunchKernelGGL((k_mosaic_frames<decltype(e), decltype(c)::value>), dim3((uint32_t)n_blocks), dim3(64, 4), 0, stream, frames, n_quads, coords, pixels, W, H,
-                           mode, feather, cx, cy, cw, ch, tiles_x, canvas, weight);
+        if (gains)
+            hipLaunchKernelGGL((k_mosaic_frames<decltype(e), decltype(c)::value, true>), dim3((uint32_t)n_blocks), dim3(64, 4), 0, stream, frames, n_quads, coords,
+                               pixels, W, H, mode, feather, cx, cy, cw, ch, tiles_x, canvas, weight, gains);
+        else
+            hipLaunchKernelGGL((k_mosaic_frames<decltype(e), decltype(c)::value>), dim3((uint32_t)n_blocks), dim3(64, 4), 0, stream, frames, n_quads, coords, pixels,
+                               W, H, mode, feather, cx, cy, cw, ch, tiles_x, canvas, weight, (const float *)nullptr);
     });
 }
 #endif

@@ -235,7 +235,14 @@ void launch_remap_bicubic_frames(const RemapFrame *frames, int n_frames, uint32_
 // cover it -- mode 0 the last one's pixel, 1 their mean, 2 their mean weighted by the distance to the W x H source's border capped at
 // `feather`; weight (or nullptr): one float per canvas pixel.  n_quads == 0 zeroes the canvas (frames, coords and pixels are not read).
 void launch_mosaic_frames(const MosaicFrame4 *frames, int n_quads, const uint8_t *coords, const uint8_t *pixels, int W, int H, int elem, int channels,
-                          int mode, float feather, int cx, int cy, int cw, int ch, uint8_t *canvas, float *weight, hipStream_t stream);
+                          int mode, float feather, int cx, int cy, int cw, int ch, uint8_t *canvas, float *weight, const float *gains, hipStream_t stream);
+// gains (or nullptr: the plain instantiation): one factor per record of the table, applied to every contributor's exposure channels before
+// the blend (hg_mosaic_frames_gain_device).
+// k_mosaic_stats<channels> (hg_k_mosaic_stats.hip; hg_mosaic_overlap_stats_device): for every ordered pair (a, b) of the n_frames (<= 256)
+// u8 frames, the canvas pixels both contribute to and a's summed intensity over them, ADDED to stats[(a * n_frames + b) * 2 + {0, 1}]
+// (the caller zeroes them) with 64-bit vector atomics.  The mosaic's tiling and table.
+void launch_mosaic_stats(const MosaicFrame4 *frames, int n_frames, const uint8_t *coords, const uint8_t *pixels, int channels, int cx, int cy, int cw,
+                         int ch, uint64_t *stats, hipStream_t stream);
 
 // Point lists (hg_k_points.hip; include/hgwarp.h hg_points_*): n_sets lists of n_points interleaved (x, y) floats, frame f reads list
 // f % n_sets and writes n_points (x, y) pairs at f * n_points of `out`; an unmapped point is the quiet NaN of HG_FIELD_COORDS in both words.

@@ -1431,8 +1431,11 @@ static napi_value fn_warp_inverse_geometric_batch(napi_env env, napi_callback_in
  * warpInversePiecewiseBatch (the bound source(s): setImage / setImages) blended into ONE picture on the device.  The set is staged and warped
  * into device scratch, its coords fields are exported beside it, hg_sync settles both, hg_mosaic_frames_device (mode: HG_MOSAIC_*; W x H: the
  * source's size) blends them over `canvas` (Int32Array x, y, width, height) and only the canvas comes down: { data: Uint8ClampedArray
- * [, weight: Float32Array] }. */
-static napi_value run_mosaic(napi_env env, handle_t *h, const batch_job *job, const int32_t *gv, int F, const napi_value *a, const char *what)
+ * [, weight: Float32Array] }.
+ * One more argument, `exposure`, equalises the frames' exposures first (hg_mosaic_frames_gain_device): a Float32Array of one gain per frame
+ * is applied as given; a Float64Array [sigmaN, sigmaG] has the gains fitted on the overlaps -- hg_mosaic_overlap_stats_device, 16 F^2 bytes
+ * down, hg_mosaic_solve_gains on the host -- and the frames still never leave the device.  The result then carries gains: Float32Array. */
+static napi_value run_mosaic(napi_env env, handle_t *h, const batch_job *job, const int32_t *gv, int F, const napi_value *a, napi_value exposure, const char *what)
 {
     const hg_geom *g = (const hg_geom *)gv;
     int mode, W, H; double feather; size_t nc; bool want_weight = false;
@@ -1444,6 +1447,17 @@ static napi_value run_mosaic(napi_env env, handle_t *h, const batch_job *job, co
     if (!get_i32(env, a[4], &W) || !get_i32(env, a[5], &H)) return NULL;
     const hg_geom canvas = { cv[0], cv[1], cv[2], cv[3] };
     const size_t n = (canvas.obj_w > 0 && canvas.obj_h > 0) ? (size_t)canvas.obj_w * (size_t)canvas.obj_h : 0;
+    int fit = 0; double sigma_n = 0.0, sigma_g = 0.0; void *gdata = NULL;      /* fit: the gains are solved for here */
+    napi_value gains_out = NULL;
+    if (exposure) {
+        napi_typedarray_type tt; size_t len = 0; void *ed = NULL; bool is_ta = false;
+        if (napi_is_typedarray(env, exposure, &is_ta) != napi_ok || !is_ta || napi_get_typedarray_info(env, exposure, &tt, &len, &ed, NULL, NULL) != napi_ok ||
+            !((tt == napi_float32_array && len == (size_t)F) || (tt == napi_float64_array && len == 2)))
+            return throw_str(env, "hgwarp: exposure must be a Float32Array of one gain per frame or a Float64Array [sigmaN, sigmaG]");
+        if (!(gains_out = make_typed(env, napi_float32_array, (size_t)F, 4, &gdata))) return NULL;
+        if (tt == napi_float64_array) { fit = 1; sigma_n = ((const double *)ed)[0]; sigma_g = ((const double *)ed)[1]; for (int f = 0; f < F; f++) ((float *)gdata)[f] = 1.0f; }
+        else memcpy(gdata, ed, sizeof(float) * (size_t)F);
+    }
     void *data = NULL, *wdata = NULL;
     napi_value result, pixels = make_typed(env, napi_uint8_clamped_array, n * 4, 1, &data), weights = NULL;
     if (!pixels) return NULL;
@@ -1451,7 +1465,12 @@ static napi_value run_mosaic(napi_env env, handle_t *h, const batch_job *job, co
     NAPI_OK(napi_create_object(env, &result));
     NAPI_OK(napi_set_named_property(env, result, "data", pixels));
     if (want_weight) NAPI_OK(napi_set_named_property(env, result, "weight", weights));
+    if (exposure) NAPI_OK(napi_set_named_property(env, result, "gains", gains_out));
     if (!n) return result;
+    if (fit && F > 256) {                                   /* before anything is staged or warped: the library's own refusal, no pointer involved */
+        int rc0 = hg_mosaic_overlap_stats_device(h->ctx, g, F, NULL, NULL, NULL, NULL, 4, canvas, NULL);
+        return rc0 != HG_OK ? throw_hg(env, h->ctx, what, rc0) : throw_str(env, "hgwarp: exposure 'gain' takes at most 256 frames");
+    }
     size_t *offs = (size_t *)malloc(sizeof(size_t) * 2 * (size_t)F);
     if (!offs) return throw_str(env, "hgwarp: out of memory (frame offsets)");
     size_t *foffs = offs + F, total = 0, ftotal = 0;
@@ -1463,7 +1482,9 @@ static napi_value run_mosaic(napi_env env, handle_t *h, const batch_job *job, co
         rc = hg_device_alloc(h->ctx, total, &h->d_batch);
         if (rc == HG_OK) h->d_batch_cap = total;
     }
-    const size_t cb = (n * 4 + 255) & ~(size_t)255, need = ftotal + cb + (want_weight ? n * 4 : 0);
+    /* the statistics lie behind the weights (8-byte aligned: the parts before them are multiples of 256, 256 and 8) */
+    const size_t cb = (n * 4 + 255) & ~(size_t)255, wb = want_weight ? ((n * 4 + 7) & ~(size_t)7) : 0;
+    const size_t sb = fit ? (size_t)F * (size_t)F * 16 : 0, need = ftotal + cb + wb + sb;
     if (rc == HG_OK && need > h->d_remap_cap) {
         if (h->d_remap) hg_device_free(h->ctx, h->d_remap);
         h->d_remap = NULL; h->d_remap_cap = 0;
@@ -1476,18 +1497,28 @@ static napi_value run_mosaic(napi_env env, handle_t *h, const batch_job *job, co
     if (rc == HG_OK) rc = job->type == JOB_PW_INV ? hg_field_inverse_piecewise_frames_device(h->ctx, HG_FIELD_COORDS, foffs, d_field)
                                                   : hg_field_inverse_geometric_frames_device(h->ctx, HG_FIELD_COORDS, foffs, d_field);
     if (rc == HG_OK) rc = hg_sync(h->ctx);
-    if (rc == HG_OK) rc = hg_mosaic_frames_device(h->ctx, g, F, d_field, foffs, h->d_batch, offs, HG_ELEM_U8, 4, W, H, mode, (float)feather, canvas, d_canvas, d_weight);
+    int host_rc = HG_OK;                                    /* a refusal of the host solve: its text is not the context's */
+    if (rc == HG_OK && fit) {
+        uint64_t *d_stats = (uint64_t *)(d_canvas + cb + wb), *stats = (uint64_t *)malloc(sb);
+        rc = hg_mosaic_overlap_stats_device(h->ctx, g, F, d_field, foffs, h->d_batch, offs, 4, canvas, d_stats);
+        if (rc == HG_OK && !stats) { free(offs); return throw_str(env, "hgwarp: out of memory (overlap statistics)"); }
+        if (rc == HG_OK) rc = hg_copy_to_host(h->ctx, stats, d_stats, sb);
+        if (rc == HG_OK) rc = host_rc = hg_mosaic_solve_gains(stats, F, 4, sigma_n, sigma_g, (float *)gdata);
+        free(stats);
+    }
+    if (rc == HG_OK) rc = hg_mosaic_frames_gain_device(h->ctx, g, F, d_field, foffs, h->d_batch, offs, HG_ELEM_U8, 4, W, H, mode, (float)feather, canvas, d_canvas, d_weight,
+                                                       exposure ? (const float *)gdata : NULL);
     if (rc == HG_OK) rc = hg_copy_to_host(h->ctx, data, d_canvas, n * 4);
     if (rc == HG_OK && want_weight) rc = hg_copy_to_host(h->ctx, wdata, d_weight, n * 4);
     free(offs);
-    if (rc != HG_OK) return throw_hg(env, h->ctx, what, rc);
+    if (rc != HG_OK) return throw_hg(env, host_rc != HG_OK ? NULL : h->ctx, what, rc);
     return result;
 }
 
 static napi_value fn_mosaic_inverse_geometric(napi_env env, napi_callback_info info)
 {
-    napi_value a[11];
-    if (!get_args(env, info, 11, a)) return NULL;
+    napi_value a[12]; int have_exposure = 0;
+    if (!get_args_opt(env, info, 11, a, &have_exposure)) return NULL;
     handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
     size_t nf, nt, ng; batch_job job = { JOB_GEO_INV, 0, NULL, NULL, NULL, NULL, 0, 0, 0 };
     if (!get_i32(env, a[1], &job.kind)) return NULL;
@@ -1499,13 +1530,13 @@ static napi_value fn_mosaic_inverse_geometric(napi_env env, napi_callback_info i
     job.per = job.kind == HG_AFFINE ? 6 : 8;
     if (F <= 0) return throw_str(env, "hgwarp: geoms must hold 4 integers per frame");
     if (nf < (size_t)F * job.per || nt < (size_t)F * job.per) return throw_str(env, "hgwarp: point sets must hold frames x points x,y pairs");
-    return run_mosaic(env, h, &job, gv, F, a + 5, "mosaicInverseGeometric");
+    return run_mosaic(env, h, &job, gv, F, a + 5, have_exposure ? a[11] : NULL, "mosaicInverseGeometric");
 }
 
 static napi_value fn_mosaic_inverse_piecewise(napi_env env, napi_callback_info info)
 {
-    napi_value a[9];
-    if (!get_args(env, info, 9, a)) return NULL;
+    napi_value a[10]; int have_exposure = 0;
+    if (!get_args_opt(env, info, 9, a, &have_exposure)) return NULL;
     handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
     size_t nd, ng; batch_job job = { JOB_PW_INV, 0, NULL, NULL, NULL, NULL, 0, 0, 0 };
     job.dst = (const float *)get_typed(env, a[1], napi_float32_array, &nd, "dstPoints"); if (!job.dst) return NULL;
@@ -1513,7 +1544,7 @@ static napi_value fn_mosaic_inverse_piecewise(napi_env env, napi_callback_info i
     const int F = (int)(ng / 4);
     if (F <= 0) return throw_str(env, "hgwarp: geoms must hold 4 integers per frame");
     if (h->n_pts == 0 || nd < (size_t)F * 2 * h->n_pts) return throw_str(env, "hgwarp: dstPoints must hold frames x mesh points x,y pairs (piecewiseSetMesh first)");
-    return run_mosaic(env, h, &job, gv, F, a + 3, "mosaicInversePiecewise");
+    return run_mosaic(env, h, &job, gv, F, a + 3, have_exposure ? a[9] : NULL, "mosaicInversePiecewise");
 }
 
 /* warpForwardPiecewiseBatch(ctx, dstPoints, maxSrcX, maxSrcY, geoms [, ownFrames, images, width, height]): the frames warp() sends down the

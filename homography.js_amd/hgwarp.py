@@ -59,7 +59,7 @@ EXPORTS = [
     "hg_points_to_source_geometric_frames_device", "hg_points_to_source_piecewise_frames_device",
     "hg_points_to_output_geometric_batch_device", "hg_points_to_output_piecewise_batch_device",
     "hg_pyramid_levels", "hg_pyramid_layout", "hg_pyramid_build_device", "hg_remap_trilinear_frames_device", "hg_remap_aniso_frames_device",
-    "hg_mosaic_frames_device",
+    "hg_mosaic_frames_device", "hg_mosaic_overlap_stats_device", "hg_mosaic_solve_gains", "hg_mosaic_frames_gain_device",
     "hg_remap_bicubic_frames_device",
 ]
 
@@ -170,6 +170,9 @@ def lib():
         "hg_remap_bicubic_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, i, i, i, sz, i, i, vp, C.POINTER(sz), C.c_float, C.c_float]),
         "hg_remap_aniso_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, i, i, i, sz, i, i, vp, C.POINTER(sz), vp, sz, i, i]),
         "hg_mosaic_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, C.POINTER(sz), i, i, i, i, i, C.c_float, Geom, vp, vp]),
+        "hg_mosaic_frames_gain_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, C.POINTER(sz), i, i, i, i, i, C.c_float, Geom, vp, vp, C.POINTER(C.c_float)]),
+        "hg_mosaic_overlap_stats_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, C.POINTER(sz), i, Geom, vp]),
+        "hg_mosaic_solve_gains": (i, [C.POINTER(C.c_uint64), i, i, C.c_double, C.c_double, C.POINTER(C.c_float)]),
         "hg_points_to_source_geometric_frames_device": (i, [vp, vp, i, i, vp]),
         "hg_points_to_source_piecewise_frames_device": (i, [vp, vp, i, i, vp]),
         "hg_points_to_output_geometric_batch_device": (i, [vp, i, f64p, C.POINTER(Geom), i, vp, i, i, vp]),
@@ -341,6 +344,20 @@ def pyramid_layout(w, h, elem, channels, levels):
     total = C.c_size_t(0)
     _check(lib().hg_pyramid_layout(int(w), int(h), int(elem), int(channels), int(levels), offs, C.byref(total)))
     return list(offs)[:int(levels)], total.value
+
+
+def mosaic_solve_gains(stats, channels, sigma_n=10.0, sigma_g=0.1):
+    """One exposure gain per frame (float32, F of them) from the overlap statistics of Context.mosaic_overlap_stats_device -- an array of
+    F * F * 2 uint64 --: Brown & Lowe's gain compensation, solved on the host in double.  sigma_n: the intensity error on the 0..255 scale,
+    sigma_g: the prior that keeps the gains near 1 (the paper's values are the defaults HERE; the C entry has none).  Frames that cover nothing
+    get 1.0."""
+    st = np.ascontiguousarray(stats, dtype=np.uint64).ravel()
+    n = int(round((st.size // 2) ** 0.5))
+    assert n * n * 2 == st.size, "stats must hold F * F * 2 words"
+    gains = np.ones(n, np.float32)
+    _check(lib().hg_mosaic_solve_gains(st.ctypes.data_as(C.POINTER(C.c_uint64)) if n else None, n, int(channels), float(sigma_n), float(sigma_g),
+                                       gains.ctypes.data_as(C.POINTER(C.c_float)) if n else None))
+    return gains
 
 
 def _field_array(fmt, h, w):
@@ -772,17 +789,37 @@ class Context:
                                                    C.c_void_p(int(d_out)), oo, C.c_void_p(int(d_pyr)), int(pyr_stride_bytes), int(levels), int(max_aniso)))
 
     def mosaic_frames_device(self, geoms, d_coords, d_frames, elem, channels, w, h, mode, feather, canvas, d_canvas, d_weight=0,
-                             field_offsets=None, frame_offsets=None):
+                             field_offsets=None, frame_offsets=None, gains=None):
         """The frames of a set blended into ONE canvas (asynchronous): frame f's pixels (obj_w x obj_h, `channels` elements of `elem`) lie at
         (x_off, y_off) of destination space and count where its FIELD_COORDS field is finite.  mode MOSAIC_LAST paints in frame order,
         MOSAIC_MEAN averages, MOSAIC_FEATHER weights by the distance to the w x h source's border, capped at `feather`.  canvas = (x, y, width,
         height): d_canvas gets every pixel of it tightly packed, d_weight (0: none) one float32 per pixel.  field_offsets=None: packed as
-        pack_field_offsets does; frame_offsets=None: as pack_plane_offsets(geoms, channels * element size) does."""
+        pack_field_offsets does; frame_offsets=None: as pack_plane_offsets(geoms, channels * element size) does.  gains (None: none): one
+        factor per frame, finite and > 0, applied to every contributor's colour channels -- not to the alpha of a 4-channel frame -- before the
+        blend (mosaic_solve_gains)."""
         fo = (C.c_size_t * len(geoms))(*field_offsets) if field_offsets is not None else None
         po = (C.c_size_t * len(geoms))(*frame_offsets) if frame_offsets is not None else None
+        if gains is not None:
+            gv = np.ascontiguousarray(gains, dtype=np.float32).ravel()
+            assert gv.size == len(geoms), "one gain per frame"
+            self._c(lib().hg_mosaic_frames_gain_device(self._h, _geoms(geoms) if len(geoms) else None, len(geoms), C.c_void_p(int(d_coords) or None), fo,
+                                                       C.c_void_p(int(d_frames) or None), po, int(elem), int(channels), int(w), int(h), int(mode), float(feather),
+                                                       Geom(*[int(v) for v in canvas]), C.c_void_p(int(d_canvas) or None), C.c_void_p(int(d_weight) or None),
+                                                       gv.ctypes.data_as(C.POINTER(C.c_float)) if gv.size else None))
+            return
         self._c(lib().hg_mosaic_frames_device(self._h, _geoms(geoms) if len(geoms) else None, len(geoms), C.c_void_p(int(d_coords) or None), fo,
                                               C.c_void_p(int(d_frames) or None), po, int(elem), int(channels), int(w), int(h), int(mode), float(feather),
                                               Geom(*[int(v) for v in canvas]), C.c_void_p(int(d_canvas) or None), C.c_void_p(int(d_weight) or None)))
+
+    def mosaic_overlap_stats_device(self, geoms, d_coords, d_frames, channels, canvas, d_stats, field_offsets=None, frame_offsets=None):
+        """The overlaps of a set of uint8 frames measured on the device (asynchronous): d_stats gets F * F * 2 uint64 words -- for every ordered
+        pair (a, b) the canvas pixels both frames contribute to and frame a's summed intensity (colour channels, no alpha) over them.  The
+        arguments are mosaic_frames_device's; at most 256 frames.  mosaic_solve_gains turns the downloaded words into gains."""
+        fo = (C.c_size_t * len(geoms))(*field_offsets) if field_offsets is not None else None
+        po = (C.c_size_t * len(geoms))(*frame_offsets) if frame_offsets is not None else None
+        self._c(lib().hg_mosaic_overlap_stats_device(self._h, _geoms(geoms) if len(geoms) else None, len(geoms), C.c_void_p(int(d_coords) or None), fo,
+                                                     C.c_void_p(int(d_frames) or None), po, int(channels), Geom(*[int(v) for v in canvas]),
+                                                     C.c_void_p(int(d_stats) or None)))
 
     # ---- piecewise
     def piecewise_set_mesh(self, src_pts, tris, min_src_x, min_src_y):

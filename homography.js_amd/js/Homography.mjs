@@ -587,11 +587,18 @@ class Homography {
      *   options.images    the loop warp(image_f): frame f reads images[f % images.length];
      *   options.pointsAreNormalized   the second argument of every setDestinyPoints;
      *   options.weight    true: also return the weight plane (the sum of the weights per canvas pixel; 0 where no frame covers).
+     *   options.exposure  equalise the frames' exposures before the blend, one gain per frame on the colour channels, alpha untouched
+     *                     (include/hgwarp.h, hg_mosaic_frames_gain_device).  'gain': the gains are fitted on the overlaps (Brown & Lowe's gain
+     *                     compensation, sigmaN = 10, sigmaG = 0.1): the overlaps are measured on the device, 16 F^2 bytes come down, a small
+     *                     system is solved on the host -- the frames never leave the device; at most 256 non-blank frames.
+     *                     { sigmaN, sigmaG }: the same with these parameters (numbers > 0).  An array or Float32Array of one gain per
+     *                     destiny point set (finite, > 0): applied as given.  'none' or absent: no gains.  The result then also carries
+     *                     `gains`, a Float32Array of one gain per destiny point set (1 for a blank frame).
      * Every setDestinyPoints(dst[f]) runs on the host exactly as in warpBatch(dstPointSets, {inverse: true}), so the instance ends in the
      * state that call leaves.  A pixel no frame covers is 0 in every channel; where exactly one frame covers it, its bytes are that frame's.
      * Returns { data: Uint8ClampedArray, width, height, x, y [, weight: Float32Array] }.  Throws a string for an unknown blend, a bad
-     * feather, a canvas that is not four integers, and for `devices` and `sourcePoints` (the mosaic runs on this instance's own device,
-     * over one source point set).
+     * feather, a canvas that is not four integers, a bad `exposure`, and for `devices` and `sourcePoints` (the mosaic runs on this
+     * instance's own device, over one source point set).
      */
     mosaic(dstPointSets, options = {}) {
         if (options === null || options === undefined) options = {};
@@ -609,6 +616,21 @@ class Homography {
         if (options.devices !== undefined && options.devices !== null) throw ("mosaic: runs on this instance's own device; {devices} is not supported");
         if (options.sourcePoints !== undefined && options.sourcePoints !== null) throw ("mosaic: one source point set for all frames; {sourcePoints} is not supported");
         if (!Array.isArray(dstPointSets)) throw ("mosaic: needs an array of destiny point sets");
+        let exposure = null;                                     // null, a Float64Array [sigmaN, sigmaG] (fit the gains) or a Float32Array of F gains
+        const ex = options.exposure;
+        if (ex !== undefined && ex !== null && ex !== 'none') {
+            const bad = "mosaic: options.exposure must be 'gain', 'none', { sigmaN, sigmaG } (numbers > 0) or one finite gain > 0 per destiny point set";
+            if (ex === 'gain') exposure = Float64Array.of(10, 0.1);
+            else if (Array.isArray(ex) || ex instanceof Float32Array) {
+                if (ex.length !== dstPointSets.length || !Array.prototype.every.call(ex, (g) => typeof g === 'number' && Number.isFinite(g) && g > 0)) throw (bad);
+                exposure = Float32Array.from(ex);
+                if (!exposure.every((g) => Number.isFinite(g) && g > 0)) throw (bad);      // (a double that leaves the float32 range)
+            } else if (typeof ex === 'object' && !ArrayBuffer.isView(ex)) {
+                const sn = ex.sigmaN === undefined ? 10 : ex.sigmaN, sg = ex.sigmaG === undefined ? 0.1 : ex.sigmaG;
+                if (typeof sn !== 'number' || typeof sg !== 'number' || !Number.isFinite(sn) || !Number.isFinite(sg) || !(sn > 0) || !(sg > 0)) throw (bad);
+                exposure = Float64Array.of(sn, sg);
+            } else throw (bad);
+        }
         const geometric = this.transform === 'affine' || this.transform === 'projective';
         if (!geometric && this.transform !== 'piecewiseaffine') throw ("hgwarp: mosaic() needs a transform (set the source points first)");
         const images = options.images === undefined ? null : options.images;
@@ -647,10 +669,12 @@ class Homography {
         if (keep.length === 0 || cw * ch === 0) {                // nothing to blend: the zero canvas
             out.data = new Uint8ClampedArray(cw * ch * 4);
             if (options.weight === true) out.weight = new Float32Array(cw * ch);
+            if (exposure !== null) out.gains = exposure instanceof Float32Array ? exposure : new Float32Array(F).fill(1);
             return out;
         }
         const sub = (arr, w) => { if (keep.length === F) return arr; const o = new arr.constructor(keep.length * w); keep.forEach((f, k) => o.set(arr.subarray(f * w, (f + 1) * w), k * w)); return o; };
         const tail = [mode, feather, Int32Array.from([cx, cy, cw, ch]), options.weight === true, this._width, this._height];
+        if (exposure !== null) tail.push(exposure instanceof Float32Array ? sub(exposure, 1) : exposure);      // (absent: the call is what it was)
         const srcs = images === null ? null : keep.map((f) => images[f % images.length]);
         let res;
         if (geometric) {
@@ -663,6 +687,10 @@ class Homography {
         }
         out.data = res.data;
         if (options.weight === true) out.weight = res.weight;
+        if (exposure !== null) {                                 // one gain per destiny point set: the blank frames were not part of the call
+            out.gains = new Float32Array(F).fill(1);
+            keep.forEach((f, k) => { out.gains[f] = res.gains[k]; });
+        }
         return out;
     }
 

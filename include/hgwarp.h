@@ -37,7 +37,8 @@ extern "C" {
                                    the forward source fields by that of hg_field_forward_geometric, point lists by that of
                                    hg_points_to_source_geometric_frames_device, mip pyramids and the trilinear remap by that of hg_pyramid_build_device,
                                    the anisotropic remap by that of hg_remap_aniso_frames_device, mosaics by the presence of hg_mosaic_frames_device,
-                                   the bicubic remap by that of hg_remap_bicubic_frames_device) */
+                                   the bicubic remap by that of hg_remap_bicubic_frames_device, exposure gains of a mosaic by that of
+                                   hg_mosaic_overlap_stats_device) */
 
 enum {
     HG_OK = 0,
@@ -524,6 +525,62 @@ int hg_mosaic_frames_device(hg_ctx *ctx, const hg_geom *geoms, int n_frames,
                             int elem, int channels, int W, int H,
                             int mode, float feather,
                             hg_geom canvas, void *d_canvas, float *d_weight);
+/* EXPOSURE of a mosaic: one gain per frame, fitted on the overlaps (Brown & Lowe, "Automatic Panoramic Image Stitching using Invariant
+ * Features", section 6).  The frames of a panorama were taken at different moments: auto-exposure, vignetting and white balance leave the same
+ * surface 10-25 % brighter in one frame than in its neighbour, which HG_MOSAIC_MEAN shows as a step at every window border and
+ * HG_MOSAIC_FEATHER as a ramp between two sides of different brightness.  Three entries, none of which brings a frame down:
+ * hg_mosaic_overlap_stats_device measures the overlaps on the device, hg_mosaic_solve_gains solves a small system on the host, and
+ * hg_mosaic_frames_gain_device applies one factor per frame while it blends.
+ *
+ * hg_mosaic_overlap_stats_device: geoms, d_coords, field_offsets, d_frames, frame_offsets, channels and canvas mean exactly what they mean in
+ * hg_mosaic_frames_device (packing defaults, alignment rules, hg_geom limits).  Elements are HG_ELEM_U8 only: the sums are integers, so the
+ * result is exact and identical from run to run.  d_stats: n_frames x n_frames x 2 64-bit words, aligned to 8 bytes; the call zeroes them itself.
+ *   CONTRIBUTOR is steps 1-3 above, unchanged.  The INTENSITY of frame a at a canvas pixel is v_a = sum of p_c over its STAT CHANNELS:
+ *   channels 0..2 when channels == 4 (alpha takes no part), all channels otherwise.  For every ordered pair (a, b), diagonal included, over all
+ *   canvas pixels where a and b both contribute:
+ *     stats[(a * F + b) * 2 + 0] = N_ab, the number of such pixels;
+ *     stats[(a * F + b) * 2 + 1] = S_ab, the sum of v_a over them.
+ *   N is symmetric, N_aa is the area a covers on the canvas and S_aa is a's own sum.
+ * n_frames is 0..256 (1 MiB of statistics).  n_frames == 0 and an empty canvas return HG_OK: the n_frames^2 pairs are zeroed, none are written
+ * for F = 0.  HG_ERR_INVALID: the mosaic's list, and n_frames > 256; d_stats NULL with n_frames > 0, or misaligned; channels outside 1..4.
+ * Asynchronous on the ctx stream; queued runs whose deferred redo could land on d_stats are settled first; no effect on hg_last_*, the
+ * sampling mode, the plan, what the policy learned or staged frame sets -- the mosaic's guarantees.
+ *
+ * hg_mosaic_solve_gains (host, double precision, no context): k = the number of stat channels, I_ab = S_ab / (k N_ab) on the 0..255 scale where
+ * N_ab > 0, alpha = 1 / sigma_n^2, beta = 1 / sigma_g^2.  Over the frames with N_aa > 0 it solves A g = b, the normal equations of the error
+ *     1/2 sum_a sum_b N_ab [ (g_a I_ab - g_b I_ba)^2 alpha [a != b] + (1 - g_a)^2 beta ]:
+ *     A_aa = beta sum_b N_ab + 2 alpha sum_{b != a} N_ab I_ab^2,   A_ab = -2 alpha N_ab I_ab I_ba (a != b),   b_a = beta sum_b N_ab
+ * (the sums over b include b = a), by a Cholesky factorisation in index order, and rounds once to f32.  A frame with N_aa = 0 gets 1.0f.
+ * The paper's sigma_n = 10 (intensity error, 0..255 scale) and sigma_g = 0.1 (gain prior) are the usual choice; there are no defaults here.
+ * HG_ERR_INVALID: sigma_n or sigma_g not finite or <= 0; n_frames outside 0..256; channels outside 1..4; a NULL pointer with n_frames > 0;
+ * statistics that are not symmetric in N; a solution with a gain that is not finite and positive.
+ *
+ * hg_mosaic_frames_gain_device: every argument of hg_mosaic_frames_device in its order, then gains: n_frames floats on the HOST, or NULL.
+ * With gains == NULL the call IS hg_mosaic_frames_device: the same kernel, the same bytes.  With gains every value of p_c on a STAT CHANNEL in
+ * steps 5-7 becomes q_c = g_f * p_c, one f32 multiply before anything else; channel 3 of a 4-channel frame passes unscaled.  HG_MOSAIC_LAST and
+ * the exactly-one-contributor case store q_c -- u8: (uint8)min(255, floor(q_c + 0.5f)) --, the accumulation is acc_c = acc_c + w_f * q_c;
+ * weights and the weight plane do not change.  A gain of exactly 1.0f therefore reproduces the ungained bytes.  f32 planes have no exposure
+ * statistics, but may be given gains of the caller's own.  HG_ERR_INVALID: the mosaic's list, and a gain that is not finite and > 0.  The gains
+ * go up behind the frame table in the same staged upload, as an array of their own.
+ * Cost (MI355X; EXPERIMENTS.md F.10): u8 x 4 frames, medians of 31 regions.  64 frames with identical 3840 x 2160 windows (4096 ordered pairs):
+ * statistics 4.15 ms, 2.55 x the HG_MOSAIC_MEAN mosaic of the same frames (1.63 ms) -- per frame and tile it issues three vector loads to the
+ * mosaic's two and 1.8 x its instructions, and waits 3.3 x as long on them; not memory.  A strip of 16 frames of 1920 x 1080 shifted by 60 % of
+ * their width: 0.27 ms, 1.13 x (0.24 ms).  256 frames of 128 x 128 over a 4K canvas: 0.20 ms, 0.20 x.  The gained MEAN and FEATHER mosaics take
+ * 1.01-1.04 x the plain ones.  Statistics, 16 F^2 bytes down, host solve and gained mosaic together: 5.9 / 0.58 / 2.2 ms of wall time, 3.6 / 2.3 /
+ * 2.2 x one plain mosaic. */
+int hg_mosaic_overlap_stats_device(hg_ctx *ctx, const hg_geom *geoms, int n_frames,
+                                   const void *d_coords, const size_t *field_offsets,
+                                   const void *d_frames, const size_t *frame_offsets,
+                                   int channels, hg_geom canvas, uint64_t *d_stats);
+int hg_mosaic_solve_gains(const uint64_t *stats, int n_frames, int channels,
+                          double sigma_n, double sigma_g, float *gains);
+int hg_mosaic_frames_gain_device(hg_ctx *ctx, const hg_geom *geoms, int n_frames,
+                                 const void *d_coords, const size_t *field_offsets,
+                                 const void *d_frames, const size_t *frame_offsets,
+                                 int elem, int channels, int W, int H,
+                                 int mode, float feather,
+                                 hg_geom canvas, void *d_canvas, float *d_weight,
+                                 const float *gains);
 /* The source field of the FORWARD warps (next section): what hg_warp_forward_* would paint, as geometry.  HG_FIELD_INDEX only, hence no
  * format argument: the forward loops copy whole pixels from integer positions, (s % W, s / W) IS the coordinate.  One int32 per output pixel
  * p, row-major obj_w x obj_h: let w be the LAST writer, in the loop's raster order (:919-930 over y < H, x < W; :955-969 over the cells of
