@@ -1,7 +1,8 @@
 // span_runs_check.cpp -- the run form of a cached row (hg_span_runs.h): the resolve the build kernel runs, driven lane by lane as the kernel drives
 // it, and the window lookup, against a brute-force largest-id scan; tables plus seeded random rows.  Stand-alone: tests/test_span_runs_cpu.py
 // builds it under AddressSanitizer + UndefinedBehaviorSanitizer and runs it.  `--over-limit N` answers whether the row of the GPU test
-// (one wide span under N separated blocks) exceeds the run limit.
+// (one wide span under N separated blocks) exceeds the run limit; `--row W lo hi id ...` checks one row given by position (the capacity rows of
+// tests/test_gpu_span_runs_wide.py, as the oracle draws them).
 #include "hg_span_runs.h"
 
 #include <cstdio>
@@ -131,6 +132,17 @@ int main(int argc, char **argv)
         const int blocks = std::atoi(argv[2]);
         const int n = check_row(blocks_row(blocks, 520), 520);
         std::printf("span_runs_check: spans %d runs %d limit %d failures %ld\n", blocks + 1, n, kRunCap, g_bad);
+        return g_bad ? 1 : 0;
+    }
+    if (argc >= 3 && (argc - 3) % 3 == 0 && !std::strcmp(argv[1], "--row")) {
+        const int W = std::atoi(argv[2]);
+        std::vector<Span> sp;
+        for (int i = 3; i + 2 < argc; i += 3) sp.push_back({ std::atoi(argv[i]), std::atoi(argv[i + 1]), std::atoi(argv[i + 2]), (i / 3) & 1 });
+        bool ok = W >= 1 && W <= 65535 && (int)sp.size() <= kRunSpanCap;
+        for (const Span &s : sp) ok = ok && 0 <= s.lo && s.lo < s.hi && s.hi <= W && s.id >= 0 && s.id <= 32767;
+        if (!ok) { std::printf("span_runs_check: --row takes W and up to %d spans 0 <= lo < hi <= W\n", kRunSpanCap); return 2; }
+        const int n = check_row(sp, W);
+        std::printf("span_runs_check: spans %d runs %d limit %d failures %ld\n", (int)sp.size(), n, kRunCap, g_bad);
         return g_bad ? 1 : 0;
     }
 

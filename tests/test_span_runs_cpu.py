@@ -6,7 +6,10 @@ import re
 import shutil
 import subprocess
 
+import numpy as np
 import pytest
+
+from hgtest import span_rows as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
@@ -49,3 +52,19 @@ def test_over_limit_row_of_the_gpu_case(exe):
     assert m
     spans, runs, limit, bad = (int(v) for v in m.groups())
     assert bad == 0 and spans == OVER_LIMIT_BLOCKS + 1 and spans < 64 and runs == 2 * OVER_LIMIT_BLOCKS + 1 and runs > limit == 64
+
+
+@pytest.mark.skipif(HIPCC is None, reason="hipcc not available")
+@pytest.mark.parametrize("name,runs", [("gap63", 64), ("rec64", 64), ("runs65", 65)])
+def test_capacity_rows_of_the_gpu_cases(exe, name, runs):
+    """The rows tests/test_gpu_span_runs_wide.py builds from 63 triangles, by position: the pieces of the oracle's winner map that bear a
+    triangle, as 63 abutting or separated spans.  At 64 runs the resolve fills every slot and the lookup finds run 63; at 65 nothing is written."""
+    wmap = S.cap_want(False)[name][1]
+    row = wmap[int(np.argmax(S.run_counts(wmap)))]
+    starts = S.run_starts(row)
+    ends = np.r_[starts[1:], row.size]
+    spans = [(int(a), int(b), int(row[a])) for a, b in zip(starts, ends) if row[a] >= 0]
+    assert len(spans) == S.SPAN_LIMIT and len(starts) == runs
+    m = re.search(r"span_runs_check: spans (\d+) runs (\d+) limit (\d+) failures (\d+)", _run([exe, "--row", str(row.size)] + [str(v) for sp in spans for v in sp]))
+    assert m
+    assert tuple(int(v) for v in m.groups()) == (S.SPAN_LIMIT, runs, S.RUN_LIMIT, 0)
