@@ -5,10 +5,7 @@ against a scalar model written from the header.  Small shapes throughout: planes
 import base64
 import functools
 import hashlib
-import json
 import os
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -19,17 +16,13 @@ sys.path.insert(0, os.path.join(ROOT, "homography.js_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import hgwarp as HG                          # noqa: E402
 from hgtest import aniso as AM               # noqa: E402
-from hgtest import oracle as O               # noqa: E402
+from hgtest import gpu_frames as GF          # noqa: E402
+from hgtest.gpu_frames import CO, F32, F32E, FILL, INVALID, POISON, U8E      # noqa: E402
 from hgtest import remap_frames as RF        # noqa: E402
 from hgtest import trilinear as TM           # noqa: E402
 from hgtest import workloads as WL           # noqa: E402
 
 pytestmark = pytest.mark.gpu
-CO = HG.FIELD_COORDS
-F32E, U8E = HG.ELEM_F32, HG.ELEM_U8
-F32 = np.float32
-INVALID = 1
-FILL, POISON = 0xA5, 0xEE                    # the output and the pyramids before a call; the bytes around the source planes
 SW, SH = 67, 45                              # the source: 8 levels, every level size odd somewhere
 LMAX = 8
 GRID = [(0, 0, 48, 32), (0, 0, 1, 7), (2, 1, 33, 5), (0, 0, 47, 1), (-1, 0, 17, 31)]
@@ -43,36 +36,16 @@ def ctx():
     c.close()
 
 
-def _es(elem):
-    return 1 if elem == U8E else 4
-
-
 # ------------------------------------------------------------------------------------------------ inputs, made once and never modified
 @functools.lru_cache(maxsize=None)
 def _planes(elem, ch, n=3):
     """n planes (SH, SW, ch); no byte of a uint8 plane (nor of a blend of its bytes) equals FILL or POISON; f32: normal-range values."""
-    rng = np.random.default_rng(3000 + 10 * ch + elem)
-    if elem == U8E:
-        ps = [rng.integers(1, 160, (SH, SW, ch), dtype=np.uint8) for _ in range(n)]
-    else:
-        ps = [(rng.standard_normal((SH, SW, ch)) * 40 + 3).astype(F32) for _ in range(n)]
-    for p in ps:
-        p.setflags(write=False)
-    return tuple(ps)
+    return GF.random_planes(3000 + 10 * ch + elem, elem, (SH, SW, ch), n)
 
 
 @functools.lru_cache(maxsize=None)
 def _pyrs(elem, ch, levels, n=3):
     return tuple(TM.pyramid(p, levels) for p in _planes(elem, ch, n))
-
-
-def _split(raw, offs, geoms):
-    out = []
-    for o, g in zip(offs, geoms):
-        a = raw[o:o + RF.n_px(g) * 8].view(F32).reshape(-1, 2).copy()
-        a.setflags(write=False)
-        out.append(a)
-    return out
 
 
 PW_GEOMS = [(0, 0, 48, 8), (-2, -1, 40, 9), (1, 1, 20, 4)]
@@ -93,7 +66,7 @@ def _library_fields():
             c.geometric_set_frames(1, pro, GRID)
             c.field_inverse_geometric_frames_device(CO, d)
             c.sync()
-            out["projective"] = (GRID, _split(c.to_host(d, total), offs, GRID))
+            out["projective"] = (GRID, GF.split(c.to_host(d, total), offs, GRID, 8, F32, 2))
         finally:
             c.free(d)
         nx, ny = 3, 2
@@ -108,7 +81,7 @@ def _library_fields():
             c.piecewise_set_frames(np.concatenate(dps), PW_GEOMS)
             c.field_inverse_piecewise_frames_device(CO, d)
             c.sync()
-            out["piecewise"] = (PW_GEOMS, _split(c.to_host(d, total), offs, PW_GEOMS))
+            out["piecewise"] = (PW_GEOMS, GF.split(c.to_host(d, total), offs, PW_GEOMS, 8, F32, 2))
         finally:
             c.free(d)
     return out
@@ -137,59 +110,14 @@ def _caller_fields():
     return out
 
 
-def _place(parts, offs, total, fill):
-    buf = np.full(total, fill, np.uint8)
-    for p, o in zip(parts, offs):
-        b = np.ascontiguousarray(p).view(np.uint8).ravel()
-        buf[o:o + b.size] = b
-    return buf
-
-
 def _run(ctx, geoms, fields, planes, elem, ch, levels, max_aniso=None, foffs=None, ooffs=None, stride=None, front=256, pyr_slack=256, call=None):
-    """Upload the fields (at foffs, or packed) and the planes (inside an allocation full of POISON, `front` bytes in, `stride` apart), fill
-    the pyramids and the output with FILL, build the pyramids, remap (call, or the anisotropic remap), and return (output bytes, offsets)."""
-    px = ch * _es(elem)
+    """GF.run_frames over pyramids of `levels` built first; call (None: the anisotropic remap) gets GF.Buffers.  Returns (output bytes, offsets)."""
     h, w = planes[0].shape[:2]
-    fo = list(foffs) if foffs is not None else RF.pack(geoms, 8)[0]
-    oo = list(ooffs) if ooffs is not None else RF.pack(geoms, px)[0]
-    stride = stride if stride is not None else (planes[0].nbytes + 255) // 256 * 256 + 256
-    pyr_stride = TM.layout(w, h, px, levels)[1] + pyr_slack
-    f_total = max([o + RF.n_px(g) * 8 for o, g in zip(fo, geoms)] + [0]) + 256
-    o_total = max([o + RF.n_px(g) * px for o, g in zip(oo, geoms)] + [0]) + 512
-    p_total = front + stride * len(planes) + 256
-    y_total = pyr_stride * len(planes) + 256
-    d_f, d_p, d_o, d_y = ctx.alloc(f_total), ctx.alloc(p_total), ctx.alloc(o_total), ctx.alloc(y_total)
-    try:
-        ctx.to_device(d_f, _place(fields, fo, f_total, 0x11))
-        ctx.to_device(d_p, _place(planes, [front + k * stride for k in range(len(planes))], p_total, POISON))
-        ctx.to_device(d_o, np.full(o_total, FILL, np.uint8))
-        ctx.to_device(d_y, np.full(y_total, FILL, np.uint8))
-        ctx.pyramid_build_device(d_p + front, w, h, len(planes), stride, elem, ch, levels, d_y, pyr_stride)
-        if call is not None:
-            call(d_f, d_p + front, stride, d_o, d_y, pyr_stride)
-        else:
-            ctx.remap_aniso_frames_device(geoms, d_f, d_p + front, w, h, len(planes), stride, elem, ch, d_o, d_y, pyr_stride, levels, max_aniso, foffs, ooffs)
-        ctx.sync()
-        return ctx.to_host(d_o, o_total), oo
-    finally:
-        for p in (d_f, d_p, d_o, d_y):
-            ctx.free(p)
-
-
-def _check(raw, oo, geoms, want, px_bytes, what):
-    """Every frame equals the model, bit for bit, and every byte outside the frames is still FILL."""
-    untouched = np.ones(raw.size, bool)
-    for f, g in enumerate(geoms):
-        n = RF.n_px(g) * px_bytes
-        untouched[oo[f]:oo[f] + n] = False
-        w = np.ascontiguousarray(want[f]).view(np.uint8).ravel()
-        assert w.size == n, (what, f)
-        got = raw[oo[f]:oo[f] + n]
-        if not np.array_equal(got, w):
-            bad = np.flatnonzero(got != w)
-            raise AssertionError(f"{what}: frame {f} {g}: {bad.size} of {n} bytes differ, first at pixel {int(bad[0]) // px_bytes}: "
-                                 f"got {got[bad[:8]].tolist()}, want {w[bad[:8]].tolist()}")
-    assert (raw[untouched] == FILL).all(), (what, "bytes between the frames, the padding and the tail must not be written")
+    if call is None:
+        def call(b):
+            ctx.remap_aniso_frames_device(geoms, b.d_f, b.d_p, w, h, len(planes), b.stride, elem, ch, b.d_o, b.d_y, b.pyr_stride, levels, max_aniso, foffs, ooffs)
+    ran = GF.run_frames(ctx, geoms, fields, 8, planes, ch * GF.es(elem), call, foffs, ooffs, stride, front, pyramid=(elem, ch, levels, pyr_slack))
+    return ran.raw, ran.oo
 
 
 def _premises(geoms, fields, levels, max_aniso):
@@ -217,20 +145,20 @@ def _assert_premises(geoms, fields, levels, max_aniso, what):
 @pytest.mark.parametrize("channels", (1, 2, 3, 4))
 @pytest.mark.parametrize("elem", (F32E, U8E))
 def test_aniso_frames_of_the_librarys_projective_fields(ctx, elem, channels):
-    px = channels * _es(elem)
+    px = channels * GF.es(elem)
     geoms, fields = _library_fields()["projective"]
     _assert_premises(geoms, fields, LMAX, 4, "projective")      # on the CPU, before anything is compared
     planes = _planes(elem, channels)
     for levels, max_aniso in ((LMAX, 4), (LMAX, 16), (2, 4)):
         want = AM.aniso_frames(geoms, fields, _pyrs(elem, channels, levels), max_aniso)
         raw, oo = _run(ctx, geoms, fields, planes, elem, channels, levels, max_aniso)
-        _check(raw, oo, geoms, want, px, ("projective", elem, channels, levels, max_aniso))
+        GF.check_frames(raw, oo, geoms, want, px, ("projective", elem, channels, levels, max_aniso))
 
 
 @pytest.mark.parametrize("elem,channels", ((U8E, 4), (F32E, 1), (U8E, 3), (F32E, 2)))
 def test_aniso_frames_of_a_piecewise_field_with_uncovered_pixels(ctx, elem, channels):
     geoms, fields = _library_fields()["piecewise"]
-    px = channels * _es(elem)
+    px = channels * GF.es(elem)
     _assert_premises(geoms, fields, LMAX, 8, "piecewise")
     nan = sum(int((~np.isfinite(f).all(-1)).sum()) for f in fields)
     assert nan > 50 and sum(int(np.isfinite(f).all(-1).sum()) for f in fields) > 300
@@ -240,12 +168,12 @@ def test_aniso_frames_of_a_piecewise_field_with_uncovered_pixels(ctx, elem, chan
             want = AM.aniso_frames(geoms, fields, _pyrs(elem, channels, LMAX)[:n_planes], max_aniso)
             assert any(not w_[~np.isfinite(f).all(-1)].any() and w_.any() for w_, f in zip(want, fields))
             raw, oo = _run(ctx, geoms, fields, planes, elem, channels, LMAX, max_aniso)
-            _check(raw, oo, geoms, want, px, ("piecewise", elem, channels, n_planes, max_aniso))
+            GF.check_frames(raw, oo, geoms, want, px, ("piecewise", elem, channels, n_planes, max_aniso))
 
 
 @pytest.mark.parametrize("elem,channels", ((U8E, 1), (U8E, 2), (U8E, 4), (F32E, 1), (F32E, 3), (F32E, 4)))
 def test_caller_made_fields_with_nan_infinite_huge_and_overflowing_steps(ctx, elem, channels):
-    px = channels * _es(elem)
+    px = channels * GF.es(elem)
     fields = _caller_fields()
     planes = _planes(elem, channels)
     _assert_premises(GRID, fields, LMAX, 8, "caller-made")
@@ -259,7 +187,7 @@ def test_caller_made_fields_with_nan_infinite_huge_and_overflowing_steps(ctx, el
         w0 = want[0].reshape(32, 48, channels)
         assert not w0[0, 5:9].any() and w0[0, 9:13].any()               # NaN / Inf: zeros; 1e30: clamped taps
         raw, oo = _run(ctx, GRID, fields, planes, elem, channels, levels, max_aniso, stride=planes[0].nbytes, front=16)      # planes back to back
-        _check(raw, oo, GRID, want, px, ("caller-made", elem, channels, levels, max_aniso))
+        GF.check_frames(raw, oo, GRID, want, px, ("caller-made", elem, channels, levels, max_aniso))
         if elem == U8E:
             assert not (raw == POISON).any()
 
@@ -269,7 +197,7 @@ def test_explicit_offsets_and_strides_that_break_every_wider_alignment(ctx):
     fo8 = [o + 8 * (2 * f + 1) + 512 * f for f, o in enumerate(RF.pack(GRID, 8)[0])]            # odd multiples of 8: no 16-byte alignment
     assert all(o % 8 == 0 and o % 16 != 0 for o in fo8)
     for elem in (U8E, F32E):
-        es = _es(elem)
+        es = GF.es(elem)
         for ch in (1, 2, 3, 4):
             planes = _planes(elem, ch)
             oo = [o + 640 * f + es * (2 * f + 1) for f, o in enumerate(RF.pack(GRID, ch * es)[0])]  # odd element offsets: no 2- or 4-byte store fits (u8)
@@ -277,7 +205,7 @@ def test_explicit_offsets_and_strides_that_break_every_wider_alignment(ctx):
             stride = planes[0].nbytes + 256 + es * 3
             want = AM.aniso_frames(GRID, fields, _pyrs(elem, ch, LMAX), 8)
             raw, used = _run(ctx, GRID, fields, planes, elem, ch, LMAX, 8, fo8, oo, stride, front=256 + es, pyr_slack=256 + es * 3)
-            _check(raw, used, GRID, want, ch * es, ("explicit offsets", elem, ch))
+            GF.check_frames(raw, used, GRID, want, ch * es, ("explicit offsets", elem, ch))
 
 
 # ------------------------------------------------------------------------------------------------ where it IS another remap
@@ -286,10 +214,10 @@ def test_max_aniso_1_is_the_trilinear_remap_and_one_level_the_bilinear_one(ctx, 
     planes = _planes(elem, channels)
 
     def trilinear(levels):
-        return lambda d_f, d_p, stride, d_o, d_y, ps: ctx.remap_trilinear_frames_device(GRID, d_f, d_p, SW, SH, 3, stride, elem, channels, d_o, d_y, ps, levels)
+        return lambda b: ctx.remap_trilinear_frames_device(GRID, b.d_f, b.d_p, SW, SH, 3, b.stride, elem, channels, b.d_o, b.d_y, b.pyr_stride, levels)
 
-    def bilinear(d_f, d_p, stride, d_o, d_y, ps):
-        ctx.remap_bilinear_frames_device(GRID, d_f, d_p, SW, SH, 3, stride, elem, channels, d_o)
+    def bilinear(b):
+        ctx.remap_bilinear_frames_device(GRID, b.d_f, b.d_p, SW, SH, 3, b.stride, elem, channels, b.d_o)
 
     for name, fields in (("caller-made", _caller_fields()), ("projective", _library_fields()["projective"][1])):
         for levels in (LMAX, 2):
@@ -313,7 +241,7 @@ def test_max_aniso_1_is_the_trilinear_remap_and_one_level_the_bilinear_one(ctx, 
     assert np.array_equal(a, b) and (a != FILL).any(), "magnifying"
     # levels == 1 needs no pyramid at all
     c, _ = _run(ctx, GRID, _caller_fields(), planes, elem, channels, 1,
-                call=lambda d_f, d_p, stride, d_o, d_y, ps: ctx.remap_aniso_frames_device(GRID, d_f, d_p, SW, SH, 3, stride, elem, channels, d_o, 0, 0, 1, 1))
+                call=lambda b: ctx.remap_aniso_frames_device(GRID, b.d_f, b.d_p, SW, SH, 3, b.stride, elem, channels, b.d_o, 0, 0, 1, 1))
     d, _ = _run(ctx, GRID, _caller_fields(), planes, elem, channels, 1, call=bilinear)
     assert np.array_equal(c, d)
 
@@ -329,7 +257,7 @@ def test_the_stripes_stay_stripes_on_the_device_where_trilinear_gives_grey(ctx):
         ani, _ = _run(ctx, g, co, (plane,), U8E, 1, levels, max_aniso)
         assert np.array_equal(ani[:512].reshape(8, 64), np.broadcast_to(plane[0, :, 0], (8, 64))), max_aniso
     tri, _ = _run(ctx, g, co, (plane,), U8E, 1, levels,
-                  call=lambda d_f, d_p, stride, d_o, d_y, ps: ctx.remap_trilinear_frames_device(g, d_f, d_p, 64, 64, 1, stride, U8E, 1, d_o, d_y, ps, levels))
+                  call=lambda b: ctx.remap_trilinear_frames_device(g, b.d_f, b.d_p, 64, 64, 1, b.stride, U8E, 1, b.d_o, b.d_y, b.pyr_stride, levels))
     assert (tri[:512] == 128).all()
 
 
@@ -345,12 +273,6 @@ def test_a_constant_u8_plane_stays_constant(ctx):
 
 
 # ------------------------------------------------------------------------------------------------ refusals
-def _code(fn, *a):
-    with pytest.raises(HG.HgError) as e:
-        fn(*a)
-    return e.value.code
-
-
 def test_refusals():
     g = [(0, 0, 8, 2), (0, 0, 4, 1)]
     W, H = 8, 4                                                  # 4 levels
@@ -360,7 +282,7 @@ def test_refusals():
         co = (np.random.default_rng(2).random((20, 2)) * [7, 3]).astype(F32)
         co[:, 1] *= F32(3)                                       # steps that ask for more than one probe
         plane = np.arange(1, 33, dtype=np.float32).reshape(H, W, 1)
-        c.to_device(d_f, _place([co[:16], co[16:]], [0, 256], 512, 0))
+        c.to_device(d_f, GF.place([co[:16], co[16:]], [0, 256], 512, 0))
         c.to_device(d_p, plane)
         want = AM.aniso_frames(g, [co[:16], co[16:]], [TM.pyramid(plane, 4)], 4)
 
@@ -373,7 +295,7 @@ def test_refusals():
             assert np.array_equal(raw[:64].view(F32), want[0].ravel()) and np.array_equal(raw[256:272].view(F32), want[1].ravel()) and (raw[64:256] == FILL).all()
 
         def refused(*a):
-            assert _code(c.remap_aniso_frames_device, *a) == INVALID, a
+            assert GF.refusal_code(c.remap_aniso_frames_device, *a) == INVALID, a
             still_works()
 
         try:
@@ -413,19 +335,9 @@ def test_refusals():
 
 
 # ------------------------------------------------------------------------------------------------ what the call leaves alone
-def _state(c):
-    return (c.last_piecewise_kernel(), c.last_piecewise_variant(), c.last_piecewise_self(), c.last_piecewise_flag(), c.last_geometric_kernel(),
-            c.last_forward_kernel(), c.last_forward_field_kernel(), c.sampling, c.redone_frames(), c.layout_walks())
-
-
 def test_state_is_untouched_and_a_queued_nearest_warp_keeps_its_bytes():
     W, H, F = 64, 40, 3
-    img = WL.lcg_image(W, H, 81)
-    s4 = WL.corners(W, H)
-    d4s = [WL.projective_dst(W, H, 0.03 * k) * np.tile([0.6, 0.15], 4) for k in range(F)]                    # an oblique shrink: the inverse loop
-    gg = [tuple(int(v) for v in O.transform_limits(1, O.projective_from_squares(s4, d4), W, H)) for d4 in d4s]
-    assert all(0 < g[2] <= 48 and 0 < g[3] <= 32 for g in gg), gg
-    offs, total = HG.pack_offsets(gg)
+    img, s4, d4s, gg, offs, total = GF.oblique_projective_set((0.6, 0.15))      # an oblique shrink (the inverse loop); windows of 48 x 32 at most
     levels = HG.pyramid_levels(W, H)
     _, ptotal = HG.pyramid_layout(W, H, U8E, 4, levels)
     with HG.Context(0) as c:
@@ -443,16 +355,16 @@ def test_state_is_untouched_and_a_queued_nearest_warp_keeps_its_bytes():
             c.field_inverse_geometric_frames_device(CO, d_f)
             c.sync()
             fo = HG.pack_field_offsets(gg, CO)[0]
-            fields = _split(c.to_host(d_f, 2 * total), fo, gg)
+            fields = GF.split(c.to_host(d_f, 2 * total), fo, gg, 8, F32, 2)
             assert (_premises(gg, fields, levels, 16)[0] > 1).any()
             c.to_device(d_w, np.zeros(total, np.uint8))
             c.warp_inverse_geometric_frames_device(d_w)                   # queued ...
-            mid = _state(c)
+            mid = GF.tap_state(c)
             c.pyramid_build_device(d_src, W, H, 1, 0, U8E, 4, levels, d_y, ptotal)
             c.remap_aniso_frames_device(gg, d_f, d_src, W, H, 1, 0, U8E, 4, d_r, d_y, ptotal, levels, 16)      # ... in front of the remap of the picture itself
-            assert _state(c) == mid
+            assert GF.tap_state(c) == mid
             c.sync()
-            assert _state(c) == mid and c.sampling == HG.SAMPLE_NEAREST
+            assert GF.tap_state(c) == mid and c.sampling == HG.SAMPLE_NEAREST
             again = c.to_host(d_w, total)
             for f, g in enumerate(gg):                                    # (the padding between frames is nobody's)
                 assert np.array_equal(again[offs[f]:offs[f] + RF.n_px(g) * 4], alone[offs[f]:offs[f] + RF.n_px(g) * 4]) and again[offs[f]:offs[f] + RF.n_px(g) * 4].any(), f
@@ -470,15 +382,8 @@ def test_a_queued_redo_never_lands_on_a_later_aniso_remap():
     """A piecewise warp whose rows carry 1100 spans is queued into buffer B (its frame is flagged, to be redone through the map at hg_sync);
     an anisotropic remap then writes B.  After hg_sync B holds the remap.  (The redo needs the wide source and window of the trilinear test of
     the same name: a row must carry more spans than the row kernel holds.)"""
-    n, W2, H2 = 1100, 2400, 8
-    img = WL.lcg_image(W2, H2, 10)
-    xs = np.linspace(0, W2, n + 1)
-    sp = np.stack([np.repeat(xs, 2), np.tile([0.0, H2], n + 1)], 1).astype(np.float32).ravel()
-    tr = np.array([[2 * i, 2 * i + 2, 2 * i + 1] for i in range(n)], np.uint32).ravel()
-    dp = sp.copy()
-    dp[1::2] *= 1.5
-    mm, md = O.minmax_xy(sp), O.minmax_xy(dp)
-    g = (int(md[0]), int(md[1]), int(md[2] - md[0]), int(md[3] - md[1]))
+    s = GF.strip_mesh_overflow()
+    img, W2, H2, g = s.img, s.W, s.H, s.g
     npx = g[2] * g[3]
     i, j = np.meshgrid(np.arange(g[2]), np.arange(g[3]))
     co = np.stack([(i * 7.3) % W2, j * 0.6], -1).astype(F32).reshape(-1, 2)
@@ -492,8 +397,8 @@ def test_a_queued_redo_never_lands_on_a_later_aniso_remap():
             c.to_device(d_src, img)
             c.to_device(d_f, co)
             c.set_image_device(d_src, W2, H2)
-            c.piecewise_set_mesh(sp, tr, int(mm[0]), int(mm[1]))
-            c.piecewise_set_frames(dp, [g], [0])
+            c.piecewise_set_mesh(s.sp, s.tris, *s.min_src)
+            c.piecewise_set_frames(s.dp, [g], [0])
             r0 = c.redone_frames()
             c.pyramid_build_device(d_src, W2, H2, 1, 0, U8E, 4, levels, d_y, ptotal)
             c.warp_inverse_piecewise_frames_device(d_b)
@@ -513,18 +418,9 @@ def test_js_class_anisotropic_matches_the_ctypes_result(ctx):
     """tests/js/aniso_gpu.mjs: remap(plane, {sampling: 'anisotropic'}) of js/Homography.mjs on the real addon for an affine, a projective
     and a piecewise oblique shrink; it prints its coordinate fields and the SHA-256 of every result, and the same planes through the same
     fields by ctypes (all levels; maxAniso 8 by default, 3 for the f32 plane) must hash alike -- and equal the model."""
-    node = shutil.which("node")
-    addon = os.path.join(ROOT, "homography.js_amd", "lib", "hgwarp.node")
-    assert node is not None and os.path.exists(addon), "node and the N-API addon are needed on a GPU box"
-    p = subprocess.run([node, os.path.join(ROOT, "tests", "js", "aniso_gpu.mjs")], capture_output=True, text=True, timeout=300, cwd=ROOT)
-    line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
-    assert line, p.stdout[-2000:] + p.stderr[-2000:]
-    res = json.loads(line[-1])
-    assert p.returncode == 0 and res["ok"] and not res["fails"], (res["fails"], p.stderr[-2000:])
+    res = GF.run_node_case("aniso_gpu.mjs")
     W, H = res["W"], res["H"]
-    idx = np.arange(W * H * 4, dtype=np.int64)
-    u8 = ((idx * 7 + (idx >> 3) * 13) & 255).astype(np.uint8).reshape(H, W, 4)
-    f32 = ((idx[:W * H] * 37 % 1001) * 0.25 - 100).astype(F32).reshape(H, W, 1)
+    u8, f32 = GF.js_pattern_planes(W, H)
     levels = HG.pyramid_levels(W, H)
     assert set(res["cases"]) == {"affine", "projective", "piecewise"}
     for name, case in res["cases"].items():
@@ -534,6 +430,6 @@ def test_js_class_anisotropic_matches_the_ctypes_result(ctx):
         assert (_premises(g, [co], levels, 8)[0] > 1).any(), name        # the case does ask for more than one probe
         for key, plane, elem, ch, max_aniso in (("u8x4", u8, U8E, 4, 8), ("f32x1", f32, F32E, 1, 3)):
             raw, oo = _run(ctx, g, [co], (plane,), elem, ch, levels, max_aniso)
-            got = raw[:co.shape[0] * ch * _es(elem)]
+            got = raw[:co.shape[0] * ch * GF.es(elem)]
             assert hashlib.sha256(got.tobytes()).hexdigest() == case[key], (name, key)
             assert np.array_equal(got, AM.aniso_frames(g, [co], [TM.pyramid(plane, levels)], max_aniso)[0].view(np.uint8).ravel()), (name, key)

@@ -2,10 +2,7 @@
 tests/hgtest/field.py, byte for byte (coordinates are compared as uint32 views).  The model's piecewise maps and inverse matrices come from
 the CPU oracle's taps, never from the library under test; tests/test_field_cpu.py pins the model itself to the reference."""
 import functools
-import json
 import os
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -18,6 +15,7 @@ import hgwarp as HG                          # noqa: E402
 from hgtest import bilinear as B             # noqa: E402
 from hgtest import edges as E                # noqa: E402
 from hgtest import field as FM               # noqa: E402
+from hgtest import gpu_frames as GF          # noqa: E402
 from hgtest import moving as M               # noqa: E402
 from hgtest import oracle as O               # noqa: E402
 from hgtest import workloads as WL           # noqa: E402
@@ -35,14 +33,10 @@ def ctx():
     c.close()
 
 
-def _u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def _same(got, want, what):
     """Bit-equal fields.  On a mismatch: how many pixels, and the first few (row, col, got, want)."""
     assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    g, w = _u32(got), _u32(want)
+    g, w = GF.u32(got), GF.u32(want)
     if not np.array_equal(g, w):
         diff = g != w
         bad = np.argwhere(diff.any(-1) if diff.ndim == 3 else diff)
@@ -397,7 +391,7 @@ def test_fields_are_independent_of_the_sampling_mode_and_leave_the_taps_alone(ct
         assert taps == (ctx.last_piecewise_kernel(), ctx.last_piecewise_variant(), ctx.last_piecewise_self(), ctx.last_geometric_kernel(),
                         ctx.last_forward_kernel())
     for a, b in zip(got[NEAR], got[BIL]):
-        assert np.array_equal(_u32(a), _u32(b))
+        assert np.array_equal(GF.u32(a), GF.u32(b))
     ctx.set_sampling(NEAR)
     # a warp run queued before a field call and synced after it keeps its result
     offs, total = HG.pack_offsets([g])
@@ -489,19 +483,13 @@ def test_remap_bilinear_f32(ctx, channels):
     finally:
         for p in (d_c, d_s, d_o):
             ctx.free(p)
-    bad = np.flatnonzero((_u32(got) != _u32(want)).any(-1))
+    bad = np.flatnonzero((GF.u32(got) != GF.u32(want)).any(-1))
     assert bad.size == 0, (bad.size, [(int(i), co[i].tolist(), got[i].tolist(), want[i].tolist()) for i in bad[:6]])
     nan_rows = ~np.isfinite(co).all(-1)
     assert nan_rows.any() and not got[nan_rows].any()
 
 
 # ------------------------------------------------------------------------------------------------ 11: refusals
-def _code(fn, *a):
-    with pytest.raises(HG.HgError) as e:
-        fn(*a)
-    return e.value.code
-
-
 def test_refusals():
     INVALID, STATE = 1, 4
     m = np.array([1, 0, 0, 1, 0, 0], np.float64)
@@ -510,39 +498,39 @@ def test_refusals():
         d = c.alloc(4096)
         try:
             # before any image size / mesh / frame set
-            assert _code(c.field_inverse_geometric, 0, m, g, IDX) == STATE
-            assert _code(c.field_inverse_geometric_device, 0, m, g, CO, d) == STATE
-            assert _code(c.field_inverse_geometric_frames_device, IDX, d) == STATE
-            assert _code(c.field_inverse_piecewise_frames_device, IDX, d) == STATE
+            assert GF.refusal_code(c.field_inverse_geometric, 0, m, g, IDX) == STATE
+            assert GF.refusal_code(c.field_inverse_geometric_device, 0, m, g, CO, d) == STATE
+            assert GF.refusal_code(c.field_inverse_geometric_frames_device, IDX, d) == STATE
+            assert GF.refusal_code(c.field_inverse_piecewise_frames_device, IDX, d) == STATE
             c.set_image(WL.lcg_image(16, 16, 1))
-            assert _code(c.field_inverse_geometric_frames_device, IDX, d) == STATE         # no frame set
-            assert _code(c.field_inverse_piecewise_frames_device, CO, d) == STATE          # no mesh
+            assert GF.refusal_code(c.field_inverse_geometric_frames_device, IDX, d) == STATE         # no frame set
+            assert GF.refusal_code(c.field_inverse_piecewise_frames_device, CO, d) == STATE          # no mesh
             sp, tris = WL.grid_points(16, 16, 2, 2), WL.grid_triangles(2, 2)
             c.piecewise_set_mesh(sp, tris, 0, 0)
-            assert _code(c.field_inverse_piecewise_frames_device, CO, d) == STATE          # no frame set
+            assert GF.refusal_code(c.field_inverse_piecewise_frames_device, CO, d) == STATE          # no frame set
             c.piecewise_prepare(sp, (0, 0, 16, 16))
             c.geometric_set_frames(0, np.concatenate([m, [0, 0]]), [g])
             # unknown formats, NULL pointers
             for fmt in (2, -1):
-                assert _code(c.field_inverse_geometric, 0, m, g, fmt) == INVALID
-                assert _code(c.field_inverse_geometric_device, 0, m, g, fmt, d) == INVALID
-                assert _code(c.field_inverse_geometric_frames_device, fmt, d) == INVALID
-                assert _code(c.field_inverse_piecewise, fmt) == INVALID
-                assert _code(c.field_inverse_piecewise_frames_device, fmt, d) == INVALID
-            assert _code(c.field_inverse_geometric_device, 0, m, g, IDX, 0) == INVALID
-            assert _code(c.field_inverse_geometric_frames_device, IDX, 0) == INVALID
-            assert _code(c.field_inverse_piecewise_frames_device, IDX, 0) == INVALID
-            assert _code(c.field_inverse_geometric_frames_device, CO, d, [4]) == INVALID   # an offset that is no multiple of the pixel size
+                assert GF.refusal_code(c.field_inverse_geometric, 0, m, g, fmt) == INVALID
+                assert GF.refusal_code(c.field_inverse_geometric_device, 0, m, g, fmt, d) == INVALID
+                assert GF.refusal_code(c.field_inverse_geometric_frames_device, fmt, d) == INVALID
+                assert GF.refusal_code(c.field_inverse_piecewise, fmt) == INVALID
+                assert GF.refusal_code(c.field_inverse_piecewise_frames_device, fmt, d) == INVALID
+            assert GF.refusal_code(c.field_inverse_geometric_device, 0, m, g, IDX, 0) == INVALID
+            assert GF.refusal_code(c.field_inverse_geometric_frames_device, IDX, 0) == INVALID
+            assert GF.refusal_code(c.field_inverse_piecewise_frames_device, IDX, 0) == INVALID
+            assert GF.refusal_code(c.field_inverse_geometric_frames_device, CO, d, [4]) == INVALID   # an offset that is no multiple of the pixel size
             # remaps
-            assert _code(c.remap_index_device, d, 16, d + 1024, 16, 3, d + 2048) == INVALID
-            assert _code(c.remap_index_device, d, 16, d + 1024, 16, 0, d + 2048) == INVALID
-            assert _code(c.remap_index_device, d, 16, d + 1024, 16, 8, d + 2048 + 4) == INVALID     # misaligned d_out
-            assert _code(c.remap_index_device, d, 16, d + 1024 + 2, 16, 4, d + 2048) == INVALID     # misaligned d_src
-            assert _code(c.remap_index_device, 0, 16, d + 1024, 16, 4, d + 2048) == INVALID
+            assert GF.refusal_code(c.remap_index_device, d, 16, d + 1024, 16, 3, d + 2048) == INVALID
+            assert GF.refusal_code(c.remap_index_device, d, 16, d + 1024, 16, 0, d + 2048) == INVALID
+            assert GF.refusal_code(c.remap_index_device, d, 16, d + 1024, 16, 8, d + 2048 + 4) == INVALID     # misaligned d_out
+            assert GF.refusal_code(c.remap_index_device, d, 16, d + 1024 + 2, 16, 4, d + 2048) == INVALID     # misaligned d_src
+            assert GF.refusal_code(c.remap_index_device, 0, 16, d + 1024, 16, 4, d + 2048) == INVALID
             for ch in (0, 5):
-                assert _code(c.remap_bilinear_f32_device, d, 16, d + 1024, 4, 4, ch, d + 2048) == INVALID
-            assert _code(c.remap_bilinear_f32_device, d, 16, d + 1024, 0, 4, 1, d + 2048) == INVALID
-            assert _code(c.remap_bilinear_f32_device, d + 4, 16, d + 1024, 4, 4, 1, d + 2048) == INVALID   # misaligned coordinates
+                assert GF.refusal_code(c.remap_bilinear_f32_device, d, 16, d + 1024, 4, 4, ch, d + 2048) == INVALID
+            assert GF.refusal_code(c.remap_bilinear_f32_device, d, 16, d + 1024, 0, 4, 1, d + 2048) == INVALID
+            assert GF.refusal_code(c.remap_bilinear_f32_device, d + 4, 16, d + 1024, 4, 4, 1, d + 2048) == INVALID   # misaligned coordinates
             # the context still works
             idx = c.field_inverse_geometric(0, m, g, IDX)
             assert np.array_equal(idx, np.arange(8)[None, :] + 16 * np.arange(8)[:, None])
@@ -553,12 +541,5 @@ def test_refusals():
 # ------------------------------------------------------------------------------------------------ the drop-in class
 def test_js_class_source_field():
     """tests/js/field_gpu.mjs: sourceField() of js/Homography.mjs on the real addon (gather == warp, NaN pattern, refusals as strings)."""
-    node = shutil.which("node")
-    addon = os.path.join(ROOT, "homography.js_amd", "lib", "hgwarp.node")
-    assert node is not None and os.path.exists(addon), "node and the N-API addon are needed on a GPU box"
-    p = subprocess.run([node, os.path.join(ROOT, "tests", "js", "field_gpu.mjs")], capture_output=True, text=True, timeout=300, cwd=ROOT)
-    line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
-    assert line, p.stdout[-2000:] + p.stderr[-2000:]
-    res = json.loads(line[-1])
-    assert p.returncode == 0 and res["ok"] and not res["fails"], (res["fails"], p.stderr[-2000:])
+    res = GF.run_node_case("field_gpu.mjs")
     assert set(res["report"]) == {"projective", "piecewise"}

@@ -10,6 +10,7 @@ import pytest
 
 from hgtest import fwd_edges as F
 from hgtest import fwd_field as M
+from hgtest import gpu_frames as GF
 from hgtest import hip
 from hgtest import oracle as O
 
@@ -345,12 +346,6 @@ def test_a_field_call_leaves_a_queued_warp_batch_alone():
 
 # ------------------------------------------------------------------------------------------------ refusals
 
-def _code(fn, *a):
-    with pytest.raises(HG.HgError) as e:
-        fn(*a)
-    return e.value.code
-
-
 def test_refusals():
     case = PW["rotated_90"]
     g, m6 = (0, 0, 64, 16), np.float64([1, 0, 0, 1, 0, 0])
@@ -361,20 +356,20 @@ def test_refusals():
     c = HG.Context(0)
     d_field = c.alloc(64 * 16 * 4 + case["geom"][2] * case["geom"][3] * 4 + 16)
     try:
-        assert _code(c.field_forward_geometric, 0, m6, g) == 4                                  # HG_ERR_STATE: no image
+        assert GF.refusal_code(c.field_forward_geometric, 0, m6, g) == 4                                  # HG_ERR_STATE: no image
         assert L.hg_field_forward_piecewise_batch_device(c._h, dpp, case["Mx"], case["My"], geoms, None, 1, C.c_void_p(d_field)) == 4
         c.set_image(F.image(case))
         assert L.hg_field_forward_piecewise_batch_device(c._h, dpp, case["Mx"], case["My"], geoms, None, 1, C.c_void_p(d_field)) == 4      # no mesh
-        assert _code(c.field_forward_geometric, 2, np.zeros(8), g) == 1                         # HG_ERR_INVALID: unknown kind
-        assert _code(c.field_forward_geometric_batch_device, 0, np.zeros(8), [g], [0], 0) == 1  # NULL field
+        assert GF.refusal_code(c.field_forward_geometric, 2, np.zeros(8), g) == 1                         # HG_ERR_INVALID: unknown kind
+        assert GF.refusal_code(c.field_forward_geometric_batch_device, 0, np.zeros(8), [g], [0], 0) == 1  # NULL field
         assert L.hg_field_forward_geometric(c._h, 0, m6.ctypes.data_as(C.POINTER(C.c_double)), HG.Geom(*g), None) == 1
         assert L.hg_field_forward_geometric(c._h, 0, None, HG.Geom(*g), C.c_void_p(d_field)) == 1
-        assert _code(c.field_forward_geometric_batch_device, 0, np.zeros(8), [g], [6], d_field) == 1      # offset not a multiple of 4
+        assert GF.refusal_code(c.field_forward_geometric_batch_device, 0, np.zeros(8), [g], [6], d_field) == 1      # offset not a multiple of 4
         _set(c, case)
-        assert _code(c.field_forward_piecewise_batch_device, case["dp"], case["Mx"], case["My"], [case["geom"]], [0], 0) == 1
+        assert GF.refusal_code(c.field_forward_piecewise_batch_device, case["dp"], case["Mx"], case["My"], [case["geom"]], [0], 0) == 1
         assert L.hg_field_forward_piecewise_batch_device(c._h, None, case["Mx"], case["My"], geoms, None, 1, C.c_void_p(d_field)) == 1
         assert L.hg_field_forward_piecewise(c._h, dpp, case["Mx"], case["My"], geoms[0], None) == 1
-        assert _code(c.field_forward_piecewise_batch_device, case["dp"], case["Mx"], case["My"], [case["geom"]], [2], d_field) == 1
+        assert GF.refusal_code(c.field_forward_piecewise_batch_device, case["dp"], case["Mx"], case["My"], [case["geom"]], [2], d_field) == 1
         assert c.last_forward_field_kernel() == 0 and c.last_forward_kernel() == 0
     finally:
         c.free(d_field); c.close()
@@ -386,7 +381,7 @@ def test_source_taller_than_65535_is_refused():
         c = _ctx(tiles)
         try:
             c.set_image(img)
-            assert _code(c.field_forward_geometric, 0, np.float64([0, 1, 1, 0, 0, 0]), (0, 0, F.SRC_MAX + 1, 16)) == 1
+            assert GF.refusal_code(c.field_forward_geometric, 0, np.float64([0, 1, 1, 0, 0, 0]), (0, 0, F.SRC_MAX + 1, 16)) == 1
         finally:
             c.close()
 
@@ -395,16 +390,7 @@ def test_source_taller_than_65535_is_refused():
 def test_js_class_source_field_loops():
     """tests/js/field_forward_gpu.mjs: sourceField(format, {loop}) of js/Homography.mjs on the real addon -- a same-size piecewise and a
     same-size affine instance: the 'warp' field gathers warp().data, the 'inverse' field warp(null, false, true).data; refusals are strings."""
-    import json, os, shutil, subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    node = shutil.which("node")
-    addon = os.path.join(root, "homography.js_amd", "lib", "hgwarp.node")
-    assert node is not None and os.path.exists(addon), "node and the N-API addon are needed on a GPU box"
-    p = subprocess.run([node, os.path.join(root, "tests", "js", "field_forward_gpu.mjs")], capture_output=True, text=True, timeout=300, cwd=root)
-    line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
-    assert line, p.stdout[-2000:] + p.stderr[-2000:]
-    res = json.loads(line[-1])
-    assert p.returncode == 0 and res["ok"] and not res["fails"], (res["fails"], p.stderr[-2000:])
+    res = GF.run_node_case("field_forward_gpu.mjs")
     assert set(res["report"]) == {"piecewise", "affine"}
     assert res["report"]["piecewise"]["forward_holes"] > 0
 
@@ -434,8 +420,8 @@ def test_source_of_2_to_the_31_pixels_is_refused():
     try:
         c.set_image_device(d_small, 65536, 32768)
         c.piecewise_set_mesh(case["sp"], case["tris"], case["msx"], case["msy"])
-        assert _code(c.field_forward_piecewise, case["dp"], case["Mx"], case["My"], case["geom"]) == 1
-        assert _code(c.field_forward_geometric, 0, np.float64([1, 0, 0, 1, 0, 0]), (0, 0, 64, 16)) == 1
+        assert GF.refusal_code(c.field_forward_piecewise, case["dp"], case["Mx"], case["My"], case["geom"]) == 1
+        assert GF.refusal_code(c.field_forward_geometric, 0, np.float64([1, 0, 0, 1, 0, 0]), (0, 0, 64, 16)) == 1
         assert c.last_forward_field_kernel() == 0
     finally:
         c.set_image(np.zeros((1, 1, 4), np.uint8))                    # drop the alias before the buffer goes away

@@ -5,10 +5,7 @@ every buffer is filled with 0xA5 before a call and the bytes outside the canvas 
 import base64
 import functools
 import hashlib
-import json
 import os
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -18,18 +15,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "homography.js_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import hgwarp as HG                          # noqa: E402
+from hgtest import gpu_frames as GF          # noqa: E402
 from hgtest import mosaic as MM              # noqa: E402
-from hgtest import oracle as O               # noqa: E402
+from hgtest.gpu_frames import CO, F32, F32E, FILL, INVALID, U8E      # noqa: E402
 from hgtest import remap_frames as RF        # noqa: E402
 from hgtest import workloads as WL           # noqa: E402
 
 pytestmark = pytest.mark.gpu
-CO = HG.FIELD_COORDS
-F32E, U8E = HG.ELEM_F32, HG.ELEM_U8
-F32 = np.float32
 INF = float("inf")
-INVALID = 1
-FILL, POISON = 0xA5, 0xEE                    # the canvas and the weights before a call; the bytes around the frames
 SW, SH = 67, 45                              # the source
 MODES = ((MM.LAST, 1.0), (MM.MEAN, 1.0), (MM.FEATHER, INF), (MM.FEATHER, 3.5))
 # windows that leave the canvas on each of its four sides, one wholly outside, a frame of width 1, an empty frame between full ones, two
@@ -45,19 +38,6 @@ def ctx():
     c = HG.Context(0)
     yield c
     c.close()
-
-
-def _es(elem):
-    return 1 if elem == U8E else 4
-
-
-def _split(raw, offs, geoms, px_bytes, dtype, cols):
-    out = []
-    for o, g in zip(offs, geoms):
-        a = raw[o:o + RF.n_px(g) * px_bytes].view(dtype).reshape(-1, cols).copy()
-        a.setflags(write=False)
-        out.append(a)
-    return out
 
 
 # ------------------------------------------------------------------------------------------------ inputs, made once and never modified
@@ -97,7 +77,7 @@ def _library_sets():
                     c.field_inverse_geometric_frames_device(CO, d_f)
                     c.warp_inverse_geometric_frames_device(d_o)
                 c.sync()
-                out[name] = (geoms, _split(c.to_host(d_f, ftotal), fo, geoms, 8, F32, 2), _split(c.to_host(d_o, ototal), oo, geoms, 4, np.uint8, 4))
+                out[name] = (geoms, GF.split(c.to_host(d_f, ftotal), fo, geoms, 8, F32, 2), GF.split(c.to_host(d_o, ototal), oo, geoms, 4, np.uint8, 4))
             finally:
                 c.free(d_f)
                 c.free(d_o)
@@ -119,53 +99,9 @@ def _frames(name, elem, ch):
     return tuple(out)
 
 
-def _place(parts, offs, total, fill):
-    buf = np.full(total, fill, np.uint8)
-    for p, o in zip(parts, offs):
-        b = np.ascontiguousarray(p).view(np.uint8).ravel()
-        buf[o:o + b.size] = b
-    return buf
-
-
-def _run(ctx, geoms, fields, frames, elem, ch, mode, feather, canvas, weight=True, foffs=None, poffs=None, front=0, cfront=0):
-    """Upload the fields (at foffs, or packed) and the frames (inside an allocation full of POISON, `front` bytes in; at poffs, or packed),
-    fill the canvas and the weight plane with FILL, run the mosaic, check that no byte outside the canvas extent (cfront bytes in) and the
-    weight extent changed, and return (canvas bytes, weights or None)."""
-    px = ch * _es(elem)
-    fo = list(foffs) if foffs is not None else RF.pack(geoms, 8)[0]
-    po = list(poffs) if poffs is not None else RF.pack(geoms, px)[0]
-    f_total = max([o + RF.n_px(g) * 8 for o, g in zip(fo, geoms)] + [0]) + 256
-    p_total = front + max([o + RF.n_px(g) * px for o, g in zip(po, geoms)] + [0]) + 256
-    n = max(canvas[2], 0) * max(canvas[3], 0)
-    c_total, w_total = cfront + n * px + 512, n * 4 + 512
-    d_f, d_p, d_c, d_w = ctx.alloc(f_total), ctx.alloc(p_total), ctx.alloc(c_total), ctx.alloc(w_total)
-    try:
-        ctx.to_device(d_f, _place(fields, fo, f_total, 0x11))
-        ctx.to_device(d_p, _place(frames, [front + o for o in po], p_total, POISON))
-        ctx.to_device(d_c, np.full(c_total, FILL, np.uint8))
-        ctx.to_device(d_w, np.full(w_total, FILL, np.uint8))
-        ctx.mosaic_frames_device(geoms, d_f, d_p + front, elem, ch, SW, SH, mode, feather, canvas, d_c + cfront, d_w if weight else 0, foffs, poffs)
-        ctx.sync()
-        raw, wraw = ctx.to_host(d_c, c_total), ctx.to_host(d_w, w_total)
-    finally:
-        for p in (d_f, d_p, d_c, d_w):
-            ctx.free(p)
-    assert (raw[:cfront] == FILL).all() and (raw[cfront + n * px:] == FILL).all(), "bytes outside the canvas must not be written"
-    assert (wraw[n * 4 if weight else 0:] == FILL).all(), "bytes outside the weight plane must not be written"
-    return raw[cfront:cfront + n * px], (wraw[:n * 4].view(F32) if weight else None)
-
-
-def _check(got, want, what):
-    canvas, weight = got
-    wc, ww = want
-    w = np.ascontiguousarray(wc).view(np.uint8).ravel()
-    if not np.array_equal(canvas, w):
-        bad = np.flatnonzero(canvas != w)
-        px = wc.dtype.itemsize * wc.shape[2]
-        raise AssertionError(f"{what}: {bad.size} of {w.size} bytes differ, first at pixel {int(bad[0]) // px} (row width {wc.shape[1]}): "
-                             f"got {canvas[bad[:8]].tolist()}, want {w[bad[:8]].tolist()}")
-    if weight is not None:
-        assert np.array_equal(weight.view(np.uint32), ww.ravel().view(np.uint32)), (what, "weight plane")
+def _run(ctx, geoms, fields, frames, elem, ch, mode, feather, canvas, **kw):
+    """GF.run_mosaic over the SW x SH source: (canvas bytes, weights or None); it checks the bytes outside the canvas and the weight plane."""
+    return GF.run_mosaic(ctx, geoms, fields, frames, elem, ch, SW, SH, mode, feather, canvas, **kw)
 
 
 def _contributors(geoms, fields, canvas):
@@ -187,7 +123,7 @@ def test_mosaic_of_the_librarys_projective_fields_and_warp_outputs(ctx, elem, ch
     frames = _frames("projective", elem, channels)
     for mode, feather in MODES:
         want = MM.mosaic(geoms, fields, frames, SW, SH, mode, feather, PRO_CANVAS)
-        _check(_run(ctx, geoms, fields, frames, elem, channels, mode, feather, PRO_CANVAS), want, ("projective", elem, channels, mode, feather))
+        GF.check_canvas(_run(ctx, geoms, fields, frames, elem, channels, mode, feather, PRO_CANVAS), want, ("projective", elem, channels, mode, feather))
 
 
 @pytest.mark.parametrize("channels", (1, 2, 3, 4))
@@ -201,7 +137,7 @@ def test_mosaic_of_a_piecewise_set_with_uncovered_pixels(ctx, elem, channels):
     frames = _frames("piecewise", elem, channels)
     for mode, feather in MODES:
         want = MM.mosaic(geoms, fields, frames, SW, SH, mode, feather, PW_CANVAS)
-        _check(_run(ctx, geoms, fields, frames, elem, channels, mode, feather, PW_CANVAS, weight=mode != MM.MEAN), want, ("piecewise", elem, channels, mode, feather))
+        GF.check_canvas(_run(ctx, geoms, fields, frames, elem, channels, mode, feather, PW_CANVAS, weight=mode != MM.MEAN), want, ("piecewise", elem, channels, mode, feather))
 
 
 @pytest.mark.parametrize("canvas", ((3, 2, 1, 7), (-6, 4, 67, 5), (-10, 11, 130, 3), (29, 9, 2, 2), (400, 400, 5, 3)))
@@ -211,7 +147,7 @@ def test_canvas_shapes_and_a_null_weight_plane(ctx, canvas):
         frames = _frames("projective", elem, ch)
         for k, (mode, feather) in enumerate(MODES):
             want = MM.mosaic(geoms, fields, frames, SW, SH, mode, feather, canvas)
-            _check(_run(ctx, geoms, fields, frames, elem, ch, mode, feather, canvas, weight=k % 2 == 0), want, (canvas, elem, ch, mode))
+            GF.check_canvas(_run(ctx, geoms, fields, frames, elem, ch, mode, feather, canvas, weight=k % 2 == 0), want, (canvas, elem, ch, mode))
     assert not MM.mosaic(geoms, fields, _frames("projective", U8E, 4), SW, SH, MM.MEAN, 1.0, (400, 400, 5, 3))[1].any()      # wholly beside every frame
 
 
@@ -242,7 +178,7 @@ def test_caller_made_fields_with_nan_infinite_and_huge_coordinates(ctx):
             want = MM.mosaic(PRO_GEOMS, fields, frames, SW, SH, mode, feather, PRO_CANVAS)
             if mode == MM.FEATHER:                                # the 1e30 pixels contribute, at the floor weight
                 assert (want[1] > 0).any() and float(MM.feather_weight(f0[5], SW, SH, feather)) == 2.0 ** -10
-            _check(_run(ctx, PRO_GEOMS, fields, frames, elem, ch, mode, feather, PRO_CANVAS), want, ("caller-made", elem, ch, mode, feather))
+            GF.check_canvas(_run(ctx, PRO_GEOMS, fields, frames, elem, ch, mode, feather, PRO_CANVAS), want, ("caller-made", elem, ch, mode, feather))
 
 
 def test_explicit_offsets_that_break_every_wider_alignment(ctx):
@@ -250,7 +186,7 @@ def test_explicit_offsets_that_break_every_wider_alignment(ctx):
     fo8 = [o + 8 * (2 * f + 1) + 512 * f for f, o in enumerate(RF.pack(PRO_GEOMS, 8)[0])]        # odd multiples of 8: no 16-byte alignment
     assert all(o % 8 == 0 and o % 16 != 0 for o in fo8)
     for elem in (U8E, F32E):
-        es = _es(elem)
+        es = GF.es(elem)
         for ch in (1, 2, 3, 4):
             frames = _frames("projective", elem, ch)
             po = [o + 640 * f + es * (2 * f + 1) for f, o in enumerate(RF.pack(PRO_GEOMS, ch * es)[0])]   # odd element offsets: no 2- or 4-byte load fits (u8)
@@ -258,12 +194,12 @@ def test_explicit_offsets_that_break_every_wider_alignment(ctx):
             for mode, feather in MODES[1:3]:
                 want = MM.mosaic(PRO_GEOMS, fields, frames, SW, SH, mode, feather, PRO_CANVAS)
                 got = _run(ctx, PRO_GEOMS, fields, frames, elem, ch, mode, feather, PRO_CANVAS, foffs=fo8, poffs=po, front=256 + 2 * es, cfront=es)
-                _check(got, want, ("explicit offsets", elem, ch, mode))
+                GF.check_canvas(got, want, ("explicit offsets", elem, ch, mode))
     # ... and where only SOME frames start aligned for the wide load, under an odd base
     frames = _frames("projective", U8E, 4)
     po = [o + (f % 4) for f, o in enumerate(RF.pack(PRO_GEOMS, 4)[0])]
     want = MM.mosaic(PRO_GEOMS, fields, frames, SW, SH, MM.LAST, 1.0, PRO_CANVAS)
-    _check(_run(ctx, PRO_GEOMS, fields, frames, U8E, 4, MM.LAST, 1.0, PRO_CANVAS, poffs=po, front=257, cfront=3), want, "mixed alignment")
+    GF.check_canvas(_run(ctx, PRO_GEOMS, fields, frames, U8E, 4, MM.LAST, 1.0, PRO_CANVAS, poffs=po, front=257, cfront=3), want, "mixed alignment")
 
 
 def test_2500_small_frames_thrown_over_the_canvas(ctx):
@@ -282,7 +218,7 @@ def test_2500_small_frames_thrown_over_the_canvas(ctx):
         frames = [rng.integers(1, 160, (RF.n_px(g), ch), dtype=np.uint8) if elem == U8E else (rng.standard_normal((RF.n_px(g), ch)) * 40).astype(F32) for g in geoms]
         for mode, feather in MODES[:3]:
             want = MM.mosaic(geoms, fields, frames, SW, SH, mode, feather, canvas)
-            _check(_run(ctx, geoms, fields, frames, elem, ch, mode, feather, canvas), want, ("2500 frames", elem, ch, mode))
+            GF.check_canvas(_run(ctx, geoms, fields, frames, elem, ch, mode, feather, canvas), want, ("2500 frames", elem, ch, mode))
 
 
 def test_no_frames_zero_the_canvas_and_an_empty_canvas_writes_nothing(ctx):
@@ -307,12 +243,6 @@ def test_no_frames_zero_the_canvas_and_an_empty_canvas_writes_nothing(ctx):
 
 
 # ------------------------------------------------------------------------------------------------ refusals
-def _code(fn, *a, **k):
-    with pytest.raises(HG.HgError) as e:
-        fn(*a, **k)
-    return e.value.code
-
-
 def test_refusals():
     g = [(0, 0, 8, 2), (4, 1, 4, 1)]
     cv = (0, 0, 8, 2)
@@ -321,8 +251,8 @@ def test_refusals():
         d_f, d_p, d_c, d_w = d, d + 4096, d + 8192, d + 12288
         co = (np.random.default_rng(2).random((20, 2)) * [7, 3]).astype(F32)
         px = np.arange(1, 21, dtype=np.float32).reshape(20, 1)
-        c.to_device(d_f, _place([co[:16], co[16:]], [0, 256], 512, 0))
-        c.to_device(d_p, _place([px[:16], px[16:]], [0, 256], 512, 0))
+        c.to_device(d_f, GF.place([co[:16], co[16:]], [0, 256], 512, 0))
+        c.to_device(d_p, GF.place([px[:16], px[16:]], [0, 256], 512, 0))
         want, ww = MM.mosaic(g, [co[:16], co[16:]], [px[:16], px[16:]], 8, 4, MM.FEATHER, 2.0, cv)
 
         def still_works():
@@ -334,7 +264,7 @@ def test_refusals():
             assert np.array_equal(raw[:64].view(F32), want.ravel()) and np.array_equal(wr[:64].view(F32), ww.ravel()) and (raw[64:] == FILL).all() and (wr[64:] == FILL).all()
 
         def refused(*a, **k):
-            assert _code(c.mosaic_frames_device, *a, **k) == INVALID, (a, k)
+            assert GF.refusal_code(c.mosaic_frames_device, *a, **k) == INVALID, (a, k)
             still_works()
 
         try:
@@ -378,24 +308,14 @@ def test_refusals():
 
 
 # ------------------------------------------------------------------------------------------------ what the call leaves alone
-def _state(c):
-    return (c.last_piecewise_kernel(), c.last_piecewise_variant(), c.last_piecewise_self(), c.last_piecewise_flag(), c.last_geometric_kernel(),
-            c.last_forward_kernel(), c.last_forward_field_kernel(), c.sampling, c.redone_frames(), c.layout_walks())
-
-
 def test_state_is_untouched_and_a_queued_nearest_warp_keeps_its_bytes():
     """The fields and the warp outputs stay on the device in the library's own layouts and go into the mosaic as they stand."""
     W, H, F = 64, 40, 3
-    img = WL.lcg_image(W, H, 81)
-    s4 = WL.corners(W, H)
-    d4s = [WL.projective_dst(W, H, 0.03 * k) * np.tile([0.6, 0.45], 4) + np.tile([7.0 * k, 3.0 * k], 4) for k in range(F)]
-    gg = [tuple(int(v) for v in O.transform_limits(1, O.projective_from_squares(s4, d4), W, H)) for d4 in d4s]
-    assert all(0 < g[2] <= 48 and 0 < g[3] <= 32 for g in gg), gg
+    img, s4, d4s, gg, offs, total = GF.oblique_projective_set((0.6, 0.45), (7.0, 3.0))      # windows of 48 x 32 at most, each 7 x 3 further on
     x0, y0 = min(g[0] for g in gg), min(g[1] for g in gg)
     canvas = (x0 - 2, y0 - 1, max(g[0] + g[2] for g in gg) - x0 + 3, max(g[1] + g[3] for g in gg) - y0 + 3)
     assert canvas[2] <= 130 and canvas[3] <= 40, canvas
     n = canvas[2] * canvas[3]
-    offs, total = HG.pack_offsets(gg)
     fo, ftotal = HG.pack_field_offsets(gg, CO)
     with HG.Context(0) as c:
         d_src, d_f, d_w, d_k, d_c, d_wt = c.alloc(img.nbytes), c.alloc(ftotal), c.alloc(total), c.alloc(total), c.alloc(n * 4), c.alloc(n * 4)
@@ -409,16 +329,16 @@ def test_state_is_untouched_and_a_queued_nearest_warp_keeps_its_bytes():
             c.field_inverse_geometric_frames_device(CO, d_f)
             c.sync()
             alone = c.to_host(d_w, total)
-            fields = _split(c.to_host(d_f, ftotal), fo, gg, 8, F32, 2)
-            frames = _split(alone, offs, gg, 4, np.uint8, 4)
+            fields = GF.split(c.to_host(d_f, ftotal), fo, gg, 8, F32, 2)
+            frames = GF.split(alone, offs, gg, 4, np.uint8, 4)
             assert alone.any() and _contributors(gg, fields, canvas).max() >= 2
             c.to_device(d_k, np.zeros(total, np.uint8))
             c.warp_inverse_geometric_frames_device(d_k)                   # queued ...
-            mid = _state(c)
+            mid = GF.tap_state(c)
             c.mosaic_frames_device(gg, d_f, d_w, U8E, 4, W, H, MM.FEATHER, 6.0, canvas, d_c, d_wt)      # ... in front of the mosaic of the first warp's frames
-            assert _state(c) == mid
+            assert GF.tap_state(c) == mid
             c.sync()
-            assert _state(c) == mid and c.sampling == HG.SAMPLE_NEAREST
+            assert GF.tap_state(c) == mid and c.sampling == HG.SAMPLE_NEAREST
             again = c.to_host(d_k, total)
             for f, g in enumerate(gg):                                    # (the padding between frames is nobody's)
                 assert np.array_equal(again[offs[f]:offs[f] + RF.n_px(g) * 4], alone[offs[f]:offs[f] + RF.n_px(g) * 4]), f
@@ -439,15 +359,8 @@ def test_a_queued_redo_never_lands_on_a_later_mosaic():
     a mosaic then writes its canvas at the start of B and its weight plane further into B.  After hg_sync both hold the mosaic's.  (The
     redo needs the wide source and window of the anisotropic test of the same name: a row must carry more spans than the row kernel
     holds; the mosaic's own canvas stays 130 x 40.)"""
-    n, W2, H2 = 1100, 2400, 8
-    img = WL.lcg_image(W2, H2, 10)
-    xs = np.linspace(0, W2, n + 1)
-    sp = np.stack([np.repeat(xs, 2), np.tile([0.0, H2], n + 1)], 1).astype(np.float32).ravel()
-    tr = np.array([[2 * i, 2 * i + 2, 2 * i + 1] for i in range(n)], np.uint32).ravel()
-    dp = sp.copy()
-    dp[1::2] *= 1.5
-    mm, md = O.minmax_xy(sp), O.minmax_xy(dp)
-    g = (int(md[0]), int(md[1]), int(md[2] - md[0]), int(md[3] - md[1]))
+    s = GF.strip_mesh_overflow()
+    img, W2, H2, g = s.img, s.W, s.H, s.g
     npx = g[2] * g[3]
     geoms, fields, warped = _library_sets()["projective"]
     canvas = PRO_CANVAS
@@ -461,11 +374,11 @@ def test_a_queued_redo_never_lands_on_a_later_mosaic():
         d_src, d_b, d_f, d_p = c.alloc(img.nbytes), c.alloc(npx * 4), c.alloc(ftotal), c.alloc(ptotal)
         try:
             c.to_device(d_src, img)
-            c.to_device(d_f, _place(fields, fo, ftotal, 0))
-            c.to_device(d_p, _place(warped, po, ptotal, 0))
+            c.to_device(d_f, GF.place(fields, fo, ftotal, 0))
+            c.to_device(d_p, GF.place(warped, po, ptotal, 0))
             c.set_image_device(d_src, W2, H2)
-            c.piecewise_set_mesh(sp, tr, int(mm[0]), int(mm[1]))
-            c.piecewise_set_frames(dp, [g], [0])
+            c.piecewise_set_mesh(s.sp, s.tris, *s.min_src)
+            c.piecewise_set_frames(s.dp, [g], [0])
             r0 = c.redone_frames()
             c.warp_inverse_piecewise_frames_device(d_b)
             c.mosaic_frames_device(geoms, d_f, d_p, U8E, 4, SW, SH, MM.FEATHER, INF, canvas, d_b, d_b + w_at)
@@ -485,17 +398,9 @@ def test_js_class_mosaic_matches_the_ctypes_pipeline():
     """tests/js/mosaic_gpu.mjs: h.mosaic of js/Homography.mjs on the real addon for an affine, a projective and a piecewise set; it prints
     its windows and the SHA-256 of every canvas and weight plane, and the same loop through ctypes -- stage the set, warp, export the
     coordinate fields, mosaic -- must hash alike."""
-    node = shutil.which("node")
-    addon = os.path.join(ROOT, "homography.js_amd", "lib", "hgwarp.node")
-    assert node is not None and os.path.exists(addon), "node and the N-API addon are needed on a GPU box"
-    p = subprocess.run([node, os.path.join(ROOT, "tests", "js", "mosaic_gpu.mjs")], capture_output=True, text=True, timeout=300, cwd=ROOT)
-    line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
-    assert line, p.stdout[-2000:] + p.stderr[-2000:]
-    res = json.loads(line[-1])
-    assert p.returncode == 0 and res["ok"] and not res["fails"], (res["fails"], p.stderr[-2000:])
+    res = GF.run_node_case("mosaic_gpu.mjs")
     W, H = res["W"], res["H"]
-    idx = np.arange(W * H * 4, dtype=np.int64)
-    img = ((idx * 7 + (idx >> 3) * 13) & 255).astype(np.uint8).reshape(H, W, 4)
+    img = GF.js_pattern_planes(W, H)[0]
     assert set(res["cases"]) == {"affine", "projective", "piecewise"}
     with HG.Context(0) as c:
         c.set_image(img)
@@ -524,7 +429,7 @@ def test_js_class_mosaic_matches_the_ctypes_pipeline():
                     c.warp_inverse_geometric_frames_device(d_o)
                     c.field_inverse_geometric_frames_device(CO, d_f)
                 c.sync()
-                fields = _split(c.to_host(d_f, ftotal), fo, geoms, 8, F32, 2)
+                fields = GF.split(c.to_host(d_f, ftotal), fo, geoms, 8, F32, 2)
                 assert _contributors(geoms, fields, canvas).max() >= 2, name         # the case does overlap
                 for key, (mode, feather) in case["runs"].items():
                     c.mosaic_frames_device(geoms, d_f, d_o, U8E, 4, W, H, mode, INF if feather is None else feather, canvas, d_c, d_w)

@@ -6,10 +6,7 @@ canvases of 130 x 40 at most, frames of 48 x 32 at most, except the one case tha
 before a call and the bytes outside its extent must keep it."""
 import base64
 import hashlib
-import json
 import os
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -19,20 +16,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "homography.js_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import hgwarp as HG                          # noqa: E402
-import test_gpu_mosaic as TM                 # noqa: E402  (its inputs and helpers; nothing of it is changed)
+import test_gpu_mosaic as TM                 # noqa: E402  (its inputs and its _run; nothing of it is changed)
+from hgtest import gpu_frames as GF          # noqa: E402
 from hgtest import mosaic as MM              # noqa: E402
 from hgtest import mosaic_gain as MG         # noqa: E402
-from hgtest import oracle as O               # noqa: E402
+from hgtest.gpu_frames import CO, F32, F32E, FILL, INVALID, POISON, U8E      # noqa: E402
 from hgtest import remap_frames as RF        # noqa: E402
-from hgtest import workloads as WL           # noqa: E402
 
 pytestmark = pytest.mark.gpu
-CO = HG.FIELD_COORDS
-F32E, U8E = HG.ELEM_F32, HG.ELEM_U8
-F32 = np.float32
 INF = float("inf")
-INVALID = 1
-FILL, POISON = TM.FILL, TM.POISON
 SW, SH = TM.SW, TM.SH
 MODES = TM.MODES
 PRO_GEOMS, PRO_CANVAS, PW_GEOMS, PW_CANVAS = TM.PRO_GEOMS, TM.PRO_CANVAS, TM.PW_GEOMS, TM.PW_CANVAS
@@ -51,8 +43,8 @@ def _upload(ctx, geoms, fields, frames, px, foffs, poffs, front):
     f_total = max([o + RF.n_px(g) * 8 for o, g in zip(fo, geoms)] + [0]) + 256
     p_total = front + max([o + RF.n_px(g) * px for o, g in zip(po, geoms)] + [0]) + 256
     d_f, d_p = ctx.alloc(f_total), ctx.alloc(p_total)
-    ctx.to_device(d_f, TM._place(fields, fo, f_total, 0x11))
-    ctx.to_device(d_p, TM._place(frames, [front + o for o in po], p_total, POISON))
+    ctx.to_device(d_f, GF.place(fields, fo, f_total, 0x11))
+    ctx.to_device(d_p, GF.place(frames, [front + o for o in po], p_total, POISON))
     return d_f, d_p
 
 
@@ -75,25 +67,9 @@ def _stats(ctx, geoms, fields, frames, ch, canvas, foffs=None, poffs=None, front
     return raw[sfront:sfront + n].copy().view(np.uint64).reshape(F, F, 2)
 
 
-def _run(ctx, geoms, fields, frames, elem, ch, mode, feather, canvas, gains, weight=True, foffs=None, poffs=None, front=0, cfront=0):
+def _run(ctx, geoms, fields, frames, elem, ch, mode, feather, canvas, gains, **kw):
     """TM._run with gains: (canvas bytes, weights or None); bytes outside the canvas and the weight plane must keep FILL."""
-    px = ch * TM._es(elem)
-    n = max(canvas[2], 0) * max(canvas[3], 0)
-    c_total, w_total = cfront + n * px + 512, n * 4 + 512
-    d_f, d_p = _upload(ctx, geoms, fields, frames, px, foffs, poffs, front)
-    d_c, d_w = ctx.alloc(c_total), ctx.alloc(w_total)
-    try:
-        ctx.to_device(d_c, np.full(c_total, FILL, np.uint8))
-        ctx.to_device(d_w, np.full(w_total, FILL, np.uint8))
-        ctx.mosaic_frames_device(geoms, d_f, d_p + front, elem, ch, SW, SH, mode, feather, canvas, d_c + cfront, d_w if weight else 0, foffs, poffs, gains=gains)
-        ctx.sync()
-        raw, wraw = ctx.to_host(d_c, c_total), ctx.to_host(d_w, w_total)
-    finally:
-        for p in (d_f, d_p, d_c, d_w):
-            ctx.free(p)
-    assert (raw[:cfront] == FILL).all() and (raw[cfront + n * px:] == FILL).all(), "bytes outside the canvas must not be written"
-    assert (wraw[n * 4 if weight else 0:] == FILL).all(), "bytes outside the weight plane must not be written"
-    return raw[cfront:cfront + n * px], (wraw[:n * 4].view(F32) if weight else None)
+    return GF.run_mosaic(ctx, geoms, fields, frames, elem, ch, SW, SH, mode, feather, canvas, gains, **kw)
 
 
 def _same_stats(got, want, what):
@@ -239,7 +215,7 @@ def test_gained_mosaic_equals_the_model(ctx, elem, channels):
             assert not np.array_equal(want[0], plain[0]) and np.array_equal(want[1], plain[1])      # the weights do not change
             if channels == 4 and mode == MM.LAST:                 # alpha stays unscaled
                 assert np.array_equal(np.ascontiguousarray(want[0][..., 3]).view(np.uint8), np.ascontiguousarray(plain[0][..., 3]).view(np.uint8)) and want[0][..., 3].any()
-            TM._check(_run(ctx, geoms, fields, frames, elem, channels, mode, feather, canvas, gains, weight=name == "projective" or mode != MM.MEAN),
+            GF.check_canvas(_run(ctx, geoms, fields, frames, elem, channels, mode, feather, canvas, gains, weight=name == "projective" or mode != MM.MEAN),
                       want, (name, elem, channels, mode, feather))
 
 
@@ -251,12 +227,12 @@ def test_no_gains_and_unit_gains_are_the_plain_mosaic(ctx, elem, channels):
     for mode, feather in MODES:
         plain = TM._run(ctx, geoms, fields, frames, elem, channels, mode, feather, PRO_CANVAS)
         want = MM.mosaic(geoms, fields, frames, SW, SH, mode, feather, PRO_CANVAS)
-        TM._check(plain, want, "plain")
+        GF.check_canvas(plain, want, "plain")
         for gains in (None, np.ones(len(geoms), F32)):
             got = _run(ctx, geoms, fields, frames, elem, channels, mode, feather, PRO_CANVAS, gains)
             assert np.array_equal(got[0], plain[0]) and np.array_equal(got[1].view(np.uint32), plain[1].view(np.uint32)), (elem, channels, mode, gains is None)
     L, vp = HG.lib(), HG.C.c_void_p                             # gains NULL through the C entry itself: it IS hg_mosaic_frames_device
-    px = channels * TM._es(elem)
+    px = channels * GF.es(elem)
     n = PRO_CANVAS[2] * PRO_CANVAS[3]
     d_f, d_p = _upload(ctx, geoms, fields, frames, px, None, None, 0)
     d_c, d_w = ctx.alloc(n * px + 512), ctx.alloc(n * 4 + 512)
@@ -269,7 +245,7 @@ def test_no_gains_and_unit_gains_are_the_plain_mosaic(ctx, elem, channels):
             ctx.sync()
             raw, wraw = ctx.to_host(d_c, n * px + 512), ctx.to_host(d_w, n * 4 + 512)
             assert (raw[n * px:] == FILL).all() and (wraw[n * 4:] == FILL).all()
-            TM._check((raw[:n * px], wraw[:n * 4].view(F32)), MM.mosaic(geoms, fields, frames, SW, SH, mode, feather, PRO_CANVAS), ("gains NULL", elem, channels, mode))
+            GF.check_canvas((raw[:n * px], wraw[:n * 4].view(F32)), MM.mosaic(geoms, fields, frames, SW, SH, mode, feather, PRO_CANVAS), ("gains NULL", elem, channels, mode))
     finally:
         for p in (d_f, d_p, d_c, d_w):
             ctx.free(p)
@@ -301,16 +277,10 @@ def test_a_gain_that_takes_bytes_beyond_255_saturates(ctx, channels):
         assert lit.any() and (want[0][..., :k][lit] == 255).mean() > 0.3 and (F32(1.75) * F32(200) > 255)      # g * p does exceed 255
         if channels == 4:
             assert (want[0][..., 3][lit] < 255).any()
-        TM._check(_run(ctx, PRO_GEOMS, fields, frames, U8E, channels, mode, feather, PRO_CANVAS, gains, poffs=po, front=259, cfront=1), want, ("saturating", channels, mode))
+        GF.check_canvas(_run(ctx, PRO_GEOMS, fields, frames, U8E, channels, mode, feather, PRO_CANVAS, gains, poffs=po, front=259, cfront=1), want, ("saturating", channels, mode))
 
 
 # ------------------------------------------------------------------------------------------------ refusals
-def _code(fn, *a, **k):
-    with pytest.raises(HG.HgError) as e:
-        fn(*a, **k)
-    return e.value.code
-
-
 def test_refusals():
     g = [(0, 0, 8, 2), (4, 1, 4, 1)]
     cv = (0, 0, 8, 2)
@@ -320,8 +290,8 @@ def test_refusals():
         co = (np.random.default_rng(2).random((20, 2)) * [7, 3]).astype(F32)
         px = np.arange(1, 21, dtype=np.uint8).reshape(20, 1)
         gains = np.array([1.5, 0.75], F32)
-        c.to_device(d_f, TM._place([co[:16], co[16:]], [0, 256], 512, 0))
-        c.to_device(d_p, TM._place([px[:16], px[16:]], [0, 256], 512, 0))
+        c.to_device(d_f, GF.place([co[:16], co[16:]], [0, 256], 512, 0))
+        c.to_device(d_p, GF.place([px[:16], px[16:]], [0, 256], 512, 0))
         want, ww = MG.mosaic_gain(g, [co[:16], co[16:]], [px[:16], px[16:]], 8, 4, MM.FEATHER, 2.0, cv, gains)
         wst = MG.overlap_stats(g, [co[:16], co[16:]], [px[:16], px[16:]], 1, cv)
         assert wst[0, 1, 0] == 4
@@ -337,7 +307,7 @@ def test_refusals():
             assert np.array_equal(sr[:64].view(np.uint64), wst.ravel()) and (sr[64:] == FILL).all()
 
         def refused(fn, *a, **k):
-            assert _code(fn, *a, **k) == INVALID, (a, k)
+            assert GF.refusal_code(fn, *a, **k) == INVALID, (a, k)
             still_works()
 
         try:
@@ -366,7 +336,7 @@ def test_refusals():
             still_works()
             # (f32 frames cannot be asked for: the entry has no element argument)  The solve's invalid sigmas:
             for sn, sg in ((0.0, 0.1), (10.0, -1.0), (float("nan"), 0.1), (10.0, INF)):
-                assert _code(HG.mosaic_solve_gains, wst, 1, sn, sg) == INVALID
+                assert GF.refusal_code(HG.mosaic_solve_gains, wst, 1, sn, sg) == INVALID
             still_works()
             got = HG.mosaic_solve_gains(wst, 1)
             assert got.shape == (2,) and (got > 0).all()
@@ -379,15 +349,11 @@ def test_state_is_untouched_and_a_queued_nearest_warp_keeps_its_bytes():
     """As the mosaic's test of this name: the warp outputs and fields stay on the device and go into the statistics and the gained mosaic
     as they stand, each queued behind a warp that must keep its bytes."""
     W, H, F = 64, 40, 3
-    img = WL.lcg_image(W, H, 81)
-    s4 = WL.corners(W, H)
-    d4s = [WL.projective_dst(W, H, 0.03 * k) * np.tile([0.6, 0.45], 4) + np.tile([7.0 * k, 3.0 * k], 4) for k in range(F)]
-    gg = [tuple(int(v) for v in O.transform_limits(1, O.projective_from_squares(s4, d4), W, H)) for d4 in d4s]
+    img, s4, d4s, gg, offs, total = GF.oblique_projective_set((0.6, 0.45), (7.0, 3.0))      # windows of 48 x 32 at most, each 7 x 3 further on
     x0, y0 = min(g[0] for g in gg), min(g[1] for g in gg)
     canvas = (x0 - 2, y0 - 1, max(g[0] + g[2] for g in gg) - x0 + 3, max(g[1] + g[3] for g in gg) - y0 + 3)
-    assert all(0 < g[2] <= 48 and 0 < g[3] <= 32 for g in gg) and canvas[2] <= 130 and canvas[3] <= 40, (gg, canvas)
+    assert canvas[2] <= 130 and canvas[3] <= 40, (gg, canvas)
     n = canvas[2] * canvas[3]
-    offs, total = HG.pack_offsets(gg)
     fo, ftotal = HG.pack_field_offsets(gg, CO)
     with HG.Context(0) as c:
         d_src, d_f, d_w, d_k, d_c, d_wt, d_s = c.alloc(img.nbytes), c.alloc(ftotal), c.alloc(total), c.alloc(total), c.alloc(n * 4), c.alloc(n * 4), c.alloc(F * F * 16)
@@ -401,22 +367,22 @@ def test_state_is_untouched_and_a_queued_nearest_warp_keeps_its_bytes():
             c.field_inverse_geometric_frames_device(CO, d_f)
             c.sync()
             alone = c.to_host(d_w, total)
-            fields = TM._split(c.to_host(d_f, ftotal), fo, gg, 8, F32, 2)
-            frames = TM._split(alone, offs, gg, 4, np.uint8, 4)
+            fields = GF.split(c.to_host(d_f, ftotal), fo, gg, 8, F32, 2)
+            frames = GF.split(alone, offs, gg, 4, np.uint8, 4)
             wst = MG.overlap_stats(gg, fields, frames, 4, canvas)
             assert alone.any() and (wst[..., 0][np.triu_indices(F, 1)] > 0).any()
             gains = HG.mosaic_solve_gains(wst, 4)
             for step in ("statistics", "gained mosaic"):
                 c.to_device(d_k, np.zeros(total, np.uint8))
                 c.warp_inverse_geometric_frames_device(d_k)               # queued ...
-                mid = TM._state(c)
+                mid = GF.tap_state(c)
                 if step == "statistics":                                  # ... in front of the call under test
                     c.mosaic_overlap_stats_device(gg, d_f, d_w, 4, canvas, d_s)
                 else:
                     c.mosaic_frames_device(gg, d_f, d_w, U8E, 4, W, H, MM.FEATHER, 6.0, canvas, d_c, d_wt, gains=gains)
-                assert TM._state(c) == mid, step
+                assert GF.tap_state(c) == mid, step
                 c.sync()
-                assert TM._state(c) == mid and c.sampling == HG.SAMPLE_NEAREST, step
+                assert GF.tap_state(c) == mid and c.sampling == HG.SAMPLE_NEAREST, step
                 again = c.to_host(d_k, total)
                 for f, g in enumerate(gg):                                # (the padding between frames is nobody's)
                     assert np.array_equal(again[offs[f]:offs[f] + RF.n_px(g) * 4], alone[offs[f]:offs[f] + RF.n_px(g) * 4]), (step, f)
@@ -436,15 +402,8 @@ def test_state_is_untouched_and_a_queued_nearest_warp_keeps_its_bytes():
 def test_a_queued_redo_never_lands_on_later_statistics():
     """As the mosaic's test of this name: a piecewise warp whose rows carry 1100 spans is queued into buffer B (its frame is flagged, to be
     redone through the map at hg_sync); the statistics are then written at the start of B.  After hg_sync they stand."""
-    n, W2, H2 = 1100, 2400, 8
-    img = WL.lcg_image(W2, H2, 10)
-    xs = np.linspace(0, W2, n + 1)
-    sp = np.stack([np.repeat(xs, 2), np.tile([0.0, H2], n + 1)], 1).astype(np.float32).ravel()
-    tr = np.array([[2 * i, 2 * i + 2, 2 * i + 1] for i in range(n)], np.uint32).ravel()
-    dp = sp.copy()
-    dp[1::2] *= 1.5
-    mm, md = O.minmax_xy(sp), O.minmax_xy(dp)
-    g = (int(md[0]), int(md[1]), int(md[2] - md[0]), int(md[3] - md[1]))
+    s = GF.strip_mesh_overflow()
+    img, W2, H2, g = s.img, s.W, s.H, s.g
     npx = g[2] * g[3]
     geoms, fields, warped = TM._library_sets()["projective"]
     F = len(geoms)
@@ -456,11 +415,11 @@ def test_a_queued_redo_never_lands_on_later_statistics():
         d_src, d_b, d_f, d_p = c.alloc(img.nbytes), c.alloc(npx * 4), c.alloc(ftotal), c.alloc(ptotal)
         try:
             c.to_device(d_src, img)
-            c.to_device(d_f, TM._place(fields, fo, ftotal, 0))
-            c.to_device(d_p, TM._place(warped, po, ptotal, 0))
+            c.to_device(d_f, GF.place(fields, fo, ftotal, 0))
+            c.to_device(d_p, GF.place(warped, po, ptotal, 0))
             c.set_image_device(d_src, W2, H2)
-            c.piecewise_set_mesh(sp, tr, int(mm[0]), int(mm[1]))
-            c.piecewise_set_frames(dp, [g], [0])
+            c.piecewise_set_mesh(s.sp, s.tris, *s.min_src)
+            c.piecewise_set_frames(s.dp, [g], [0])
             r0 = c.redone_frames()
             c.warp_inverse_piecewise_frames_device(d_b)
             c.mosaic_overlap_stats_device(geoms, d_f, d_p, 4, PRO_CANVAS, d_b)
@@ -478,17 +437,9 @@ def test_js_class_exposure_gain_matches_the_ctypes_pipeline():
     """tests/js/mosaic_gain_gpu.mjs: h.mosaic(sets, {exposure: 'gain'}) of js/Homography.mjs on the real addon for a projective and a
     piecewise set; it prints its windows and the SHA-256 of canvas, weight plane and gains, and the same loop through ctypes -- stage the
     set, warp, export the coordinate fields, statistics, 16 F^2 bytes down, solve, gained mosaic -- must hash alike."""
-    node = shutil.which("node")
-    addon = os.path.join(ROOT, "homography.js_amd", "lib", "hgwarp.node")
-    assert node is not None and os.path.exists(addon), "node and the N-API addon are needed on a GPU box"
-    p = subprocess.run([node, os.path.join(ROOT, "tests", "js", "mosaic_gain_gpu.mjs")], capture_output=True, text=True, timeout=300, cwd=ROOT)
-    line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
-    assert line, p.stdout[-2000:] + p.stderr[-2000:]
-    res = json.loads(line[-1])
-    assert p.returncode == 0 and res["ok"] and not res["fails"], (res["fails"], p.stderr[-2000:])
+    res = GF.run_node_case("mosaic_gain_gpu.mjs")
     W, H = res["W"], res["H"]
-    idx = np.arange(W * H * 4, dtype=np.int64)
-    img = ((idx * 7 + (idx >> 3) * 13) & 255).astype(np.uint8).reshape(H, W, 4)
+    img = GF.js_pattern_planes(W, H)[0]
     assert set(res["cases"]) == {"projective", "piecewise"}
     with HG.Context(0) as c:
         c.set_image(img)

@@ -5,13 +5,12 @@ the premises that make wrong frame indexing visible are asserted in tests/test_m
 import hashlib
 import json
 import os
-import shutil
-import subprocess
 import tempfile
 
 import numpy as np
 import pytest
 
+from hgtest import gpu_frames as GF
 from hgtest import hip
 from hgtest import moving as M
 from hgtest import oracle as O
@@ -387,9 +386,6 @@ def test_js_class_warp_batch_with_source_points():
     """warpBatch(dst, {sourcePoints, images}) of the class for Set A, bilinear and nearest (every window is taller than the source: warp()
     picks the inverse loop).  The class mirrors the reference's caches: the source minima are refreshed only while its map field is null,
     so every frame is tested against frame 0's minima (:252, :756-758) -- the oracle is called with exactly that."""
-    node = shutil.which("node")
-    addon = os.path.join(ROOT, "homography.js_amd", "lib", "hgwarp.node")
-    assert node is not None and os.path.exists(addon), "node and the N-API addon are needed on a GPU box"
     ms = M.set_a(4)
     assert all(g[3] > ms.H for g in ms.geoms)
     with tempfile.TemporaryDirectory() as tmp:
@@ -397,10 +393,7 @@ def test_js_class_warp_batch_with_source_points():
         with open(path, "w") as fh:
             json.dump({"W": ms.W, "H": ms.H, "seed0": 40, "tris": [int(t) for t in ms.tris],
                        "src": [[float(v) for v in a] for a in ms.srcs], "dst": [[float(v) for v in a] for a in ms.dsts]}, fh)
-        p = subprocess.run([node, os.path.join(ROOT, "tests", "js", "moving_gpu.mjs"), path], capture_output=True, text=True, timeout=600, cwd=ROOT)
-    line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
-    assert p.returncode == 0 and line, p.stdout[-2000:] + p.stderr[-2000:]
-    res = json.loads(line[-1])
+        res = GF.run_node_case("moving_gpu.mjs", path, timeout=600, verdict=False)      # (its record carries `failures`)
     assert res["failures"] == [], res["failures"]
     assert len(res["bilinear"]) == ms.F and len(res["nearest_inverse"]) == ms.F
     for f in range(ms.F):

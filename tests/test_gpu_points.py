@@ -3,10 +3,7 @@ uint32 views) against two anchors: the library's own HG_FIELD_COORDS fields at e
 tests/hgtest/points.py (pinned to the field model and to the oracle's forward warps by tests/test_points_cpu.py) everywhere else.  The
 model's maps and matrices come from the CPU oracle, never from the library under test."""
 import functools
-import json
 import os
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -17,6 +14,7 @@ sys.path.insert(0, os.path.join(ROOT, "homography.js_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import hgwarp as HG                          # noqa: E402
 from hgtest import folds as FO               # noqa: E402
+from hgtest import gpu_frames as GF          # noqa: E402
 from hgtest import moving as M               # noqa: E402
 from hgtest import oracle as O               # noqa: E402
 from hgtest import points as P               # noqa: E402
@@ -37,12 +35,8 @@ def ctx():
     c.close()
 
 
-def _u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def _same(got, want, what):
-    g, w = _u32(got).reshape(-1, 2), _u32(want).reshape(-1, 2)
+    g, w = GF.u32(got).reshape(-1, 2), GF.u32(want).reshape(-1, 2)
     assert g.shape == w.shape, (what, g.shape, w.shape)
     bad = np.flatnonzero((g != w).any(1))
     if bad.size:
@@ -101,7 +95,7 @@ def anchor(ctx, pcall, fcall, geoms, what):
         want[:max(g[3], 0), :max(g[2], 0)] = flds[f]
         _same(got[f], want, (what, f))
         if g[2] > 0 and g[3] > 0:
-            nan = _u32(flds[f])[..., 0] == NAN
+            nan = GF.u32(flds[f])[..., 0] == NAN
             assert not nan.all(), (what, f, "nothing mapped")
     return got
 
@@ -204,7 +198,7 @@ def test_fractional_points_geometric(ctx, kind):
     got = run(ctx, ctx.points_to_source_geometric_frames_device, pts, 2)
     for f in range(2):
         want = P.to_source_geometric(kind, inv[f], pts, geoms[f], W, H)
-        nan = (_u32(want) == NAN).all(1)
+        nan = (GF.u32(want) == NAN).all(1)
         assert nan[1000:].sum() >= 8 and 100 < nan[:1000].sum() < 1000
         _same(got[f], want, ("to source", kind, f))
     fwd = np.array([GEO_FWD[kind][1], GEO_FWD[kind][1]], np.float64)
@@ -213,17 +207,17 @@ def test_fractional_points_geometric(ctx, kind):
     got = run(ctx, lambda p, n, s, o: ctx.points_to_output_geometric_batch_device(kind, fwd, geoms, p, n, s, o), pts, 2)
     for f in range(2):
         want = P.to_output_geometric(kind, fwd[f], pts, geoms[f], W, H)
-        assert 0 < (_u32(want) == NAN).all(1).sum() < 400
+        assert 0 < (GF.u32(want) == NAN).all(1).sum() < 400
         _same(got[f], want, ("to output", kind, f))
     # one list per frame (n_sets = F): frame f reads list f, in both directions
     lists = np.stack([fractional(31 + kind, 0, 0, W, H), fractional(41 + kind, 0, 0, W, H)])
-    assert not np.array_equal(_u32(lists[0]), _u32(lists[1]))
+    assert not np.array_equal(GF.u32(lists[0]), GF.u32(lists[1]))
     got = run(ctx, ctx.points_to_source_geometric_frames_device, lists, 2, 2)
     gout = run(ctx, lambda p, n, s, o: ctx.points_to_output_geometric_batch_device(kind, fwd, geoms, p, n, s, o), lists, 2, 2)
     for f in range(2):
         _same(got[f], P.to_source_geometric(kind, inv[f], lists[f], geoms[f], W, H), ("to source, own list", kind, f))
         _same(gout[f], P.to_output_geometric(kind, fwd[f], lists[f], geoms[f], W, H), ("to output, own list", kind, f))
-        assert not np.array_equal(_u32(got[f]), _u32(P.to_source_geometric(kind, inv[f], lists[1 - f], geoms[f], W, H)))
+        assert not np.array_equal(GF.u32(got[f]), GF.u32(P.to_source_geometric(kind, inv[f], lists[1 - f], geoms[f], W, H)))
 
 
 def test_fractional_points_piecewise(ctx):
@@ -238,7 +232,7 @@ def test_fractional_points_piecewise(ctx):
     got = run(ctx, ctx.points_to_source_piecewise_frames_device, pts, 2)
     for f in range(2):
         want = P.to_source_piecewise_mesh(sp, dsts[f], tris, pts, geoms[f], W, H, msx, msy)
-        assert 100 < (_u32(want) == NAN).all(1).sum() < 1000
+        assert 100 < (GF.u32(want) == NAN).all(1).sum() < 1000
         _same(got[f], want, ("to source", f))
     x0, y0, x1, y1 = src_box(sp)
     pts = fractional(41, x0, y0, x1 - x0, y1 - y0)
@@ -246,7 +240,7 @@ def test_fractional_points_piecewise(ctx):
     fmap = P.forward_map(sp, tris, x0, y0, x1, y1)
     for f in range(2):
         want = P.to_output_piecewise(fmap, O.piecewise_matrices(sp, dsts[f], tris), pts, geoms[f], x0, y0, x1, y1)
-        assert 0 < (_u32(want) == NAN).all(1).sum() < 400
+        assert 0 < (GF.u32(want) == NAN).all(1).sum() < 400
         _same(got[f], want, ("to output", f))
 
 
@@ -315,7 +309,7 @@ def test_irregular_frames_are_redone_through_the_map(ctx):
     assert ctx.redone_frames() == r0 + 2
     for f in range(3):
         _same(own[f], P.to_source_piecewise_mesh(sp2, dsts[f], tr2, lists[f], geoms[f], W, H, msx, msy), ("redo, own list", f))
-    assert not np.array_equal(_u32(own[2]), _u32(P.to_source_piecewise_mesh(sp2, dsts[2], tr2, lists[0], geoms[2], W, H, msx, msy)))
+    assert not np.array_equal(GF.u32(own[2]), GF.u32(P.to_source_piecewise_mesh(sp2, dsts[2], tr2, lists[0], geoms[2], W, H, msx, msy)))
     # the unflagged mesh without that triangle agrees wherever the triangle covers nothing
     ctx.piecewise_set_mesh(sp, tris, msx, msy)
     ctx.piecewise_set_frames(dp, [WIN])
@@ -328,7 +322,7 @@ def test_irregular_frames_are_redone_through_the_map(ctx):
     free = ~ins
     free[ins] = ~alone[cy[ins].astype(np.int64) * WIN[2] + cx[ins].astype(np.int64)]
     assert free.sum() > pts.shape[0] // 2
-    assert np.array_equal(_u32(plain)[free], _u32(got[0])[free])
+    assert np.array_equal(GF.u32(plain)[free], GF.u32(got[0])[free])
 
 
 # ------------------------------------------------------------------------------------------------ to output, piecewise
@@ -346,7 +340,7 @@ def test_to_output_piecewise_paints_the_forward_warp_and_reuses_the_map(ctx):
     call = lambda p, n, s, o: ctx.points_to_output_piecewise_batch_device(dp, x1, y1, [g], p, n, s, o)      # noqa: E731
     res = run(ctx, call, pts, 1)[0]
     again = run(ctx, call, pts, 1)[0]                                    # the cached forward map
-    assert np.array_equal(_u32(res), _u32(again))
+    assert np.array_equal(GF.u32(res), GF.u32(again))
     _same(res, P.to_output_piecewise(fmap, fwd, pts, g, x0, y0, x1, y1), "model")
     x, y, ok = P.to_output_piecewise(fmap, fwd, pts, g, x0, y0, x1, y1, raw=True)
     p64 = pts.astype(np.int64)
@@ -421,12 +415,6 @@ def test_a_queued_flagged_batch_is_settled_by_the_points_call(ctx):
 
 
 # ------------------------------------------------------------------------------------------------ refusals
-def _code(fn, *a):
-    with pytest.raises(HG.HgError) as e:
-        fn(*a)
-    return e.value.code
-
-
 def test_refusals():
     INVALID, STATE = 1, 4
     m8 = np.array([[1, 0, 0, 1, 0, 0, 0, 0]], np.float64)
@@ -441,33 +429,33 @@ def test_refusals():
             out_p = lambda *a: c.points_to_output_piecewise_batch_device(sp, 16, 16, [g], *a)   # noqa: E731
             calls = (src_g, src_p, out_g, out_p)
             for fn in calls:                                             # no image / mesh / frame set yet
-                assert _code(fn, d, 4, 1, d + 1024) == STATE
+                assert GF.refusal_code(fn, d, 4, 1, d + 1024) == STATE
                 fn(d, 0, 1, d + 1024)                                    # n_points == 0: nothing happens, whatever the state
                 fn(0, 0, 1, 0)
             c.set_image(WL.lcg_image(16, 16, 1))
-            assert _code(src_g, d, 4, 1, d + 1024) == STATE              # no frame set
-            assert _code(src_p, d, 4, 1, d + 1024) == STATE              # no mesh
-            assert _code(out_p, d, 4, 1, d + 1024) == STATE
+            assert GF.refusal_code(src_g, d, 4, 1, d + 1024) == STATE              # no frame set
+            assert GF.refusal_code(src_p, d, 4, 1, d + 1024) == STATE              # no mesh
+            assert GF.refusal_code(out_p, d, 4, 1, d + 1024) == STATE
             c.piecewise_set_mesh(sp, tris, 0, 0)
-            assert _code(src_p, d, 4, 1, d + 1024) == STATE              # no frame set
+            assert GF.refusal_code(src_p, d, 4, 1, d + 1024) == STATE              # no frame set
             c.piecewise_prepare(sp, (0, 0, 16, 16))
             c.geometric_set_frames(0, m8, [g])
             for fn in calls:
-                assert _code(fn, 0, 4, 1, d + 1024) == INVALID           # NULL pointers with work to do
-                assert _code(fn, d, 4, 1, 0) == INVALID
-                assert _code(fn, d, -1, 1, d + 1024) == INVALID
-                assert _code(fn, d, (1 << 24) + 1, 1, d + 1024) == INVALID
-                assert _code(fn, d, 4, 0, d + 1024) == INVALID
-                assert _code(fn, d + 4, 4, 1, d + 1024) == INVALID       # misaligned
-                assert _code(fn, d, 4, 1, d + 1028) == INVALID
-            assert _code(c.points_to_output_geometric_batch_device, 2, m8, [g], d, 4, 1, d + 1024) == INVALID     # unknown kind
+                assert GF.refusal_code(fn, 0, 4, 1, d + 1024) == INVALID           # NULL pointers with work to do
+                assert GF.refusal_code(fn, d, 4, 1, 0) == INVALID
+                assert GF.refusal_code(fn, d, -1, 1, d + 1024) == INVALID
+                assert GF.refusal_code(fn, d, (1 << 24) + 1, 1, d + 1024) == INVALID
+                assert GF.refusal_code(fn, d, 4, 0, d + 1024) == INVALID
+                assert GF.refusal_code(fn, d + 4, 4, 1, d + 1024) == INVALID       # misaligned
+                assert GF.refusal_code(fn, d, 4, 1, d + 1028) == INVALID
+            assert GF.refusal_code(c.points_to_output_geometric_batch_device, 2, m8, [g], d, 4, 1, d + 1024) == INVALID     # unknown kind
             # the context still works
             pts = np.float32([[1, 2], [3.5, 4.25], [7.5, 0], [15.5, 3], [np.nan, 0]])
             fmap, fwd = P.forward_map(sp, tris, 0, 0, 16, 16), O.piecewise_matrices(sp, sp, tris)
             want = {src_g: P.to_source_geometric(0, m8[0], pts, g, 16, 16), src_p: P.to_source_piecewise_mesh(sp, sp, tris, pts, (0, 0, 16, 16), 16, 16, 0, 0),
                     out_g: P.to_output_geometric(0, m8[0], pts, g, 16, 16), out_p: P.to_output_piecewise(fmap, fwd, pts, g, 0, 0, 16, 16)}
             for fn in calls:
-                nan = (_u32(want[fn]) == NAN).all(1)
+                nan = (GF.u32(want[fn]) == NAN).all(1)
                 assert nan[4] and not nan[:2].any(), want[fn]
                 _same(run(c, fn, pts, 1)[0], want[fn], "after the refusals")
         finally:
@@ -478,14 +466,7 @@ def test_refusals():
 def test_js_class_transform_points():
     """tests/js/points_gpu.mjs: transformPoints() of js/Homography.mjs on the real addon, both directions, the three transforms; the ctypes
     calls on the same state give the same bits."""
-    node = shutil.which("node")
-    addon = os.path.join(ROOT, "homography.js_amd", "lib", "hgwarp.node")
-    assert node is not None and os.path.exists(addon), "node and the N-API addon are needed on a GPU box"
-    p = subprocess.run([node, os.path.join(ROOT, "tests", "js", "points_gpu.mjs")], capture_output=True, text=True, timeout=300, cwd=ROOT)
-    line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
-    assert line, p.stdout[-2000:] + p.stderr[-2000:]
-    res = json.loads(line[-1])
-    assert p.returncode == 0 and res["ok"] and not res["fails"], (res["fails"], p.stderr[-2000:])
+    res = GF.run_node_case("points_gpu.mjs")
     W2, H2 = res["W"], res["H"]
     pts_src, pts_out = np.float32(res["points_source"]), np.float32(res["points_output"])
     with HG.Context(0) as c:

@@ -3,10 +3,7 @@ hg_remap_bilinear_frames_device, hg_remap_bilinear_u8_device) against the numpy 
 bit for bit --, against the loop of single-list calls, and against the warps whose geometry the fields carry.  tests/test_remap_frames_cpu.py
 pins the u8 model itself on hand-computed cases."""
 import functools
-import json
 import os
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -18,16 +15,15 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import hgwarp as HG                          # noqa: E402
 from hgtest import field as FM               # noqa: E402
 from hgtest import fwd_edges as FE           # noqa: E402
+from hgtest import gpu_frames as GF          # noqa: E402
+from hgtest.gpu_frames import CO, F32E, FILL, INVALID, POISON, U8E      # noqa: E402
 from hgtest import moving as MV              # noqa: E402
 from hgtest import oracle as O               # noqa: E402
 from hgtest import remap_frames as RF        # noqa: E402
 from hgtest import workloads as WL           # noqa: E402
 
 pytestmark = pytest.mark.gpu
-IDX, CO = HG.FIELD_INDEX, HG.FIELD_COORDS
-F32E, U8E = HG.ELEM_F32, HG.ELEM_U8
-INVALID = 1
-FILL, POISON = 0xA5, 0xEE                    # the output before a call; the bytes around the source planes
+IDX = HG.FIELD_INDEX
 SW, SH = 97, 61                              # the small source
 N_SRC = SW * SH
 # pixel counts 1, 3, 4, 5, an empty frame in the middle, 255, 257, 1021 and one frame of several blocks
@@ -75,70 +71,21 @@ def _coord_fields():
 @functools.lru_cache(maxsize=None)
 def _planes(dtype, per_px, n=3):
     """n source planes of per_px elements per pixel; no byte of a uint8 plane equals FILL or POISON."""
-    rng = np.random.default_rng(1000 + per_px + (0 if dtype == "u8" else 50))
-    if dtype == "u8":
-        ps = [rng.integers(1, 160, (N_SRC, per_px), dtype=np.uint8) for _ in range(n)]
-    else:
-        ps = [rng.standard_normal((N_SRC, per_px)).astype(np.float32) for _ in range(n)]
-    for p in ps:
-        p.setflags(write=False)
-    return tuple(ps)
+    return GF.random_planes(1000 + per_px + (0 if dtype == "u8" else 50), U8E if dtype == "u8" else F32E, (N_SRC, per_px), n, f32_affine=None)
 
 
-def _place(parts, offs, total, fill):
-    buf = np.full(total, fill, np.uint8)
-    for p, o in zip(parts, offs):
-        b = np.ascontiguousarray(p).view(np.uint8).ravel()
-        buf[o:o + b.size] = b
-    return buf
-
-
-def _run(ctx, geoms, fields, fld_px, planes, px_bytes, call, foffs=None, ooffs=None, stride=None, front=256):
-    """Upload the fields (at foffs, or packed) and the planes (inside a larger allocation full of POISON, `front` bytes in, `stride` apart),
-    fill the output with FILL, run call(d_field, d_planes, stride, d_out), and return (output bytes, output offsets)."""
-    fo = list(foffs) if foffs is not None else RF.pack(geoms, fld_px)[0]
-    oo = list(ooffs) if ooffs is not None else RF.pack(geoms, px_bytes)[0]
-    plane_bytes = planes[0].nbytes
-    stride = stride if stride is not None else (plane_bytes + 255) // 256 * 256 + 256
-    assert stride >= plane_bytes
-    f_total = max([o + RF.n_px(g) * fld_px for o, g in zip(fo, geoms)] + [0]) + 256
-    o_total = max([o + RF.n_px(g) * px_bytes for o, g in zip(oo, geoms)] + [0]) + 512
-    p_total = front + stride * len(planes) + 256
-    d_f, d_p, d_o = ctx.alloc(f_total), ctx.alloc(p_total), ctx.alloc(o_total)
-    try:
-        ctx.to_device(d_f, _place(fields, fo, f_total, 0x11))
-        ctx.to_device(d_p, _place(planes, [front + k * stride for k in range(len(planes))], p_total, POISON))
-        ctx.to_device(d_o, np.full(o_total, FILL, np.uint8))
-        call(d_f, d_p + front, stride, d_o)
-        ctx.sync()
-        return ctx.to_host(d_o, o_total), oo
-    finally:
-        for p in (d_f, d_p, d_o):
-            ctx.free(p)
-
-
-def _check(raw, oo, geoms, want, px_bytes, what):
-    """Every frame equals the model, bit for bit, and every byte outside the frames is still FILL."""
-    untouched = np.ones(raw.size, bool)
-    for f, g in enumerate(geoms):
-        n = RF.n_px(g) * px_bytes
-        untouched[oo[f]:oo[f] + n] = False
-        w = np.ascontiguousarray(want[f]).view(np.uint8).ravel()
-        assert w.size == n, (what, f)
-        got = raw[oo[f]:oo[f] + n]
-        if not np.array_equal(got, w):
-            bad = np.flatnonzero(got != w)
-            raise AssertionError(f"{what}: frame {f}: {bad.size} of {n} bytes differ, first at pixel {int(bad[0]) // px_bytes} of {RF.n_px(g)}: "
-                                 f"got {got[bad[:8]].tolist()}, want {w[bad[:8]].tolist()}")
-    assert (raw[untouched] == FILL).all(), (what, "bytes between the frames, the padding and the tail must not be written")
+def _run(*a, **k):
+    """GF.run_frames(ctx, geoms, fields, fld_px, planes, px_bytes, call, foffs, ooffs, stride, front): (output bytes, output offsets)."""
+    ran = GF.run_frames(*a, **k)
+    return ran.raw, ran.oo
 
 
 def _index_call(ctx, geoms, pb, n_planes, foffs=None, ooffs=None):
-    return lambda d_f, d_p, stride, d_o: ctx.remap_index_frames_device(geoms, d_f, d_p, N_SRC, n_planes, stride, pb, d_o, foffs, ooffs)
+    return lambda b: ctx.remap_index_frames_device(geoms, b.d_f, b.d_p, N_SRC, n_planes, b.stride, pb, b.d_o, foffs, ooffs)
 
 
 def _bilinear_call(ctx, geoms, elem, ch, n_planes, foffs=None, ooffs=None):
-    return lambda d_f, d_p, stride, d_o: ctx.remap_bilinear_frames_device(geoms, d_f, d_p, SW, SH, n_planes, stride, elem, ch, d_o, foffs, ooffs)
+    return lambda b: ctx.remap_bilinear_frames_device(geoms, b.d_f, b.d_p, SW, SH, n_planes, b.stride, elem, ch, b.d_o, foffs, ooffs)
 
 
 def _hwc(planes, ch):
@@ -159,7 +106,7 @@ def test_index_frames_of_a_ragged_set(ctx, pixel_bytes, n_planes):
     want = RF.index_frames(RAGGED, _index_fields(), planes)
     assert any(w.any() for w in want) and not want[5][:4].any()
     raw, oo = _run(ctx, RAGGED, _index_fields(), 4, planes, pixel_bytes, _index_call(ctx, RAGGED, pixel_bytes, n_planes))
-    _check(raw, oo, RAGGED, want, pixel_bytes, ("index", pixel_bytes, n_planes))
+    GF.check_frames(raw, oo, RAGGED, want, pixel_bytes, ("index", pixel_bytes, n_planes))
     assert not (raw == POISON).any()
 
 
@@ -172,17 +119,17 @@ def test_bilinear_frames_of_a_ragged_set(ctx, elem, channels, n_planes):
     want = RF.bilinear_frames(RAGGED, _coord_fields(), _hwc(planes, channels))
     assert not want[8][:4].any() and want[8][4:8].any()       # NaN / infinite coordinates: zeros; 1e30, -1e30, -1e-30: clamped taps
     raw, oo = _run(ctx, RAGGED, _coord_fields(), 8, planes, px, _bilinear_call(ctx, RAGGED, elem, channels, n_planes))
-    _check(raw, oo, RAGGED, want, px, ("bilinear", elem, channels, n_planes))
+    GF.check_frames(raw, oo, RAGGED, want, px, ("bilinear", elem, channels, n_planes))
 
 
 # ------------------------------------------------------------------------------------------------ the frames form == the loop of single calls
 def _loop_of_singles(ctx, single):
     """single(f, d_field_f, n_px, d_plane_f, d_out_f) for every non-empty frame, over the packed layouts."""
     def call(fo, oo, n_planes):
-        def run(d_f, d_p, stride, d_o):
+        def run(b):
             for f, g in enumerate(RAGGED):
                 if RF.n_px(g):
-                    single(d_f + fo[f], RF.n_px(g), d_p + (f % n_planes) * stride, d_o + oo[f])
+                    single(b.d_f + fo[f], RF.n_px(g), b.d_p + (f % n_planes) * b.stride, b.d_o + oo[f])
         return run
     return call
 
@@ -226,7 +173,7 @@ def test_offsets_and_strides_that_break_the_packed_alignment(ctx):
         want = RF.index_frames(RAGGED, _index_fields(), planes)
         for fo_, oo_ in ((fo4, oo), (None, oo), (fo4, None)):
             raw, used = _run(ctx, RAGGED, _index_fields(), 4, planes, pb, _index_call(ctx, RAGGED, pb, 3, fo_, oo_), fo_, oo_, stride, front=256 + pb)
-            _check(raw, used, RAGGED, want, pb, ("index, explicit offsets", pb, fo_ is None, oo_ is None))
+            GF.check_frames(raw, used, RAGGED, want, pb, ("index, explicit offsets", pb, fo_ is None, oo_ is None))
     fo8 = [o + 8 * (2 * f + 1) + 512 * f for f, o in enumerate(RF.pack(RAGGED, 8)[0])]
     for elem, es in ((U8E, 1), (F32E, 4)):
         for ch in (1, 2, 3, 4):
@@ -235,7 +182,7 @@ def test_offsets_and_strides_that_break_the_packed_alignment(ctx):
             stride = planes[0].nbytes + 256 + es * 3
             want = RF.bilinear_frames(RAGGED, _coord_fields(), _hwc(planes, ch))
             raw, used = _run(ctx, RAGGED, _coord_fields(), 8, planes, ch * es, _bilinear_call(ctx, RAGGED, elem, ch, 3, fo8, oo), fo8, oo, stride, front=256 + es)
-            _check(raw, used, RAGGED, want, ch * es, ("bilinear, explicit offsets", elem, ch))
+            GF.check_frames(raw, used, RAGGED, want, ch * es, ("bilinear, explicit offsets", elem, ch))
     assert n == 9
 
 
@@ -337,9 +284,9 @@ def test_caller_made_fields_never_read_outside_their_plane(ctx):
         planes = _planes("u8", pb)
         want = RF.index_frames(geoms, fields, planes)
         assert not want[0][:8].any() and want[0][8:].all()
-        raw, oo = _run(ctx, geoms, fields, 4, planes, pb, lambda d_f, d_p, stride, d_o: ctx.remap_index_frames_device(geoms, d_f, d_p, N_SRC, 3, stride, pb, d_o),
+        raw, oo = _run(ctx, geoms, fields, 4, planes, pb, lambda b: ctx.remap_index_frames_device(geoms, b.d_f, b.d_p, N_SRC, 3, b.stride, pb, b.d_o),
                        stride=planes[0].nbytes, front=16)          # planes back to back, poison right in front and behind
-        _check(raw, oo, geoms, want, pb, ("caller-made index field", pb))
+        GF.check_frames(raw, oo, geoms, want, pb, ("caller-made index field", pb))
         assert not (raw == POISON).any(), pb
     co = np.float32([[np.nan, 1], [1, np.nan], [np.inf, 1], [1, np.inf], [-np.inf, 1], [1, -np.inf], [np.nan, np.nan],
                      [1e30, 1e30], [-1e30, -1e30], [1e30, -1e30], [-1e30, 2.5], [SW - 1, SH - 1], [SW, SH], [-1, -1], [0, 0], [SW - 0.5, 0.25]])
@@ -354,9 +301,9 @@ def test_caller_made_fields_never_read_outside_their_plane(ctx):
             assert np.array_equal(want[0][7], hw[0][SH - 1, SW - 1]) and np.array_equal(want[0][8], hw[0][0, 0]) and np.array_equal(want[0][9], hw[0][0, SW - 1])
             assert np.array_equal(want[1][12], hw[1][SH - 1, SW - 1]) and np.array_equal(want[1][13], hw[1][0, 0])      # clamped
             raw, oo = _run(ctx, cgeoms, [co, co], 8, planes, ch * es,
-                           lambda d_f, d_p, stride, d_o: ctx.remap_bilinear_frames_device(cgeoms, d_f, d_p, SW, SH, 3, stride, elem, ch, d_o),
+                           lambda b: ctx.remap_bilinear_frames_device(cgeoms, b.d_f, b.d_p, SW, SH, 3, b.stride, elem, ch, b.d_o),
                            stride=planes[0].nbytes, front=16)
-            _check(raw, oo, cgeoms, want, ch * es, ("caller-made coordinates", elem, ch))
+            GF.check_frames(raw, oo, cgeoms, want, ch * es, ("caller-made coordinates", elem, ch))
             if elem == U8E:
                 assert not (raw == POISON).any()
 
@@ -393,8 +340,8 @@ def test_65535_one_pixel_frames_launch_and_65536_are_refused(ctx):
         raw = ctx.to_host(d_o, F * 4 + 256)
         assert np.array_equal(raw[:F * 4].view(np.uint32)[order], want_b.view(np.uint32).ravel()) and (raw[F * 4:] == FILL).all()
         more = geoms + [(0, 0, 1, 1)]
-        assert _code(ctx.remap_index_frames_device, more, d_f, d_p, N_SRC, NP, stride, 4, d_o, foffs4 + [0], ooffs + [0]) == INVALID
-        assert _code(ctx.remap_bilinear_frames_device, more, d_f, d_p, SW, SH, NP, stride, F32E, 1, d_o, foffs8 + [0], ooffs + [0]) == INVALID
+        assert GF.refusal_code(ctx.remap_index_frames_device, more, d_f, d_p, N_SRC, NP, stride, 4, d_o, foffs4 + [0], ooffs + [0]) == INVALID
+        assert GF.refusal_code(ctx.remap_bilinear_frames_device, more, d_f, d_p, SW, SH, NP, stride, F32E, 1, d_o, foffs8 + [0], ooffs + [0]) == INVALID
         assert (ctx.to_host(d_o, F * 4 + 256) == raw).all()
     finally:
         for p in (d_f, d_p, d_o):
@@ -463,12 +410,6 @@ def test_u8_ties_clamp_and_the_single_list_form(ctx):
 
 
 # ------------------------------------------------------------------------------------------------ refusals
-def _code(fn, *a):
-    with pytest.raises(HG.HgError) as e:
-        fn(*a)
-    return e.value.code
-
-
 def test_refusals():
     g = [(0, 0, 8, 2), (0, 0, 4, 1)]
     with HG.Context(0) as c:
@@ -476,7 +417,7 @@ def test_refusals():
         d_f, d_p, d_o = d, d + 4096, d + 8192
         fld = np.arange(20, dtype=np.int32)[::-1].copy()
         plane = (np.arange(1, 65, dtype=np.uint64) * 2654435761 % (2 ** 32)).astype(np.uint32)
-        c.to_device(d_f, _place([fld[:16], fld[16:]], [0, 256], 512, 0))
+        c.to_device(d_f, GF.place([fld[:16], fld[16:]], [0, 256], 512, 0))
         c.to_device(d_p, plane)
 
         def still_works():
@@ -487,7 +428,7 @@ def test_refusals():
             assert np.array_equal(raw[:16], plane[fld[:16]]) and np.array_equal(raw[64:68], plane[fld[16:]]) and (raw[16:64] == 0xA5A5A5A5).all()
 
         def refused(fn, *a):
-            assert _code(fn, *a) == INVALID, a
+            assert GF.refusal_code(fn, *a) == INVALID, a
             still_works()
 
         ri, rb, ru = c.remap_index_frames_device, c.remap_bilinear_frames_device, c.remap_bilinear_u8_device
@@ -551,15 +492,8 @@ def test_refusals():
 def test_a_queued_redo_never_lands_on_a_later_frames_remap():
     """A piecewise warp whose rows carry 1100 spans is queued into buffer B (its frame is flagged, to be redone through the map at hg_sync); a
     frames remap then writes B.  After hg_sync B holds the remap."""
-    n, W2, H2 = 1100, 2400, 8
-    img = WL.lcg_image(W2, H2, 10)
-    xs = np.linspace(0, W2, n + 1)
-    sp = np.stack([np.repeat(xs, 2), np.tile([0.0, H2], n + 1)], 1).astype(np.float32).ravel()
-    tr = np.array([[2 * i, 2 * i + 2, 2 * i + 1] for i in range(n)], np.uint32).ravel()
-    dp = sp.copy()
-    dp[1::2] *= 1.5
-    mm, md = O.minmax_xy(sp), O.minmax_xy(dp)
-    g = (int(md[0]), int(md[1]), int(md[2] - md[0]), int(md[3] - md[1]))
+    s = GF.strip_mesh_overflow()
+    img, W2, H2, g = s.img, s.W, s.H, s.g
     npx = g[2] * g[3]
     fld = ((np.arange(npx, dtype=np.int64) * 7919) % (W2 * H2)).astype(np.int32)
     want = FM.remap_index(fld, img.reshape(-1, 4))
@@ -569,8 +503,8 @@ def test_a_queued_redo_never_lands_on_a_later_frames_remap():
             c.to_device(d_src, img)
             c.to_device(d_f, fld)
             c.set_image_device(d_src, W2, H2)
-            c.piecewise_set_mesh(sp, tr, int(mm[0]), int(mm[1]))
-            c.piecewise_set_frames(dp, [g], [0])
+            c.piecewise_set_mesh(s.sp, s.tris, *s.min_src)
+            c.piecewise_set_frames(s.dp, [g], [0])
             r0 = c.redone_frames()
             c.warp_inverse_piecewise_frames_device(d_b)
             c.remap_index_frames_device([g], d_f, d_src, W2 * H2, 1, 0, 4, d_b)
@@ -587,12 +521,5 @@ def test_a_queued_redo_never_lands_on_a_later_frames_remap():
 # ------------------------------------------------------------------------------------------------ the drop-in class
 def test_js_class_remap():
     """tests/js/remap_gpu.mjs: remap() of js/Homography.mjs on the real addon, for affine, projective and piecewise instances."""
-    node = shutil.which("node")
-    addon = os.path.join(ROOT, "homography.js_amd", "lib", "hgwarp.node")
-    assert node is not None and os.path.exists(addon), "node and the N-API addon are needed on a GPU box"
-    p = subprocess.run([node, os.path.join(ROOT, "tests", "js", "remap_gpu.mjs")], capture_output=True, text=True, timeout=300, cwd=ROOT)
-    line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
-    assert line, p.stdout[-2000:] + p.stderr[-2000:]
-    res = json.loads(line[-1])
-    assert p.returncode == 0 and res["ok"] and not res["fails"], (res["fails"], p.stderr[-2000:])
+    res = GF.run_node_case("remap_gpu.mjs")
     assert set(res["report"]) == {"affine", "projective", "piecewise"}

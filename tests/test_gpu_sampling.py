@@ -2,10 +2,7 @@
 tests/hgtest/bilinear.py.  The model's per-pixel triangle ids and inverse matrices come from the CPU oracle (taps), never from the
 library under test."""
 import hashlib
-import json
 import os
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -16,6 +13,7 @@ sys.path.insert(0, os.path.join(ROOT, "homography.js_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import hgwarp as HG                          # noqa: E402
 from hgtest import bilinear as B             # noqa: E402
+from hgtest import gpu_frames as GF          # noqa: E402
 from hgtest import oracle as O               # noqa: E402
 from hgtest import workloads as WL           # noqa: E402
 
@@ -330,13 +328,7 @@ def test_mode_switching_on_one_context(ctx):
 
 
 def test_js_class_bilinear_equals_ctypes(ctx):
-    node = shutil.which("node")
-    addon = os.path.join(ROOT, "homography.js_amd", "lib", "hgwarp.node")
-    assert node is not None and os.path.exists(addon), "node and the N-API addon are needed on a GPU box"
-    p = subprocess.run([node, os.path.join(ROOT, "tests", "js", "sampling_gpu.mjs")], capture_output=True, text=True, timeout=600, cwd=ROOT)
-    line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
-    assert p.returncode == 0 and line, p.stdout[-2000:] + p.stderr[-2000:]
-    res = json.loads(line[-1])
+    res = GF.run_node_case("sampling_gpu.mjs", timeout=600, verdict=False)      # (its record carries hashes only)
     img = WL.lcg_image(res["W"], res["H"], res["seed"])
     sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
     ctx.set_sampling(BIL)

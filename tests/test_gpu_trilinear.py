@@ -5,10 +5,7 @@ tests/test_trilinear_cpu.py pins the model itself against a scalar model written
 import base64
 import functools
 import hashlib
-import json
 import os
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -18,17 +15,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "homography.js_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import hgwarp as HG                          # noqa: E402
-from hgtest import oracle as O               # noqa: E402
+from hgtest import gpu_frames as GF          # noqa: E402
+from hgtest.gpu_frames import CO, F32, F32E, FILL, INVALID, POISON, U8E      # noqa: E402
 from hgtest import remap_frames as RF        # noqa: E402
 from hgtest import trilinear as TM           # noqa: E402
 from hgtest import workloads as WL           # noqa: E402
 
 pytestmark = pytest.mark.gpu
-CO = HG.FIELD_COORDS
-F32E, U8E = HG.ELEM_F32, HG.ELEM_U8
-F32 = np.float32
-INVALID = 1
-FILL, POISON = 0xA5, 0xEE                    # the output and the pyramids before a call; the bytes around the source planes
 SW, SH = 600, 40                             # the source of the remap tests: 11 levels
 LMAX = 11
 GRID = [(0, 0, w, h) for h in (1, 2, 5) for w in (1, 3, 63, 64, 65, 257)]
@@ -42,37 +35,19 @@ def ctx():
     c.close()
 
 
-def _es(elem):
-    return 1 if elem == U8E else 4
-
-
 # ------------------------------------------------------------------------------------------------ inputs, made once and never modified
 @functools.lru_cache(maxsize=None)
 def _planes(elem, ch, w=SW, h=SH, n=3):
     """n planes (h, w, ch); no byte of a uint8 plane (nor of a blend of its bytes) equals FILL or POISON; f32: normal-range values."""
-    rng = np.random.default_rng(2000 + 10 * ch + elem + w * 7 + h)
-    if elem == U8E:
-        ps = [rng.integers(1, 160, (h, w, ch), dtype=np.uint8) for _ in range(n)]
-    else:
-        ps = [(rng.standard_normal((h, w, ch)) * 40 + 3).astype(F32) for _ in range(n)]
+    ps = GF.random_planes(2000 + 10 * ch + elem + w * 7 + h, elem, (h, w, ch), n)
+    if elem != U8E:
         assert all((np.abs(p) > 1e-30).all() for p in ps)
-    for p in ps:
-        p.setflags(write=False)
-    return tuple(ps)
+    return ps
 
 
 @functools.lru_cache(maxsize=None)
 def _pyrs(elem, ch, levels, w=SW, h=SH, n=3):
     return tuple(TM.pyramid(p, levels) for p in _planes(elem, ch, w, h, n))
-
-
-def _split(raw, offs, geoms):
-    out = []
-    for o, g in zip(offs, geoms):
-        a = raw[o:o + RF.n_px(g) * 8].view(F32).reshape(-1, 2).copy()
-        a.setflags(write=False)
-        out.append(a)
-    return out
 
 
 @functools.lru_cache(maxsize=None)
@@ -92,7 +67,7 @@ def _library_fields():
                 c.geometric_set_frames(kind, mats, GRID)
                 c.field_inverse_geometric_frames_device(CO, d)
                 c.sync()
-                out[name] = (GRID, _split(c.to_host(d, total), offs, GRID))
+                out[name] = (GRID, GF.split(c.to_host(d, total), offs, GRID, 8, F32, 2))
             finally:
                 c.free(d)
         nx, ny = 6, 2
@@ -107,7 +82,7 @@ def _library_fields():
             c.piecewise_set_frames(np.concatenate(dps), geoms)
             c.field_inverse_piecewise_frames_device(CO, d)
             c.sync()
-            out["piecewise"] = (geoms, _split(c.to_host(d, total), offs, geoms))
+            out["piecewise"] = (geoms, GF.split(c.to_host(d, total), offs, geoms, 8, F32, 2))
         finally:
             c.free(d)
     return out
@@ -134,61 +109,14 @@ def _caller_fields():
     return out
 
 
-def _place(parts, offs, total, fill):
-    buf = np.full(total, fill, np.uint8)
-    for p, o in zip(parts, offs):
-        b = np.ascontiguousarray(p).view(np.uint8).ravel()
-        buf[o:o + b.size] = b
-    return buf
-
-
 def _run(ctx, geoms, fields, planes, elem, ch, levels, foffs=None, ooffs=None, stride=None, front=256, pyr_slack=256, call=None):
-    """Upload the fields (at foffs, or packed) and the planes (inside an allocation full of POISON, `front` bytes in, `stride` apart), fill
-    the pyramids and the output with FILL, build the pyramids, remap, and return (output bytes, output offsets, pyramid bytes, pyramid stride)."""
-    px = ch * _es(elem)
+    """GF.run_frames over pyramids of `levels` built first; call (None: the trilinear remap) gets GF.Buffers.  Returns (output bytes, output
+    offsets, pyramid bytes, pyramid stride)."""
     h, w = planes[0].shape[:2]
-    fo = list(foffs) if foffs is not None else RF.pack(geoms, 8)[0]
-    oo = list(ooffs) if ooffs is not None else RF.pack(geoms, px)[0]
-    plane_bytes = planes[0].nbytes
-    stride = stride if stride is not None else (plane_bytes + 255) // 256 * 256 + 256
-    pyr_total = TM.layout(w, h, px, levels)[1]
-    pyr_stride = pyr_total + pyr_slack
-    f_total = max([o + RF.n_px(g) * 8 for o, g in zip(fo, geoms)] + [0]) + 256
-    o_total = max([o + RF.n_px(g) * px for o, g in zip(oo, geoms)] + [0]) + 512
-    p_total = front + stride * len(planes) + 256
-    y_total = pyr_stride * len(planes) + 256
-    d_f, d_p, d_o, d_y = ctx.alloc(f_total), ctx.alloc(p_total), ctx.alloc(o_total), ctx.alloc(y_total)
-    try:
-        ctx.to_device(d_f, _place(fields, fo, f_total, 0x11))
-        ctx.to_device(d_p, _place(planes, [front + k * stride for k in range(len(planes))], p_total, POISON))
-        ctx.to_device(d_o, np.full(o_total, FILL, np.uint8))
-        ctx.to_device(d_y, np.full(y_total, FILL, np.uint8))
-        ctx.pyramid_build_device(d_p + front, w, h, len(planes), stride, elem, ch, levels, d_y, pyr_stride)
-        if call is not None:
-            call(d_f, d_p + front, stride, d_o, d_y, pyr_stride)
-        else:
-            ctx.remap_trilinear_frames_device(geoms, d_f, d_p + front, w, h, len(planes), stride, elem, ch, d_o, d_y, pyr_stride, levels, foffs, ooffs)
-        ctx.sync()
-        return ctx.to_host(d_o, o_total), oo, ctx.to_host(d_y, y_total), pyr_stride
-    finally:
-        for p in (d_f, d_p, d_o, d_y):
-            ctx.free(p)
-
-
-def _check(raw, oo, geoms, want, px_bytes, what):
-    """Every frame equals the model, bit for bit, and every byte outside the frames is still FILL."""
-    untouched = np.ones(raw.size, bool)
-    for f, g in enumerate(geoms):
-        n = RF.n_px(g) * px_bytes
-        untouched[oo[f]:oo[f] + n] = False
-        w = np.ascontiguousarray(want[f]).view(np.uint8).ravel()
-        assert w.size == n, (what, f)
-        got = raw[oo[f]:oo[f] + n]
-        if not np.array_equal(got, w):
-            bad = np.flatnonzero(got != w)
-            raise AssertionError(f"{what}: frame {f} {g}: {bad.size} of {n} bytes differ, first at pixel {int(bad[0]) // px_bytes}: "
-                                 f"got {got[bad[:8]].tolist()}, want {w[bad[:8]].tolist()}")
-    assert (raw[untouched] == FILL).all(), (what, "bytes between the frames, the padding and the tail must not be written")
+    if call is None:
+        def call(b):
+            ctx.remap_trilinear_frames_device(geoms, b.d_f, b.d_p, w, h, len(planes), b.stride, elem, ch, b.d_o, b.d_y, b.pyr_stride, levels, foffs, ooffs)
+    return GF.run_frames(ctx, geoms, fields, 8, planes, ch * GF.es(elem), call, foffs, ooffs, stride, front, pyramid=(elem, ch, levels, pyr_slack))
 
 
 def _check_pyramids(raw, stride, pyrs, px_bytes, what):
@@ -210,7 +138,7 @@ def _check_pyramids(raw, stride, pyrs, px_bytes, what):
 @pytest.mark.parametrize("channels", (1, 2, 3, 4))
 @pytest.mark.parametrize("elem", (F32E, U8E))
 def test_pyramid_build(ctx, elem, channels):
-    es, px = _es(elem), channels * _es(elem)
+    es, px = GF.es(elem), channels * GF.es(elem)
     for w, h in ((1, 1), (2, 2), (3, 5), (64, 3), (65, 67), (257, 130)):
         lmax = TM.n_levels(w, h)
         assert HG.pyramid_levels(w, h) == lmax
@@ -224,7 +152,7 @@ def test_pyramid_build(ctx, elem, channels):
                 pyr_stride = total + 256 + 3 * es
                 d_p, d_y = ctx.alloc(front + stride * n_planes + 256), ctx.alloc(pyr_stride * n_planes + 512)
                 try:
-                    src = _place(planes, [front + k * stride for k in range(n_planes)], front + stride * n_planes + 256, POISON)
+                    src = GF.place(planes, [front + k * stride for k in range(n_planes)], front + stride * n_planes + 256, POISON)
                     ctx.to_device(d_p, src)
                     ctx.to_device(d_y, np.full(pyr_stride * n_planes + 512, FILL, np.uint8))
                     ctx.pyramid_build_device(d_p + front, w, h, n_planes, stride, elem, channels, levels, d_y + es, pyr_stride)
@@ -244,14 +172,14 @@ def test_pyramid_build(ctx, elem, channels):
 @pytest.mark.parametrize("channels", (1, 2, 3, 4))
 @pytest.mark.parametrize("elem", (F32E, U8E))
 def test_trilinear_frames_of_the_librarys_geometric_fields(ctx, elem, channels):
-    px = channels * _es(elem)
+    px = channels * GF.es(elem)
     for name in ("affine", "projective"):
         geoms, fields = _library_fields()[name]
         planes = _planes(elem, channels)
         for levels in (1, 2, LMAX):
             want = TM.trilinear_frames(geoms, fields, _pyrs(elem, channels, levels))
             raw, oo, pyr, pstride = _run(ctx, geoms, fields, planes, elem, channels, levels)
-            _check(raw, oo, geoms, want, px, (name, elem, channels, levels))
+            GF.check_frames(raw, oo, geoms, want, px, (name, elem, channels, levels))
             _check_pyramids(pyr, pstride, _pyrs(elem, channels, levels), px, (name, elem, channels, levels))
 
 
@@ -284,18 +212,18 @@ def test_the_premises_of_the_librarys_fields():
 @pytest.mark.parametrize("elem,channels", ((U8E, 4), (F32E, 1), (U8E, 3), (F32E, 2)))
 def test_trilinear_frames_of_a_piecewise_field_with_uncovered_pixels(ctx, elem, channels):
     geoms, fields = _library_fields()["piecewise"]
-    px = channels * _es(elem)
+    px = channels * GF.es(elem)
     for n_planes in (1, 3):
         planes = _planes(elem, channels)[:n_planes]
         want = TM.trilinear_frames(geoms, fields, _pyrs(elem, channels, LMAX)[:n_planes])
         assert any(not w_[~np.isfinite(f).all(-1)].any() and w_.any() for w_, f in zip(want, fields))
         raw, oo, _, _ = _run(ctx, geoms, fields, planes, elem, channels, LMAX)
-        _check(raw, oo, geoms, want, px, ("piecewise", elem, channels, n_planes))
+        GF.check_frames(raw, oo, geoms, want, px, ("piecewise", elem, channels, n_planes))
 
 
 @pytest.mark.parametrize("elem,channels", ((U8E, 1), (U8E, 2), (U8E, 4), (F32E, 1), (F32E, 3), (F32E, 4)))
 def test_caller_made_fields_with_nan_infinite_and_huge_coordinates(ctx, elem, channels):
-    px = channels * _es(elem)
+    px = channels * GF.es(elem)
     fields = _caller_fields()
     planes = _planes(elem, channels)
     for levels in (2, LMAX):
@@ -304,7 +232,7 @@ def test_caller_made_fields_with_nan_infinite_and_huge_coordinates(ctx, elem, ch
         assert not want[17].reshape(5, 257, channels)[0, 5:9].any() and want[17].reshape(5, 257, channels)[0, 9:13].any()      # NaN / Inf: zeros; 1e30: clamped taps
         assert np.isnan(f17).any() and np.isinf(f17).any() and (np.abs(f17[np.isfinite(f17)]) >= 1e30).any()
         raw, oo, _, _ = _run(ctx, GRID, fields, planes, elem, channels, levels, stride=planes[0].nbytes, front=16)      # planes back to back, poison in front and behind
-        _check(raw, oo, GRID, want, px, ("caller-made", elem, channels, levels))
+        GF.check_frames(raw, oo, GRID, want, px, ("caller-made", elem, channels, levels))
         if elem == U8E:
             assert not (raw == POISON).any()
     k, two, _ = TM.level_choice(np.concatenate([TM.footprint(f.reshape(g[3], g[2], 2)).ravel() for f, g in zip(fields, GRID)]), LMAX)
@@ -316,7 +244,7 @@ def test_explicit_offsets_and_strides_that_break_every_wider_alignment(ctx):
     fo8 = [o + 8 * (2 * f + 1) + 512 * f for f, o in enumerate(RF.pack(GRID, 8)[0])]            # odd multiples of 8: no 16-byte alignment
     assert all(o % 8 == 0 and o % 16 != 0 for o in fo8)
     for elem in (U8E, F32E):
-        es = _es(elem)
+        es = GF.es(elem)
         for ch in (1, 2, 3, 4):
             planes = _planes(elem, ch)
             oo = [o + 640 * f + es * (2 * f + 1) for f, o in enumerate(RF.pack(GRID, ch * es)[0])]  # odd element offsets: multiples of 4 (f32) but never of 8 or 16; no 2- or 4-byte store fits (u8)
@@ -324,7 +252,7 @@ def test_explicit_offsets_and_strides_that_break_every_wider_alignment(ctx):
             stride = planes[0].nbytes + 256 + es * 3
             want = TM.trilinear_frames(GRID, fields, _pyrs(elem, ch, LMAX))
             raw, used, pyr, pstride = _run(ctx, GRID, fields, planes, elem, ch, LMAX, fo8, oo, stride, front=256 + es, pyr_slack=256 + es * 3)
-            _check(raw, used, GRID, want, ch * es, ("explicit offsets", elem, ch))
+            GF.check_frames(raw, used, GRID, want, ch * es, ("explicit offsets", elem, ch))
             _check_pyramids(pyr, pstride, _pyrs(elem, ch, LMAX), ch * es, ("explicit offsets", elem, ch))
 
 
@@ -341,16 +269,16 @@ def test_one_level_and_magnifying_fields_equal_the_bilinear_frames_remap(ctx, el
             co[0, 7] = np.nan                                   # (a hole only removes neighbours)
         mag.append(co.reshape(-1, 2))
 
-    def bilinear(d_f, d_p, stride, d_o, d_y, pyr_stride):
-        ctx.remap_bilinear_frames_device(GRID, d_f, d_p, SW, SH, 3, stride, elem, channels, d_o)
+    def bilinear(b):
+        ctx.remap_bilinear_frames_device(GRID, b.d_f, b.d_p, SW, SH, 3, b.stride, elem, channels, b.d_o)
 
     for name, fields, levels in (("levels == 1", _caller_fields(), 1), ("magnifying", mag, LMAX), ("magnifying, 2 levels", mag, 2)):
         a, _, _, _ = _run(ctx, GRID, fields, planes, elem, channels, levels)
         b, _, _, _ = _run(ctx, GRID, fields, planes, elem, channels, levels, call=bilinear)
         assert np.array_equal(a, b) and (a != FILL).any(), (name, int((a != b).sum()))
     # levels == 1 needs no pyramid at all
-    def no_pyramid(d_f, d_p, stride, d_o, d_y, pyr_stride):
-        ctx.remap_trilinear_frames_device(GRID, d_f, d_p, SW, SH, 3, stride, elem, channels, d_o, 0, 0, 1)
+    def no_pyramid(b):
+        ctx.remap_trilinear_frames_device(GRID, b.d_f, b.d_p, SW, SH, 3, b.stride, elem, channels, b.d_o, 0, 0, 1)
 
     c, _, _, _ = _run(ctx, GRID, _caller_fields(), planes, elem, channels, 1, call=no_pyramid)
     d, _, _, _ = _run(ctx, GRID, _caller_fields(), planes, elem, channels, 1, call=bilinear)
@@ -366,17 +294,11 @@ def test_the_checkerboard_shrunk_8x_is_grey_on_the_device(ctx):
     co = [np.stack([8.0 * i + 1, 8.0 * j], -1).astype(F32).reshape(-1, 2)]
     tri, oo, _, _ = _run(ctx, g, co, (board,), U8E, 1, TM.n_levels(n, n))
     bil, _, _, _ = _run(ctx, g, co, (board,), U8E, 1, TM.n_levels(n, n),
-                        call=lambda d_f, d_p, stride, d_o, d_y, ps: ctx.remap_bilinear_frames_device(g, d_f, d_p, n, n, 1, stride, U8E, 1, d_o))
+                        call=lambda b: ctx.remap_bilinear_frames_device(g, b.d_f, b.d_p, n, n, 1, b.stride, U8E, 1, b.d_o))
     assert (tri[:1024] == 128).all() and (bil[:1024] == 255).all()
 
 
 # ------------------------------------------------------------------------------------------------ refusals
-def _code(fn, *a):
-    with pytest.raises(HG.HgError) as e:
-        fn(*a)
-    return e.value.code
-
-
 def test_refusals():
     g = [(0, 0, 8, 2), (0, 0, 4, 1)]
     W, H = 8, 4                                                  # 4 levels
@@ -385,7 +307,7 @@ def test_refusals():
         d_f, d_p, d_o, d_y = d, d + 4096, d + 8192, d + 12288
         co = (np.random.default_rng(2).random((20, 2)) * [7, 3]).astype(F32)
         plane = np.arange(1, 33, dtype=np.float32).reshape(H, W, 1)
-        c.to_device(d_f, _place([co[:16], co[16:]], [0, 256], 512, 0))
+        c.to_device(d_f, GF.place([co[:16], co[16:]], [0, 256], 512, 0))
         c.to_device(d_p, plane)
         want = TM.trilinear_frames(g, [co[:16], co[16:]], [TM.pyramid(plane, 4)])
 
@@ -398,7 +320,7 @@ def test_refusals():
             assert np.array_equal(raw[:64].view(F32), want[0].ravel()) and np.array_equal(raw[256:272].view(F32), want[1].ravel()) and (raw[64:256] == FILL).all()
 
         def refused(fn, *a):
-            assert _code(fn, *a) == INVALID, a
+            assert GF.refusal_code(fn, *a) == INVALID, a
             still_works()
 
         rt, pb = c.remap_trilinear_frames_device, c.pyramid_build_device
@@ -459,18 +381,9 @@ def test_refusals():
 
 
 # ------------------------------------------------------------------------------------------------ what the calls leave alone
-def _state(c):
-    return (c.last_piecewise_kernel(), c.last_piecewise_variant(), c.last_piecewise_self(), c.last_piecewise_flag(), c.last_geometric_kernel(),
-            c.last_forward_kernel(), c.last_forward_field_kernel(), c.sampling, c.redone_frames(), c.layout_walks())
-
-
 def test_state_is_untouched_and_a_queued_nearest_warp_keeps_its_bytes():
     W, H, F = 256, 160, 3
-    img = WL.lcg_image(W, H, 81)
-    s4 = WL.corners(W, H)
-    d4s = [WL.projective_dst(W, H, 0.03 * k) * 0.3 for k in range(F)]                         # a shrink: the inverse loop
-    gg = [tuple(int(v) for v in O.transform_limits(1, O.projective_from_squares(s4, d4), W, H)) for d4 in d4s]
-    offs, total = HG.pack_offsets(gg)
+    img, s4, d4s, gg, offs, total = GF.oblique_projective_set(0.3, W=W, H=H, fit=None)      # a shrink (the inverse loop) of a larger picture
     levels = HG.pyramid_levels(W, H)
     _, ptotal = HG.pyramid_layout(W, H, U8E, 4, levels)
     with HG.Context(0) as c:
@@ -488,15 +401,15 @@ def test_state_is_untouched_and_a_queued_nearest_warp_keeps_its_bytes():
             c.field_inverse_geometric_frames_device(CO, d_f)
             c.sync()
             fo = HG.pack_field_offsets(gg, CO)[0]
-            fields = _split(c.to_host(d_f, 2 * total), fo, gg)
+            fields = GF.split(c.to_host(d_f, 2 * total), fo, gg, 8, F32, 2)
             c.to_device(d_w, np.zeros(total, np.uint8))
             c.warp_inverse_geometric_frames_device(d_w)                   # queued ...
-            mid = _state(c)
+            mid = GF.tap_state(c)
             c.pyramid_build_device(d_src, W, H, 1, 0, U8E, 4, levels, d_y, ptotal)
             c.remap_trilinear_frames_device(gg, d_f, d_src, W, H, 1, 0, U8E, 4, d_r, d_y, ptotal, levels)      # ... in front of the remap of the picture itself
-            assert _state(c) == mid
+            assert GF.tap_state(c) == mid
             c.sync()
-            assert _state(c) == mid and c.sampling == HG.SAMPLE_NEAREST
+            assert GF.tap_state(c) == mid and c.sampling == HG.SAMPLE_NEAREST
             again = c.to_host(d_w, total)
             for f, g in enumerate(gg):                                    # (the padding between frames is nobody's)
                 assert np.array_equal(again[offs[f]:offs[f] + RF.n_px(g) * 4], alone[offs[f]:offs[f] + RF.n_px(g) * 4]) and again[offs[f]:offs[f] + RF.n_px(g) * 4].any(), f
@@ -513,15 +426,8 @@ def test_state_is_untouched_and_a_queued_nearest_warp_keeps_its_bytes():
 def test_a_queued_redo_never_lands_on_a_later_trilinear_remap():
     """A piecewise warp whose rows carry 1100 spans is queued into buffer B (its frame is flagged, to be redone through the map at hg_sync); a
     trilinear remap then writes B.  After hg_sync B holds the remap."""
-    n, W2, H2 = 1100, 2400, 8
-    img = WL.lcg_image(W2, H2, 10)
-    xs = np.linspace(0, W2, n + 1)
-    sp = np.stack([np.repeat(xs, 2), np.tile([0.0, H2], n + 1)], 1).astype(np.float32).ravel()
-    tr = np.array([[2 * i, 2 * i + 2, 2 * i + 1] for i in range(n)], np.uint32).ravel()
-    dp = sp.copy()
-    dp[1::2] *= 1.5
-    mm, md = O.minmax_xy(sp), O.minmax_xy(dp)
-    g = (int(md[0]), int(md[1]), int(md[2] - md[0]), int(md[3] - md[1]))
+    s = GF.strip_mesh_overflow()
+    img, W2, H2, g = s.img, s.W, s.H, s.g
     npx = g[2] * g[3]
     i, j = np.meshgrid(np.arange(g[2]), np.arange(g[3]))
     co = np.stack([(i * 3.3) % W2, j * 0.6], -1).astype(F32).reshape(-1, 2)
@@ -534,8 +440,8 @@ def test_a_queued_redo_never_lands_on_a_later_trilinear_remap():
             c.to_device(d_src, img)
             c.to_device(d_f, co)
             c.set_image_device(d_src, W2, H2)
-            c.piecewise_set_mesh(sp, tr, int(mm[0]), int(mm[1]))
-            c.piecewise_set_frames(dp, [g], [0])
+            c.piecewise_set_mesh(s.sp, s.tris, *s.min_src)
+            c.piecewise_set_frames(s.dp, [g], [0])
             r0 = c.redone_frames()
             c.pyramid_build_device(d_src, W2, H2, 1, 0, U8E, 4, levels, d_y, ptotal)
             c.warp_inverse_piecewise_frames_device(d_b)
@@ -555,18 +461,9 @@ def test_js_class_trilinear_matches_the_ctypes_result(ctx):
     """tests/js/trilinear_gpu.mjs: remap(plane, {sampling: 'trilinear'}) of js/Homography.mjs on the real addon for an affine, a projective
     and a piecewise shrink; it prints its coordinate fields and the SHA-256 of every result, and the same planes through the same fields
     by ctypes (all levels) must hash alike -- and equal the model."""
-    node = shutil.which("node")
-    addon = os.path.join(ROOT, "homography.js_amd", "lib", "hgwarp.node")
-    assert node is not None and os.path.exists(addon), "node and the N-API addon are needed on a GPU box"
-    p = subprocess.run([node, os.path.join(ROOT, "tests", "js", "trilinear_gpu.mjs")], capture_output=True, text=True, timeout=300, cwd=ROOT)
-    line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
-    assert line, p.stdout[-2000:] + p.stderr[-2000:]
-    res = json.loads(line[-1])
-    assert p.returncode == 0 and res["ok"] and not res["fails"], (res["fails"], p.stderr[-2000:])
+    res = GF.run_node_case("trilinear_gpu.mjs")
     W, H = res["W"], res["H"]
-    idx = np.arange(W * H * 4, dtype=np.int64)
-    u8 = ((idx * 7 + (idx >> 3) * 13) & 255).astype(np.uint8).reshape(H, W, 4)
-    f32 = ((idx[:W * H] * 37 % 1001) * 0.25 - 100).astype(F32).reshape(H, W, 1)
+    u8, f32 = GF.js_pattern_planes(W, H)
     levels = HG.pyramid_levels(W, H)
     assert set(res["cases"]) == {"affine", "projective", "piecewise"}
     for name, case in res["cases"].items():
@@ -577,6 +474,6 @@ def test_js_class_trilinear_matches_the_ctypes_result(ctx):
         assert (k[np.isfinite(co).all(-1).reshape(k.shape)] >= 1).any(), name        # the case does shrink
         for key, plane, elem, ch in (("u8x4", u8, U8E, 4), ("f32x1", f32, F32E, 1)):
             raw, oo, _, _ = _run(ctx, g, [co], (plane,), elem, ch, levels)
-            got = raw[:co.shape[0] * ch * _es(elem)]
+            got = raw[:co.shape[0] * ch * GF.es(elem)]
             assert hashlib.sha256(got.tobytes()).hexdigest() == case[key], (name, key)
             assert np.array_equal(got, TM.trilinear_frames(g, [co], [TM.pyramid(plane, levels)])[0].view(np.uint8).ravel()), (name, key)
