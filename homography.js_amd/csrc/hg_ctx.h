@@ -1,6 +1,6 @@
 // hg_ctx.h -- the context behind the C ABI of include/hgwarp.h and the helpers its translation units share
 // (hg_api.hip: library / context / buffers / host-side solves / source image; hg_api_geometric.hip; hg_api_piecewise.hip;
-// hg_api_forward.hip; hg_api_state.hip; hg_api_field.hip).  Its memory is owned through hg_mem.h.  Internal: nothing here is exported.
+// hg_api_forward.hip; hg_api_state.hip; hg_api_field.hip; hg_api_points.hip; hg_api_fit.hip).  Its memory is owned through hg_mem.h.  Internal: nothing here is exported.
 #pragma once
 #include "../../include/hgwarp.h"
 #include "hg_kernels.h"
@@ -208,6 +208,12 @@ struct hg_ctx {
     DevBuf<uint64_t> d_tri_table;                              // hg_remap_trilinear_frames_device: 32 level offsets, then the TriRemapFrame records; staged through field_stage
     DevBuf<MosaicFrame4> d_mosaic_frames;                      // the frame table of the hg_mosaic_* calls (quads of records) and, behind it, a gained mosaic's gains; staged through field_stage
     int opt_remap_pack = -1;                                   // k_remap_index_frames: 0 = one pixel per lane even for the pixel sizes that carry the packed form (measurements)
+
+    // fitting transforms to matches (hg_api_fit.hip): the hypotheses' matrices and flags, the per-frame counts and best words; grown on demand
+    DevBuf<double> d_fit_mats;
+    DevBuf<int32_t> d_fit_valid;
+    DevBuf<uint64_t> d_fit_frames;                             // F best words, then the F counts (int32, padded to 8 bytes)
+    StageRing<4> fit_stage;                                    // the counts go up through page-locked staging, stream-ordered
 
     // scratch
     DevBuf<int32_t> d_map32;

@@ -260,6 +260,17 @@ void launch_points_from_map(const PwMesh &mesh, const PwFrames &fr, int f, const
 void launch_pw_points_out(const int32_t *fmap, const float *fwd, const FrameDesc *frames, int n_frames, int T, int min_src_x, int min_src_y,
                           int map_w, int map_h, const float *points, int n_points, int n_sets, float *out, hipStream_t stream);
 
+// Fitting transforms to matches (hg_k_fit.hip; the rules: hg_fit_dev.h): k_fit_hypotheses + k_fit_score (n_hyp > 0), then k_fit_finish.
+// matches = F x n_points (x, y, u, v) float32, 16-byte aligned; counts = F int32 on the device; samples = F x n_hyp x 4 int32 or nullptr (drawn);
+// scratch: hyp_mats = F x n_hyp x 8 doubles, hyp_valid = F x n_hyp flags, best = F words ZEROED by the caller ((count << 32) | (0xffffffff - h)
+// of the best valid hypothesis).  out_min / out_best / out_mask may be nullptr.
+struct FitArgs {
+    int kind; const void *matches; int n_points; const int32_t *counts; int n_frames; double threshold; int n_hyp; uint32_t seed;
+    const int32_t *samples; int refit; double *hyp_mats; int32_t *hyp_valid; unsigned long long *best;
+    double *out_mats, *out_min; int32_t *out_counts, *out_best; uint8_t *out_mask;
+};
+void launch_fit(const FitArgs &a, hipStream_t stream);
+
 // k_geo: _inverseGeometricWarp pixel loop :997-1011 for all frames.  mats = F x 8 doubles (inverse matrices).
 // f32_exact: every affine matrix entry is a float value and |x| < 2^28 (lets the kernel use an exact-product fma).
 // n_imgs / img_stride: frame f reads the source at img + (f % n_imgs) * img_stride.

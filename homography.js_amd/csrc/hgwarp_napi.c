@@ -1101,6 +1101,69 @@ static napi_value fn_points_forward_piecewise(napi_env env, napi_callback_info i
     return points_finish(env, h, &j);
 }
 
+/* fitMatches(handle, kind, matches, nPoints, counts, threshold, nHyp, seed, samples | null, refit): one transform per frame from point matches
+ * (hg_fit_matches_frames_device).  matches: Float32Array of F x nPoints x 4 (x, y, u, v), F = counts.length; counts: Int32Array; samples: Int32Array
+ * of F x nHyp x 4 or null (the device draws them from `seed`).  Everything goes up into device memory of the call's own, the entry runs, and
+ * { matrices, minimal: Float64Array(8 F), counts, best: Int32Array(F), mask: Uint8Array(F x nPoints) } come down.  Needs no image. */
+static napi_value fn_fit_matches(napi_env env, napi_callback_info info)
+{
+    napi_value a[10];
+    if (!get_args(env, info, 10, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    int kind, n_points, n_hyp, refit; size_t n_m = 0, n_c = 0, n_s = 0; double thr, seed_d;
+    if (!get_i32(env, a[1], &kind)) return NULL;
+    float *m = (float *)get_typed(env, a[2], napi_float32_array, &n_m, "matches"); if (!m) return NULL;
+    if (!get_i32(env, a[3], &n_points)) return NULL;
+    int32_t *counts = (int32_t *)get_typed(env, a[4], napi_int32_array, &n_c, "counts"); if (!counts) return NULL;
+    if (napi_get_value_double(env, a[5], &thr) != napi_ok) return throw_str(env, "hgwarp: threshold must be a number");
+    if (!get_i32(env, a[6], &n_hyp)) return NULL;
+    if (napi_get_value_double(env, a[7], &seed_d) != napi_ok || !(seed_d >= 0 && seed_d <= 4294967295.0)) return throw_str(env, "hgwarp: seed must be a uint32");
+    napi_valuetype vt;
+    NAPI_OK(napi_typeof(env, a[8], &vt));
+    int32_t *samples = NULL;
+    if (vt != napi_null && vt != napi_undefined) { samples = (int32_t *)get_typed(env, a[8], napi_int32_array, &n_s, "samples"); if (!samples) return NULL; }
+    if (!get_i32(env, a[9], &refit)) return NULL;
+    if (n_points < 0 || n_points > 65536 || n_hyp < 0 || n_hyp > 65536 || n_c > 4096) return throw_str(env, "hgwarp: fitMatches: nPoints, nHyp or the number of frames is out of range");
+    const size_t F = n_c, N = (size_t)n_points, H = (size_t)n_hyp;
+    if (n_m != F * N * 4) return throw_str(env, "hgwarp: matches must hold counts.length x nPoints x 4 floats");
+    if (samples && n_s != F * H * 4) return throw_str(env, "hgwarp: samples must hold counts.length x nHyp x 4 indices");
+    void *p_mats, *p_min, *p_cnt, *p_best, *p_mask;
+    napi_value out, v_mats, v_min, v_cnt, v_best, v_mask;
+    if (!(v_mats = make_typed(env, napi_float64_array, F * 8, 8, &p_mats)) || !(v_min = make_typed(env, napi_float64_array, F * 8, 8, &p_min)) ||
+        !(v_cnt = make_typed(env, napi_int32_array, F, 4, &p_cnt)) || !(v_best = make_typed(env, napi_int32_array, F, 4, &p_best)) ||
+        !(v_mask = make_typed(env, napi_uint8_array, F * N, 1, &p_mask))) return NULL;
+    NAPI_OK(napi_create_object(env, &out));
+    NAPI_OK(napi_set_named_property(env, out, "matrices", v_mats)); NAPI_OK(napi_set_named_property(env, out, "minimal", v_min));
+    NAPI_OK(napi_set_named_property(env, out, "counts", v_cnt)); NAPI_OK(napi_set_named_property(env, out, "best", v_best));
+    NAPI_OK(napi_set_named_property(env, out, "mask", v_mask));
+    if (!F) return out;
+#define FIT_PAD(b) (((size_t)(b) + 255) & ~(size_t)255)
+    const size_t o_m = 0, o_s = o_m + FIT_PAD(F * N * 16), o_mats = o_s + FIT_PAD(samples ? F * H * 16 : 0), o_min = o_mats + FIT_PAD(F * 64),
+                 o_cnt = o_min + FIT_PAD(F * 64), o_best = o_cnt + FIT_PAD(F * 4), o_mask = o_best + FIT_PAD(F * 4), total = o_mask + FIT_PAD(F * N);
+#undef FIT_PAD
+    void *d = NULL;
+    HG_CALL(h->ctx, "hg_device_alloc", hg_device_alloc(h->ctx, total, &d));
+    uint8_t *b = (uint8_t *)d;
+    int rc = HG_OK;
+    const char *what = "hg_copy_to_device";
+    if (F * N) rc = hg_copy_to_device(h->ctx, b + o_m, m, F * N * 16);
+    if (rc == HG_OK && samples && F * H) rc = hg_copy_to_device(h->ctx, b + o_s, samples, F * H * 16);
+    if (rc == HG_OK) {
+        what = "hg_fit_matches_frames_device";
+        rc = hg_fit_matches_frames_device(h->ctx, kind, F * N ? b + o_m : NULL, n_points, counts, (int)F, thr, n_hyp, (uint32_t)seed_d,
+                                          samples ? (const int32_t *)(b + o_s) : NULL, refit, (double *)(b + o_mats), (double *)(b + o_min),
+                                          (int32_t *)(b + o_cnt), (int32_t *)(b + o_best), (uint8_t *)(b + o_mask));
+    }
+    if (rc == HG_OK) { what = "hg_copy_to_host"; rc = hg_copy_to_host(h->ctx, p_mats, b + o_mats, F * 64); }
+    if (rc == HG_OK) rc = hg_copy_to_host(h->ctx, p_min, b + o_min, F * 64);
+    if (rc == HG_OK) rc = hg_copy_to_host(h->ctx, p_cnt, b + o_cnt, F * 4);
+    if (rc == HG_OK) rc = hg_copy_to_host(h->ctx, p_best, b + o_best, F * 4);
+    if (rc == HG_OK && F * N) rc = hg_copy_to_host(h->ctx, p_mask, b + o_mask, F * N);
+    if (rc != HG_OK) { napi_value e = throw_hg(env, h->ctx, what, rc); hg_device_free(h->ctx, d); return e; }
+    HG_CALL(h->ctx, "hg_device_free", hg_device_free(h->ctx, d));
+    return out;
+}
+
 /* redoneFrames(ctx): frames the fused kernels flagged and hg_sync redid through the map so far (hg_redone_frames; tests) */
 static napi_value fn_redone_frames(napi_env env, napi_callback_info info)
 {
@@ -1814,6 +1877,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "mosaicInverseGeometric", fn_mosaic_inverse_geometric }, { "mosaicInversePiecewise", fn_mosaic_inverse_piecewise },
         { "pointsInverseGeometric", fn_points_inverse_geometric }, { "pointsInversePiecewise", fn_points_inverse_piecewise },
         { "pointsForwardGeometric", fn_points_forward_geometric }, { "pointsForwardPiecewise", fn_points_forward_piecewise },
+        { "fitMatches", fn_fit_matches },
         { "solveAffineTriangles", fn_solve_affine_triangles }, { "warpInversePiecewiseState", fn_warp_inverse_piecewise_state },
         { "warpForwardPiecewiseState", fn_warp_forward_piecewise_state },
         { "release", fn_release }, { "setPinnedLimit", fn_set_pinned_limit }, { "poolStats", fn_pool_stats }, { "redoneFrames", fn_redone_frames }, { "spanCacheStats", fn_span_cache_stats }, { "setSampling", fn_set_sampling }, { "multiSetSampling", fn_multi_set_sampling }, { "_poolTestFrames", fn_pool_test_frames }, { "poolPressure", fn_pool_pressure }, { "poolCollected", fn_pool_collected },

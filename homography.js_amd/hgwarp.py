@@ -61,6 +61,7 @@ EXPORTS = [
     "hg_pyramid_levels", "hg_pyramid_layout", "hg_pyramid_build_device", "hg_remap_trilinear_frames_device", "hg_remap_aniso_frames_device",
     "hg_mosaic_frames_device", "hg_mosaic_overlap_stats_device", "hg_mosaic_solve_gains", "hg_mosaic_frames_gain_device",
     "hg_remap_bicubic_frames_device",
+    "hg_fit_sample_indices", "hg_fit_matches_frames_device",
 ]
 
 
@@ -173,6 +174,8 @@ def lib():
         "hg_mosaic_frames_gain_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, C.POINTER(sz), i, i, i, i, i, C.c_float, Geom, vp, vp, C.POINTER(C.c_float)]),
         "hg_mosaic_overlap_stats_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, C.POINTER(sz), i, Geom, vp]),
         "hg_mosaic_solve_gains": (i, [C.POINTER(C.c_uint64), i, i, C.c_double, C.c_double, C.POINTER(C.c_float)]),
+        "hg_fit_sample_indices": (i, [i, C.c_uint32, i, C.POINTER(C.c_int32), i, i, C.POINTER(C.c_int32)]),
+        "hg_fit_matches_frames_device": (i, [vp, i, vp, i, C.POINTER(C.c_int32), i, d, i, C.c_uint32, vp, i, vp, vp, vp, vp, vp]),
         "hg_points_to_source_geometric_frames_device": (i, [vp, vp, i, i, vp]),
         "hg_points_to_source_piecewise_frames_device": (i, [vp, vp, i, i, vp]),
         "hg_points_to_output_geometric_batch_device": (i, [vp, i, f64p, C.POINTER(Geom), i, vp, i, i, vp]),
@@ -358,6 +361,24 @@ def mosaic_solve_gains(stats, channels, sigma_n=10.0, sigma_g=0.1):
     _check(lib().hg_mosaic_solve_gains(st.ctypes.data_as(C.POINTER(C.c_uint64)) if n else None, n, int(channels), float(sigma_n), float(sigma_g),
                                        gains.ctypes.data_as(C.POINTER(C.c_float)) if n else None))
     return gains
+
+
+def _counts(counts, n_frames=None):
+    """The host counts of a fit as (array or None, ctypes pointer or None, F)."""
+    if counts is None:
+        return None, None, int(n_frames)
+    a = np.ascontiguousarray(counts, dtype=np.int32).ravel()
+    return a, (a.ctypes.data_as(C.POINTER(C.c_int32)) if a.size else None), a.size
+
+
+def fit_sample_indices(kind, seed, counts, n_points, n_hyp):
+    """The samples the device draws for a fit with d_samples NULL (hg_fit_sample_indices): an (F, n_hyp, 4) int32 array for the F frames of
+    `counts` (matches per frame), -1 in all four slots of an invalid hypothesis and in the fourth slot for affine."""
+    a, p, F = _counts(counts)
+    out = np.empty((F, max(int(n_hyp), 0), 4), np.int32)
+    _check(lib().hg_fit_sample_indices(int(kind), int(seed) & 0xffffffff, F, p, int(n_points), int(n_hyp),
+                                       out.ctypes.data_as(C.POINTER(C.c_int32)) if out.size else None))
+    return out
 
 
 def _field_array(fmt, h, w):
@@ -810,6 +831,17 @@ class Context:
         self._c(lib().hg_mosaic_frames_device(self._h, _geoms(geoms) if len(geoms) else None, len(geoms), C.c_void_p(int(d_coords) or None), fo,
                                               C.c_void_p(int(d_frames) or None), po, int(elem), int(channels), int(w), int(h), int(mode), float(feather),
                                               Geom(*[int(v) for v in canvas]), C.c_void_p(int(d_canvas) or None), C.c_void_p(int(d_weight) or None)))
+
+    def fit_matches_frames_device(self, kind, d_matches, n_points, counts, n_frames, threshold, n_hyp, seed, d_mats, d_counts, d_samples=0, refit=True,
+                                  d_min_mats=0, d_best=0, d_mask=0):
+        """hg_fit_matches_frames_device: one transform per frame from n_frames x n_points (x, y, u, v) float32 matches on the device (counts: per
+        frame on the host, or None for all), by RANSAC over n_hyp hypotheses (drawn from `seed`, or read from d_samples) and, with refit, least
+        squares over the best one's inliers.  Asynchronous; every output is device memory, 0 = not wanted."""
+        _, p, _ = _counts(counts, n_frames)
+        vp = lambda v: C.c_void_p(int(v) or None)
+        self._c(lib().hg_fit_matches_frames_device(self._h, int(kind), vp(d_matches), int(n_points), p, int(n_frames), float(threshold), int(n_hyp),
+                                                   int(seed) & 0xffffffff, vp(d_samples), 1 if refit else 0, vp(d_mats), vp(d_min_mats), vp(d_counts),
+                                                   vp(d_best), vp(d_mask)))
 
     def mosaic_overlap_stats_device(self, geoms, d_coords, d_frames, channels, canvas, d_stats, field_offsets=None, frame_offsets=None):
         """The overlaps of a set of uint8 frames measured on the device (asynchronous): d_stats gets F * F * 2 uint64 words -- for every ordered

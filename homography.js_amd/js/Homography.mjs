@@ -412,6 +412,56 @@ class Homography {
     }
 
     /**
+     * One transform per frame from point MATCHES, robust to wrong ones (not part of the reference; hg_fit_matches_frames_device in
+     * include/hgwarp.h has the rules): RANSAC over `hypotheses` minimal samples per frame, the best one refitted by least squares over its
+     * inliers.  matchSets: an array of F lists, each a Float32Array of x, y, u, v quadruples or an array of [x, y, u, v]; (x, y) is the FROM
+     * position, (u, v) the TO position and the matrix maps from -> to.  The lengths may differ: the lists are padded to the longest and the
+     * device is told each frame's count.
+     * options: { transform: 'projective' (default) | 'affine', threshold = 3 (pixels), hypotheses = 1024 (0: plain least squares over every
+     *            finite match; needs refit), seed = 0, refit = true, samples: Int32Array of F x hypotheses x 4 indices instead of drawn ones }.
+     * Returns { kind, matrices: Float64Array(8 F) -- the result to use, row f at 8 f; affine in the first 6 of each 8; NaN for a frame
+     *           without a valid hypothesis --, minimal: Float64Array(8 F) -- the best hypothesis' matrix as solved --, counts: Int32Array(F),
+     *           best: Int32Array(F) (-1: failed), inliers: [Uint8Array(n_f), ...] one flag per match of frame f }.
+     * `matrices` go straight into the geometric batch calls; calculateTransformLimits-style windows come from hg_transform_limits.
+     * Needs no image and changes no state of the instance.  Throws a bare string for an unknown transform, a list whose length is not a
+     * multiple of 4, a bad threshold or a bad hypotheses count.
+     */
+    fitMatches(matchSets, options = {}) {
+        if (options === null || options === undefined) options = {};
+        const transform = options.transform === undefined ? 'projective' : options.transform;
+        if (transform !== 'projective' && transform !== 'affine') throw ("fitMatches: options.transform must be 'projective' or 'affine'");
+        if (!Array.isArray(matchSets)) throw ("fitMatches: matchSets must be an array of match lists");
+        if (matchSets.length > 4096) throw ("fitMatches: at most 4096 frames");
+        const threshold = options.threshold === undefined ? 3 : options.threshold;
+        if (typeof threshold !== 'number' || !Number.isFinite(threshold) || threshold < 0) throw ("fitMatches: options.threshold must be a finite number >= 0");
+        const hypotheses = options.hypotheses === undefined ? 1024 : options.hypotheses;
+        if (!Number.isInteger(hypotheses) || hypotheses < 0 || hypotheses > 65536) throw ("fitMatches: options.hypotheses must be an integer in 0..65536");
+        const refit = options.refit === undefined ? true : !!options.refit;
+        if (hypotheses === 0 && !refit) throw ("fitMatches: options.hypotheses = 0 is the least-squares fit and needs refit");
+        const seed = options.seed === undefined ? 0 : options.seed;
+        if (!Number.isInteger(seed) || seed < 0 || seed > 0xffffffff) throw ("fitMatches: options.seed must be an integer in 0..2^32-1");
+        const lists = matchSets.map((s, f) => {
+            if (!(s instanceof Float32Array) && !Array.isArray(s)) throw ("fitMatches: match list " + f + " must be a Float32Array or an array of [x, y, u, v]");
+            const l = s instanceof Float32Array ? s : Float32Array.from(s.flat());
+            if (l.length % 4 !== 0) throw ("fitMatches: match list " + f + " must hold x, y, u, v quadruples");
+            return l;
+        });
+        const F = lists.length, nPoints = lists.reduce((m, l) => Math.max(m, l.length / 4), 0);
+        if (nPoints > 65536) throw ("fitMatches: at most 65536 matches per frame");
+        const counts = Int32Array.from(lists, (l) => l.length / 4);
+        const packed = new Float32Array(F * nPoints * 4);
+        lists.forEach((l, f) => packed.set(l, f * nPoints * 4));
+        let samples = null;
+        if (options.samples !== undefined && options.samples !== null) {
+            samples = options.samples instanceof Int32Array ? options.samples : Int32Array.from(options.samples.flat(Infinity));
+            if (samples.length !== F * hypotheses * 4) throw ("fitMatches: options.samples must hold frames x hypotheses x 4 indices");
+        }
+        const r = this._native.fitMatches(this._ctx, transform === 'projective' ? 1 : 0, packed, nPoints, counts, threshold, hypotheses, seed, samples, refit ? 1 : 0);
+        const inliers = lists.map((l, f) => r.mask.slice(f * nPoints, f * nPoints + counts[f]));
+        return { kind: transform, matrices: r.matrices, minimal: r.minimal, counts: r.counts, best: r.best, inliers };
+    }
+
+    /**
      * What sourceField() and remap() share: which field entry point of the addon the current state and options.loop lead to, with its
      * arguments after the context -- { entry, args, width, height }; the addon's functions are 'field' + entry and 'remap' + entry -- after
      * the refusals, the solves and the uploads that field needs.  null: the window is empty.  fmt: 0 = index, 1 = coords.

@@ -38,7 +38,7 @@ extern "C" {
                                    hg_points_to_source_geometric_frames_device, mip pyramids and the trilinear remap by that of hg_pyramid_build_device,
                                    the anisotropic remap by that of hg_remap_aniso_frames_device, mosaics by the presence of hg_mosaic_frames_device,
                                    the bicubic remap by that of hg_remap_bicubic_frames_device, exposure gains of a mosaic by that of
-                                   hg_mosaic_overlap_stats_device) */
+                                   hg_mosaic_overlap_stats_device, fitting transforms to matches by that of hg_fit_matches_frames_device) */
 
 enum {
     HG_OK = 0,
@@ -669,6 +669,75 @@ int hg_points_to_output_geometric_batch_device(hg_ctx *ctx, int kind, const doub
                                                const void *d_points, int n_points, int n_sets, void *d_out);
 int hg_points_to_output_piecewise_batch_device(hg_ctx *ctx, const float *dst_points, int max_src_x, int max_src_y, const hg_geom *geoms,
                                                int n_frames, const void *d_points, int n_points, int n_sets, void *d_out);
+
+/* ------------------------------------------------------------------------------------------------ fitting transforms to matches
+ * Every geometric entry point above starts from a matrix or from exactly three or four point pairs.  A feature matcher hands over hundreds
+ * to thousands of matches per frame, a good part of them wrong: these two calls fit one affine or projective transform per frame that
+ * ignores the wrong ones (RANSAC: many minimal hypotheses, each scored by how many matches it explains, the best one refitted by least
+ * squares over its inliers).  Not part of the reference.  The result goes straight into hg_geometric_set_frames; hg_transform_limits gives
+ * the windows.
+ * MATCHES.  d_matches holds n_frames lists of n_points slots, tightly packed; a slot is (x, y, u, v) float32, the buffer is 16-byte
+ * aligned.  (x, y) is the FROM position, (u, v) the TO position, and the matrix of frame f maps from -> to: a caller who wants the matrix the
+ * inverse warps take passes output positions as from and source positions as to (the convention of hg_geometric_set_frames_points).
+ * counts is on the HOST: frame f uses its first counts[f] slots, 0 <= counts[f] <= n_points; NULL = all of them.  NaN, +-Inf and 1e30 are
+ * legal coordinates.  A match with a coordinate that is not finite is never an inlier (and never enters a least-squares sum); a match at
+ * 1e30 obeys the score rule below like any other, which no sensible threshold lets it pass.
+ * K = 3 for HG_AFFINE, 4 for HG_PROJECTIVE.
+ * SAMPLES.  Hypothesis h of frame f is K distinct match indices.  d_samples non-NULL: n_frames x n_hyp x 4 int32 in device memory (4-byte
+ * aligned), read as they stand; affine ignores the fourth; an index outside [0, counts[f]) or a repeated index makes the hypothesis
+ * INVALID.  d_samples NULL: the device draws them by this rule, which hg_fit_sample_indices computes on the host (out = n_frames x n_hyp x 4
+ * int32, -1 in all four slots of an invalid hypothesis, -1 in the fourth slot for affine), all in uint32 arithmetic:
+ *     mix(a): a ^= a >> 16; a *= 0x7feb352d; a ^= a >> 15; a *= 0x846ca68b; a ^= a >> 16
+ *     k = mix(mix(mix(seed + 0x9e3779b9) + f) + h)
+ *     draw t = 0, 1, ..., 15:  i_t = (uint32)(((uint64)mix(k + t) * (uint32)counts[f]) >> 32)
+ * The draws are walked in order; i_t is accepted when it differs from every index accepted so far; the walk stops at K accepted.  Fewer than
+ * K after 16 draws, or counts[f] < K, makes the hypothesis invalid: at counts = 4 about 4 % of the projective hypotheses are, at 5 about
+ * 0.2 %, at 65 none in 3840 -- a frame with that few matches has few distinct samples anyway.
+ * MINIMAL SOLVE.  Projective: hg_solve_projective on the K sampled (from, to) pairs, h0..h7 with h8 == 1.  Affine: hg_solve_affine widened to
+ * double in the first 6 of 8 slots, slots 6 and 7 zero (the layout of every affine matrix here: x' = m0 x + m2 y + m4, y' = m1 x + m3 y + m5).
+ * A hypothesis whose matrix has an entry that is not finite is invalid too (collinear or coincident points).
+ * SCORE.  For match i < counts[f]: (px, py) = the matrix applied to ((double)x, (double)y) as applyProjectiveTransformToPoint :1401-1404 resp.
+ * applyAffineTransformToPoint :1382-1385 do, in f64 with IEEE division and contraction off; e = (px - u)(px - u) + (py - v)(py - v), products
+ * and sum rounded separately; the match is an INLIER iff e <= threshold * threshold (a NaN e is none).  The score of a valid hypothesis is
+ * its inlier count; the BEST hypothesis has the highest count, the lowest h among equals -- a total order, so the result does not depend on
+ * scheduling.  A frame without a valid hypothesis FAILS.
+ * OUTPUTS, all in device memory; d_mats (8-byte aligned) and d_counts are required, the others may be NULL.
+ *   d_best[f]    the best hypothesis' index, -1 for a failed frame.
+ *   d_counts[f]  its inlier count, 0 for a failed frame.
+ *   d_mask       n_frames x n_points bytes: 1 for an inlier of the best hypothesis, else 0; slots at and beyond counts[f] are 0; a failed
+ *                frame is all 0.
+ *   d_min_mats   n_frames x 8 doubles: the best hypothesis' matrix exactly as solved (the bits of hg_solve_projective / hg_solve_affine on
+ *                the sampled points); 8 quiet NaNs (0x7ff8000000000000) for a failed frame.
+ *   d_mats       n_frames x 8 doubles, the result to use: with refit == 0 a copy of d_min_mats; with refit != 0 the least-squares refit over
+ *                the best hypothesis' inliers, and the minimal matrix where the frame has K inliers or fewer or where an entry of the refit
+ *                is not finite.
+ * The mask and the count always describe the best hypothesis, not the refit (what findHomography-style callers expect, and exact).
+ * LEAST SQUARES WITHOUT SAMPLING.  n_hyp == 0 with refit != 0: every match of the frame whose four coordinates are finite is an inlier; the
+ * mask and d_counts say so; d_best is -1, d_min_mats holds NaNs, d_mats is the refit -- NaNs when fewer than K such matches remain or an entry
+ * is not finite.  n_hyp == 0 with refit == 0 is HG_ERR_INVALID.
+ * REFIT, all in f64.  Each side is normalised: c = the mean of the inliers' positions, s = sqrt(2) / the mean of sqrt(ax ax + ay ay) over
+ * a = position - c, x' = (x - cx) s (likewise y', and u', v' with the to side's c and s).  Projective: the normal equations A^T A (8 x 8) and
+ * A^T b of the rows [x' y' 1 0 0 0 -u'x' -u'y'] -> u' and [0 0 0 x' y' 1 -v'x' -v'y'] -> v', accumulated as the sums of x'x', x'y', y'y', x',
+ * y', 1, of the same six weighted by u', by v', and of the first five weighted by w = u'u' + v'v' (w (x'x') and so on); solved by Gaussian
+ * elimination with partial pivoting in one lane; denormalised as T_to^-1 H' T_from and divided through by its last entry, so h8 == 1.
+ * Affine: the 3 x 3 system of the first six sums with the two right-hand sides (sums of u'[x' y' 1]) and (sums of v'[x' y' 1]), denormalised the
+ * same way and written in the affine layout.  Every sum is accumulated in a fixed order (lane-strided partial sums, then a fixed tree) with
+ * no floating-point atomics: two runs of one call give the same bits.  The VALUE of the refit is pinned by tolerance, not bit for bit.
+ * LIMITS (HG_ERR_INVALID): NULL ctx; unknown kind; NULL or misaligned required pointers when there is work; n_points outside 0..65536; n_hyp
+ * outside 0..65536; n_frames outside 0..4096; a counts[f] outside [0, n_points]; threshold not finite or negative (0 is legal).  n_frames == 0
+ * is HG_OK and nothing is written.  hg_fit_sample_indices makes the same checks, without a context.
+ * CONTEXT.  The call needs no image, mesh or frame set.  It settles what hg_points_to_output_geometric_batch_device settles (queued runs),
+ * then is asynchronous on the ctx stream; counts is copied before it returns.  It touches no hg_last_*, no sampling mode, no plan, no policy
+ * state and no staged frame set.  Its scratch (n_frames x n_hyp matrices and flags) lives in buffers the context owns, grown on demand and
+ * reused.
+ * COST.  The hot loop is n_frames x n_hyp x counts reprojections, two IEEE f64 divisions each for projective.  MEASURED (MI355X, whole call,
+ * medians of 31; EXPERIMENTS.md, "Fitting"): 64 frames x 2048 matches x 2048 hypotheses 0.46 ms projective (5.9e11 reprojections / s), 0.21 ms
+ * affine, the refit 0.02-0.03 ms on top; 64 x 512 x 512 0.10 / 0.07 ms; ONE frame x 4096 x 4096 0.48 / 0.25 ms -- a single frame fills only
+ * n_hyp / 256 workgroups, so frames are what the call scales over.  The numpy model takes 94 ms for ONE frame of the first case. */
+int hg_fit_sample_indices(int kind, uint32_t seed, int n_frames, const int32_t *counts, int n_points, int n_hyp, int32_t *out);
+int hg_fit_matches_frames_device(hg_ctx *ctx, int kind, const void *d_matches, int n_points, const int32_t *counts, int n_frames,
+                                 double threshold, int n_hyp, uint32_t seed, const int32_t *d_samples, int refit,
+                                 double *d_mats, double *d_min_mats, int32_t *d_counts, int32_t *d_best, uint8_t *d_mask);
 
 /* ------------------------------------------------------------------------------------------------ forward (scatter) paths
  * What warp() dispatches to when the output is not larger than the input (:421, :426).  `m` is the FORWARD matrix
