@@ -1,6 +1,6 @@
 // hg_ctx.h -- the context behind the C ABI of include/hgwarp.h and the helpers its translation units share
 // (hg_api.hip: library / context / buffers / host-side solves / source image; hg_api_geometric.hip; hg_api_piecewise.hip;
-// hg_api_forward.hip; hg_api_state.hip; hg_api_field.hip; hg_api_points.hip; hg_api_fit.hip).  Its memory is owned through hg_mem.h.  Internal: nothing here is exported.
+// hg_api_forward.hip; hg_api_state.hip; hg_api_field.hip; hg_api_points.hip; hg_api_fit.hip; hg_api_match.hip).  Its memory is owned through hg_mem.h.  Internal: nothing here is exported.
 #pragma once
 #include "../../include/hgwarp.h"
 #include "hg_kernels.h"
@@ -214,6 +214,14 @@ struct hg_ctx {
     DevBuf<int32_t> d_fit_valid;
     DevBuf<uint64_t> d_fit_frames;                             // F best words, then the F counts (int32, padded to 8 bytes)
     StageRing<4> fit_stage;                                    // the counts go up through page-locked staging, stream-ordered
+
+    // matching descriptors (hg_api_match.hip): the two-nearest records of the queries and, for the cross-check, of the train rows; the counts of
+    // both sides; grown on demand
+    DevBuf<uint4> d_match_fwd, d_match_rev;
+    DevBuf<uint64_t> d_match_keys;                             // the cross-check's atomic form: per train row of every frame the word (d << 32) | i of its best query
+    int opt_match_cross = -1;                                  // the cross-check of HG_DESC_U8: 0 = by a second launch with the sides swapped (measurements), else by atomicMin
+    DevBuf<int32_t> d_match_counts;                            // F query counts, then n_train_sets train counts (padded to 8 bytes)
+    StageRing<4> match_stage;
 
     // scratch
     DevBuf<int32_t> d_map32;

@@ -271,6 +271,20 @@ struct FitArgs {
 };
 void launch_fit(const FitArgs &a, hipStream_t stream);
 
+// Matching descriptors (hg_k_match.hip; the rules: hg_match_dev.h): k_match_bits resp. k_match_u8 for the two nearest train rows of every query,
+// the same kernel with the sides swapped for the best query of every train row (cross_check), then k_match_finish.  query = F lists of
+// n_query rows of `stride` bytes, train = n_train_sets lists of n_train rows (frame f reads list f % n_train_sets), both 16-byte aligned;
+// counts_q = F and counts_t = n_train_sets int32 on the device; rr = ratio (bits) resp. ratio * ratio (bytes), ratio_on = 0: no ratio test.
+// cross_check: 0 none, 1 the swapped launch (scratch ws_rev), 2 the atomic form (scratch ws_keys = F x n_train words set to all ones by the caller).
+// scratch: ws_fwd = F x n_query and ws_rev = F x n_train records {j1, d1, d2, 0}.  out_matches / out_pairs /
+// out_nn may be nullptr; out_matches needs both point lists.
+struct MatchArgs {
+    int kind, desc_bytes; size_t stride; const void *query; int n_query; const void *train; int n_train; int n_frames, n_train_sets;
+    const int32_t *counts_q, *counts_t; int ratio_on; double rr; uint32_t max_distance; int cross_check; const void *query_pts, *train_pts;
+    uint4 *ws_fwd, *ws_rev; unsigned long long *ws_keys; int32_t *out_counts; void *out_matches; int32_t *out_pairs, *out_nn;
+};
+void launch_match(const MatchArgs &a, hipStream_t stream);
+
 // k_geo: _inverseGeometricWarp pixel loop :997-1011 for all frames.  mats = F x 8 doubles (inverse matrices).
 // f32_exact: every affine matrix entry is a float value and |x| < 2^28 (lets the kernel use an exact-product fma).
 // n_imgs / img_stride: frame f reads the source at img + (f % n_imgs) * img_stride.

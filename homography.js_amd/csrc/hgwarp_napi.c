@@ -1164,6 +1164,78 @@ static napi_value fn_fit_matches(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* matchDescriptors(handle, kind, descBytes, stride, query, nQuery, countsQ, train, nTrain, countsT, ratio, maxDistance, crossCheck,
+ * queryPoints | null, trainPoints | null): the accepted nearest-neighbour pairs of every frame (hg_match_descriptors_frames_device).  query:
+ * Uint8Array of F x nQuery x stride, F = countsQ.length; train: Uint8Array of S x nTrain x stride, S = countsT.length; the points: Float32Array
+ * of F x nQuery x 2 resp. S x nTrain x 2, both or none.  Everything goes up into device memory of the call's own, the entry runs, and
+ * { counts: Int32Array(F), pairs: Int32Array(F x nQuery x 2), matches: Float32Array(F x nQuery x 4) | null } come down.  Needs no image. */
+static napi_value fn_match_descriptors(napi_env env, napi_callback_info info)
+{
+    napi_value a[15];
+    if (!get_args(env, info, 15, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    int kind, desc_bytes, stride, n_query, n_train, cross; size_t n_q = 0, n_t = 0, n_cq = 0, n_ct = 0, n_qp = 0, n_tp = 0; double ratio, maxd;
+    if (!get_i32(env, a[1], &kind) || !get_i32(env, a[2], &desc_bytes) || !get_i32(env, a[3], &stride)) return NULL;
+    uint8_t *q = (uint8_t *)get_typed(env, a[4], napi_uint8_array, &n_q, "query"); if (!q) return NULL;
+    if (!get_i32(env, a[5], &n_query)) return NULL;
+    int32_t *cq = (int32_t *)get_typed(env, a[6], napi_int32_array, &n_cq, "countsQ"); if (!cq) return NULL;
+    uint8_t *t = (uint8_t *)get_typed(env, a[7], napi_uint8_array, &n_t, "train"); if (!t) return NULL;
+    if (!get_i32(env, a[8], &n_train)) return NULL;
+    int32_t *ct = (int32_t *)get_typed(env, a[9], napi_int32_array, &n_ct, "countsT"); if (!ct) return NULL;
+    if (napi_get_value_double(env, a[10], &ratio) != napi_ok) return throw_str(env, "hgwarp: ratio must be a number");
+    if (napi_get_value_double(env, a[11], &maxd) != napi_ok || !(maxd >= 0 && maxd <= 4294967295.0)) return throw_str(env, "hgwarp: maxDistance must be a uint32");
+    if (!get_i32(env, a[12], &cross)) return NULL;
+    napi_valuetype vq, vt;
+    NAPI_OK(napi_typeof(env, a[13], &vq)); NAPI_OK(napi_typeof(env, a[14], &vt));
+    const int has_q = vq != napi_null && vq != napi_undefined, has_t = vt != napi_null && vt != napi_undefined;
+    if (has_q != has_t) return throw_str(env, "hgwarp: matchDescriptors: queryPoints and trainPoints come together");
+    float *qp = NULL, *tp = NULL;
+    if (has_q) {
+        qp = (float *)get_typed(env, a[13], napi_float32_array, &n_qp, "queryPoints"); if (!qp) return NULL;
+        tp = (float *)get_typed(env, a[14], napi_float32_array, &n_tp, "trainPoints"); if (!tp) return NULL;
+    }
+    if (stride < 16 || stride > 1024 || n_query < 0 || n_query > 65536 || n_train < 0 || n_train > 65536 || n_cq > 4096 || n_ct > 4096)
+        return throw_str(env, "hgwarp: matchDescriptors: stride, nQuery, nTrain or the number of sets is out of range");
+    const size_t F = n_cq, S = n_ct, NQ = (size_t)n_query, NT = (size_t)n_train, ST = (size_t)stride;
+    if (n_q != F * NQ * ST || n_t != S * NT * ST) return throw_str(env, "hgwarp: query / train must hold sets x rows x stride bytes");
+    if (has_q && (n_qp != F * NQ * 2 || n_tp != S * NT * 2)) return throw_str(env, "hgwarp: queryPoints / trainPoints must hold sets x rows x 2 floats");
+    void *p_cnt, *p_pairs, *p_m = NULL;
+    napi_value out, v_cnt, v_pairs, v_m;
+    if (!(v_cnt = make_typed(env, napi_int32_array, F, 4, &p_cnt)) || !(v_pairs = make_typed(env, napi_int32_array, F * NQ * 2, 4, &p_pairs))) return NULL;
+    if (has_q) { if (!(v_m = make_typed(env, napi_float32_array, F * NQ * 4, 4, &p_m))) return NULL; }
+    else NAPI_OK(napi_get_null(env, &v_m));
+    NAPI_OK(napi_create_object(env, &out));
+    NAPI_OK(napi_set_named_property(env, out, "counts", v_cnt)); NAPI_OK(napi_set_named_property(env, out, "pairs", v_pairs));
+    NAPI_OK(napi_set_named_property(env, out, "matches", v_m));
+    if (!F) return out;
+#define MATCH_PAD(b) (((size_t)(b) + 255) & ~(size_t)255)
+    const size_t o_q = 0, o_t = o_q + MATCH_PAD(F * NQ * ST), o_qp = o_t + MATCH_PAD(S * NT * ST), o_tp = o_qp + MATCH_PAD(has_q ? F * NQ * 8 : 0),
+                 o_cnt = o_tp + MATCH_PAD(has_q ? S * NT * 8 : 0), o_pairs = o_cnt + MATCH_PAD(F * 4), o_m = o_pairs + MATCH_PAD(F * NQ * 8),
+                 total = o_m + MATCH_PAD(has_q ? F * NQ * 16 : 0);
+#undef MATCH_PAD
+    void *d = NULL;
+    HG_CALL(h->ctx, "hg_device_alloc", hg_device_alloc(h->ctx, total, &d));
+    uint8_t *b = (uint8_t *)d;
+    int rc = HG_OK;
+    const char *what = "hg_copy_to_device";
+    if (F * NQ) rc = hg_copy_to_device(h->ctx, b + o_q, q, F * NQ * ST);
+    if (rc == HG_OK && S * NT) rc = hg_copy_to_device(h->ctx, b + o_t, t, S * NT * ST);
+    if (rc == HG_OK && has_q && F * NQ) rc = hg_copy_to_device(h->ctx, b + o_qp, qp, F * NQ * 8);
+    if (rc == HG_OK && has_q && S * NT) rc = hg_copy_to_device(h->ctx, b + o_tp, tp, S * NT * 8);
+    if (rc == HG_OK) {
+        what = "hg_match_descriptors_frames_device";
+        rc = hg_match_descriptors_frames_device(h->ctx, kind, desc_bytes, ST, b + o_q, n_query, cq, (int)F, b + o_t, n_train, ct, (int)S, ratio, (uint32_t)maxd, cross,
+                                                has_q ? b + o_qp : NULL, has_q ? b + o_tp : NULL, (int32_t *)(b + o_cnt), has_q ? b + o_m : NULL,
+                                                (int32_t *)(b + o_pairs), NULL);
+    }
+    if (rc == HG_OK) { what = "hg_copy_to_host"; rc = hg_copy_to_host(h->ctx, p_cnt, b + o_cnt, F * 4); }
+    if (rc == HG_OK && F * NQ) rc = hg_copy_to_host(h->ctx, p_pairs, b + o_pairs, F * NQ * 8);
+    if (rc == HG_OK && has_q && F * NQ) rc = hg_copy_to_host(h->ctx, p_m, b + o_m, F * NQ * 16);
+    if (rc != HG_OK) { napi_value e = throw_hg(env, h->ctx, what, rc); hg_device_free(h->ctx, d); return e; }
+    HG_CALL(h->ctx, "hg_device_free", hg_device_free(h->ctx, d));
+    return out;
+}
+
 /* redoneFrames(ctx): frames the fused kernels flagged and hg_sync redid through the map so far (hg_redone_frames; tests) */
 static napi_value fn_redone_frames(napi_env env, napi_callback_info info)
 {
@@ -1878,6 +1950,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "pointsInverseGeometric", fn_points_inverse_geometric }, { "pointsInversePiecewise", fn_points_inverse_piecewise },
         { "pointsForwardGeometric", fn_points_forward_geometric }, { "pointsForwardPiecewise", fn_points_forward_piecewise },
         { "fitMatches", fn_fit_matches },
+        { "matchDescriptors", fn_match_descriptors },
         { "solveAffineTriangles", fn_solve_affine_triangles }, { "warpInversePiecewiseState", fn_warp_inverse_piecewise_state },
         { "warpForwardPiecewiseState", fn_warp_forward_piecewise_state },
         { "release", fn_release }, { "setPinnedLimit", fn_set_pinned_limit }, { "poolStats", fn_pool_stats }, { "redoneFrames", fn_redone_frames }, { "spanCacheStats", fn_span_cache_stats }, { "setSampling", fn_set_sampling }, { "multiSetSampling", fn_multi_set_sampling }, { "_poolTestFrames", fn_pool_test_frames }, { "poolPressure", fn_pool_pressure }, { "poolCollected", fn_pool_collected },

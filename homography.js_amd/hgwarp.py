@@ -28,6 +28,8 @@ ELEM_F32, ELEM_U8 = 0, 1
 MOSAIC_LAST, MOSAIC_MEAN, MOSAIC_FEATHER = 0, 1, 2
 # (B, C) of the named cubics of the bicubic remap (hg_remap_bicubic_frames_device)
 CUBIC_CATMULL_ROM, CUBIC_MITCHELL, CUBIC_BSPLINE = (0.0, 0.5), (1 / 3, 1 / 3), (1.0, 0.0)
+# descriptor kinds of the matcher (hg_match_descriptors_frames_device): binary rows under the Hamming distance, byte vectors under squared L2
+DESC_BITS, DESC_U8 = 0, 1
 
 # every symbol include/hgwarp.h declares (tests check that the built library exports all of them)
 EXPORTS = [
@@ -62,6 +64,7 @@ EXPORTS = [
     "hg_mosaic_frames_device", "hg_mosaic_overlap_stats_device", "hg_mosaic_solve_gains", "hg_mosaic_frames_gain_device",
     "hg_remap_bicubic_frames_device",
     "hg_fit_sample_indices", "hg_fit_matches_frames_device",
+    "hg_match_descriptors_frames_device",
 ]
 
 
@@ -176,6 +179,8 @@ def lib():
         "hg_mosaic_solve_gains": (i, [C.POINTER(C.c_uint64), i, i, C.c_double, C.c_double, C.POINTER(C.c_float)]),
         "hg_fit_sample_indices": (i, [i, C.c_uint32, i, C.POINTER(C.c_int32), i, i, C.POINTER(C.c_int32)]),
         "hg_fit_matches_frames_device": (i, [vp, i, vp, i, C.POINTER(C.c_int32), i, d, i, C.c_uint32, vp, i, vp, vp, vp, vp, vp]),
+        "hg_match_descriptors_frames_device": (i, [vp, i, i, sz, vp, i, C.POINTER(C.c_int32), i, vp, i, C.POINTER(C.c_int32), i, d, C.c_uint32, i,
+                                                   vp, vp, vp, vp, vp, vp]),
         "hg_points_to_source_geometric_frames_device": (i, [vp, vp, i, i, vp]),
         "hg_points_to_source_piecewise_frames_device": (i, [vp, vp, i, i, vp]),
         "hg_points_to_output_geometric_batch_device": (i, [vp, i, f64p, C.POINTER(Geom), i, vp, i, i, vp]),
@@ -842,6 +847,22 @@ class Context:
         self._c(lib().hg_fit_matches_frames_device(self._h, int(kind), vp(d_matches), int(n_points), p, int(n_frames), float(threshold), int(n_hyp),
                                                    int(seed) & 0xffffffff, vp(d_samples), 1 if refit else 0, vp(d_mats), vp(d_min_mats), vp(d_counts),
                                                    vp(d_best), vp(d_mask)))
+
+    def match_descriptors_frames_device(self, kind, desc_bytes, stride, d_query, n_query, counts_q, n_frames, d_train, n_train, counts_t, n_train_sets,
+                                        d_counts, ratio=0.8, max_distance=0xffffffff, cross_check=False, d_query_pts=0, d_train_pts=0, d_matches=0,
+                                        d_pairs=0, d_nn=0):
+        """hg_match_descriptors_frames_device: per frame the nearest and second-nearest of n_train train descriptors (list f % n_train_sets) for
+        each of n_query query descriptors (rows of `stride` bytes, the first desc_bytes of them data; kind DESC_BITS: Hamming, DESC_U8: squared
+        L2), the ratio test (0 = none), the distance cap and the optional cross-check.  counts_q / counts_t: rows used per list, on the host, or
+        None for all.  d_counts gets the accepted pairs per frame; d_pairs the compacted (i, j) lists, d_matches the (x, y, u, v) slots a fit
+        reads (needs both point buffers), d_nn {j1, d1, d2, accepted} per query.  Asynchronous; every output is device memory, 0 = not wanted."""
+        _, pq, _ = _counts(counts_q, n_frames)
+        _, pt, _ = _counts(counts_t, n_train_sets)
+        vp = lambda v: C.c_void_p(int(v) or None)
+        self._c(lib().hg_match_descriptors_frames_device(self._h, int(kind), int(desc_bytes), int(stride), vp(d_query), int(n_query), pq, int(n_frames),
+                                                         vp(d_train), int(n_train), pt, int(n_train_sets), float(ratio), int(max_distance) & 0xffffffff,
+                                                         1 if cross_check else 0, vp(d_query_pts), vp(d_train_pts), vp(d_counts), vp(d_matches),
+                                                         vp(d_pairs), vp(d_nn)))
 
     def mosaic_overlap_stats_device(self, geoms, d_coords, d_frames, channels, canvas, d_stats, field_offsets=None, frame_offsets=None):
         """The overlaps of a set of uint8 frames measured on the device (asynchronous): d_stats gets F * F * 2 uint64 words -- for every ordered

@@ -462,6 +462,73 @@ class Homography {
     }
 
     /**
+     * The matches fitMatches() starts from: per frame the nearest train descriptor of every query descriptor, kept when it passes Lowe's
+     * ratio test, the distance cap and, if asked for, the cross-check (not part of the reference; hg_match_descriptors_frames_device in
+     * include/hgwarp.h has the rules, all of them exact).  querySets: an array of F Uint8Arrays of count_f x descBytes bytes; trainSets: an
+     * array of S Uint8Arrays, 1 <= S <= max(F, 1): frame f is matched against train set f % S (one keyframe for all frames: S = 1).  The
+     * counts may differ: the sets are padded to the longest (rows to a multiple of 16 bytes) and the device is told each set's count.
+     * options: { kind: 'bits' (default; binary descriptors, Hamming distance) | 'u8' (byte vectors, squared L2), descBytes = 32 for 'bits',
+     *            128 for 'u8', ratio = 0.8 (0: no ratio test), maxDistance = 0xffffffff (no cap), crossCheck = false,
+     *            queryPoints / trainPoints: per set a Float32Array of x, y pairs or an array of [x, y], one per descriptor; both or none }.
+     * Returns one record per frame: { count, pairs: Int32Array(2 count) of (query index, train index) in ascending query index,
+     *                                 matches: Float32Array(4 count) of (x, y, u, v) = (query position, train position) -- with points only }.
+     * The array of `matches` is what fitMatches() accepts as matchSets; its matrices map query -> train.
+     * Needs no image and changes no state of the instance.  Throws a bare string for an unknown kind, a set whose length is not a multiple of
+     * descBytes, a bad ratio, a bad maxDistance or points that do not fit their set.
+     */
+    matchDescriptors(querySets, trainSets, options = {}) {
+        if (options === null || options === undefined) options = {};
+        const kind = options.kind === undefined ? 'bits' : options.kind;
+        if (kind !== 'bits' && kind !== 'u8') throw ("matchDescriptors: options.kind must be 'bits' or 'u8'");
+        const descBytes = options.descBytes === undefined ? (kind === 'bits' ? 32 : 128) : options.descBytes;
+        if (!Number.isInteger(descBytes) || descBytes < 1 || descBytes > 512) throw ("matchDescriptors: options.descBytes must be an integer in 1..512");
+        const ratio = options.ratio === undefined ? 0.8 : options.ratio;
+        if (typeof ratio !== 'number' || !(ratio >= 0 && ratio <= 1)) throw ("matchDescriptors: options.ratio must be a number in 0..1 (0: no ratio test)");
+        const maxDistance = options.maxDistance === undefined ? 0xffffffff : options.maxDistance;
+        if (!Number.isInteger(maxDistance) || maxDistance < 0 || maxDistance > 0xffffffff) throw ("matchDescriptors: options.maxDistance must be an integer in 0..2^32-1");
+        const crossCheck = options.crossCheck === undefined ? false : !!options.crossCheck;
+        if (!Array.isArray(querySets) || !Array.isArray(trainSets)) throw ("matchDescriptors: querySets and trainSets must be arrays of Uint8Arrays");
+        if (querySets.length > 4096) throw ("matchDescriptors: at most 4096 frames");
+        if (trainSets.length < 1 || trainSets.length > Math.max(querySets.length, 1)) throw ("matchDescriptors: trainSets must hold 1..max(frames, 1) sets");
+        const stride = (descBytes + 15) & ~15;
+        const pack = (sets, name) => {
+            const counts = Int32Array.from(sets, (s, f) => {
+                if (!(s instanceof Uint8Array)) throw ("matchDescriptors: " + name + " set " + f + " must be a Uint8Array");
+                if (s.length % descBytes !== 0) throw ("matchDescriptors: " + name + " set " + f + " must hold rows of descBytes bytes");
+                return s.length / descBytes;
+            });
+            const n = counts.reduce((m, c) => Math.max(m, c), 0);
+            if (n > 65536) throw ("matchDescriptors: at most 65536 descriptors per set");
+            const rows = new Uint8Array(sets.length * n * stride);
+            sets.forEach((s, f) => { for (let i = 0; i < counts[f]; i++) rows.set(s.subarray(i * descBytes, (i + 1) * descBytes), (f * n + i) * stride); });
+            return { counts, n, rows };
+        };
+        const q = pack(querySets, 'query'), t = pack(trainSets, 'train');
+        const points = (lists, side, name) => {
+            if (!Array.isArray(lists) || lists.length !== side.counts.length) throw ("matchDescriptors: options." + name + " must hold one list per set");
+            const out = new Float32Array(side.counts.length * side.n * 2);
+            lists.forEach((p, f) => {
+                if (!(p instanceof Float32Array) && !Array.isArray(p)) throw ("matchDescriptors: options." + name + " list " + f + " must be a Float32Array or an array of [x, y]");
+                const l = p instanceof Float32Array ? p : Float32Array.from(p.flat());
+                if (l.length !== side.counts[f] * 2) throw ("matchDescriptors: options." + name + " list " + f + " must hold one x, y pair per descriptor");
+                out.set(l, f * side.n * 2);
+            });
+            return out;
+        };
+        const hasQ = options.queryPoints !== undefined && options.queryPoints !== null, hasT = options.trainPoints !== undefined && options.trainPoints !== null;
+        if (hasQ !== hasT) throw ("matchDescriptors: options.queryPoints and options.trainPoints come together");
+        const qp = hasQ ? points(options.queryPoints, q, 'queryPoints') : null, tp = hasT ? points(options.trainPoints, t, 'trainPoints') : null;
+        const r = this._native.matchDescriptors(this._ctx, kind === 'bits' ? 0 : 1, descBytes, stride, q.rows, q.n, q.counts, t.rows, t.n, t.counts, ratio, maxDistance,
+                                                crossCheck ? 1 : 0, qp, tp);
+        return querySets.map((s, f) => {
+            const count = r.counts[f];
+            const rec = { count, pairs: r.pairs.slice(f * q.n * 2, (f * q.n + count) * 2) };
+            if (hasQ) rec.matches = r.matches.slice(f * q.n * 4, (f * q.n + count) * 4);
+            return rec;
+        });
+    }
+
+    /**
      * What sourceField() and remap() share: which field entry point of the addon the current state and options.loop lead to, with its
      * arguments after the context -- { entry, args, width, height }; the addon's functions are 'field' + entry and 'remap' + entry -- after
      * the refusals, the solves and the uploads that field needs.  null: the window is empty.  fmt: 0 = index, 1 = coords.

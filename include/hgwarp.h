@@ -38,7 +38,8 @@ extern "C" {
                                    hg_points_to_source_geometric_frames_device, mip pyramids and the trilinear remap by that of hg_pyramid_build_device,
                                    the anisotropic remap by that of hg_remap_aniso_frames_device, mosaics by the presence of hg_mosaic_frames_device,
                                    the bicubic remap by that of hg_remap_bicubic_frames_device, exposure gains of a mosaic by that of
-                                   hg_mosaic_overlap_stats_device, fitting transforms to matches by that of hg_fit_matches_frames_device) */
+                                   hg_mosaic_overlap_stats_device, fitting transforms to matches by that of hg_fit_matches_frames_device);
+                                   matching descriptors by the presence of hg_match_descriptors_frames_device */
 
 enum {
     HG_OK = 0,
@@ -739,6 +740,68 @@ int hg_fit_matches_frames_device(hg_ctx *ctx, int kind, const void *d_matches, i
                                  double threshold, int n_hyp, uint32_t seed, const int32_t *d_samples, int refit,
                                  double *d_mats, double *d_min_mats, int32_t *d_counts, int32_t *d_best, uint8_t *d_mask);
 
+/* ------------------------------------------------------------------------------------------------ matching descriptors
+ * The matcher that hands hg_fit_matches_frames_device its matches: for every frame a brute-force search of the nearest and second-nearest
+ * train descriptor of every query descriptor, Lowe's ratio test, a distance cap and an optional cross-check, compacted into exactly the slot
+ * format the fit reads.  Descriptors -> matches -> transforms -> warps -> mosaic then stay in device memory; only n_frames counts come down
+ * to the host.  Not part of the reference.  Every result is an integer or a copied word: the call is exact, it has no tolerance.
+ * DESCRIPTORS.  d_query holds n_frames lists of n_query rows of `stride` bytes, d_train holds n_train_sets lists of n_train rows; frame f
+ * reads train list f % n_train_sets (the rule hg_set_images_device gives images; one keyframe for all frames is n_train_sets = 1).  Only the
+ * first desc_bytes bytes of a row are data; the bytes from desc_bytes to stride are padding, may hold anything and never enter a distance.
+ * stride is a multiple of 16 and >= desc_bytes; both buffers are 16-byte aligned.  counts_q (n_frames entries) and counts_t (n_train_sets
+ * entries) are on the HOST; NULL = every slot.  Frame f uses its first cq = counts_q[f] query rows and the first ct = counts_t[f %
+ * n_train_sets] train rows.
+ * DISTANCES, exact non-negative integers.  HG_DESC_BITS (binary descriptors: ORB 32 bytes, BRISK 64, AKAZE 61): d = the number of set bits
+ * of q XOR t over desc_bytes bytes (Hamming).  HG_DESC_U8 (byte vectors: SIFT as 128 x u8): d = the sum over k < desc_bytes of
+ * (q_k - t_k)(q_k - t_k), bytes read as unsigned; at most 512 * 255 * 255 < 2^25.
+ * NEIGHBOURS of query i < cq, with ct >= 1: d1 = the smallest distance over j < ct; j1 = the LOWEST j that attains it; d2 = the second entry
+ * of the ascending multiset of the ct distances, so d2 == d1 when two train rows tie for the nearest; with ct == 1 there is no d2.  This is
+ * a total order: the result does not depend on tiling or scheduling.
+ * ACCEPTANCE.  Query i yields the pair (i, j1) iff all of
+ *   1. d1 <= max_distance (uint32 comparison; 0xFFFFFFFF = no cap);
+ *   2. the ratio test: ratio == 0 switches it off; otherwise, with ct >= 2, in f64 with the product rounded on its own:
+ *        HG_DESC_BITS  (double)d1 < ratio * (double)d2
+ *        HG_DESC_U8    (double)d1 < r2 * (double)d2, r2 = ratio * ratio rounded once in double (squared distances, squared ratio)
+ *      so a tie d1 == d2 fails every ratio <= 1 (d1 == d2 == 0 included); with ct == 1 there is nothing to compare with and the test PASSES;
+ *   3. with cross_check != 0: i is the best query of j1, where the best query of train row j is the query i' < cq with the smallest
+ *      distance to j, the lowest i' among equals.
+ * OUTPUTS, all in device memory.  d_counts is required; the others may be NULL and are then never written.
+ *   d_counts[f]  the number of accepted pairs of frame f.
+ *   d_pairs      n_frames x n_query x 2 int32: the accepted pairs (i, j1) of the frame compacted to the front in ascending i, the
+ *                remaining slots (-1, -1).
+ *   d_matches    n_frames x n_query slots (x, y, u, v) float32, 16-byte aligned: slot k describes pair k; (x, y) is the query row's
+ *                position, (u, v) the train row's, copied bit for bit (NaN payloads included) from d_query_pts (n_frames x n_query x 2
+ *                float32, 8-byte aligned) and d_train_pts (n_train_sets x n_train x 2, the list of f % n_train_sets); slots at and beyond
+ *                d_counts[f] hold 0x7fc00000 in all four words.  Needs both point buffers.  This is d_matches of
+ *                hg_fit_matches_frames_device with n_points = n_query and counts = the downloaded d_counts; the fit then gives the matrix
+ *                query -> train.  For the matrix the inverse warps take (output -> source) pass the descriptors of the OUTPUT side (the
+ *                keyframe, the panorama) as query and those of the frame to be warped as train.
+ *   d_nn         n_frames x n_query x 4 int32 {j1, d1, d2, accepted}: the raw two-nearest answer, accepted = 1 or 0; d2 = -1 when
+ *                ct == 1; {-1, -1, -1, 0} for i >= cq or ct == 0.
+ * LIMITS (HG_ERR_INVALID), checked in this order (the shape first: those checks need no device): unknown kind; desc_bytes outside
+ * 1..512; stride not a multiple of 16 or below desc_bytes; n_query outside 0..65536; n_train outside 0..65536; n_frames outside 0..4096;
+ * n_train_sets outside 1..max(n_frames, 1); a counts_q[f] outside [0, n_query]; a counts_t[s] outside [0, n_train]; ratio not finite,
+ * negative or above 1; NULL ctx; then, with n_frames > 0: d_counts NULL, d_query or d_train NULL while n_query > 0 and n_train > 0; a
+ * misaligned pointer (descriptors and d_matches 16, points 8, the int32 outputs 4); d_matches without both point buffers.  n_frames == 0 is HG_OK and nothing is written.  n_query == 0 writes d_counts only, all
+ * zeros.  n_train == 0 (or ct == 0) accepts nothing: zero counts, padding everywhere.
+ * CONTEXT.  As the fit: no image, mesh or frame set is needed; queued runs are settled first, then the call is asynchronous on the ctx
+ * stream; the counts are copied before it returns.  It touches no hg_last_*, no sampling mode, no plan, no policy state and no staged frame
+ * set.  Its scratch (one 16-byte record per query row and, with cross_check, per train row of every frame) lives in buffers the context owns,
+ * grown on demand and reused.  No floating-point atomics; the only atomics are integer minima on a total order ((d << 32) | i per train
+ * row, the cross-check of HG_DESC_U8): two runs of one call give the same bytes.
+ * COST.  n_frames x cq x ct distances.  HG_DESC_U8 runs on the i8 matrix cores.  cross_check runs the search a second time with the sides
+ * swapped for HG_DESC_BITS (2 x) and folds the best query of a train row into the one search for HG_DESC_U8 (about 1.5 x).  MEASURED
+ * (MI355X, whole call, medians of 31; EXPERIMENTS.md, "Matching"): 64 frames x 2048 x 2048 rows take 0.25 ms for 32-byte bits (1.1e12
+ * pairs / s; 0.46 ms with cross_check) and 0.18 ms for 128-byte u8 (1.5e12 pairs / s; 0.27 ms); ONE frame x 4096 x 4096 takes 0.34 / 0.14 ms
+ * -- a single frame fills only n_query / 64 workgroups, so frames are what the call scales over. */
+enum { HG_DESC_BITS = 0, HG_DESC_U8 = 1 };
+int hg_match_descriptors_frames_device(hg_ctx *ctx, int desc_kind, int desc_bytes, size_t stride,
+                                       const void *d_query, int n_query, const int32_t *counts_q, int n_frames,
+                                       const void *d_train, int n_train, const int32_t *counts_t, int n_train_sets,
+                                       double ratio, uint32_t max_distance, int cross_check,
+                                       const void *d_query_pts, const void *d_train_pts,
+                                       int32_t *d_counts, void *d_matches, int32_t *d_pairs, int32_t *d_nn);
+
 /* ------------------------------------------------------------------------------------------------ forward (scatter) paths
  * What warp() dispatches to when the output is not larger than the input (:421, :426).  `m` is the FORWARD matrix
  * (_transformMatrix).  Sequential "last writer in raster order wins" is reproduced deterministically (atomicMax of the
@@ -944,7 +1007,10 @@ int hg_span_cache_stats(hg_ctx *ctx, int64_t out[6]);
  *           redoes it and the mesh goes back to k_pw_patch;
  *   "fwd_tiles": see hg_last_forward_kernel;
  *   "remap_pack" (default -1 = on): hg_remap_index_frames_device gives a lane 4 consecutive 1-byte pixels and one packed store (the
- *           only pixel size for which that was measured to win); 0: one pixel per lane, for measurements.
+ *           only pixel size for which that was measured to win); 0: one pixel per lane, for measurements;
+ *   "match_cross" (default -1): the cross-check of hg_match_descriptors_frames_device for HG_DESC_U8 finds the best query of a train row
+ *           by atomicMin inside the search; 0: by a second search with the sides swapped (what HG_DESC_BITS always does), for measurements.
+ *           The results never depend on it.
  * Unknown keys are refused (HG_ERR_INVALID). */
 int hg_set_option(hg_ctx *ctx, const char *key, int value);
 /* Number of XCCs the ctx maps row bands to (what hg_create read from the device, or the "xcc" option). */
