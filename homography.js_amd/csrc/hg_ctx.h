@@ -1,6 +1,6 @@
 // hg_ctx.h -- the context behind the C ABI of include/hgwarp.h and the helpers its translation units share
 // (hg_api.hip: library / context / buffers / host-side solves / source image; hg_api_geometric.hip; hg_api_piecewise.hip;
-// hg_api_forward.hip; hg_api_state.hip; hg_api_field.hip; hg_api_points.hip; hg_api_fit.hip; hg_api_match.hip).  Its memory is owned through hg_mem.h.  Internal: nothing here is exported.
+// hg_api_forward.hip; hg_api_state.hip; hg_api_field.hip; hg_api_points.hip; hg_api_fit.hip; hg_api_match.hip; hg_api_detect.hip).  Its memory is owned through hg_mem.h.  Internal: nothing here is exported.
 #pragma once
 #include "../../include/hgwarp.h"
 #include "hg_kernels.h"
@@ -222,6 +222,12 @@ struct hg_ctx {
     int opt_match_cross = -1;                                  // the cross-check of HG_DESC_U8: 0 = by a second launch with the sides swapped (measurements), else by atomicMin
     DevBuf<int32_t> d_match_counts;                            // F query counts, then n_train_sets train counts (padded to 8 bytes)
     StageRing<4> match_stage;
+
+    // detecting and describing keypoints (hg_api_detect.hip): the per-cell records and counts, the planes' lists of flat indices, and the turned
+    // pattern, uploaded once; grown on demand
+    DevBuf<uint4> d_detect_rec;
+    DevBuf<int32_t> d_detect_cnt, d_detect_list;
+    DevBuf<int8_t> d_detect_table;
 
     // scratch
     DevBuf<int32_t> d_map32;

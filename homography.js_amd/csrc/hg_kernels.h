@@ -285,6 +285,16 @@ struct MatchArgs {
 };
 void launch_match(const MatchArgs &a, hipStream_t stream);
 
+// Detecting and describing keypoints (hg_k_detect.hip; the rules: hg_detect_dev.h): k_detect_cells, k_detect_compact and, when descriptors or
+// info are asked for, k_detect_describe.  planes = n_planes planes of W x H x channels u8 at plane_stride bytes.  scratch: ws_rec = n_planes x
+// cells x per_cell 16-byte records, ws_cnt = n_planes x cells counts, ws_list = n_planes x n_slots flat indices in list order (-1: padding),
+// ws_table = the turned pattern of hg_describe_pattern (4-byte aligned).  out_points / out_desc / out_info may be nullptr.
+struct DetectArgs {
+    const uint8_t *planes; int W, H, n_planes; size_t plane_stride; int channels, cell, per_cell, cells_x, cells_y; int64_t min_response; size_t desc_stride;
+    void *ws_rec; int32_t *ws_cnt, *ws_list; const int8_t *ws_table; int32_t *out_counts; void *out_points, *out_desc, *out_info;
+};
+void launch_detect(const DetectArgs &a, hipStream_t stream);
+
 // k_geo: _inverseGeometricWarp pixel loop :997-1011 for all frames.  mats = F x 8 doubles (inverse matrices).
 // f32_exact: every affine matrix entry is a float value and |x| < 2^28 (lets the kernel use an exact-product fma).
 // n_imgs / img_stride: frame f reads the source at img + (f % n_imgs) * img_stride.

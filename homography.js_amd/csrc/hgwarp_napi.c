@@ -1236,6 +1236,57 @@ static napi_value fn_match_descriptors(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* detectAndDescribe(handle, planes, nPlanes, width, height, channels, cell, perCell, minResponse): the keypoints of nPlanes planes
+ * (hg_detect_describe_frames_device).  planes: Uint8Array of nPlanes x width x height x channels; minResponse: an integer number in 1..2^53.
+ * Everything goes up into device memory of the call's own, the entry runs, and { nSlots, counts: Int32Array(nPlanes), points:
+ * Float32Array(nPlanes x nSlots x 2), descriptors: Uint8Array(nPlanes x nSlots x 32) } come down.  Needs no image. */
+static napi_value fn_detect_describe(napi_env env, napi_callback_info info)
+{
+    napi_value a[9];
+    if (!get_args(env, info, 9, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    int n_planes, W, H, channels, cell, per_cell; size_t n_p = 0; double thr;
+    uint8_t *planes = (uint8_t *)get_typed(env, a[1], napi_uint8_array, &n_p, "planes"); if (!planes) return NULL;
+    if (!get_i32(env, a[2], &n_planes) || !get_i32(env, a[3], &W) || !get_i32(env, a[4], &H) || !get_i32(env, a[5], &channels) || !get_i32(env, a[6], &cell) ||
+        !get_i32(env, a[7], &per_cell)) return NULL;
+    if (napi_get_value_double(env, a[8], &thr) != napi_ok || !(thr >= 1.0 && thr <= 9007199254740992.0) || thr != (double)(int64_t)thr)
+        return throw_str(env, "hgwarp: minResponse must be an integer in 1..2^53");
+    int cx = 0, cy = 0, n_slots = 0;
+    if (hg_detect_layout(W, H, cell, per_cell, &cx, &cy, &n_slots) != HG_OK) return throw_str(env, hg_last_error(NULL));
+    if (n_planes < 0 || n_planes > 4096 || (channels != 1 && channels != 4)) return throw_str(env, "hgwarp: detectAndDescribe: nPlanes or channels is out of range");
+    const size_t P = (size_t)n_planes, NS = (size_t)n_slots, plane = (size_t)W * (size_t)H * (size_t)channels;
+    if (n_p != P * plane) return throw_str(env, "hgwarp: planes must hold nPlanes x width x height x channels bytes");
+    void *p_cnt, *p_pts, *p_desc;
+    napi_value out, v_cnt, v_pts, v_desc, v_slots;
+    if (!(v_cnt = make_typed(env, napi_int32_array, P, 4, &p_cnt)) || !(v_pts = make_typed(env, napi_float32_array, P * NS * 2, 4, &p_pts)) ||
+        !(v_desc = make_typed(env, napi_uint8_array, P * NS * 32, 1, &p_desc))) return NULL;
+    NAPI_OK(napi_create_object(env, &out));
+    NAPI_OK(napi_create_int32(env, n_slots, &v_slots));
+    NAPI_OK(napi_set_named_property(env, out, "nSlots", v_slots)); NAPI_OK(napi_set_named_property(env, out, "counts", v_cnt));
+    NAPI_OK(napi_set_named_property(env, out, "points", v_pts)); NAPI_OK(napi_set_named_property(env, out, "descriptors", v_desc));
+    if (!P) return out;
+#define DETECT_PAD(b) (((size_t)(b) + 255) & ~(size_t)255)
+    const size_t o_p = 0, o_cnt = o_p + DETECT_PAD(P * plane), o_pts = o_cnt + DETECT_PAD(P * 4), o_desc = o_pts + DETECT_PAD(P * NS * 8),
+                 total = o_desc + DETECT_PAD(P * NS * 32);
+#undef DETECT_PAD
+    void *d = NULL;
+    HG_CALL(h->ctx, "hg_device_alloc", hg_device_alloc(h->ctx, total, &d));
+    uint8_t *b = (uint8_t *)d;
+    const char *what = "hg_copy_to_device";
+    int rc = hg_copy_to_device(h->ctx, b + o_p, planes, P * plane);
+    if (rc == HG_OK) {
+        what = "hg_detect_describe_frames_device";
+        rc = hg_detect_describe_frames_device(h->ctx, b + o_p, W, H, n_planes, plane, channels, cell, per_cell, (int64_t)thr, 32, (int32_t *)(b + o_cnt), b + o_pts,
+                                              b + o_desc, NULL);
+    }
+    if (rc == HG_OK) { what = "hg_copy_to_host"; rc = hg_copy_to_host(h->ctx, p_cnt, b + o_cnt, P * 4); }
+    if (rc == HG_OK) rc = hg_copy_to_host(h->ctx, p_pts, b + o_pts, P * NS * 8);
+    if (rc == HG_OK) rc = hg_copy_to_host(h->ctx, p_desc, b + o_desc, P * NS * 32);
+    if (rc != HG_OK) { napi_value e = throw_hg(env, h->ctx, what, rc); hg_device_free(h->ctx, d); return e; }
+    HG_CALL(h->ctx, "hg_device_free", hg_device_free(h->ctx, d));
+    return out;
+}
+
 /* redoneFrames(ctx): frames the fused kernels flagged and hg_sync redid through the map so far (hg_redone_frames; tests) */
 static napi_value fn_redone_frames(napi_env env, napi_callback_info info)
 {
@@ -1951,6 +2002,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "pointsForwardGeometric", fn_points_forward_geometric }, { "pointsForwardPiecewise", fn_points_forward_piecewise },
         { "fitMatches", fn_fit_matches },
         { "matchDescriptors", fn_match_descriptors },
+        { "detectAndDescribe", fn_detect_describe },
         { "solveAffineTriangles", fn_solve_affine_triangles }, { "warpInversePiecewiseState", fn_warp_inverse_piecewise_state },
         { "warpForwardPiecewiseState", fn_warp_forward_piecewise_state },
         { "release", fn_release }, { "setPinnedLimit", fn_set_pinned_limit }, { "poolStats", fn_pool_stats }, { "redoneFrames", fn_redone_frames }, { "spanCacheStats", fn_span_cache_stats }, { "setSampling", fn_set_sampling }, { "multiSetSampling", fn_multi_set_sampling }, { "_poolTestFrames", fn_pool_test_frames }, { "poolPressure", fn_pool_pressure }, { "poolCollected", fn_pool_collected },

@@ -30,6 +30,8 @@ MOSAIC_LAST, MOSAIC_MEAN, MOSAIC_FEATHER = 0, 1, 2
 CUBIC_CATMULL_ROM, CUBIC_MITCHELL, CUBIC_BSPLINE = (0.0, 0.5), (1 / 3, 1 / 3), (1.0, 0.0)
 # descriptor kinds of the matcher (hg_match_descriptors_frames_device): binary rows under the Hamming distance, byte vectors under squared L2
 DESC_BITS, DESC_U8 = 0, 1
+# the keypoint detector (hg_detect_describe_frames_device): the distance a keypoint keeps from the borders, the bytes of a descriptor, the direction bins
+DETECT_MARGIN, DETECT_DESC_BYTES, DETECT_BINS = 16, 32, 32
 
 # every symbol include/hgwarp.h declares (tests check that the built library exports all of them)
 EXPORTS = [
@@ -65,6 +67,7 @@ EXPORTS = [
     "hg_remap_bicubic_frames_device",
     "hg_fit_sample_indices", "hg_fit_matches_frames_device",
     "hg_match_descriptors_frames_device",
+    "hg_detect_layout", "hg_describe_pattern", "hg_detect_describe_frames_device",
 ]
 
 
@@ -181,6 +184,9 @@ def lib():
         "hg_fit_matches_frames_device": (i, [vp, i, vp, i, C.POINTER(C.c_int32), i, d, i, C.c_uint32, vp, i, vp, vp, vp, vp, vp]),
         "hg_match_descriptors_frames_device": (i, [vp, i, i, sz, vp, i, C.POINTER(C.c_int32), i, vp, i, C.POINTER(C.c_int32), i, d, C.c_uint32, i,
                                                    vp, vp, vp, vp, vp, vp]),
+        "hg_detect_layout": (i, [i, i, i, i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "hg_describe_pattern": (i, [C.POINTER(C.c_int8)]),
+        "hg_detect_describe_frames_device": (i, [vp, vp, i, i, i, sz, i, i, i, C.c_int64, sz, vp, vp, vp, vp]),
         "hg_points_to_source_geometric_frames_device": (i, [vp, vp, i, i, vp]),
         "hg_points_to_source_piecewise_frames_device": (i, [vp, vp, i, i, vp]),
         "hg_points_to_output_geometric_batch_device": (i, [vp, i, f64p, C.POINTER(Geom), i, vp, i, i, vp]),
@@ -383,6 +389,21 @@ def fit_sample_indices(kind, seed, counts, n_points, n_hyp):
     out = np.empty((F, max(int(n_hyp), 0), 4), np.int32)
     _check(lib().hg_fit_sample_indices(int(kind), int(seed) & 0xffffffff, F, p, int(n_points), int(n_hyp),
                                        out.ctypes.data_as(C.POINTER(C.c_int32)) if out.size else None))
+    return out
+
+
+def detect_layout(W, H, cell, per_cell):
+    """(cells_x, cells_y, n_slots) of a W x H plane under cell x cell cells that keep per_cell keypoints each (hg_detect_layout): n_slots is the
+    capacity of a plane's keypoint list."""
+    cx, cy, ns = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(lib().hg_detect_layout(int(W), int(H), int(cell), int(per_cell), C.byref(cx), C.byref(cy), C.byref(ns)))
+    return cx.value, cy.value, ns.value
+
+
+def describe_pattern():
+    """The sampling pattern of the descriptor (hg_describe_pattern): an int8 array of shape (32, 256, 4), {ax, ay, bx, by} of test b under bin k."""
+    out = np.empty((DETECT_BINS, 256, 4), np.int8)
+    _check(lib().hg_describe_pattern(out.ctypes.data_as(C.POINTER(C.c_int8))))
     return out
 
 
@@ -863,6 +884,18 @@ class Context:
                                                          vp(d_train), int(n_train), pt, int(n_train_sets), float(ratio), int(max_distance) & 0xffffffff,
                                                          1 if cross_check else 0, vp(d_query_pts), vp(d_train_pts), vp(d_counts), vp(d_matches),
                                                          vp(d_pairs), vp(d_nn)))
+
+    def detect_describe_frames_device(self, d_planes, w, h, n_planes, channels, d_counts, cell=32, per_cell=2, min_response=10 ** 10, desc_stride=32,
+                                      plane_stride_bytes=None, d_points=0, d_desc=0, d_info=0):
+        """hg_detect_describe_frames_device: the keypoints of n_planes u8 planes of w x h x channels (1 or 4) on the device -- Harris corners in
+        integers, the best per_cell of every cell x cell cell, an orientation bin and a 256-bit descriptor each.  d_counts gets the keypoints
+        per plane; d_points the (x, y) float32 positions, d_desc rows of desc_stride bytes (the first 32 the descriptor), d_info {int64 R, int32
+        bin, int32 flat index}, each n_planes x detect_layout(...)[2] slots: what match_descriptors_frames_device takes as a query or train side.
+        Asynchronous; every output is device memory, 0 = not wanted."""
+        vp = lambda v: C.c_void_p(int(v) or None)
+        stride = int(w) * int(h) * int(channels) if plane_stride_bytes is None else int(plane_stride_bytes)
+        self._c(lib().hg_detect_describe_frames_device(self._h, vp(d_planes), int(w), int(h), int(n_planes), stride, int(channels), int(cell), int(per_cell),
+                                                       int(min_response), int(desc_stride), vp(d_counts), vp(d_points), vp(d_desc), vp(d_info)))
 
     def mosaic_overlap_stats_device(self, geoms, d_coords, d_frames, channels, canvas, d_stats, field_offsets=None, frame_offsets=None):
         """The overlaps of a set of uint8 frames measured on the device (asynchronous): d_stats gets F * F * 2 uint64 words -- for every ordered

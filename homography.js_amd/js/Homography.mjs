@@ -529,6 +529,48 @@ class Homography {
     }
 
     /**
+     * The descriptors matchDescriptors() starts from: the keypoints of a set of pictures -- Harris corners in integer arithmetic, the best
+     * perCell of every cell x cell cell of the picture, an orientation and a 256-bit binary descriptor each (not part of the reference;
+     * hg_detect_describe_frames_device in include/hgwarp.h has the rules, all of them exact).  It is not ORB: both sides of a match have to
+     * come from this call.  It is single-scale.  images: an array of Uint8Arrays of equal size, width x height x channels bytes each.
+     * options: { width, height (required), channels = 4 (RGBA; 1: grey), cell = 32 (8..256), perCell = 2 (1..16), minResponse = 1e10 (an
+     *            integer in 1..2^53: the smallest corner response kept.  The default is a guess: on the numpy model thresholds from 1 to 1e13
+     *            changed the keypoint count of a textured 192 x 160 scene by under 20 %; nobody has measured it on photographs) }.
+     * Returns one record per picture: { count, points: Float32Array(2 count) of x, y, descriptors: Uint8Array(32 count) } -- what
+     * matchDescriptors() takes as a query or train set (kind 'bits', descBytes 32) and as queryPoints / trainPoints.
+     * Needs no image and changes no state of the instance.  Throws a bare string for pictures of the wrong size and options out of range.
+     */
+    detectAndDescribe(images, options = {}) {
+        if (options === null || options === undefined) options = {};
+        const { width, height } = options;
+        if (!Number.isInteger(width) || !Number.isInteger(height) || width < 1 || height < 1 || width > 32768 || height > 32768) throw ("detectAndDescribe: options.width and options.height must be integers in 1..32768");
+        const channels = options.channels === undefined ? 4 : options.channels;
+        if (channels !== 1 && channels !== 4) throw ("detectAndDescribe: options.channels must be 1 or 4");
+        const cell = options.cell === undefined ? 32 : options.cell;
+        if (!Number.isInteger(cell) || cell < 8 || cell > 256) throw ("detectAndDescribe: options.cell must be an integer in 8..256");
+        const perCell = options.perCell === undefined ? 2 : options.perCell;
+        if (!Number.isInteger(perCell) || perCell < 1 || perCell > 16) throw ("detectAndDescribe: options.perCell must be an integer in 1..16");
+        const minResponse = options.minResponse === undefined ? 1e10 : options.minResponse;
+        if (!Number.isInteger(minResponse) || minResponse < 1 || minResponse > 2 ** 53) throw ("detectAndDescribe: options.minResponse must be an integer in 1..2^53");
+        if (Math.ceil(width / cell) * Math.ceil(height / cell) * perCell > 65536) throw ("detectAndDescribe: at most 65536 keypoint slots per picture (cells x perCell)");
+        if (!Array.isArray(images)) throw ("detectAndDescribe: images must be an array of Uint8Arrays");
+        if (images.length > 4096) throw ("detectAndDescribe: at most 4096 pictures");
+        const plane = width * height * channels;
+        const planes = new Uint8Array(images.length * plane);
+        images.forEach((im, f) => {
+            if (!(im instanceof Uint8Array) && !(im instanceof Uint8ClampedArray)) throw ("detectAndDescribe: picture " + f + " must be a Uint8Array");
+            if (im.length !== plane) throw ("detectAndDescribe: picture " + f + " must hold width x height x channels bytes");
+            planes.set(im, f * plane);
+        });
+        const r = this._native.detectAndDescribe(this._ctx, planes, images.length, width, height, channels, cell, perCell, minResponse);
+        return images.map((im, f) => {
+            const count = r.counts[f];
+            return { count, points: r.points.slice(f * r.nSlots * 2, (f * r.nSlots + count) * 2),
+                     descriptors: r.descriptors.slice(f * r.nSlots * 32, (f * r.nSlots + count) * 32) };
+        });
+    }
+
+    /**
      * What sourceField() and remap() share: which field entry point of the addon the current state and options.loop lead to, with its
      * arguments after the context -- { entry, args, width, height }; the addon's functions are 'field' + entry and 'remap' + entry -- after
      * the refusals, the solves and the uploads that field needs.  null: the window is empty.  fmt: 0 = index, 1 = coords.

@@ -39,7 +39,8 @@ extern "C" {
                                    the anisotropic remap by that of hg_remap_aniso_frames_device, mosaics by the presence of hg_mosaic_frames_device,
                                    the bicubic remap by that of hg_remap_bicubic_frames_device, exposure gains of a mosaic by that of
                                    hg_mosaic_overlap_stats_device, fitting transforms to matches by that of hg_fit_matches_frames_device);
-                                   matching descriptors by the presence of hg_match_descriptors_frames_device */
+                                   matching descriptors by the presence of hg_match_descriptors_frames_device, keypoints by the presence of
+                                   hg_detect_describe_frames_device */
 
 enum {
     HG_OK = 0,
@@ -801,6 +802,71 @@ int hg_match_descriptors_frames_device(hg_ctx *ctx, int desc_kind, int desc_byte
                                        double ratio, uint32_t max_distance, int cross_check,
                                        const void *d_query_pts, const void *d_train_pts,
                                        int32_t *d_counts, void *d_matches, int32_t *d_pairs, int32_t *d_nn);
+
+/* ------------------------------------------------------------------------------------------------ detecting and describing keypoints
+ * The first stage of the chain descriptors -> matches -> transforms -> warps -> mosaic: corner detection, an orientation and a 256-bit binary
+ * descriptor per keypoint, for a whole set of planes in one call, written in exactly the layout hg_match_descriptors_frames_device reads
+ * (d_desc as d_query / d_train with HG_DESC_BITS and desc_bytes 32, d_points as d_query_pts / d_train_pts, the downloaded d_counts as counts_q
+ * / counts_t, n_slots as n_query / n_train).  Not part of the reference.  Every rule is integer arithmetic: the result is exact, it has no
+ * tolerance, ties included, and two runs give the same bytes.  It is NOT ORB-compatible: the sampling pattern is this library's own, generated
+ * by a rule; both sides of a match come from this call, so it only has to agree with itself.  It is single-scale: for octaves run it on the
+ * levels of hg_pyramid_build_device and scale the positions.
+ * PLANES.  n_planes planes of u8, W x H, rows tight, `channels` 1 or 4 (interleaved); plane p lies at d_planes + p * plane_stride_bytes.
+ * LUMA L.  1 channel: the byte.  4 channels: L = (77 R + 150 G + 29 B + 128) >> 8; alpha is ignored.  Everything below is integers on L.
+ * RESPONSE R(x, y), for 4 <= x < W - 4 and 4 <= y < H - 4.  Sobel, y growing downwards: Ix = (L[y-1][x+1] + 2 L[y][x+1] + L[y+1][x+1]) - (the
+ * same three at x - 1), Iy = (L[y+1][x-1] + 2 L[y+1][x] + L[y+1][x+1]) - (the same three at y - 1).  A, C, B = the sums of Ix Ix, Iy Iy, Ix Iy
+ * over the 7 x 7 window centred on (x, y) (each at most 49 * 1020^2: int32).  R = 16 (A C - B B) - (A + C)^2 in int64: Harris with k = 1/16,
+ * |R| < 2^56.
+ * CANDIDATES.  A pixel with 16 <= x < W - 16 and 16 <= y < H - 16 is a candidate iff R >= min_response and it beats each of its 8 neighbours
+ * under the total order "larger R, among equal R the lower flat index y W + x".  A plane with W < 33 or H < 33 has none.  No read leaves the
+ * plane: the deepest reach is the orientation disc, radius 15 (the turned tests reach 13, the 5 x 5 boxes on them 15).
+ * SELECTION.  The plane is tiled from (0, 0) by cell x cell cells, cells_x = ceil(W / cell), cells_y alike; a pixel belongs to cell
+ * (y / cell) cells_x + x / cell.  Each cell keeps its best per_cell candidates under the same order.  The keypoints of a plane are listed by
+ * ascending cell number, within a cell by rank.  n_slots = cells_x cells_y per_cell is the capacity of a plane's list (hg_detect_layout).
+ * The bucketing is deliberate: a global top-K clusters on one textured object, a panorama needs matches spread over the overlap.
+ * ORIENTATION.  Over the disc dx^2 + dy^2 <= 225: m10 = sum dx L, m01 = sum dy L (int32).  Direction table, 32 bins, Q14: c_0..c_8 = 16384,
+ * 16069, 15137, 13623, 11585, 9102, 6270, 3196, 0; c_{16-k} = -c_k; c_{32-k} = c_k; s_k = c_{(k + 24) mod 32}.  The bin is the k that maximises
+ * m10 c_k + m01 s_k in int64, the lowest k among equals (a flat patch: 0).
+ * PATTERN.  mix(a): a ^= a >> 16; a *= 0x7feb352d; a ^= a >> 15; a *= 0x846ca68b; a ^= a >> 16 in uint32 (the fit's).  Test b = 0..255:
+ * key = mix(mix(0x9e3779b9) + b); the words w_t = mix(key + t), t = 0, 1, ..., each propose a point x = (w & 7) + ((w >> 3) & 7) + ((w >> 6) & 7)
+ * + ((w >> 9) & 7) - 14, y the same from bits 12, 15, 18, 21; a point with x^2 + y^2 > 144 is skipped; the first kept point is a, the next kept
+ * point that differs from a is b.  (Tests 0, 1, 2 are {-1,1,0,0}, {-3,2,10,-3}, {-3,-6,1,4}; test 139 repeats test 79, which is accepted.)
+ * Bin k turns every point with arithmetic shifts: x' = (x c_k - y s_k + 8192) >> 14, y' = (x s_k + y c_k + 8192) >> 14; bin 0 is the base
+ * pattern; every turned coordinate lies in -12..12.  hg_describe_pattern returns the table.
+ * DESCRIPTOR.  S(x, y) = the sum of L over the 5 x 5 box centred on (x, y).  Bit b, stored in byte b >> 3 at bit b & 7, is 1 iff
+ * S(p + a'_b) < S(p + b'_b) with the turned table of the keypoint's bin.
+ * OUTPUTS, all in device memory; d_counts is required, the others may be NULL and are then never written.
+ *   d_counts[p]  int32, 4-byte aligned: the number of keypoints of plane p.
+ *   d_points     n_planes x n_slots x 2 float32, 8-byte aligned: (x, y) as floats of the integer pixel position, compacted to the front in
+ *                list order; 0x7fc00000 in both words at and beyond the count.  The layout of d_query_pts.
+ *   d_desc       n_planes x n_slots rows of desc_stride bytes (a multiple of 16, >= 32), 16-byte aligned: the first 32 bytes of a row are the
+ *                descriptor, 32 zero bytes at and beyond the count; bytes 32..desc_stride of every row are never written.
+ *   d_info       n_planes x n_slots x {int64 R, int32 bin, int32 flat index}, 8-byte aligned; {0, -1, -1} at and beyond the count.
+ * LIMITS (HG_ERR_INVALID), checked in this order (the shape first: those checks need no device; each names itself in hg_last_error): W or H
+ * outside 1..32768 or W H > 2^30; channels not 1 or 4; cell outside 8..256; per_cell outside 1..16; n_slots > 65536 (the matcher's row limit);
+ * n_planes outside 0..4096; min_response < 1; desc_stride not a multiple of 16 or below 32; plane_stride_bytes < W H channels; NULL ctx; then,
+ * with n_planes > 0: d_planes or d_counts NULL, a misaligned pointer.  n_planes == 0 is HG_OK and nothing is written.  hg_detect_layout makes
+ * the shape checks that concern it (W, H, cell, per_cell, n_slots) and refuses NULL outputs; hg_describe_pattern refuses NULL.
+ * CONTEXT.  As the matcher: no image, mesh or frame set is needed; queued runs are settled first, then the call is asynchronous on the ctx
+ * stream.  It touches no hg_last_*, no sampling mode, no plan, no policy state and no staged frame set.  Its scratch (one 16-byte record per
+ * slot, one count per cell, one index per slot, and the turned table, uploaded once per context) lives in buffers the context owns, grown
+ * on demand and reused.  No floating-point operations and no atomics at all.
+ * COST.  Three kernels: the response and the per-cell selection (one workgroup per cell; the halo of 5 makes small cells redundant: about
+ * 5x the pixels at cell 8, 1.7x at cell 32), the compaction (one workgroup per plane) and the description (one wavefront per slot).
+ * The call is bound by the integer work of the response, not by memory.  MEASURED (MI355X, whole call with all four outputs, medians of 31;
+ * EXPERIMENTS.md, "Detecting"; cell 32, per_cell 2, planes of a many-cornered scene): 64 planes of 1920 x 1080 x 4 take 2.36 ms (35 x the
+ * 0.066 ms of reading them once at 8 TB/s; 63 % response and selection, 1 % compaction, 36 % description), 8 planes of 3840 x 2160 x 4
+ * 1.20 ms, ONE such plane 0.24 ms (the compaction, one workgroup per plane, is a quarter of that); the 1-channel forms 2.20 / 1.17 / 0.23 ms.
+ * Against cell 32, at per_cell 1, the 64-plane call costs 5.9 x at cell 8, 2.5 x at cell 16, 0.9 x at cell 64 and 128 (fewer keypoints to
+ * describe; the first two kernels alone: 6.1 x, 2.3 x, 1.1 x, 1.2 x) and 1.2 x at cell 256 (1.6 x). */
+enum { HG_DETECT_MARGIN = 16, HG_DETECT_DESC_BYTES = 32, HG_DETECT_BINS = 32 };
+/* host only: the cell grid and the capacity of a plane's list */
+int hg_detect_layout(int W, int H, int cell, int per_cell, int *cells_x, int *cells_y, int *n_slots);
+/* host only: HG_DETECT_BINS x 256 x 4 int8 = {ax, ay, bx, by} of test b under bin k */
+int hg_describe_pattern(int8_t *out);
+int hg_detect_describe_frames_device(hg_ctx *ctx, const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int channels,
+                                     int cell, int per_cell, int64_t min_response, size_t desc_stride,
+                                     int32_t *d_counts, void *d_points, void *d_desc, void *d_info);
 
 /* ------------------------------------------------------------------------------------------------ forward (scatter) paths
  * What warp() dispatches to when the output is not larger than the input (:421, :426).  `m` is the FORWARD matrix
