@@ -207,7 +207,8 @@ struct hg_ctx {
     DevBuf<RemapFrame> d_remap_frames;                         // the frame table of a frames remap (hg_remap_*_frames_device), staged through field_stage
     DevBuf<uint64_t> d_tri_table;                              // hg_remap_trilinear_frames_device: 32 level offsets, then the TriRemapFrame records; staged through field_stage
     DevBuf<MosaicFrame4> d_mosaic_frames;                      // the frame table of the hg_mosaic_* calls (quads of records) and, behind it, a gained mosaic's gains; staged through field_stage
-    int opt_remap_pack = -1;                                   // k_remap_index_frames: 0 = one pixel per lane even for the pixel sizes that carry the packed form (measurements)
+    DevBuf<uint64_t> d_mb_table;                               // hg_mosaic_multiband_device: the mosaic's quads, then the MbFrame records of the frames that take part; staged through field_stage
+    int opt_remap_pack = -1;                                  // k_remap_index_frames: 0 = one pixel per lane even for the pixel sizes that carry the packed form (measurements)
 
     // fitting transforms to matches (hg_api_fit.hip): the hypotheses' matrices and flags, the per-frame counts and best words; grown on demand
     DevBuf<double> d_fit_mats;

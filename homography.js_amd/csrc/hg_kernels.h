@@ -244,6 +244,16 @@ void launch_mosaic_frames(const MosaicFrame4 *frames, int n_quads, const uint8_t
 void launch_mosaic_stats(const MosaicFrame4 *frames, int n_frames, const uint8_t *coords, const uint8_t *pixels, int channels, int cx, int cy, int cw,
                          int ch, uint64_t *stats, hipStream_t stream);
 
+// The multi-band mosaic (hg_k_multiband.hip; the rules: hg_multiband_dev.h; include/hgwarp.h hg_mosaic_multiband_device): k_mb_label over the
+// quad table of the mosaic, k_mb_seed, one k_mb_reduce<element, channels, FIRST> per level 1..L-1 and one k_mb_blend<element, channels, LAST>
+// per level L-1..0 over the table of the n_frames frames that take part.  blocks[0]: the seed's grid, blocks[k]: that of the reduce that
+// writes level k (a launch without blocks is skipped); labels = the caller's plane or the one in the work area; weight may be nullptr.
+struct MbArgs {
+    const MosaicFrame4 *quads; int n_quads; const MbFrame *frames; int n_frames; MbCanvas cv; uint32_t blocks[kMbMaxBands];
+    const uint8_t *coords, *pixels; int W, H, elem, channels; float feather; uint8_t *work; int32_t *labels; uint8_t *canvas; float *weight;
+};
+void launch_multiband(const MbArgs &a, hipStream_t stream);
+
 // Point lists (hg_k_points.hip; include/hgwarp.h hg_points_*): n_sets lists of n_points interleaved (x, y) floats, frame f reads list
 // f % n_sets and writes n_points (x, y) pairs at f * n_points of `out`; an unmapped point is the quiet NaN of HG_FIELD_COORDS in both words.
 // k_geo_points<kind, dir>: dir 0 = to source (mats: the inverse matrices, W x H the source's size: coverage test :1001), dir 1 = to output

@@ -28,4 +28,25 @@ struct MosaicFrame { uint64_t fld_off, pix_off; int32_t x_off, y_off, obj_w, obj
 struct MosaicFrame4 { MosaicFrame f[4]; };
 static_assert(sizeof(MosaicFrame4) == 128, "the table is staged in 8-byte words");
 
+// The multi-band mosaic (hg_k_multiband.hip; include/hgwarp.h hg_mosaic_multiband_device).
+constexpr int kMbMaxBands = 8;
+constexpr int kMbSeedPx = 1024;                               // grid pixels per block of k_mb_seed: 4 per lane
+constexpr int kMbTileW = 32, kMbTileH = 8;                    // the output tile of k_mb_reduce; its input tile with the halo:
+constexpr int kMbInW = 2 * kMbTileW + 3, kMbInH = 2 * kMbTileH + 3;
+// A frame that TAKES PART (its window meets the canvas): the mosaic's record, its level-0 grid in canvas-relative coordinates -- aligned to
+// A = 2^(L-1) with a margin of A, so level k's grid is this one shifted right by k --, where its flag bytes and its levels 1..L-1 of I (C
+// floats per pixel) and M lie in the work area, its gain, its index in the caller's list (what a label names), and its first block in the
+// seed launch (blk0[0]) and in the reduce launch that writes level k (blk0[k]).
+struct MbFrame {
+    MosaicFrame m;
+    int32_t gx, gy, gw, gh;
+    uint64_t flag_off;
+    float gain; int32_t index;
+    uint64_t img_off[kMbMaxBands], msk_off[kMbMaxBands];      // (entry 0 unused: level 0 is the frame's own pixels and the flag bytes)
+    uint32_t blk0[kMbMaxBands];
+};
+static_assert(sizeof(MbFrame) == 224, "the table is staged in 8-byte words");
+// The canvas window, the size of level 0 of its grid (origin (-A, -A)), the band count, A, and where levels 1..L-1 of R lie in the work area.
+struct MbCanvas { int32_t cx, cy, cw, ch, pw, ph, L, A; uint64_t r_off[kMbMaxBands]; };
+
 } // namespace hg

@@ -1620,12 +1620,19 @@ static napi_value fn_warp_inverse_geometric_batch(napi_env env, napi_callback_in
  * [, weight: Float32Array] }.
  * One more argument, `exposure`, equalises the frames' exposures first (hg_mosaic_frames_gain_device): a Float32Array of one gain per frame
  * is applied as given; a Float64Array [sigmaN, sigmaG] has the gains fitted on the overlaps -- hg_mosaic_overlap_stats_device, 16 F^2 bytes
- * down, hg_mosaic_solve_gains on the host -- and the frames still never leave the device.  The result then carries gains: Float32Array. */
-static napi_value run_mosaic(napi_env env, handle_t *h, const batch_job *job, const int32_t *gv, int F, const napi_value *a, napi_value exposure, const char *what)
+ * down, hg_mosaic_solve_gains on the host -- and the frames still never leave the device.  The result then carries gains: Float32Array.
+ * mosaicMultibandInverseGeometric(ctx, kind, from, to, geoms, bands, feather, canvas, wantWeight, W, H, wantLabels [, exposure]) /
+ * mosaicMultibandInversePiecewise(ctx, dstPoints, geoms, bands, feather, canvas, wantWeight, W, H, wantLabels [, exposure]): the same with
+ * hg_mosaic_multiband_device as the blend (`bands` in the place of the mode, feather ranks the frames).  The work area is allocated for the
+ * call and freed behind it; with wantLabels the result carries labels: Int32Array, the owner of every canvas pixel or -1. */
+static napi_value run_mosaic(napi_env env, handle_t *h, const batch_job *job, const int32_t *gv, int F, const napi_value *a, napi_value exposure, const char *what,
+                             napi_value multiband_labels)
 {
     const hg_geom *g = (const hg_geom *)gv;
-    int mode, W, H; double feather; size_t nc; bool want_weight = false;
+    int mode, W, H; double feather; size_t nc; bool want_weight = false, want_labels = false;
+    const int multiband = multiband_labels != NULL;         /* then a[0] is the band count */
     if (!get_i32(env, a[0], &mode)) return NULL;
+    if (multiband && napi_get_value_bool(env, multiband_labels, &want_labels) != napi_ok) return throw_str(env, "hgwarp: wantLabels must be a boolean");
     if (napi_get_value_double(env, a[1], &feather) != napi_ok) return throw_str(env, "hgwarp: feather must be a number");
     const int32_t *cv = (const int32_t *)get_typed(env, a[2], napi_int32_array, &nc, "canvas"); if (!cv) return NULL;
     if (nc != 4) return throw_str(env, "hgwarp: canvas must hold x, y, width, height");
@@ -1644,14 +1651,16 @@ static napi_value run_mosaic(napi_env env, handle_t *h, const batch_job *job, co
         if (tt == napi_float64_array) { fit = 1; sigma_n = ((const double *)ed)[0]; sigma_g = ((const double *)ed)[1]; for (int f = 0; f < F; f++) ((float *)gdata)[f] = 1.0f; }
         else memcpy(gdata, ed, sizeof(float) * (size_t)F);
     }
-    void *data = NULL, *wdata = NULL;
-    napi_value result, pixels = make_typed(env, napi_uint8_clamped_array, n * 4, 1, &data), weights = NULL;
+    void *data = NULL, *wdata = NULL, *ldata = NULL;
+    napi_value result, pixels = make_typed(env, napi_uint8_clamped_array, n * 4, 1, &data), weights = NULL, labels = NULL;
     if (!pixels) return NULL;
     if (want_weight && !(weights = make_typed(env, napi_float32_array, n, 4, &wdata))) return NULL;
+    if (want_labels && !(labels = make_typed(env, napi_int32_array, n, 4, &ldata))) return NULL;
     NAPI_OK(napi_create_object(env, &result));
     NAPI_OK(napi_set_named_property(env, result, "data", pixels));
     if (want_weight) NAPI_OK(napi_set_named_property(env, result, "weight", weights));
     if (exposure) NAPI_OK(napi_set_named_property(env, result, "gains", gains_out));
+    if (want_labels) NAPI_OK(napi_set_named_property(env, result, "labels", labels));
     if (!n) return result;
     if (fit && F > 256) {                                   /* before anything is staged or warped: the library's own refusal, no pointer involved */
         int rc0 = hg_mosaic_overlap_stats_device(h->ctx, g, F, NULL, NULL, NULL, NULL, 4, canvas, NULL);
@@ -1692,19 +1701,31 @@ static napi_value run_mosaic(napi_env env, handle_t *h, const batch_job *job, co
         if (rc == HG_OK) rc = host_rc = hg_mosaic_solve_gains(stats, F, 4, sigma_n, sigma_g, (float *)gdata);
         free(stats);
     }
-    if (rc == HG_OK) rc = hg_mosaic_frames_gain_device(h->ctx, g, F, d_field, foffs, h->d_batch, offs, HG_ELEM_U8, 4, W, H, mode, (float)feather, canvas, d_canvas, d_weight,
-                                                       exposure ? (const float *)gdata : NULL);
+    void *d_mb = NULL;                                      /* a multi-band blend: the labels, then the work area; this call's own */
+    if (rc == HG_OK && multiband) {
+        size_t work = 0;
+        const size_t lb = want_labels ? ((n * 4 + 255) & ~(size_t)255) : 0;
+        rc = host_rc = hg_mosaic_multiband_layout(g, F, canvas, 4, mode, &work);
+        if (rc == HG_OK) { host_rc = HG_OK; rc = hg_device_alloc(h->ctx, lb + work + 256, &d_mb); }
+        if (rc == HG_OK) rc = hg_mosaic_multiband_device(h->ctx, g, F, d_field, foffs, h->d_batch, offs, HG_ELEM_U8, 4, W, H, (float)feather, mode, canvas, d_canvas,
+                                                         d_weight, want_labels ? (int32_t *)d_mb : NULL, exposure ? (const float *)gdata : NULL,
+                                                         (uint8_t *)d_mb + lb, work);
+        if (rc == HG_OK && want_labels) rc = hg_copy_to_host(h->ctx, ldata, d_mb, n * 4);
+    } else if (rc == HG_OK)
+        rc = hg_mosaic_frames_gain_device(h->ctx, g, F, d_field, foffs, h->d_batch, offs, HG_ELEM_U8, 4, W, H, mode, (float)feather, canvas, d_canvas, d_weight,
+                                          exposure ? (const float *)gdata : NULL);
     if (rc == HG_OK) rc = hg_copy_to_host(h->ctx, data, d_canvas, n * 4);
     if (rc == HG_OK && want_weight) rc = hg_copy_to_host(h->ctx, wdata, d_weight, n * 4);
+    if (d_mb) { if (rc != HG_OK) hg_sync(h->ctx); hg_device_free(h->ctx, d_mb); }
     free(offs);
     if (rc != HG_OK) return throw_hg(env, host_rc != HG_OK ? NULL : h->ctx, what, rc);
     return result;
 }
 
-static napi_value fn_mosaic_inverse_geometric(napi_env env, napi_callback_info info)
+static napi_value mosaic_inverse_geometric(napi_env env, napi_callback_info info, int multiband)
 {
-    napi_value a[12]; int have_exposure = 0;
-    if (!get_args_opt(env, info, 11, a, &have_exposure)) return NULL;
+    napi_value a[13]; int have_exposure = 0;
+    if (!get_args_opt(env, info, 11 + (size_t)multiband, a, &have_exposure)) return NULL;
     handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
     size_t nf, nt, ng; batch_job job = { JOB_GEO_INV, 0, NULL, NULL, NULL, NULL, 0, 0, 0 };
     if (!get_i32(env, a[1], &job.kind)) return NULL;
@@ -1716,13 +1737,16 @@ static napi_value fn_mosaic_inverse_geometric(napi_env env, napi_callback_info i
     job.per = job.kind == HG_AFFINE ? 6 : 8;
     if (F <= 0) return throw_str(env, "hgwarp: geoms must hold 4 integers per frame");
     if (nf < (size_t)F * job.per || nt < (size_t)F * job.per) return throw_str(env, "hgwarp: point sets must hold frames x points x,y pairs");
-    return run_mosaic(env, h, &job, gv, F, a + 5, have_exposure ? a[11] : NULL, "mosaicInverseGeometric");
+    return run_mosaic(env, h, &job, gv, F, a + 5, have_exposure ? a[11 + multiband] : NULL, multiband ? "mosaicMultibandInverseGeometric" : "mosaicInverseGeometric",
+                      multiband ? a[11] : NULL);
 }
+static napi_value fn_mosaic_inverse_geometric(napi_env env, napi_callback_info info) { return mosaic_inverse_geometric(env, info, 0); }
+static napi_value fn_mosaic_multiband_inverse_geometric(napi_env env, napi_callback_info info) { return mosaic_inverse_geometric(env, info, 1); }
 
-static napi_value fn_mosaic_inverse_piecewise(napi_env env, napi_callback_info info)
+static napi_value mosaic_inverse_piecewise(napi_env env, napi_callback_info info, int multiband)
 {
-    napi_value a[10]; int have_exposure = 0;
-    if (!get_args_opt(env, info, 9, a, &have_exposure)) return NULL;
+    napi_value a[11]; int have_exposure = 0;
+    if (!get_args_opt(env, info, 9 + (size_t)multiband, a, &have_exposure)) return NULL;
     handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
     size_t nd, ng; batch_job job = { JOB_PW_INV, 0, NULL, NULL, NULL, NULL, 0, 0, 0 };
     job.dst = (const float *)get_typed(env, a[1], napi_float32_array, &nd, "dstPoints"); if (!job.dst) return NULL;
@@ -1730,8 +1754,11 @@ static napi_value fn_mosaic_inverse_piecewise(napi_env env, napi_callback_info i
     const int F = (int)(ng / 4);
     if (F <= 0) return throw_str(env, "hgwarp: geoms must hold 4 integers per frame");
     if (h->n_pts == 0 || nd < (size_t)F * 2 * h->n_pts) return throw_str(env, "hgwarp: dstPoints must hold frames x mesh points x,y pairs (piecewiseSetMesh first)");
-    return run_mosaic(env, h, &job, gv, F, a + 3, have_exposure ? a[9] : NULL, "mosaicInversePiecewise");
+    return run_mosaic(env, h, &job, gv, F, a + 3, have_exposure ? a[9 + multiband] : NULL, multiband ? "mosaicMultibandInversePiecewise" : "mosaicInversePiecewise",
+                      multiband ? a[9] : NULL);
 }
+static napi_value fn_mosaic_inverse_piecewise(napi_env env, napi_callback_info info) { return mosaic_inverse_piecewise(env, info, 0); }
+static napi_value fn_mosaic_multiband_inverse_piecewise(napi_env env, napi_callback_info info) { return mosaic_inverse_piecewise(env, info, 1); }
 
 /* warpForwardPiecewiseBatch(ctx, dstPoints, maxSrcX, maxSrcY, geoms [, ownFrames, images, width, height]): the frames warp() sends down the
  * FORWARD piecewise path (:421-422: output not larger than the input and at least input / 1.2) */
@@ -1998,6 +2025,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "remapAnisoInverseGeometric", fn_remap_aniso_inverse_geometric }, { "remapAnisoInversePiecewise", fn_remap_aniso_inverse_piecewise },
         { "remapBicubicInverseGeometric", fn_remap_bicubic_inverse_geometric }, { "remapBicubicInversePiecewise", fn_remap_bicubic_inverse_piecewise },
         { "mosaicInverseGeometric", fn_mosaic_inverse_geometric }, { "mosaicInversePiecewise", fn_mosaic_inverse_piecewise },
+        { "mosaicMultibandInverseGeometric", fn_mosaic_multiband_inverse_geometric }, { "mosaicMultibandInversePiecewise", fn_mosaic_multiband_inverse_piecewise },
         { "pointsInverseGeometric", fn_points_inverse_geometric }, { "pointsInversePiecewise", fn_points_inverse_piecewise },
         { "pointsForwardGeometric", fn_points_forward_geometric }, { "pointsForwardPiecewise", fn_points_forward_piecewise },
         { "fitMatches", fn_fit_matches },

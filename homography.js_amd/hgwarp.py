@@ -68,6 +68,7 @@ EXPORTS = [
     "hg_fit_sample_indices", "hg_fit_matches_frames_device",
     "hg_match_descriptors_frames_device",
     "hg_detect_layout", "hg_describe_pattern", "hg_detect_describe_frames_device",
+    "hg_mosaic_multiband_layout", "hg_mosaic_multiband_device",
 ]
 
 
@@ -180,6 +181,9 @@ def lib():
         "hg_mosaic_frames_gain_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, C.POINTER(sz), i, i, i, i, i, C.c_float, Geom, vp, vp, C.POINTER(C.c_float)]),
         "hg_mosaic_overlap_stats_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, C.POINTER(sz), i, Geom, vp]),
         "hg_mosaic_solve_gains": (i, [C.POINTER(C.c_uint64), i, i, C.c_double, C.c_double, C.POINTER(C.c_float)]),
+        "hg_mosaic_multiband_layout": (i, [C.POINTER(Geom), i, Geom, i, i, C.POINTER(sz)]),
+        "hg_mosaic_multiband_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, C.POINTER(sz), i, i, i, i, C.c_float, i, Geom, vp, vp, vp,
+                                           C.POINTER(C.c_float), vp, sz]),
         "hg_fit_sample_indices": (i, [i, C.c_uint32, i, C.POINTER(C.c_int32), i, i, C.POINTER(C.c_int32)]),
         "hg_fit_matches_frames_device": (i, [vp, i, vp, i, C.POINTER(C.c_int32), i, d, i, C.c_uint32, vp, i, vp, vp, vp, vp, vp]),
         "hg_match_descriptors_frames_device": (i, [vp, i, i, sz, vp, i, C.POINTER(C.c_int32), i, vp, i, C.POINTER(C.c_int32), i, d, C.c_uint32, i,
@@ -372,6 +376,15 @@ def mosaic_solve_gains(stats, channels, sigma_n=10.0, sigma_g=0.1):
     _check(lib().hg_mosaic_solve_gains(st.ctypes.data_as(C.POINTER(C.c_uint64)) if n else None, n, int(channels), float(sigma_n), float(sigma_g),
                                        gains.ctypes.data_as(C.POINTER(C.c_float)) if n else None))
     return gains
+
+
+def mosaic_multiband_layout(geoms, canvas, channels, n_bands):
+    """The bytes of scratch Context.mosaic_multiband_device needs for these windows (hg_mosaic_multiband_layout): the labels, one flag byte
+    per pixel of every frame's grid, levels 1..n_bands-1 of every frame's image and weight pyramids and of the blended pyramid."""
+    total = C.c_size_t(0)
+    _check(lib().hg_mosaic_multiband_layout(_geoms(geoms) if len(geoms) else None, len(geoms), Geom(*[int(v) for v in canvas]), int(channels), int(n_bands),
+                                            C.byref(total)))
+    return total.value
 
 
 def _counts(counts, n_frames=None):
@@ -857,6 +870,25 @@ class Context:
         self._c(lib().hg_mosaic_frames_device(self._h, _geoms(geoms) if len(geoms) else None, len(geoms), C.c_void_p(int(d_coords) or None), fo,
                                               C.c_void_p(int(d_frames) or None), po, int(elem), int(channels), int(w), int(h), int(mode), float(feather),
                                               Geom(*[int(v) for v in canvas]), C.c_void_p(int(d_canvas) or None), C.c_void_p(int(d_weight) or None)))
+
+    def mosaic_multiband_device(self, geoms, d_coords, d_frames, elem, channels, w, h, feather, n_bands, canvas, d_canvas, d_work, work_bytes,
+                                d_weight=0, d_labels=0, field_offsets=None, frame_offsets=None, gains=None):
+        """The frames of a set blended into ONE canvas in n_bands (1..8) frequency bands (asynchronous): every canvas pixel is owned by the
+        contributor with the largest feather weight (capped at `feather`), low frequencies are blended across the seams between owners over
+        a wide range and high frequencies over a narrow one.  The arguments are mosaic_frames_device's; d_work: 256-byte aligned scratch of
+        work_bytes >= mosaic_multiband_layout(geoms, canvas, channels, n_bands); d_weight (0: none): 1.0 where a frame owns the pixel;
+        d_labels (0: none): one int32 per canvas pixel, the owner's index or -1."""
+        fo = (C.c_size_t * len(geoms))(*field_offsets) if field_offsets is not None else None
+        po = (C.c_size_t * len(geoms))(*frame_offsets) if frame_offsets is not None else None
+        gp = None
+        if gains is not None:
+            gv = np.ascontiguousarray(gains, dtype=np.float32).ravel()
+            assert gv.size == len(geoms), "one gain per frame"
+            gp = gv.ctypes.data_as(C.POINTER(C.c_float)) if gv.size else None
+        vp = lambda v: C.c_void_p(int(v) or None)
+        self._c(lib().hg_mosaic_multiband_device(self._h, _geoms(geoms) if len(geoms) else None, len(geoms), vp(d_coords), fo, vp(d_frames), po, int(elem),
+                                                 int(channels), int(w), int(h), float(feather), int(n_bands), Geom(*[int(v) for v in canvas]), vp(d_canvas),
+                                                 vp(d_weight), vp(d_labels), gp, vp(d_work), int(work_bytes)))
 
     def fit_matches_frames_device(self, kind, d_matches, n_points, counts, n_frames, threshold, n_hyp, seed, d_mats, d_counts, d_samples=0, refit=True,
                                   d_min_mats=0, d_best=0, d_mask=0):

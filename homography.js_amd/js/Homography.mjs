@@ -739,7 +739,14 @@ class Homography {
      * exported beside them, and only the canvas comes down.  Piecewise, affine and projective transforms.
      *   options.blend     'feather' (default): every frame weighs in by the distance of the pixel's SOURCE position to the border of the
      *                     source image, in source pixels, capped at options.feather -- seams fade; 'mean': plain average of the frames
-     *                     that cover the pixel; 'last': the last frame that covers it (painter's order);
+     *                     that cover the pixel; 'last': the last frame that covers it (painter's order); 'multiband': every pixel is
+     *                     owned by the frame with the largest 'feather' weight, and the frames are blended across the seams between
+     *                     owners in options.bands frequency bands -- low frequencies over a wide range, so exposure differences fade,
+     *                     high frequencies over a narrow one, so detail comes from one frame and nothing is doubled
+     *                     (include/hgwarp.h, hg_mosaic_multiband_device; the weight plane is then 1 where a frame owns the pixel);
+     *   options.bands     the band count of 'multiband', an integer 1..8 (default 5; 1: a paste along the seams);
+     *   options.labels    'multiband' only, true: also return labels, an Int32Array of the owning destiny point set per canvas pixel
+     *                     (-1: none);
      *   options.feather   the cap of the 'feather' weight, a number > 0 (default Infinity: uncapped);
      *   options.canvas    { x, y, width, height } in the windows' coordinate system (four integers); default: the bounding box of the
      *                     non-blank windows;
@@ -755,15 +762,20 @@ class Homography {
      *                     `gains`, a Float32Array of one gain per destiny point set (1 for a blank frame).
      * Every setDestinyPoints(dst[f]) runs on the host exactly as in warpBatch(dstPointSets, {inverse: true}), so the instance ends in the
      * state that call leaves.  A pixel no frame covers is 0 in every channel; where exactly one frame covers it, its bytes are that frame's.
-     * Returns { data: Uint8ClampedArray, width, height, x, y [, weight: Float32Array] }.  Throws a string for an unknown blend, a bad
-     * feather, a canvas that is not four integers, a bad `exposure`, and for `devices` and `sourcePoints` (the mosaic runs on this
+     * Returns { data: Uint8ClampedArray, width, height, x, y [, weight: Float32Array] [, labels: Int32Array] }.  Throws a string for an
+     * unknown blend, bad `bands`, `labels` without 'multiband', a bad feather, a canvas that is not four integers, a bad `exposure`, and for `devices` and `sourcePoints` (the mosaic runs on this
      * instance's own device, over one source point set).
      */
     mosaic(dstPointSets, options = {}) {
         if (options === null || options === undefined) options = {};
         const blend = options.blend === undefined ? 'feather' : options.blend;
+        const multiband = blend === 'multiband';
         const mode = ['last', 'mean', 'feather'].indexOf(blend);
-        if (mode < 0) throw ("mosaic: options.blend must be 'feather', 'mean' or 'last'");
+        if (mode < 0 && !multiband) throw ("mosaic: options.blend must be 'feather', 'mean', 'last' or 'multiband'");
+        const bands = options.bands === undefined ? 5 : options.bands;
+        if (multiband && !(Number.isInteger(bands) && bands >= 1 && bands <= 8)) throw ("mosaic: options.bands must be an integer 1..8");
+        if (!multiband && options.labels === true) throw ("mosaic: options.labels needs blend 'multiband'");
+        const wantLabels = multiband && options.labels === true;
         const feather = options.feather === undefined ? Infinity : options.feather;
         if (typeof feather !== 'number' || !(feather > 0)) throw ("mosaic: options.feather must be a number > 0 (Infinity: uncapped)");
         let canvas = null;
@@ -828,24 +840,27 @@ class Homography {
         if (keep.length === 0 || cw * ch === 0) {                // nothing to blend: the zero canvas
             out.data = new Uint8ClampedArray(cw * ch * 4);
             if (options.weight === true) out.weight = new Float32Array(cw * ch);
+            if (wantLabels) out.labels = new Int32Array(cw * ch).fill(-1);
             if (exposure !== null) out.gains = exposure instanceof Float32Array ? exposure : new Float32Array(F).fill(1);
             return out;
         }
         const sub = (arr, w) => { if (keep.length === F) return arr; const o = new arr.constructor(keep.length * w); keep.forEach((f, k) => o.set(arr.subarray(f * w, (f + 1) * w), k * w)); return o; };
-        const tail = [mode, feather, Int32Array.from([cx, cy, cw, ch]), options.weight === true, this._width, this._height];
+        const tail = [multiband ? bands : mode, feather, Int32Array.from([cx, cy, cw, ch]), options.weight === true, this._width, this._height];
+        if (multiband) tail.push(wantLabels);
         if (exposure !== null) tail.push(exposure instanceof Float32Array ? sub(exposure, 1) : exposure);      // (absent: the call is what it was)
         const srcs = images === null ? null : keep.map((f) => images[f % images.length]);
         let res;
         if (geometric) {
             this._uploadSources(srcs);
-            res = this._native.mosaicInverseGeometric(this._ctx, this.transform === 'affine' ? AFFINE : PROJECTIVE, sub(dsts, n), sub(srcPts, n), sub(geoms, 4), ...tail);
+            res = this._native[multiband ? 'mosaicMultibandInverseGeometric' : 'mosaicInverseGeometric'](this._ctx, this.transform === 'affine' ? AFFINE : PROJECTIVE, sub(dsts, n), sub(srcPts, n), sub(geoms, 4), ...tail);
         } else {
             this._uploadMesh();
             this._uploadSources(srcs);
-            res = this._native.mosaicInversePiecewise(this._ctx, sub(dsts, n), sub(geoms, 4), ...tail);
+            res = this._native[multiband ? 'mosaicMultibandInversePiecewise' : 'mosaicInversePiecewise'](this._ctx, sub(dsts, n), sub(geoms, 4), ...tail);
         }
         out.data = res.data;
         if (options.weight === true) out.weight = res.weight;
+        if (wantLabels) out.labels = keep.length === F ? res.labels : res.labels.map((l) => (l < 0 ? l : keep[l]));      // (the blank frames were not part of the call)
         if (exposure !== null) {                                 // one gain per destiny point set: the blank frames were not part of the call
             out.gains = new Float32Array(F).fill(1);
             keep.forEach((f, k) => { out.gains[f] = res.gains[k]; });

@@ -40,7 +40,7 @@ extern "C" {
                                    the bicubic remap by that of hg_remap_bicubic_frames_device, exposure gains of a mosaic by that of
                                    hg_mosaic_overlap_stats_device, fitting transforms to matches by that of hg_fit_matches_frames_device);
                                    matching descriptors by the presence of hg_match_descriptors_frames_device, keypoints by the presence of
-                                   hg_detect_describe_frames_device */
+                                   hg_detect_describe_frames_device, multi-band mosaics by the presence of hg_mosaic_multiband_device */
 
 enum {
     HG_OK = 0,
@@ -583,6 +583,78 @@ int hg_mosaic_frames_gain_device(hg_ctx *ctx, const hg_geom *geoms, int n_frames
                                  int mode, float feather,
                                  hg_geom canvas, void *d_canvas, float *d_weight,
                                  const float *gains);
+/* MULTI-BAND blending of a mosaic (Brown & Lowe, section 7, after Burt & Adelson): low frequencies are blended over a wide range and high
+ * frequencies over a narrow one, so exposure differences fade across a seam while detail comes from one frame only -- no step as with
+ * HG_MOSAIC_LAST / HG_MOSAIC_MEAN, no ghosting as with HG_MOSAIC_FEATHER.  As a by-product it yields the SEAM LABEL MAP: which frame owns
+ * each canvas pixel.
+ *
+ * hg_mosaic_multiband_device: the arguments up to canvas, d_canvas and d_weight mean exactly what they mean in hg_mosaic_frames_gain_device
+ * (packing defaults, alignment rules, hg_geom limits, gains on the HOST or NULL, a gain of exactly 1.0f == no gain).  feather is the cap of
+ * HG_MOSAIC_FEATHER (> 0, +Inf: uncapped) and RANKS the frames here; n_bands is 1..8; d_labels may be NULL, otherwise one int32 per canvas
+ * pixel, aligned to 4 bytes; d_work is the caller's scratch, aligned to 256 bytes, of at least the work_bytes hg_mosaic_multiband_layout
+ * returns for the same geoms, canvas, channels and n_bands.  The library allocates nothing, as with d_pyr.
+ * All arithmetic is f32 in the written order, contraction off.  L = n_bands, A = 2^(L-1).
+ *   1. CONTRIBUTORS AND LABELS.  Per canvas pixel, candidates and contributors are steps 1-3 of hg_mosaic_frames_device.  A contributor's
+ *      rank is the HG_MOSAIC_FEATHER weight w_f of step 6 (the same expression, cap and 2^-10 floor).  The LABEL is the contributor with the
+ *      largest w_f, the lowest f among equals; -1 without a contributor.  d_labels receives it.
+ *   2. LEVEL GRIDS.  x = X - canvas.x_off is the level-0 coordinate of a position (y alike); position x of level k stands for x 2^k of
+ *      level 0.  Level k of the CANVAS covers [-(A >> k), (A ceil(cw / A) + A) >> k) in x, and likewise in y.  A frame TAKES PART iff its
+ *      window meets the canvas window, in [a0, a1) x [b0, b1) of canvas-relative coordinates; frame pixels outside the canvas are not read.
+ *      Its level-0 grid is [A (floor(a0 / A) - 1), A (ceil(a1 / A) + 1)) in x, likewise in y: aligned to A with a margin of A, so every
+ *      level-k grid is the level-0 grid shifted right by k, and the grids of different frames coincide pixel for pixel.  Every array below is
+ *      0.0f outside its grid.
+ *   3. LEVEL 0 of frame f: I_f,0,c(x) = q_c if f contributes at x, else 0.0f, with q_c = g_f * p_c on the stat channels (the alpha of 4
+ *      channels unscaled; one multiply by 1.0f without gains); M_f,0(x) = 1.0f iff the label at x is f, else 0.0f.  Neither is stored as
+ *      floats: "contributes" and "is the label" are two bits of one byte per grid pixel in the work area.
+ *   4. REDUCE, k -> k + 1, images and weights alike: for output (x, y) the taps are t[j][i] = in(2x + i - 2, 2y + j - 2), i, j = 0..4;
+ *      r_j = ((t0 + t4) + (t1 + t3) * 4.0f) + t2 * 6.0f along row j, out = (((r_0 + r_4) + (r_1 + r_3) * 4.0f) + r_2 * 6.0f) * 0.00390625f.
+ *   5. EXPAND of an array T of level k + 1 at position (x, y) of level k.  In one dimension: x even, i = x / 2:
+ *      ((T[i-1] + T[i+1]) + T[i] * 6.0f) * 0.125f; x odd, i = (x - 1) / 2: (T[i] + T[i+1]) * 0.5f.  Horizontally on the at most three rows
+ *      the vertical rule needs, then the same rule vertically on those results.
+ *   6. BLEND AND COLLAPSE, k = L-1 down to 0, per position x of the canvas's level k: over the frames, in ascending f, whose level-k grid
+ *      holds x and whose w = M_f,k(x) is not 0.0f: lap_c = I_f,k,c(x) - expand(I_f,k+1,c)(x) (k = L-1: I_f,k,c(x)), num_c = num_c + w * lap_c,
+ *      den = den + w, both from 0.0f.  B_c = den > 0 ? num_c / den : 0.0f.  R_k,c = B_c + expand(R_k+1,c)(x) (k = L-1: B_c).
+ *   7. STORE, for k = 0 and canvas pixels only.  Label -1: every channel 0, weight 0.0f.  Otherwise f32 stores R_0,c, u8 stores
+ *      (uint8)fminf(255.0f, fmaxf(0.0f, floorf(R_0,c + 0.5f))), weight 1.0f.  Every canvas pixel is written.
+ * Hence: with n_bands == 1 the canvas is, per pixel, the label frame's q_c -- u8 rounded as the gain mosaic rounds --, a paste along the
+ * seam, equal to HG_MOSAIC_LAST where frames do not overlap.  Frames with identical windows, full coverage and the same constant value
+ * give that constant.  Non-finite f32 pixels give unspecified payloads.  DECIDED where the rule left a choice: at level 0 the blend runs
+ * like every other level (num = 0.0f + 1.0f * lap, B = num / 1.0f), so a Laplacian of -0.0f enters as +0.0f; "label -1" at the store is
+ * den == 0 at level 0, the same pixels; expand takes a row outside the grid as a row of 0.0f; the labels' part of the work area is
+ * reserved whether d_labels is given or not, since the layout call cannot know.
+ * LIMITATION: uncovered pixels enter the image pyramids as 0, as in OpenCV's blender: where a seam runs into a coverage border a faint dark
+ * halo is possible (a coverage-normalised pyramid is not offered).  The result depends on the canvas window chosen, through clipping and
+ * the grid origin.
+ * n_frames == 0 zeroes the canvas, labels are -1 (geoms / d_coords / d_frames may be NULL).  An empty canvas: HG_OK, nothing is written.
+ * HG_ERR_INVALID: the gain mosaic's list; n_bands outside 1..8; feather NaN or <= 0; with a non-empty canvas a d_work that is NULL,
+ * misaligned or smaller than the layout's work_bytes; a misaligned d_labels; frame grids that need more than 2^31 - 1 blocks in one launch.
+ * Asynchronous on the ctx stream; the frame table goes up through the page-locked staging ring; queued runs whose deferred redo could land on
+ * d_canvas, d_weight, d_labels or d_work are settled first.  No effect on hg_last_*, the sampling mode, the plan, what the policy learned or
+ * staged frame sets.  Launches: k_mb_label, k_mb_seed, L - 1 reduces, L blends -- 2 + (L - 1) + L whatever n_frames is.
+ *
+ * hg_mosaic_multiband_layout (host only, no context): *work_bytes for these windows.  The work area holds, each part aligned to 256 bytes,
+ * in this order: the labels (4 bytes per canvas pixel; used when d_labels is NULL); the flag bytes of every taking-part frame's level-0
+ * grid, in frame order; per taking-part frame, for k = 1..L-1, level k of I (channels floats per grid pixel) and then level k of M (one
+ * float); levels 1..L-1 of R on the canvas grid (channels floats).  Level 0 of I and R is never stored.  An empty canvas needs 0 bytes.
+ * 64 frames of 3840 x 2160, u8 x 4, on their common window at 5 bands: 4 228 678 656 bytes (3.94 GiB) -- 33.2 MB of labels, 64 x 8.5 MB
+ * of flags (grids of 3872 x 2192), 64 x 56.4 MB of I and M, 45.1 MB of R.  (Arithmetic, not a measurement.)
+ * HG_ERR_INVALID: work_bytes NULL; n_frames outside 0..65535; geoms NULL with n_frames > 0; channels outside 1..4; n_bands outside 1..8; a
+ * canvas or a frame beyond the hg_geom limits.
+ * Cost (MI355X; EXPERIMENTS.md "Multi-band"; tools/bench_multiband.py): u8 x 4 frames with weight plane and d_labels, medians of 31 regions,
+ * as ratios to HG_MOSAIC_FEATHER on the same frames in the same process and to the byte floor of the work-area traffic at 8 TB/s (every used
+ * part of the work area written and read once, coordinates twice, pixels once, labels, canvas and weights once).  64 frames with identical
+ * 3840 x 2160 windows (feather 1.63 ms): 1 band 3.35 ms, 2.05 x feather, 2.3 x the floor; 3 bands 8.88 ms, 5.4 x, 3.8 x; 5 bands 9.35 ms,
+ * 5.7 x, 3.9 x.  A strip of 16 frames of 1920 x 1080 shifted by 60 % of their width, canvas 19200 x 1080 (feather 0.24 ms): 0.58 / 1.51 /
+ * 1.60 ms, 2.4 / 6.4 / 6.8 x feather, 4.7 / 7.5 / 7.7 x the floor, with work areas of 116 / 431 / 465 MB.  Level 1 carries three quarters of
+ * the pyramid bytes, so bands beyond the third cost little. */
+int hg_mosaic_multiband_layout(const hg_geom *geoms, int n_frames, hg_geom canvas,
+                               int channels, int n_bands, size_t *work_bytes);
+int hg_mosaic_multiband_device(hg_ctx *ctx, const hg_geom *geoms, int n_frames,
+                               const void *d_coords, const size_t *field_offsets,
+                               const void *d_frames, const size_t *frame_offsets,
+                               int elem, int channels, int W, int H, float feather, int n_bands,
+                               hg_geom canvas, void *d_canvas, float *d_weight, int32_t *d_labels,
+                               const float *gains, void *d_work, size_t work_bytes);
 /* The source field of the FORWARD warps (next section): what hg_warp_forward_* would paint, as geometry.  HG_FIELD_INDEX only, hence no
  * format argument: the forward loops copy whole pixels from integer positions, (s % W, s / W) IS the coordinate.  One int32 per output pixel
  * p, row-major obj_w x obj_h: let w be the LAST writer, in the loop's raster order (:919-930 over y < H, x < W; :955-969 over the cells of
