@@ -604,7 +604,10 @@ static int span_cache_prepare(hg_ctx *c, SpanCacheDev *sc)
         const size_t entries = 1 + (size_t)key.n_frames * gpf;
         HG_TRY(ensure(c, c->d_span_rec, (size_t)std::max<uint64_t>(bytes / 16, 1)));        // (growing drains the stream first: once per build)
         HG_TRY(ensure(c, c->d_span_dir, entries));
+        HG_TRY(ensure(c, c->d_span_fblk, (size_t)std::max(key.n_frames, 1)));
         HIP_TRY(c, hipMemsetAsync(c->d_span_dir, 0, sizeof(int4) * entries, c->stream));   // cursor 0, every group "not cached"
+        launch_span_frame_blocks(mesh_of(c), frames_of(c), c->d_span_fblk, c->stream);      // the frames' blocks of the use kernel's start, once per build
+        HIP_TRY(c, hipGetLastError());
         c->span_cap16 = (uint32_t)(bytes / 16); c->span_gpf = gpf;
         c->span_builds++;
     }
@@ -649,7 +652,7 @@ static void run_warp(hg_ctx *c, uint8_t *d_out, int16_t *map_out, const SpanCach
     c->pw_last_kernel = kernel_code(p);
     switch (p.kernel) {
     case PwKernel::Rows:
-        c->pw_last_variant = launch_pw_rows(mesh_of(c), frames_of(c), rows_of(c), d_out, map_out, c->status_next, c->stream, sc); break;
+        c->pw_last_variant = launch_pw_rows(mesh_of(c), frames_of(c), rows_of(c), d_out, map_out, c->status_next, c->stream, sc, c->d_span_fblk); break;
     case PwKernel::Patch: case PwKernel::PatchGlobal:
         c->pw_last_variant = launch_pw_patch(mesh_of(c), frames_of(c), rows_of(c), d_out, c->status_next, p.kernel == PwKernel::PatchGlobal, c->stream); break;
     case PwKernel::Tile:

@@ -176,6 +176,7 @@ struct hg_ctx {
     // span cache of k_pw_rows<SELF> in packed 4-row groups (hg_span_cache.h; span_cache_prepare in hg_api_piecewise.hip)
     DevBuf<uint4> d_span_rec;                                  // records, 16-byte words
     DevBuf<int4> d_span_dir;                                   // entry 0: the cursor (first 8 bytes), then one SpanDirEnt per (frame, 4-row group)
+    DevBuf<SpanFrameBlock> d_span_fblk;                        // one block per frame, beside the directory (hg_span_start.h): the use kernel's flat start
     uint32_t span_cap16 = 0; int span_gpf = 0;                 // words the build may hand out; groups per frame of the directory
     uint64_t pw_epoch = 1;                                     // frame-set epoch: bumped by whatever can change an input of k_tri_setup or of the span prologue
     SpanCacheState span_state;

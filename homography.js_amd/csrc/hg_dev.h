@@ -26,6 +26,8 @@ extern "C" __device__ uint32_t hg_struct_load_u32(__amdgpu_buffer_rsrc_t rsrc, i
 //   * plain: the XCD walks its contiguous band of `groups_per_xcd` groups frame by frame (band xcd, or xcd + frame where the bands rotate);
 //   * fr.sub_groups > 0 (shared source, fixed bands; PwFrames): the frame's groups are cut into sub-bands of sub_groups groups, sub-band j belongs
 //     to XCD j mod XCCs, and the XCD takes all frames of one of its sub-bands before the next.
+// (Two copies follow this arithmetic and have to be changed with it: span_start_decode in hg_span_start.h, the use kernel's division-free form, and
+//  frame_group_ref in tests/cpp/span_start_check.cpp, the transcription that form is proved against.)
 __device__ __forceinline__ bool frame_group(const PwFrames &fr, int xcd, int bi, int groups_per_xcd, int &f, int &g)
 {
     if (fr.sub_groups > 0) {

@@ -311,10 +311,29 @@ __global__ __launch_bounds__(kTriGroupThreads) void k_tri_spans_grouped(PwMesh m
 }
 
 
+// A wave-uniform value moved to scalar registers of its own: the 8- or 16-register block a wide scalar load delivered it in is free again as soon
+// as every word that is needed later has been taken out of it (otherwise one late use keeps the whole block allocated to the end of the kernel).
+template <typename T>
+__device__ __forceinline__ T sgpr_own(T v)
+{
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "one or two scalar registers");
+    T o;
+    if constexpr (sizeof(T) == 4) asm volatile("s_mov_b32 %0, %1" : "=s"(o) : "s"(v));
+    else asm volatile("s_mov_b64 %0, %1" : "=s"(o) : "s"(v));
+    return o;
+}
+
+// Where the SELF 3 form (the use kernel) takes its inputs from -- everything else in the body is shared with the other forms:
+//   argument block `sa` (hg_span_start.h): block decode, directory / record / frame-block pointers, out, source pointer and size, safe_spans,
+//       rows_per_group, and the housekeeping's status_next / cnt_clear / row_stride / n_frames (the wrapper passes out, rows_per_group and
+//       status_next as the parameters of those names);
+//   the frame's block: FrameDesc fields, source minima, HiBounds words, fp64 limits (fp64-bounds form only);
+//   the directory entry: state, record offset and counts, and the frame's record form (one_fma) for a valid group;
+//   mesh / fr / rl: only in the branch of a group that is not valid -- the prologue's arrays, two_round / gen, flag_frame.  `sc` is unused.
 template <int CAP, bool MAP, int PH, bool COMPACT, bool HIB, int SELF>      // SELF: 0 row lists, 1 own spans, 2 own spans written to the span cache, 3 spans from the cache
 __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl, uint8_t *__restrict__ out,
                                              int16_t *__restrict__ map_out, int groups_per_xcd, int rows_per_group,
-                                             int32_t *__restrict__ status_next, const SpanCacheDev &sc)
+                                             int32_t *__restrict__ status_next, const SpanCacheDev &sc, const SpanStartArgs &sa_in = SpanStartArgs())
 {
     // A workgroup owns rows_per_group consecutive output rows: kRowGroup = 4 when the host expects short span lists, 1
     // for dense meshes (there, rows that share source lines should run side by side in different workgroups).  1-D grid decoded so that XCD x (= block id % number of XCCs of the device -- hipDeviceAttributeNumberOfXccs, hg_create --, the observed
@@ -323,23 +342,83 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
     const int bid = blockIdx.x, xcd = bid & ((1 << fr.xcc_log2) - 1);
     const int bi = bid >> fr.xcc_log2;
     int f, gi;                                              // frame and row group of it (frame_group, hg_dev.h: bands, rotating bands or dealt sub-bands)
+    SpanStartArgs sa = sa_in;
+    if constexpr (SELF == 3) {
+        // The whole argument block is asked for in the entry block -- the empty statement reads every field, so none of its loads is sunk behind a
+        // branch to be waited for on its own -- and the decode runs without its divisions (hg_span_start.h).
+        asm volatile("" :: "s"(sa.dir), "s"(sa.rec), "s"(sa.fblk), "s"(sa.out), "s"(sa.img), "s"(sa.status_next), "s"(sa.cnt_clear), "s"(sa.src_w), "s"(sa.src_h),
+                           "s"(sa.groups_per_frame), "s"(sa.rows_per_group), "s"(sa.safe_spans), "s"(sa.row_stride), "s"(sa.dec.xcc_log2), "s"(sa.dec.xcc_rotate),
+                           "s"(sa.dec.sub_groups), "s"(sa.dec.n_frames), "s"(sa.dec.per_sub), "s"(sa.dec.groups_per_xcd), "s"(sa.dec.by_per_sub.mul),
+                           "s"(sa.dec.by_per_sub.shift), "s"(sa.dec.by_sub.mul), "s"(sa.dec.by_sub.shift), "s"(sa.dec.by_gpx.mul), "s"(sa.dec.by_gpx.shift));
+        // (what is needed beyond the decode, word by word: sgpr_own)
+        sa.dir = sgpr_own(sa.dir); sa.rec = sgpr_own(sa.rec); sa.fblk = sgpr_own(sa.fblk); sa.img = sgpr_own(sa.img); sa.cnt_clear = sgpr_own(sa.cnt_clear);
+        sa.src_w = sgpr_own(sa.src_w); sa.src_h = sgpr_own(sa.src_h); sa.groups_per_frame = sgpr_own(sa.groups_per_frame);
+        sa.safe_spans = sgpr_own(sa.safe_spans); sa.row_stride = sgpr_own(sa.row_stride); sa.dec.n_frames = sgpr_own(sa.dec.n_frames);
+        out = sgpr_own(out); rows_per_group = sgpr_own(rows_per_group); status_next = sgpr_own(status_next);      // (the wrapper passes the block's)
+        if (!span_start_decode(sa.dec, bid, f, gi)) return;
+    } else
     if (!frame_group(fr, xcd, bi, groups_per_xcd, f, gi)) return;
     // (fr.xcc_rotate: the band an XCD takes rotates with the frame.  Where rows differ in cost -- C4's face mesh fills the middle
     //  bands and leaves the top and bottom ones nearly empty -- a fixed band per XCD hands the same XCD the expensive band of EVERY
     //  frame: C4 0.234 -> 0.220 ms.  Where they do not and the frames share one source, the fixed band is what keeps that band's
     //  source rows in the XCD's L2 from frame to frame: C3 0.551 fixed, 0.607 rotating.  The host decides, hg_api_piecewise.hip.)
     const int r0 = gi * rows_per_group;
-    const FrameDesc fd = fr.frames[f];
-    const int2 ms = frame_min_src(mesh, fr, f);              // the source minima of :1047: the mesh's, or this frame's own (two scalars, fetched by the decoded frame index)
+    // SELF 3, the flat start: everything that depends on (f, gi) -- the frame's block and the group's directory entry -- is fetched
+    // here in ONE round trip; the records follow.  Both addresses are wave-uniform, and the loads go through the constant address space, which makes
+    // them scalar loads whatever precedes them: nothing writes either array in this launch.  The empty statement reads what was loaded, so both
+    // loads are issued in front of it and waited for once.
+    SpanFrameBlock fb = {};
+    int4 dir_e = make_int4(0, 0, 0, 0);
+    if constexpr (SELF == 3) {
+        typedef uint32_t v16u __attribute__((ext_vector_type(16)));
+        typedef uint32_t v8u __attribute__((ext_vector_type(8)));
+        typedef int v4i __attribute__((ext_vector_type(4)));
+        const v16u w = *reinterpret_cast<const __attribute__((address_space(4))) v16u *>(reinterpret_cast<uintptr_t>(sa.fblk + f));
+        // (group slots past the tallest frame's last group -- the XCD bands are padded -- have no entry: they read the frame's last one and leave below, by their rows)
+        const v4i e = *reinterpret_cast<const __attribute__((address_space(4))) v4i *>(reinterpret_cast<uintptr_t>(static_cast<const int4 *>(sa.dir) + ((size_t)f * sa.groups_per_frame + min(gi, sa.groups_per_frame - 1))));
+        v8u lim = { 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u };
+        if constexpr (!HIB) lim = *reinterpret_cast<const __attribute__((address_space(4))) v8u *>(reinterpret_cast<uintptr_t>(sa.fblk + f) + offsetof(SpanFrameBlock, bx_lo));
+        asm volatile("" :: "s"(w), "s"(e));
+        if constexpr (!HIB) asm volatile("" :: "s"(lim));
+        fb.x_off = (int)sgpr_own(w[0]); fb.y_off = (int)sgpr_own(w[1]); fb.obj_w = (int)sgpr_own(w[2]); fb.obj_h = (int)sgpr_own(w[3]);
+        fb.out_off = (uint64_t)sgpr_own(w[4]) | ((uint64_t)sgpr_own(w[5]) << 32);
+        fb.ms_x = (int)sgpr_own(w[6]); fb.ms_y = (int)sgpr_own(w[7]); fb.hb_lox = sgpr_own(w[8]); fb.hb_rx = sgpr_own(w[9]); fb.hb_loy = sgpr_own(w[10]); fb.hb_ry = sgpr_own(w[11]);
+        fb.bx_lo = __hiloint2double((int)lim[1], (int)lim[0]); fb.bx_hi = __hiloint2double((int)lim[3], (int)lim[2]);       // (pinned below, each word)
+        fb.by_lo = __hiloint2double((int)lim[5], (int)lim[4]); fb.by_hi = __hiloint2double((int)lim[7], (int)lim[6]);
+        dir_e = make_int4(sgpr_own(e[0]), sgpr_own(e[1]), sgpr_own(e[2]), sgpr_own(e[3]));
+    }
+    FrameDesc fd;
+    int2 ms;
+    if constexpr (SELF == 3) {
+        fd.x_off = fb.x_off; fd.y_off = fb.y_off; fd.obj_w = fb.obj_w; fd.obj_h = fb.obj_h; fd.out_off = fb.out_off; fd.map_off = 0;
+        ms = make_int2(fb.ms_x, fb.ms_y);
+    } else {
+        fd = fr.frames[f];
+        ms = frame_min_src(mesh, fr, f);                    // the source minima of :1047: the mesh's, or this frame's own (two scalars, fetched by the decoded frame index)
+    }
     // housekeeping for the NEXT step (saves its memset): the next status set is cleared here, and every workgroup zeroes the
     // span counters of its rows in the OTHER of the two counter sets -- the one the previous step consumed and the next step's
     // k_tri_spans will count into (ping-pong: nobody reads it during this launch, so no ordering against this launch's readers)
-    const int nthreads = (int)blockDim.x, nwaves = nthreads >> 6;       // 256 threads
+    const int nthreads = SELF == 3 ? 256 : (int)blockDim.x, nwaves = nthreads >> 6;       // 256 threads (SELF 3: as launched, not asked of the dispatch packet)
+    if constexpr (SELF != 3) {
     if (bid == 0 && status_next) for (int i = threadIdx.x; i < fr.n_frames; i += nthreads) status_next[i] = 0;
     // (every row of the frame's counter block, not only the rows of THIS step's window: the other set was filled under the
     //  previous step's geometry, whose frame may have been a row taller)
     if ((int)threadIdx.x < rows_per_group && r0 + (int)threadIdx.x < rl.row_stride) rl.cnt_clear[(size_t)f * rl.row_stride + r0 + threadIdx.x] = 0;
-    if (r0 >= fd.obj_h || fd.obj_w <= 0) return;
+    }
+    // SELF 3: the same two stores from the argument block, issued once the group's records are in LDS -- or on the way out -- instead of in front of
+    // every load.  (Pointers that went through sgpr_own have lost their address space: told again, or the stores would be flat ones.)
+    [[maybe_unused]] auto housekeeping = [&]() {
+        typedef __attribute__((address_space(1))) int32_t gmem_i32;
+        gmem_i32 *const hk_clear = reinterpret_cast<gmem_i32 *>(reinterpret_cast<uintptr_t>(sa.cnt_clear));
+        gmem_i32 *const hk_status = reinterpret_cast<gmem_i32 *>(reinterpret_cast<uintptr_t>(status_next));
+        if (bid == 0 && hk_status) for (int i = threadIdx.x; i < sa.dec.n_frames; i += nthreads) hk_status[i] = 0;
+        if ((int)threadIdx.x < rows_per_group && r0 + (int)threadIdx.x < sa.row_stride) hk_clear[(size_t)f * sa.row_stride + r0 + threadIdx.x] = 0;
+    };
+    if (r0 >= fd.obj_h || fd.obj_w <= 0) {
+        if constexpr (SELF == 3) housekeeping();
+        return;
+    }
 
     __shared__ __align__(16) double s_m[CAP * 6];
     __shared__ int s_lo[CAP], s_hi[CAP], s_len[CAP], s_key[CAP];   // span start / end (window overlap test), length, key (KS)
@@ -383,25 +462,33 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
     // Source: buffer of W*H records of 4 bytes, gathered by PIXEL index (`buffer_load_dword ... idxen`: one v_mad per address instead of a
     // mad and a shift, EXPERIMENTS.md R6.9): an index at or beyond its end (and the -1 of rejected pixels) returns 0 from the hardware
     // range check == the JS `undefined` -> 0 of :1051.
-    const __amdgpu_buffer_rsrc_t src = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(frame_img(mesh, f)), 4, mesh.W * mesh.H, 0x00020000);   // (records of 4 bytes: gathers by pixel index, hg_struct_load_u32)
+    // (SELF 3: the shared source, from the argument block)
+    const __amdgpu_buffer_rsrc_t src = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(SELF == 3 ? sa.img : frame_img(mesh, f)), 4, SELF == 3 ? sa.src_w * sa.src_h : mesh.W * mesh.H, 0x00020000);   // (records of 4 bytes: gathers by pixel index, hg_struct_load_u32)
     // :1047 on h = RTN(s + 0.5):  minSrcX <= sx < W + minSrcX  <=>  minSrcX + 0.5 <= hx < W + minSrcX + 0.5, same for y.
     // All four are tested on the doubles: the rounded coordinates are only 32-bit (a source row of 300 * 2^24 must be
     // rejected, not wrapped back into the image); what the range check of the buffer load still provides is the `undefined`
     // -> 0 of flat indices that pass :1047 and yet fall outside the array (sx in [W - 0.5, W) on the last row).
-    const double bx_lo = pin_f64<SELF == 3>(sgpr_f64((double)ms.x + 0.5)), bx_hi = pin_f64<SELF == 3>(sgpr_f64((double)mesh.W + (double)ms.x + 0.5));
-    const double by_lo = pin_f64<SELF == 3>(sgpr_f64((double)ms.y + 0.5)), by_hi = pin_f64<SELF == 3>(sgpr_f64((double)mesh.H + (double)ms.y + 0.5));
+    // (SELF 3: the finished limits of the frame's block -- k_span_frame_blocks formed them with these expressions, once per build)
+    // (and only where they are compared: the high-dword form of SELF 3 has no use for them, span_unsafe included)
+    constexpr bool PIN64 = SELF == 3 && !HIB;
+    const double bx_lo = SELF == 3 && HIB ? 0.0 : pin_f64<PIN64>(sgpr_f64(SELF == 3 ? fb.bx_lo : (double)ms.x + 0.5));
+    const double bx_hi = SELF == 3 && HIB ? 0.0 : pin_f64<PIN64>(sgpr_f64(SELF == 3 ? fb.bx_hi : (double)mesh.W + (double)ms.x + 0.5));
+    const double by_lo = SELF == 3 && HIB ? 0.0 : pin_f64<PIN64>(sgpr_f64(SELF == 3 ? fb.by_lo : (double)ms.y + 0.5));
+    const double by_hi = SELF == 3 && HIB ? 0.0 : pin_f64<PIN64>(sgpr_f64(SELF == 3 ? fb.by_hi : (double)mesh.H + (double)ms.y + 0.5));
     // HIB (host: hi_bounds_ok): the same four tests as two 32-bit compares on the high dwords of h (hg_dev.h)
     // (SELF 3: pinned, these and the fp64 limits above -- the compiler sees through readfirstlane of a uniform value and keeps the limits in
     //  vector registers for the whole kernel, which is what stands between the use kernel's two window loops and the parent's occupancy)
-    const HiBounds hb = pin_hi_bounds<SELF == 3>(make_hi_bounds((double)ms.x + 0.5, (double)mesh.W + (double)ms.x + 0.5,
-                                                                (double)ms.y + 0.5, (double)mesh.H + (double)ms.y + 0.5));
-    const bool flag_spans = fr.safe_spans != 0;             // (wave-uniform; host: by the rows' span density)
+    const HiBounds hb = SELF == 3 ? pin_hi_bounds<SELF == 3>(HiBounds{fb.hb_lox, fb.hb_rx, fb.hb_loy, fb.hb_ry})
+                                  : make_hi_bounds((double)ms.x + 0.5, (double)mesh.W + (double)ms.x + 0.5, (double)ms.y + 0.5, (double)mesh.H + (double)ms.y + 0.5);
+    const bool flag_spans = (SELF == 3 ? sa.safe_spans : fr.safe_spans) != 0;      // (wave-uniform; host: by the rows' span density)
     // One fma per coordinate for the whole frame: (m0 x) + (m2 y) + m4 of :1383 rounds twice, but where m0 x + m2 y and m2 y + m4 are exactly
     // representable for every pixel of the window -- k_tri_setup checked every triangle of the frame that has rows (affine_fusable, hg_math.h:
     // both are multiples of the smallest ulp of the f32 entries involved, bounded by the window) -- fma(m0, x, A) with A = (m2 y) + m4 has the same
     // bits.  The span records of such a frame hold {m0, A, m1, B}: 32 bytes of LDS per pixel instead of 48, which is what this kernel runs
     // on (EXPERIMENTS.md R5.8).  Uniform for the workgroup; the row lists (small frame sets) keep the long form.
-    const bool one_fma = SELF != 0 && fr.two_round && __builtin_amdgcn_readfirstlane(fr.two_round[f]) != fr.gen;
+    // (SELF 3: decided below -- a valid group's records carry their form in the directory entry; a group the directory does not hold asks as here)
+    bool one_fma = false;
+    if constexpr (SELF != 3) one_fma = SELF != 0 && fr.two_round && __builtin_amdgcn_readfirstlane(fr.two_round[f]) != fr.gen;
     // bit 0 of a span's key (span_unsafe, hg_spans.h), for a span with record {m0, m2*y, m4, m1, m3*y, m5}
     auto unsafe_bit = [&](double m0, double m2y, double m4, double m1, double m3y, double m5, int lo, int hi) -> int {
         return span_unsafe<HIB>(flag_spans, hb, bx_lo, bx_hi, by_lo, by_hi, fd.x_off, m0, m2y, m4, m1, m3y, m5, lo, hi);
@@ -517,8 +604,7 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
     };
 
     // Run form (SELF 3, hg_span_runs.h): the row's records in LDS are disjoint sorted runs, slot == run index, gap runs hold the NaN record; lane i
-    // keeps the start of run i and the runs' unsafe and gap bits are two wave-wide masks.  Workgroup-uniform; false everywhere else.
-    bool runs = false;
+    // keeps the start of run i and the runs' unsafe and gap bits are two wave-wide masks.
     int run_start_r = 0x7fffffff;
     unsigned long long run_unsafe_m = 0ull, run_gap_m = 0ull;
 
@@ -657,7 +743,7 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
                             round_half_x4(v, r);
 #pragma unroll
                             for (int k = kk; k < kk + 2; k++)
-                                px[p][k] = hg_struct_load_u32(src, __mul24(r[2 * (k - kk) + 1], mesh.W) + r[2 * (k - kk)], 0, 0, 0);     // :1048-1049, in pixels
+                                px[p][k] = hg_struct_load_u32(src, __mul24(r[2 * (k - kk) + 1], SELF == 3 ? sa.src_w : mesh.W) + r[2 * (k - kk)], 0, 0, 0);     // :1048-1049, in pixels
                         }
                     } else
 #pragma unroll
@@ -673,7 +759,7 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
                             const int q = 2 * (k - kk);
                             const bool inb = HIB ? hi_inb(hb, h[q], h[q + 1])
                                                  : (bool)((int)(h[q] >= bx_lo) & (int)(h[q] < bx_hi) & (int)(h[q + 1] >= by_lo) & (int)(h[q + 1] < by_hi));   // NaN fails
-                            const int o = __mul24((int)dlo(rd[q + 1]), mesh.W) + (int)dlo(rd[q]);                           // :1048-1049, in pixels
+                            const int o = __mul24((int)dlo(rd[q + 1]), SELF == 3 ? sa.src_w : mesh.W) + (int)dlo(rd[q]);                           // :1048-1049, in pixels
                             px[p][k] = hg_struct_load_u32(src, inb ? o : -1, 0, 0, 0);                       // range-checked buffer load: outside the array -> 0
                         }
                     }
@@ -717,18 +803,18 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
             typedef uint32_t v4u __attribute__((ext_vector_type(4)));
             // (directory index, words per record, and the row whose slot `lane` this thread copies: one thread per slot of the four 64-slot blocks.
             //  Lambdas, evaluated where they are needed: nothing of the cache is live across the prologue)
-            auto dir_at = [&]() -> size_t { return (size_t)__builtin_amdgcn_readfirstlane(f) * sc.groups_per_frame + __builtin_amdgcn_readfirstlane(gi); };
+            [[maybe_unused]] auto dir_at = [&]() -> size_t { return (size_t)__builtin_amdgcn_readfirstlane(f) * sc.groups_per_frame + __builtin_amdgcn_readfirstlane(gi); };
             auto rec_words = [&]() -> int { return one_fma ? kSpanRecWordsFma : kSpanRecWordsLong; };
             if constexpr (SELF == 3) {
-                const size_t di = dir_at();
-                const int recw = rec_words(), crow = wave;
-                const int4 e = sc.dir[di];
+                const int crow = wave;
+                const int4 e = dir_e;
                 const int state = __builtin_amdgcn_readfirstlane(e.x);
-                if (packed && state == SPAN_DIR_OVERFLOWED) {           // what the prologue of the build found: the same flag, every call
-                    if (threadIdx.x == 0) flag_frame(fr, f, FRAME_LDS_OVERFLOW);
-                    return;
-                }
-                if (packed && state == SPAN_DIR_VALID && __builtin_amdgcn_readfirstlane(e.w) == recw) {     // (records of the form this step's k_tri_setup decided for the frame)
+                // (valid first, everything else in ONE other branch: what only that branch reads of the structs behind the argument block is then fetched there)
+                if (packed && state == SPAN_DIR_VALID) {
+                    // (the records' own form: the build wrote it beside them, from the setup of the same frame set.  What this step's k_tri_setup says of
+                    //  the frame is the same -- or, by a stale word, the long form, which yields the same bytes -- and is not fetched)
+                    one_fma = __builtin_amdgcn_readfirstlane(e.w) == kSpanRecWordsFma;
+                    const int recw = rec_words();
                     const uint32_t off16 = (uint32_t)__builtin_amdgcn_readfirstlane(e.y), counts = (uint32_t)__builtin_amdgcn_readfirstlane(e.z);
                     // Wave j copies row j's slots into row j's block and is the only reader of that block (packed groups: wave j walks row
                     // r0 + j alone): no barrier, a wave starts on its row as soon as its own records have landed.
@@ -739,7 +825,8 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
                     for (int j = 0; j < RG; j++) { cnts[j] = span_count(counts, j); before += j < crow ? cnts[j] : 0; }
                     bool r_unsafe = false, r_gap = false;
                     if (lane < span_count(counts, crow)) {
-                        const v4u *p = reinterpret_cast<const v4u *>(sc.rec) + off16 + (size_t)(before + lane) * recw;
+                        typedef const __attribute__((address_space(1))) v4u gmem_v4u;       // (global memory, said again behind sgpr_own)
+                        gmem_v4u *p = reinterpret_cast<gmem_v4u *>(reinterpret_cast<uintptr_t>(sa.rec)) + off16 + (size_t)(before + lane) * recw;
                         const v4u a = p[0], b = p[1];
                         const int at = crow * 64 + lane;
                         run_start_r = run_start(a.x); r_gap = run_gap(a.x) != 0; r_unsafe = span_unsafe_bit(a.y) != 0;
@@ -752,8 +839,22 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
                         }
                     }
                     run_unsafe_m = __ballot(r_unsafe); run_gap_m = __ballot(r_gap);
-                    runs = true;
-                    have = true;
+                    // The housekeeping stores, once the records are in: a store issued between the record loads and their use waited for the loads
+                    // itself (its operand took a register of theirs) and then made wave 0 wait for its own acknowledgement -- read in the assembly.
+                    // Here nothing waits for it but the first window's gathers, a whole resolve later.
+                    housekeeping();
+                    // (the row's walk from here, not from the join below: what follows this block is then the other branch's alone, and so are its fetches)
+                    if (crow < nrows) do_row(std::true_type{}, crow, span_count(counts, crow), wave * 64, 63, w_lo, 1);
+                    return;
+                }
+                else {
+                    housekeeping();
+                    if (packed && state == SPAN_DIR_OVERFLOWED) {       // what the prologue of the build found: the same flag, every call
+                        if (threadIdx.x == 0) flag_frame(fr, f, FRAME_LDS_OVERFLOW);
+                        return;
+                    }
+                    // not cached: the prologue, with the record form this step's k_tri_setup decided
+                    one_fma = fr.two_round && __builtin_amdgcn_readfirstlane(fr.two_round[f]) != fr.gen;
                 }
             }
             if (!have) {
@@ -824,7 +925,6 @@ __device__ __forceinline__ void pw_rows_body(const PwMesh &mesh, const PwFrames 
         for (int j = 0; j < RG; j++) cnt_row += cnts[j] * (row == j);
         const int cnt = __builtin_amdgcn_readfirstlane(cnt_row);
         if (row < nrows) {
-            if constexpr (SELF == 3) { if (runs) { do_row(std::true_type{}, row, cnt, wave * 64, 63, w_lo, 1); return; } }
             do_row(std::false_type{}, row, cnt, packed ? wave * 64 : 0, packed ? 63 : CAP - 1, w_lo + (packed ? 0 : wave), packed ? 1 : nwaves);
         }
         return;
@@ -853,8 +953,40 @@ template <int PH, bool HIB, int SELF>
 __global__ __launch_bounds__(256) void k_pw_rows_cached(PwMesh mesh, PwFrames fr, RowLists rl, uint8_t *__restrict__ out, int groups_per_xcd, int rows_per_group,
                                                         int32_t *__restrict__ status_next, SpanCacheDev sc)
 {
-    static_assert(SELF == 2 || SELF == 3, "build or use");
+    static_assert(SELF == 2, "the build; the use form is the overload below");
     pw_rows_body<kRowSpanCapFast, false, PH, false, HIB, SELF>(mesh, fr, rl, out, nullptr, groups_per_xcd, rows_per_group, status_next, sc);
+}
+// The use form: the argument block first (hg_span_start.h), so that what a valid group's start needs arrives in two scalar loads; the structs
+// behind it are touched by the housekeeping stores and by groups the directory does not hold.
+// (amdgpu_num_sgpr: 100 scalar registers in all is the most that 8 waves per SIMD can have; left alone the allocator takes 104 because nothing tells it)
+template <int PH, bool HIB, int SELF>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(102))) void k_pw_rows_cached(SpanStartArgs sa, PwMesh mesh, PwFrames fr, RowLists rl)
+{
+    static_assert(SELF == 3, "the use form");
+    pw_rows_body<kRowSpanCapFast, false, PH, false, HIB, SELF>(mesh, fr, rl, sa.out, nullptr, sa.dec.groups_per_xcd, sa.rows_per_group, sa.status_next, SpanCacheDev(), sa);
+}
+
+// The frame blocks of the span cache (hg_span_start.h), one thread per frame, once per build: the frame record, its source minima and the limits of
+// the bounds test :1047 in both forms, formed with the expressions pw_rows_body uses.
+__global__ __launch_bounds__(64) void k_span_frame_blocks(PwMesh mesh, PwFrames fr, SpanFrameBlock *__restrict__ blk)
+{
+    const int f = blockIdx.x * 64 + threadIdx.x;
+    if (f >= fr.n_frames) return;
+    const FrameDesc fd = fr.frames[f];
+    const int2 ms = fr.min_src ? fr.min_src[f] : make_int2(mesh.min_src_x, mesh.min_src_y);
+    SpanFrameBlock b = {};
+    b.x_off = fd.x_off; b.y_off = fd.y_off; b.obj_w = fd.obj_w; b.obj_h = fd.obj_h; b.out_off = fd.out_off;
+    b.ms_x = ms.x; b.ms_y = ms.y;
+    b.bx_lo = (double)ms.x + 0.5; b.bx_hi = (double)mesh.W + (double)ms.x + 0.5;
+    b.by_lo = (double)ms.y + 0.5; b.by_hi = (double)mesh.H + (double)ms.y + 0.5;
+    b.hb_lox = (uint32_t)__double2hiint(b.bx_lo); b.hb_rx = (uint32_t)__double2hiint(b.bx_hi) - b.hb_lox;      // make_hi_bounds (hg_dev.h), per thread
+    b.hb_loy = (uint32_t)__double2hiint(b.by_lo); b.hb_ry = (uint32_t)__double2hiint(b.by_hi) - b.hb_loy;
+    blk[f] = b;
+}
+void launch_span_frame_blocks(const PwMesh &mesh, const PwFrames &fr, SpanFrameBlock *blk, hipStream_t stream)
+{
+    if (fr.n_frames <= 0 || !blk) return;
+    hipLaunchKernelGGL(k_span_frame_blocks, dim3((unsigned)((fr.n_frames + 63) / 64)), dim3(64), 0, stream, mesh, fr, blk);
 }
 
 // The same kernel held to 80 SGPRs.  A 256-thread workgroup puts one wave on each SIMD and a SIMD has 800 SGPRs, allocated in
@@ -947,7 +1079,7 @@ void launch_tri_spans(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl
 // windows-or-blocks per phase * 1000 + (8-byte entries) * 100 + (bounds on the high dwords) * 10 + self-span form; kind 1 k_pw_rows,
 // 3 k_pw_rows_s80, 4 k_pw_patch, 5 k_pw_tile, 6 k_pw_fused, 8 k_pw_patch with global records; + 50 for a parity-tap (map) instantiation.
 int launch_pw_rows(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl, uint8_t *out, int16_t *map_out, int32_t *status_next, hipStream_t stream,
-                   const SpanCacheDev &sc)
+                   const SpanCacheDev &sc, const SpanFrameBlock *fblk)
 {
     if (fr.n_frames <= 0 || fr.max_obj_h <= 0) return 0;
     int code = 0;
@@ -969,10 +1101,18 @@ int launch_pw_rows(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl, u
         // ONE depth: 4 windows per phase (R4.10: a wash to a slight gain over 2 for every self-span set; the census of round 6 found the
         // 1- / 2-window, the 80-SGPR and the three-edges-in-flight instantiations never picked: deleted, EXPERIMENTS.md R6.6)
         // span cache (host: packed 4-row groups, no tap): the same two forms with the cache behind them; the code reported is the uncached form's
-        if (sc.mode && !map_out && rg == kRowGroup && sc.dir && sc.rec && sc.cursor) {
+        if (sc.mode && !map_out && rg == kRowGroup && sc.dir && sc.rec && sc.cursor && (sc.mode == 1 || fblk) && mesh.n_imgs <= 1) {
+            // the use form's argument block (hg_span_start.h): this launch's scalars, copied from the structs above
+            SpanStartArgs sa;
+            sa.dir = sc.dir; sa.rec = sc.rec; sa.fblk = fblk; sa.out = out; sa.img = mesh.img; sa.status_next = status_next; sa.cnt_clear = rl.cnt_clear;
+            sa.src_w = mesh.W; sa.src_h = mesh.H;
+            sa.groups_per_frame = sc.groups_per_frame; sa.rows_per_group = rg; sa.safe_spans = fr.safe_spans; sa.row_stride = rl.row_stride;
+            sa.dec = span_start_decode_make(fr.xcc_log2, fr.xcc_rotate, frs.sub_groups, fr.n_frames, rpx);
 #define HG_ROWS_SC(PHV, HB, SF) hipLaunchKernelGGL((k_pw_rows_cached<PHV, HB, SF>), grid, block, pad, stream, mesh, frs, rl, out, rpx, rg, status_next, sc)
-            if (!hib) { code = 101001; if (sc.mode == 1) HG_ROWS_SC(1, false, 2); else HG_ROWS_SC(1, false, 3); }
-            else      { code = 104011; if (sc.mode == 1) HG_ROWS_SC(4, true, 2); else HG_ROWS_SC(4, true, 3); }
+#define HG_ROWS_USE(PHV, HB) hipLaunchKernelGGL((k_pw_rows_cached<PHV, HB, 3>), grid, block, pad, stream, sa, mesh, frs, rl)
+            if (!hib) { code = 101001; if (sc.mode == 1) HG_ROWS_SC(1, false, 2); else HG_ROWS_USE(1, false); }
+            else      { code = 104011; if (sc.mode == 1) HG_ROWS_SC(4, true, 2); else HG_ROWS_USE(4, true); }
+#undef HG_ROWS_USE
 #undef HG_ROWS_SC
             return code;
         }

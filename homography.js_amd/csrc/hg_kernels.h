@@ -5,6 +5,7 @@
 #include "hg_math.h"
 #include "hg_span_cache.h"
 #include "hg_span_runs.h"
+#include "hg_span_start.h"
 #include "hg_remap_records.h"
 
 namespace hg {
@@ -159,8 +160,10 @@ struct SpanCacheDev {
     int32_t groups_per_frame = 0;
     int32_t mode = 0;
 };
+// The frame blocks of the use form's flat start (hg_span_start.h), n_frames of them: written at build time, handed to launch_pw_rows with mode 2.
+void launch_span_frame_blocks(const PwMesh &mesh, const PwFrames &fr, SpanFrameBlock *blk, hipStream_t stream);
 int launch_pw_rows(const PwMesh &mesh, const PwFrames &fr, const RowLists &rl, uint8_t *out, int16_t *map_out, int32_t *status_next, hipStream_t stream,
-                   const SpanCacheDev &sc = SpanCacheDev());
+                   const SpanCacheDev &sc = SpanCacheDev(), const SpanFrameBlock *fblk = nullptr);
 // Dense meshes (64..199 spans per row, obj_w <= 8192): 4 rows per workgroup, 16 x 4 pixel gather patches, one matrix record
 // per triangle of the group.  Same row lists, same status protocol as launch_pw_rows; no map tap.
 // (limits on the HOST ESTIMATES, which run ~10 % above the real counts the kernel enforces: 199 spans per row, 208 triangles
