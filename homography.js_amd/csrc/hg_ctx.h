@@ -1,6 +1,6 @@
 // hg_ctx.h -- the context behind the C ABI of include/hgwarp.h and the helpers its translation units share
 // (hg_api.hip: library / context / buffers / host-side solves / source image; hg_api_geometric.hip; hg_api_piecewise.hip;
-// hg_api_forward.hip; hg_api_state.hip; hg_api_field.hip; hg_api_points.hip; hg_api_fit.hip; hg_api_match.hip; hg_api_detect.hip).  Its memory is owned through hg_mem.h.  Internal: nothing here is exported.
+// hg_api_forward.hip; hg_api_state.hip; hg_api_field.hip; hg_api_points.hip; hg_api_fit.hip; hg_api_match.hip; hg_api_detect.hip; hg_api_align.hip).  Its memory is owned through hg_mem.h.  Internal: nothing here is exported.
 #pragma once
 #include "../../include/hgwarp.h"
 #include "hg_kernels.h"
@@ -216,6 +216,12 @@ struct hg_ctx {
     DevBuf<int32_t> d_fit_valid;
     DevBuf<uint64_t> d_fit_frames;                             // F best words, then the F counts (int32, padded to 8 bytes)
     StageRing<4> fit_stage;                                    // the counts go up through page-locked staging, stream-ordered
+
+    // refining transforms on the pixels (hg_api_align.hip): the per-frame iterate and flags, the chunks' partial records and the luma copies of
+    // 4-channel planes; grown on demand
+    DevBuf<hg::AlignState> d_align_state;
+    DevBuf<double> d_align_part;
+    DevBuf<uint8_t> d_align_luma;
 
     // matching descriptors (hg_api_match.hip): the two-nearest records of the queries and, for the cross-check, of the train rows; the counts of
     // both sides; grown on demand

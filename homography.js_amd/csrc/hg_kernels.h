@@ -7,6 +7,7 @@
 #include "hg_span_runs.h"
 #include "hg_span_start.h"
 #include "hg_remap_records.h"
+#include "hg_align_dev.h"
 
 namespace hg {
 
@@ -283,6 +284,18 @@ struct FitArgs {
     double *out_mats, *out_min; int32_t *out_counts, *out_best; uint8_t *out_mask;
 };
 void launch_fit(const FitArgs &a, hipStream_t stream);
+
+// Refining transforms on the pixels (hg_k_align.hip; the rules: hg_align_dev.h): n_iter + 1 passes of k_align_accumulate + k_align_update over all
+// frames, none of them waited for.  from / to: ONE-byte luma planes (the caller's, or the copies launch_align_luma made of 4-channel planes),
+// frame f reads from + f * from_stride and to + (f % n_to_sets) * to_stride.  nx = samples per row of the grid, n_samples = all of them,
+// n_chunks = ceil(n_samples / kAlignChunk).  scratch: state = F records, part = F x n_chunks x kAlignRec doubles.  sums may be nullptr.
+struct AlignArgs {
+    int kind, photometric; const uint8_t *from; int Wf, Hf; size_t from_stride; const uint8_t *to; int Wt, Ht, n_to_sets; size_t to_stride;
+    int rx, ry, rw, rh, step, nx, n_samples, n_chunks, n_frames, n_iter; double eps; int min_valid;
+    const double *mats_in; double *mats_out; AlignInfo *info; double *sums; AlignState *state; double *part;
+};
+void launch_align_luma(const uint8_t *src, size_t src_stride, int W, int H, int n_planes, uint8_t *dst, hipStream_t stream);
+void launch_align(const AlignArgs &a, hipStream_t stream);
 
 // Matching descriptors (hg_k_match.hip; the rules: hg_match_dev.h): k_match_bits resp. k_match_u8 for the two nearest train rows of every query,
 // the same kernel with the sides swapped for the best query of every train row (cross_check), then k_match_finish.  query = F lists of

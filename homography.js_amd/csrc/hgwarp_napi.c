@@ -1164,6 +1164,151 @@ static napi_value fn_fit_matches(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* The alignment of the drop-in class (refineAlignment): the planes and their pyramids stay in device memory of a JOB between the calls of
+ * a coarse-to-fine walk; only the matrices travel.
+ *   alignBegin(handle, from, Wf, Hf, nFrames, to, Wt, Ht, nToSets, channels, levels) -> job: from / to are Uint8Arrays of nFrames resp.
+ *     nToSets planes of W x H x channels; they go up, and with levels > 1 hg_pyramid_build_device builds both pyramids.
+ *   alignLevel(handle, job, kind, level, rect: Int32Array(4), step, photometric, nIter, eps, minValid, matrices: Float64Array(8 F)) ->
+ *     { matrices, status, updates: Int32Array(F), nValid: Int32Array(2 F), rms, gains: Float64Array(2 F) }: hg_align_refine_frames_device on
+ *     that level of both pyramids (matrices and rect in the level's pixels); nValid and rms hold (first, last), gains (gain, bias) per frame.
+ *   alignScaleMatrix(kind, matrices: Float64Array(8 F), levelIn, levelOut) -> Float64Array(8 F): hg_align_scale_matrix row by row; a row with
+ *     an entry that is not finite is copied.  Host only.
+ *   alignEnd(handle, job): frees the job's device memory. */
+typedef struct { void *d; int Wf, Hf, F, Wt, Ht, S, channels, levels; size_t o_from, o_to, o_fpyr, o_tpyr, o_mats, o_info, fpyr_bytes, tpyr_bytes; size_t foffs[32], toffs[32]; } align_job_t;
+
+static void align_job_finalize(napi_env env, void *data, void *hint) { (void)env; (void)hint; free(data); }      /* (the device block is alignEnd's) */
+
+static napi_value fn_align_begin(napi_env env, napi_callback_info info)
+{
+    napi_value a[11];
+    if (!get_args(env, info, 11, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    int Wf, Hf, F, Wt, Ht, S, ch, levels; size_t n_f = 0, n_t = 0;
+    uint8_t *from = (uint8_t *)get_typed(env, a[1], napi_uint8_array, &n_f, "from"); if (!from) return NULL;
+    if (!get_i32(env, a[2], &Wf) || !get_i32(env, a[3], &Hf) || !get_i32(env, a[4], &F)) return NULL;
+    uint8_t *to = (uint8_t *)get_typed(env, a[5], napi_uint8_array, &n_t, "to"); if (!to) return NULL;
+    if (!get_i32(env, a[6], &Wt) || !get_i32(env, a[7], &Ht) || !get_i32(env, a[8], &S) || !get_i32(env, a[9], &ch) || !get_i32(env, a[10], &levels)) return NULL;
+    if (Wf < 1 || Hf < 1 || Wt < 1 || Ht < 1 || Wf > 32768 || Hf > 32768 || Wt > 32768 || Ht > 32768 || F < 1 || F > 4096 || S < 1 || S > F || (ch != 1 && ch != 4))
+        return throw_str(env, "hgwarp: alignBegin: sizes, frame counts or channels are out of range");
+    const size_t fb = (size_t)Wf * Hf * ch, tb = (size_t)Wt * Ht * ch;
+    if (n_f != fb * F || n_t != tb * S) return throw_str(env, "hgwarp: alignBegin: from / to must hold nFrames resp. nToSets planes of W x H x channels bytes");
+    if (levels < 1 || levels > 31 || levels > hg_pyramid_levels(Wf, Hf) || levels > hg_pyramid_levels(Wt, Ht)) return throw_str(env, "hgwarp: alignBegin: levels must exist on both sides");
+    align_job_t *j = (align_job_t *)calloc(1, sizeof *j);
+    if (!j) return throw_str(env, "hgwarp: out of memory");
+    j->Wf = Wf; j->Hf = Hf; j->F = F; j->Wt = Wt; j->Ht = Ht; j->S = S; j->channels = ch; j->levels = levels;
+    if (hg_pyramid_layout(Wf, Hf, HG_ELEM_U8, ch, levels, j->foffs, &j->fpyr_bytes) != HG_OK || hg_pyramid_layout(Wt, Ht, HG_ELEM_U8, ch, levels, j->toffs, &j->tpyr_bytes) != HG_OK) {
+        free(j); return throw_str(env, "hgwarp: alignBegin: hg_pyramid_layout failed");
+    }
+#define ALIGN_PAD(b) (((size_t)(b) + 255) & ~(size_t)255)
+    j->o_from = 0; j->o_to = j->o_from + ALIGN_PAD(fb * F); j->o_fpyr = j->o_to + ALIGN_PAD(tb * S); j->o_tpyr = j->o_fpyr + ALIGN_PAD(j->fpyr_bytes * F);
+    j->o_mats = j->o_tpyr + ALIGN_PAD(j->tpyr_bytes * S); j->o_info = j->o_mats + ALIGN_PAD((size_t)F * 64);
+    const size_t total = j->o_info + ALIGN_PAD((size_t)F * 48);
+#undef ALIGN_PAD
+    int rc = hg_device_alloc(h->ctx, total, &j->d);
+    const char *what = "hg_device_alloc";
+    uint8_t *b = (uint8_t *)j->d;
+    if (rc == HG_OK) { what = "hg_copy_to_device"; rc = hg_copy_to_device(h->ctx, b + j->o_from, from, fb * F); }
+    if (rc == HG_OK) rc = hg_copy_to_device(h->ctx, b + j->o_to, to, tb * S);
+    if (rc == HG_OK && levels > 1) {
+        what = "hg_pyramid_build_device";
+        rc = hg_pyramid_build_device(h->ctx, b + j->o_from, Wf, Hf, F, fb, HG_ELEM_U8, ch, levels, b + j->o_fpyr, j->fpyr_bytes);
+        if (rc == HG_OK) rc = hg_pyramid_build_device(h->ctx, b + j->o_to, Wt, Ht, S, tb, HG_ELEM_U8, ch, levels, b + j->o_tpyr, j->tpyr_bytes);
+    }
+    if (rc != HG_OK) { napi_value e = throw_hg(env, h->ctx, what, rc); if (j->d) hg_device_free(h->ctx, j->d); free(j); return e; }
+    napi_value ext;
+    if (napi_create_external(env, j, align_job_finalize, NULL, &ext) != napi_ok) { hg_device_free(h->ctx, j->d); free(j); return throw_str(env, "hgwarp: cannot wrap the alignment job"); }
+    return ext;
+}
+
+static align_job_t *get_align_job(napi_env env, napi_value v)
+{
+    void *p = NULL;
+    if (napi_get_value_external(env, v, &p) != napi_ok || !p || !((align_job_t *)p)->d) { throw_str(env, "hgwarp: invalid or ended alignment job"); return NULL; }
+    return (align_job_t *)p;
+}
+
+static napi_value fn_align_level(napi_env env, napi_callback_info info)
+{
+    napi_value a[11];
+    if (!get_args(env, info, 11, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    align_job_t *j = get_align_job(env, a[1]); if (!j) return NULL;
+    int kind, level, step, photo, n_iter, min_valid; double eps; size_t n_r = 0, n_m = 0;
+    if (!get_i32(env, a[2], &kind) || !get_i32(env, a[3], &level)) return NULL;
+    int32_t *rect = (int32_t *)get_typed(env, a[4], napi_int32_array, &n_r, "rect"); if (!rect) return NULL;
+    if (!get_i32(env, a[5], &step) || !get_i32(env, a[6], &photo) || !get_i32(env, a[7], &n_iter)) return NULL;
+    if (napi_get_value_double(env, a[8], &eps) != napi_ok) return throw_str(env, "hgwarp: eps must be a number");
+    if (!get_i32(env, a[9], &min_valid)) return NULL;
+    double *m = (double *)get_typed(env, a[10], napi_float64_array, &n_m, "matrices"); if (!m) return NULL;
+    const size_t F = (size_t)j->F;
+    if (n_r != 4 || n_m != F * 8 || level < 0 || level >= j->levels) return throw_str(env, "hgwarp: alignLevel: rect must hold 4 numbers, matrices 8 per frame, level must exist");
+    int Wf = j->Wf, Hf = j->Hf, Wt = j->Wt, Ht = j->Ht;
+    for (int k = 0; k < level; k++) { Wf = (Wf + 1) >> 1; Hf = (Hf + 1) >> 1; Wt = (Wt + 1) >> 1; Ht = (Ht + 1) >> 1; }
+    void *p_m, *p_st, *p_up, *p_nv, *p_rms, *p_g;
+    napi_value out, v_m, v_st, v_up, v_nv, v_rms, v_g;
+    if (!(v_m = make_typed(env, napi_float64_array, F * 8, 8, &p_m)) || !(v_st = make_typed(env, napi_int32_array, F, 4, &p_st)) ||
+        !(v_up = make_typed(env, napi_int32_array, F, 4, &p_up)) || !(v_nv = make_typed(env, napi_int32_array, F * 2, 4, &p_nv)) ||
+        !(v_rms = make_typed(env, napi_float64_array, F * 2, 8, &p_rms)) || !(v_g = make_typed(env, napi_float64_array, F * 2, 8, &p_g))) return NULL;
+    NAPI_OK(napi_create_object(env, &out));
+    NAPI_OK(napi_set_named_property(env, out, "matrices", v_m)); NAPI_OK(napi_set_named_property(env, out, "status", v_st));
+    NAPI_OK(napi_set_named_property(env, out, "updates", v_up)); NAPI_OK(napi_set_named_property(env, out, "nValid", v_nv));
+    NAPI_OK(napi_set_named_property(env, out, "rms", v_rms)); NAPI_OK(napi_set_named_property(env, out, "gains", v_g));
+    uint8_t *b = (uint8_t *)j->d;
+    const size_t px = (size_t)j->channels;
+    const uint8_t *d_from = level == 0 ? b + j->o_from : b + j->o_fpyr + j->foffs[level], *d_to = level == 0 ? b + j->o_to : b + j->o_tpyr + j->toffs[level];
+    const size_t fs = level == 0 ? (size_t)j->Wf * j->Hf * px : j->fpyr_bytes, ts = level == 0 ? (size_t)j->Wt * j->Ht * px : j->tpyr_bytes;
+    HG_CALL(h->ctx, "hg_copy_to_device", hg_copy_to_device(h->ctx, b + j->o_mats, m, F * 64));
+    HG_CALL(h->ctx, "hg_align_refine_frames_device", hg_align_refine_frames_device(h->ctx, kind, d_from, Wf, Hf, j->F, fs, d_to, Wt, Ht, j->S, ts, j->channels,
+            rect[0], rect[1], rect[2], rect[3], step, photo, n_iter, eps, min_valid, (const double *)(b + j->o_mats), (double *)(b + j->o_mats), b + j->o_info, NULL));
+    HG_CALL(h->ctx, "hg_copy_to_host", hg_copy_to_host(h->ctx, p_m, b + j->o_mats, F * 64));
+    uint8_t *raw = (uint8_t *)malloc(F * 48);
+    if (!raw) return throw_str(env, "hgwarp: out of memory");
+    int rc = hg_copy_to_host(h->ctx, raw, b + j->o_info, F * 48);
+    if (rc != HG_OK) { free(raw); return throw_hg(env, h->ctx, "hg_copy_to_host", rc); }
+    for (size_t f = 0; f < F; f++) {
+        const uint8_t *r = raw + f * 48;
+        memcpy((int32_t *)p_st + f, r, 4); memcpy((int32_t *)p_up + f, r + 4, 4); memcpy((int32_t *)p_nv + 2 * f, r + 8, 8);
+        memcpy((double *)p_rms + 2 * f, r + 16, 16); memcpy((double *)p_g + 2 * f, r + 32, 16);
+    }
+    free(raw);
+    return out;
+}
+
+static napi_value fn_align_scale_matrix(napi_env env, napi_callback_info info)
+{
+    napi_value a[4];
+    if (!get_args(env, info, 4, a)) return NULL;
+    int kind, li, lo; size_t n = 0;
+    if (!get_i32(env, a[0], &kind)) return NULL;
+    double *m = (double *)get_typed(env, a[1], napi_float64_array, &n, "matrices"); if (!m) return NULL;
+    if (!get_i32(env, a[2], &li) || !get_i32(env, a[3], &lo)) return NULL;
+    if (n % 8 != 0) return throw_str(env, "hgwarp: alignScaleMatrix: matrices must hold 8 numbers per frame");
+    void *p; napi_value out;
+    if (!(out = make_typed(env, napi_float64_array, n, 8, &p))) return NULL;
+    for (size_t f = 0; f < n / 8; f++) {
+        const double *r = m + 8 * f; double *o = (double *)p + 8 * f;
+        int fin = 1;
+        for (int k = 0; k < 8; k++) fin = fin && r[k] - r[k] == 0.0;
+        if (!fin) { memcpy(o, r, 64); continue; }
+        HG_CALL(NULL, "hg_align_scale_matrix", hg_align_scale_matrix(kind, r, li, lo, o));
+    }
+    return out;
+}
+
+static napi_value fn_align_end(napi_env env, napi_callback_info info)
+{
+    napi_value a[2];
+    if (!get_args(env, info, 2, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    void *p = NULL;
+    if (napi_get_value_external(env, a[1], &p) != napi_ok || !p) return throw_str(env, "hgwarp: invalid alignment job");
+    align_job_t *j = (align_job_t *)p;
+    if (j->d) { void *d = j->d; j->d = NULL; HG_CALL(h->ctx, "hg_device_free", hg_device_free(h->ctx, d)); }
+    napi_value u;
+    NAPI_OK(napi_get_undefined(env, &u));
+    return u;
+}
+
 /* matchDescriptors(handle, kind, descBytes, stride, query, nQuery, countsQ, train, nTrain, countsT, ratio, maxDistance, crossCheck,
  * queryPoints | null, trainPoints | null): the accepted nearest-neighbour pairs of every frame (hg_match_descriptors_frames_device).  query:
  * Uint8Array of F x nQuery x stride, F = countsQ.length; train: Uint8Array of S x nTrain x stride, S = countsT.length; the points: Float32Array
@@ -2029,6 +2174,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "pointsInverseGeometric", fn_points_inverse_geometric }, { "pointsInversePiecewise", fn_points_inverse_piecewise },
         { "pointsForwardGeometric", fn_points_forward_geometric }, { "pointsForwardPiecewise", fn_points_forward_piecewise },
         { "fitMatches", fn_fit_matches },
+        { "alignBegin", fn_align_begin }, { "alignLevel", fn_align_level }, { "alignScaleMatrix", fn_align_scale_matrix }, { "alignEnd", fn_align_end },
         { "matchDescriptors", fn_match_descriptors },
         { "detectAndDescribe", fn_detect_describe },
         { "solveAffineTriangles", fn_solve_affine_triangles }, { "warpInversePiecewiseState", fn_warp_inverse_piecewise_state },

@@ -32,6 +32,11 @@ CUBIC_CATMULL_ROM, CUBIC_MITCHELL, CUBIC_BSPLINE = (0.0, 0.5), (1 / 3, 1 / 3), (
 DESC_BITS, DESC_U8 = 0, 1
 # the keypoint detector (hg_detect_describe_frames_device): the distance a keypoint keeps from the borders, the bytes of a descriptor, the direction bins
 DETECT_MARGIN, DETECT_DESC_BYTES, DETECT_BINS = 16, 32, 32
+# refining transforms on the pixels (hg_align_refine_frames_device): the status of a frame, the doubles of a frame's record of sums
+ALIGN_CONVERGED, ALIGN_MAX_ITER, ALIGN_TOO_FEW, ALIGN_SINGULAR, ALIGN_WORSE, ALIGN_BAD_INPUT = 0, 1, 2, 3, 4, 5
+ALIGN_SUMS = 66
+ALIGN_INFO = np.dtype([("status", np.int32), ("updates", np.int32), ("n_valid_first", np.int32), ("n_valid_last", np.int32),
+                       ("rms_first", np.float64), ("rms_last", np.float64), ("gain", np.float64), ("bias", np.float64)])
 
 # every symbol include/hgwarp.h declares (tests check that the built library exports all of them)
 EXPORTS = [
@@ -66,6 +71,7 @@ EXPORTS = [
     "hg_mosaic_frames_device", "hg_mosaic_overlap_stats_device", "hg_mosaic_solve_gains", "hg_mosaic_frames_gain_device",
     "hg_remap_bicubic_frames_device",
     "hg_fit_sample_indices", "hg_fit_matches_frames_device",
+    "hg_align_scale_matrix", "hg_align_refine_frames_device",
     "hg_match_descriptors_frames_device",
     "hg_detect_layout", "hg_describe_pattern", "hg_detect_describe_frames_device",
     "hg_mosaic_multiband_layout", "hg_mosaic_multiband_device",
@@ -186,6 +192,8 @@ def lib():
                                            C.POINTER(C.c_float), vp, sz]),
         "hg_fit_sample_indices": (i, [i, C.c_uint32, i, C.POINTER(C.c_int32), i, i, C.POINTER(C.c_int32)]),
         "hg_fit_matches_frames_device": (i, [vp, i, vp, i, C.POINTER(C.c_int32), i, d, i, C.c_uint32, vp, i, vp, vp, vp, vp, vp]),
+        "hg_align_scale_matrix": (i, [i, f64p, i, i, f64p]),
+        "hg_align_refine_frames_device": (i, [vp, i, vp, i, i, i, sz, vp, i, i, i, sz, i, i, i, i, i, i, i, i, d, i, vp, vp, vp, vp]),
         "hg_match_descriptors_frames_device": (i, [vp, i, i, sz, vp, i, C.POINTER(C.c_int32), i, vp, i, C.POINTER(C.c_int32), i, d, C.c_uint32, i,
                                                    vp, vp, vp, vp, vp, vp]),
         "hg_detect_layout": (i, [i, i, i, i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -403,6 +411,70 @@ def fit_sample_indices(kind, seed, counts, n_points, n_hyp):
     _check(lib().hg_fit_sample_indices(int(kind), int(seed) & 0xffffffff, F, p, int(n_points), int(n_hyp),
                                        out.ctypes.data_as(C.POINTER(C.c_int32)) if out.size else None))
     return out
+
+
+def align_scale_matrix(kind, m, level_in, level_out):
+    """A transform between two planes, both at pyramid level level_in, converted to level_out (hg_align_scale_matrix): 8 doubles in the fit's
+    layouts.  A position at level k is x_k = (x_0 + 0.5) 2^-k - 0.5."""
+    a = np.ascontiguousarray(m, dtype=np.float64).ravel()
+    assert a.size == 8, "a matrix is 8 doubles"
+    out = np.empty(8, np.float64)
+    _check(lib().hg_align_scale_matrix(int(kind), a.ctypes.data_as(C.POINTER(C.c_double)), int(level_in), int(level_out),
+                                       out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def align_refine_coarse_to_fine(ctx, kind, d_from, wf, hf, n_frames, d_to, wt, ht, n_to_sets, channels, mats, levels, rect=None, step=2,
+                                photometric=True, n_iter=10, eps=0.01, min_valid=None, from_stride_bytes=None, to_stride_bytes=None):
+    """Context.align_refine_frames_device from pyramid level levels - 1 down to level 0: both pyramids are built on the device
+    (pyramid_build_device), every level is refined from the result of the coarser one, and only the matrices travel -- they are converted
+    between levels on the host (align_scale_matrix).  mats: (n_frames, 8) doubles at level 0; rect: (rx, ry, rw, rh) at level 0 (None: the
+    whole FROM plane), shrunk to the pixels of each level whose centres lie inside it; the same step, n_iter, eps and min_valid (None: P)
+    at every level.  A frame a level fails keeps that level's input (the call's rule), so the walk goes on from there.
+    Returns (mats (n_frames, 8), info of level 0 as ALIGN_INFO records)."""
+    F, levels = int(n_frames), int(levels)
+    mats = np.ascontiguousarray(mats, dtype=np.float64).reshape(F, 8).copy()
+    assert 1 <= levels <= min(pyramid_levels(wf, hf), pyramid_levels(wt, ht)), "levels must exist on both sides"
+    P = (8 if int(kind) == HG_PROJECTIVE else 6) + (2 if photometric else 0)
+    min_valid = P if min_valid is None else int(min_valid)
+    rect = (0, 0, int(wf), int(hf)) if rect is None else tuple(int(v) for v in rect)
+    fs = int(wf) * int(hf) * int(channels) if from_stride_bytes is None else int(from_stride_bytes)
+    ts = int(wt) * int(ht) * int(channels) if to_stride_bytes is None else int(to_stride_bytes)
+    fo, f_total = pyramid_layout(wf, hf, ELEM_U8, channels, levels)
+    to, t_total = pyramid_layout(wt, ht, ELEM_U8, channels, levels)
+    d_fp = ctx.alloc(max(f_total * F, 256))
+    d_tp = ctx.alloc(max(t_total * int(n_to_sets), 256))
+    d_m = ctx.alloc(F * (64 + 48))
+    d_i = d_m + F * 64
+    try:
+        if levels > 1:
+            ctx.pyramid_build_device(d_from, wf, hf, F, fs, ELEM_U8, channels, levels, d_fp, f_total)
+            ctx.pyramid_build_device(d_to, wt, ht, int(n_to_sets), ts, ELEM_U8, channels, levels, d_tp, t_total)
+        info = np.zeros(F, ALIGN_INFO)
+        fsz, tsz = [(int(wf), int(hf))], [(int(wt), int(ht))]
+        for _ in range(1, levels):                                            # (a level halves the one below, rounding up)
+            fsz.append(((fsz[-1][0] + 1) >> 1, (fsz[-1][1] + 1) >> 1))
+            tsz.append(((tsz[-1][0] + 1) >> 1, (tsz[-1][1] + 1) >> 1))
+        for k in range(levels - 1, -1, -1):
+            cur = np.stack([align_scale_matrix(kind, m, 0, k) if np.isfinite(m).all() else m for m in mats]) if F else mats
+            (lw, lh), (tw, th) = fsz[k], tsz[k]
+            # the level-k pixels whose centres, x_0 = (x_k + 0.5) 2^k - 0.5, lie inside the rectangle
+            lo = lambda a: -((-(2 * a + 1 - (1 << k))) // (2 << k))
+            hi = lambda b: (2 * b - 1 - (1 << k)) // (2 << k)
+            x0, y0 = max(lo(rect[0]), 0), max(lo(rect[1]), 0)
+            x1, y1 = min(hi(rect[0] + rect[2]), lw - 1), min(hi(rect[1] + rect[3]), lh - 1)
+            ctx.to_device(d_m, cur)
+            ctx.align_refine_frames_device(kind, d_from if k == 0 else d_fp + fo[k], lw, lh, F, d_to if k == 0 else d_tp + to[k], tw, th, n_to_sets, channels,
+                                           (x0, y0, x1 - x0 + 1, y1 - y0 + 1), d_m, d_m, d_i, step=step, photometric=photometric, n_iter=n_iter, eps=eps,
+                                           min_valid=min_valid, from_stride_bytes=fs if k == 0 else f_total, to_stride_bytes=ts if k == 0 else t_total)
+            ctx.sync()
+            got = ctx.to_host(d_m, F * 64).view(np.float64).reshape(F, 8)
+            info = ctx.to_host(d_i, F * 48).view(ALIGN_INFO).copy()
+            mats = np.stack([align_scale_matrix(kind, m, k, 0) if np.isfinite(m).all() else m for m in got]) if F else got
+        return mats, info
+    finally:
+        for p in (d_fp, d_tp, d_m):
+            ctx.free(p)
 
 
 def detect_layout(W, H, cell, per_cell):
@@ -900,6 +972,23 @@ class Context:
         self._c(lib().hg_fit_matches_frames_device(self._h, int(kind), vp(d_matches), int(n_points), p, int(n_frames), float(threshold), int(n_hyp),
                                                    int(seed) & 0xffffffff, vp(d_samples), 1 if refit else 0, vp(d_mats), vp(d_min_mats), vp(d_counts),
                                                    vp(d_best), vp(d_mask)))
+
+    def align_refine_frames_device(self, kind, d_from, wf, hf, n_frames, d_to, wt, ht, n_to_sets, channels, rect, d_mats_in, d_mats_out, d_info,
+                                   step=2, photometric=True, n_iter=10, eps=0.01, min_valid=None, d_sums=0, from_stride_bytes=None, to_stride_bytes=None):
+        """hg_align_refine_frames_device: the transforms of n_frames frames (8 doubles each at d_mats_in, FROM -> TO, the fit's layouts) refined
+        on the pixels -- Gauss-Newton on the intensity difference between the u8 FROM plane of every frame (wf x hf x channels) and TO plane
+        f % n_to_sets (wt x ht), over the FROM pixels of rect = (rx, ry, rw, rh) taken every `step`; with photometric a gain and a bias are
+        fitted too.  At most n_iter updates, stopping when the rectangle's corners move less than eps TO pixels; min_valid (None: P) valid
+        samples are needed.  d_mats_out (may be d_mats_in) gets the matrices, d_info one ALIGN_INFO record per frame, d_sums (0: not wanted)
+        ALIGN_SUMS doubles per frame: the sums of the first pass.  Asynchronous; a local refinement: start within a few pixels."""
+        vp = lambda v: C.c_void_p(int(v) or None)
+        P = (8 if int(kind) == HG_PROJECTIVE else 6) + (2 if photometric else 0)
+        fs = int(wf) * int(hf) * int(channels) if from_stride_bytes is None else int(from_stride_bytes)
+        ts = int(wt) * int(ht) * int(channels) if to_stride_bytes is None else int(to_stride_bytes)
+        rx, ry, rw, rh = [int(v) for v in rect]
+        self._c(lib().hg_align_refine_frames_device(self._h, int(kind), vp(d_from), int(wf), int(hf), int(n_frames), fs, vp(d_to), int(wt), int(ht),
+                                                    int(n_to_sets), ts, int(channels), rx, ry, rw, rh, int(step), int(photometric), int(n_iter), float(eps),
+                                                    P if min_valid is None else int(min_valid), vp(d_mats_in), vp(d_mats_out), vp(d_info), vp(d_sums)))
 
     def match_descriptors_frames_device(self, kind, desc_bytes, stride, d_query, n_query, counts_q, n_frames, d_train, n_train, counts_t, n_train_sets,
                                         d_counts, ratio=0.8, max_distance=0xffffffff, cross_check=False, d_query_pts=0, d_train_pts=0, d_matches=0,

@@ -462,6 +462,95 @@ class Homography {
     }
 
     /**
+     * The transforms fitMatches() returns, refined on the PIXELS of the two pictures (not part of the reference;
+     * hg_align_refine_frames_device in include/hgwarp.h has the rules): Gauss-Newton on the intensity difference between every frame
+     * (FROM) and the picture it was matched against (TO), started from `matrices`.  A local refinement: it needs a start within a few
+     * pixels, or levels > 1, which walks both pictures' mip pyramids from the coarsest level down -- the planes and pyramids stay on the
+     * device, only the matrices travel and are converted between levels (hg_align_scale_matrix).
+     * fromImages: an array of F Uint8Arrays / Uint8ClampedArrays of width x height x channels bytes; toImages: an array of S of them
+     * (toWidth x toHeight), 1 <= S <= F: frame f is aligned to picture f % S; matrices: Float64Array(8 F) or an array of 8 F numbers,
+     * FROM -> TO, what fitMatches() returns.
+     * options: { width, height, toWidth = width, toHeight = height, channels = 4 (or 1), transform: 'projective' (default) | 'affine',
+     *            rect: [x, y, w, h] of the FROM picture (default: all of it), step = 2, iterations = 10, eps = 0.01 (pixels),
+     *            photometric = true (fit a gain and a bias too), minValid (default: the number of parameters), levels = 1 }.
+     * Returns { matrices: Float64Array(8 F) -- a frame that could not be refined keeps its input --, status: Int32Array(F) (0 converged,
+     *           1 ran all iterations, 2 too few samples, 3 singular, 4 worse, 5 bad input; of level 0), updates: Int32Array(F),
+     *           rms: Float64Array(F) (the final one), gains: Float64Array(2 F) (gain, bias per frame) }.
+     * Needs no image and changes no state of the instance.  Throws a bare string for a bad option or a picture of the wrong size.
+     */
+    refineAlignment(fromImages, toImages, matrices, options = {}) {
+        if (options === null || options === undefined) options = {};
+        const isInt = (v, lo, hi) => Number.isInteger(v) && v >= lo && v <= hi;
+        const transform = options.transform === undefined ? 'projective' : options.transform;
+        if (transform !== 'projective' && transform !== 'affine') throw ("refineAlignment: options.transform must be 'projective' or 'affine'");
+        const { width, height } = options;
+        if (!isInt(width, 1, 32768) || !isInt(height, 1, 32768)) throw ("refineAlignment: options.width and options.height must be integers in 1..32768");
+        const toWidth = options.toWidth === undefined ? width : options.toWidth, toHeight = options.toHeight === undefined ? height : options.toHeight;
+        if (!isInt(toWidth, 1, 32768) || !isInt(toHeight, 1, 32768)) throw ("refineAlignment: options.toWidth and options.toHeight must be integers in 1..32768");
+        const channels = options.channels === undefined ? 4 : options.channels;
+        if (channels !== 1 && channels !== 4) throw ("refineAlignment: options.channels must be 1 or 4");
+        const step = options.step === undefined ? 2 : options.step;
+        if (!isInt(step, 1, 64)) throw ("refineAlignment: options.step must be an integer in 1..64");
+        const iterations = options.iterations === undefined ? 10 : options.iterations;
+        if (!isInt(iterations, 0, 64)) throw ("refineAlignment: options.iterations must be an integer in 0..64");
+        const eps = options.eps === undefined ? 0.01 : options.eps;
+        if (typeof eps !== 'number' || !Number.isFinite(eps) || eps < 0) throw ("refineAlignment: options.eps must be a finite number >= 0");
+        const photometric = options.photometric === undefined ? true : !!options.photometric;
+        const kind = transform === 'projective' ? 1 : 0;
+        const P = (kind === 1 ? 8 : 6) + (photometric ? 2 : 0);
+        const minValid = options.minValid === undefined ? P : options.minValid;
+        if (!isInt(minValid, P, 0x7fffffff)) throw ("refineAlignment: options.minValid must be an integer >= " + P + " (the number of parameters)");
+        const levels = options.levels === undefined ? 1 : options.levels;
+        const sizes = [[width, height, toWidth, toHeight]];
+        if (!isInt(levels, 1, 31)) throw ("refineAlignment: options.levels must be an integer >= 1");
+        for (let k = 1; k < levels; k++) {
+            const [w, h, tw, th] = sizes[k - 1];
+            if (Math.max(w, h) === 1 || Math.max(tw, th) === 1) throw ("refineAlignment: options.levels must exist in both pictures' pyramids");
+            sizes.push([(w + 1) >> 1, (h + 1) >> 1, (tw + 1) >> 1, (th + 1) >> 1]);
+        }
+        const rect = options.rect === undefined ? [0, 0, width, height] : Array.from(options.rect);
+        if (rect.length !== 4 || !rect.every((v) => Number.isInteger(v)) || rect[0] < 0 || rect[1] < 0 || rect[2] < 1 || rect[3] < 1 || rect[0] + rect[2] > width || rect[1] + rect[3] > height)
+            throw ("refineAlignment: options.rect must be [x, y, w, h], non-empty and inside the FROM picture");
+        if (!Array.isArray(fromImages) || !Array.isArray(toImages)) throw ("refineAlignment: fromImages and toImages must be arrays of pictures");
+        const F = fromImages.length, S = toImages.length;
+        if (F > 4096) throw ("refineAlignment: at most 4096 frames");
+        if (F > 0 && (S < 1 || S > F)) throw ("refineAlignment: toImages must hold 1..fromImages.length pictures");
+        const pack = (imgs, w, h, name) => {
+            const n = w * h * channels, out = new Uint8Array(imgs.length * n);
+            imgs.forEach((im, f) => {
+                if (!(im instanceof Uint8Array) && !(im instanceof Uint8ClampedArray)) throw ("refineAlignment: " + name + " " + f + " must be a Uint8Array or a Uint8ClampedArray");
+                if (im.length !== n) throw ("refineAlignment: " + name + " " + f + " must hold width x height x channels bytes");
+                out.set(im, f * n);
+            });
+            return out;
+        };
+        const from = pack(fromImages, width, height, 'fromImages'), to = pack(toImages, toWidth, toHeight, 'toImages');
+        if (!(matrices instanceof Float64Array) && !Array.isArray(matrices)) throw ("refineAlignment: matrices must be a Float64Array or an array of 8 numbers per frame");
+        let cur = Float64Array.from(matrices instanceof Float64Array ? matrices : matrices.flat(Infinity));
+        if (cur.length !== 8 * F) throw ("refineAlignment: matrices must hold 8 numbers per frame");
+        if (F === 0) return { matrices: new Float64Array(0), status: new Int32Array(0), updates: new Int32Array(0), rms: new Float64Array(0), gains: new Float64Array(0) };
+        // the level-k pixels whose centres, x_0 = (x_k + 0.5) 2^k - 0.5, lie inside the rectangle
+        const levelRect = (k, lw, lh) => {
+            const lo = (a) => Math.ceil((2 * a + 1 - 2 ** k) / 2 ** (k + 1)), hi = (b) => Math.floor((2 * b - 1 - 2 ** k) / 2 ** (k + 1));
+            const x0 = Math.max(lo(rect[0]), 0), y0 = Math.max(lo(rect[1]), 0);
+            const x1 = Math.min(hi(rect[0] + rect[2]), lw - 1), y1 = Math.min(hi(rect[1] + rect[3]), lh - 1);
+            return Int32Array.from([x0, y0, x1 - x0 + 1, y1 - y0 + 1]);
+        };
+        const job = this._native.alignBegin(this._ctx, from, width, height, F, to, toWidth, toHeight, S, channels, levels);
+        try {
+            let r = null;
+            for (let k = levels - 1; k >= 0; k--) {
+                const atK = k === 0 ? cur : this._native.alignScaleMatrix(kind, cur, 0, k);
+                r = this._native.alignLevel(this._ctx, job, kind, k, levelRect(k, sizes[k][0], sizes[k][1]), step, photometric ? 1 : 0, iterations, eps, minValid, atK);
+                cur = k === 0 ? r.matrices : this._native.alignScaleMatrix(kind, r.matrices, k, 0);
+            }
+            return { matrices: cur, status: r.status, updates: r.updates, rms: Float64Array.from({ length: F }, (_, f) => r.rms[2 * f + 1]), gains: r.gains };
+        } finally {
+            this._native.alignEnd(this._ctx, job);
+        }
+    }
+
+    /**
      * The matches fitMatches() starts from: per frame the nearest train descriptor of every query descriptor, kept when it passes Lowe's
      * ratio test, the distance cap and, if asked for, the cross-check (not part of the reference; hg_match_descriptors_frames_device in
      * include/hgwarp.h has the rules, all of them exact).  querySets: an array of F Uint8Arrays of count_f x descBytes bytes; trainSets: an

@@ -40,7 +40,8 @@ extern "C" {
                                    the bicubic remap by that of hg_remap_bicubic_frames_device, exposure gains of a mosaic by that of
                                    hg_mosaic_overlap_stats_device, fitting transforms to matches by that of hg_fit_matches_frames_device);
                                    matching descriptors by the presence of hg_match_descriptors_frames_device, keypoints by the presence of
-                                   hg_detect_describe_frames_device, multi-band mosaics by the presence of hg_mosaic_multiband_device */
+                                   hg_detect_describe_frames_device, multi-band mosaics by the presence of hg_mosaic_multiband_device, refining transforms
+                                   on the pixels by the presence of hg_align_refine_frames_device */
 
 enum {
     HG_OK = 0,
@@ -812,6 +813,96 @@ int hg_fit_sample_indices(int kind, uint32_t seed, int n_frames, const int32_t *
 int hg_fit_matches_frames_device(hg_ctx *ctx, int kind, const void *d_matches, int n_points, const int32_t *counts, int n_frames,
                                  double threshold, int n_hyp, uint32_t seed, const int32_t *d_samples, int refit,
                                  double *d_mats, double *d_min_mats, int32_t *d_counts, int32_t *d_best, uint8_t *d_mask);
+
+/* ------------------------------------------------------------------------------------------------ refining transforms on the pixels
+ * The detector's keypoints are integer pixel positions, so a transform fitted to a few dozen matches is good to a fraction of a pixel, not
+ * better.  hg_align_refine_frames_device refines such a transform on the PIXELS of the two pictures: direct (photometric) alignment, Gauss-
+ * Newton on the intensity difference over a grid of samples (Lucas-Kanade with an affine or projective warp), started from the matrix the fit
+ * gave.  Not part of the reference.  It is a LOCAL refinement: it needs a start within a few pixels, or a walk over pyramid levels that
+ * brings it there (hg_align_scale_matrix).
+ * PLANES.  u8, rows tight, `channels` 1 or 4; of 4 channels the luma (77 R + 150 G + 29 B + 128) >> 8 is used (the detector's), alpha is
+ * ignored.  Frame f has its own FROM plane at d_from + f * from_stride_bytes (Wf x Hf) and reads TO plane f % n_to_sets at d_to + (f %
+ * n_to_sets) * to_stride_bytes (Wt x Ht), the rule the matcher gives train sets.  The matrix of frame f maps FROM positions to TO positions,
+ * in the layouts hg_fit_matches_frames_device writes: projective h0..h7 with h8 == 1, affine m0..m5 in the first six of eight slots (x' =
+ * m0 x + m2 y + m4, y' = m1 x + m3 y + m5).  For a chain that matched frames (query) against a keyframe (train), FROM = the frame, TO = the
+ * keyframe, and the fit's d_mats is d_mats_in as it stands.
+ * SAMPLES.  The FROM pixels (x, y) = (rx + i step, ry + j step), i = 0 .. ceil(rw / step) - 1, j = 0 .. ceil(rh / step) - 1; sample number
+ * s = j * ceil(rw / step) + i.  a = the luma there, as a double.
+ * NORMALISATION.  Each side uses c = ((W - 1) / 2, (H - 1) / 2) and s = 2 / max(W, H): x' = (x - cx) s, y' = (y - cy) s on the FROM side,
+ * likewise u', v' with the TO side's c and s.  With M the input as a 3 x 3 matrix, A = M T_from^-1 (columns 0 and 1 divided by s_from,
+ * column 2 = (col0 cx + col1 cy) + col2), B = T_to A (row 0 = (row0 - cx_to row2) s_to, row 1 likewise with cy_to, row 2 as it is), H' = B
+ * divided through by its last entry.  Gauss-Newton runs on the entries of H' (affine: its six); the way back is M = T_to^-1 H' T_from as
+ * the fit's refit writes it (column 2 = (h2 - h0 (s cx)) - h1 (s cy); row 0 = row0 / s_to + cx_to row2), divided through by its last entry.
+ * ONE PASS over the iterate H' (with the photometric terms g, b; they start at 1, 0), all in f64 with IEEE division, contraction off,
+ * every product and sum rounded on its own, sums from left to right.  For the sample (x', y'):
+ *   1. D = (h6' x' + h7' y') + 1; 1 for affine.
+ *   2. u' = ((h0' x' + h1' y') + h2') / D, v' = ((h3' x' + h4' y') + h5') / D; u = u' / s_to + cx_to, v = v' / s_to + cy_to (TO pixels).
+ *   3. The sample is VALID iff u and v are finite, D > 0, 1 <= u < Wt - 2 and 1 <= v < Ht - 2: no tap below leaves the plane.
+ *   4. x0 = floor(u), fx = u - x0 (likewise y0, fy).  blend(p00, p01, p10, p11) = ((p00 (1 - fx) + p01 fx) (1 - fy)) + ((p10 (1 - fx) + p11 fx)
+ *      fy), p = the TO luma (for RGBA the integer luma of each tap first).  I = blend of the taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1),
+ *      (x0 + 1, y0 + 1).
+ *   5. dx = (I(u + 1, v) - I(u - 1, v)) / 2: the same blend, the same fractions, the taps one column to the right resp. left; dy likewise
+ *      with rows: 12 distinct taps.  jx = (dx / s_to) / D, jy = (dy / s_to) / D (the derivative with respect to u', v', over D).
+ *   6. r = a - I with photometric == 0, r = ((g a) + b) - I with photometric == 1.
+ *   7. The Jacobian row.  Projective: [jx x', jx y', jx, jy x', jy y', jy, w x', w y'] with w = -((jx u') + (jy v')).  Affine, in the
+ *      affine slot order m0..m5: [jx x', jy x', jx y', jy y', jx, jy].  With photometric [-a, -1] is appended.  P = 6, 8 or 10.
+ *   8. Per frame the pass produces n_valid (an integer) and the sums over the valid samples of: J_p J_q for p <= q, row by row of the upper
+ *      triangle (P (P + 1) / 2 values), J_p r (P values), r r (one): P (P + 1) / 2 + P + 1 <= HG_ALIGN_SUMS doubles, in that order.
+ * UPDATE.  J^T J delta = J^T r is solved by Gaussian elimination with partial pivoting in one lane (the refit's routine); delta_k is added
+ * to parameter k (projective h0'..h7'; affine m0'..m5', m0' = h0', m1' = h3', m2' = h1', m3' = h4', m4' = h2', m5' = h5'; then g, b).
+ * rms = sqrt(sum r r / n_valid).
+ * ITERATION.  Pass 0 evaluates the input.  After update k (k = 1, 2, ...) the DISPLACEMENT is the largest distance, in TO pixels, between
+ * the images (steps 1 and 2) of the four corners (rx, ry), (rx + rw - 1, ry), (rx, ry + rh - 1), (rx + rw - 1, ry + rh - 1) of the sample
+ * rectangle under the iterate before and after it.  The frame stops iterating when displacement < eps (HG_ALIGN_CONVERGED) or after n_iter
+ * updates (HG_ALIGN_MAX_ITER); one more pass then evaluates the final iterate: n_iter + 1 passes at most, n_iter == 0 is an evaluation only
+ * (status HG_ALIGN_MAX_ITER, 0 updates).
+ * RESULT.  d_mats_out[f] (8 doubles) is the final iterate brought back to pixels, in the input's layout: h8 normalised to 1, affine slots 6
+ * and 7 zero.  The INPUT's bits (all 8 slots) are copied instead when
+ *   - a pass found n_valid < min_valid (HG_ALIGN_TOO_FEW);
+ *   - a solution, an iterate or a photometric term has an entry that is not finite (HG_ALIGN_SINGULAR; a constant TO plane ends here);
+ *   - the final rms exceeds pass 0's (HG_ALIGN_WORSE);
+ *   - the input matrix has an entry that is not finite (HG_ALIGN_BAD_INPUT; affine: of its first six): a failed frame of the fit, all NaNs,
+ *     passes through untouched;
+ *   - no update was applied (n_iter == 0): the iterate IS the input.
+ * d_mats_out may alias d_mats_in (frame f's slots are read before they are written, by the workgroup that writes them).
+ * INFO.  d_info[f] is 48 bytes, 8-byte aligned: { int32 status, updates, n_valid_first, n_valid_last; double rms_first, rms_last, gain, bias }.
+ * n_valid_first / rms_first are pass 0's, n_valid_last that of the last pass that ran, rms_last that of the last pass that found min_valid
+ * samples; an rms is NaN where no such pass exists; BAD_INPUT has counts 0.  gain, bias = g, b of the returned matrix: 1, 0 without
+ * photometric and wherever the input was copied.
+ * SUMS.  d_sums is optional (NULL: not written): n_frames x HG_ALIGN_SUMS doubles, the sums of PASS 0 in the order of step 8, the tail zero.
+ * DETERMINISM.  A workgroup takes a CHUNK of 8192 consecutive samples; lane t of its 256 adds the samples t, t + 256, ... of the chunk in
+ * that order, the workgroup adds the lanes' sums through a fixed tree (lane l += lane l + s for s = 128, 64, .. 1), and the chunks' records
+ * are added in ascending chunk order.  No floating-point atomics: two runs of one call give the same bits.  The VALUES are pinned by
+ * tolerance, as the refit's are.
+ * LIMITS (HG_ERR_INVALID), checked in this order, the shape before the context: unknown kind; Wf, Hf, Wt, Ht outside 1..32768 or W * H >
+ * 2^30; channels not 1 or 4; a rectangle that is empty or leaves the FROM plane; step outside 1..64; photometric not 0 or 1; n_iter outside
+ * 0..64; eps negative or not finite; min_valid < P; n_frames outside 0..4096; n_to_sets outside 1..max(n_frames, 1); a stride below its
+ * plane's bytes; then NULL ctx; NULL d_from, d_to, d_mats_in, d_mats_out or d_info; matrices, sums or info not aligned to 8 bytes.
+ * n_frames == 0 is HG_OK and nothing is written.
+ * CONTEXT.  As the fit: no image, mesh or frame set is needed; queued runs are settled first, then the call is asynchronous on the ctx
+ * stream, with no host synchronisation between the passes (every pass of every frame is launched; the workgroups of a stopped frame read
+ * its flag and return, so a stopped frame's outputs are never touched again).  It touches no hg_last_*, no sampling mode, no plan, no policy
+ * state and no staged frame set.  Its scratch -- per frame the iterate and flags, per chunk a record of 67 doubles, and for 4-channel planes
+ * a one-byte luma copy of every plane, made once per call so that the passes do not redo 12 lumas per sample -- lives in buffers the
+ * context owns, grown on demand and reused.
+ * hg_align_scale_matrix (host only) converts a matrix between levels of hg_pyramid_build_device, both sides at the same level: a position
+ * at level k is x_k = (x_0 + 0.5) 2^-k - 0.5 (the rule hg_remap_trilinear_frames_device states), so with e = 2^(level_in - level_out) and
+ * o = (e - 1) / 2 positions move as x_out = e x_in + o and m_out = S m_in S^-1, S = [e 0 o; 0 e o; 0 0 1], divided through by its last
+ * entry.  Affine stays affine.  Levels are 0..30; NULL pointers and unknown kinds are HG_ERR_INVALID.  m_out may be m_in.
+ * COST.  Every pass reads 12 TO taps and one FROM byte per sample and does about 150 f64 operations on them (P = 10).  MEASURED (MI355X,
+ * whole call, medians of 31; EXPERIMENTS.md, "Aligning"): 64 RGBA frames of 1920 x 1080 against one keyframe, projective, photometric, 8
+ * updates (9 passes): 30.8 ms at step 1 (3.9e10 samples / s), 8.1 ms at step 2, 2.3 ms at step 4; 8 frames of 3840 x 2160: 17.5 / 4.8 /
+ * 1.3 ms; ONE frame of 1920 x 1080: 0.74 / 0.62 / 0.60 ms -- the 20 launches, so frames are what the call scales over.  ONE pass of one
+ * 1080p frame takes a plain torch formulation 257 ms at step 1 on the same GPU, the numpy model about 0.2 s at step 2. */
+enum { HG_ALIGN_CONVERGED = 0, HG_ALIGN_MAX_ITER = 1, HG_ALIGN_TOO_FEW = 2, HG_ALIGN_SINGULAR = 3, HG_ALIGN_WORSE = 4, HG_ALIGN_BAD_INPUT = 5 };
+enum { HG_ALIGN_SUMS = 66 };   /* doubles per frame in d_sums */
+int hg_align_scale_matrix(int kind, const double *m_in, int level_in, int level_out, double *m_out);
+int hg_align_refine_frames_device(hg_ctx *ctx, int kind,
+                                  const void *d_from, int Wf, int Hf, int n_frames, size_t from_stride_bytes,
+                                  const void *d_to, int Wt, int Ht, int n_to_sets, size_t to_stride_bytes, int channels,
+                                  int rx, int ry, int rw, int rh, int step,
+                                  int photometric, int n_iter, double eps, int min_valid,
+                                  const double *d_mats_in, double *d_mats_out, void *d_info, double *d_sums);
 
 /* ------------------------------------------------------------------------------------------------ matching descriptors
  * The matcher that hands hg_fit_matches_frames_device its matches: for every frame a brute-force search of the nearest and second-nearest
