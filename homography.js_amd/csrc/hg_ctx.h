@@ -1,6 +1,6 @@
 // hg_ctx.h -- the context behind the C ABI of include/hgwarp.h and the helpers its translation units share
 // (hg_api.hip: library / context / buffers / host-side solves / source image; hg_api_geometric.hip; hg_api_piecewise.hip;
-// hg_api_forward.hip; hg_api_state.hip; hg_api_field.hip; hg_api_points.hip; hg_api_fit.hip; hg_api_match.hip; hg_api_detect.hip; hg_api_align.hip).  Its memory is owned through hg_mem.h.  Internal: nothing here is exported.
+// hg_api_forward.hip; hg_api_state.hip; hg_api_field.hip; hg_api_points.hip; hg_api_fit.hip; hg_api_match.hip; hg_api_detect.hip; hg_api_align.hip; hg_api_tps.hip).  Its memory is owned through hg_mem.h.  Internal: nothing here is exported.
 #pragma once
 #include "../../include/hgwarp.h"
 #include "hg_kernels.h"

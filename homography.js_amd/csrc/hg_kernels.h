@@ -8,6 +8,7 @@
 #include "hg_span_start.h"
 #include "hg_remap_records.h"
 #include "hg_align_dev.h"
+#include "hg_tps_dev.h"
 
 namespace hg {
 
@@ -296,6 +297,12 @@ struct AlignArgs {
 };
 void launch_align_luma(const uint8_t *src, size_t src_stride, int W, int H, int n_planes, uint8_t *dst, hipStream_t stream);
 void launch_align(const AlignArgs &a, hipStream_t stream);
+
+// Thin-plate splines (hg_k_tps.hip; the rules and the argument blocks: hg_tps_dev.h): k_tps_solve, one workgroup per frame; k_tps_field over the
+// windows (step 1) or over the lattice and then k_tps_blend (step > 1; fmt = HG_FIELD_*); k_tps_points, frame f reading list f % n_sets.
+void launch_tps_solve(const TpsSolveArgs &a, hipStream_t stream);
+void launch_tps_field(const TpsFieldArgs &a, int fmt, hipStream_t stream);
+void launch_tps_points(const double *records, int n_points, int n_frames, const float *points, int n_pts, int n_sets, float *out, hipStream_t stream);
 
 // Matching descriptors (hg_k_match.hip; the rules: hg_match_dev.h): k_match_bits resp. k_match_u8 for the two nearest train rows of every query,
 // the same kernel with the sides swapped for the best query of every train row (cross_check), then k_match_finish.  query = F lists of

@@ -1309,6 +1309,95 @@ static napi_value fn_align_end(napi_env env, napi_callback_info info)
     return u;
 }
 
+/* warpThinPlate(handle, from, nFromSets, to, nToSets, nPoints, windows, smoothing, step, output, images | null, W, H, nImages): thin-plate
+ * splines through landmark pairs, one per window (hg_tps_solve_frames_device -> hg_field_tps_frames_device -> a remap), all on the device.
+ * from / to: Float32Arrays of nFromSets resp. nToSets lists of nPoints x,y pairs (from = output space, to = source space); windows:
+ * Int32Array of F x (x, y, width, height); output: 0 = picture by the index field (hg_remap_index_frames_device, 4-byte pixels), 1 = picture
+ * by the coords field (hg_remap_bilinear_frames_device, u8 x 4), 2 = the index field, 3 = the coords field; images: Uint8Array of nImages
+ * RGBA pictures of W x H (outputs 0 and 1; frame f reads picture f % nImages), else null.  Returns { data: Uint8Array, the frames packed at
+ * the 256-byte grain, status: Int32Array(F) }.  Only the results come down. */
+static napi_value fn_warp_thin_plate(napi_env env, napi_callback_info info)
+{
+    napi_value a[14];
+    if (!get_args(env, info, 14, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    int n_fs, n_ts, N, step, output, W, H, n_img; size_t n_f = 0, n_t = 0, n_w = 0, n_i = 0; double lambda;
+    float *from = (float *)get_typed(env, a[1], napi_float32_array, &n_f, "from"); if (!from) return NULL;
+    if (!get_i32(env, a[2], &n_fs)) return NULL;
+    float *to = (float *)get_typed(env, a[3], napi_float32_array, &n_t, "to"); if (!to) return NULL;
+    if (!get_i32(env, a[4], &n_ts) || !get_i32(env, a[5], &N)) return NULL;
+    int32_t *win = (int32_t *)get_typed(env, a[6], napi_int32_array, &n_w, "windows"); if (!win && n_w) return NULL;
+    if (napi_get_value_double(env, a[7], &lambda) != napi_ok) return throw_str(env, "hgwarp: smoothing must be a number");
+    if (!get_i32(env, a[8], &step) || !get_i32(env, a[9], &output)) return NULL;
+    napi_valuetype vt;
+    NAPI_OK(napi_typeof(env, a[10], &vt));
+    uint8_t *img = NULL;
+    if (vt != napi_null && vt != napi_undefined) { img = (uint8_t *)get_typed(env, a[10], napi_uint8_array, &n_i, "images"); if (!img) return NULL; }
+    if (!get_i32(env, a[11], &W) || !get_i32(env, a[12], &H) || !get_i32(env, a[13], &n_img)) return NULL;
+    if (N < 3 || N > HG_TPS_MAX_POINTS || n_fs < 1 || n_ts < 1 || n_w % 4 != 0 || n_w / 4 > 4096 || output < 0 || output > 3 || W < 1 || H < 1)
+        return throw_str(env, "hgwarp: warpThinPlate: nPoints, set counts, windows, output or the source size is out of range");
+    const size_t F = n_w / 4;
+    if (n_f != (size_t)n_fs * N * 2 || n_t != (size_t)n_ts * N * 2) return throw_str(env, "hgwarp: warpThinPlate: from / to must hold their sets of nPoints x,y pairs");
+    const int picture = output < 2, fmt = (output == 0 || output == 2) ? HG_FIELD_INDEX : HG_FIELD_COORDS;
+    const size_t plane = (size_t)W * (size_t)H * 4;
+    if (picture && (!img || n_img < 1 || n_i != plane * (size_t)n_img)) return throw_str(env, "hgwarp: warpThinPlate: images must hold nImages RGBA pictures of W x H");
+    hg_geom *g = (hg_geom *)calloc(F ? F : 1, sizeof *g);
+    if (!g) return throw_str(env, "hgwarp: out of memory");
+    for (size_t f = 0; f < F; f++) { g[f].x_off = win[4 * f]; g[f].y_off = win[4 * f + 1]; g[f].obj_w = win[4 * f + 2]; g[f].obj_h = win[4 * f + 3]; }
+    size_t fld_total = 0, out_total = 0, rec_b = 0, scr_b = 0, node_b = 0;
+    int rc = hg_tps_layout(N, (int)F, &rec_b, &scr_b);
+    const char *what = "hg_tps_layout";
+    if (rc == HG_OK) { what = "hg_tps_field_layout"; rc = hg_tps_field_layout(g, (int)F, step, &node_b); }
+    if (rc != HG_OK) { napi_value e = throw_hg(env, h->ctx, what, rc); free(g); return e; }
+    for (size_t f = 0; f < F; f++) {
+        const size_t px = (g[f].obj_w > 0 && g[f].obj_h > 0) ? (size_t)g[f].obj_w * (size_t)g[f].obj_h : 0;
+        fld_total += (px * (fmt == HG_FIELD_INDEX ? 4 : 8) + 255) & ~(size_t)255;
+        out_total += (px * 4 + 255) & ~(size_t)255;
+    }
+    const size_t res_total = picture ? out_total : fld_total;
+    void *p_data, *p_status;
+    napi_value out, v_data, v_status;
+    if (!(v_data = make_typed(env, napi_uint8_array, res_total, 1, &p_data)) || !(v_status = make_typed(env, napi_int32_array, F, 4, &p_status))) { free(g); return NULL; }
+    if (napi_create_object(env, &out) != napi_ok || napi_set_named_property(env, out, "data", v_data) != napi_ok ||
+        napi_set_named_property(env, out, "status", v_status) != napi_ok) { free(g); return throw_str(env, "hgwarp: N-API call failed"); }
+    if (!F) { free(g); return out; }
+#define TPS_PAD(b) (((size_t)(b) + 255) & ~(size_t)255)
+    const size_t o_from = 0, o_to = o_from + TPS_PAD(n_f * 4), o_rec = o_to + TPS_PAD(n_t * 4), o_st = o_rec + TPS_PAD(rec_b * F), o_scr = o_st + TPS_PAD(F * 4),
+                 o_node = o_scr + TPS_PAD(scr_b), o_fld = o_node + TPS_PAD(node_b), o_img = o_fld + TPS_PAD(fld_total), o_out = o_img + TPS_PAD(picture ? n_i : 0),
+                 total = o_out + TPS_PAD(picture ? out_total : 0);
+#undef TPS_PAD
+    void *d = NULL;
+    rc = hg_device_alloc(h->ctx, total, &d);
+    if (rc != HG_OK) { napi_value e = throw_hg(env, h->ctx, "hg_device_alloc", rc); free(g); return e; }
+    uint8_t *b = (uint8_t *)d;
+    what = "hg_copy_to_device";
+    rc = hg_copy_to_device(h->ctx, b + o_from, from, n_f * 4);
+    if (rc == HG_OK) rc = hg_copy_to_device(h->ctx, b + o_to, to, n_t * 4);
+    if (rc == HG_OK && picture) rc = hg_copy_to_device(h->ctx, b + o_img, img, n_i);
+    if (rc == HG_OK) {
+        what = "hg_tps_solve_frames_device";
+        rc = hg_tps_solve_frames_device(h->ctx, b + o_from, n_fs, b + o_to, n_ts, N, (int)F, lambda, (double *)(b + o_rec), (int32_t *)(b + o_st), scr_b ? b + o_scr : NULL);
+    }
+    if (rc == HG_OK) {
+        what = "hg_field_tps_frames_device";
+        rc = hg_field_tps_frames_device(h->ctx, (const double *)(b + o_rec), N, g, (int)F, W, H, fmt, step, NULL, b + o_fld, node_b ? b + o_node : NULL);
+    }
+    if (rc == HG_OK && output == 0) {
+        what = "hg_remap_index_frames_device";
+        rc = hg_remap_index_frames_device(h->ctx, g, (int)F, b + o_fld, NULL, b + o_img, (size_t)W * (size_t)H, n_img, plane, 4, b + o_out, NULL);
+    }
+    if (rc == HG_OK && output == 1) {
+        what = "hg_remap_bilinear_frames_device";
+        rc = hg_remap_bilinear_frames_device(h->ctx, g, (int)F, b + o_fld, NULL, b + o_img, W, H, n_img, plane, HG_ELEM_U8, 4, b + o_out, NULL);
+    }
+    if (rc == HG_OK && res_total) { what = "hg_copy_to_host"; rc = hg_copy_to_host(h->ctx, p_data, picture ? b + o_out : b + o_fld, res_total); }
+    if (rc == HG_OK) { what = "hg_copy_to_host"; rc = hg_copy_to_host(h->ctx, p_status, b + o_st, F * 4); }
+    free(g);
+    if (rc != HG_OK) { napi_value e = throw_hg(env, h->ctx, what, rc); hg_device_free(h->ctx, d); return e; }
+    HG_CALL(h->ctx, "hg_device_free", hg_device_free(h->ctx, d));
+    return out;
+}
+
 /* matchDescriptors(handle, kind, descBytes, stride, query, nQuery, countsQ, train, nTrain, countsT, ratio, maxDistance, crossCheck,
  * queryPoints | null, trainPoints | null): the accepted nearest-neighbour pairs of every frame (hg_match_descriptors_frames_device).  query:
  * Uint8Array of F x nQuery x stride, F = countsQ.length; train: Uint8Array of S x nTrain x stride, S = countsT.length; the points: Float32Array
@@ -2175,6 +2264,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "pointsForwardGeometric", fn_points_forward_geometric }, { "pointsForwardPiecewise", fn_points_forward_piecewise },
         { "fitMatches", fn_fit_matches },
         { "alignBegin", fn_align_begin }, { "alignLevel", fn_align_level }, { "alignScaleMatrix", fn_align_scale_matrix }, { "alignEnd", fn_align_end },
+        { "warpThinPlate", fn_warp_thin_plate },
         { "matchDescriptors", fn_match_descriptors },
         { "detectAndDescribe", fn_detect_describe },
         { "solveAffineTriangles", fn_solve_affine_triangles }, { "warpInversePiecewiseState", fn_warp_inverse_piecewise_state },

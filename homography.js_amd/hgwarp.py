@@ -37,6 +37,10 @@ ALIGN_CONVERGED, ALIGN_MAX_ITER, ALIGN_TOO_FEW, ALIGN_SINGULAR, ALIGN_WORSE, ALI
 ALIGN_SUMS = 66
 ALIGN_INFO = np.dtype([("status", np.int32), ("updates", np.int32), ("n_valid_first", np.int32), ("n_valid_last", np.int32),
                        ("rms_first", np.float64), ("rms_last", np.float64), ("gain", np.float64), ("bias", np.float64)])
+# thin-plate splines (hg_tps_solve_frames_device): the most control points of a frame, the status of a frame, the doubles in front of a record's points
+TPS_MAX_POINTS = 1024
+TPS_OK, TPS_SINGULAR, TPS_BAD_INPUT = 0, 1, 2
+TPS_HEAD = 16
 
 # every symbol include/hgwarp.h declares (tests check that the built library exports all of them)
 EXPORTS = [
@@ -72,6 +76,7 @@ EXPORTS = [
     "hg_remap_bicubic_frames_device",
     "hg_fit_sample_indices", "hg_fit_matches_frames_device",
     "hg_align_scale_matrix", "hg_align_refine_frames_device",
+    "hg_tps_layout", "hg_tps_solve_frames_device", "hg_tps_field_layout", "hg_field_tps_frames_device", "hg_points_tps_frames_device",
     "hg_match_descriptors_frames_device",
     "hg_detect_layout", "hg_describe_pattern", "hg_detect_describe_frames_device",
     "hg_mosaic_multiband_layout", "hg_mosaic_multiband_device",
@@ -194,6 +199,11 @@ def lib():
         "hg_fit_matches_frames_device": (i, [vp, i, vp, i, C.POINTER(C.c_int32), i, d, i, C.c_uint32, vp, i, vp, vp, vp, vp, vp]),
         "hg_align_scale_matrix": (i, [i, f64p, i, i, f64p]),
         "hg_align_refine_frames_device": (i, [vp, i, vp, i, i, i, sz, vp, i, i, i, sz, i, i, i, i, i, i, i, i, d, i, vp, vp, vp, vp]),
+        "hg_tps_layout": (i, [i, i, C.POINTER(sz), C.POINTER(sz)]),
+        "hg_tps_solve_frames_device": (i, [vp, vp, i, vp, i, i, i, d, vp, vp, vp]),
+        "hg_tps_field_layout": (i, [C.POINTER(Geom), i, i, C.POINTER(sz)]),
+        "hg_field_tps_frames_device": (i, [vp, vp, i, C.POINTER(Geom), i, i, i, i, i, C.POINTER(sz), vp, vp]),
+        "hg_points_tps_frames_device": (i, [vp, vp, i, i, vp, i, i, vp]),
         "hg_match_descriptors_frames_device": (i, [vp, i, i, sz, vp, i, C.POINTER(C.c_int32), i, vp, i, C.POINTER(C.c_int32), i, d, C.c_uint32, i,
                                                    vp, vp, vp, vp, vp, vp]),
         "hg_detect_layout": (i, [i, i, i, i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -356,6 +366,21 @@ def pack_plane_offsets(geoms, px_bytes):
     total = C.c_size_t(0)
     _check(lib().hg_pack_plane_offsets(g, len(geoms), int(px_bytes), offs, C.byref(total)))
     return list(offs)[:len(geoms)], total.value
+
+
+def tps_layout(n_points, n_frames):
+    """(record bytes per frame, solve scratch bytes) of hg_tps_solve_frames_device: a record is 16 + 4 n_points doubles; the scratch is 0
+    while the system fits LDS (n_points <= 69), else n_frames x (n_points + 3)^2 doubles."""
+    rec, scr = C.c_size_t(0), C.c_size_t(0)
+    _check(lib().hg_tps_layout(int(n_points), int(n_frames), C.byref(rec), C.byref(scr)))
+    return rec.value, scr.value
+
+
+def tps_field_layout(geoms, step):
+    """Scratch bytes of hg_field_tps_frames_device at `step`: the node lattices of the frames as f64 pairs (0 at step 1)."""
+    total = C.c_size_t(0)
+    _check(lib().hg_tps_field_layout(_geoms(geoms) if len(geoms) else None, len(geoms), int(step), C.byref(total)))
+    return total.value
 
 
 def pyramid_levels(w, h):
@@ -989,6 +1014,29 @@ class Context:
         self._c(lib().hg_align_refine_frames_device(self._h, int(kind), vp(d_from), int(wf), int(hf), int(n_frames), fs, vp(d_to), int(wt), int(ht),
                                                     int(n_to_sets), ts, int(channels), rx, ry, rw, rh, int(step), int(photometric), int(n_iter), float(eps),
                                                     P if min_valid is None else int(min_valid), vp(d_mats_in), vp(d_mats_out), vp(d_info), vp(d_sums)))
+
+    def tps_solve_frames_device(self, d_from, n_from_sets, d_to, n_to_sets, n_points, n_frames, d_records, d_status, smoothing=0.0, d_scratch=0):
+        """hg_tps_solve_frames_device: one thin-plate spline per frame through n_points pairs (from -> to, (x, y) float32 lists on the device;
+        frame f reads from-list f % n_from_sets and to-list f % n_to_sets), smoothing = lambda >= 0 in the normalised frame (0 interpolates).
+        d_records gets 16 + 4 n_points doubles per frame, d_status one int32 (TPS_*); d_scratch: tps_layout's bytes (0 where none are needed).
+        Asynchronous."""
+        vp = lambda v: C.c_void_p(int(v) or None)
+        self._c(lib().hg_tps_solve_frames_device(self._h, vp(d_from), int(n_from_sets), vp(d_to), int(n_to_sets), int(n_points), int(n_frames),
+                                                 float(smoothing), vp(d_records), vp(d_status), vp(d_scratch)))
+
+    def field_tps_frames_device(self, d_records, n_points, geoms, w, h, fmt, d_field, step=1, field_offsets=None, d_scratch=0):
+        """hg_field_tps_frames_device: the source field (FIELD_INDEX / FIELD_COORDS) of the frames' splines over the windows `geoms` into a
+        source of w x h pixels; step > 1 evaluates a lattice and blends (an approximation; d_scratch: tps_field_layout's bytes).  Asynchronous."""
+        fo = (C.c_size_t * len(geoms))(*field_offsets) if field_offsets is not None else None
+        vp = lambda v: C.c_void_p(int(v) or None)
+        self._c(lib().hg_field_tps_frames_device(self._h, vp(d_records), int(n_points), _geoms(geoms) if len(geoms) else None, len(geoms), int(w), int(h),
+                                                 int(fmt), int(step), fo, vp(d_field), vp(d_scratch)))
+
+    def points_tps_frames_device(self, d_records, n_points, n_frames, d_points, n_pts, n_sets, d_out):
+        """hg_points_tps_frames_device: n_sets lists of n_pts absolute from-space positions through the frames' splines (frame f reads list
+        f % n_sets); d_out gets n_frames x n_pts (x, y) float32, NaN / NaN for a position that is not finite or a failed frame.  Asynchronous."""
+        vp = lambda v: C.c_void_p(int(v) or None)
+        self._c(lib().hg_points_tps_frames_device(self._h, vp(d_records), int(n_points), int(n_frames), vp(d_points), int(n_pts), int(n_sets), vp(d_out)))
 
     def match_descriptors_frames_device(self, kind, desc_bytes, stride, d_query, n_query, counts_q, n_frames, d_train, n_train, counts_t, n_train_sets,
                                         d_counts, ratio=0.8, max_distance=0xffffffff, cross_check=False, d_query_pts=0, d_train_pts=0, d_matches=0,

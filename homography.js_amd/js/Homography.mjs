@@ -618,6 +618,99 @@ class Homography {
     }
 
     /**
+     * Thin-plate spline warps: the smooth interpolant through landmark pairs, where the piecewise affine transform kinks at every triangle
+     * edge and ends at the hull of its mesh (not part of the reference; "thin-plate splines" in include/hgwarp.h has the rules).  One spline
+     * per destiny point set, solved and evaluated on the device; only the results come down.
+     * sourcePoints: the landmarks in the source picture, a Float32Array of x, y pairs or an array of [x, y] (3..1024 of them, in pixels);
+     * destinyPointSets: an array of such lists, one per frame, where the landmarks go.
+     * options: { smoothing = 0 (lambda >= 0 in the normalised frame; 0 interpolates), step = 1 (2, 4, 8, 16, 32: the spline is evaluated on
+     *            a lattice and blended in between -- an approximation whose error sits around the landmarks),
+     *            output = 'image' ('index' / 'coords': the source field itself, an Int32Array resp. a Float32Array of x, y pairs),
+     *            sampling = 'nearest' ('bilinear'; pictures only),
+     *            window: { x, y, width, height } for every frame, or an array of them (default: the integer bounding box of each destiny set),
+     *            images: ImageData-shaped sources of one size, frame f reads images[f % images.length] (default: the instance's image) }.
+     * Returns one record per frame: { data, width, height, x, y, status } -- status 0 ok, 1 singular (coincident or collinear landmarks),
+     * 2 a coordinate that is not finite; a failed frame is empty (zero pixels, index -1, NaN coordinates).
+     * Changes no state of the instance.  Throws a bare string for point lists that do not fit and options out of range.
+     */
+    warpThinPlate(sourcePoints, destinyPointSets, options = {}) {
+        if (options === null || options === undefined) options = {};
+        const list = (p, name) => {
+            if (!(p instanceof Float32Array) && !Array.isArray(p)) throw ("warpThinPlate: " + name + " must be a Float32Array or an array of [x, y]");
+            const l = p instanceof Float32Array ? p : Float32Array.from(p.flat());
+            if (l.length % 2 !== 0) throw ("warpThinPlate: " + name + " must hold x, y pairs");
+            return l;
+        };
+        const src = list(sourcePoints, 'sourcePoints'), N = src.length / 2;
+        if (N < 3 || N > 1024) throw ("warpThinPlate: 3 to 1024 landmarks are needed, but " + N + " were given");
+        if (!Array.isArray(destinyPointSets)) throw ("warpThinPlate: destinyPointSets must be an array of point lists");
+        const F = destinyPointSets.length;
+        if (F > 4096) throw ("warpThinPlate: at most 4096 frames");
+        const dst = new Float32Array(F * N * 2);
+        destinyPointSets.forEach((p, f) => {
+            const l = list(p, 'destiny point set ' + f);
+            if (l.length !== 2 * N) throw (`It must be the same amount of destiny points (${l.length / 2}) than source points (${N})`);
+            dst.set(l, f * N * 2);
+        });
+        const smoothing = options.smoothing === undefined ? 0 : options.smoothing;
+        if (typeof smoothing !== 'number' || !Number.isFinite(smoothing) || smoothing < 0) throw ("warpThinPlate: options.smoothing must be a finite number >= 0");
+        const step = options.step === undefined ? 1 : options.step;
+        if (![1, 2, 4, 8, 16, 32].includes(step)) throw ("warpThinPlate: options.step must be 1, 2, 4, 8, 16 or 32");
+        const output = options.output === undefined ? 'image' : options.output;
+        if (output !== 'image' && output !== 'index' && output !== 'coords') throw ("warpThinPlate: options.output must be 'image', 'index' or 'coords'");
+        const sampling = options.sampling === undefined ? 'nearest' : options.sampling;
+        if (sampling !== 'nearest' && sampling !== 'bilinear') throw ("warpThinPlate: options.sampling must be 'nearest' or 'bilinear'");
+        const isInt = (v) => Number.isInteger(v) && Math.abs(v) <= 0x7fffffff;
+        const windows = new Int32Array(4 * F);
+        for (let f = 0; f < F; f++) {
+            let w = Array.isArray(options.window) ? options.window[f] : options.window;
+            if (Array.isArray(options.window) && options.window.length !== F) throw ("warpThinPlate: options.window must hold one window per frame");
+            if (w === undefined || w === null) {
+                let x0 = Infinity, y0 = Infinity, x1 = -Infinity, y1 = -Infinity, finite = true;
+                for (let i = 0; i < N; i++) {
+                    const x = dst[(f * N + i) * 2], y = dst[(f * N + i) * 2 + 1];
+                    finite = finite && Number.isFinite(x) && Number.isFinite(y);
+                    if (x < x0) x0 = x; if (x > x1) x1 = x; if (y < y0) y0 = y; if (y > y1) y1 = y;
+                }
+                w = finite ? { x: Math.floor(x0), y: Math.floor(y0), width: Math.ceil(x1) - Math.floor(x0) + 1, height: Math.ceil(y1) - Math.floor(y0) + 1 }
+                                                       : { x: 0, y: 0, width: 0, height: 0 };      // (a coordinate that is not finite: the frame fails, its window is empty)
+            }
+            if (!w || !isInt(w.x) || !isInt(w.y) || !isInt(w.width) || !isInt(w.height)) throw ("warpThinPlate: options.window must be { x, y, width, height }, four integers");
+            windows.set([w.x, w.y, Math.max(w.width, 0), Math.max(w.height, 0)], 4 * f);
+        }
+        let W = this._width, H = this._height, planes = null, nImages = 0;
+        if (options.images !== undefined && options.images !== null) {
+            const images = options.images;
+            if (!Array.isArray(images) || images.length === 0) throw ("warpThinPlate: options.images needs a non-empty array of ImageData-shaped sources");
+            W = images[0] ? images[0].width : 0; H = images[0] ? images[0].height : 0;
+            for (const im of images)
+                if (!im || !ArrayBuffer.isView(im.data) || im.width !== W || im.height !== H || im.data.length !== W * H * 4)
+                    throw ("warpThinPlate: every image must be ImageData-shaped RGBA and of one size");
+            if (output === 'image') {
+                planes = new Uint8Array(images.length * W * H * 4);
+                images.forEach((im, k) => planes.set(im.data, k * W * H * 4));
+                nImages = images.length;
+            }
+        } else if (output === 'image') {
+            if (this._image === null) throw ("warp() must receive an image if it was not setted before through `setImage(img)` or  `setSourcePoints(points, img)`");
+            planes = new Uint8Array(this._image.buffer, this._image.byteOffset, this._image.length);
+            nImages = 1;
+        }
+        if (!Number.isInteger(W) || !Number.isInteger(H) || W < 1 || H < 1) throw ("warpThinPlate: the source size is not known: give options.images or set an image first");
+        const code = output === 'image' ? (sampling === 'bilinear' ? 1 : 0) : (output === 'index' ? 2 : 3);
+        const r = this._native.warpThinPlate(this._ctx, dst, F, src, 1, N, windows, smoothing, step, code, planes, W, H, nImages);
+        const px = code === 3 ? 8 : 4;
+        let off = 0;
+        return destinyPointSets.map((p, f) => {
+            const width = windows[4 * f + 2], height = windows[4 * f + 3], bytes = width * height * px;
+            const b = r.data.buffer.slice(r.data.byteOffset + off, r.data.byteOffset + off + bytes);
+            off += (bytes + 255) & ~255;
+            const data = code === 2 ? new Int32Array(b) : code === 3 ? new Float32Array(b) : new Uint8ClampedArray(b);
+            return { data, width, height, x: windows[4 * f], y: windows[4 * f + 1], status: r.status[f] };
+        });
+    }
+
+    /**
      * The descriptors matchDescriptors() starts from: the keypoints of a set of pictures -- Harris corners in integer arithmetic, the best
      * perCell of every cell x cell cell of the picture, an orientation and a 256-bit binary descriptor each (not part of the reference;
      * hg_detect_describe_frames_device in include/hgwarp.h has the rules, all of them exact).  It is not ORB: both sides of a match have to

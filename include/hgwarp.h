@@ -40,8 +40,9 @@ extern "C" {
                                    the bicubic remap by that of hg_remap_bicubic_frames_device, exposure gains of a mosaic by that of
                                    hg_mosaic_overlap_stats_device, fitting transforms to matches by that of hg_fit_matches_frames_device);
                                    matching descriptors by the presence of hg_match_descriptors_frames_device, keypoints by the presence of
-                                   hg_detect_describe_frames_device, multi-band mosaics by the presence of hg_mosaic_multiband_device, refining transforms
-                                   on the pixels by the presence of hg_align_refine_frames_device */
+                                   hg_detect_describe_frames_device, multi-band mosaics by the presence of hg_mosaic_multiband_device, thin-plate splines
+                                   by the presence of hg_tps_solve_frames_device, refining transforms on the pixels by the presence of
+                                   hg_align_refine_frames_device */
 
 enum {
     HG_OK = 0,
@@ -903,6 +904,82 @@ int hg_align_refine_frames_device(hg_ctx *ctx, int kind,
                                   int rx, int ry, int rw, int rh, int step,
                                   int photometric, int n_iter, double eps, int min_valid,
                                   const double *d_mats_in, double *d_mats_out, void *d_info, double *d_sums);
+
+/* ------------------------------------------------------------------------------------------------ thin-plate splines
+ * The piecewise transform is C0 only -- every triangle edge is a kink -- and undefined outside the hull of its mesh.  The THIN-PLATE SPLINE
+ * is the smooth interpolant through the same landmark pairs, defined everywhere.  Not part of the reference.  These calls fit one spline per
+ * frame on the device, and export it as a source field (what every remap, the mosaics and the multi-band blend read) or send point lists
+ * through it.  None needs an image, a mesh or a frame set.
+ * POINTS.  Frame f has n_points pairs (from_i -> to_i), 3 <= n_points <= HG_TPS_MAX_POINTS, interleaved (x, y) float32, 8-byte aligned.
+ * d_from holds n_from_sets lists of n_points points, d_to n_to_sets lists, tightly packed; frame f reads from-list f % n_from_sets and
+ * to-list f % n_to_sets.  The spline maps FROM-space positions to TO-space positions.  For a source field FROM holds output-space (destiny)
+ * points and TO source-image points, the convention of hg_geometric_set_frames_points; swapping the roles gives the landmark-to-output map
+ * (a spline has no closed-form inverse: that map is a second spline, solved on its own).
+ * All arithmetic is f64, IEEE division and square root, contraction off.
+ * NORMALISATION (the rule of the fit's refit, on the from side).  c = the mean of the from-points, s = sqrt(2) / the mean of
+ * sqrt(ax ax + ay ay) over a = from_i - c, d_i = (from_i - c) s; t = the mean of the to-points, b_i = to_i - t.  Sums run in index order.
+ * SYSTEM, of size M = n_points + 3: [[K + lambda I, P], [P^T, 0]] [w; a] = [b; 0] with K_ij = U(|d_i - d_j|^2), U(q) = q log q, U(0) = 0
+ * (r^2 log r^2, twice the textbook kernel; the factor is absorbed into w), row i of P = [1, dx_i, dy_i], and two right-hand sides, the x and
+ * the y parts of b.  lambda >= 0 is finite and lives in the normalised frame; 0 interpolates.
+ * SOLVE.  Gaussian elimination with partial pivoting: in column k the pivot is the entry of largest magnitude in rows k.., the lowest row
+ * among equals; rows are swapped; row i > k becomes row_i - (a_ik / pivot) row_k, entry by entry, the right-hand sides alike; then back
+ * substitution, x_k = b_k / a_kk, b_i -= a_ik x_k for i < k.  The order is fixed: two runs give the same bits.  One workgroup per frame; the
+ * matrix lives in LDS for n_points <= 69, else in d_scratch (hg_tps_layout: n_frames x M x M doubles, 0 for n_points <= 69).
+ * RECORD of a frame: 16 + 4 n_points doubles.  [0] cx [1] cy [2] s [3] tx [4] ty [8] a0x [9] a0y [10] a1x [11] a1y [12] a2x [13] a2y, the
+ * other slots below 16 are 0; then n_points x (dx_i, dy_i, wx_i, wy_i).
+ * STATUS of a frame (int32): HG_TPS_BAD_INPUT when any coordinate of the frame is not finite; else HG_TPS_SINGULAR when the mean distance is
+ * 0 (all from-points coincide), a pivot is 0 or not finite, or a coefficient is not finite; else HG_TPS_OK.  Two coincident from-points at
+ * lambda == 0 are HG_TPS_SINGULAR: their rows stay equal through the elimination, so a pivot is exactly 0; at lambda > 0 they solve.  A set
+ * that is NEARLY singular but still gives finite numbers is the caller's business: it is HG_TPS_OK with whatever coefficients came out.
+ * Every slot of a failed frame's record is 0x7ff8000000000000; other frames are not affected.
+ * EVALUATION at the from-space position (X, Y): x' = (X - cx) s, y' = (Y - cy) s, q_i = (x' - dx_i)^2 + (y' - dy_i)^2,
+ *   sx = tx + (((a0x + a1x x') + a2x y') + sum_i wx_i U(q_i)), sy alike, the sum in index order, in f64: the terms are large and cancel (at
+ * 200 points and 20 px displacements sum |w U| reaches 5e6 for results of a few thousand), so an f32 sum would be wrong by tenths of a pixel.
+ * The logarithm is this library's own (tps_log, csrc/hg_tps_dev.h), good to 2 ulp and not libm's to the bit: values are pinned by tolerance.
+ * hg_field_tps_frames_device writes the source field of the frames' splines: pixel (i, j) of frame f is the position (i + x_off, j + y_off);
+ * it is covered iff sx >= 0 && sx < W && sy >= 0 && sy < H (NaN fails; W, H >= 1 are arguments, as for the remaps), and its value is stored by
+ * the rules of the other field calls: HG_FIELD_INDEX and HG_FIELD_COORDS mean exactly what they mean above, -1 and the NaN pattern
+ * included.  field_offsets, packing, alignment, "bytes between frames are never written" and the settling of queued runs are those of
+ * hg_field_inverse_geometric_frames_device.  A failed frame is all -1 resp. all NaN.
+ * STEP is 1, 2, 4, 8, 16 or 32.  1 evaluates every pixel: the defined result.  Above 1 the spline is evaluated on the LATTICE of window columns
+ * and rows k step, k = 0 .. nodes - 1, nodes = max(2, (n + step - 2) / step + 1) for a window of n pixels along the axis: the last node lies
+ * at or beyond the last pixel, so nodes may lie outside the window.  Node values go as f64 pairs into d_scratch (hg_tps_field_layout; 16-byte
+ * aligned; per frame nodes_x x nodes_y x 16 bytes, frames at the 256-byte grain).  Pixel column c has k = min(c / step, nodes - 2) and fx =
+ * (c - k step) / step, rows alike, and blends its four nodes in f64 as (n00 (1 - fx) + n01 fx) (1 - fy) + (n10 (1 - fx) + n11 fx) fy; it is
+ * then tested and stored like any other.  A pixel on a node takes the node's value as it stands and equals the step-1 field bit for bit.
+ * The mode is an APPROXIMATION whose error sits around the control points, where the spline's second derivative has a log singularity.  On
+ * the numpy model, 68 points on a smooth deformation with 0.5 px of landmark noise: step 4 is off by 0.05 px at its worst pixel (mean
+ * 0.0006), step 8 by 0.18 px (mean 0.0025); with 8 px of independent noise per landmark step 2 is already 0.5 px off at its worst pixel.
+ * Measure on your own landmarks (tools/bench_tps.py reports the error per step).
+ * hg_points_tps_frames_device sends point lists through the splines, in the layout of the point-list calls: d_points holds n_sets lists of
+ * n_pts (x, y) float32, frame f reads list f % n_sets, d_out receives n_frames x n_pts pairs.  Positions are ABSOLUTE from-space positions
+ * and there is no coverage test: the result is ((float)sx, (float)sy).  A position that is not finite, a failed frame and a result with a NaN
+ * part hold 0x7fc00000 in both words; 1e30 is a legal input.  An integer position equals the HG_FIELD_COORDS field's value at that pixel where
+ * the pixel is covered, bit for bit.
+ * LIMITS (HG_ERR_INVALID), the shape before the context: n_points outside 3..1024; n_frames outside 0..4096; set counts below 1; lambda
+ * negative or not finite; an unknown format or step; W or H below 1; for HG_FIELD_INDEX a source of 2^31 pixels or more; n_pts outside
+ * 0..2^24; what hg_geom refuses; a field offset that is no multiple of the pixel size; then NULL or misaligned pointers when there is work,
+ * and a NULL ctx.  n_frames == 0 (and n_pts == 0, and a set of empty windows) is HG_OK and nothing is written.
+ * CONTEXT.  hg_tps_solve_frames_device settles what hg_fit_matches_frames_device settles (queued runs), the other two what their
+ * counterparts settle; then each is asynchronous on the ctx stream.  None touches hg_last_*, the sampling mode, a plan, policy state or a
+ * staged frame set.  Scratch comes from the caller and may be reused once the call that used it has completed.
+ * COST.  n_points logarithms in f64 per pixel (the project's own, good to 2 ulp: 46 instructions per term).  MEASURED (MI355X, whole call,
+ * medians of 9; EXPERIMENTS.md, "Thin-plate"; tools/bench_tps.py): 64 frames of 3840 x 2160, HG_FIELD_COORDS, 68 points: 45.5 ms at step 1
+ * (7.9e11 terms / s, bound by f64 issue whatever n_points is), 5.1 ms at step 4, 2.0 ms at step 8, 1.5 ms at step 16; the solve 0.3 ms.  200
+ * points: 132 / 11.3 / 3.5 / 1.9 ms, the solve 1.8 ms.  1024 points: 677 / 50 / 13 / 4.5 ms, the solve 221 ms (one workgroup per frame, the
+ * matrix in scratch).  The piecewise coords field of the same 68 landmarks takes 1.9 ms; scipy's RBFInterpolator 5.3 s for ONE frame.  The
+ * lattice's error on those frames, which move every landmark 77 px on its own (max / mean px): 68 points 0.30 / 0.005 at step 4, 0.89 / 0.02
+ * at step 8; at 200 points, where that is more than the landmarks' spacing and the spline folds, 41 / 0.02 at step 4. */
+enum { HG_TPS_MAX_POINTS = 1024 };
+enum { HG_TPS_OK = 0, HG_TPS_SINGULAR = 1, HG_TPS_BAD_INPUT = 2 };
+int hg_tps_layout(int n_points, int n_frames, size_t *record_bytes_per_frame, size_t *solve_scratch_bytes);
+int hg_tps_solve_frames_device(hg_ctx *ctx, const void *d_from, int n_from_sets, const void *d_to, int n_to_sets, int n_points, int n_frames,
+                               double lambda, double *d_records, int32_t *d_status, void *d_scratch);
+int hg_tps_field_layout(const hg_geom *geoms, int n_frames, int step, size_t *scratch_bytes);
+int hg_field_tps_frames_device(hg_ctx *ctx, const double *d_records, int n_points, const hg_geom *geoms, int n_frames, int W, int H,
+                               int format, int step, const size_t *field_offsets, void *d_field, void *d_scratch);
+int hg_points_tps_frames_device(hg_ctx *ctx, const double *d_records, int n_points, int n_frames, const void *d_points, int n_pts, int n_sets,
+                                void *d_out);
 
 /* ------------------------------------------------------------------------------------------------ matching descriptors
  * The matcher that hands hg_fit_matches_frames_device its matches: for every frame a brute-force search of the nearest and second-nearest
