@@ -401,10 +401,11 @@ static int check_remap_frames(hg_ctx *c, const std::string &who, const hg_geom *
 }
 
 // The bilinear and the bicubic frames remap (who: the entry point's name): one check, one table, one staging; cubic == nullptr launches the
-// bilinear kernel, otherwise the bicubic one with those coefficients.
-static int remap_flat_frames(hg_ctx *c, const char *who, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
-                             const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
-                             void *d_out, const size_t *out_offsets, const CubicCoef *cubic)
+// bilinear kernel, otherwise the bicubic one with those coefficients.  compose (hg_api_flow.hip; elem HG_ELEM_F32, channels 2, no cubic): the
+// planes are inner fields and the chained-field kernel takes the bilinear one's place.
+int remap_flat_frames(hg_ctx *c, const char *who, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
+                      const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
+                      void *d_out, const size_t *out_offsets, const CubicCoef *cubic, bool compose)
 {
     HG_TRY(bind(c));
     size_t lvl[32];
@@ -413,13 +414,15 @@ static int remap_flat_frames(hg_ctx *c, const char *who, const hg_geom *geoms, i
     const size_t es = elem == HG_ELEM_F32 ? 4 : 1;
     std::vector<RemapFrame> recs;
     size_t extent = 0;
-    HG_TRY(remap_frame_table(c, geoms, n_frames, 8, field_offsets, es * (size_t)channels, es, out_offsets, n_planes, &recs, &extent));
+    if (compose && misaligned(d_out, 8)) return fail(c, HG_ERR_INVALID, std::string(who) + ": d_out must be aligned to 8 bytes");      // (a field)
+    HG_TRY(remap_frame_table(c, geoms, n_frames, 8, field_offsets, es * (size_t)channels, compose ? 8 : es, out_offsets, n_planes, &recs, &extent));
     if (extent == 0) return HG_OK;
     uint64_t blk_px = 0; uint32_t n_blocks = 0;
     assign_remap_blocks(recs, 1024, &blk_px, &n_blocks);
     HG_TRY(stage_remap_frames(c, recs, d_out, extent));
     const uint8_t *co = static_cast<const uint8_t *>(d_coords), *pl = static_cast<const uint8_t *>(d_planes);
-    if (cubic) launch_remap_bicubic_frames(c->d_remap_frames, n_frames, n_blocks, blk_px, *cubic, co, pl, plane_stride_bytes, W, H, elem, channels, static_cast<uint8_t *>(d_out), c->stream);
+    if (compose) launch_field_compose_frames(c->d_remap_frames, n_frames, n_blocks, blk_px, co, pl, plane_stride_bytes, W, H, static_cast<uint8_t *>(d_out), c->stream);
+    else if (cubic) launch_remap_bicubic_frames(c->d_remap_frames, n_frames, n_blocks, blk_px, *cubic, co, pl, plane_stride_bytes, W, H, elem, channels, static_cast<uint8_t *>(d_out), c->stream);
     else launch_remap_bilinear_frames(c->d_remap_frames, RemapFrame{}, n_frames, n_blocks, blk_px, co, pl, plane_stride_bytes, W, H, elem, channels, static_cast<uint8_t *>(d_out), c->stream);
     HIP_TRY(c, hipGetLastError());
     return HG_OK;
@@ -430,7 +433,7 @@ extern "C" int hg_remap_bilinear_frames_device(hg_ctx *c, const hg_geom *geoms, 
                                                void *d_out, const size_t *out_offsets)
 {
     return remap_flat_frames(c, "hg_remap_bilinear_frames_device", geoms, n_frames, d_coords, field_offsets, d_planes, W, H, n_planes, plane_stride_bytes,
-                             elem, channels, d_out, out_offsets, nullptr);
+                             elem, channels, d_out, out_offsets, nullptr, false);
 }
 
 // The coefficients of the (B, C) cubic: in double from (double)B and (double)C in the header's written order, each rounded once to f32.
@@ -456,7 +459,7 @@ extern "C" int hg_remap_bicubic_frames_device(hg_ctx *c, const hg_geom *geoms, i
     if (!(C >= 0.0f && C <= 1.0f)) return fail(c, HG_ERR_INVALID, "hg_remap_bicubic_frames_device: C must lie in [0, 1]");
     const CubicCoef k = cubic_coefficients(B, C);
     return remap_flat_frames(c, "hg_remap_bicubic_frames_device", geoms, n_frames, d_coords, field_offsets, d_planes, W, H, n_planes, plane_stride_bytes,
-                             elem, channels, d_out, out_offsets, &k);
+                             elem, channels, d_out, out_offsets, &k, false);
 }
 
 extern "C" int hg_remap_bilinear_u8_device(hg_ctx *c, const void *d_coords, size_t n_px, const uint8_t *d_src, int W, int H, int channels, uint8_t *d_out)

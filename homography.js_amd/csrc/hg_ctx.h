@@ -341,6 +341,10 @@ inline int bind(hg_ctx *c)
 int time_begin(hg_ctx *c);                                   // hg_api.hip: event pair around the dominant kernel (hg_set_timing)
 int time_end(hg_ctx *c);
 int fill_frames(hg_ctx *c, std::vector<FrameDesc> &v, const hg_geom *geoms, const size_t *offs, int n);      // hg_api.hip
+// hg_api_field.hip: the bilinear / bicubic frames remap behind its entry points; compose: the chained field of hg_field_compose_frames_device
+int remap_flat_frames(hg_ctx *c, const char *who, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
+                      const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
+                      void *d_out, const size_t *out_offsets, const CubicCoef *cubic, bool compose);
 // The bytes a frame list writes from its output pointer on, and a hash of its (offset, size) pairs (0 is never returned).
 void output_layout(const std::vector<FrameDesc> &frames, size_t *extent, uint64_t *layout);                  // hg_api.hip
 // Before a call writes [out, out + extent): queued runs whose deferred redo could land on those bytes later are settled now, unless

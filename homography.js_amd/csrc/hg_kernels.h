@@ -9,6 +9,7 @@
 #include "hg_remap_records.h"
 #include "hg_align_dev.h"
 #include "hg_tps_dev.h"
+#include "hg_flow_dev.h"
 
 namespace hg {
 
@@ -303,6 +304,15 @@ void launch_align(const AlignArgs &a, hipStream_t stream);
 void launch_tps_solve(const TpsSolveArgs &a, hipStream_t stream);
 void launch_tps_field(const TpsFieldArgs &a, int fmt, hipStream_t stream);
 void launch_tps_points(const double *records, int n_points, int n_frames, const float *points, int n_pts, int n_sets, float *out, hipStream_t stream);
+
+// Dense optical flow (hg_k_flow.hip; the rules and the argument blocks: hg_flow_dev.h): k_flow_up, the flow of a level from the level below it;
+// k_flow_iter, one Jacobi iteration of a level over tiles of kFlowTileW x kFlowTileH pixels; k_flow_finish, field, flow pairs and residual of
+// level 0.  k_field_compose_frames: the bilinear frames remap's launch over an inner field as a 2-channel f32 plane, NaN pattern where not finite.
+void launch_flow_up(const FlowUpArgs &a, int n_frames, hipStream_t stream);
+void launch_flow_iter(const FlowIterArgs &a, int n_frames, hipStream_t stream);
+void launch_flow_finish(const FlowFinishArgs &a, int n_frames, hipStream_t stream);
+void launch_field_compose_frames(const RemapFrame *frames, int n_frames, uint32_t n_blocks, uint64_t blk_px, const uint8_t *outer, const uint8_t *inner,
+                                 size_t inner_stride, int W, int H, uint8_t *out, hipStream_t stream);
 
 // Matching descriptors (hg_k_match.hip; the rules: hg_match_dev.h): k_match_bits resp. k_match_u8 for the two nearest train rows of every query,
 // the same kernel with the sides swapped for the best query of every train row (cross_check), then k_match_finish.  query = F lists of

@@ -1398,6 +1398,80 @@ static napi_value fn_warp_thin_plate(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* denseFlow(handle, from, to, W, H, channels, nFrames, nToSets, levels, iterations, radius, minEig, maxUpdate, flags): dense optical flow
+ * between nFrames pairs of u8 planes (hg_flow_dense_frames_device), all on the device.  from: Uint8Array of nFrames planes of W x H x
+ * channels, to: Uint8Array of nToSets planes (frame f is registered onto plane f % nToSets).  flags: 1 = the field comes down, 2 = the
+ * residual, 4 = the good flags, 8 = the FROM planes sent through the field by hg_remap_bilinear_frames_device (u8 x channels).  Returns
+ * { field: Float32Array(F x W x H x 2) | null, residual: Uint8Array(F x W x H) | null, good: Uint8Array | null, images: Uint8Array(F x W x
+ * H x channels) | null }, every frame tightly packed.  Only what was asked for comes down. */
+static napi_value fn_dense_flow(napi_env env, napi_callback_info info)
+{
+    napi_value a[14];
+    if (!get_args(env, info, 14, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    int W, H, ch, F, S, levels, n_iter, radius, flags; size_t n_f = 0, n_t = 0; double min_eig, max_update;
+    uint8_t *from = (uint8_t *)get_typed(env, a[1], napi_uint8_array, &n_f, "from"); if (!from && n_f) return NULL;
+    uint8_t *to = (uint8_t *)get_typed(env, a[2], napi_uint8_array, &n_t, "to"); if (!to && n_t) return NULL;
+    if (!get_i32(env, a[3], &W) || !get_i32(env, a[4], &H) || !get_i32(env, a[5], &ch) || !get_i32(env, a[6], &F) || !get_i32(env, a[7], &S) ||
+        !get_i32(env, a[8], &levels) || !get_i32(env, a[9], &n_iter) || !get_i32(env, a[10], &radius)) return NULL;
+    if (napi_get_value_double(env, a[11], &min_eig) != napi_ok || napi_get_value_double(env, a[12], &max_update) != napi_ok)
+        return throw_str(env, "hgwarp: minEig and maxUpdate must be numbers");
+    if (!get_i32(env, a[13], &flags)) return NULL;
+    if (W < 1 || W > 32768 || H < 1 || H > 32768 || (ch != 1 && ch != 4) || F < 0 || F > 4096 || S < 1 || flags < 0 || flags > 15)
+        return throw_str(env, "hgwarp: denseFlow: the size, channels, frame counts or flags are out of range");
+    const size_t n_px = (size_t)W * (size_t)H, plane = n_px * (size_t)ch, NF = (size_t)F;
+    if (n_f != plane * NF || n_t != plane * (size_t)S) return throw_str(env, "hgwarp: denseFlow: from / to must hold their planes of W x H x channels bytes");
+    size_t scr_b = 0;
+    int rc = hg_flow_layout(W, H, ch, F, S, levels, &scr_b);
+    if (rc != HG_OK) return throw_hg(env, h->ctx, "hg_flow_layout", rc);
+    void *p_fld = NULL, *p_res = NULL, *p_good = NULL, *p_img = NULL;
+    napi_value out, v_fld, v_res, v_good, v_img;
+    if (flags & 1) { if (!(v_fld = make_typed(env, napi_float32_array, NF * n_px * 2, 4, &p_fld))) return NULL; } else NAPI_OK(napi_get_null(env, &v_fld));
+    if (flags & 2) { if (!(v_res = make_typed(env, napi_uint8_array, NF * n_px, 1, &p_res))) return NULL; } else NAPI_OK(napi_get_null(env, &v_res));
+    if (flags & 4) { if (!(v_good = make_typed(env, napi_uint8_array, NF * n_px, 1, &p_good))) return NULL; } else NAPI_OK(napi_get_null(env, &v_good));
+    if (flags & 8) { if (!(v_img = make_typed(env, napi_uint8_array, NF * plane, 1, &p_img))) return NULL; } else NAPI_OK(napi_get_null(env, &v_img));
+    NAPI_OK(napi_create_object(env, &out));
+    NAPI_OK(napi_set_named_property(env, out, "field", v_fld)); NAPI_OK(napi_set_named_property(env, out, "residual", v_res));
+    NAPI_OK(napi_set_named_property(env, out, "good", v_good)); NAPI_OK(napi_set_named_property(env, out, "images", v_img));
+    if (!F) return out;
+#define FLOW_PAD(b) (((size_t)(b) + 255) & ~(size_t)255)
+    const size_t fld_frame = FLOW_PAD(n_px * 8), img_frame = FLOW_PAD(plane);
+    const size_t o_from = 0, o_to = o_from + FLOW_PAD(n_f), o_scr = o_to + FLOW_PAD(n_t), o_fld = o_scr + FLOW_PAD(scr_b), o_res = o_fld + fld_frame * NF,
+                 o_good = o_res + FLOW_PAD((flags & 2) ? NF * n_px : 0), o_img = o_good + FLOW_PAD((flags & 4) ? NF * n_px : 0),
+                 total = o_img + ((flags & 8) ? img_frame * NF : 0);
+#undef FLOW_PAD
+    hg_geom *g = (hg_geom *)calloc(NF, sizeof *g);
+    if (!g) return throw_str(env, "hgwarp: out of memory");
+    for (size_t f = 0; f < NF; f++) { g[f].obj_w = W; g[f].obj_h = H; }
+    void *d = NULL;
+    rc = hg_device_alloc(h->ctx, total, &d);
+    if (rc != HG_OK) { napi_value e = throw_hg(env, h->ctx, "hg_device_alloc", rc); free(g); return e; }
+    uint8_t *b = (uint8_t *)d;
+    const char *what = "hg_copy_to_device";
+    rc = hg_copy_to_device(h->ctx, b + o_from, from, n_f);
+    if (rc == HG_OK) rc = hg_copy_to_device(h->ctx, b + o_to, to, n_t);
+    if (rc == HG_OK) {
+        what = "hg_flow_dense_frames_device";
+        rc = hg_flow_dense_frames_device(h->ctx, b + o_from, F, plane, b + o_to, S, plane, W, H, ch, levels, n_iter, radius, min_eig, max_update, NULL, b + o_fld,
+                                         NULL, (flags & 2) ? b + o_res : NULL, (flags & 4) ? b + o_good : NULL, b + o_scr);
+    }
+    if (rc == HG_OK && (flags & 8)) {
+        what = "hg_remap_bilinear_frames_device";
+        rc = hg_remap_bilinear_frames_device(h->ctx, g, F, b + o_fld, NULL, b + o_from, W, H, F, plane, HG_ELEM_U8, ch, b + o_img, NULL);
+    }
+    free(g);
+    what = rc == HG_OK ? "hg_copy_to_host" : what;
+    for (size_t f = 0; f < NF && rc == HG_OK; f++) {
+        if (flags & 1) rc = hg_copy_to_host(h->ctx, (uint8_t *)p_fld + f * n_px * 8, b + o_fld + f * fld_frame, n_px * 8);
+        if (rc == HG_OK && (flags & 8)) rc = hg_copy_to_host(h->ctx, (uint8_t *)p_img + f * plane, b + o_img + f * img_frame, plane);
+    }
+    if (rc == HG_OK && (flags & 2)) rc = hg_copy_to_host(h->ctx, p_res, b + o_res, NF * n_px);
+    if (rc == HG_OK && (flags & 4)) rc = hg_copy_to_host(h->ctx, p_good, b + o_good, NF * n_px);
+    if (rc != HG_OK) { napi_value e = throw_hg(env, h->ctx, what, rc); hg_device_free(h->ctx, d); return e; }
+    HG_CALL(h->ctx, "hg_device_free", hg_device_free(h->ctx, d));
+    return out;
+}
+
 /* matchDescriptors(handle, kind, descBytes, stride, query, nQuery, countsQ, train, nTrain, countsT, ratio, maxDistance, crossCheck,
  * queryPoints | null, trainPoints | null): the accepted nearest-neighbour pairs of every frame (hg_match_descriptors_frames_device).  query:
  * Uint8Array of F x nQuery x stride, F = countsQ.length; train: Uint8Array of S x nTrain x stride, S = countsT.length; the points: Float32Array
@@ -2265,6 +2339,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "fitMatches", fn_fit_matches },
         { "alignBegin", fn_align_begin }, { "alignLevel", fn_align_level }, { "alignScaleMatrix", fn_align_scale_matrix }, { "alignEnd", fn_align_end },
         { "warpThinPlate", fn_warp_thin_plate },
+        { "denseFlow", fn_dense_flow },
         { "matchDescriptors", fn_match_descriptors },
         { "detectAndDescribe", fn_detect_describe },
         { "solveAffineTriangles", fn_solve_affine_triangles }, { "warpInversePiecewiseState", fn_warp_inverse_piecewise_state },

@@ -77,6 +77,7 @@ EXPORTS = [
     "hg_fit_sample_indices", "hg_fit_matches_frames_device",
     "hg_align_scale_matrix", "hg_align_refine_frames_device",
     "hg_tps_layout", "hg_tps_solve_frames_device", "hg_tps_field_layout", "hg_field_tps_frames_device", "hg_points_tps_frames_device",
+    "hg_flow_layout", "hg_flow_dense_frames_device", "hg_field_compose_frames_device",
     "hg_match_descriptors_frames_device",
     "hg_detect_layout", "hg_describe_pattern", "hg_detect_describe_frames_device",
     "hg_mosaic_multiband_layout", "hg_mosaic_multiband_device",
@@ -204,6 +205,9 @@ def lib():
         "hg_tps_field_layout": (i, [C.POINTER(Geom), i, i, C.POINTER(sz)]),
         "hg_field_tps_frames_device": (i, [vp, vp, i, C.POINTER(Geom), i, i, i, i, i, C.POINTER(sz), vp, vp]),
         "hg_points_tps_frames_device": (i, [vp, vp, i, i, vp, i, i, vp]),
+        "hg_flow_layout": (i, [i, i, i, i, i, i, C.POINTER(sz)]),
+        "hg_flow_dense_frames_device": (i, [vp, vp, i, sz, vp, i, sz, i, i, i, i, i, i, d, d, C.POINTER(sz), vp, vp, vp, vp, vp]),
+        "hg_field_compose_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, i, i, i, sz, vp, C.POINTER(sz)]),
         "hg_match_descriptors_frames_device": (i, [vp, i, i, sz, vp, i, C.POINTER(C.c_int32), i, vp, i, C.POINTER(C.c_int32), i, d, C.c_uint32, i,
                                                    vp, vp, vp, vp, vp, vp]),
         "hg_detect_layout": (i, [i, i, i, i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -381,6 +385,23 @@ def tps_field_layout(geoms, step):
     total = C.c_size_t(0)
     _check(lib().hg_tps_field_layout(_geoms(geoms) if len(geoms) else None, len(geoms), int(step), C.byref(total)))
     return total.value
+
+
+def flow_layout(w, h, channels, n_frames, n_to_sets, levels):
+    """Scratch bytes of hg_flow_dense_frames_device: the luma copies of 4-channel planes, the pyramids of both plane sets and two flow
+    buffers per level."""
+    total = C.c_size_t()
+    _check(lib().hg_flow_layout(int(w), int(h), int(channels), int(n_frames), int(n_to_sets), int(levels), C.byref(total)))
+    return total.value
+
+
+def flow_default_levels(w, h):
+    """The default number of levels of a flow: as many as leave the coarsest level at least 16 pixels on its shorter side (at least 1, at most 12)."""
+    n, s = 1, min(int(w), int(h))
+    while n < 12 and ((s + 1) >> 1) >= 16:
+        s = (s + 1) >> 1
+        n += 1
+    return n
 
 
 def pyramid_levels(w, h):
@@ -1037,6 +1058,32 @@ class Context:
         f % n_sets); d_out gets n_frames x n_pts (x, y) float32, NaN / NaN for a position that is not finite or a failed frame.  Asynchronous."""
         vp = lambda v: C.c_void_p(int(v) or None)
         self._c(lib().hg_points_tps_frames_device(self._h, vp(d_records), int(n_points), int(n_frames), vp(d_points), int(n_pts), int(n_sets), vp(d_out)))
+
+    def flow_dense_frames_device(self, d_from, n_frames, d_to, n_to_sets, w, h, channels, d_field, d_scratch, levels=None, n_iter=4, radius=3,
+                                 min_eig=1.0, max_update=1.0, field_offsets=None, d_flow=0, d_residual=0, d_good=0, from_stride_bytes=None,
+                                 to_stride_bytes=None):
+        """hg_flow_dense_frames_device: pyramidal dense Lucas-Kanade between n_frames pairs of u8 planes (w x h x channels, 1 or 4): FROM plane f
+        is registered onto TO plane f % n_to_sets.  d_field gets, per frame, a FIELD_COORDS field over TO's grid whose values are FROM positions
+        (the NaN pattern where they leave the plane); d_flow (0: not wanted) the raw (u, v) pairs at the field's offsets, d_residual one byte per
+        pixel, d_good the level-0 good flags.  levels=None: flow_default_levels(w, h); d_scratch: flow_layout's bytes.  Asynchronous."""
+        vp = lambda v: C.c_void_p(int(v) or None)
+        fo = (C.c_size_t * int(n_frames))(*field_offsets) if field_offsets is not None else None
+        fs = int(w) * int(h) * int(channels) if from_stride_bytes is None else int(from_stride_bytes)
+        ts = int(w) * int(h) * int(channels) if to_stride_bytes is None else int(to_stride_bytes)
+        self._c(lib().hg_flow_dense_frames_device(self._h, vp(d_from), int(n_frames), fs, vp(d_to), int(n_to_sets), ts, int(w), int(h), int(channels),
+                                                  flow_default_levels(w, h) if levels is None else int(levels), int(n_iter), int(radius),
+                                                  float(min_eig), float(max_update), fo, vp(d_field), vp(d_flow), vp(d_residual), vp(d_good),
+                                                  vp(d_scratch)))
+
+    def field_compose_frames_device(self, geoms, d_outer, d_inner, wi, hi, n_inner, inner_stride_bytes, d_out, outer_offsets=None, out_offsets=None):
+        """hg_field_compose_frames_device: the FIELD_COORDS fields at d_outer chained with the inner fields (wi x hi pairs each, frame f reads
+        inner field f % n_inner): the bilinear frames remap of the inner field as a 2-channel float32 plane where the outer coordinate and both
+        results are finite, the NaN pattern elsewhere.  Arguments as remap_bilinear_frames_device.  Asynchronous."""
+        fo = (C.c_size_t * len(geoms))(*outer_offsets) if outer_offsets is not None else None
+        oo = (C.c_size_t * len(geoms))(*out_offsets) if out_offsets is not None else None
+        vp = lambda v: C.c_void_p(int(v) or None)
+        self._c(lib().hg_field_compose_frames_device(self._h, _geoms(geoms) if len(geoms) else None, len(geoms), vp(d_outer), fo, vp(d_inner), int(wi),
+                                                     int(hi), int(n_inner), int(inner_stride_bytes), vp(d_out), oo))
 
     def match_descriptors_frames_device(self, kind, desc_bytes, stride, d_query, n_query, counts_q, n_frames, d_train, n_train, counts_t, n_train_sets,
                                         d_counts, ratio=0.8, max_distance=0xffffffff, cross_check=False, d_query_pts=0, d_train_pts=0, d_matches=0,

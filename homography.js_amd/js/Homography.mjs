@@ -711,6 +711,72 @@ class Homography {
     }
 
     /**
+     * Dense optical flow between pairs of pictures: a per-pixel, non-parametric registration for what a homography cannot follow --
+     * parallax, a rolling shutter, things that move (not part of the reference; hg_flow_dense_frames_device in include/hgwarp.h has the
+     * rule, pyramidal Lucas-Kanade with integer window sums, exact to the bit).
+     * fromImages / toImages: arrays of Uint8Arrays of equal size, width x height x channels bytes each; picture f of fromImages is
+     * registered onto picture f % toImages.length of toImages.
+     * options: { width, height (required), channels = 4 (RGBA; 1: grey), levels (default: as many as leave the coarsest level at least 16
+     *            pixels on its shorter side), iterations = 4 (1..32 per level), radius = 3 (1..7: the window is 2 radius + 1 pixels a side),
+     *            minEig = 1 (>= 0: the smallest per-pixel gradient eigenvalue a window may have and still be solved), maxUpdate = 1 ((0, 4]:
+     *            the cap on the change of one iteration, pixels), residual = false, good = false, warp = false,
+     *            field (default: true without warp, false with it) }.
+     * Returns { field, width, height, frames, residual?, good?, images? }: field is a Float32Array of frames x width x height x, y pairs
+     * over toImages' pixel grid whose values are positions in the FROM picture (NaN where they leave it) -- what the remaps and the
+     * mosaics read --, or null when it was not asked for; residual and good one byte per pixel; images (warp: true) the FROM pictures sent
+     * through the field by the bilinear remap on the device, one Uint8Array per frame.
+     * Needs no image and changes no state of the instance.  Throws a bare string for pictures of the wrong size and options out of range.
+     */
+    denseFlow(fromImages, toImages, options = {}) {
+        if (options === null || options === undefined) options = {};
+        const isInt = (v) => Number.isInteger(v);
+        const W = options.width, H = options.height;
+        if (!isInt(W) || !isInt(H) || W < 1 || H < 1 || W > 32768 || H > 32768 || W * H > 2 ** 30) throw ("denseFlow: options.width and options.height must be integers in 1..32768");
+        const channels = options.channels === undefined ? 4 : options.channels;
+        if (channels !== 1 && channels !== 4) throw ("denseFlow: options.channels must be 1 or 4");
+        let top = 1;
+        for (let w = W, h = H; w > 1 || h > 1; top++) { w = (w + 1) >> 1; h = (h + 1) >> 1; }
+        let levels = options.levels;
+        if (levels === undefined) {
+            levels = 1;
+            for (let s = Math.min(W, H); levels < 12 && ((s + 1) >> 1) >= 16; levels++) s = (s + 1) >> 1;
+        }
+        if (!isInt(levels) || levels < 1 || levels > Math.min(top, 12)) throw ("denseFlow: options.levels must be an integer in 1.." + Math.min(top, 12));
+        const iterations = options.iterations === undefined ? 4 : options.iterations;
+        if (!isInt(iterations) || iterations < 1 || iterations > 32) throw ("denseFlow: options.iterations must be an integer in 1..32");
+        const radius = options.radius === undefined ? 3 : options.radius;
+        if (!isInt(radius) || radius < 1 || radius > 7) throw ("denseFlow: options.radius must be an integer in 1..7");
+        const minEig = options.minEig === undefined ? 1 : options.minEig;
+        if (typeof minEig !== 'number' || !Number.isFinite(minEig) || minEig < 0) throw ("denseFlow: options.minEig must be a finite number >= 0");
+        const maxUpdate = options.maxUpdate === undefined ? 1 : options.maxUpdate;
+        if (typeof maxUpdate !== 'number' || !(maxUpdate > 0) || !(maxUpdate <= 4)) throw ("denseFlow: options.maxUpdate must lie in (0, 4]");
+        const plane = W * H * channels;
+        const pack = (images, name) => {
+            if (!Array.isArray(images)) throw ("denseFlow: " + name + " must be an array of Uint8Arrays");
+            const all = new Uint8Array(images.length * plane);
+            images.forEach((im, k) => {
+                if (!(im instanceof Uint8Array) && !(im instanceof Uint8ClampedArray)) throw ("denseFlow: " + name + "[" + k + "] must be a Uint8Array");
+                if (im.length !== plane) throw ("denseFlow: " + name + "[" + k + "] must hold width x height x channels = " + plane + " bytes, but holds " + im.length);
+                all.set(im, k * plane);
+            });
+            return all;
+        };
+        const from = pack(fromImages, 'fromImages'), to = pack(toImages, 'toImages');
+        const F = fromImages.length, S = toImages.length;
+        if (F > 4096) throw ("denseFlow: at most 4096 frames");
+        if (S < 1 || S > Math.max(F, 1)) throw ("denseFlow: toImages must hold between 1 and fromImages.length pictures");
+        const warp = options.warp === true;
+        const wantField = options.field === undefined ? !warp : options.field === true;
+        const flags = (wantField ? 1 : 0) | (options.residual === true ? 2 : 0) | (options.good === true ? 4 : 0) | (warp ? 8 : 0);
+        const r = this._native.denseFlow(this._ctx, from, to, W, H, channels, F, S, levels, iterations, radius, minEig, maxUpdate, flags);
+        const out = { field: r.field, width: W, height: H, frames: F };
+        if (options.residual === true) out.residual = r.residual;
+        if (options.good === true) out.good = r.good;
+        if (warp) out.images = Array.from({ length: F }, (_, f) => r.images.slice(f * plane, (f + 1) * plane));
+        return out;
+    }
+
+    /**
      * The descriptors matchDescriptors() starts from: the keypoints of a set of pictures -- Harris corners in integer arithmetic, the best
      * perCell of every cell x cell cell of the picture, an orientation and a 256-bit binary descriptor each (not part of the reference;
      * hg_detect_describe_frames_device in include/hgwarp.h has the rules, all of them exact).  It is not ORB: both sides of a match have to

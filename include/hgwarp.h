@@ -41,7 +41,8 @@ extern "C" {
                                    hg_mosaic_overlap_stats_device, fitting transforms to matches by that of hg_fit_matches_frames_device);
                                    matching descriptors by the presence of hg_match_descriptors_frames_device, keypoints by the presence of
                                    hg_detect_describe_frames_device, multi-band mosaics by the presence of hg_mosaic_multiband_device, thin-plate splines
-                                   by the presence of hg_tps_solve_frames_device, refining transforms on the pixels by the presence of
+                                   by the presence of hg_tps_solve_frames_device, dense optical flow by the presence of
+                                   hg_flow_dense_frames_device, refining transforms on the pixels by the presence of
                                    hg_align_refine_frames_device */
 
 enum {
@@ -980,6 +981,92 @@ int hg_field_tps_frames_device(hg_ctx *ctx, const double *d_records, int n_point
                                int format, int step, const size_t *field_offsets, void *d_field, void *d_scratch);
 int hg_points_tps_frames_device(hg_ctx *ctx, const double *d_records, int n_points, int n_frames, const void *d_points, int n_pts, int n_sets,
                                 void *d_out);
+
+/* ------------------------------------------------------------------------------------------------ dense optical flow
+ * Every registration above is parametric: six or eight numbers per frame, or landmarks somebody supplies.  Parallax, a rolling shutter and
+ * things that move do not fit them.  hg_flow_dense_frames_device registers two pictures PER PIXEL -- pyramidal dense Lucas-Kanade -- and
+ * writes the result as a HG_FIELD_COORDS source field, which every remap, the mosaics and the multi-band blend read.  Not part of the
+ * reference.  It needs no image, mesh or frame set.
+ * PLANES.  n_frames pairs of u8 planes of one size W x H, `channels` 1 or 4, interleaved; FROM plane f lies at d_from + f * from_stride_bytes,
+ * TO plane s at d_to + s * to_stride_bytes, and FROM plane f is registered onto TO plane f % n_to_sets (the set rule of the matcher and the
+ * aligner).  With 4 channels every pixel is first reduced to the integer luma of the detector and the aligner, (77 R + 150 G + 29 B + 128)
+ * >> 8, into scratch; below, T and F are those one-byte planes.  The result of frame f is a field over TO's pixel grid whose values are FROM
+ * positions: gathering FROM plane f through it with any remap gives FROM registered to TO.
+ * All window sums are INTEGER sums, so their order is free, tiling cannot change a bit, and two runs give the same bytes.  Everything else is
+ * f32 or f64 in the written order, IEEE division, ties to even, contraction off: a numpy model of this text matches the device byte for byte.
+ * PYRAMIDS.  Levels 0 .. levels-1 of both luma planes are exactly what hg_pyramid_build_device builds of a one-channel u8 plane: level k+1
+ * pixel (x, y) = ((a + b) + (c + d) + 2) >> 2 over columns min(2x, Wk-1), min(2x+1, Wk-1) and rows alike of level k, sizes (n + 1) >> 1.  The
+ * call builds them itself, in scratch.
+ * WALK, from level levels-1 down to level 0.  On a level, T and F are TO's and FROM's level of Wk x Hk pixels, and (u, v) is one f32 pair per
+ * pixel.
+ *   START.  The coarsest level starts from u = v = 0.  A finer level takes the flow of the level below it -- the (u, v) pairs as a 2-channel
+ *     f32 plane of that level's size -- at cx = ((float)x + 0.5f) * 0.5f - 0.5f, cy alike, blended by exactly the rule of
+ *     hg_remap_bilinear_f32_device (floorf, fraction, taps clamped in float, that operation order), each part then multiplied by 2.0f.
+ *   GRADIENTS.  gx(q) = T(min(x+1, Wk-1), y) - T(max(x-1, 0), y), gy alike: integers in -255..255, TWICE the central difference.
+ *     Gxx, Gxy, Gyy = the sums of gx gx, gx gy, gy gy over the window |dx|, |dy| <= radius around the pixel, clipped to the plane; n = the
+ *     number of window pixels inside the plane.
+ *   GOOD.  A pixel is good iff trace = Gxx + Gyy > 0, det = Gxx Gyy - Gxy Gxy > 0 and (double)det >= ((4.0 * n) * min_eig) * (double)trace.
+ *     (det and trace are integers below 2^53, so the doubles are exact; det > 0 follows from the last test unless min_eig is 0, and keeps a
+ *     division by zero out of the solve.)  det / trace lies between lmin / 2 and lmin, lmin being the smaller eigenvalue of the window's
+ *     tensor of twice-gradients; divided by 4 n it is the per-pixel eigenvalue in true-gradient units that min_eig is compared with.
+ *   ONE ITERATION, n_iter of them per level, Jacobi style: every pixel reads the flow of the iteration before.
+ *     1. for every pixel q: s = the f32 bilinear blend (that same rule) of F at ((float)x + u(q), (float)y + v(q));
+ *     2. e = s - (float)T(q), in f32;
+ *     3. e0 = (double)e - (((double)gx * (double)u) + ((double)gy * (double)v)) / 2.0;
+ *     4. eq = llrint(16.0 * e0), ties to even;
+ *     5. for every pixel p, over its clipped window: bx = sum gx eq, by = sum gy eq, in 64-bit integers;
+ *     6. if p is good, in f64: U = -((((double)Gyy * (double)bx) - ((double)Gxy * (double)by)) / (double)det) / 8.0,
+ *                               V = -((((double)Gxx * (double)by) - ((double)Gxy * (double)bx)) / (double)det) / 8.0;
+ *     7. d = U - (double)u, clamped to [-max_update, max_update]; u_new = (float)((double)u + d); v alike;
+ *     8. a pixel that is not good keeps its flow.
+ *   Every pixel's equation is linearised around its OWN flow (step 3 takes the pixel's flow back out), and the window solves for ONE common
+ *   flow.  The cheaper u += -G^-1 sum g e, with e taken at every pixel's own flow, acts on the flow error as identity - box filter, has gain
+ *   above 1 at some frequencies, and diverges (EXPERIMENTS.md, "Dense flow").
+ * OUTPUTS, all asynchronous on the ctx stream.
+ *   d_field     per frame W x H pairs ((float)x + u, (float)y + v) of level 0, in HG_FIELD_COORDS: a pixel is covered iff 0 <= sx < W and
+ *               0 <= sy < H (the f32 values); every other pixel holds 0x7fc00000 in both words.  field_offsets (NULL: packed as
+ *               hg_pack_field_offsets does), the multiple-of-8 rule, alignment and "bytes between frames are never written" are those of
+ *               hg_field_tps_frames_device.
+ *   d_flow      optional (NULL: not wanted): the raw (u, v) pairs with no coverage test, frame f at the same byte offset as in d_field.
+ *   d_residual  optional: one byte per pixel, min(255, floor(|e| + 0.5f)) with e = s - (float)T taken once more at the FINAL level-0 flow;
+ *               frame f at f * W * H.  A plane to threshold into a moving-object mask.
+ *   d_good      optional: one byte per pixel, 1 where the pixel is good on level 0, else 0; frame f at f * W * H.
+ * SCRATCH comes from the caller, as for the multi-band blend; the library allocates nothing.  hg_flow_layout (host only) gives the bytes: the
+ * luma copies of 4-channel planes, the pyramids of both plane sets, and two flow buffers per level.  d_scratch is aligned to 16 bytes.  Only
+ * d_scratch[0, bytes) and the outputs are written.  It may be reused once the call that used it has completed.
+ * DEFAULTS the bindings use (from the model runs in EXPERIMENTS.md, "Dense flow"): levels such that the coarsest level is at least 16 pixels
+ * on its shorter side, 4 iterations, radius 3, min_eig 1, max_update 1.  More iterations do not make the result worse; one level alone
+ * cannot follow a flow of several pixels.
+ * LIMITS (HG_ERR_INVALID), the shape before the context, in this order: W, H outside 1..32768 or W * H > 2^30; channels not 1 or 4; levels
+ * outside 1..min(hg_pyramid_levels(W, H), 12); n_iter outside 1..32; radius outside 1..7; min_eig negative or not finite; max_update outside
+ * (0, 4]; n_frames outside 0..4096; n_to_sets outside 1..max(n_frames, 1); a stride below W * H * channels; then a NULL ctx; then, with
+ * n_frames > 0, a field offset that is no multiple of 8, NULL d_from / d_to / d_field / d_scratch, and misaligned d_field / d_flow (8 bytes) or
+ * d_scratch (16).  n_frames == 0 is HG_OK and nothing is written.  With these limits |u| stays below 4 * 32 * 2^12, |eq| below 2^33, and every
+ * window sum (at most 225 terms of |gx eq| < 2^41) below 2^53.
+ * CONTEXT.  The call settles what hg_align_refine_frames_device settles (queued runs), then is asynchronous on the ctx stream: no host wait
+ * between levels or iterations.  It touches no hg_last_*, no sampling mode, no plan, no policy state and no staged frame set.
+ * COST.  Per pixel and iteration four taps of F, a halo of T and five window sums, formed separably in LDS by one workgroup per 32 x 16
+ * tile; G is re-formed there every iteration instead of being stored.  MEASURED (MI355X, whole call, medians of 9; EXPERIMENTS.md, "Dense
+ * flow"; tools/bench_flow.py): 64 RGBA pairs of 1920 x 1080 against one keyframe at the defaults (7 levels) 14.2 ms, at radius 7 28.6 ms; 8
+ * pairs of 3840 x 2160 (8 levels) 7.2 / 14.4 ms: 5e10 pixel-iterations per second at radius 3, bound by the LDS passes and the 64-bit sums,
+ * not by memory (the time doubles with the window's side).  One iteration of one 1080p frame costs 0.042 ms; a plain torch formulation
+ * (grid_sample + avg_pool2d) 0.75 ms on the same GPU.  99.4 % of the pixels of those smooth pictures are good at radius 3.
+ *
+ * hg_field_compose_frames_device CHAINS two fields.  Flow is computed between pictures that were registered roughly before -- FROM warped
+ * through a fitted homography's field --, and to feed a mosaic the flow field must be chained with that field: out(p) = inner(outer(p)).
+ * Per pixel of frame f, where the outer coordinate is finite and both blended parts are finite, the result is that of
+ * hg_remap_bilinear_frames_device with elem = HG_ELEM_F32 and channels = 2 on inner field f % n_inner (Wi x Hi pairs at d_inner +
+ * (f % n_inner) * inner_stride_bytes), bit for bit; everywhere else -- a NaN or infinite outer coordinate, which that remap answers with 0, "covered,
+ * pixel (0, 0)" to a consumer; an inner tap that is NaN or infinite -- both words hold 0x7fc00000.  Arguments, offsets (out_offsets: multiples
+ * of 8, NULL: packed as hg_pack_field_offsets does), refusals and settling are those of hg_remap_bilinear_frames_device; d_out is aligned to 8. */
+int hg_flow_layout(int W, int H, int channels, int n_frames, int n_to_sets, int levels, size_t *scratch_bytes);
+int hg_flow_dense_frames_device(hg_ctx *ctx, const void *d_from, int n_frames, size_t from_stride_bytes, const void *d_to, int n_to_sets,
+                                size_t to_stride_bytes, int W, int H, int channels, int levels, int n_iter, int radius, double min_eig,
+                                double max_update, const size_t *field_offsets, void *d_field, void *d_flow, void *d_residual, void *d_good,
+                                void *d_scratch);
+int hg_field_compose_frames_device(hg_ctx *ctx, const hg_geom *geoms, int n_frames, const void *d_outer, const size_t *outer_offsets,
+                                   const void *d_inner, int Wi, int Hi, int n_inner, size_t inner_stride_bytes, void *d_out,
+                                   const size_t *out_offsets);
 
 /* ------------------------------------------------------------------------------------------------ matching descriptors
  * The matcher that hands hg_fit_matches_frames_device its matches: for every frame a brute-force search of the nearest and second-nearest
