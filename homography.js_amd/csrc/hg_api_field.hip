@@ -626,6 +626,43 @@ extern "C" int hg_mosaic_frames_gain_device(hg_ctx *c, const hg_geom *geoms, int
                          feather, canvas, d_canvas, d_weight, n_frames > 0 ? gains : nullptr);
 }
 
+// ------------------------------------------------------------------------------------------------ the robust mosaic
+// The mosaic's entry with an order statistic for a blend: its checks in its order (those that do not apply -- elem, W, H, feather -- left
+// out), then this entry's own.  u8 only.
+extern "C" int hg_mosaic_robust_device(hg_ctx *c, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
+                                       const void *d_frames, const size_t *frame_offsets, int channels, int mode, float trim, const float *gains,
+                                       hg_geom canvas, void *d_canvas, float *d_weight)
+{
+    HG_TRY(bind(c));
+    const char *what = "hg_mosaic_robust_device";
+    const std::string fn(what);
+    if (n_frames < 0 || n_frames > 65535) return fail(c, HG_ERR_INVALID, fn + ": n_frames must be 0..256");
+    if (!d_canvas) return fail(c, HG_ERR_INVALID, fn + ": d_canvas is NULL");
+    if (channels < 1 || channels > 4) return fail(c, HG_ERR_INVALID, fn + ": channels must be 1..4");
+    if (n_frames > 0 && (!geoms || !d_coords || !d_frames)) return fail(c, HG_ERR_INVALID, fn + ": NULL pointer");
+    if (misaligned(d_coords, 8) || misaligned(d_weight, 4)) return fail(c, HG_ERR_INVALID, fn + ": d_coords must be aligned to 8 bytes, d_weight to 4");
+    std::vector<MosaicFrame4> quads;
+    if (const int rc = mosaic_table(c, what, geoms, n_frames, field_offsets, frame_offsets, 1, (size_t)channels, canvas, &quads))
+        return c->err.find(fn) == std::string::npos ? fail(c, rc, fn + ": " + c->err) : rc;       // (the shared checks do not all name their caller)
+    if (n_frames > 256) return fail(c, HG_ERR_INVALID, fn + ": n_frames must be 0..256");
+    if (mode != HG_ROBUST_MEDIAN && mode != HG_ROBUST_TRIMMED && mode != HG_ROBUST_MIN && mode != HG_ROBUST_MAX)
+        return fail(c, HG_ERR_INVALID, fn + ": unknown mode (HG_ROBUST_MEDIAN, HG_ROBUST_TRIMMED, HG_ROBUST_MIN or HG_ROBUST_MAX)");
+    if (mode == HG_ROBUST_TRIMMED && !(trim >= 0.0f && trim < 0.5f)) return fail(c, HG_ERR_INVALID, fn + ": trim must lie in [0, 0.5)");
+    if (n_frames == 0) gains = nullptr;
+    for (int f = 0; gains && f < n_frames; f++)
+        if (!(gains[f] > 0.0f) || !std::isfinite(gains[f])) return fail(c, HG_ERR_INVALID, fn + ": every gain must be finite and > 0");
+    const size_t n_px = frame_px(canvas.obj_w, canvas.obj_h);
+    if (n_px == 0) return HG_OK;
+    HG_TRY(settle_pending_on(c, d_canvas, n_px * (size_t)channels));
+    if (d_weight) HG_TRY(settle_pending_on(c, d_weight, n_px * 4));
+    const float *d_gains = nullptr;
+    HG_TRY(upload_mosaic_table(c, quads, gains, n_frames, &d_gains));
+    launch_mosaic_robust(c->d_mosaic_frames, n_frames, static_cast<const uint8_t *>(d_coords), static_cast<const uint8_t *>(d_frames), channels, mode, trim,
+                         canvas.x_off, canvas.y_off, canvas.obj_w, canvas.obj_h, static_cast<uint8_t *>(d_canvas), d_weight, d_gains, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return HG_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ exposure: overlap statistics and the gain solve
 extern "C" int hg_mosaic_overlap_stats_device(hg_ctx *c, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
                                               const void *d_frames, const size_t *frame_offsets, int channels, hg_geom canvas, uint64_t *d_stats)

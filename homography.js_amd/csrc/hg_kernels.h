@@ -249,6 +249,12 @@ void launch_mosaic_frames(const MosaicFrame4 *frames, int n_quads, const uint8_t
 // (the caller zeroes them) with 64-bit vector atomics.  The mosaic's tiling and table.
 void launch_mosaic_stats(const MosaicFrame4 *frames, int n_frames, const uint8_t *coords, const uint8_t *pixels, int channels, int cx, int cy, int cw,
                          int ch, uint64_t *stats, hipStream_t stream);
+// k_mosaic_robust<channels> (hg_k_robust.hip; the rules: hg_robust_dev.h; hg_mosaic_robust_device): every pixel of the canvas window from the
+// n_frames (<= 256) u8 frames that cover it -- per channel the median (mode 0), a mean trimmed by `trim` at both ends (1), the minimum (2)
+// or the maximum (3) of the contributors' bytes; weight (or nullptr): their number.  gains (or nullptr): one factor per record of the table.
+// The mosaic's tiling and table; n_frames == 0 zeroes the canvas.
+void launch_mosaic_robust(const MosaicFrame4 *frames, int n_frames, const uint8_t *coords, const uint8_t *pixels, int channels, int mode, float trim,
+                          int cx, int cy, int cw, int ch, uint8_t *canvas, float *weight, const float *gains, hipStream_t stream);
 
 // The multi-band mosaic (hg_k_multiband.hip; the rules: hg_multiband_dev.h; include/hgwarp.h hg_mosaic_multiband_device): k_mb_label over the
 // quad table of the mosaic, k_mb_seed, one k_mb_reduce<element, channels, FIRST> per level 1..L-1 and one k_mb_blend<element, channels, LAST>

@@ -1932,16 +1932,19 @@ static napi_value fn_warp_inverse_geometric_batch(napi_env env, napi_callback_in
  * mosaicMultibandInverseGeometric(ctx, kind, from, to, geoms, bands, feather, canvas, wantWeight, W, H, wantLabels [, exposure]) /
  * mosaicMultibandInversePiecewise(ctx, dstPoints, geoms, bands, feather, canvas, wantWeight, W, H, wantLabels [, exposure]): the same with
  * hg_mosaic_multiband_device as the blend (`bands` in the place of the mode, feather ranks the frames).  The work area is allocated for the
- * call and freed behind it; with wantLabels the result carries labels: Int32Array, the owner of every canvas pixel or -1. */
+ * call and freed behind it; with wantLabels the result carries labels: Int32Array, the owner of every canvas pixel or -1.
+ * mosaicRobustInverseGeometric(ctx, kind, from, to, geoms, mode, trim, canvas, wantWeight, W, H [, exposure]) /
+ * mosaicRobustInversePiecewise(ctx, dstPoints, geoms, mode, trim, canvas, wantWeight, W, H [, exposure]): the plain mosaic's arguments with
+ * hg_mosaic_robust_device as the blend (mode: HG_ROBUST_*, `trim` in the place of the feather; W and H are not read). */
 static napi_value run_mosaic(napi_env env, handle_t *h, const batch_job *job, const int32_t *gv, int F, const napi_value *a, napi_value exposure, const char *what,
-                             napi_value multiband_labels)
+                             napi_value multiband_labels, int robust)
 {
     const hg_geom *g = (const hg_geom *)gv;
     int mode, W, H; double feather; size_t nc; bool want_weight = false, want_labels = false;
     const int multiband = multiband_labels != NULL;         /* then a[0] is the band count */
     if (!get_i32(env, a[0], &mode)) return NULL;
     if (multiband && napi_get_value_bool(env, multiband_labels, &want_labels) != napi_ok) return throw_str(env, "hgwarp: wantLabels must be a boolean");
-    if (napi_get_value_double(env, a[1], &feather) != napi_ok) return throw_str(env, "hgwarp: feather must be a number");
+    if (napi_get_value_double(env, a[1], &feather) != napi_ok) return throw_str(env, robust ? "hgwarp: trim must be a number" : "hgwarp: feather must be a number");
     const int32_t *cv = (const int32_t *)get_typed(env, a[2], napi_int32_array, &nc, "canvas"); if (!cv) return NULL;
     if (nc != 4) return throw_str(env, "hgwarp: canvas must hold x, y, width, height");
     if (napi_get_value_bool(env, a[3], &want_weight) != napi_ok) return throw_str(env, "hgwarp: wantWeight must be a boolean");
@@ -2019,7 +2022,10 @@ static napi_value run_mosaic(napi_env env, handle_t *h, const batch_job *job, co
                                                          d_weight, want_labels ? (int32_t *)d_mb : NULL, exposure ? (const float *)gdata : NULL,
                                                          (uint8_t *)d_mb + lb, work);
         if (rc == HG_OK && want_labels) rc = hg_copy_to_host(h->ctx, ldata, d_mb, n * 4);
-    } else if (rc == HG_OK)
+    } else if (rc == HG_OK && robust)
+        rc = hg_mosaic_robust_device(h->ctx, g, F, d_field, foffs, h->d_batch, offs, 4, mode, (float)feather, exposure ? (const float *)gdata : NULL, canvas, d_canvas,
+                                     d_weight);
+    else if (rc == HG_OK)
         rc = hg_mosaic_frames_gain_device(h->ctx, g, F, d_field, foffs, h->d_batch, offs, HG_ELEM_U8, 4, W, H, mode, (float)feather, canvas, d_canvas, d_weight,
                                           exposure ? (const float *)gdata : NULL);
     if (rc == HG_OK) rc = hg_copy_to_host(h->ctx, data, d_canvas, n * 4);
@@ -2030,7 +2036,7 @@ static napi_value run_mosaic(napi_env env, handle_t *h, const batch_job *job, co
     return result;
 }
 
-static napi_value mosaic_inverse_geometric(napi_env env, napi_callback_info info, int multiband)
+static napi_value mosaic_inverse_geometric(napi_env env, napi_callback_info info, int multiband, int robust)
 {
     napi_value a[13]; int have_exposure = 0;
     if (!get_args_opt(env, info, 11 + (size_t)multiband, a, &have_exposure)) return NULL;
@@ -2045,13 +2051,14 @@ static napi_value mosaic_inverse_geometric(napi_env env, napi_callback_info info
     job.per = job.kind == HG_AFFINE ? 6 : 8;
     if (F <= 0) return throw_str(env, "hgwarp: geoms must hold 4 integers per frame");
     if (nf < (size_t)F * job.per || nt < (size_t)F * job.per) return throw_str(env, "hgwarp: point sets must hold frames x points x,y pairs");
-    return run_mosaic(env, h, &job, gv, F, a + 5, have_exposure ? a[11 + multiband] : NULL, multiband ? "mosaicMultibandInverseGeometric" : "mosaicInverseGeometric",
-                      multiband ? a[11] : NULL);
+    return run_mosaic(env, h, &job, gv, F, a + 5, have_exposure ? a[11 + multiband] : NULL, multiband ? "mosaicMultibandInverseGeometric" : robust ? "mosaicRobustInverseGeometric" : "mosaicInverseGeometric",
+                      multiband ? a[11] : NULL, robust);
 }
-static napi_value fn_mosaic_inverse_geometric(napi_env env, napi_callback_info info) { return mosaic_inverse_geometric(env, info, 0); }
-static napi_value fn_mosaic_multiband_inverse_geometric(napi_env env, napi_callback_info info) { return mosaic_inverse_geometric(env, info, 1); }
+static napi_value fn_mosaic_inverse_geometric(napi_env env, napi_callback_info info) { return mosaic_inverse_geometric(env, info, 0, 0); }
+static napi_value fn_mosaic_robust_inverse_geometric(napi_env env, napi_callback_info info) { return mosaic_inverse_geometric(env, info, 0, 1); }
+static napi_value fn_mosaic_multiband_inverse_geometric(napi_env env, napi_callback_info info) { return mosaic_inverse_geometric(env, info, 1, 0); }
 
-static napi_value mosaic_inverse_piecewise(napi_env env, napi_callback_info info, int multiband)
+static napi_value mosaic_inverse_piecewise(napi_env env, napi_callback_info info, int multiband, int robust)
 {
     napi_value a[11]; int have_exposure = 0;
     if (!get_args_opt(env, info, 9 + (size_t)multiband, a, &have_exposure)) return NULL;
@@ -2062,11 +2069,12 @@ static napi_value mosaic_inverse_piecewise(napi_env env, napi_callback_info info
     const int F = (int)(ng / 4);
     if (F <= 0) return throw_str(env, "hgwarp: geoms must hold 4 integers per frame");
     if (h->n_pts == 0 || nd < (size_t)F * 2 * h->n_pts) return throw_str(env, "hgwarp: dstPoints must hold frames x mesh points x,y pairs (piecewiseSetMesh first)");
-    return run_mosaic(env, h, &job, gv, F, a + 3, have_exposure ? a[9 + multiband] : NULL, multiband ? "mosaicMultibandInversePiecewise" : "mosaicInversePiecewise",
-                      multiband ? a[9] : NULL);
+    return run_mosaic(env, h, &job, gv, F, a + 3, have_exposure ? a[9 + multiband] : NULL, multiband ? "mosaicMultibandInversePiecewise" : robust ? "mosaicRobustInversePiecewise" : "mosaicInversePiecewise",
+                      multiband ? a[9] : NULL, robust);
 }
-static napi_value fn_mosaic_inverse_piecewise(napi_env env, napi_callback_info info) { return mosaic_inverse_piecewise(env, info, 0); }
-static napi_value fn_mosaic_multiband_inverse_piecewise(napi_env env, napi_callback_info info) { return mosaic_inverse_piecewise(env, info, 1); }
+static napi_value fn_mosaic_inverse_piecewise(napi_env env, napi_callback_info info) { return mosaic_inverse_piecewise(env, info, 0, 0); }
+static napi_value fn_mosaic_robust_inverse_piecewise(napi_env env, napi_callback_info info) { return mosaic_inverse_piecewise(env, info, 0, 1); }
+static napi_value fn_mosaic_multiband_inverse_piecewise(napi_env env, napi_callback_info info) { return mosaic_inverse_piecewise(env, info, 1, 0); }
 
 /* warpForwardPiecewiseBatch(ctx, dstPoints, maxSrcX, maxSrcY, geoms [, ownFrames, images, width, height]): the frames warp() sends down the
  * FORWARD piecewise path (:421-422: output not larger than the input and at least input / 1.2) */
@@ -2334,6 +2342,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "remapBicubicInverseGeometric", fn_remap_bicubic_inverse_geometric }, { "remapBicubicInversePiecewise", fn_remap_bicubic_inverse_piecewise },
         { "mosaicInverseGeometric", fn_mosaic_inverse_geometric }, { "mosaicInversePiecewise", fn_mosaic_inverse_piecewise },
         { "mosaicMultibandInverseGeometric", fn_mosaic_multiband_inverse_geometric }, { "mosaicMultibandInversePiecewise", fn_mosaic_multiband_inverse_piecewise },
+        { "mosaicRobustInverseGeometric", fn_mosaic_robust_inverse_geometric }, { "mosaicRobustInversePiecewise", fn_mosaic_robust_inverse_piecewise },
         { "pointsInverseGeometric", fn_points_inverse_geometric }, { "pointsInversePiecewise", fn_points_inverse_piecewise },
         { "pointsForwardGeometric", fn_points_forward_geometric }, { "pointsForwardPiecewise", fn_points_forward_piecewise },
         { "fitMatches", fn_fit_matches },

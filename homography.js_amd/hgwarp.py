@@ -26,6 +26,9 @@ FIELD_INDEX, FIELD_COORDS = 0, 1
 ELEM_F32, ELEM_U8 = 0, 1
 # blend modes of the mosaic (hg_mosaic_frames_device): the last contributor's pixel, the contributors' mean, their feathered mean
 MOSAIC_LAST, MOSAIC_MEAN, MOSAIC_FEATHER = 0, 1, 2
+# order statistics of the robust mosaic (hg_mosaic_robust_device), and the frames over one 64 x 4 tile it stages in LDS (HG_ROBUST_LMAX)
+ROBUST_MEDIAN, ROBUST_TRIMMED, ROBUST_MIN, ROBUST_MAX = 0, 1, 2, 3
+ROBUST_LMAX = 64
 # (B, C) of the named cubics of the bicubic remap (hg_remap_bicubic_frames_device)
 CUBIC_CATMULL_ROM, CUBIC_MITCHELL, CUBIC_BSPLINE = (0.0, 0.5), (1 / 3, 1 / 3), (1.0, 0.0)
 # descriptor kinds of the matcher (hg_match_descriptors_frames_device): binary rows under the Hamming distance, byte vectors under squared L2
@@ -81,6 +84,7 @@ EXPORTS = [
     "hg_match_descriptors_frames_device",
     "hg_detect_layout", "hg_describe_pattern", "hg_detect_describe_frames_device",
     "hg_mosaic_multiband_layout", "hg_mosaic_multiband_device",
+    "hg_mosaic_robust_device",
 ]
 
 
@@ -191,6 +195,7 @@ def lib():
         "hg_remap_aniso_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, i, i, i, sz, i, i, vp, C.POINTER(sz), vp, sz, i, i]),
         "hg_mosaic_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, C.POINTER(sz), i, i, i, i, i, C.c_float, Geom, vp, vp]),
         "hg_mosaic_frames_gain_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, C.POINTER(sz), i, i, i, i, i, C.c_float, Geom, vp, vp, C.POINTER(C.c_float)]),
+        "hg_mosaic_robust_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, C.POINTER(sz), i, i, C.c_float, C.POINTER(C.c_float), Geom, vp, vp]),
         "hg_mosaic_overlap_stats_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, C.POINTER(sz), i, Geom, vp]),
         "hg_mosaic_solve_gains": (i, [C.POINTER(C.c_uint64), i, i, C.c_double, C.c_double, C.POINTER(C.c_float)]),
         "hg_mosaic_multiband_layout": (i, [C.POINTER(Geom), i, Geom, i, i, C.POINTER(sz)]),
@@ -987,6 +992,24 @@ class Context:
             return
         self._c(lib().hg_mosaic_frames_device(self._h, _geoms(geoms) if len(geoms) else None, len(geoms), C.c_void_p(int(d_coords) or None), fo,
                                               C.c_void_p(int(d_frames) or None), po, int(elem), int(channels), int(w), int(h), int(mode), float(feather),
+                                              Geom(*[int(v) for v in canvas]), C.c_void_p(int(d_canvas) or None), C.c_void_p(int(d_weight) or None)))
+
+    def mosaic_robust_device(self, geoms, d_coords, d_frames, channels, mode, canvas, d_canvas, d_weight=0, trim=0.0,
+                             field_offsets=None, frame_offsets=None, gains=None):
+        """The u8 frames of a set (at most 256) blended into ONE canvas by an order statistic per pixel and channel (asynchronous), so that
+        what covers a pixel in a minority of the frames drops out: mode ROBUST_MEDIAN, ROBUST_TRIMMED (the mean of what is left when the
+        share `trim`, in [0, 0.5), is cut off at both ends), ROBUST_MIN or ROBUST_MAX of the contributors' bytes.  geoms, d_coords, d_frames,
+        canvas, d_canvas, d_weight (0: none; the number of contributors), the offsets and gains are mosaic_frames_device's; a gained value is a
+        byte again before it is ranked."""
+        fo = (C.c_size_t * len(geoms))(*field_offsets) if field_offsets is not None else None
+        po = (C.c_size_t * len(geoms))(*frame_offsets) if frame_offsets is not None else None
+        gp = None
+        if gains is not None:
+            gv = np.ascontiguousarray(gains, dtype=np.float32).ravel()
+            assert gv.size == len(geoms), "one gain per frame"
+            gp = gv.ctypes.data_as(C.POINTER(C.c_float)) if gv.size else None
+        self._c(lib().hg_mosaic_robust_device(self._h, _geoms(geoms) if len(geoms) else None, len(geoms), C.c_void_p(int(d_coords) or None), fo,
+                                              C.c_void_p(int(d_frames) or None), po, int(channels), int(mode), float(trim), gp,
                                               Geom(*[int(v) for v in canvas]), C.c_void_p(int(d_canvas) or None), C.c_void_p(int(d_weight) or None)))
 
     def mosaic_multiband_device(self, geoms, d_coords, d_frames, elem, channels, w, h, feather, n_bands, canvas, d_canvas, d_work, work_bytes,

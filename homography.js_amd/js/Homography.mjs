@@ -992,6 +992,13 @@ class Homography {
      *                     owners in options.bands frequency bands -- low frequencies over a wide range, so exposure differences fade,
      *                     high frequencies over a narrow one, so detail comes from one frame and nothing is doubled
      *                     (include/hgwarp.h, hg_mosaic_multiband_device; the weight plane is then 1 where a frame owns the pixel);
+     *                     'median', 'trimmed', 'min', 'max': an order statistic of the frames that cover the pixel, channel by channel
+     *                     (include/hgwarp.h, hg_mosaic_robust_device) -- what moves through a minority of the frames of a stack drops
+     *                     out of the median and of the trimmed mean with no mask or threshold; 'min' / 'max' keep the darkest /
+     *                     brightest value.  At most 256 non-blank frames; the weight plane is then the number of frames that cover
+     *                     the pixel; options.feather and options.bands are ignored; 8-bit images only (an f32 image is a TypeError);
+     *   options.trim      'trimmed' only: the share cut off at EACH end before the rest is averaged, a number in [0, 0.5) (default 0.25;
+     *                     0: the mean);
      *   options.bands     the band count of 'multiband', an integer 1..8 (default 5; 1: a paste along the seams);
      *   options.labels    'multiband' only, true: also return labels, an Int32Array of the owning destiny point set per canvas pixel
      *                     (-1: none);
@@ -1011,20 +1018,25 @@ class Homography {
      * Every setDestinyPoints(dst[f]) runs on the host exactly as in warpBatch(dstPointSets, {inverse: true}), so the instance ends in the
      * state that call leaves.  A pixel no frame covers is 0 in every channel; where exactly one frame covers it, its bytes are that frame's.
      * Returns { data: Uint8ClampedArray, width, height, x, y [, weight: Float32Array] [, labels: Int32Array] }.  Throws a string for an
-     * unknown blend, bad `bands`, `labels` without 'multiband', a bad feather, a canvas that is not four integers, a bad `exposure`, and for `devices` and `sourcePoints` (the mosaic runs on this
+     * unknown blend, bad `bands`, `labels` without 'multiband', a bad feather, a bad `trim`, a canvas that is not four integers, a bad `exposure`, and for `devices` and `sourcePoints` (the mosaic runs on this
      * instance's own device, over one source point set).
      */
     mosaic(dstPointSets, options = {}) {
         if (options === null || options === undefined) options = {};
         const blend = options.blend === undefined ? 'feather' : options.blend;
         const multiband = blend === 'multiband';
-        const mode = ['last', 'mean', 'feather'].indexOf(blend);
-        if (mode < 0 && !multiband) throw ("mosaic: options.blend must be 'feather', 'mean', 'last' or 'multiband'");
+        const robust = ['median', 'trimmed', 'min', 'max'].indexOf(blend);      // HG_ROBUST_*
+        const mode = robust >= 0 ? robust : ['last', 'mean', 'feather'].indexOf(blend);
+        if (mode < 0 && !multiband) throw ("mosaic: options.blend must be 'feather', 'mean', 'last', 'multiband', 'median', 'trimmed', 'min' or 'max'");
+        if (robust >= 0 && typeof this._native.mosaicRobustInverseGeometric !== 'function')      // (an addon from before hg_mosaic_robust_device)
+            throw (`mosaic: options.blend '${blend}' needs an addon built with the robust mosaics; this one knows 'feather', 'mean', 'last' and 'multiband'`);
+        const trim = options.trim === undefined ? 0.25 : options.trim;
+        if (blend === 'trimmed' && !(typeof trim === 'number' && trim >= 0 && trim < 0.5)) throw ("mosaic: options.trim must be a number in [0, 0.5)");
         const bands = options.bands === undefined ? 5 : options.bands;
         if (multiband && !(Number.isInteger(bands) && bands >= 1 && bands <= 8)) throw ("mosaic: options.bands must be an integer 1..8");
         if (!multiband && options.labels === true) throw ("mosaic: options.labels needs blend 'multiband'");
         const wantLabels = multiband && options.labels === true;
-        const feather = options.feather === undefined ? Infinity : options.feather;
+        const feather = options.feather === undefined || robust >= 0 ? Infinity : options.feather;
         if (typeof feather !== 'number' || !(feather > 0)) throw ("mosaic: options.feather must be a number > 0 (Infinity: uncapped)");
         let canvas = null;
         if (options.canvas !== undefined && options.canvas !== null) {
@@ -1053,6 +1065,10 @@ class Homography {
         const geometric = this.transform === 'affine' || this.transform === 'projective';
         if (!geometric && this.transform !== 'piecewiseaffine') throw ("hgwarp: mosaic() needs a transform (set the source points first)");
         const images = options.images === undefined ? null : options.images;
+        if (robust >= 0) {                                       // the order statistics rank bytes
+            const isF32 = (im) => im instanceof Float32Array || (im !== null && typeof im === 'object' && im.data instanceof Float32Array);
+            if ((Array.isArray(images) && images.some(isF32)) || (!images && isF32(this._image))) throw new TypeError(`mosaic: blend '${blend}' takes 8-bit images only`);
+        }
         const F = dstPointSets.length, n = geometric ? (this.transform === 'affine' ? 6 : 8) : this._srcPoints.length;
         const dsts = new Float32Array(F * n), srcPts = new Float32Array(geometric ? F * n : 0), geoms = new Int32Array(F * 4), keep = [];
         for (let f = 0; f < F; f++) {                            // warpBatch(dstPointSets, {inverse: true})'s host loop, frame for frame
@@ -1093,18 +1109,18 @@ class Homography {
             return out;
         }
         const sub = (arr, w) => { if (keep.length === F) return arr; const o = new arr.constructor(keep.length * w); keep.forEach((f, k) => o.set(arr.subarray(f * w, (f + 1) * w), k * w)); return o; };
-        const tail = [multiband ? bands : mode, feather, Int32Array.from([cx, cy, cw, ch]), options.weight === true, this._width, this._height];
+        const tail = [multiband ? bands : mode, robust >= 0 ? (blend === 'trimmed' ? trim : 0) : feather, Int32Array.from([cx, cy, cw, ch]), options.weight === true, this._width, this._height];
         if (multiband) tail.push(wantLabels);
         if (exposure !== null) tail.push(exposure instanceof Float32Array ? sub(exposure, 1) : exposure);      // (absent: the call is what it was)
         const srcs = images === null ? null : keep.map((f) => images[f % images.length]);
         let res;
         if (geometric) {
             this._uploadSources(srcs);
-            res = this._native[multiband ? 'mosaicMultibandInverseGeometric' : 'mosaicInverseGeometric'](this._ctx, this.transform === 'affine' ? AFFINE : PROJECTIVE, sub(dsts, n), sub(srcPts, n), sub(geoms, 4), ...tail);
+            res = this._native[multiband ? 'mosaicMultibandInverseGeometric' : robust >= 0 ? 'mosaicRobustInverseGeometric' : 'mosaicInverseGeometric'](this._ctx, this.transform === 'affine' ? AFFINE : PROJECTIVE, sub(dsts, n), sub(srcPts, n), sub(geoms, 4), ...tail);
         } else {
             this._uploadMesh();
             this._uploadSources(srcs);
-            res = this._native[multiband ? 'mosaicMultibandInversePiecewise' : 'mosaicInversePiecewise'](this._ctx, sub(dsts, n), sub(geoms, 4), ...tail);
+            res = this._native[multiband ? 'mosaicMultibandInversePiecewise' : robust >= 0 ? 'mosaicRobustInversePiecewise' : 'mosaicInversePiecewise'](this._ctx, sub(dsts, n), sub(geoms, 4), ...tail);
         }
         out.data = res.data;
         if (options.weight === true) out.weight = res.weight;

@@ -40,7 +40,8 @@ extern "C" {
                                    the bicubic remap by that of hg_remap_bicubic_frames_device, exposure gains of a mosaic by that of
                                    hg_mosaic_overlap_stats_device, fitting transforms to matches by that of hg_fit_matches_frames_device);
                                    matching descriptors by the presence of hg_match_descriptors_frames_device, keypoints by the presence of
-                                   hg_detect_describe_frames_device, multi-band mosaics by the presence of hg_mosaic_multiband_device, thin-plate splines
+                                   hg_detect_describe_frames_device, multi-band mosaics by the presence of hg_mosaic_multiband_device, robust mosaics
+                                   by the presence of hg_mosaic_robust_device, thin-plate splines
                                    by the presence of hg_tps_solve_frames_device, dense optical flow by the presence of
                                    hg_flow_dense_frames_device, refining transforms on the pixels by the presence of
                                    hg_align_refine_frames_device */
@@ -586,6 +587,61 @@ int hg_mosaic_frames_gain_device(hg_ctx *ctx, const hg_geom *geoms, int n_frames
                                  int mode, float feather,
                                  hg_geom canvas, void *d_canvas, float *d_weight,
                                  const float *gains);
+/* ROBUST mosaic: an order statistic per canvas pixel in the place of a weighted mean, for a stack of aligned exposures (a tripod burst, a
+ * stabilised clip, the overlaps of a panorama).  A walking person, a car or a waving flag covers a pixel in a minority of the frames, so it
+ * is not in the median or the trimmed mean of the contributors: no mask, threshold or tuning.  HG_ROBUST_MIN and HG_ROBUST_MAX are the
+ * dark-frame and star-trail variants.
+ *
+ * hg_mosaic_robust_device: geoms, d_coords, field_offsets, d_frames, frame_offsets, channels, canvas, d_canvas and d_weight mean exactly what
+ * they mean in hg_mosaic_frames_device (packing defaults, alignment rules, hg_geom limits, EVERY canvas pixel is written, the empty canvas);
+ * gains is n_frames floats on the HOST, or NULL, and means what it means in hg_mosaic_frames_gain_device.  There is no W, H: nothing here
+ * feathers.  Elements are HG_ELEM_U8 only, as for hg_mosaic_overlap_stats_device and for the same reason: every rule below is integer
+ * arithmetic, so the result is exact and identical from run to run.  f32 planes are out of scope.  n_frames is 0..256.  Canvas pixel (i, j):
+ *   1. Candidates and contributors are steps 1-3 of hg_mosaic_frames_device.  n is the number of contributors.
+ *   2. The value of contributor f on channel c is x = p_c without gains; with gains the byte min(255, floor(g_f * (float)p_c + 0.5f)) on the
+ *      STAT CHANNELS (one f32 multiply, rounded as hg_mosaic_frames_gain_device rounds what it stores), channel 3 of a 4-channel frame
+ *      unscaled.  A gained value is a byte again BEFORE it is ranked.
+ *   3. Every channel is ranked on its own: its n values in ascending order are s_0 <= ... <= s_{n-1}.  Alpha is a channel like any other.
+ *      The result may therefore be a colour that no single frame held.
+ *   4. n == 0: every channel 0, weight 0.  HG_ROBUST_MIN: s_0.  HG_ROBUST_MAX: s_{n-1}.  HG_ROBUST_MEDIAN: s_{(n-1)/2} for odd n,
+ *      (s_{n/2-1} + s_{n/2} + 1) >> 1 for even n.  HG_ROBUST_TRIMMED: t = min((int)(trim * (float)n), (n - 1) / 2) with the product as one
+ *      f32 multiply, truncated; m = n - 2 t; S = s_t + ... + s_{n-1-t} as an integer; the result is (2 S + m) / (2 m) in integer division
+ *      (S / m rounded to nearest, halves up).  Weight = (float)n in every mode.
+ *   5. Hence: ONE contributor gives that contributor's (gained) bytes in every mode, so frames that do not overlap give a paste, equal to
+ *      HG_MOSAIC_LAST.  HG_ROBUST_TRIMMED with trim == 0 and no gains equals HG_MOSAIC_MEAN on u8 byte for byte, weight plane included:
+ *      there t = 0, m = n, and the mean's accumulator holds S exactly (integers below 2^24).  The exact quotient S / n is a multiple of 1 / n,
+ *      a rounding boundary k + 1/2 a multiple of 1/2, so unless they coincide they lie at least 1 / (2 n) >= 1/512 apart, far beyond the errors
+ *      of the f32 division of values below 65536 and of the addition of 0.5f (at most 2^-17 each); where they coincide both are exact.  The mean's
+ *      floor(acc / wsum + 0.5f) is therefore this entry's (2 S + n) / (2 n).
+ * n_frames == 0 zeroes the canvas (geoms / d_coords / d_frames / gains may be NULL).  An empty canvas: HG_OK, nothing is written.
+ * HG_ERR_INVALID, in this order: the mosaic's own list in its order -- n_frames negative (or above 65535); d_canvas NULL; channels outside
+ * 1..4; geoms / d_coords / d_frames NULL with n_frames > 0; a misaligned d_coords (8) or d_weight (4); a canvas or a frame beyond the hg_geom
+ * limits; field offsets that are no multiples of 8 --; n_frames > 256; an unknown mode; in HG_ROBUST_TRIMMED mode a trim that is NaN or
+ * outside [0, 0.5) (ignored otherwise); a gain that is not finite and > 0.
+ * Asynchronous on the ctx stream; the frame table goes up through the page-locked staging ring as the frames remaps' does, the gains behind
+ * it in the same upload; queued runs whose deferred redo could land on d_canvas or d_weight are settled first; frames or fields that are
+ * outputs of queued warps are the caller's to settle (hg_sync), as for every remap.  No effect on hg_last_*, the sampling mode, the plan,
+ * what the policy learned or staged frame sets.
+ * How (hg_k_robust.hip): a selection, not a sort.  A tile of 64 x 4 canvas pixels lists the frames whose window meets it; up to
+ * HG_ROBUST_LMAX listed frames have their contributors staged in LDS from ONE walk of global memory (a launch allocates 16, 32 or 64 slots
+ * by n_frames: LDS bounds the waves a CU holds), more are walked again per round; the
+ * ranks are resolved bit by bit from bit 7 down, 8 rounds of counting for all channels at once; pixels with one or two contributors need none.
+ * Cost (MI355X; EXPERIMENTS.md "Robust mosaic"; tools/bench_robust.py): u8 x 4 frames with the weight plane, medians of 25 regions, as ratios to
+ * HG_MOSAIC_MEAN on the same frames in the same process and to the byte floor (coordinates and pixels of every candidate once, canvas and weights,
+ * at 8 TB/s).  64 frames with identical 3840 x 2160 windows (64 contributors per pixel, staged; mean 1.57 ms): MEDIAN 8.38 ms, 5.3 x the mean, 10.4 x
+ * the floor; TRIMMED 8.83 ms, 5.6 x; MIN / MAX 8.34 ms, 5.3 x.  Built with a cap of 32 the same frames are walked in global memory per round and
+ * MEDIAN takes 21.8 ms, 13.8 x.  A strip of 16 frames of 1920 x 1080 shifted by 60 % of their width (1-2 contributors, no rounds): every mode 0.28 ms,
+ * 1.17 x the mean (0.24 ms), 4.0 x the floor.  256 frames of 128 x 128 over a 4K canvas (at most 3 contributors): 0.36 ms, 0.35 x the mean (1.02 ms),
+ * which walks all 256 records in every tile where this kernel walks its list. */
+#ifndef HG_ROBUST_LMAX
+#define HG_ROBUST_LMAX 64       /* frames hitting one 64 x 4 tile that are staged in LDS; beyond it the tile re-walks them (slower, as correct) */
+#endif
+enum { HG_ROBUST_MEDIAN = 0, HG_ROBUST_TRIMMED = 1, HG_ROBUST_MIN = 2, HG_ROBUST_MAX = 3 };
+int hg_mosaic_robust_device(hg_ctx *ctx, const hg_geom *geoms, int n_frames,
+                            const void *d_coords, const size_t *field_offsets,
+                            const void *d_frames, const size_t *frame_offsets,
+                            int channels, int mode, float trim, const float *gains,
+                            hg_geom canvas, void *d_canvas, float *d_weight);
 /* MULTI-BAND blending of a mosaic (Brown & Lowe, section 7, after Burt & Adelson): low frequencies are blended over a wide range and high
  * frequencies over a narrow one, so exposure differences fade across a seam while detail comes from one frame only -- no step as with
  * HG_MOSAIC_LAST / HG_MOSAIC_MEAN, no ghosting as with HG_MOSAIC_FEATHER.  As a by-product it yields the SEAM LABEL MAP: which frame owns
