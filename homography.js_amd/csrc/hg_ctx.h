@@ -216,6 +216,7 @@ struct hg_ctx {
     DevBuf<int32_t> d_fit_valid;
     DevBuf<uint64_t> d_fit_frames;                             // F best words, then the F counts (int32, padded to 8 bytes)
     StageRing<4> fit_stage;                                    // the counts go up through page-locked staging, stream-ordered
+    StageRing<4> bundle_stage;                                 // the bundle adjustment's host-built lists (hg_api_bundle.hip), likewise
 
     // refining transforms on the pixels (hg_api_align.hip): the per-frame iterate and flags, the chunks' partial records and the luma copies of
     // 4-channel planes; grown on demand

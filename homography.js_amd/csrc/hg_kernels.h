@@ -10,6 +10,7 @@
 #include "hg_align_dev.h"
 #include "hg_tps_dev.h"
 #include "hg_flow_dev.h"
+#include "hg_bundle_dev.h"
 
 namespace hg {
 
@@ -307,6 +308,11 @@ void launch_align(const AlignArgs &a, hipStream_t stream);
 
 // Thin-plate splines (hg_k_tps.hip; the rules and the argument blocks: hg_tps_dev.h): k_tps_solve, one workgroup per frame; k_tps_field over the
 // windows (step 1) or over the lattice and then k_tps_blend (step > 1; fmt = HG_FIELD_*); k_tps_points, frame f reading list f % n_sets.
+// Adjusting a frame set over all pairs (hg_k_bundle.hip; the rules and the argument block: hg_bundle_dev.h): pass 0, then per round assembly,
+// solve, pass, reduction and decision (up to kBundleLdsCap unknowns all but the pass in ONE workgroup per round, H in LDS; above, the blocked
+// factorisation in scratch), none of them waited for.
+hipError_t launch_bundle(const BundleArgs &a, hipStream_t stream);   // (the first error of the attribute call or of a launch)
+
 void launch_tps_solve(const TpsSolveArgs &a, hipStream_t stream);
 void launch_tps_field(const TpsFieldArgs &a, int fmt, hipStream_t stream);
 void launch_tps_points(const double *records, int n_points, int n_frames, const float *points, int n_pts, int n_sets, float *out, hipStream_t stream);

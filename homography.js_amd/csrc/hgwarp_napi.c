@@ -1164,6 +1164,108 @@ static napi_value fn_fit_matches(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* bundleAdjust(handle, kind, W, H, fixed, pairs, matches, nPoints, counts, mask | null, nIter, eps, lambda0, huber, matrices): the frame -> canvas
+ * matrices of a frame set adjusted over all pairs (hg_bundle_adjust_frames_device).  fixed: Uint8Array(F); pairs: Int32Array(2 P); matches:
+ * Float32Array of P x nPoints x 4 (x, y, u, v); counts: Int32Array(P); mask: Uint8Array(P x nPoints) or null; matrices: Float64Array(8 F).
+ * Everything goes up into device memory of the call's own, beside the scratch of hg_bundle_layout, the entry runs, and { matrices:
+ * Float64Array(8 F), info: Uint8Array (the bytes of d_info: the call's record, one int32 per frame padded to 8 bytes, 24 bytes per pair) }
+ * come down.  Needs no image. */
+static napi_value fn_bundle_adjust(napi_env env, napi_callback_info info)
+{
+    napi_value a[15];
+    if (!get_args(env, info, 15, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    int kind, W, H, n_points, n_iter; size_t n_fx = 0, n_pr = 0, n_m = 0, n_c = 0, n_k = 0, n_mat = 0; double eps, lambda0, huber;
+    if (!get_i32(env, a[1], &kind) || !get_i32(env, a[2], &W) || !get_i32(env, a[3], &H)) return NULL;
+    uint8_t *fixed = (uint8_t *)get_typed(env, a[4], napi_uint8_array, &n_fx, "fixed"); if (!fixed) return NULL;
+    int32_t *pairs = (int32_t *)get_typed(env, a[5], napi_int32_array, &n_pr, "pairs"); if (!pairs) return NULL;
+    float *m = (float *)get_typed(env, a[6], napi_float32_array, &n_m, "matches"); if (!m) return NULL;
+    if (!get_i32(env, a[7], &n_points)) return NULL;
+    int32_t *counts = (int32_t *)get_typed(env, a[8], napi_int32_array, &n_c, "counts"); if (!counts) return NULL;
+    napi_valuetype vt;
+    NAPI_OK(napi_typeof(env, a[9], &vt));
+    uint8_t *mask = NULL;
+    if (vt != napi_null && vt != napi_undefined) { mask = (uint8_t *)get_typed(env, a[9], napi_uint8_array, &n_k, "mask"); if (!mask) return NULL; }
+    if (!get_i32(env, a[10], &n_iter)) return NULL;
+    if (napi_get_value_double(env, a[11], &eps) != napi_ok || napi_get_value_double(env, a[12], &lambda0) != napi_ok || napi_get_value_double(env, a[13], &huber) != napi_ok)
+        return throw_str(env, "hgwarp: eps, lambda and huber must be numbers");
+    double *mats = (double *)get_typed(env, a[14], napi_float64_array, &n_mat, "matrices"); if (!mats) return NULL;
+    const size_t F = n_fx, P = n_c, N = (size_t)(n_points > 0 ? n_points : 0);
+    if (n_points < 0 || n_points > 65536 || F > HG_BUNDLE_MAX_FRAMES || P > HG_BUNDLE_MAX_PAIRS) return throw_str(env, "hgwarp: bundleAdjust: nPoints, the number of frames or the number of pairs is out of range");
+    if (n_mat != F * 8) return throw_str(env, "hgwarp: matrices must hold fixed.length x 8 numbers");
+    if (n_pr != P * 2) return throw_str(env, "hgwarp: pairs must hold counts.length x 2 indices");
+    if (n_m != P * N * 4) return throw_str(env, "hgwarp: matches must hold counts.length x nPoints x 4 floats");
+    if (mask && n_k != P * N) return throw_str(env, "hgwarp: mask must hold counts.length x nPoints bytes");
+    const size_t info_bytes = 48 + ((4 * F + 7) & ~(size_t)7) + 24 * P;
+    void *p_mats, *p_info;
+    napi_value out, v_mats, v_info;
+    if (!(v_mats = make_typed(env, napi_float64_array, F * 8, 8, &p_mats)) || !(v_info = make_typed(env, napi_uint8_array, F ? info_bytes : 0, 1, &p_info))) return NULL;
+    NAPI_OK(napi_create_object(env, &out));
+    NAPI_OK(napi_set_named_property(env, out, "matrices", v_mats)); NAPI_OK(napi_set_named_property(env, out, "info", v_info));
+    size_t scratch = 0;
+    HG_CALL(h->ctx, "hg_bundle_layout", hg_bundle_layout(kind, (int)F, (int)P, n_points, &scratch));
+    if (!F) {
+        HG_CALL(h->ctx, "hg_bundle_adjust_frames_device", hg_bundle_adjust_frames_device(h->ctx, kind, W, H, 0, fixed, pairs, (int)P, NULL, n_points, counts, NULL, n_iter, eps, lambda0,
+                                                                                         huber, NULL, NULL, NULL, NULL, NULL, 0));
+        return out;
+    }
+#define BUNDLE_PAD(b) (((size_t)(b) + 255) & ~(size_t)255)
+    const size_t o_m = 0, o_k = o_m + BUNDLE_PAD(P * N * 16), o_in = o_k + BUNDLE_PAD(mask ? P * N : 0), o_out = o_in + BUNDLE_PAD(F * 64), o_info = o_out + BUNDLE_PAD(F * 64),
+                 o_s = o_info + BUNDLE_PAD(info_bytes), total = o_s + BUNDLE_PAD(scratch);
+#undef BUNDLE_PAD
+    void *d = NULL;
+    HG_CALL(h->ctx, "hg_device_alloc", hg_device_alloc(h->ctx, total, &d));
+    uint8_t *b = (uint8_t *)d;
+    int rc = HG_OK;
+    const char *what = "hg_copy_to_device";
+    if (P * N) rc = hg_copy_to_device(h->ctx, b + o_m, m, P * N * 16);
+    if (rc == HG_OK && mask && P * N) rc = hg_copy_to_device(h->ctx, b + o_k, mask, P * N);
+    if (rc == HG_OK) rc = hg_copy_to_device(h->ctx, b + o_in, mats, F * 64);
+    if (rc == HG_OK) {
+        what = "hg_bundle_adjust_frames_device";
+        rc = hg_bundle_adjust_frames_device(h->ctx, kind, W, H, (int)F, fixed, pairs, (int)P, P * N ? b + o_m : NULL, n_points, counts, mask && P * N ? b + o_k : NULL, n_iter, eps,
+                                            lambda0, huber, (const double *)(b + o_in), (double *)(b + o_out), b + o_info, NULL, b + o_s, scratch);
+    }
+    if (rc == HG_OK) { what = "hg_copy_to_host"; rc = hg_copy_to_host(h->ctx, p_mats, b + o_out, F * 64); }
+    if (rc == HG_OK) rc = hg_copy_to_host(h->ctx, p_info, b + o_info, info_bytes);
+    if (rc != HG_OK) { napi_value e = throw_hg(env, h->ctx, what, rc); hg_device_free(h->ctx, d); return e; }
+    HG_CALL(h->ctx, "hg_device_free", hg_device_free(h->ctx, d));
+    return out;
+}
+
+/* bundleChain(kind, nFrames, pairs: Int32Array(2 P), pairMatrices: Float64Array(8 P), anchor) -> Float64Array(8 nFrames): hg_bundle_chain_from_pairs.
+ * bundleInvert(kind, matrix: Float64Array(8)) -> Float64Array(8): hg_bundle_invert_matrix.  Host only: no handle. */
+static napi_value fn_bundle_chain(napi_env env, napi_callback_info info)
+{
+    napi_value a[5];
+    if (!get_args(env, info, 5, a)) return NULL;
+    int kind, n_frames, anchor; size_t n_pr = 0, n_pm = 0;
+    if (!get_i32(env, a[0], &kind) || !get_i32(env, a[1], &n_frames)) return NULL;
+    int32_t *pairs = (int32_t *)get_typed(env, a[2], napi_int32_array, &n_pr, "pairs"); if (!pairs) return NULL;
+    double *pm = (double *)get_typed(env, a[3], napi_float64_array, &n_pm, "pairMatrices"); if (!pm) return NULL;
+    if (!get_i32(env, a[4], &anchor)) return NULL;
+    if (n_frames < 0 || n_frames > HG_BUNDLE_MAX_FRAMES || n_pr % 2 != 0 || n_pr / 2 > HG_BUNDLE_MAX_PAIRS) return throw_str(env, "hgwarp: bundleChain: the number of frames or of pairs is out of range");
+    if (n_pm != (n_pr / 2) * 8) return throw_str(env, "hgwarp: pairMatrices must hold 8 numbers per pair");
+    void *p; napi_value out;
+    if (!(out = make_typed(env, napi_float64_array, (size_t)n_frames * 8, 8, &p))) return NULL;
+    HG_CALL(NULL, "hg_bundle_chain_from_pairs", hg_bundle_chain_from_pairs(kind, n_frames, pairs, (int)(n_pr / 2), pm, anchor, (double *)p));
+    return out;
+}
+
+static napi_value fn_bundle_invert(napi_env env, napi_callback_info info)
+{
+    napi_value a[2];
+    if (!get_args(env, info, 2, a)) return NULL;
+    int kind; size_t n = 0;
+    if (!get_i32(env, a[0], &kind)) return NULL;
+    double *m = (double *)get_typed(env, a[1], napi_float64_array, &n, "matrix"); if (!m) return NULL;
+    if (n != 8) return throw_str(env, "hgwarp: bundleInvert: a matrix is 8 numbers");
+    void *p; napi_value out;
+    if (!(out = make_typed(env, napi_float64_array, 8, 8, &p))) return NULL;
+    HG_CALL(NULL, "hg_bundle_invert_matrix", hg_bundle_invert_matrix(kind, m, (double *)p));
+    return out;
+}
+
 /* The alignment of the drop-in class (refineAlignment): the planes and their pyramids stay in device memory of a JOB between the calls of
  * a coarse-to-fine walk; only the matrices travel.
  *   alignBegin(handle, from, Wf, Hf, nFrames, to, Wt, Ht, nToSets, channels, levels) -> job: from / to are Uint8Arrays of nFrames resp.
@@ -2347,6 +2449,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "pointsForwardGeometric", fn_points_forward_geometric }, { "pointsForwardPiecewise", fn_points_forward_piecewise },
         { "fitMatches", fn_fit_matches },
         { "alignBegin", fn_align_begin }, { "alignLevel", fn_align_level }, { "alignScaleMatrix", fn_align_scale_matrix }, { "alignEnd", fn_align_end },
+        { "bundleAdjust", fn_bundle_adjust }, { "bundleChain", fn_bundle_chain }, { "bundleInvert", fn_bundle_invert },
         { "warpThinPlate", fn_warp_thin_plate },
         { "denseFlow", fn_dense_flow },
         { "matchDescriptors", fn_match_descriptors },

@@ -40,6 +40,15 @@ ALIGN_CONVERGED, ALIGN_MAX_ITER, ALIGN_TOO_FEW, ALIGN_SINGULAR, ALIGN_WORSE, ALI
 ALIGN_SUMS = 66
 ALIGN_INFO = np.dtype([("status", np.int32), ("updates", np.int32), ("n_valid_first", np.int32), ("n_valid_last", np.int32),
                        ("rms_first", np.float64), ("rms_last", np.float64), ("gain", np.float64), ("bias", np.float64)])
+# adjusting a frame set over all pairs (hg_bundle_adjust_frames_device): the limits, the status of a call and of a frame, the doubles of a
+# pair's record of sums, the records of d_info
+BUNDLE_MAX_FRAMES, BUNDLE_MAX_PAIRS = 256, 8192
+BUNDLE_CONVERGED, BUNDLE_MAX_ITER, BUNDLE_STALLED, BUNDLE_SINGULAR = 0, 1, 2, 3
+BUNDLE_FRAME_ADJUSTED, BUNDLE_FRAME_FIXED, BUNDLE_FRAME_UNANCHORED, BUNDLE_FRAME_BAD_INPUT = 0, 1, 2, 3
+BUNDLE_SUMS = 154
+BUNDLE_INFO = np.dtype([("status", np.int32), ("rounds", np.int32), ("accepted", np.int32), ("n_valid_first", np.int32), ("n_valid_last", np.int32),
+                        ("pad", np.int32), ("rms_first", np.float64), ("rms_last", np.float64), ("lambda_last", np.float64)])
+BUNDLE_PAIR_INFO = np.dtype([("n_valid_first", np.int32), ("n_valid_last", np.int32), ("rms_first", np.float64), ("rms_last", np.float64)])
 # thin-plate splines (hg_tps_solve_frames_device): the most control points of a frame, the status of a frame, the doubles in front of a record's points
 TPS_MAX_POINTS = 1024
 TPS_OK, TPS_SINGULAR, TPS_BAD_INPUT = 0, 1, 2
@@ -79,6 +88,7 @@ EXPORTS = [
     "hg_remap_bicubic_frames_device",
     "hg_fit_sample_indices", "hg_fit_matches_frames_device",
     "hg_align_scale_matrix", "hg_align_refine_frames_device",
+    "hg_bundle_layout", "hg_bundle_adjust_frames_device", "hg_bundle_chain_from_pairs", "hg_bundle_invert_matrix",
     "hg_tps_layout", "hg_tps_solve_frames_device", "hg_tps_field_layout", "hg_field_tps_frames_device", "hg_points_tps_frames_device",
     "hg_flow_layout", "hg_flow_dense_frames_device", "hg_field_compose_frames_device",
     "hg_match_descriptors_frames_device",
@@ -205,6 +215,11 @@ def lib():
         "hg_fit_matches_frames_device": (i, [vp, i, vp, i, C.POINTER(C.c_int32), i, d, i, C.c_uint32, vp, i, vp, vp, vp, vp, vp]),
         "hg_align_scale_matrix": (i, [i, f64p, i, i, f64p]),
         "hg_align_refine_frames_device": (i, [vp, i, vp, i, i, i, sz, vp, i, i, i, sz, i, i, i, i, i, i, i, i, d, i, vp, vp, vp, vp]),
+        "hg_bundle_layout": (i, [i, i, i, i, C.POINTER(sz)]),
+        "hg_bundle_adjust_frames_device": (i, [vp, i, i, i, i, u8p, C.POINTER(C.c_int32), i, vp, i, C.POINTER(C.c_int32), vp, i, d, d, d, vp, vp, vp,
+                                               vp, vp, sz]),
+        "hg_bundle_chain_from_pairs": (i, [i, i, C.POINTER(C.c_int32), i, f64p, i, f64p]),
+        "hg_bundle_invert_matrix": (i, [i, f64p, f64p]),
         "hg_tps_layout": (i, [i, i, C.POINTER(sz), C.POINTER(sz)]),
         "hg_tps_solve_frames_device": (i, [vp, vp, i, vp, i, i, i, d, vp, vp, vp]),
         "hg_tps_field_layout": (i, [C.POINTER(Geom), i, i, C.POINTER(sz)]),
@@ -472,6 +487,48 @@ def align_scale_matrix(kind, m, level_in, level_out):
     out = np.empty(8, np.float64)
     _check(lib().hg_align_scale_matrix(int(kind), a.ctypes.data_as(C.POINTER(C.c_double)), int(level_in), int(level_out),
                                        out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def bundle_layout(kind, n_frames, n_pairs, n_points):
+    """Scratch bytes of hg_bundle_adjust_frames_device for a shape (0 for no frames)."""
+    total = C.c_size_t(0)
+    _check(lib().hg_bundle_layout(int(kind), int(n_frames), int(n_pairs), int(n_points), C.byref(total)))
+    return total.value
+
+
+def bundle_info_bytes(n_frames, n_pairs):
+    """Bytes of d_info of hg_bundle_adjust_frames_device: the call's record, one int32 per frame padded to 8 bytes, one record per pair."""
+    return 48 + ((4 * int(n_frames) + 7) & ~7) + 24 * int(n_pairs)
+
+
+def bundle_split_info(raw, n_frames, n_pairs):
+    """(call record as BUNDLE_INFO, frame status int32 array, pair records as BUNDLE_PAIR_INFO) from the bytes of d_info."""
+    raw = np.ascontiguousarray(raw, np.uint8)
+    o = 48 + ((4 * int(n_frames) + 7) & ~7)
+    return (raw[:48].view(BUNDLE_INFO)[0].copy(), raw[48:48 + 4 * int(n_frames)].view(np.int32).copy(),
+            raw[o:o + 24 * int(n_pairs)].view(BUNDLE_PAIR_INFO).copy())
+
+
+def bundle_chain_from_pairs(kind, n_frames, pairs, pair_mats, anchor=0):
+    """Frame -> canvas matrices chained from pairwise ones (hg_bundle_chain_from_pairs; host only): pair_mats[p] maps frame pairs[p][0] to
+    frame pairs[p][1]; the anchor is the identity, frames are reached breadth-first, unreached frames come back as NaNs.  (n_frames, 8)."""
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    pm = np.ascontiguousarray(pair_mats, dtype=np.float64).reshape(-1, 8)
+    assert pm.shape[0] == pr.shape[0], "one matrix per pair"
+    out = np.empty((int(n_frames), 8), np.float64)
+    _check(lib().hg_bundle_chain_from_pairs(int(kind), int(n_frames), pr.ctypes.data_as(C.POINTER(C.c_int32)) if pr.size else None, pr.shape[0],
+                                            pm.ctypes.data_as(C.POINTER(C.c_double)) if pm.size else None, int(anchor),
+                                            out.ctypes.data_as(C.POINTER(C.c_double)) if out.size else None))
+    return out
+
+
+def bundle_invert_matrix(kind, m):
+    """The inverse of a matrix in the fit's layouts (hg_bundle_invert_matrix; host only): the adjugate divided through by its last entry."""
+    a = np.ascontiguousarray(m, dtype=np.float64).ravel()
+    assert a.size == 8, "a matrix is 8 doubles"
+    out = np.empty(8, np.float64)
+    _check(lib().hg_bundle_invert_matrix(int(kind), a.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(C.c_double))))
     return out
 
 
@@ -1058,6 +1115,30 @@ class Context:
         self._c(lib().hg_align_refine_frames_device(self._h, int(kind), vp(d_from), int(wf), int(hf), int(n_frames), fs, vp(d_to), int(wt), int(ht),
                                                     int(n_to_sets), ts, int(channels), rx, ry, rw, rh, int(step), int(photometric), int(n_iter), float(eps),
                                                     P if min_valid is None else int(min_valid), vp(d_mats_in), vp(d_mats_out), vp(d_info), vp(d_sums)))
+
+    def bundle_adjust_frames_device(self, kind, w, h, n_frames, fixed, pairs, d_matches, n_points, counts, d_mats_in, d_mats_out, d_info, d_scratch,
+                                    scratch_bytes, d_mask=0, n_iter=10, eps=0.01, lambda0=1e-3, huber=0.0, d_pair_sums=0):
+        """hg_bundle_adjust_frames_device: the frame -> canvas matrices of n_frames frames of w x h (8 doubles each at d_mats_in, the fit's
+        layouts) adjusted over all pairs at once by Levenberg-Marquardt.  fixed: one flag per frame (host; at least one set); pairs: (n_pairs,
+        2) frame indices (host); d_matches: n_pairs lists of n_points (x, y, u, v) float32, (x, y) in the pair's first frame; counts: slots
+        used per pair (host; None: all); d_mask (0: none): the fit's inlier mask.  At most n_iter rounds, stopping when no frame corner moves
+        eps canvas pixels; lambda0: the first damping; huber (pixels, 0: off).  d_mats_out may be d_mats_in; d_info gets
+        bundle_info_bytes(n_frames, n_pairs) bytes (bundle_split_info), d_pair_sums (0: not wanted) BUNDLE_SUMS doubles per pair, the records
+        of the first pass; d_scratch: bundle_layout's bytes.  Asynchronous."""
+        vp = lambda v: C.c_void_p(int(v) or None)
+        fx = np.ascontiguousarray(fixed, dtype=np.uint8).ravel()
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        assert fx.size == int(n_frames), "one fixed flag per frame"
+        cn = None
+        if counts is not None:
+            cn = np.ascontiguousarray(counts, dtype=np.int32).ravel()
+            assert cn.size == pr.shape[0], "one count per pair"
+        self._c(lib().hg_bundle_adjust_frames_device(self._h, int(kind), int(w), int(h), int(n_frames),
+                                                     fx.ctypes.data_as(C.POINTER(C.c_uint8)) if fx.size else None,
+                                                     pr.ctypes.data_as(C.POINTER(C.c_int32)) if pr.size else None, pr.shape[0], vp(d_matches),
+                                                     int(n_points), cn.ctypes.data_as(C.POINTER(C.c_int32)) if cn is not None and cn.size else None,
+                                                     vp(d_mask), int(n_iter), float(eps), float(lambda0), float(huber), vp(d_mats_in), vp(d_mats_out),
+                                                     vp(d_info), vp(d_pair_sums), vp(d_scratch), int(scratch_bytes)))
 
     def tps_solve_frames_device(self, d_from, n_from_sets, d_to, n_to_sets, n_points, n_frames, d_records, d_status, smoothing=0.0, d_scratch=0):
         """hg_tps_solve_frames_device: one thin-plate spline per frame through n_points pairs (from -> to, (x, y) float32 lists on the device;

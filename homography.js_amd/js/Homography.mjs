@@ -462,6 +462,129 @@ class Homography {
     }
 
     /**
+     * The frame -> canvas matrices of a frame set adjusted over ALL pairs at once (not part of the reference; hg_bundle_adjust_frames_device
+     * in include/hgwarp.h has the rules): Levenberg-Marquardt on the disagreement, in the canvas, of the matches of every pair.  The
+     * planar-mosaic formulation: at least one frame is held fixed, the unknowns are the entries of the matrices; no camera model, no lens
+     * terms.  A local refinement: start from chainMatrices().
+     * matrices: Float64Array(8 F) or an array of 8 F numbers, frame -> canvas; pairs: an array of [a, b] (or an Int32Array of 2 P indices);
+     * matchSets: one list per pair, a Float32Array of x, y, u, v quadruples or an array of [x, y, u, v] -- (x, y) in frame a, (u, v) in frame
+     * b; the lists are padded to the longest and the device is told each pair's count.
+     * options: { transform: 'projective' (default) | 'affine', width, height (of every frame), fixed = [0] (frame indices), iterations = 10,
+     *            eps = 0.01 (canvas pixels), lambda = 1e-3 (the first damping), huber = 0 (pixels; 0: off), masks: one Uint8Array per pair
+     *            (0 = leave the match out; what fitMatches() returns as `inliers`) }.
+     * Returns { matrices: Float64Array(8 F), status (0 converged, 1 ran all iterations, 2 stalled, 3 singular), rounds, accepted, rmsFirst,
+     *           rmsLast (canvas pixels), frames: Int32Array(F) (0 adjusted, 1 fixed, 2 unanchored, 3 bad input), pairs: [{ nValidFirst,
+     *           nValidLast, rmsFirst, rmsLast }, ...] -- which names the pair that does not fit }.
+     * Needs no image and changes no state of the instance.  Throws a bare string for a bad option, pair or list.
+     */
+    bundleAdjust(matrices, pairs, matchSets, options = {}) {
+        if (options === null || options === undefined) options = {};
+        const transform = options.transform === undefined ? 'projective' : options.transform;
+        if (transform !== 'projective' && transform !== 'affine') throw ("bundleAdjust: options.transform must be 'projective' or 'affine'");
+        const isInt = (v, lo, hi) => Number.isInteger(v) && v >= lo && v <= hi;
+        const { width, height } = options;
+        if (!isInt(width, 1, 32768) || !isInt(height, 1, 32768)) throw ("bundleAdjust: options.width and options.height must be integers in 1..32768");
+        const iterations = options.iterations === undefined ? 10 : options.iterations;
+        if (!isInt(iterations, 0, 64)) throw ("bundleAdjust: options.iterations must be an integer in 0..64");
+        const num = (v, d) => (v === undefined ? d : v);
+        const eps = num(options.eps, 0.01), lambda = num(options.lambda, 1e-3), huber = num(options.huber, 0);
+        if (typeof eps !== 'number' || !Number.isFinite(eps) || eps < 0) throw ("bundleAdjust: options.eps must be a finite number >= 0");
+        if (typeof lambda !== 'number' || !Number.isFinite(lambda) || lambda <= 0) throw ("bundleAdjust: options.lambda must be a finite number > 0");
+        if (typeof huber !== 'number' || !Number.isFinite(huber) || huber < 0) throw ("bundleAdjust: options.huber must be a finite number >= 0");
+        if (!(matrices instanceof Float64Array) && !Array.isArray(matrices)) throw ("bundleAdjust: matrices must be a Float64Array or an array of numbers");
+        const mats = matrices instanceof Float64Array ? matrices : Float64Array.from(matrices.flat());
+        if (mats.length % 8 !== 0) throw ("bundleAdjust: matrices must hold 8 numbers per frame");
+        const F = mats.length / 8;
+        if (F > 256) throw ("bundleAdjust: at most 256 frames");
+        const P2 = this._bundlePairs('bundleAdjust', pairs, F);
+        const P = P2.length / 2;
+        if (!Array.isArray(matchSets) || matchSets.length !== P) throw ("bundleAdjust: matchSets must be an array of one match list per pair");
+        const fixedList = options.fixed === undefined ? (F > 0 ? [0] : []) : options.fixed;
+        if (!Array.isArray(fixedList) || !fixedList.every((f) => isInt(f, 0, F - 1))) throw ("bundleAdjust: options.fixed must be an array of frame indices");
+        if (F > 0 && fixedList.length === 0) throw ("bundleAdjust: options.fixed must name at least one frame");
+        const fixed = new Uint8Array(F);
+        fixedList.forEach((f) => { fixed[f] = 1; });
+        const lists = matchSets.map((s, p) => {
+            if (!(s instanceof Float32Array) && !Array.isArray(s)) throw ("bundleAdjust: match list " + p + " must be a Float32Array or an array of [x, y, u, v]");
+            const l = s instanceof Float32Array ? s : Float32Array.from(s.flat());
+            if (l.length % 4 !== 0) throw ("bundleAdjust: match list " + p + " must hold x, y, u, v quadruples");
+            return l;
+        });
+        const nPoints = lists.reduce((m, l) => Math.max(m, l.length / 4), 0);
+        if (nPoints > 65536) throw ("bundleAdjust: at most 65536 matches per pair");
+        const counts = Int32Array.from(lists, (l) => l.length / 4);
+        const packed = new Float32Array(P * nPoints * 4);
+        lists.forEach((l, p) => packed.set(l, p * nPoints * 4));
+        let mask = null;
+        if (options.masks !== undefined && options.masks !== null) {
+            if (!Array.isArray(options.masks) || options.masks.length !== P) throw ("bundleAdjust: options.masks must be an array of one mask per pair");
+            mask = new Uint8Array(P * nPoints);
+            options.masks.forEach((k, p) => {
+                if ((!(k instanceof Uint8Array) && !Array.isArray(k)) || k.length !== counts[p]) throw ("bundleAdjust: mask " + p + " must hold one flag per match of its pair");
+                mask.set(k, p * nPoints);
+            });
+        }
+        const r = this._native.bundleAdjust(this._ctx, transform === 'projective' ? 1 : 0, width, height, fixed, P2, packed, nPoints, counts, mask, iterations, eps, lambda,
+                                            huber, mats);
+        if (F === 0) return { matrices: r.matrices, status: 1, rounds: 0, accepted: 0, rmsFirst: NaN, rmsLast: NaN, frames: new Int32Array(0), pairs: [] };
+        const v = new DataView(r.info.buffer, r.info.byteOffset, r.info.byteLength);
+        const frames = Int32Array.from({ length: F }, (_, f) => v.getInt32(48 + 4 * f, true));
+        const o = 48 + ((4 * F + 7) & ~7);
+        const perPair = Array.from({ length: P }, (_, p) => ({ nValidFirst: v.getInt32(o + 24 * p, true), nValidLast: v.getInt32(o + 24 * p + 4, true),
+                                                                rmsFirst: v.getFloat64(o + 24 * p + 8, true), rmsLast: v.getFloat64(o + 24 * p + 16, true) }));
+        return { matrices: r.matrices, status: v.getInt32(0, true), rounds: v.getInt32(4, true), accepted: v.getInt32(8, true), rmsFirst: v.getFloat64(24, true),
+                 rmsLast: v.getFloat64(32, true), frames, pairs: perPair };
+    }
+
+    _bundlePairs(who, pairs, F) {
+        if (!(pairs instanceof Int32Array) && !Array.isArray(pairs)) throw (who + ": pairs must be an array of [a, b] or an Int32Array");
+        const flat = pairs instanceof Int32Array ? pairs : pairs.flat();
+        if (flat.length % 2 !== 0) throw (who + ": pairs must hold two frame indices each");
+        if (flat.length / 2 > 8192) throw (who + ": at most 8192 pairs");
+        for (let p = 0; p < flat.length; p += 2) {
+            const a = flat[p], b = flat[p + 1];
+            if (!Number.isInteger(a) || !Number.isInteger(b) || a < 0 || b < 0 || a >= F || b >= F || a === b) throw (who + ": pair " + (p / 2) + " must name two different frames");
+        }
+        return pairs instanceof Int32Array ? pairs : Int32Array.from(flat);
+    }
+
+    /**
+     * Frame -> canvas matrices chained from pairwise ones, the start bundleAdjust() wants (hg_bundle_chain_from_pairs; host only).
+     * pairMatrices: Float64Array(8 P) or an array of 8 P numbers, matrix p maps frame a to frame b of pairs[p] -- what fitMatches() returns
+     * with a as FROM; options: { frames (required), anchor = 0, transform: 'projective' (default) | 'affine' }.  The anchor is the identity,
+     * frames are reached breadth-first, pairs whose matrix is not finite are skipped, frames never reached come back as NaNs.
+     * Returns Float64Array(8 frames).
+     */
+    chainMatrices(pairMatrices, pairs, options = {}) {
+        if (options === null || options === undefined) options = {};
+        const transform = options.transform === undefined ? 'projective' : options.transform;
+        if (transform !== 'projective' && transform !== 'affine') throw ("chainMatrices: options.transform must be 'projective' or 'affine'");
+        const frames = options.frames;
+        if (!Number.isInteger(frames) || frames < 0 || frames > 256) throw ("chainMatrices: options.frames must be an integer in 0..256");
+        const anchor = options.anchor === undefined ? 0 : options.anchor;
+        if (frames > 0 && (!Number.isInteger(anchor) || anchor < 0 || anchor >= frames)) throw ("chainMatrices: options.anchor must be a frame index");
+        if (!(pairMatrices instanceof Float64Array) && !Array.isArray(pairMatrices)) throw ("chainMatrices: pairMatrices must be a Float64Array or an array of numbers");
+        const pm = pairMatrices instanceof Float64Array ? pairMatrices : Float64Array.from(pairMatrices.flat());
+        const P2 = this._bundlePairs('chainMatrices', pairs, frames);
+        if (pm.length !== (P2.length / 2) * 8) throw ("chainMatrices: pairMatrices must hold 8 numbers per pair");
+        if (frames === 0) return new Float64Array(0);
+        return this._native.bundleChain(transform === 'projective' ? 1 : 0, frames, P2, pm, anchor);
+    }
+
+    /**
+     * The inverse of a matrix in the layouts fitMatches() and bundleAdjust() use (hg_bundle_invert_matrix; host only): what turns a frame ->
+     * canvas matrix into the canvas -> frame matrix the inverse warps take.  m: 8 numbers; options: { transform: 'projective' (default) |
+     * 'affine' }.  Returns Float64Array(8); affine stays affine.
+     */
+    invertMatrix(m, options = {}) {
+        if (options === null || options === undefined) options = {};
+        const transform = options.transform === undefined ? 'projective' : options.transform;
+        if (transform !== 'projective' && transform !== 'affine') throw ("invertMatrix: options.transform must be 'projective' or 'affine'");
+        if ((!(m instanceof Float64Array) && !Array.isArray(m)) || m.length !== 8) throw ("invertMatrix: a matrix is 8 numbers");
+        return this._native.bundleInvert(transform === 'projective' ? 1 : 0, m instanceof Float64Array ? m : Float64Array.from(m));
+    }
+
+    /**
      * The transforms fitMatches() returns, refined on the PIXELS of the two pictures (not part of the reference;
      * hg_align_refine_frames_device in include/hgwarp.h has the rules): Gauss-Newton on the intensity difference between every frame
      * (FROM) and the picture it was matched against (TO), started from `matrices`.  A local refinement: it needs a start within a few

@@ -41,7 +41,8 @@ extern "C" {
                                    hg_mosaic_overlap_stats_device, fitting transforms to matches by that of hg_fit_matches_frames_device);
                                    matching descriptors by the presence of hg_match_descriptors_frames_device, keypoints by the presence of
                                    hg_detect_describe_frames_device, multi-band mosaics by the presence of hg_mosaic_multiband_device, robust mosaics
-                                   by the presence of hg_mosaic_robust_device, thin-plate splines
+                                   by the presence of hg_mosaic_robust_device, adjusting a frame set over all pairs by the presence of
+                                   hg_bundle_adjust_frames_device, thin-plate splines
                                    by the presence of hg_tps_solve_frames_device, dense optical flow by the presence of
                                    hg_flow_dense_frames_device, refining transforms on the pixels by the presence of
                                    hg_align_refine_frames_device */
@@ -961,6 +962,119 @@ int hg_align_refine_frames_device(hg_ctx *ctx, int kind,
                                   int rx, int ry, int rw, int rh, int step,
                                   int photometric, int n_iter, double eps, int min_valid,
                                   const double *d_mats_in, double *d_mats_out, void *d_info, double *d_sums);
+
+/* ------------------------------------------------------------------------------------------------ adjusting a frame set over all pairs
+ * The fit and the alignment give one matrix per PAIR of pictures.  A panorama is no star around one keyframe: frame 7 overlaps frame 6, not
+ * frame 0, so its place in the canvas is a product of pairwise matrices, every factor adds its error, and where a strip closes on itself the
+ * product misses by many pixels.  hg_bundle_adjust_frames_device refines the frame -> canvas matrices of ALL frames at once so that the
+ * matches of all pairs agree in the canvas: Levenberg-Marquardt on the device, nothing but the info record crossing to the host.  Not part of
+ * the reference.  It is the PLANAR-MOSAIC formulation: the residual lives in the canvas, at least one frame is held fixed, the unknowns are
+ * the entries of the matrices themselves (h8 == 1 is kept).  There is no rotation / focal-length camera model and there are no lens terms; a
+ * set whose true geometry is not a chain of homographies (parallax) is not helped.  It is a LOCAL refinement: start from a chain
+ * (hg_bundle_chain_from_pairs).
+ * MATRICES.  The layouts of the fit: projective h0..h7 with h8 == 1, affine m0..m5 in the first six of eight slots (x' = m0 x + m2 y + m4,
+ * y' = m1 x + m3 y + m5).  d_mats_in[f] (8 doubles) maps positions of frame f to the common canvas.  All frames are W x H; the size is used
+ * for the normalisation and the displacement measure only.
+ * PAIRS AND MATCHES.  pairs (HOST) holds n_pairs x 2 int32: pair p = (a, b), a != b, both in 0..n_frames-1; repeated and reversed pairs are
+ * legal.  List p of d_matches is n_points slots of (x, y, u, v) float32, tightly packed, the buffer 16-byte aligned -- the matcher's and the
+ * fit's layout; (x, y) lies in frame a, (u, v) in frame b.  counts (HOST, NULL = n_points each): pair p uses its first counts[p] slots.
+ * d_mask (optional) is the fit's d_mask as it stands: n_pairs x n_points bytes, 0 = leave the slot out.  A "pair" here is what the matcher
+ * and the fit call a frame, so their outputs are this call's inputs with no repacking.
+ * NORMALISATION.  One T for frames and canvas, the alignment's rule with both sides W x H: c = ((W - 1) / 2, (H - 1) / 2), s = 2 / max(W, H),
+ * x' = (x - cx) s.  The iterate of frame f is M' = T M T^-1 divided through by its last entry, formed exactly as the alignment forms H'; the
+ * way back is the alignment's too.  An input with an entry that is not finite (affine: of its first six), or whose M' has one, becomes an
+ * all-NaN iterate.
+ * ONE SLOT, all in f64 with IEEE division and square root, contraction off, sums from left to right.  With (x', y'), (u', v') the normalised
+ * coordinates widened from f32 and A, B the iterates of frames a and b:
+ *   D_a = (A6 x' + A7 y') + 1 (1 for affine), pa = (((A0 x' + A1 y') + A2) / D_a, ((A3 x' + A4 y') + A5) / D_a); D_b, pb alike from B, (u', v').
+ *   The slot is VALID iff it lies below counts[p], its mask byte is not 0, each of its four coordinates c has |c| <= 16777216 (2^24: beyond
+ *   it f32 holds no pixel positions; NaN fails), pa and pb are finite, D_a > 0 and D_b > 0.  NaN, +-Inf and 1e30 are legal coordinates and
+ *   never valid.  r = pa - pb; e = sqrt(rx rx + ry ry) / s, the residual in canvas pixels.
+ *   WEIGHT.  huber == 0 or e <= huber: w = 1, rho = e e.  Else w = huber / e, rho = (2 huber) e - huber huber.  The COST is the sum of rho
+ *   over the valid slots of all pairs (pixels squared); rms = sqrt(cost / n_valid).
+ *   ROWS.  Projective, the x row and the y row of J_a = d pa / d A:  [x'/D_a, y'/D_a, 1/D_a, 0, 0, 0, -((pa_x x') / D_a), -((pa_x y') / D_a)]
+ *   and [0, 0, 0, x'/D_a, y'/D_a, 1/D_a, -((pa_y x') / D_a), -((pa_y y') / D_a)]; J_b is the same on (u', v', pb, D_b), negated.  Affine, in the
+ *   slot order m0..m5: [x', 0, y', 0, 1, 0] and [0, x', 0, y', 0, 1]; J_b negated.  P = 8 or 6.  v_x = [J_a row x | J_b row x | r_x], v_y
+ *   alike: 2 P + 1 values each.
+ * PAIR RECORD.  G = the sum over the pair's valid slots of w (v_x^T v_x + v_y^T v_y), entry (i, j) of a slot formed as w * ((v_x[i] v_x[j])
+ * + (v_y[i] v_y[j])): a symmetric (2 P + 1) x (2 P + 1) matrix whose blocks are sum w J_a^T J_a, sum w J_a^T J_b, sum w J_b^T J_b, sum w
+ * J_a^T r and sum w J_b^T r.  The record is its upper triangle row by row -- entry (i, j), i <= j, at i (2 P + 1) - i (i - 1) / 2 + (j - i)
+ * -- with the LAST entry (r, r) replaced by the pair's cost, then n_valid as a double: (2 P + 1)(P + 1) + 1 = 154 resp. 92 doubles.
+ * d_pair_sums is optional: n_pairs x HG_BUNDLE_SUMS doubles, PASS 0's records, the tail of an affine record zero.
+ * UNKNOWNS.  The P parameters of every FREE frame.  A frame is FIXED where fixed[f] != 0 (HOST, n_frames bytes); at least one must be.  A
+ * frame is UNANCHORED where no path of pairs with counts > 0 leads from it to a fixed frame (decided on the host); it is treated as fixed.
+ * N = P x (free frames) must be <= 2048.  Free frame number i (ascending frame index) owns unknowns i P .. i P + P - 1.
+ * SYSTEM.  H (N x N) and g (N) are sums over the records in ascending pair index: for pair (a, b), sum w J_a^T J_a goes to a's diagonal block,
+ * sum w J_b^T J_b to b's, sum w J_a^T J_b to block (a, b) and its transpose to (b, a) where both are free; g_a -= sum w J_a^T r, g_b -= sum
+ * w J_b^T r.  Blocks of frames that are not free are dropped.
+ * LEVENBERG-MARQUARDT.  Pass 0 evaluates the input: cost c, n_valid n, lambda = lambda0.  Round k = 1 .. n_iter solves (H + lambda I) delta =
+ * g; the parameters are normalised to O(1), so additive damping is well scaled, and H + lambda I is positive definite for every lambda > 0,
+ * frames without a valid match included.  The CANDIDATE is the iterate + delta (parameter k of a frame is entry k of M' for projective, m_k
+ * for affine); a pass evaluates it.  ACCEPT iff every entry of the candidate of every free frame with a finite input is finite, its n_valid
+ * is >= n and its cost is < c: the candidate becomes the iterate, lambda = max(lambda / 10, 1e-12).  Otherwise REJECT: lambda = 10 lambda
+ * and the same H and g are solved again.  The call stops with
+ *   HG_BUNDLE_CONVERGED  when after an accepted round the largest distance, in canvas pixels, between the images of the four frame corners
+ *                        (0, 0), (W-1, 0), (0, H-1), (W-1, H-1) of any free frame with a finite input under the iterate before and after is
+ *                        < eps (the alignment's measure);
+ *   HG_BUNDLE_STALLED    when after a rejected round lambda > 1e12;
+ *   HG_BUNDLE_MAX_ITER   after n_iter rounds (n_iter == 0, or N == 0: an evaluation only, 0 rounds);
+ *   HG_BUNDLE_SINGULAR   when a pivot of the factorisation is not positive and finite; the round counts, its candidate is not evaluated.
+ * SOLVE.  Cholesky of H + lambda I with g as one more row below it: l_jj = sqrt(a_jj), l_ij = a_ij / l_jj, where every a_ij has had l_ik
+ * l_jk subtracted for k = 0, 1, .. j - 1, one product at a time in that order; row N then holds y = L^-1 g.  L^T delta = y by back
+ * substitution: delta_k = y_k / l_kk, then y_i -= l_ki delta_k for i < k, k descending.  For N <= 128 ONE workgroup per round does everything
+ * but the pass -- the pass's reduction, the decision, assembly, damping, factorisation, substitution and the candidate -- with H and g in LDS;
+ * above, the factorisation is blocked (panels of 32 columns: the diagonal block, the rows below it, the trailing matrix) in the scratch.  Both
+ * follow the order above, so they give the same bits.
+ * RESULT.  d_mats_out[f] is the final iterate brought back to pixels, in the input's layout.  The INPUT's bits (all 8 slots) are copied
+ * for fixed frames, unanchored frames and frames whose input is not finite -- such a frame makes all its slots invalid, so its neighbours
+ * simply do not see it -- and for every frame when no round was accepted.  d_mats_out may alias d_mats_in.
+ * INFO.  d_info, 8-byte aligned, 48 + ((4 n_frames + 7) & ~7) + 24 n_pairs bytes: first { int32 status, rounds, accepted, n_valid_first,
+ * n_valid_last, 0; double rms_first, rms_last, lambda_last } -- first: pass 0, last: the returned iterate, an rms is NaN where n_valid is 0,
+ * lambda_last the damping the next round would have used; then one int32 per frame (HG_BUNDLE_FRAME_ADJUSTED: it was an unknown,
+ * _FIXED, _UNANCHORED, _BAD_INPUT: free, but its input is not finite), padded to 8 bytes; then per pair { int32 n_valid_first, n_valid_last;
+ * double rms_first, rms_last }, which tells a caller WHICH pair is inconsistent.
+ * DETERMINISM.  A workgroup takes a CHUNK of 512 consecutive slots of one pair and adds every entry of the record over the chunk's slots in
+ * ascending slot order (one lane per entry); the chunks' records are added in ascending chunk order, the pairs' records in ascending pair
+ * index, the cost and the count over pairs p, p + 256, .. per lane and then through the alignment's tree.  The factorisation's order is the
+ * one above.  No floating-point atomics: two runs of one call give the same bytes in every output.  VALUES are pinned by tolerance.
+ * LIMITS (HG_ERR_INVALID), checked in this order, the shape before the context: unknown kind; W, H outside 1..32768; n_frames outside
+ * 0..256; n_pairs outside 0..8192; n_points outside 0..65536; pairs NULL with n_pairs > 0, a pair index out of range, a == b; a count outside
+ * [0, n_points]; n_iter outside 0..64; eps, lambda0 or huber negative or not finite, lambda0 == 0; (n_frames == 0 is HG_OK here, nothing
+ * is written;) fixed NULL; no fixed frame; more than 2048 unknowns; scratch_bytes below hg_bundle_layout's; NULL d_mats_in, d_mats_out,
+ * d_info, d_scratch, or d_matches while a count is > 0; d_matches or d_scratch not aligned to 16 bytes, matrices, info or sums not to 8; NULL
+ * ctx.
+ * CONTEXT.  As the fit and the alignment: no image, mesh or frame set is needed; queued runs are settled first, then the call is
+ * asynchronous on the ctx stream with no host synchronisation between the rounds (every round is queued; the kernels of rounds after the
+ * stop read the flag and return).  The host arrays are copied before it returns.  It touches no hg_last_*, no sampling mode, no plan, no
+ * policy state and no staged frame set.  hg_bundle_layout gives the scratch for a shape (kind, n_frames, n_pairs, n_points; 0 for no
+ * frames): it may be reused once the call has completed.
+ * HOST HELPERS, in double.  hg_bundle_chain_from_pairs builds a start: pair_mats[p] (8 doubles) maps frame a to frame b -- what the fit
+ * writes with a as FROM.  M_anchor = identity.  Frames are reached breadth-first from the anchor: level 0 is the anchor; for level L = 0, 1,
+ * .. the pairs are walked in ascending index, and a pair with one end in level L and the other not yet reached gives that end its matrix,
+ * M_a = M_b Q resp. M_b = M_a Q^-1 (3 x 3 products, sums from left to right, divided through by the last entry; Q^-1 as below), and puts it
+ * into level L + 1.  Pairs whose matrix has an entry that is not finite are skipped; frames never reached come back as 8 NaNs.  n_frames <=
+ * 256, n_pairs <= 8192.  hg_bundle_invert_matrix: the adjugate of the 3 x 3 form divided through by its last entry, written in the layout of
+ * `kind` (affine stays affine, slots 6 and 7 zero); m_out may be m_in.  It is what turns a frame -> canvas matrix into the canvas -> frame
+ * matrix hg_geometric_set_frames takes.
+ * COST.  A pass is about 600 f64 operations per slot at P = 8; a factorisation N^3 / 3 multiply-subtracts; a round of the large path is 3
+ * launches per 32 columns.  MEASURED (MI355X, whole call, medians of 31; EXPERIMENTS.md, "Bundle adjustment"; tools/bench_bundle.py), 10
+ * rounds each: 64 projective frames x 125 pairs x 2048 matches (504 unknowns) 10.8 ms, of which the pass over all 256 000 matches, its
+ * reduction and the decision are under 0.1 ms -- a round is its solve, 1.07 ms; 16 frames x 29 pairs x 2048 (120 unknowns, one workgroup)
+ * 3.6 ms, 0.35 ms a round; 256 frames x 1014 pairs x 256 matches (2040 unknowns) 49.1 ms, 4.9 ms a round, 68 MB of scratch.  ONE round of
+ * the numpy model of the first case takes 629 ms. */
+enum { HG_BUNDLE_MAX_FRAMES = 256, HG_BUNDLE_MAX_PAIRS = 8192 };
+enum { HG_BUNDLE_CONVERGED = 0, HG_BUNDLE_MAX_ITER = 1, HG_BUNDLE_STALLED = 2, HG_BUNDLE_SINGULAR = 3 };
+enum { HG_BUNDLE_FRAME_ADJUSTED = 0, HG_BUNDLE_FRAME_FIXED = 1, HG_BUNDLE_FRAME_UNANCHORED = 2, HG_BUNDLE_FRAME_BAD_INPUT = 3 };
+enum { HG_BUNDLE_SUMS = 154 };   /* doubles per pair in d_pair_sums */
+int hg_bundle_layout(int kind, int n_frames, int n_pairs, int n_points, size_t *scratch_bytes);
+int hg_bundle_adjust_frames_device(hg_ctx *ctx, int kind, int W, int H, int n_frames, const uint8_t *fixed,
+                                   const int32_t *pairs, int n_pairs, const void *d_matches, int n_points, const int32_t *counts,
+                                   const uint8_t *d_mask, int n_iter, double eps, double lambda0, double huber,
+                                   const double *d_mats_in, double *d_mats_out, void *d_info, double *d_pair_sums,
+                                   void *d_scratch, size_t scratch_bytes);
+int hg_bundle_chain_from_pairs(int kind, int n_frames, const int32_t *pairs, int n_pairs, const double *pair_mats, int anchor,
+                               double *mats_out);
+int hg_bundle_invert_matrix(int kind, const double *m_in, double *m_out);
 
 /* ------------------------------------------------------------------------------------------------ thin-plate splines
  * The piecewise transform is C0 only -- every triangle edge is a kink -- and undefined outside the hull of its mesh.  The THIN-PLATE SPLINE
