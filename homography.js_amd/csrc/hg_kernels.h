@@ -11,6 +11,7 @@
 #include "hg_tps_dev.h"
 #include "hg_flow_dev.h"
 #include "hg_bundle_dev.h"
+#include "hg_camera_dev.h"
 
 namespace hg {
 
@@ -316,6 +317,12 @@ hipError_t launch_bundle(const BundleArgs &a, hipStream_t stream);   // (the fir
 void launch_tps_solve(const TpsSolveArgs &a, hipStream_t stream);
 void launch_tps_field(const TpsFieldArgs &a, int fmt, hipStream_t stream);
 void launch_tps_points(const double *records, int n_points, int n_frames, const float *points, int n_pts, int n_sets, float *out, hipStream_t stream);
+
+// Camera models (hg_k_camera.hip; the rules and the argument blocks: hg_camera_dev.h): k_camera_field, one workgroup per frame, piece of 256
+// columns and band of kCamBandRows rows (fmt = HG_FIELD_*, surface = HG_SURFACE_*); k_camera_points, frame f reading list f % n_sets, canvas ->
+// source or source -> canvas.
+void launch_camera_field(const CamFieldArgs &a, int fmt, int surface, hipStream_t stream);
+void launch_camera_points(const CamPointArgs &a, bool to_source, hipStream_t stream);
 
 // Dense optical flow (hg_k_flow.hip; the rules and the argument blocks: hg_flow_dev.h): k_flow_up, the flow of a level from the level below it;
 // k_flow_iter, one Jacobi iteration of a level over tiles of kFlowTileW x kFlowTileH pixels; k_flow_finish, field, flow pairs and residual of

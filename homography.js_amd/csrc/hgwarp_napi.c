@@ -1500,6 +1500,150 @@ static napi_value fn_warp_thin_plate(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* The camera models ("camera models" in include/hgwarp.h).  Host only, no handle:
+ *   cameraPackRecord(R: Float64Array(9), fx, fy, cx, cy, dist: Float64Array(5) | null, W, H) -> Float64Array(32): hg_camera_pack_record.
+ *   cameraLimits(record: Float64Array(32), W, H, surface, scale, u0, v0) -> Int32Array(4) {x, y, width, height}: hg_camera_limits.
+ *   cameraFocals(H: Float64Array(9)) -> Float64Array(4) {fFrom, fTo, okFrom, okTo}: hg_camera_focals_from_matrix.
+ *   cameraRotation(H: Float64Array(9), kFrom: Float64Array(4), kTo: Float64Array(4)) -> Float64Array(9): hg_camera_rotation_from_matrix. */
+static int get_f64(napi_env env, napi_value v, double *out)
+{
+    if (napi_get_value_double(env, v, out) != napi_ok) { throw_str(env, "hgwarp: expected a number"); return 0; }
+    return 1;
+}
+
+static napi_value fn_camera_pack_record(napi_env env, napi_callback_info info)
+{
+    napi_value a[8];
+    if (!get_args(env, info, 8, a)) return NULL;
+    size_t n_r = 0, n_d = 0; double fx, fy, cx, cy; int W, H;
+    double *R = (double *)get_typed(env, a[0], napi_float64_array, &n_r, "rotation"); if (!R) return NULL;
+    if (!get_f64(env, a[1], &fx) || !get_f64(env, a[2], &fy) || !get_f64(env, a[3], &cx) || !get_f64(env, a[4], &cy)) return NULL;
+    napi_valuetype vt;
+    NAPI_OK(napi_typeof(env, a[5], &vt));
+    double *dist = NULL;
+    if (vt != napi_null && vt != napi_undefined) { dist = (double *)get_typed(env, a[5], napi_float64_array, &n_d, "distortion"); if (!dist) return NULL; }
+    if (!get_i32(env, a[6], &W) || !get_i32(env, a[7], &H)) return NULL;
+    if (n_r != 9 || (dist && n_d != 5)) return throw_str(env, "hgwarp: cameraPackRecord: a rotation is 9 numbers, a distortion 5");
+    void *p; napi_value out;
+    if (!(out = make_typed(env, napi_float64_array, HG_CAMERA_RECORD_DOUBLES, 8, &p))) return NULL;
+    HG_CALL(NULL, "hg_camera_pack_record", hg_camera_pack_record(R, fx, fy, cx, cy, dist, W, H, (double *)p));
+    return out;
+}
+
+static napi_value fn_camera_limits(napi_env env, napi_callback_info info)
+{
+    napi_value a[7];
+    if (!get_args(env, info, 7, a)) return NULL;
+    size_t n = 0; int W, H, surface; double scale, u0, v0;
+    double *rec = (double *)get_typed(env, a[0], napi_float64_array, &n, "record"); if (!rec) return NULL;
+    if (!get_i32(env, a[1], &W) || !get_i32(env, a[2], &H) || !get_i32(env, a[3], &surface)) return NULL;
+    if (!get_f64(env, a[4], &scale) || !get_f64(env, a[5], &u0) || !get_f64(env, a[6], &v0)) return NULL;
+    if (n != HG_CAMERA_RECORD_DOUBLES) return throw_str(env, "hgwarp: cameraLimits: a record is 32 numbers");
+    void *p; napi_value out;
+    if (!(out = make_typed(env, napi_int32_array, 4, 4, &p))) return NULL;
+    HG_CALL(NULL, "hg_camera_limits", hg_camera_limits(rec, W, H, surface, scale, u0, v0, (int32_t *)p));
+    return out;
+}
+
+static napi_value fn_camera_focals(napi_env env, napi_callback_info info)
+{
+    napi_value a[1];
+    if (!get_args(env, info, 1, a)) return NULL;
+    size_t n = 0;
+    double *m = (double *)get_typed(env, a[0], napi_float64_array, &n, "matrix"); if (!m) return NULL;
+    if (n != 9) return throw_str(env, "hgwarp: cameraFocals: a matrix is 9 numbers");
+    void *p; napi_value out;
+    if (!(out = make_typed(env, napi_float64_array, 4, 8, &p))) return NULL;
+    double *o = (double *)p; int ok_from = 0, ok_to = 0;
+    HG_CALL(NULL, "hg_camera_focals_from_matrix", hg_camera_focals_from_matrix(m, &o[0], &o[1], &ok_from, &ok_to));
+    o[2] = ok_from; o[3] = ok_to;
+    return out;
+}
+
+static napi_value fn_camera_rotation(napi_env env, napi_callback_info info)
+{
+    napi_value a[3];
+    if (!get_args(env, info, 3, a)) return NULL;
+    size_t n = 0, n_a = 0, n_b = 0;
+    double *m = (double *)get_typed(env, a[0], napi_float64_array, &n, "matrix"); if (!m) return NULL;
+    double *ka = (double *)get_typed(env, a[1], napi_float64_array, &n_a, "kFrom"); if (!ka) return NULL;
+    double *kb = (double *)get_typed(env, a[2], napi_float64_array, &n_b, "kTo"); if (!kb) return NULL;
+    if (n != 9 || n_a != 4 || n_b != 4) return throw_str(env, "hgwarp: cameraRotation: a matrix is 9 numbers, an intrinsic 4");
+    void *p; napi_value out;
+    if (!(out = make_typed(env, napi_float64_array, 9, 8, &p))) return NULL;
+    HG_CALL(NULL, "hg_camera_rotation_from_matrix", hg_camera_rotation_from_matrix(m, ka, kb, (double *)p));
+    return out;
+}
+
+/* warpCamera(handle, records, windows, surface, scale, u0, v0, output, images | null, W, H, nImages): the frames of a camera set on a plane,
+ * a cylinder or a sphere (hg_field_camera_frames_device -> a remap), all on the device.  records: Float64Array of F x 32 doubles
+ * (cameraPackRecord); windows: Int32Array of F x (x, y, width, height) of the canvas; output, images, W, H, nImages and the result's data
+ * as for warpThinPlate.  Returns { data: Uint8Array, the frames packed at the 256-byte grain }.  Only the results come down. */
+static napi_value fn_warp_camera(napi_env env, napi_callback_info info)
+{
+    napi_value a[12];
+    if (!get_args(env, info, 12, a)) return NULL;
+    handle_t *h = get_handle(env, a[0]); if (!h) return NULL;
+    int surface, output, W, H, n_img; size_t n_r = 0, n_w = 0, n_i = 0; double scale, u0, v0;
+    double *rec = (double *)get_typed(env, a[1], napi_float64_array, &n_r, "records"); if (!rec && n_r) return NULL;
+    int32_t *win = (int32_t *)get_typed(env, a[2], napi_int32_array, &n_w, "windows"); if (!win && n_w) return NULL;
+    if (!get_i32(env, a[3], &surface) || !get_f64(env, a[4], &scale) || !get_f64(env, a[5], &u0) || !get_f64(env, a[6], &v0) || !get_i32(env, a[7], &output)) return NULL;
+    napi_valuetype vt;
+    NAPI_OK(napi_typeof(env, a[8], &vt));
+    uint8_t *img = NULL;
+    if (vt != napi_null && vt != napi_undefined) { img = (uint8_t *)get_typed(env, a[8], napi_uint8_array, &n_i, "images"); if (!img) return NULL; }
+    if (!get_i32(env, a[9], &W) || !get_i32(env, a[10], &H) || !get_i32(env, a[11], &n_img)) return NULL;
+    if (n_w % 4 != 0 || n_w / 4 > 4096 || n_r != (n_w / 4) * HG_CAMERA_RECORD_DOUBLES || output < 0 || output > 3 || W < 1 || H < 1)
+        return throw_str(env, "hgwarp: warpCamera: records, windows, output or the source size is out of range");
+    const size_t F = n_w / 4;
+    const int picture = output < 2, fmt = (output == 0 || output == 2) ? HG_FIELD_INDEX : HG_FIELD_COORDS;
+    const size_t plane = (size_t)W * (size_t)H * 4;
+    if (picture && (!img || n_img < 1 || n_i != plane * (size_t)n_img)) return throw_str(env, "hgwarp: warpCamera: images must hold nImages RGBA pictures of W x H");
+    hg_geom *g = (hg_geom *)calloc(F ? F : 1, sizeof *g);
+    if (!g) return throw_str(env, "hgwarp: out of memory");
+    size_t fld_total = 0, out_total = 0;
+    for (size_t f = 0; f < F; f++) {
+        g[f].x_off = win[4 * f]; g[f].y_off = win[4 * f + 1]; g[f].obj_w = win[4 * f + 2]; g[f].obj_h = win[4 * f + 3];
+        const size_t px = (g[f].obj_w > 0 && g[f].obj_h > 0) ? (size_t)g[f].obj_w * (size_t)g[f].obj_h : 0;
+        fld_total += (px * (fmt == HG_FIELD_INDEX ? 4 : 8) + 255) & ~(size_t)255;
+        out_total += (px * 4 + 255) & ~(size_t)255;
+    }
+    const size_t res_total = picture ? out_total : fld_total;
+    void *p_data;
+    napi_value out, v_data;
+    if (!(v_data = make_typed(env, napi_uint8_array, res_total, 1, &p_data))) { free(g); return NULL; }
+    if (napi_create_object(env, &out) != napi_ok || napi_set_named_property(env, out, "data", v_data) != napi_ok) { free(g); return throw_str(env, "hgwarp: N-API call failed"); }
+    if (!F) { free(g); return out; }
+#define CAM_PAD(b) (((size_t)(b) + 255) & ~(size_t)255)
+    const size_t o_rec = 0, o_fld = o_rec + CAM_PAD(n_r * 8), o_img = o_fld + CAM_PAD(fld_total), o_out = o_img + CAM_PAD(picture ? n_i : 0),
+                 total = o_out + CAM_PAD(picture ? out_total : 0);
+#undef CAM_PAD
+    void *d = NULL;
+    int rc = hg_device_alloc(h->ctx, total, &d);
+    if (rc != HG_OK) { napi_value e = throw_hg(env, h->ctx, "hg_device_alloc", rc); free(g); return e; }
+    uint8_t *b = (uint8_t *)d;
+    const char *what = "hg_copy_to_device";
+    rc = hg_copy_to_device(h->ctx, b + o_rec, rec, n_r * 8);
+    if (rc == HG_OK && picture) rc = hg_copy_to_device(h->ctx, b + o_img, img, n_i);
+    if (rc == HG_OK) {
+        what = "hg_field_camera_frames_device";
+        rc = hg_field_camera_frames_device(h->ctx, (const double *)(b + o_rec), g, (int)F, W, H, surface, scale, u0, v0, fmt, NULL, b + o_fld);
+    }
+    if (rc == HG_OK && output == 0) {
+        what = "hg_remap_index_frames_device";
+        rc = hg_remap_index_frames_device(h->ctx, g, (int)F, b + o_fld, NULL, b + o_img, (size_t)W * (size_t)H, n_img, plane, 4, b + o_out, NULL);
+    }
+    if (rc == HG_OK && output == 1) {
+        what = "hg_remap_bilinear_frames_device";
+        rc = hg_remap_bilinear_frames_device(h->ctx, g, (int)F, b + o_fld, NULL, b + o_img, W, H, n_img, plane, HG_ELEM_U8, 4, b + o_out, NULL);
+    }
+    if (rc == HG_OK && res_total) { what = "hg_copy_to_host"; rc = hg_copy_to_host(h->ctx, p_data, picture ? b + o_out : b + o_fld, res_total); }
+    free(g);
+    if (rc != HG_OK) { napi_value e = throw_hg(env, h->ctx, what, rc); hg_device_free(h->ctx, d); return e; }
+    HG_CALL(h->ctx, "hg_device_free", hg_device_free(h->ctx, d));
+    return out;
+}
+
 /* denseFlow(handle, from, to, W, H, channels, nFrames, nToSets, levels, iterations, radius, minEig, maxUpdate, flags): dense optical flow
  * between nFrames pairs of u8 planes (hg_flow_dense_frames_device), all on the device.  from: Uint8Array of nFrames planes of W x H x
  * channels, to: Uint8Array of nToSets planes (frame f is registered onto plane f % nToSets).  flags: 1 = the field comes down, 2 = the
@@ -2451,6 +2595,8 @@ static napi_value init(napi_env env, napi_value exports)
         { "alignBegin", fn_align_begin }, { "alignLevel", fn_align_level }, { "alignScaleMatrix", fn_align_scale_matrix }, { "alignEnd", fn_align_end },
         { "bundleAdjust", fn_bundle_adjust }, { "bundleChain", fn_bundle_chain }, { "bundleInvert", fn_bundle_invert },
         { "warpThinPlate", fn_warp_thin_plate },
+        { "cameraPackRecord", fn_camera_pack_record }, { "cameraLimits", fn_camera_limits }, { "cameraFocals", fn_camera_focals },
+        { "cameraRotation", fn_camera_rotation }, { "warpCamera", fn_warp_camera },
         { "denseFlow", fn_dense_flow },
         { "matchDescriptors", fn_match_descriptors },
         { "detectAndDescribe", fn_detect_describe },

@@ -53,6 +53,10 @@ BUNDLE_PAIR_INFO = np.dtype([("n_valid_first", np.int32), ("n_valid_last", np.in
 TPS_MAX_POINTS = 1024
 TPS_OK, TPS_SINGULAR, TPS_BAD_INPUT = 0, 1, 2
 TPS_HEAD = 16
+# camera models (hg_field_camera_frames_device): the canvas surfaces, the doubles of a frame's record, the rounds of the fixed-point undistortion
+SURFACE_PLANE, SURFACE_CYLINDER, SURFACE_SPHERE = 0, 1, 2
+CAMERA_RECORD_DOUBLES = 32
+CAMERA_UNDISTORT_ITERS = 20
 
 # every symbol include/hgwarp.h declares (tests check that the built library exports all of them)
 EXPORTS = [
@@ -90,6 +94,8 @@ EXPORTS = [
     "hg_align_scale_matrix", "hg_align_refine_frames_device",
     "hg_bundle_layout", "hg_bundle_adjust_frames_device", "hg_bundle_chain_from_pairs", "hg_bundle_invert_matrix",
     "hg_tps_layout", "hg_tps_solve_frames_device", "hg_tps_field_layout", "hg_field_tps_frames_device", "hg_points_tps_frames_device",
+    "hg_camera_pack_record", "hg_camera_limits", "hg_camera_focals_from_matrix", "hg_camera_rotation_from_matrix",
+    "hg_field_camera_frames_device", "hg_points_camera_to_source_frames_device", "hg_points_camera_to_canvas_frames_device",
     "hg_flow_layout", "hg_flow_dense_frames_device", "hg_field_compose_frames_device",
     "hg_match_descriptors_frames_device",
     "hg_detect_layout", "hg_describe_pattern", "hg_detect_describe_frames_device",
@@ -225,6 +231,13 @@ def lib():
         "hg_tps_field_layout": (i, [C.POINTER(Geom), i, i, C.POINTER(sz)]),
         "hg_field_tps_frames_device": (i, [vp, vp, i, C.POINTER(Geom), i, i, i, i, i, C.POINTER(sz), vp, vp]),
         "hg_points_tps_frames_device": (i, [vp, vp, i, i, vp, i, i, vp]),
+        "hg_camera_pack_record": (i, [f64p, d, d, d, d, f64p, i, i, f64p]),
+        "hg_camera_limits": (i, [f64p, i, i, i, d, d, d, C.POINTER(C.c_int32)]),
+        "hg_camera_focals_from_matrix": (i, [f64p, f64p, f64p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "hg_camera_rotation_from_matrix": (i, [f64p, f64p, f64p, f64p]),
+        "hg_field_camera_frames_device": (i, [vp, vp, C.POINTER(Geom), i, i, i, i, d, d, d, i, C.POINTER(sz), vp]),
+        "hg_points_camera_to_source_frames_device": (i, [vp, vp, i, i, d, d, d, vp, i, i, vp]),
+        "hg_points_camera_to_canvas_frames_device": (i, [vp, vp, i, i, d, d, d, vp, i, i, vp]),
         "hg_flow_layout": (i, [i, i, i, i, i, i, C.POINTER(sz)]),
         "hg_flow_dense_frames_device": (i, [vp, vp, i, sz, vp, i, sz, i, i, i, i, i, i, d, d, C.POINTER(sz), vp, vp, vp, vp, vp]),
         "hg_field_compose_frames_device": (i, [vp, C.POINTER(Geom), i, vp, C.POINTER(sz), vp, i, i, i, sz, vp, C.POINTER(sz)]),
@@ -405,6 +418,46 @@ def tps_field_layout(geoms, step):
     total = C.c_size_t(0)
     _check(lib().hg_tps_field_layout(_geoms(geoms) if len(geoms) else None, len(geoms), int(step), C.byref(total)))
     return total.value
+
+
+def camera_pack_record(rotation, focal, principal, w, h, distortion=None):
+    """hg_camera_pack_record: the 32-double record of one camera.  rotation: 3 x 3, camera <- world; focal: f or (fx, fy); principal: (cx, cy);
+    distortion: (k1, k2, p1, p2, k3) or None; w, h: the picture's size (r2_max comes from its corners and edge midpoints)."""
+    _, rp = _f64(np.asarray(rotation, np.float64).reshape(9))
+    fx, fy = (float(focal), float(focal)) if np.isscalar(focal) else (float(focal[0]), float(focal[1]))
+    dk = None
+    if distortion is not None:
+        dk, dp = _f64(np.asarray(distortion, np.float64).reshape(5))
+    out = np.empty(CAMERA_RECORD_DOUBLES, np.float64)
+    _check(lib().hg_camera_pack_record(rp, fx, fy, float(principal[0]), float(principal[1]), dp if dk is not None else None, int(w), int(h),
+                                       out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def camera_limits(record, w, h, surface, scale, u0, v0):
+    """hg_camera_limits: the window (x_off, y_off, w, h) of the canvas that holds the frame of `record`, one pixel of margin included."""
+    _, rp = _f64(np.asarray(record, np.float64).reshape(CAMERA_RECORD_DOUBLES))
+    out = (C.c_int32 * 4)()
+    _check(lib().hg_camera_limits(rp, int(w), int(h), int(surface), float(scale), float(u0), float(v0), out))
+    return tuple(int(v) for v in out)
+
+
+def camera_focals_from_matrix(h9):
+    """hg_camera_focals_from_matrix: (f_from, f_to, ok_from, ok_to) of a homography between pictures in principal-point coordinates."""
+    _, hp = _f64(np.asarray(h9, np.float64).reshape(9))
+    f0, f1, k0, k1 = C.c_double(0), C.c_double(0), C.c_int(0), C.c_int(0)
+    _check(lib().hg_camera_focals_from_matrix(hp, C.byref(f0), C.byref(f1), C.byref(k0), C.byref(k1)))
+    return f0.value, f1.value, bool(k0.value), bool(k1.value)
+
+
+def camera_rotation_from_matrix(h9, k_from, k_to):
+    """hg_camera_rotation_from_matrix: the rotation (3 x 3, TO camera <- FROM camera) nearest to K_to^-1 H K_from; K = (fx, fy, cx, cy)."""
+    _, hp = _f64(np.asarray(h9, np.float64).reshape(9))
+    _, ap = _f64(np.asarray(k_from, np.float64).reshape(4))
+    _, bp = _f64(np.asarray(k_to, np.float64).reshape(4))
+    out = np.empty(9, np.float64)
+    _check(lib().hg_camera_rotation_from_matrix(hp, ap, bp, out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out.reshape(3, 3)
 
 
 def flow_layout(w, h, channels, n_frames, n_to_sets, levels):
@@ -1156,6 +1209,27 @@ class Context:
         vp = lambda v: C.c_void_p(int(v) or None)
         self._c(lib().hg_field_tps_frames_device(self._h, vp(d_records), int(n_points), _geoms(geoms) if len(geoms) else None, len(geoms), int(w), int(h),
                                                  int(fmt), int(step), fo, vp(d_field), vp(d_scratch)))
+
+    def field_camera_frames_device(self, d_records, geoms, w, h, surface, scale, u0, v0, fmt, d_field, field_offsets=None):
+        """hg_field_camera_frames_device: the source field (FIELD_INDEX / FIELD_COORDS) of the cameras at d_records (32 doubles each) over the
+        canvas windows `geoms` of a SURFACE_* at `scale` pixels per radian around (u0, v0), into a source of w x h pixels.  Asynchronous."""
+        vp = C.c_void_p
+        offs = (C.c_size_t * len(field_offsets))(*[int(o) for o in field_offsets]) if field_offsets is not None else None
+        self._c(lib().hg_field_camera_frames_device(self._h, vp(d_records), _geoms(geoms) if len(geoms) else None, len(geoms), int(w), int(h), int(surface),
+                                                    float(scale), float(u0), float(v0), int(fmt), offs, vp(d_field)))
+
+    def points_camera_to_source_frames_device(self, d_records, n_frames, surface, scale, u0, v0, d_points, n_pts, n_sets, d_out):
+        """hg_points_camera_to_source_frames_device: n_sets lists of n_pts absolute canvas positions to source positions of the frames' cameras
+        (frame f reads list f % n_sets); a point behind the camera or beyond r2_max is the NaN pattern.  Asynchronous."""
+        vp = C.c_void_p
+        self._c(lib().hg_points_camera_to_source_frames_device(self._h, vp(d_records), int(n_frames), int(surface), float(scale), float(u0), float(v0),
+                                                               vp(d_points), int(n_pts), int(n_sets), vp(d_out)))
+
+    def points_camera_to_canvas_frames_device(self, d_records, n_frames, surface, scale, u0, v0, d_points, n_pts, n_sets, d_out):
+        """hg_points_camera_to_canvas_frames_device: the same lists, source positions to canvas positions.  Asynchronous."""
+        vp = C.c_void_p
+        self._c(lib().hg_points_camera_to_canvas_frames_device(self._h, vp(d_records), int(n_frames), int(surface), float(scale), float(u0), float(v0),
+                                                               vp(d_points), int(n_pts), int(n_sets), vp(d_out)))
 
     def points_tps_frames_device(self, d_records, n_points, n_frames, d_points, n_pts, n_sets, d_out):
         """hg_points_tps_frames_device: n_sets lists of n_pts absolute from-space positions through the frames' splines (frame f reads list

@@ -834,6 +834,143 @@ class Homography {
     }
 
     /**
+     * Frames projected onto a plane, a cylinder or a sphere from a camera per frame: what a panorama wider than about 100 degrees needs,
+     * and the only way to say "this picture was taken with k1 = -0.2" (not part of the reference; "camera models" in include/hgwarp.h has
+     * the rules).  The fields are written and the pictures gathered on the device; only the results come down.
+     * cameras: one per frame, { rotation: 9 numbers (row-major, camera <- world) or three rows of three, focal: f or [fx, fy],
+     *          principal: [cx, cy] (default: the centre of the source), distortion: [k1, k2, p1, p2, k3] (default: none) }.
+     * options: { surface = 'sphere' ('plane' / 'cylinder'), scale (required: pixels per radian; for the plane the canvas focal length),
+     *            center = [0, 0] (the canvas position of azimuth 0, elevation 0),
+     *            window: { x, y, width, height } for every frame, or an array of them (default: hg_camera_limits of each camera),
+     *            sampling = 'nearest' ('bilinear'; pictures only), output = 'image' ('index' / 'coords': the source field itself),
+     *            images: ImageData-shaped sources of one size, frame f reads images[f % images.length] (default: the instance's image) }.
+     * Returns one record per frame: { data, width, height, x, y }; pixels no camera ray reaches are empty (zero pixels, index -1, NaN
+     * coordinates).  Changes no state of the instance.  Throws a bare string for cameras that do not fit and options out of range.
+     */
+    warpCamera(cameras, options = {}) {
+        if (options === null || options === undefined) options = {};
+        if (!Array.isArray(cameras)) throw ("warpCamera: cameras must be an array of { rotation, focal, principal, distortion }");
+        const F = cameras.length;
+        if (F > 4096) throw ("warpCamera: at most 4096 frames");
+        const surface = options.surface === undefined ? 'sphere' : options.surface;
+        const surfaceCode = ['plane', 'cylinder', 'sphere'].indexOf(surface);
+        if (surfaceCode < 0) throw ("warpCamera: options.surface must be 'plane', 'cylinder' or 'sphere'");
+        const scale = options.scale;
+        if (typeof scale !== 'number' || !Number.isFinite(scale) || scale <= 0) throw ("warpCamera: options.scale must be a finite number > 0 (pixels per radian)");
+        const center = options.center === undefined ? [0, 0] : options.center;
+        if (!Array.isArray(center) || center.length !== 2 || !center.every((v) => typeof v === 'number' && Number.isFinite(v))) throw ("warpCamera: options.center must be [u0, v0], two finite numbers");
+        const output = options.output === undefined ? 'image' : options.output;
+        if (output !== 'image' && output !== 'index' && output !== 'coords') throw ("warpCamera: options.output must be 'image', 'index' or 'coords'");
+        const sampling = options.sampling === undefined ? 'nearest' : options.sampling;
+        if (sampling !== 'nearest' && sampling !== 'bilinear') throw ("warpCamera: options.sampling must be 'nearest' or 'bilinear'");
+        let W = this._width, H = this._height, planes = null, nImages = 0;
+        if (options.images !== undefined && options.images !== null) {
+            const images = options.images;
+            if (!Array.isArray(images) || images.length === 0) throw ("warpCamera: options.images needs a non-empty array of ImageData-shaped sources");
+            W = images[0] ? images[0].width : 0; H = images[0] ? images[0].height : 0;
+            for (const im of images)
+                if (!im || !ArrayBuffer.isView(im.data) || im.width !== W || im.height !== H || im.data.length !== W * H * 4)
+                    throw ("warpCamera: every image must be ImageData-shaped RGBA and of one size");
+            if (output === 'image') {
+                planes = new Uint8Array(images.length * W * H * 4);
+                images.forEach((im, k) => planes.set(im.data, k * W * H * 4));
+                nImages = images.length;
+            }
+        } else if (output === 'image') {
+            if (this._image === null) throw ("warp() must receive an image if it was not setted before through `setImage(img)` or  `setSourcePoints(points, img)`");
+            planes = new Uint8Array(this._image.buffer, this._image.byteOffset, this._image.length);
+            nImages = 1;
+        }
+        if (!Number.isInteger(W) || !Number.isInteger(H) || W < 1 || H < 1) throw ("warpCamera: the source size is not known: give options.images or set an image first");
+        const records = new Float64Array(F * 32);
+        cameras.forEach((c, f) => records.set(this._cameraRecord('warpCamera', c, f, W, H), f * 32));
+        const isInt = (v) => Number.isInteger(v) && Math.abs(v) <= 0x7fffffff;
+        if (Array.isArray(options.window) && options.window.length !== F) throw ("warpCamera: options.window must hold one window per frame");
+        const windows = new Int32Array(4 * F);
+        for (let f = 0; f < F; f++) {
+            let w = Array.isArray(options.window) ? options.window[f] : options.window;
+            if (w === undefined || w === null) {
+                const l = this._native.cameraLimits(records.subarray(f * 32, f * 32 + 32), W, H, surfaceCode, scale, center[0], center[1]);
+                w = { x: l[0], y: l[1], width: l[2], height: l[3] };
+            }
+            if (!w || !isInt(w.x) || !isInt(w.y) || !isInt(w.width) || !isInt(w.height)) throw ("warpCamera: options.window must be { x, y, width, height }, four integers");
+            windows.set([w.x, w.y, Math.max(w.width, 0), Math.max(w.height, 0)], 4 * f);
+        }
+        const code = output === 'image' ? (sampling === 'bilinear' ? 1 : 0) : (output === 'index' ? 2 : 3);
+        const r = this._native.warpCamera(this._ctx, records, windows, surfaceCode, scale, center[0], center[1], code, planes, W, H, nImages);
+        const px = code === 3 ? 8 : 4;
+        let off = 0;
+        return cameras.map((c, f) => {
+            const width = windows[4 * f + 2], height = windows[4 * f + 3], bytes = width * height * px;
+            const b = r.data.buffer.slice(r.data.byteOffset + off, r.data.byteOffset + off + bytes);
+            off += (bytes + 255) & ~255;
+            const data = code === 2 ? new Int32Array(b) : code === 3 ? new Float32Array(b) : new Uint8ClampedArray(b);
+            return { data, width, height, x: windows[4 * f], y: windows[4 * f + 1] };
+        });
+    }
+
+    /** The 32-double record of one camera of warpCamera (hg_camera_pack_record), after the class's own checks of its shape. */
+    _cameraRecord(who, c, f, W, H) {
+        if (c === null || typeof c !== 'object') throw (who + ": camera " + f + " must be { rotation, focal, principal, distortion }");
+        const rot = Array.isArray(c.rotation) ? c.rotation.flat() : c.rotation;
+        if ((!Array.isArray(rot) && !(rot instanceof Float64Array)) || rot.length !== 9 || !Array.from(rot).every((v) => typeof v === 'number'))
+            throw (who + ": camera " + f + ": rotation must be 9 numbers, row-major, or three rows of three");
+        const fo = typeof c.focal === 'number' ? [c.focal, c.focal] : c.focal;
+        if (!Array.isArray(fo) || fo.length !== 2 || !fo.every((v) => typeof v === 'number' && Number.isFinite(v) && v > 0))
+            throw (who + ": camera " + f + ": focal must be a finite number > 0 or [fx, fy]");
+        const pp = c.principal === undefined ? [W / 2, H / 2] : c.principal;
+        if (!Array.isArray(pp) || pp.length !== 2 || !pp.every((v) => typeof v === 'number' && Number.isFinite(v)))
+            throw (who + ": camera " + f + ": principal must be [cx, cy], two finite numbers");
+        let dist = null;
+        if (c.distortion !== undefined && c.distortion !== null) {
+            if (!Array.isArray(c.distortion) || c.distortion.length !== 5 || !c.distortion.every((v) => typeof v === 'number' && Number.isFinite(v)))
+                throw (who + ": camera " + f + ": distortion must be [k1, k2, p1, p2, k3], five finite numbers");
+            dist = Float64Array.from(c.distortion);
+        }
+        return this._native.cameraPackRecord(Float64Array.from(rot), fo[0], fo[1], pp[0], pp[1], dist, W, H);
+    }
+
+    /**
+     * From homographies to cameras: the focal lengths and the rotation a homography between two pictures of one rotating camera implies
+     * (hg_camera_focals_from_matrix, hg_camera_rotation_from_matrix).  matrix: 9 numbers, row-major, or the 8 of this library's projective
+     * matrices (h8 = 1), x_to ~ H x_from in PIXEL coordinates.
+     * options: { principalFrom = [0, 0], principalTo = [0, 0] (the principal points; the focal lengths are estimated in coordinates relative
+     *            to them), focalFrom, focalTo (numbers or [fx, fy]: skip the estimate of that side) }.
+     * Returns { focalFrom, focalTo, okFrom, okTo, rotation } -- rotation: Float64Array(9), TO camera <- FROM camera, or null when a focal
+     * length is neither given nor estimable (a rotation about the optical axis says nothing about it).
+     */
+    cameraFromMatrices(matrix, options = {}) {
+        if (options === null || options === undefined) options = {};
+        if ((!Array.isArray(matrix) && !(matrix instanceof Float64Array)) || (matrix.length !== 9 && matrix.length !== 8) || !Array.from(matrix).every((v) => typeof v === 'number' && Number.isFinite(v)))
+            throw ("cameraFromMatrices: a matrix is 9 (or 8) finite numbers");
+        const m = Float64Array.from(matrix.length === 9 ? matrix : [...matrix, 1]);
+        const point = (p, name) => {
+            const v = p === undefined ? [0, 0] : p;
+            if (!Array.isArray(v) || v.length !== 2 || !v.every((t) => typeof t === 'number' && Number.isFinite(t))) throw ("cameraFromMatrices: options." + name + " must be [cx, cy], two finite numbers");
+            return v;
+        };
+        const focal = (v, name) => {
+            if (v === undefined || v === null) return null;
+            const fo = typeof v === 'number' ? [v, v] : v;
+            if (!Array.isArray(fo) || fo.length !== 2 || !fo.every((t) => typeof t === 'number' && Number.isFinite(t) && t > 0)) throw ("cameraFromMatrices: options." + name + " must be a finite number > 0 or [fx, fy]");
+            return fo;
+        };
+        const pf = point(options.principalFrom, 'principalFrom'), pt = point(options.principalTo, 'principalTo');
+        let ff = focal(options.focalFrom, 'focalFrom'), ft = focal(options.focalTo, 'focalTo');
+        // the matrix between coordinates relative to the principal points: T_to^-1 H T_from, T = the shift by the principal point
+        const c = new Float64Array(9);
+        for (let r = 0; r < 3; r++) { c[3 * r] = m[3 * r]; c[3 * r + 1] = m[3 * r + 1]; c[3 * r + 2] = m[3 * r] * pf[0] + m[3 * r + 1] * pf[1] + m[3 * r + 2]; }
+        for (let k = 0; k < 3; k++) { c[k] -= pt[0] * c[6 + k]; c[3 + k] -= pt[1] * c[6 + k]; }
+        const e = this._native.cameraFocals(c);
+        const okFrom = ff !== null || e[2] === 1, okTo = ft !== null || e[3] === 1;
+        if (ff === null && e[2] === 1) ff = [e[0], e[0]];
+        if (ft === null && e[3] === 1) ft = [e[1], e[1]];
+        let rotation = null;
+        if (okFrom && okTo) rotation = this._native.cameraRotation(m, Float64Array.from([ff[0], ff[1], pf[0], pf[1]]), Float64Array.from([ft[0], ft[1], pt[0], pt[1]]));
+        return { focalFrom: ff === null ? null : (ff[0] === ff[1] ? ff[0] : ff), focalTo: ft === null ? null : (ft[0] === ft[1] ? ft[0] : ft), okFrom, okTo, rotation };
+    }
+
+    /**
      * Dense optical flow between pairs of pictures: a per-pixel, non-parametric registration for what a homography cannot follow --
      * parallax, a rolling shutter, things that move (not part of the reference; hg_flow_dense_frames_device in include/hgwarp.h has the
      * rule, pyramidal Lucas-Kanade with integer window sums, exact to the bit).

@@ -44,7 +44,8 @@ extern "C" {
                                    by the presence of hg_mosaic_robust_device, adjusting a frame set over all pairs by the presence of
                                    hg_bundle_adjust_frames_device, thin-plate splines
                                    by the presence of hg_tps_solve_frames_device, dense optical flow by the presence of
-                                   hg_flow_dense_frames_device, refining transforms on the pixels by the presence of
+                                   hg_flow_dense_frames_device, camera models by the presence of hg_field_camera_frames_device,
+                                   refining transforms on the pixels by the presence of
                                    hg_align_refine_frames_device */
 
 enum {
@@ -1151,6 +1152,101 @@ int hg_field_tps_frames_device(hg_ctx *ctx, const double *d_records, int n_point
                                int format, int step, const size_t *field_offsets, void *d_field, void *d_scratch);
 int hg_points_tps_frames_device(hg_ctx *ctx, const double *d_records, int n_points, int n_frames, const void *d_points, int n_pts, int n_sets,
                                 void *d_out);
+
+/* ------------------------------------------------------------------------------------------------ camera models
+ * Every geometry above is a map between two planes.  On a planar canvas the frames at the ends of a strip stretch without bound, and at 180
+ * degrees the map is singular: a panorama wider than about 100 degrees needs a CYLINDER or a SPHERE as its canvas.  And real lenses bend
+ * straight lines, which no homography follows.  These calls write the source field of a frame set from a CAMERA per frame -- a rotation,
+ * focal lengths, a principal point and Brown-Conrady lens terms -- onto a plane, a cylinder or a sphere, and send point lists through the
+ * same map in both directions.  Not part of the reference.  A field is what every remap, the pyramids, the mosaics, the multi-band and the
+ * robust blend read; none of these calls needs an image, a mesh or a frame set.
+ * All arithmetic is f64, IEEE division and square root, contraction off, in the operation order written here; sin, cos, atan2 are the
+ * platform's, good to a few ulp, so values are pinned by tolerance.
+ * RECORD of a frame: HG_CAMERA_RECORD_DOUBLES = 32 doubles.  [0..8] R, row-major, camera <- world; [9] fx [10] fy [11] cx [12] cy; [13] k1
+ * [14] k2 [15] p1 [16] p2 [17] k3 (Brown-Conrady, OpenCV's meaning); [18] r2_max; [19] a_c, the azimuth atan2(w.x, w.z) of the optical axis
+ * w = R^T (0, 0, 1); the other slots are 0.  World axes: x to the right, y down, z forward at azimuth 0.
+ * SURFACE is HG_SURFACE_PLANE, HG_SURFACE_CYLINDER or HG_SURFACE_SPHERE.  The canvas parameters scale, u0, v0 are per call: pixels per radian
+ * (for the plane: the canvas focal length) and the canvas position of azimuth 0, elevation 0.
+ * CANVAS -> SOURCE at the canvas position (U, V): a = (U - u0) / scale, b = (V - v0) / scale;
+ *   PLANE ray = (a, b, 1); CYLINDER ray = (sin a, b, cos a); SPHERE ray = (sin a cos b, sin b, cos a cos b);
+ *   c = R ray, each component as ((r0 x + r1 y) + r2 z); xn = c.x / c.z, yn = c.y / c.z; r2 = xn xn + yn yn;
+ *   rad = 1 + r2 (k1 + r2 (k2 + r2 k3));
+ *   xd = xn rad + (((2 p1) xn) yn + p2 (r2 + (2 xn) xn));  yd = yn rad + (p1 (r2 + (2 yn) yn) + ((2 p2) xn) yn);
+ *   sx = fx xd + cx, sy = fy yd + cy.
+ * A pixel is covered iff c.z > 0, r2 <= r2_max, 0 <= sx < W and 0 <= sy < H (NaN fails), and its value is stored by the rules of the other
+ * field calls: HG_FIELD_INDEX and HG_FIELD_COORDS mean exactly what they mean above, -1 and the NaN pattern included.  r2_max exists because
+ * the radial polynomial folds back at large r: without it, rays far outside the picture land inside it.
+ * SOURCE -> CANVAS at the source position (x, y): xd = (x - cx) / fx, yd = (y - cy) / fy; undistortion by the fixed-point rule, starting
+ * from (xn, yn) = (xd, yd), exactly HG_CAMERA_UNDISTORT_ITERS = 20 rounds of
+ *   r2, rad and the two tangential sums tx, ty (the bracketed terms above) at (xn, yn); xn <- (xd - tx) / rad, yn <- (yd - ty) / rad;
+ * then (xn, yn) goes through the distortion once more and the point is valid iff it lands within 1e-9 of (xd, yd) in both parts (<=) and
+ * r2 <= r2_max.  w = R^T (xn, yn, 1), each component as ((r0 xn + r3 yn) + r6).
+ *   PLANE: valid iff w.z > 0; a = w.x / w.z, b = w.y / w.z.
+ *   CYLINDER: a = atan2(w.x, w.z), b = w.y / sqrt(w.x w.x + w.z w.z).  SPHERE: a alike, b = atan2(w.y, sqrt(w.x w.x + w.z w.z)).
+ *   On the two curved surfaces a is unwrapped about the frame's own axis: a = a_c + remainder(a - a_c, 2 pi), IEEE remainder, 2 pi =
+ *   6.283185307179586: a frame that straddles the +-pi seam keeps a contiguous window.
+ *   U = u0 + scale a, V = v0 + scale b.
+ * Canvas positions beyond +-pi scale are legal everywhere, because sin and cos are periodic.
+ * HOST CALLS (no device, no context; errors in hg_last_error(NULL)).
+ *   hg_camera_pack_record fills a record, a_c included.  dist is {k1, k2, p1, p2, k3} or NULL.  Without distortion r2_max = +Infinity; with
+ *     it r2_max = 1.05 x the largest undistorted r2 over the four corners and the four edge midpoints of [0, W] x [0, H], and the call
+ *     returns HG_ERR_INVALID when one of those eight does not pass the validity rule above (taken with r2_max = +Infinity): the distortion
+ *     is too strong for this picture.  It refuses NULL, W or H below 1, anything not finite, fx or fy <= 0 and an R with |R^T R - I| > 1e-6
+ *     in any entry.
+ *   hg_camera_limits returns the window {x_off, y_off, w, h} (the members of an hg_geom) that holds the frame: hg_transform_limits'
+ *     counterpart.  Every border position of the source -- steps of one pixel along the four edges of [0, W] x [0, H] -- goes through
+ *     source -> canvas in double; positions that are not valid or not finite are left out; the window reaches from floor(min) - 1 to
+ *     ceil(max) + 1 on both axes, ends included.  On the sphere a pole direction (0, +-1, 0) that projects inside the picture (the coverage
+ *     rule above) makes the window span a_c +- pi horizontally and reach the pole's row, v0 +- scale pi / 2; on the cylinder, where a pole
+ *     lies at infinity, such a picture is refused.  HG_ERR_INVALID also when no border position is valid, for a record with a NaN and for a
+ *     window hg_geom cannot hold.
+ *   hg_camera_focals_from_matrix: the closed form of Szeliski & Shum for a homography H = K_to R K_from^-1 (row-major h0..h8, x_to ~ H
+ *     x_from) between pictures whose coordinates are relative to their principal points, K = diag(f, f, 1).  K_to^-1 H K_from is a multiple
+ *     of a rotation: its columns 0 and 1 are orthogonal and of equal length, which gives f_to^2 = -(h0 h1 + h3 h4) / (h6 h7) and
+ *     f_to^2 = (h0^2 + h3^2 - h1^2 - h4^2) / ((h7 - h6)(h7 + h6)); its rows 0 and 1 alike, f_from^2 = -(h2 h5) / (h0 h3 + h1 h4) and
+ *     f_from^2 = (h5^2 - h2^2) / (h0^2 + h1^2 - h3^2 - h4^2).  Each focal length takes the candidate with the larger denominator magnitude
+ *     and is ok (1) iff that value is finite and > 0, else not ok (0) and 0: a rotation about the optical axis says nothing about either.
+ *   hg_camera_rotation_from_matrix: K = {fx, fy, cx, cy}; M = K_to^-1 H K_from divided by cbrt(det M), HG_ERR_INVALID when det <= 0 or not
+ *     finite; R9 = the nearest rotation by the polar iteration R <- (R + R^-T) / 2, 30 rounds in a fixed order.  R takes directions of
+ *     the FROM camera to directions of the TO camera: with the TO camera's record rotation R_to, the FROM camera's is R^T R_to.
+ *   Together with the matrices of hg_bundle_adjust_frames_device these take a caller from homographies to cameras.
+ * hg_field_camera_frames_device writes the source field of n_frames cameras (d_records: n_frames records on the device, 8-byte aligned):
+ * pixel (i, j) of frame f is the canvas position (i + x_off, j + y_off).  field_offsets, packing, alignment, "bytes between frames are never
+ * written", the settling of queued runs and the context rules are those of hg_field_tps_frames_device.  A record with a NaN in any slot
+ * gives a frame that is all -1 resp. all NaN; other frames are not affected.
+ * hg_points_camera_to_source_frames_device sends point lists through canvas -> source, in the layout of the other point-list calls (n_sets
+ * lists of n_pts (x, y) float32, frame f reads list f % n_sets, d_out receives n_frames x n_pts pairs): ABSOLUTE canvas positions, no test
+ * against W or H, but c.z > 0 and r2 <= r2_max are tested.  An invalid point, a position that is not finite, a frame whose record holds a NaN
+ * and a result with a NaN part hold 0x7fc00000 in both words; 1e30 is a legal input.  At an integer position the result equals the
+ * HG_FIELD_COORDS value of that pixel, bit for bit, wherever the pixel is covered.  hg_points_camera_to_canvas_frames_device: the same
+ * arguments, source -> canvas, with that direction's validity rule.
+ * LIMITS (HG_ERR_INVALID), the shape before the context, in this order: an unknown surface or format; scale not finite or <= 0; u0 or v0 not
+ * finite; W or H below 1; n_frames outside 0..4096; n_pts outside 0..2^24; set counts below 1; NULL geoms and what hg_geom refuses; for
+ * HG_FIELD_INDEX a source of 2^31 pixels or more; a field offset that is no multiple of the pixel size; a widest and a tallest window that
+ * together span 2^31 tiles of 256 x 32 pixels or more; then NULL or misaligned pointers where there is work, and a NULL ctx.  n_frames == 0
+ * (and n_pts == 0, and a set of empty windows) is HG_OK and nothing is written.
+ * COST.  a depends on the column only and b on the row only: a workgroup takes one frame, 256 columns and a band of 32 rows, evaluates the
+ * 256 column terms and the 32 row terms once, and the pixel loop is two table reads, the 3 x 3 product, two divisions and the polynomial:
+ * 576 sin / cos calls per 8192 pixels on the curved surfaces, none at all on the plane.  MEASURED (MI355X, whole call, medians of 9;
+ * EXPERIMENTS.md, "Camera"; tools/bench_camera.py): 64 windows of 3840 x 2160, HG_FIELD_COORDS: plane 1.38 ms, cylinder 1.43 ms, sphere
+ * 1.53 ms (1.105 x the plane), the same with lens terms (1.37 / 1.41 / 1.53 ms); the projective field of
+ * hg_field_inverse_geometric_frames_device over windows of that size 0.87 ms; the byte floor of 8 bytes per pixel at 8 TB/s 0.53 ms.
+ * The call is bound by f64 issue (the 3 x 3 product, two divisions, the polynomial), not by memory.
+ * OUT OF SCOPE, each its own addition: a rotation / focal-length bundle adjustment; fisheye lens models (equidistant, stereographic);
+ * estimating distortion coefficients; exposing the canvas as anything but a field. */
+enum { HG_CAMERA_RECORD_DOUBLES = 32, HG_CAMERA_UNDISTORT_ITERS = 20 };
+enum { HG_SURFACE_PLANE = 0, HG_SURFACE_CYLINDER = 1, HG_SURFACE_SPHERE = 2 };
+/* host only */
+int hg_camera_pack_record(const double *R, double fx, double fy, double cx, double cy, const double *dist, int W, int H, double *record);
+int hg_camera_limits(const double *record, int W, int H, int surface, double scale, double u0, double v0, int32_t *out);
+int hg_camera_focals_from_matrix(const double *H9, double *f_from, double *f_to, int *ok_from, int *ok_to);
+int hg_camera_rotation_from_matrix(const double *H9, const double *K_from, const double *K_to, double *R9);
+int hg_field_camera_frames_device(hg_ctx *ctx, const double *d_records, const hg_geom *geoms, int n_frames, int W, int H, int surface,
+                                  double scale, double u0, double v0, int format, const size_t *field_offsets, void *d_field);
+int hg_points_camera_to_source_frames_device(hg_ctx *ctx, const double *d_records, int n_frames, int surface, double scale, double u0,
+                                             double v0, const void *d_points, int n_pts, int n_sets, void *d_out);
+int hg_points_camera_to_canvas_frames_device(hg_ctx *ctx, const double *d_records, int n_frames, int surface, double scale, double u0,
+                                             double v0, const void *d_points, int n_pts, int n_sets, void *d_out);
 
 /* ------------------------------------------------------------------------------------------------ dense optical flow
  * Every registration above is parametric: six or eight numbers per frame, or landmarks somebody supplies.  Parallax, a rolling shutter and
