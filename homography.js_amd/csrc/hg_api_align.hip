@@ -42,7 +42,6 @@ extern "C" int hg_align_refine_frames_device(hg_ctx *c, int kind, const void *d_
     if (from_stride_bytes < from_bytes || to_stride_bytes < to_bytes) return fail(c, HG_ERR_INVALID, "align: a plane stride must be >= W * H * channels");
     HG_TRY(bind(c));
     if (n_frames == 0) return HG_OK;
-    auto misaligned = [](const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
     if (!d_from || !d_to || !d_mats_in || !d_mats_out || !d_info)
         return fail(c, HG_ERR_INVALID, "hg_align_refine_frames_device: d_from / d_to / d_mats_in / d_mats_out / d_info is NULL");
     if (misaligned(d_mats_in, 8) || misaligned(d_mats_out, 8) || misaligned(d_sums, 8))

@@ -101,7 +101,6 @@ extern "C" int hg_bundle_adjust_frames_device(hg_ctx *c, int kind, int W, int H,
     const int n_free = lists.n_free, N = P * n_free;
     if (N > kBundleMaxUnknowns) return fail(c, HG_ERR_INVALID, "bundle: more than 2048 unknowns");
     if (scratch_bytes < plan.total) return fail(c, HG_ERR_INVALID, "bundle: scratch_bytes is below hg_bundle_layout's");
-    auto misaligned = [](const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
     if (!d_mats_in || !d_mats_out || !d_info || !d_scratch || (n_work > 0 && !d_matches))
         return fail(c, HG_ERR_INVALID, "hg_bundle_adjust_frames_device: d_matches / d_mats_in / d_mats_out / d_info / d_scratch is NULL");
     if (misaligned(d_matches, 16) || misaligned(d_scratch, 16)) return fail(c, HG_ERR_INVALID, "hg_bundle_adjust_frames_device: d_matches / d_scratch must be aligned to 16 bytes");
@@ -111,11 +110,7 @@ extern "C" int hg_bundle_adjust_frames_device(hg_ctx *c, int kind, int W, int H,
     HG_TRY(hg_sync(c));                                      // queued runs: settled first, as the fit does
     uint8_t *S = static_cast<uint8_t *>(d_scratch);
     int32_t *d_ints = reinterpret_cast<int32_t *>(S + plan.ints);
-    StageSlot *gs = nullptr;
-    HG_TRY(c->bundle_stage.acquire(c, ints.size() * 4, "bundle lists staging", &gs));
-    memcpy(gs->h, ints.data(), ints.size() * 4);
-    HG_TRY(upload_staged(c, d_ints, gs->h, ints.size() * 4));
-    HG_TRY(c->bundle_stage.commit(c, gs));
+    HG_TRY(upload_copied(c, c->bundle_stage, "bundle lists staging", d_ints, ints.data(), ints.size() * 4));
     hg::BundleArgs a{};
     a.kind = kind; a.W = W; a.H = H; a.n_frames = F; a.n_pairs = n_pairs; a.n_points = n_points; a.n_work = (int)n_work; a.n_free = n_free; a.N = N;
     a.n_iter = N == 0 ? 0 : n_iter;

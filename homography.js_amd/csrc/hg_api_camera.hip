@@ -10,8 +10,6 @@
 
 constexpr int kCamMaxFrames = 4096;
 
-static bool cam_misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 // ------------------------------------------------------------------------------------------------ host only
 extern "C" int hg_camera_pack_record(const double *R, double fx, double fy, double cx, double cy, const double *dist, int W, int H, double *record)
 {
@@ -174,7 +172,7 @@ extern "C" int hg_field_camera_frames_device(hg_ctx *c, const double *d_records,
                                              double scale, double u0, double v0, int fmt, const size_t *field_offsets, void *d_field)
 {
     HG_TRY(check_cam_surface(c, surface));
-    if (fmt != HG_FIELD_INDEX && fmt != HG_FIELD_COORDS) return fail(c, HG_ERR_INVALID, "unknown field format (HG_FIELD_INDEX or HG_FIELD_COORDS)");
+    HG_TRY(check_field_fmt(c, fmt));
     HG_TRY(check_cam_canvas(c, scale, u0, v0));
     if (W < 1 || H < 1) return fail(c, HG_ERR_INVALID, "hg_field_camera_frames_device: W and H must be >= 1");
     HG_TRY(check_cam_frames(c, n_frames));
@@ -182,37 +180,21 @@ extern "C" int hg_field_camera_frames_device(hg_ctx *c, const double *d_records,
     if (n_frames == 0) return HG_OK;
     std::vector<FrameDesc> fds;
     HG_TRY(fill_frames(c, fds, geoms, nullptr, n_frames));   // (the window limits of every frame)
-    if (fmt == HG_FIELD_INDEX && (int64_t)W * H >= ((int64_t)1 << 31))
-        return fail(c, HG_ERR_INVALID, "HG_FIELD_INDEX: the source has 2^31 pixels or more (an int32 cannot index it)");
-    const size_t px = fmt == HG_FIELD_INDEX ? 4 : 8;
-    size_t off = 0, extent = 0;
-    std::vector<CamFrame> recs((size_t)n_frames);
-    int mw = 0, mh = 0;
-    for (int f = 0; f < n_frames; f++) {
-        const hg_geom &g = geoms[f];
-        CamFrame &r = recs[(size_t)f];
-        r = CamFrame{g.x_off, g.y_off, g.obj_w, g.obj_h, field_offsets ? field_offsets[f] : off, 0};
-        if (r.out_off & (px - 1)) return fail(c, HG_ERR_INVALID, "field offsets must be multiples of the field's pixel size (4 or 8 bytes)");
-        const size_t n_px = frame_px(g.obj_w, g.obj_h);
-        off += pad256(n_px * px);
-        if (n_px) { extent = std::max(extent, (size_t)r.out_off + n_px * px); mw = std::max(mw, g.obj_w); mh = std::max(mh, g.obj_h); }
-    }
-    if (extent == 0) return HG_OK;                           // (every frame is empty)
+    HG_TRY(check_field_fmt(c, fmt, W, H));
+    FieldTable<CamFrame> t;
+    HG_TRY(field_table(c, geoms, (size_t)n_frames, fmt, field_offsets, &t));
+    if (t.extent == 0) return HG_OK;                         // (every frame is empty)
+    const int mw = t.max_w, mh = t.max_h;
     if ((int64_t)cam_pieces(mw) * cam_bands(mh) >= ((int64_t)1 << 31))
         return fail(c, HG_ERR_INVALID, "hg_field_camera_frames_device: the widest and the tallest window together span 2^31 tiles or more");
     if (!d_records || !d_field) return fail(c, HG_ERR_INVALID, "hg_field_camera_frames_device: d_records / d_field is NULL");
-    if (cam_misaligned(d_records, 8) || cam_misaligned(d_field, px))
+    if (misaligned(d_records, 8) || misaligned(d_field, field_px_bytes(fmt)))
         return fail(c, HG_ERR_INVALID, "hg_field_camera_frames_device: d_records must be aligned to 8 bytes, d_field to its pixel size");
     HG_TRY(bind(c));
-    if (!c->pw_pending_out.empty() || !c->fwd_pending.empty()) HG_TRY(settle_output_conflicts(c, d_field, extent, 0));
+    HG_TRY(settle_pending_on(c, d_field, t.extent));
     static_assert(sizeof(CamFrame) == sizeof(FrameDesc), "the field calls' frame table carries either record");
     HG_TRY(ensure(c, c->d_field_frames, (size_t)n_frames));
-    StageSlot *gs = nullptr;
-    const size_t bytes = sizeof(CamFrame) * (size_t)n_frames;
-    HG_TRY(c->field_stage.acquire(c, bytes, "field frame staging", &gs));
-    std::memcpy(gs->h, recs.data(), bytes);
-    HG_TRY(upload_staged(c, c->d_field_frames, gs->h, bytes));
-    HG_TRY(c->field_stage.commit(c, gs));
+    HG_TRY(upload_frame_table(c, c->d_field_frames, t.recs.data(), sizeof(CamFrame) * (size_t)n_frames));
     CamFieldArgs a{d_records, reinterpret_cast<const CamFrame *>(c->d_field_frames.p), n_frames, mw, mh, cam_pieces(mw), W, H, scale, u0, v0,
                    static_cast<uint8_t *>(d_field)};
     HG_TRY(time_begin(c));
@@ -232,10 +214,10 @@ static int camera_points(hg_ctx *c, const char *who, bool to_source, const doubl
     if (n_sets < 1) return fail(c, HG_ERR_INVALID, std::string(who) + ": n_sets must be >= 1");
     if (n_frames == 0 || n_pts == 0) return HG_OK;
     if (!d_records || !d_points || !d_out) return fail(c, HG_ERR_INVALID, std::string(who) + ": d_records / d_points / d_out is NULL");
-    if (cam_misaligned(d_records, 8) || cam_misaligned(d_points, 8) || cam_misaligned(d_out, 8))
+    if (misaligned(d_records, 8) || misaligned(d_points, 8) || misaligned(d_out, 8))
         return fail(c, HG_ERR_INVALID, std::string(who) + ": d_records / d_points / d_out must be aligned to 8 bytes");
     HG_TRY(bind(c));
-    if (!c->pw_pending_out.empty() || !c->fwd_pending.empty()) HG_TRY(settle_output_conflicts(c, d_out, (size_t)n_frames * (size_t)n_pts * 8, 0));
+    HG_TRY(settle_pending_on(c, d_out, (size_t)n_frames * (size_t)n_pts * 8));
     CamPointArgs a{d_records, n_frames, surface, scale, u0, v0, static_cast<const float *>(d_points), n_pts, n_sets, static_cast<float *>(d_out)};
     launch_camera_points(a, to_source, c->stream);
     HIP_TRY(c, hipGetLastError());

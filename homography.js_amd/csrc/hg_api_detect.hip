@@ -61,7 +61,6 @@ extern "C" int hg_detect_describe_frames_device(hg_ctx *c, const void *d_planes,
     if (plane_stride_bytes < (size_t)W * (size_t)H * (size_t)channels) return fail(c, HG_ERR_INVALID, "detect: plane_stride_bytes must be >= W * H * channels");
     HG_TRY(bind(c));
     if (n_planes == 0) return HG_OK;
-    auto misaligned = [](const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
     if (!d_planes || !d_counts) return fail(c, HG_ERR_INVALID, "hg_detect_describe_frames_device: d_planes / d_counts is NULL");
     if (misaligned(d_counts, 4)) return fail(c, HG_ERR_INVALID, "hg_detect_describe_frames_device: d_counts must be aligned to 4 bytes");
     if (misaligned(d_points, 8) || misaligned(d_info, 8)) return fail(c, HG_ERR_INVALID, "hg_detect_describe_frames_device: d_points / d_info must be aligned to 8 bytes");

@@ -40,7 +40,6 @@ extern "C" int hg_fit_matches_frames_device(hg_ctx *c, int kind, const void *d_m
     if (!(threshold >= 0.0) || !(threshold < INFINITY)) return fail(c, HG_ERR_INVALID, "hg_fit_matches_frames_device: threshold must be finite and >= 0");
     if (n_hyp == 0 && !refit) return fail(c, HG_ERR_INVALID, "hg_fit_matches_frames_device: n_hyp == 0 needs refit (the least-squares fit)");
     if (n_frames == 0) return HG_OK;
-    auto misaligned = [](const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
     if (!d_mats || !d_counts || (n_points > 0 && !d_matches)) return fail(c, HG_ERR_INVALID, "hg_fit_matches_frames_device: d_matches / d_mats / d_counts is NULL");
     if (misaligned(d_matches, 16)) return fail(c, HG_ERR_INVALID, "hg_fit_matches_frames_device: d_matches must be aligned to 16 bytes ((x, y, u, v) float32)");
     if (misaligned(d_mats, 8) || misaligned(d_min_mats, 8)) return fail(c, HG_ERR_INVALID, "hg_fit_matches_frames_device: d_mats / d_min_mats must be aligned to 8 bytes");
@@ -52,13 +51,11 @@ extern "C" int hg_fit_matches_frames_device(hg_ctx *c, int kind, const void *d_m
     HG_TRY(ensure(c, c->d_fit_mats, std::max<size_t>(F * H * 8, 8)));
     HG_TRY(ensure(c, c->d_fit_valid, std::max<size_t>(F * H, 1)));
     HG_TRY(ensure(c, c->d_fit_frames, F + cnt_words));
-    StageSlot *gs = nullptr;
-    HG_TRY(c->fit_stage.acquire(c, cnt_words * 8, "fit counts staging", &gs));
-    int32_t *hc = reinterpret_cast<int32_t *>(gs->h);
-    for (size_t f = 0; f < 2 * cnt_words; f++) hc[f] = f < F ? (counts ? counts[f] : n_points) : 0;
     int32_t *d_cnt = reinterpret_cast<int32_t *>(c->d_fit_frames.p + F);
-    HG_TRY(upload_staged(c, d_cnt, gs->h, cnt_words * 8));
-    HG_TRY(c->fit_stage.commit(c, gs));
+    HG_TRY(upload_filled(c, c->fit_stage, "fit counts staging", d_cnt, cnt_words * 8, [&](uint8_t *h) {
+        int32_t *hc = reinterpret_cast<int32_t *>(h);
+        for (size_t f = 0; f < 2 * cnt_words; f++) hc[f] = f < F ? (counts ? counts[f] : n_points) : 0;
+    }));
     HIP_TRY(c, hipMemsetAsync(c->d_fit_frames.p, 0, F * 8, c->stream));
     FitArgs a{kind, d_matches, n_points, d_cnt, n_frames, threshold, n_hyp, seed, d_samples, refit ? 1 : 0, c->d_fit_mats, c->d_fit_valid,
               reinterpret_cast<unsigned long long *>(c->d_fit_frames.p), d_mats, d_min_mats, d_counts, d_best, d_mask};

@@ -55,8 +55,6 @@ void plan_flow(int W, int H, int channels, int n_frames, int n_to_sets, int leve
     p->total = off;
 }
 
-bool flow_misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 } // namespace
 
 extern "C" int hg_flow_layout(int W, int H, int channels, int n_frames, int n_to_sets, int levels, size_t *scratch_bytes)
@@ -95,7 +93,7 @@ extern "C" int hg_flow_dense_frames_device(hg_ctx *c, const void *d_from, int n_
         off += pad256(n_px * 8);
     }
     if (!d_from || !d_to || !d_field || !d_scratch) return fail(c, HG_ERR_INVALID, "hg_flow_dense_frames_device: d_from / d_to / d_field / d_scratch is NULL");
-    if (flow_misaligned(d_field, 8) || flow_misaligned(d_flow, 8) || flow_misaligned(d_scratch, 16))
+    if (misaligned(d_field, 8) || misaligned(d_flow, 8) || misaligned(d_scratch, 16))
         return fail(c, HG_ERR_INVALID, "hg_flow_dense_frames_device: d_field / d_flow must be aligned to 8 bytes, d_scratch to 16 bytes");
     HG_TRY(hg_sync(c));                                      // queued runs: settled first, as the aligner does
     FlowPlan p;
@@ -104,11 +102,7 @@ extern "C" int hg_flow_dense_frames_device(hg_ctx *c, const void *d_from, int n_
     // the table of field offsets: through the field calls' staging, stream-ordered
     static_assert(sizeof(FlowOff) * 2 == sizeof(FrameDesc), "the field calls' frame table carries either record");
     HG_TRY(ensure(c, c->d_field_frames, (F + 1) / 2));
-    StageSlot *gs = nullptr;
-    HG_TRY(c->field_stage.acquire(c, sizeof(FlowOff) * F, "field frame staging", &gs));
-    std::memcpy(gs->h, offs.data(), sizeof(FlowOff) * F);
-    HG_TRY(upload_staged(c, c->d_field_frames, gs->h, sizeof(FlowOff) * F));
-    HG_TRY(c->field_stage.commit(c, gs));
+    HG_TRY(upload_frame_table(c, c->d_field_frames, offs.data(), sizeof(FlowOff) * F));
     // level 0 of both sides: the caller's planes, or their luma copies
     const uint8_t *from = static_cast<const uint8_t *>(d_from), *to = static_cast<const uint8_t *>(d_to);
     size_t from_stride = from_stride_bytes, to_stride = to_stride_bytes;

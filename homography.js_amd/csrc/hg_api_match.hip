@@ -35,7 +35,6 @@ extern "C" int hg_match_descriptors_frames_device(hg_ctx *c, int desc_kind, int 
     HG_TRY(check_match_shape(c, desc_kind, desc_bytes, stride, n_query, counts_q, n_frames, n_train, counts_t, n_train_sets, ratio));      // (needs no device)
     HG_TRY(bind(c));
     if (n_frames == 0) return HG_OK;
-    auto misaligned = [](const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
     const bool work = n_query > 0 && n_train > 0;                // (without rows on one side no descriptor is read)
     if (!d_counts || (work && (!d_query || !d_train))) return fail(c, HG_ERR_INVALID, "hg_match_descriptors_frames_device: d_query / d_train / d_counts is NULL");
     if (misaligned(d_query, 16) || misaligned(d_train, 16)) return fail(c, HG_ERR_INVALID, "hg_match_descriptors_frames_device: d_query / d_train must be aligned to 16 bytes");
@@ -58,14 +57,12 @@ extern "C" int hg_match_descriptors_frames_device(hg_ctx *c, int desc_kind, int 
         HG_TRY(ensure(c, c->d_match_keys, std::max<size_t>(F * (size_t)n_train, 1)));
         if (work) HIP_TRY(c, hipMemsetAsync(c->d_match_keys.p, 0xff, F * (size_t)n_train * 8, c->stream));
     }
-    StageSlot *gs = nullptr;
-    HG_TRY(c->match_stage.acquire(c, cnt_words * 8, "match counts staging", &gs));
-    int32_t *hc = reinterpret_cast<int32_t *>(gs->h);
-    for (size_t f = 0; f < F; f++) hc[f] = counts_q ? counts_q[f] : n_query;
-    for (size_t s = 0; s < S; s++) hc[F + s] = counts_t ? counts_t[s] : n_train;
-    for (size_t k = F + S; k < 2 * cnt_words; k++) hc[k] = 0;
-    HG_TRY(upload_staged(c, c->d_match_counts.p, gs->h, cnt_words * 8));
-    HG_TRY(c->match_stage.commit(c, gs));
+    HG_TRY(upload_filled(c, c->match_stage, "match counts staging", c->d_match_counts.p, cnt_words * 8, [&](uint8_t *h) {
+        int32_t *hc = reinterpret_cast<int32_t *>(h);
+        for (size_t f = 0; f < F; f++) hc[f] = counts_q ? counts_q[f] : n_query;
+        for (size_t s = 0; s < S; s++) hc[F + s] = counts_t ? counts_t[s] : n_train;
+        for (size_t k = F + S; k < 2 * cnt_words; k++) hc[k] = 0;
+    }));
     hg::MatchArgs a{bits ? 0 : 1, desc_bytes, stride, d_query, n_query, d_train, n_train, n_frames, n_train_sets, c->d_match_counts.p, c->d_match_counts.p + F,
                     ratio != 0.0 ? 1 : 0, bits ? ratio : ratio * ratio, max_distance, cross, d_query_pts, d_train_pts, c->d_match_fwd.p,
                     cross == 1 ? c->d_match_rev.p : nullptr, cross == 2 ? reinterpret_cast<unsigned long long *>(c->d_match_keys.p) : nullptr, d_counts, d_matches, d_pairs, d_nn};

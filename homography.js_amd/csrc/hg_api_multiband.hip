@@ -8,7 +8,6 @@
 
 namespace {
 
-bool misaligned(const void *p, size_t align) { return (reinterpret_cast<uintptr_t>(p) & (align - 1)) != 0; }      // (align: a power of two)
 int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 int64_t ceil_div(int64_t a, int64_t b) { return -floor_div(-a, b); }
 
@@ -89,12 +88,6 @@ int mb_plan(hg_ctx *c, const std::string &fn, const hg_geom *geoms, int n_frames
     return HG_OK;
 }
 
-int settle_pending_on(hg_ctx *c, const void *ptr, size_t bytes)
-{
-    if (c->pw_pending_out.empty() && c->fwd_pending.empty()) return HG_OK;
-    return settle_output_conflicts(c, ptr, bytes, 0);
-}
-
 } // namespace
 
 extern "C" int hg_mosaic_multiband_layout(const hg_geom *geoms, int n_frames, hg_geom canvas, int channels, int n_bands, size_t *work_bytes)
@@ -149,12 +142,7 @@ extern "C" int hg_mosaic_multiband_device(hg_ctx *c, const hg_geom *geoms, int n
     const MbFrame *d_recs = nullptr;
     if (q_bytes + f_bytes) {
         HG_TRY(ensure(c, c->d_mb_table, (q_bytes + f_bytes) / 8));
-        StageSlot *gs = nullptr;
-        HG_TRY(c->field_stage.acquire(c, q_bytes + f_bytes, "field frame staging", &gs));
-        std::memcpy(gs->h, plan.quads.data(), q_bytes);
-        if (f_bytes) std::memcpy(gs->h + q_bytes, plan.frames.data(), f_bytes);
-        HG_TRY(upload_staged(c, c->d_mb_table.p, gs->h, q_bytes + f_bytes));
-        HG_TRY(c->field_stage.commit(c, gs));
+        HG_TRY(upload_frame_table(c, c->d_mb_table.p, plan.quads.data(), q_bytes, plan.frames.data(), f_bytes));
         d_quads = reinterpret_cast<const MosaicFrame4 *>(c->d_mb_table.p);
         d_recs = reinterpret_cast<const MbFrame *>(reinterpret_cast<const uint8_t *>(c->d_mb_table.p) + q_bytes);
     }

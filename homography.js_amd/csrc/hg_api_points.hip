@@ -14,17 +14,10 @@ static int check_points_args(hg_ctx *c, const void *d_points, int n_points, int 
     if (n_sets < 1) return fail(c, HG_ERR_INVALID, "n_sets must be >= 1");
     if (n_points == 0) return HG_OK;
     if (!d_points || !d_out) return fail(c, HG_ERR_INVALID, "d_points / d_out is NULL");
-    if ((reinterpret_cast<uintptr_t>(d_points) & 7) || (reinterpret_cast<uintptr_t>(d_out) & 7))
+    if (misaligned(d_points, 8) || misaligned(d_out, 8))
         return fail(c, HG_ERR_INVALID, "d_points / d_out must be aligned to 8 bytes (interleaved x,y float32)");
     *work = true;
     return HG_OK;
-}
-
-// A queued run's deferred redo must not land on the results later: runs whose output overlaps them are settled first (as the fields do).
-static int settle_points_conflicts(hg_ctx *c, const void *d_out, size_t n_frames, int n_points)
-{
-    if (c->pw_pending_out.empty() && c->fwd_pending.empty()) return HG_OK;
-    return settle_output_conflicts(c, d_out, n_frames * (size_t)n_points * 8, 0);
 }
 
 // ------------------------------------------------------------------------------------------------ to source
@@ -37,7 +30,7 @@ extern "C" int hg_points_to_source_geometric_frames_device(hg_ctx *c, const void
     if (!c->d_img || c->W <= 0 || c->H <= 0) return fail(c, HG_ERR_STATE, "no source image: the coverage test needs its size (hg_set_image)");
     if (c->geo_frames.empty()) return fail(c, HG_ERR_STATE, "no frames: call hg_geometric_set_frames first");
     const size_t F = c->geo_frames.size();
-    HG_TRY(settle_points_conflicts(c, d_out, F, n_points));
+    HG_TRY(settle_pending_on(c, d_out, F * (size_t)n_points * 8));      // (as the fields do)
     // frames given as point sets: the matrices are solved on the device, as at the head of every warp of the set (:994)
     if (c->geo_from_points)
         launch_solve_frames(c->geo_kind, c->d_geo_pts, c->d_geo_pts + F * 8, c->d_geo_frames, c->d_mats, c->d_geo_plain, (int)F, c->stream);

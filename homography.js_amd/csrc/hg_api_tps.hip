@@ -9,7 +9,6 @@
 
 constexpr int kTpsMaxFrames = 4096;
 
-static bool tps_misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 static bool tps_step_ok(int step) { return step == 1 || step == 2 || step == 4 || step == 8 || step == 16 || step == 32; }
 
 static int check_tps_shape(hg_ctx *c, int n_points, int n_frames)
@@ -38,9 +37,9 @@ extern "C" int hg_tps_solve_frames_device(hg_ctx *c, const void *d_from, int n_f
     const bool scratch = !tps_in_lds(n_points);
     if (!d_from || !d_to || !d_records || !d_status || (scratch && !d_scratch))
         return fail(c, HG_ERR_INVALID, "hg_tps_solve_frames_device: d_from / d_to / d_records / d_status / d_scratch is NULL");
-    if (tps_misaligned(d_from, 8) || tps_misaligned(d_to, 8) || tps_misaligned(d_records, 8) || tps_misaligned(d_scratch, 8))
+    if (misaligned(d_from, 8) || misaligned(d_to, 8) || misaligned(d_records, 8) || misaligned(d_scratch, 8))
         return fail(c, HG_ERR_INVALID, "hg_tps_solve_frames_device: d_from / d_to / d_records / d_scratch must be aligned to 8 bytes");
-    if (tps_misaligned(d_status, 4)) return fail(c, HG_ERR_INVALID, "hg_tps_solve_frames_device: d_status must be aligned to 4 bytes");
+    if (misaligned(d_status, 4)) return fail(c, HG_ERR_INVALID, "hg_tps_solve_frames_device: d_status must be aligned to 4 bytes");
     HG_TRY(bind(c));
     HG_TRY(hg_sync(c));                                      // queued runs: settled first, as the fit does
     TpsSolveArgs a{static_cast<const float *>(d_from), n_from_sets, static_cast<const float *>(d_to), n_to_sets, n_points, n_frames, lambda,
@@ -84,43 +83,28 @@ extern "C" int hg_field_tps_frames_device(hg_ctx *c, const double *d_records, in
 {
     HG_TRY(check_tps_shape(c, n_points, n_frames));
     HG_TRY(check_tps_field_shape(c, geoms, n_frames, step));
-    if (fmt != HG_FIELD_INDEX && fmt != HG_FIELD_COORDS) return fail(c, HG_ERR_INVALID, "unknown field format (HG_FIELD_INDEX or HG_FIELD_COORDS)");
+    HG_TRY(check_field_fmt(c, fmt));
     if (W < 1 || H < 1) return fail(c, HG_ERR_INVALID, "hg_field_tps_frames_device: W and H must be >= 1");
-    if (fmt == HG_FIELD_INDEX && (int64_t)W * H >= ((int64_t)1 << 31))
-        return fail(c, HG_ERR_INVALID, "HG_FIELD_INDEX: the source has 2^31 pixels or more (an int32 cannot index it)");
+    HG_TRY(check_field_fmt(c, fmt, W, H));
     if (n_frames == 0) return HG_OK;
     std::vector<FrameDesc> fds;
     HG_TRY(fill_frames(c, fds, geoms, nullptr, n_frames));   // (the window limits of every frame)
-    const size_t px = fmt == HG_FIELD_INDEX ? 4 : 8;
     std::vector<size_t> node_offs;
-    size_t node_bytes = 0, off = 0, extent = 0;
+    size_t node_bytes = 0;
     HG_TRY(tps_node_layout(geoms, n_frames, step, &node_offs, &node_bytes));
-    std::vector<TpsFrame> recs((size_t)n_frames);
-    int mw = 0, mh = 0;
-    for (int f = 0; f < n_frames; f++) {
-        const hg_geom &g = geoms[f];
-        TpsFrame &r = recs[(size_t)f];
-        r = TpsFrame{g.x_off, g.y_off, g.obj_w, g.obj_h, field_offsets ? field_offsets[f] : off, node_offs[(size_t)f]};
-        if (r.out_off & (px - 1)) return fail(c, HG_ERR_INVALID, "field offsets must be multiples of the field's pixel size (4 or 8 bytes)");
-        const size_t n_px = frame_px(g.obj_w, g.obj_h);
-        off += pad256(n_px * px);
-        if (n_px) { extent = std::max(extent, (size_t)r.out_off + n_px * px); mw = std::max(mw, g.obj_w); mh = std::max(mh, g.obj_h); }
-    }
-    if (extent == 0) return HG_OK;                           // (every frame is empty)
+    FieldTable<TpsFrame> t;
+    HG_TRY(field_table(c, geoms, (size_t)n_frames, fmt, field_offsets, &t));
+    for (int f = 0; f < n_frames; f++) t.recs[(size_t)f].node_off = node_offs[(size_t)f];
+    if (t.extent == 0) return HG_OK;                         // (every frame is empty)
     if (!d_records || !d_field || (node_bytes > 0 && !d_scratch)) return fail(c, HG_ERR_INVALID, "hg_field_tps_frames_device: d_records / d_field / d_scratch is NULL");
-    if (tps_misaligned(d_records, 8) || tps_misaligned(d_field, px) || tps_misaligned(d_scratch, 16))
+    if (misaligned(d_records, 8) || misaligned(d_field, field_px_bytes(fmt)) || misaligned(d_scratch, 16))
         return fail(c, HG_ERR_INVALID, "hg_field_tps_frames_device: d_records must be aligned to 8 bytes, d_field to its pixel size, d_scratch to 16 bytes");
     HG_TRY(bind(c));
-    if (!c->pw_pending_out.empty() || !c->fwd_pending.empty()) HG_TRY(settle_output_conflicts(c, d_field, extent, 0));
+    HG_TRY(settle_pending_on(c, d_field, t.extent));
     static_assert(sizeof(TpsFrame) == sizeof(FrameDesc), "the field calls' frame table carries either record");
     HG_TRY(ensure(c, c->d_field_frames, (size_t)n_frames));
-    StageSlot *gs = nullptr;
-    const size_t bytes = sizeof(TpsFrame) * (size_t)n_frames;
-    HG_TRY(c->field_stage.acquire(c, bytes, "field frame staging", &gs));
-    std::memcpy(gs->h, recs.data(), bytes);
-    HG_TRY(upload_staged(c, c->d_field_frames, gs->h, bytes));
-    HG_TRY(c->field_stage.commit(c, gs));
-    TpsFieldArgs a{d_records, n_points, reinterpret_cast<const TpsFrame *>(c->d_field_frames.p), n_frames, mw, mh, W, H, step,
+    HG_TRY(upload_frame_table(c, c->d_field_frames, t.recs.data(), sizeof(TpsFrame) * (size_t)n_frames));
+    TpsFieldArgs a{d_records, n_points, reinterpret_cast<const TpsFrame *>(c->d_field_frames.p), n_frames, t.max_w, t.max_h, W, H, step,
                    static_cast<uint8_t *>(d_field), static_cast<uint8_t *>(d_scratch)};
     HG_TRY(time_begin(c));
     launch_tps_field(a, fmt, c->stream);
@@ -137,10 +121,10 @@ extern "C" int hg_points_tps_frames_device(hg_ctx *c, const double *d_records, i
     if (n_sets < 1) return fail(c, HG_ERR_INVALID, "hg_points_tps_frames_device: n_sets must be >= 1");
     if (n_frames == 0 || n_pts == 0) return HG_OK;
     if (!d_records || !d_points || !d_out) return fail(c, HG_ERR_INVALID, "hg_points_tps_frames_device: d_records / d_points / d_out is NULL");
-    if (tps_misaligned(d_records, 8) || tps_misaligned(d_points, 8) || tps_misaligned(d_out, 8))
+    if (misaligned(d_records, 8) || misaligned(d_points, 8) || misaligned(d_out, 8))
         return fail(c, HG_ERR_INVALID, "hg_points_tps_frames_device: d_records / d_points / d_out must be aligned to 8 bytes");
     HG_TRY(bind(c));
-    if (!c->pw_pending_out.empty() || !c->fwd_pending.empty()) HG_TRY(settle_output_conflicts(c, d_out, (size_t)n_frames * (size_t)n_pts * 8, 0));
+    HG_TRY(settle_pending_on(c, d_out, (size_t)n_frames * (size_t)n_pts * 8));
     launch_tps_points(d_records, n_points, n_frames, static_cast<const float *>(d_points), n_pts, n_sets, static_cast<float *>(d_out), c->stream);
     HIP_TRY(c, hipGetLastError());
     return HG_OK;

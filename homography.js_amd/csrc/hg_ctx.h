@@ -1,6 +1,8 @@
 // hg_ctx.h -- the context behind the C ABI of include/hgwarp.h and the helpers its translation units share
 // (hg_api.hip: library / context / buffers / host-side solves / source image; hg_api_geometric.hip; hg_api_piecewise.hip;
-// hg_api_forward.hip; hg_api_state.hip; hg_api_field.hip; hg_api_points.hip; hg_api_fit.hip; hg_api_match.hip; hg_api_detect.hip; hg_api_align.hip; hg_api_tps.hip).  Its memory is owned through hg_mem.h.  Internal: nothing here is exported.
+// hg_api_forward.hip; hg_api_state.hip; hg_api_field.hip; hg_api_remap.hip; hg_api_mosaic.hip; hg_api_points.hip; hg_api_fit.hip; hg_api_match.hip;
+// hg_api_detect.hip; hg_api_multiband.hip; hg_api_align.hip; hg_api_tps.hip; hg_api_flow.hip; hg_api_bundle.hip; hg_api_camera.hip).  Its memory is
+// owned through hg_mem.h.  Internal: nothing here is exported.
 #pragma once
 #include "../../include/hgwarp.h"
 #include "hg_kernels.h"
@@ -11,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace hg;
@@ -342,7 +345,7 @@ inline int bind(hg_ctx *c)
 int time_begin(hg_ctx *c);                                   // hg_api.hip: event pair around the dominant kernel (hg_set_timing)
 int time_end(hg_ctx *c);
 int fill_frames(hg_ctx *c, std::vector<FrameDesc> &v, const hg_geom *geoms, const size_t *offs, int n);      // hg_api.hip
-// hg_api_field.hip: the bilinear / bicubic frames remap behind its entry points; compose: the chained field of hg_field_compose_frames_device
+// hg_api_remap.hip: the bilinear / bicubic frames remap behind its entry points; compose: the chained field of hg_field_compose_frames_device
 int remap_flat_frames(hg_ctx *c, const char *who, const hg_geom *geoms, int n_frames, const void *d_coords, const size_t *field_offsets,
                       const void *d_planes, int W, int H, int n_planes, size_t plane_stride_bytes, int elem, int channels,
                       void *d_out, const size_t *out_offsets, const CubicCoef *cubic, bool compose);
@@ -363,3 +366,86 @@ int redo_forward_frame_staged(hg_ctx *c, int stage, int f, int max_src_x, int ma
 // and its forward matrices queued (k_tri_setup) -- for the warps, the fields and the point lists
 int forward_piecewise_stage(hg_ctx *c, const float *dst_points, int max_src_x, int max_src_y, const hg_geom *geoms, const size_t *offs, int n,
                             bool field, int64_t *map_w, int64_t *map_h);
+
+// ------------------------------------------------------------------------------------------------ what the entry points do alike
+// p does not lie at a multiple of a (a power of two).  NULL is aligned: whether a pointer may be NULL is the caller's own check.
+inline bool misaligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+// A queued run's deferred redo must not land later on what this call writes: queued runs whose output overlaps [ptr, ptr + bytes) are
+// settled first.
+inline int settle_pending_on(hg_ctx *c, const void *ptr, size_t bytes)
+{
+    if (c->pw_pending_out.empty() && c->fwd_pending.empty()) return HG_OK;
+    return settle_output_conflicts(c, ptr, bytes, 0);
+}
+
+// A host-built table (a multiple of 8 bytes) to d_dst through a staging ring, stream-ordered: the next slot is acquired (what: its name in
+// the out-of-memory message), fill(h) writes its `bytes`, the upload is queued, and only then is the slot committed -- the event that guards
+// its bytes is recorded behind the upload, and a call that failed anywhere has handed nothing over: the next one takes the same slot.
+template <int N, typename Slot, typename Fill>
+inline int upload_filled(hg_ctx *c, StageRing<N, Slot> &ring, const char *what, void *d_dst, size_t bytes, Fill fill)
+{
+    Slot *s = nullptr;
+    HG_TRY(ring.acquire(c, bytes, what, &s));
+    fill(s->h);
+    HG_TRY(upload_staged(c, d_dst, s->h, bytes));
+    return ring.commit(c, s);
+}
+// ... a copy of the caller's block a, or of a and b back to back, in ONE upload.
+template <int N, typename Slot>
+inline int upload_copied(hg_ctx *c, StageRing<N, Slot> &ring, const char *what, void *d_dst, const void *a, size_t a_bytes,
+                         const void *b = nullptr, size_t b_bytes = 0)
+{
+    return upload_filled(c, ring, what, d_dst, a_bytes + b_bytes, [=](uint8_t *h) {
+        std::memcpy(h, a, a_bytes);
+        if (b_bytes) std::memcpy(h + a_bytes, b, b_bytes);
+    });
+}
+// ... a frame table of the field, remap and mosaic calls, which share a ring (no GPU wait unless the upload that used the slot four calls
+// ago is still queued).
+inline int upload_frame_table(hg_ctx *c, void *d_dst, const void *a, size_t a_bytes, const void *b = nullptr, size_t b_bytes = 0)
+{
+    return upload_copied(c, c->field_stage, "field frame staging", d_dst, a, a_bytes, b, b_bytes);
+}
+
+// ------------------------------------------------------------------------------------------------ fields
+inline bool field_fmt_ok(int fmt) { return fmt == HG_FIELD_INDEX || fmt == HG_FIELD_COORDS; }
+inline size_t field_px_bytes(int fmt) { return fmt == HG_FIELD_INDEX ? 4 : 8; }
+
+// What a field call checks of its format: that it is one and, once the call knows the source's size W x H (0 x 0 before that), that the
+// index format can address it: below 2^31 pixels.
+inline int check_field_fmt(hg_ctx *c, int fmt, int W = 0, int H = 0)
+{
+    if (!field_fmt_ok(fmt)) return fail(c, HG_ERR_INVALID, "unknown field format (HG_FIELD_INDEX or HG_FIELD_COORDS)");
+    if (fmt == HG_FIELD_INDEX && (int64_t)W * H >= ((int64_t)1 << 31))
+        return fail(c, HG_ERR_INVALID, "HG_FIELD_INDEX: the source has 2^31 pixels or more (an int32 cannot index it)");
+    return HG_OK;
+}
+
+// The frame table of a field call over n windows (hg_geom or FrameDesc: x_off, y_off, obj_w, obj_h).  Rec is FrameDesc or a record of its
+// size and head (CamFrame, TpsFrame): the window, then the FIELD offset in out_off -- offs[f] as given, a multiple of the field's pixel size,
+// or packed as hg_pack_field_offsets does.  A FrameDesc source is copied whole; otherwise the last word is zero and the caller's to fill in.
+// extent: the bytes the call writes from d_field on; max_w, max_h: the widest and the tallest non-empty window.
+template <typename Rec> struct FieldTable { std::vector<Rec> recs; size_t extent = 0; int max_w = 0, max_h = 0; };
+
+template <typename Rec, typename Win>
+inline int field_table(hg_ctx *c, const Win *win, size_t n, int fmt, const size_t *offs, FieldTable<Rec> *t)
+{
+    static_assert(sizeof(Rec) == sizeof(FrameDesc), "the field calls' frame table carries either record");
+    const size_t px = field_px_bytes(fmt);
+    t->recs.resize(n);
+    t->extent = 0; t->max_w = t->max_h = 0;
+    size_t off = 0;
+    for (size_t f = 0; f < n; f++) {
+        const Win &w = win[f];
+        Rec &r = t->recs[f];
+        if constexpr (std::is_same<Rec, Win>::value) r = w;
+        else r = Rec{w.x_off, w.y_off, w.obj_w, w.obj_h, 0, 0};
+        r.out_off = offs ? offs[f] : off;
+        if (r.out_off & (px - 1)) return fail(c, HG_ERR_INVALID, "field offsets must be multiples of the field's pixel size (4 or 8 bytes)");
+        const size_t n_px = frame_px(w.obj_w, w.obj_h);
+        off += pad256(n_px * px);
+        if (n_px) { t->extent = std::max(t->extent, (size_t)r.out_off + n_px * px); t->max_w = std::max(t->max_w, w.obj_w); t->max_h = std::max(t->max_h, w.obj_h); }
+    }
+    return HG_OK;
+}

@@ -3,6 +3,8 @@
 // the HIP library's) as malloc-backed fakes that log every call in order and can be told to fail the next allocation.
 //   ensure: the growth rule, nothing at all when the buffer is large enough, stream sync -> free -> malloc when it regrows, a failed hipMalloc;
 //   StageRing<4>, StageRing<64>: when a slot waits, when it regrows, acquire without commit, where commit records;
+//   upload_filled / upload_copied (hg_ctx.h) on a StageRing<4>: acquire, fill, upload, commit in that order; what a failed allocation and a failed
+//   upload leave behind; the bytes that arrive, from one block and from two;
 //   PwSolve: the six sizes, the six pointers;  hg_ctx: deleting it behind a stream synchronisation frees everything but a borrowed image.
 // Built and run by tests/test_ctx_mem_cpu.py with -fsanitize=address,undefined (the leak check at exit covers the fakes' own blocks).
 #include "hg_ctx.h"
@@ -12,11 +14,12 @@
 thread_local std::string g_err;
 
 // ------------------------------------------------------------------------------------------------ the fake runtime
-enum Op { SYNC, MALLOC, FREE, HOST_MALLOC, HOST_FREE, EV_CREATE, EV_RECORD, EV_SYNC, EV_DESTROY };
+enum Op { SYNC, MALLOC, FREE, HOST_MALLOC, HOST_FREE, EV_CREATE, EV_RECORD, EV_SYNC, EV_DESTROY, UPLOAD, MEMCPY };
 struct Call { Op op; const void *p; size_t bytes; const void *stream; };
 static std::vector<Call> g_log;
 static std::set<const void *> g_dev, g_host, g_events;
 static bool g_fail_next = false;                    // the next hipMalloc / hipHostMalloc fails
+static bool g_fail_upload = false;                  // the next hipGetLastError / hipMemcpyAsync reports a failure
 static long g_bad = 0, g_checks = 0;
 
 #define CHECK(cond) do { g_checks++; if (!(cond)) { g_bad++; std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } } while (0)
@@ -59,7 +62,23 @@ hipError_t hipEventDestroy(hipEvent_t e)
     std::free(e);
     return hipSuccess;
 }
+hipError_t hipMemcpyAsync(void *dst, const void *src, size_t n, hipMemcpyKind kind, hipStream_t s)
+{
+    CHECK(kind == hipMemcpyHostToDevice);
+    g_log.push_back({MEMCPY, dst, n, s});
+    if (g_fail_upload) { g_fail_upload = false; return hipErrorInvalidValue; }
+    std::memcpy(dst, src, n);
+    return hipSuccess;
+}
+hipError_t hipGetLastError(void) { const bool f = g_fail_upload; g_fail_upload = false; return f ? hipErrorLaunchFailure : hipSuccess; }
 const char *hipGetErrorString(hipError_t e) { return e == hipErrorOutOfMemory ? "out of memory (fake)" : "error (fake)"; }
+}
+
+// k_upload's launch: the segments are copied at once; one log entry with the first destination and the bytes of all three
+void hg::launch_upload(const UploadSegs &sg, hipStream_t s)
+{
+    for (int k = 0; k < 3; k++) if (sg.n8[k]) std::memcpy(sg.dst[k], sg.src[k], sg.n8[k] * 8);
+    g_log.push_back({UPLOAD, sg.dst[0], (sg.n8[0] + sg.n8[1] + sg.n8[2]) * 8, s});
 }
 
 static size_t count(Op op) { size_t n = 0; for (const Call &c : g_log) n += c.op == op; return n; }
@@ -136,6 +155,95 @@ static void check_ring(hg_ctx *c)
         CHECK(ring.acquire(c, 1000, "field frame staging", &s) == HG_OK && s == &ring.slot[1 % N] && s->cap == 1250);
     }
     CHECK(g_host.empty() && g_events.empty());                  // the ring's destructor
+}
+
+// ------------------------------------------------------------------------------------------------ staged uploads
+static std::vector<uint8_t> pattern(size_t n, unsigned seed)
+{
+    std::vector<uint8_t> v(n);
+    for (size_t i = 0; i < n; i++) v[i] = (uint8_t)(seed * 37u + i * 11u + 1u);
+    return v;
+}
+static size_t find(Op op, size_t from = 0) { for (size_t i = from; i < g_log.size(); i++) if (g_log[i].op == op) return i; return g_log.size(); }
+
+static void check_staged_upload(hg_ctx *c)
+{
+    {
+        StageRing<4> ring;
+        DevBuf<uint8_t> d;
+        CHECK(ensure(c, d, 4096) == HG_OK);
+        // five uploads in a row: (create, allocate, upload, record) x 4, then ONE wait, on slot 0's event, before the fifth fill
+        g_log.clear();
+        for (unsigned i = 0; i < 4; i++) {
+            const std::vector<uint8_t> src = pattern(64, i);
+            CHECK(upload_copied(c, ring, "table staging", d.p, src.data(), src.size()) == HG_OK && ring.cur == (int)i);
+            CHECK(std::memcmp(d.p, src.data(), 64) == 0);
+        }
+        CHECK(g_log.size() == 16);
+        for (size_t i = 0; i + 3 < g_log.size() && i < 16; i += 4) {
+            const StageSlot &sl = ring.slot[i / 4];
+            CHECK(g_log[i].op == EV_CREATE && g_log[i].p == sl.done);
+            CHECK(g_log[i + 1].op == HOST_MALLOC && g_log[i + 1].bytes == 80 && g_log[i + 1].p == sl.h);
+            CHECK(g_log[i + 2].op == UPLOAD && g_log[i + 2].p == d.p && g_log[i + 2].bytes == 64 && g_log[i + 2].stream == kStream);
+            CHECK(g_log[i + 3].op == EV_RECORD && g_log[i + 3].p == sl.done && g_log[i + 3].stream == kStream);
+        }
+        g_log.clear();
+        size_t at_fill = 0; uint8_t *filled = nullptr;
+        const std::vector<uint8_t> fifth = pattern(72, 5);
+        CHECK(upload_filled(c, ring, "table staging", d.p, fifth.size(), [&](uint8_t *h) { at_fill = g_log.size(); filled = h; std::memcpy(h, fifth.data(), fifth.size()); }) == HG_OK);
+        CHECK(filled == ring.slot[0].h && ring.cur == 0 && at_fill == 1 && std::memcmp(d.p, fifth.data(), 72) == 0);
+        CHECK(g_log.size() == 3 && g_log[0].op == EV_SYNC && g_log[0].p == ring.slot[0].done && g_log[1].op == UPLOAD && g_log[1].bytes == 72 && g_log[2].op == EV_RECORD && g_log[2].p == ring.slot[0].done);
+        // larger than the slot: wait, free the old host block, allocate bytes + bytes / 4, upload, record
+        g_log.clear();
+        uint8_t *const old = ring.slot[1].h;
+        const std::vector<uint8_t> big = pattern(200, 6);
+        CHECK(upload_copied(c, ring, "table staging", d.p, big.data(), big.size()) == HG_OK && ring.cur == 1 && ring.slot[1].cap == 250);
+        CHECK(g_log.size() == 5 && g_log[0].op == EV_SYNC && g_log[0].p == ring.slot[1].done && g_log[1].op == HOST_FREE && g_log[1].p == old);
+        CHECK(g_log.size() == 5 && g_log[2].op == HOST_MALLOC && g_log[2].bytes == 250 && g_log[3].op == UPLOAD && g_log[3].bytes == 200 && g_log[4].op == EV_RECORD);
+        CHECK(std::memcmp(d.p, big.data(), 200) == 0);
+        // a failed host allocation: its message, nothing filled, uploaded or recorded, the cursor where it was; the next call takes the same slot
+        g_log.clear(); g_fail_next = true; c->err.clear();
+        bool called = false;
+        CHECK(upload_filled(c, ring, "table staging", d.p, 1000, [&](uint8_t *) { called = true; }) == HG_ERR_NOMEM);
+        CHECK(c->err.rfind("hipHostMalloc (table staging): ", 0) == 0 && !called && ring.cur == 1 && ring.next() == 2);
+        CHECK(count(UPLOAD) == 0 && count(MEMCPY) == 0 && count(EV_RECORD) == 0);
+        CHECK(std::memcmp(d.p, big.data(), 200) == 0);           // (the device block is as the last upload left it)
+        g_log.clear();
+        const std::vector<uint8_t> again = pattern(1000, 7);
+        CHECK(upload_filled(c, ring, "table staging", d.p, 1000, [&](uint8_t *h) { filled = h; std::memcpy(h, again.data(), 1000); }) == HG_OK);
+        CHECK(filled == ring.slot[2].h && ring.cur == 2 && ring.slot[2].cap == 1250 && std::memcmp(d.p, again.data(), 1000) == 0);
+        CHECK(find(UPLOAD) < find(EV_RECORD) && count(UPLOAD) == 1 && count(EV_RECORD) == 1);
+        // a failed upload, by the kernel and by the copy engine: no commit -- nothing recorded, the cursor where it was, the same slot next
+        for (size_t bytes : {(size_t)64, (size_t)12}) {             // (12 bytes: no multiple of 8, so the copy engine takes it)
+            g_log.clear(); g_fail_upload = true; c->err.clear();
+            const std::vector<uint8_t> src = pattern(bytes, 8);
+            CHECK(upload_copied(c, ring, "table staging", d.p, src.data(), bytes) == HG_ERR_HIP && !c->err.empty());
+            CHECK(count(EV_RECORD) == 0 && ring.cur == 2 && ring.next() == 3);
+            CHECK(count(bytes == 64 ? UPLOAD : MEMCPY) == 1);
+        }
+        // the bytes that arrive: one block and two blocks back to back, by the kernel and by the copy engine; the record is behind the upload
+        struct { size_t a, b; Op how; } const shapes[] = { {64, 0, UPLOAD}, {24, 40, UPLOAD}, {8, 8, UPLOAD}, {12, 0, MEMCPY}, {6, 6, MEMCPY}, {24, 4, MEMCPY} };
+        unsigned seed = 20;
+        for (const auto &sh : shapes) {
+            const std::vector<uint8_t> a = pattern(sh.a, seed++), b = pattern(sh.b, seed++);
+            std::memset(d.p, 0, 128);
+            g_log.clear();
+            const int before = ring.cur;
+            CHECK(upload_copied(c, ring, "table staging", d.p, a.data(), sh.a, sh.b ? b.data() : nullptr, sh.b) == HG_OK && ring.cur == (before + 1) % 4);
+            CHECK(std::memcmp(d.p, a.data(), sh.a) == 0 && (sh.b == 0 || std::memcmp(d.p + sh.a, b.data(), sh.b) == 0) && d.p[sh.a + sh.b] == 0);
+            CHECK(std::memcmp(ring.slot[ring.cur].h, d.p, sh.a + sh.b) == 0);
+            const size_t up = find(sh.how), rec = find(EV_RECORD);
+            CHECK(count(UPLOAD) + count(MEMCPY) == 1 && count(EV_RECORD) == 1 && up < rec && rec == g_log.size() - 1);
+            CHECK(up < g_log.size() && g_log[up].p == d.p && g_log[up].bytes == sh.a + sh.b && g_log[up].stream == kStream);
+        }
+        // option "upload_kernel" 0: the copy engine for every size
+        c->opt_upload_kernel = 0;
+        g_log.clear();
+        const std::vector<uint8_t> src = pattern(64, 40);
+        CHECK(upload_copied(c, ring, "table staging", d.p, src.data(), 64) == HG_OK && count(UPLOAD) == 0 && count(MEMCPY) == 1 && find(MEMCPY) < find(EV_RECORD));
+        c->opt_upload_kernel = -1;
+    }
+    CHECK(g_host.empty() && g_events.empty() && g_dev.empty());
 }
 
 // ------------------------------------------------------------------------------------------------ PwSolve
@@ -221,6 +329,7 @@ int main()
         check_ensure<Seg>(&ctx);
         check_ring<4>(&ctx);
         check_ring<64>(&ctx);
+        check_staged_upload(&ctx);
         check_solve(&ctx);
     }
     check_lifetime();
